@@ -14,11 +14,16 @@ N = 1 is BASELINE.json's headline shape (10M x 50k x 32, k = 5).  N > 1 defaults
 scaling -- the same 10M-row job split over the ranks (`--scaling weak`: 10M rows per rank) --
 because BASELINE.json's configurations shard a fixed job over the GPUs of a node.
 
-Rank 0 prints ONE JSON line: BASELINE.json's metric (Mqueries/s, whole job) with
+Rank 0 prints ONE JSON line: BASELINE.json's metric (Mqueries/s, whole job) with ``ms_per_step`` and
   ``roofline``      dominant kernel = the MFMA pre-filter, HIP events on its launch stream inside
-                    the library, summed over the timed region;
+                    the library, summed over the timed region (HBM traffic quoted from the committed
+                    counter passes of the same build).
+A plain run does only that: set up, warm up, time ``--steps`` steps, write ``--dump-outputs DIR`` if given,
+print the line.  ``--full`` adds everything else, with runs of its own:
+  ``roofline.traffic`` counted in this run (``--traffic auto``: two rocprofv3 --pmc child passes, N = 1);
   ``cpu_baseline``  the reference's CPU arithmetic (sklearn ArgKmin + restated reorder) on this host
-                    on a bounded sample (N = 1 only);
+                    on a bounded sample, with its parity check (N = 1 only);
+  ``gather_check``  N > 1: a block of the gathered result recomputed on rank 0;
 and, at N = 1 unless ``--no-extras``, ``configs`` (BASELINE.json configs 2-5 at one GPU, each with an
 oracle-checked slice), ``host_to_host_Mq_s`` / ``stream_Mq_s`` / ``estimator_Mq_s`` (the same
 workload entered from numpy arrays: PCIe-inclusive, never ``value``), ``cpu_baseline_c5`` (kd_tree
@@ -57,8 +62,14 @@ def parse_args(argv=None):
     ap.add_argument("--k", type=int, default=5)
     ap.add_argument("--targets", type=int, default=40)
     ap.add_argument("--cpu-sample", type=int, default=2_000_000, help="rows of the CPU baseline sample (about 12 s on the GPU box's host)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (skip configs 2-5, host paths, laws)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: in-run HBM traffic, CPU baseline and parity, "
+                         "configs 2-5, host paths, laws, the N > 1 gather check (off: set up, warm up, time, print)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the (dist, idx) the last step returned as DIR/dist.npy and DIR/idx.npy "
+                         "(float64; a fixed, seeded sample of rows when both would exceed 48 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip configs 2-5, host paths, laws")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the all-gather of (dist, idx)")
     ap.add_argument("--gather-chunks", type=int, default=2, choices=[1, 2, 3, 4], help="N>1: calls a rank's share is split into (all but the last gather overlap compute)")
     ap.add_argument("--force-dist", action="store_true",
@@ -66,7 +77,7 @@ def parse_args(argv=None):
     ap.add_argument("--traffic", choices=["auto", "measure", "committed", "off"], default="auto",
                     help="HBM bytes of the dominant kernel and of the step: 'measure' runs this bench twice more as a CHILD under "
                          "`rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (counters only, no trace domains) before this process "
-                         "touches the GPU; 'auto' does so at N = 1 when rocprofv3 is on PATH, else quotes the committed passes")
+                         "touches the GPU; 'auto' does so with --full at N = 1 when rocprofv3 is on PATH, else quotes the committed passes")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="N > 1: 'nccl' = RCCL over xGMI, one rank per GPU (the measured configuration); 'gloo' rehearses the "
@@ -74,7 +85,10 @@ def parse_args(argv=None):
     ap.add_argument("--dry-launch", action="store_true",
                     help="--gpus N > 1 outside a launcher: print the command that would start the N ranks and exit")
     ap.add_argument("--master-port", type=int, default=0, help="self-launch: rendezvous port (default: a free one)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_command(argv, n_gpus, port):
@@ -287,10 +301,11 @@ def measure_traffic(args, argv):
         if skip_next:
             skip_next = False
             continue
-        if a in ("--steps", "--warmup", "--traffic", "--gpus"):
+        if a in ("--steps", "--warmup", "--traffic", "--gpus", "--dump-outputs"):
             skip_next = True
             continue
-        if a.startswith(("--steps=", "--warmup=", "--traffic=", "--gpus=")) or a in ("--no-extras", "--no-cpu-baseline"):
+        if (a.startswith(("--steps=", "--warmup=", "--traffic=", "--gpus=", "--dump-outputs="))
+                or a in ("--no-extras", "--no-cpu-baseline", "--full")):
             continue
         keep.append(a)
     child = [sys.executable, os.path.abspath(__file__), *keep, "--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-baseline",
@@ -359,6 +374,25 @@ def committed_traffic(n_ref, d_t, k):
     return pmc["hbm_bytes_per_query_row"], pmc.get("step_hbm_bytes_per_query_row"), (
         "profiles/r04_coarse_pmc.json (rocprofv3 --pmc, separate passes; FETCH_SIZE x2 only for the kernels whose reads are "
         "wide coalesced: the pre-filter's LDS-DMA stages; WRITE_SIZE as read), same library build, scaled to this step's rows")
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: (dist, idx) together at most this many bytes
+
+
+def dump_outputs(out_dir, dist, idx, max_bytes=DUMP_BYTES):
+    """--dump-outputs: the (dist, idx) tensors a step returned, as DIR/dist.npy and DIR/idx.npy in float64 (the indices
+    are exact in it).  When the whole would exceed `max_bytes`, the rows written are a fixed, seeded sample (sorted), the
+    same in every run of the same shape, so that two builds can be compared row for row.  Returns the rows written."""
+    n, k = dist.shape
+    m = min(n, max(1, max_bytes // (16 * k)))
+    if m < n:
+        rows = np.sort(np.random.default_rng(1234).choice(n, size=m, replace=False))
+        sel = dist.new_tensor(rows, dtype=idx.dtype)
+        dist, idx = dist.index_select(0, sel), idx.index_select(0, sel)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "dist.npy"), dist.cpu().numpy().astype(np.float64, copy=False))
+    np.save(os.path.join(out_dir, "idx.npy"), idx.cpu().numpy().astype(np.float64))
+    return m
 
 
 def mfma_frac(nq, n_ref, d_t, coarse_ms):
@@ -486,7 +520,9 @@ def main():
     # HBM traffic counted in-run (profiler children first: this process has not touched the GPU yet)
     measured, measured_note = None, None
     world_env = int(os.environ.get("WORLD_SIZE", 1))
-    if args.traffic in ("auto", "measure") and world_env == 1 and not args.force_dist and not args.traffic_child:
+    if args.traffic == "auto" and not args.full:
+        measured_note = "in-run counter passes only with --full"
+    elif args.traffic in ("auto", "measure") and world_env == 1 and not args.force_dist and not args.traffic_child:
         import shutil
 
         under_profiler = any(k.startswith(("ROCP_", "ROCPROF")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
@@ -619,6 +655,8 @@ def main():
     elapsed = float(t_max.item())
     ms_per_step = elapsed / args.steps * 1e3
     value = total_rows * args.steps / elapsed / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_out, i_out)
 
     if rank == 0:
         # this rank's rows through this rank's kernel: the rows of the launches that coarse_ms sums (when the thin last
@@ -677,7 +715,7 @@ def main():
         }
         if use_dist:
             result["gather_in_place"] = gather_in_place[0]
-        if use_dist and not args.no_gather:
+        if args.full and use_dist and not args.no_gather:
             # The gathered arrays hold what the OTHER ranks computed: rank 0 regenerates the last rank's rows (seeded) and
             # answers a prefix of its first gather chunk itself, at that block's global position -- equal bit for bit when
             # every block sits where the chunk-cyclic layout says and every rank ran the same index.
@@ -690,7 +728,7 @@ def main():
             result["gather_check"] = {"rank": r_chk, "rows": int(n_chk), "global_row": int(lo),
                                       "equal": bool(torch.equal(i_out[lo:lo + n_chk], i_exp) and torch.equal(d_out[lo:lo + n_chk], d_exp))}
             del q_r
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             n_s = min(args.cpu_sample, nq)
             q_host = q[:n_s].cpu().numpy()
             base, (cd, ci) = cpu_reference(x_ref_t, affine, q_host, k)
@@ -703,7 +741,7 @@ def main():
                 "max_rel_dist_err": float(rel.max()),
             }
             result["speedup_vs_cpu"] = value / base["value"]
-        if world == 1 and not args.no_extras and not use_dist:
+        if args.full and world == 1 and not args.no_extras and not use_dist:
             del d_out, i_out
             result.update(extras(args, eng, q, x_ref_t, affine, torch, device))
         emit(json.dumps(result))

@@ -115,7 +115,7 @@ def test_bench_force_dist_single_rank():
     kernel timings) with one rank -- runs on the 1-GPU box."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT=str(_free_port()))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "2", "--warmup", "1", "--rows", "3000000",
-           "--cpu-sample", "20000", "--no-extras", "--gather-chunks", "3"]
+           "--full", "--cpu-sample", "20000", "--no-extras", "--gather-chunks", "3"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -211,7 +211,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo():
     hardware; only the transport differs from the measured configuration."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1",
-           "--rows", "2000000", "--gather-chunks", "3"]
+           "--rows", "2000000", "--gather-chunks", "3", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

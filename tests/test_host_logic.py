@@ -236,6 +236,40 @@ def test_bench_starts_its_own_ranks():
     assert "os.exec" not in src
 
 
+def test_bench_options_and_output_dump(tmp_path):
+    """bench.py: a plain run leaves everything beside the headline to --full; --steps below 1 is refused; --dump-outputs
+    writes (dist, idx) as float64, whole when they fit the byte budget, else the same seeded sample of rows every time."""
+    import importlib.util
+
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_module_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 2, False, None)
+    assert bench.parse_args(["--full", "--dump-outputs", "x"]).full
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+    rng = np.random.default_rng(0)
+    dist = torch.as_tensor(rng.random((1000, 5)))
+    idx = torch.as_tensor(rng.integers(0, 50_000, (1000, 5)))
+    assert bench.dump_outputs(str(tmp_path / "whole"), dist, idx) == 1000
+    d, i = np.load(tmp_path / "whole" / "dist.npy"), np.load(tmp_path / "whole" / "idx.npy")
+    assert d.dtype == np.float64 and i.dtype == np.float64
+    np.testing.assert_array_equal(d, dist.numpy())
+    np.testing.assert_array_equal(i, idx.numpy())
+    budget = 200 * 16 * 5
+    for name in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / name), dist, idx, max_bytes=budget) == 200
+    sa, sb = np.load(tmp_path / "a" / "idx.npy"), np.load(tmp_path / "b" / "idx.npy")
+    assert sa.shape == (200, 5) and np.array_equal(sa, sb)
+    rows = [int(np.nonzero((idx.numpy() == r).all(axis=1))[0][0]) for r in sa]
+    assert rows == sorted(rows) and len(set(rows)) == 200
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "dist.npy"), dist.numpy()[rows])
+
+
 @pytest.mark.parametrize("deterministic", [True, False])
 @pytest.mark.parametrize("self_query", [False, True])
 def test_numpy_tie_replay_equals_scikit_learns_brute_hamming_search(deterministic, self_query):
@@ -305,7 +339,7 @@ def test_bench_counts_hbm_traffic_from_counter_passes(tmp_path, monkeypatch):
     spec = importlib.util.spec_from_file_location("bench_module_traffic", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
-    argv = ["--rows", "123456", "--steps", "30", "--traffic", "measure", "--no-extras"]
+    argv = ["--rows", "123456", "--steps", "30", "--traffic", "measure", "--no-extras", "--full", "--dump-outputs", "dump_dir"]
     got, note = bench.measure_traffic(bench.parse_args(argv), argv)
     assert got["steps_counted"] == 4
     assert got["dominant_bytes_per_launch"] == (2 * 1000 + 100) * 1024          # FETCH x2 + WRITE, KiB -> bytes
@@ -318,3 +352,4 @@ def test_bench_counts_hbm_traffic_from_counter_passes(tmp_path, monkeypatch):
     assert child[0] == sys.executable and child[1].endswith("bench.py")
     assert "--traffic off" in calls[0] and "--traffic-child" in calls[0] and "--rows 123456" in calls[0]
     assert "--steps 3" in calls[0] and "--steps 30" not in calls[0]
+    assert "--full" not in child and "--dump-outputs" not in child and "dump_dir" not in child
