@@ -89,6 +89,13 @@ def replay_reference_selection(full, kk, call_rows, self_query, deterministic, d
     neigh = np.argpartition(full, kk - 1, axis=1)[:, :kk]
     neigh = neigh[sample_range, np.argsort(full[sample_range, neigh])]
     nd = full[sample_range, neigh]
+    return _finish_selection(nd, neigh, kk, call_rows, self_query, deterministic, decimals)
+
+
+def _finish_selection(nd, neigh, kk, call_rows, self_query, deterministic, decimals):
+    """The X=None self removal (SKL/neighbors/_base.py:936-963) and sknnr's deterministic reorder
+    (REF src/sknnr/_base.py:166-175) on the ``kk`` selected rows of each query."""
+    n = neigh.shape[0]
     call_rows = np.asarray(call_rows, dtype=np.int64)
     if self_query:
         sample_mask = neigh != call_rows[:, None]
@@ -104,6 +111,32 @@ def replay_reference_selection(full, kk, call_rows, self_query, deterministic, d
         nd = np.take_along_axis(nd, order, axis=1)
         neigh = np.take_along_axis(neigh, order, axis=1)
     return nd, neigh
+
+
+def build_reference_tree(fit_X, algorithm, leaf_size):
+    """The tree the reference's ``fit`` builds for ``algorithm`` (SKL/neighbors/_base.py:678-703; the Euclidean metric
+    after the minkowski / p=2 mapping, SKL/neighbors/_base.py:544-559)."""
+    from sklearn.neighbors import BallTree, KDTree
+
+    cls = {"kd_tree": KDTree, "ball_tree": BallTree}[algorithm]
+    return cls(np.ascontiguousarray(fit_X, dtype=np.float64), leaf_size, metric="euclidean")
+
+
+def replay_tree_selection(fit_X, rows_X, kk, algorithm, leaf_size, call_rows, self_query, deterministic, decimals,
+                          tree=None):
+    """The reference's tree search for the rows ``rows_X`` (n, d), with its choice among exactly tied rows.
+
+    ``fit_X``: the fitted (transformed) rows; ``rows_X``: the query rows in the same space (for X=None the fitted rows of
+    the queries themselves).  ``kk``: neighbours searched (k, + 1 for the X=None path).  ``call_rows`` (n): each row's
+    position in the whole call (for X=None also its own reference index).  Steps: ``KDTree`` / ``BallTree.query``
+    (SKL/neighbors/_base.py:919-926), the X=None self removal and sknnr's reorder.  ``tree``: a tree from
+    :func:`build_reference_tree` on the same ``fit_X`` (built here when None).  Returns ``(dist, idx)`` with k columns.
+    """
+    if tree is None:
+        tree = build_reference_tree(fit_X, algorithm, leaf_size)
+    rows_X = np.ascontiguousarray(rows_X, dtype=np.float64)
+    nd, neigh = tree.query(rows_X, k=kk)
+    return _finish_selection(nd, neigh.astype(np.int64, copy=False), kk, call_rows, self_query, deterministic, decimals)
 
 
 def _reraise(err, estimator):
@@ -136,9 +169,10 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
     neighbour ordering -- computed on the GPU.
 
     Same parameters as ``sklearn.neighbors.KNeighborsRegressor`` (REF _base.py:53-73);
-    ``leaf_size`` and ``n_jobs`` are accepted and ignored (there is no tree and no thread
-    pool), ``algorithm`` only selects which of the reference's two float64 distance
-    expressions is reproduced.
+    ``n_jobs`` is accepted and ignored (there is no thread pool), ``algorithm`` selects which of
+    the reference's two float64 distance expressions is reproduced, and ``leaf_size`` shapes the
+    host-side tree that ``tree_tie_policy("tree")`` queries for rows with exact ties (with the
+    default policy there is no tree and ``leaf_size`` has no effect).
     """
 
     DISTANCE_PRECISION_DECIMALS = 10
@@ -192,6 +226,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 raise ValueError(f"the Hamming weights have {w.size} entries for {X.shape[1]} columns")
             self._hamming_w = w
         self._affine = affine
+        self._ref_tree = None  # tree_tie_policy("tree"): built on first use
         self._device = default_device() if device is None else device
         self._build_engine()
         self._set_independent_prediction_attributes(y)
@@ -217,12 +252,14 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
     def __getstate__(self):
         state = dict(super().__getstate__())
         state["_engine"] = None  # device handles do not pickle; see engine_
+        state["_ref_tree"] = None  # a cache, rebuilt on first use
         return state
 
     def _formula(self) -> str:
         if getattr(self, "effective_metric_", "euclidean") == "hamming":
             return "hamming"
-        return "direct" if self._fit_method == "kd_tree" else "expanded"
+        # both trees evaluate rdist = sum((x - y)^2) (SKL/metrics/_dist_metrics.pxd.tp); only brute expands the square
+        return "expanded" if self._fit_method == "brute" else "direct"
 
     def _set_independent_prediction_attributes(self, y) -> None:
         """REF _base.py:37-40: predict and score with X=None."""
@@ -301,11 +338,92 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             return torch.as_tensor(dist, device=X.device), torch.as_tensor(idx, device=X.device)
         return dist, idx
 
+    def _tree_ties(self) -> bool:
+        """Euclidean kd_tree / ball_tree under ``tree_tie_policy("tree")``: exactly tied rows as the reference's tree keeps them."""
+        return (getattr(self, "effective_metric_", "euclidean") != "hamming"
+                and self._fit_method in ("kd_tree", "ball_tree")
+                and _config.get_tree_tie_policy() == "tree")
+
+    def _reference_ties(self) -> bool:
+        """Is one of the reference tie policies in force for this estimator (the choice among tied rows made on the host)?"""
+        return self._numpy_ties() or self._tree_ties()
+
+    def _check_reference_ties_supported(self, what):
+        """Paths that cannot replay the reference's choice among tied rows refuse to run under a reference tie policy
+        rather than answer with the device's lowest-index rule."""
+        if self._numpy_ties():
+            raise NotImplementedError(f"{what} does not support hamming_tie_policy('numpy'); use the default policy "
+                                      "'lowest_index' or the estimator's own kneighbors / predict")
+        if self._tree_ties():
+            raise NotImplementedError(f"{what} does not support tree_tie_policy('tree'); use the default policy "
+                                      "'lowest_index' or the estimator's own kneighbors / predict")
+
+    def _reference_tree(self):
+        """scikit-learn's tree over the fitted rows, as the reference's ``fit`` builds it (lazily, once per fit)."""
+        if getattr(self, "_ref_tree", None) is None:
+            self._ref_tree = build_reference_tree(self._fit_X, self._fit_method, self.leaf_size)
+        return self._ref_tree
+
+    def _kneighbors_tree_ties(self, X, k, use_deterministic_ordering, row_offset, n_self_rows, apply_affine):
+        """Euclidean kd_tree / ball_tree neighbours with the REFERENCE's choice among exactly tied rows.
+
+        The device answers every row (direct formula, the tree's arithmetic; tied rows lowest index first).  A second
+        device search for one neighbour more shows which queries have an exact tie that the choice depends on (across
+        the last slot; without the deterministic reorder, anywhere among the kept rows).  Those rows are queried in
+        scikit-learn's tree over the fitted rows (:func:`replay_tree_selection`), in the space the device searched: the
+        fitted rows, and for affine estimators the query rows mapped by the same device kernel as at fit time.
+        """
+        eng = self.engine_
+        cuda_in = is_torch_cuda_tensor(X)
+        X_host = X.cpu().numpy() if cuda_in else X
+        self_query = X is None
+        kk = k + (1 if self_query else 0)
+        n_fit = self.n_samples_fit_
+        formula = self._formula()
+        dist, idx = eng.kneighbors(X_host, k, exclude_self=self_query, deterministic=use_deterministic_ordering,
+                                   decimals=self.DISTANCE_PRECISION_DECIMALS, formula=formula,
+                                   apply_affine=apply_affine and not self_query, row_offset=row_offset,
+                                   n_self_rows=n_self_rows, check_finite=not self_query)
+        nq = idx.shape[0]
+        if nq:
+            rows_q = self._fit_X[row_offset:row_offset + nq] if self_query else X_host
+            probe = min(kk + 1, n_fit)
+            pd, _ = eng.kneighbors(rows_q, probe, exclude_self=False, deterministic=False, formula=formula,
+                                   apply_affine=apply_affine and not self_query)
+            if use_deterministic_ordering:  # only the SET of kept rows can differ: a tie across the last slot
+                flagged = pd[:, kk - 1] == pd[:, kk] if probe > kk else np.zeros(nq, dtype=bool)
+            else:  # the order among equal distances is the tree's too
+                flagged = (pd[:, :-1] == pd[:, 1:]).any(axis=1) if probe > 1 else np.zeros(nq, dtype=bool)
+            rows = np.flatnonzero(flagged)
+            if rows.size:
+                rows_X = rows_q[rows]
+                if apply_affine and not self_query:
+                    d_in, center, scale, proj = self._affine
+                    rows_X = _native.affine_transform_host(np.ascontiguousarray(rows_X, dtype=np.float64), center,
+                                                           scale, proj, device=self._device)
+                dist[rows], idx[rows] = replay_tree_selection(
+                    self._fit_X, rows_X, kk, self._fit_method, self.leaf_size, rows + row_offset, self_query,
+                    use_deterministic_ordering, self.DISTANCE_PRECISION_DECIMALS, tree=self._reference_tree())
+            self._last_tree_tie_rows = int(rows.size)
+        if cuda_in:
+            import torch
+
+            return torch.as_tensor(dist, device=X.device), torch.as_tensor(idx, device=X.device)
+        return dist, idx
+
+    def _kneighbors_reference_ties(self, X, k, use_deterministic_ordering, row_offset, n_self_rows, apply_affine):
+        if self._numpy_ties():
+            return self._kneighbors_hamming_numpy_ties(X, k, use_deterministic_ordering, row_offset, n_self_rows)
+        return self._kneighbors_tree_ties(X, k, use_deterministic_ordering, row_offset, n_self_rows, apply_affine)
+
     def _kneighbors_engine(self, X, k, *, apply_affine, use_deterministic_ordering, row_offset=0,
                            n_self_rows=None, return_distance=True, out=None, owner=None):
+        if out is not None and self._reference_ties():
+            self._check_reference_ties_supported("kneighbors into caller tensors (out=, ShardedKNN)")
         try:
-            if self._numpy_ties() and out is None:
-                return self._kneighbors_hamming_numpy_ties(X, k, use_deterministic_ordering, row_offset, n_self_rows)
+            if self._reference_ties():
+                return self._kneighbors_reference_ties(X, k, use_deterministic_ordering, row_offset, n_self_rows,
+                                                       apply_affine)
             return self.engine_.kneighbors(
                 X, k, exclude_self=X is None, deterministic=use_deterministic_ordering,
                 decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula(),
@@ -367,10 +485,11 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
     def _predict_engine(self, X, *, apply_affine, row_offset=0, n_self_rows=None, owner=None):
         weights = None if self.weights is None else self.weights
         try:
-            if self._numpy_ties():
+            if self._reference_ties():
                 # the reference's predict() calls ITS kneighbors (deterministic ordering on): the same neighbours here,
                 # then the reduction on the device (SKL/neighbors/_regression.py:224-268)
-                dist, idx = self._kneighbors_hamming_numpy_ties(X, self.n_neighbors, True, row_offset, n_self_rows)
+                dist, idx = self._kneighbors_reference_ties(X, self.n_neighbors, True, row_offset, n_self_rows,
+                                                            apply_affine)
                 cuda = is_torch_cuda_tensor(dist)
                 if cuda:
                     dev = dist.device
@@ -413,7 +532,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         eng = self.engine_
         want_pred = weights is not None
         t_cols = eng.t
-        if self._numpy_ties():
+        if self._reference_ties():
             # the reference's choice among tied rows is made on the host, per call: tile by tile, positions carried
             parts, row = [], 0
             for tile in tiles:

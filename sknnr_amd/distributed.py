@@ -395,6 +395,9 @@ class RefShardedKNN:
 
         if self.estimator is not None:
             reg, transformed = self._reg()
+            # the merge keeps the lowest index among tied rows: it cannot replay the reference's choice (same test on
+            # every rank, before any collective)
+            reg._check_reference_ties_supported("RefShardedKNN")
             k = reg._resolve_k(n_neighbors)
             if X is not None:
                 X = (self.estimator._validate_raw_query(X) if transformed else reg._validate_query(X))

@@ -11,6 +11,10 @@ synthetic problems of ``sknnr_amd.synth``, and stores inputs/expected outputs as
 small ``.npz`` files.  Only arrays are written (data, fitted matrices, neighbour
 indices, distances, predictions, scores); no reference source travels.
 
+``tree_ties_*.npz`` / ``tree_ball_continuous_*.npz`` (``make_tree_ties``; ``--tree-ties`` writes only those) hold the
+reference's kd_tree / ball_tree answers on integer lattices -- exact ties at the k-th distance on most rows -- and its
+explicit ball_tree on continuous data.
+
 ``tests/golden/ref_regressions/*.npz`` are the reference's own regression data
 files (raw, euclidean, mahalanobis, gnn, msn, and -- since round 2 -- randomForest and gbnn),
 copied verbatim from /root/reference/tests/test_regressions/.
@@ -285,7 +289,113 @@ def tree_cases():
     print("synth_gbnn", est.transformer_.transform(x_ref).shape)
 
 
+def _lattice_sets():
+    """The two integer-lattice fit sets of the tree-tie fixtures (uint8, as an integer raster arrives): 1,500 distinct
+    6-D rows with values 0..5, and 1,500 8-D rows with values 0..3 of which 300 repeat earlier rows; 20,000 lattice
+    queries each, and two float targets per fit row."""
+    rng = np.random.default_rng(20261016)
+    codes = rng.choice(6 ** 6, size=1500, replace=False)
+    fit6 = np.stack([(codes // 6 ** c) % 6 for c in range(6)], axis=1).astype(np.uint8)
+    q6 = rng.integers(0, 6, (20000, 6)).astype(np.uint8)
+    fit8 = rng.integers(0, 4, (1500, 8)).astype(np.uint8)
+    fit8[1200:] = fit8[rng.integers(0, 1200, 300)]
+    q8 = rng.integers(0, 4, (20000, 8)).astype(np.uint8)
+    y6 = np.round(rng.standard_normal((1500, 2)), 3)
+    y8 = np.round(rng.standard_normal((1500, 2)), 3)
+    return {"d6": (fit6, y6, q6), "d8_dup": (fit8, y8, q8)}
+
+
+def _put_neighbors(out, key, dist, nn, squared_ints):
+    """Neighbour indices as int16 (n_fit < 32768); lattice distances as the integer d2 they are the square root of
+    (checked bit for bit), continuous ones as float64."""
+    out[key + "_nn"] = np.asarray(nn).astype(np.int16)
+    assert np.array_equal(out[key + "_nn"], nn)
+    if squared_ints:
+        d2 = np.rint(np.asarray(dist) ** 2).astype(np.uint8)
+        assert np.array_equal(np.sqrt(d2.astype(np.float64)), dist), key
+        out[key + "_d2"] = d2
+    else:
+        out[key + "_dist"] = np.asarray(dist)
+
+
+def _tree_kneighbors(out, est, X, ks, squared_ints):
+    """kneighbors of X (``tgt``) and of X=None (``ref``), deterministic ordering on (``det``) and off (``nd``); k = 1 is
+    stored once (one column has one order)."""
+    for k in ks:
+        for q, XX in (("tgt", X), ("ref", None)):
+            dd, di = est.kneighbors(XX, n_neighbors=k)
+            nd, ni = est.kneighbors(XX, n_neighbors=k, use_deterministic_ordering=False)
+            if k == 1:
+                assert np.array_equal(di, ni) and np.array_equal(dd, nd)
+                _put_neighbors(out, f"{q}_k1", dd, di, squared_ints)
+            else:
+                _put_neighbors(out, f"{q}_k{k}_det", dd, di, squared_ints)
+                # the same rows in the tree's own order: stored as the permutation of the deterministic columns
+                perm = np.argmax(di[:, None, :] == ni[:, :, None], axis=2)  # ni[r, j] == di[r, perm[r, j]]
+                assert np.array_equal(np.take_along_axis(di, perm, 1), ni)
+                assert np.array_equal(np.take_along_axis(dd, perm, 1), nd)
+                out[f"{q}_k{k}_nd_perm"] = perm.astype(np.uint8)
+
+
+def make_tree_ties():
+    """The reference's kd_tree / ball_tree searches where their choice among EXACTLY tied rows decides the answer
+    (integer lattices: most queries have several rows at the k-th distance), and explicit ball_tree on continuous data
+    (the direct distance expression above 15 features).  Read by tests/test_tree_ties_oracle.py and
+    tests/test_tree_ties_gpu.py."""
+    sets = _lattice_sets()
+    n_pred = 2000  # predictions are stored for the first rows of the call only (size)
+    for name, (fit, y, q) in sets.items():
+        out = {"fit_X": fit, "X": q, "y": y}
+        est = RawKNNRegressor(n_neighbors=5).fit(fit, y)
+        assert est._fit_method == "kd_tree", est._fit_method
+        out["fit_method"] = np.asarray(est._fit_method)
+        out["leaf_size"] = np.asarray(est.leaf_size)
+        _tree_kneighbors(out, est, q, (1, 5), True)
+        for w in ("uniform", "distance"):
+            e = RawKNNRegressor(n_neighbors=5, weights=w).fit(fit, y)
+            out[f"pred_{w}"] = e.predict(q[:n_pred])
+            out[f"indep_pred_{w}"] = e.independent_prediction_
+            out[f"indep_score_{w}"] = np.asarray(e.independent_score_)
+        np.savez_compressed(os.path.join(HERE, f"tree_ties_{name}.npz"), **out)
+        print("tree_ties", name, str(out["fit_method"]))
+    # the tree's shape decides the choice: kd_tree with small leaves, and the ball tree, on the first 5,000 queries
+    for tag, src, kw in (("leaf5", "d6", dict(algorithm="kd_tree", leaf_size=5)),
+                         ("ball", "d8_dup", dict(algorithm="ball_tree"))):
+        fit, y, q = sets[src]
+        est = RawKNNRegressor(n_neighbors=5, **kw).fit(fit, y)
+        out = {"source": np.asarray(src), "n_queries": np.asarray(5000), "fit_method": np.asarray(est._fit_method),
+               "leaf_size": np.asarray(est.leaf_size)}
+        _tree_kneighbors(out, est, q[:5000], (5,), True)
+        np.savez_compressed(os.path.join(HERE, f"tree_ties_{tag}.npz"), **out)
+        print("tree_ties", tag, str(out["fit_method"]), int(out["leaf_size"]))
+    # explicit ball_tree on continuous features (sknnr_amd.synth data, regenerated by the tests): the direct expression
+    for d in (8, 32):
+        x_ref, y, x_q = synth.make_problem(1000, 500, d, t=3, n_dup_queries=20)
+        est = RawKNNRegressor(n_neighbors=5, algorithm="ball_tree").fit(x_ref, y)
+        assert est._fit_method == "ball_tree"
+        out = {"fit_method": np.asarray(est._fit_method)}
+        _tree_kneighbors(out, est, x_q, (5,), False)
+        out["pred_uniform"] = est.predict(x_q)
+        np.savez_compressed(os.path.join(HERE, f"tree_ball_continuous_d{d}.npz"), **out)
+        print("tree_ball_continuous", d)
+    # a transformed estimator on the duplicated lattice: the reference's transformed rows travel too
+    fit, y, q = sets["d8_dup"]
+    est = EuclideanKNNRegressor(n_neighbors=5).fit(fit, y)
+    assert est.regressor_._fit_method == "kd_tree"
+    out = {"fit_method": np.asarray(est.regressor_._fit_method), "n_queries": np.asarray(n_pred),
+           "Xt_train": est.transformer_.transform(fit), "Xt_test": est.transformer_.transform(q[:n_pred])}
+    _tree_kneighbors(out, est, q[:n_pred], (5,), False)
+    out["pred_uniform"] = est.predict(q[:n_pred])
+    out["indep_pred_uniform"] = est.independent_prediction_
+    out["indep_score_uniform"] = np.asarray(est.independent_score_)
+    np.savez_compressed(os.path.join(HERE, "tree_ties_euclidean.npz"), **out)
+    print("tree_ties euclidean")
+
+
 def main():
+    if "--tree-ties" in sys.argv:  # the tree-tie fixtures only (every other file stays byte for byte)
+        make_tree_ties()
+        return
     if "--only-new" in sys.argv:  # round 2 additions only (the earlier files stay byte for byte)
         synthetic_wide_estimator_cases()
         tree_cases()
@@ -298,6 +408,7 @@ def main():
     synthetic_estimator_cases()
     synthetic_wide_estimator_cases()
     tree_cases()
+    make_tree_ties()
 
 
 if __name__ == "__main__":
