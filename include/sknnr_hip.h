@@ -107,15 +107,18 @@ typedef struct sknnr_query_opts {
     int32_t deterministic; /* 1 = apply sknnr's tie-break reorder (REF _base.py:166-175) */
     int32_t decimals;      /* RawKNNRegressor.DISTANCE_PRECISION_DECIMALS (REF _base.py:102), default 10 */
     int32_t formula;       /* sknnr_formula */
-    int32_t apply_affine;  /* 1 = queries are untransformed (d_in columns) and the handle's affine map
-                              is applied first (REF _base.py:236-239); 0 = already transformed (d columns) */
+    int32_t apply_affine;  /* 1 = apply the handle's query-time map: queries are untransformed (d_in columns) and
+                              go through the affine map (REF _base.py:236-239) -- or, with formula = HAMMING on a
+                              handle with a forest (sknnr_index_set_forest), through the forests, which turn them
+                              into node ids; 0 = already transformed (d columns) */
     int32_t weight_mode;   /* predict only: sknnr_weight_mode */
     int32_t check_finite;  /* 1 = the kernels that read the query rows also test them for NaN / infinity
                               (what validate_data(ensure_all_finite=True) does on the host in the reference).
                               Host-memory calls then fail with SKNNR_ERR_NONFINITE; device-memory calls stay
                               asynchronous and the caller polls sknnr_check_finite() */
     int32_t query_dtype;   /* sknnr_dtype of the query rows `q` (0 = float64).  Other types need the MFMA envelope
-                              (d <= 128) and a Euclidean formula; they are widened by the kernel that reads them */
+                              (d <= 128) and a Euclidean formula, or the forest map (formula = HAMMING with
+                              apply_affine = 1); they are widened by the kernel that reads them */
     int32_t reserved_;     /* keep 0 */
     int64_t row_offset;    /* position of query row 0 inside the logical call: key 2 of the reorder is
                               |idx - row| with row counted over the whole call (REF _base.py:171), so a
@@ -185,6 +188,35 @@ int sknnr_index_set_affine(sknnr_index* index, int32_t d_in, const double* cente
  * transformers/_tree_node_transformer.py:177-201) and answers opts->formula = SKNNR_FORMULA_HAMMING.
  */
 int sknnr_index_set_hamming_weights(sknnr_index* index, const double* w, int32_t n);
+
+/*
+ * Install the query-time forest map of RFNN / GBNN: raw feature rows -> the node each tree sends them to.
+ * Replaces transformer_.transform(X) of the tree-node transformers (REF transformers/_tree_node_transformer.py:177-201:
+ * forest.apply per forest, SKL/tree/_tree.pyx:956-995 _apply_dense) for query rows: a row's features are converted
+ * to float32 (as apply does) and walked down every tree (x <= threshold: left child, else right).  Tree t yields
+ * column t of the node-id rows the weighted-Hamming search reads, so n_trees must equal the handle's d.
+ *   d_in        : features of a raw row
+ *   tree_offset : host, (n_trees + 1) int64: tree t owns nodes [tree_offset[t], tree_offset[t + 1]), at least one
+ *   threshold   : host, (tree_offset[n_trees]) float64, the trees' tree_.threshold one after another
+ *   feature, left, right : host, int32, the same length: tree_.feature, tree_.children_left / children_right
+ *                 (child ids local to the tree; -1 on both for a leaf)
+ * Checked on the host: every child id is greater than its parent's and below the tree's node count, every internal
+ * node's feature lies in [0, d_in) and its threshold is not NaN (else SKNNR_ERR_INVALID).  The map then applies with
+ * opts->formula = SKNNR_FORMULA_HAMMING and opts->apply_affine = 1, to float64 rows or any narrower query_dtype.
+ * Besides NaN and infinity, a finite value that overflows float32 is refused with SKNNR_ERR_NONFINITE and
+ * scikit-learn's message ("Input X contains infinity or a value too large for dtype('float32').").
+ */
+int sknnr_index_set_forest(sknnr_index* index, int32_t d_in, int32_t n_trees, const int64_t* tree_offset,
+                           const double* threshold, const int32_t* feature, const int32_t* left,
+                           const int32_t* right);
+
+/*
+ * The installed forest map alone: out_ids (nq, n_trees) float64 = the node ids of the rows q (nq, d_in) of
+ * query_dtype, in `mem` (device: launched on the default stream; the call returns when the ids are written).
+ * Fails with SKNNR_ERR_NONFINITE as the map does inside a search.  Replaces forest.apply for those rows.
+ */
+int sknnr_forest_apply(sknnr_index* index, const void* q, int64_t nq, int32_t query_dtype, int32_t mem,
+                       double* out_ids);
 
 /*
  * The same affine map as a stand-alone call (no handle): out = ((x - center) / scale) @ proj.

@@ -148,7 +148,9 @@ def _reraise(err, estimator):
         # (SKL/utils/validation.py _assert_all_finite)
         from sklearn.utils.validation import check_array
 
-        bad = np.array([[np.nan if "NaN" in err.message else np.inf]])
+        # (the forest map also reports values beyond the float32 range, as forest.apply's float32 validation does)
+        bad = np.array([[np.nan if "NaN" in err.message else np.inf]],
+                       dtype=np.float32 if "dtype('float32')" in err.message else np.float64)
         check_array(bad, estimator=estimator, input_name="X", ensure_min_features=1)
         raise ValueError(err.message) from None  # not reached
     raise err
@@ -210,7 +212,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         self._set_dataframe_index_in(X)
         return self._fit_arrays(X, y, affine=None)
 
-    def _fit_arrays(self, X, y, affine, device=None):
+    def _fit_arrays(self, X, y, affine, device=None, forest=None):
         self._check_params()
         X, y = validate_data(self, X, y, multi_output=True, order="C", dtype=np.float64,
                              ensure_all_finite=True, reset=True)
@@ -226,6 +228,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 raise ValueError(f"the Hamming weights have {w.size} entries for {X.shape[1]} columns")
             self._hamming_w = w
         self._affine = affine
+        self._forest = forest  # forest image of a tree-node space (TreeNodeTransformer.forest_image), or None
         self._ref_tree = None  # tree_tie_policy("tree"): built on first use
         self._device = default_device() if device is None else device
         self._build_engine()
@@ -240,6 +243,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         if self._affine is not None:
             d_in, center, scale, proj = self._affine
             self._engine.set_affine(d_in, center, scale, proj)
+        if getattr(self, "_forest", None) is not None:
+            self._engine.set_forest(self._forest)
 
     @property
     def engine_(self) -> KNNEngine:
@@ -293,7 +298,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         return (getattr(self, "effective_metric_", "euclidean") == "hamming"
                 and _config.get_hamming_tie_policy() == "numpy")
 
-    def _kneighbors_hamming_numpy_ties(self, X, k, use_deterministic_ordering, row_offset, n_self_rows):
+    def _kneighbors_hamming_numpy_ties(self, X, k, use_deterministic_ordering, row_offset, n_self_rows, apply_affine=False):
         """Weighted-Hamming neighbours with the REFERENCE's choice among exactly tied rows.
 
         The device answers every row (tied rows lowest index first).  A second device search for one neighbour more, on the
@@ -304,21 +309,25 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         (SKL/neighbors/_base.py:733-760: argpartition, argsort), the X=None self removal (SKL/neighbors/_base.py:936-963)
         and sknnr's reorder (REF src/sknnr/_base.py:166-175) -- reached in the reference from
         REF src/sknnr/_weighted_trees.py:53-59, :139-140 and pinned by REF tests/test_regressions.py:125-195.
+        ``apply_affine``: ``X`` holds raw rows that the engine's forest map turns into node ids (the flagged rows' ids
+        come from ``forest_apply``).
         """
         eng = self.engine_
         cuda_in = is_torch_cuda_tensor(X)
         X_host = X.cpu().numpy() if cuda_in else X
         self_query = X is None
+        forest = bool(apply_affine) and not self_query
         kk = k + (1 if self_query else 0)
         n_fit = self.n_samples_fit_
         dist, idx = eng.kneighbors(X_host, k, exclude_self=self_query, deterministic=use_deterministic_ordering,
-                                   decimals=self.DISTANCE_PRECISION_DECIMALS, formula="hamming", row_offset=row_offset,
-                                   n_self_rows=n_self_rows, check_finite=X is not None)
+                                   decimals=self.DISTANCE_PRECISION_DECIMALS, formula="hamming", apply_affine=forest,
+                                   row_offset=row_offset, n_self_rows=n_self_rows, check_finite=X is not None)
         nq = idx.shape[0]
         if nq:
             rows_q = self._fit_X[row_offset:row_offset + nq] if self_query else X_host
             probe = min(kk + 1, n_fit)
-            pd, _ = eng.kneighbors(rows_q, probe, exclude_self=False, deterministic=False, formula="hamming")
+            pd, _ = eng.kneighbors(rows_q, probe, exclude_self=False, deterministic=False, formula="hamming",
+                                   apply_affine=forest)
             if use_deterministic_ordering:  # only the SET of kept rows can differ: a tie across the last slot
                 flagged = pd[:, kk - 1] == pd[:, kk] if probe > kk else np.zeros(nq, dtype=bool)
             else:  # the order among equal distances is argpartition's too
@@ -327,7 +336,10 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             step = max(1, (256 << 20) // (8 * n_fit))  # distance rows of at most ~256 MB at a time
             for a in range(0, rows.size, step):
                 sel = rows[a:a + step]
-                full = eng.hamming_distances(None if self_query else X_host, sel + (row_offset if self_query else 0))
+                if forest:
+                    full = eng.hamming_distances(eng.forest_apply(X_host[sel]))
+                else:
+                    full = eng.hamming_distances(None if self_query else X_host, sel + (row_offset if self_query else 0))
                 dist[sel], idx[sel] = replay_reference_selection(full, kk, sel + row_offset, self_query,
                                                                   use_deterministic_ordering,
                                                                   self.DISTANCE_PRECISION_DECIMALS)
@@ -413,7 +425,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
     def _kneighbors_reference_ties(self, X, k, use_deterministic_ordering, row_offset, n_self_rows, apply_affine):
         if self._numpy_ties():
-            return self._kneighbors_hamming_numpy_ties(X, k, use_deterministic_ordering, row_offset, n_self_rows)
+            return self._kneighbors_hamming_numpy_ties(X, k, use_deterministic_ordering, row_offset, n_self_rows,
+                                                       apply_affine)
         return self._kneighbors_tree_ties(X, k, use_deterministic_ordering, row_offset, n_self_rows, apply_affine)
 
     def _kneighbors_engine(self, X, k, *, apply_affine, use_deterministic_ordering, row_offset=0,
@@ -573,7 +586,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                     continue
                 if stream is None:
                     # the element type of the first tile is the stream's (narrow rasters travel at their own width)
-                    code = eng.query_dtype_code(tile, self._formula())
+                    code = eng.query_dtype_code(tile, self._formula(), apply_affine)
                     stream_dtype = tile.dtype if code else np.dtype(np.float64)
                     stream = eng.open_stream(k, weights=weights, want_dist=return_distance,
                                              deterministic=use_deterministic_ordering,
@@ -693,7 +706,9 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
 
     ``fit`` learns the transformer on the host, maps the training rows through the GPU
     affine kernel, and installs the same map in the engine so that ``kneighbors`` /
-    ``predict`` take *untransformed* rows and transform them inside the launch.
+    ``predict`` take *untransformed* rows and transform them inside the launch.  Tree-node
+    spaces (RFNN / GBNN) install their forests instead: query rows are walked down every tree
+    on the device (``sknnr_index_set_forest``) and never visit scikit-learn's ``apply``.
     """
 
     def __init__(self, n_neighbors=5, *, weights="uniform", algorithm="auto", leaf_size=30, p=2,
@@ -728,9 +743,10 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         self._set_fitted_transformer(X, y)
 
         device = default_device()
-        # Affine feature spaces are applied on the device (fit rows here, query rows inside the launch);
-        # tree-node spaces (scikit-learn forests) are evaluated on the host and the device searches node ids.
+        # Affine feature spaces are applied on the device (fit rows here, query rows inside the launch); tree-node spaces
+        # (scikit-learn forests) map the fit rows on the host and install the forests for the query rows.
         self._device_affine = hasattr(self.transformer_, "affine_params")
+        self._device_forest = hasattr(self.transformer_, "forest_image")
         if self._device_affine:
             center, scale, proj = self.transformer_.affine_params()
             X_arr = np.ascontiguousarray(
@@ -748,7 +764,8 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         }
         kwargs.update(self._get_additional_regressor_init_kwargs())
         self.regressor_ = RawKNNRegressor(**kwargs)
-        self.regressor_._fit_arrays(X_transformed, y, affine=affine, device=device)
+        forest = self.transformer_.forest_image() if self._device_forest else None
+        self.regressor_._fit_arrays(X_transformed, y, affine=affine, device=device, forest=forest)
         self.regressor_._set_dataframe_index_in(X)
 
         self.n_features_in_ = self.regressor_.n_features_in_
@@ -758,10 +775,17 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
             self.dataframe_index_in_ = self.regressor_.dataframe_index_in_
         return self
 
-    def _validate_raw_query(self, X):
+    def _map_on_device(self) -> bool:
+        """Do query rows reach the engine raw, to be mapped there (affine map or forests)?"""
+        return self._device_affine or getattr(self, "_device_forest", False)
+
+    def _validate_raw_query(self, X, host_ids=False):
         """Same checks the transformer's ``transform`` applies (feature names/count, finiteness)
-        without transforming on the host -- or, for host-side feature spaces, the transform itself."""
+        without transforming on the host -- or, for host-side feature spaces, the transform itself.
+        ``host_ids``: tree-node spaces return scikit-learn's node ids (the reference-sharded search takes those)."""
         check_is_fitted(self, "transformer_")
+        if getattr(self, "_device_forest", False) and not host_ids:
+            return self._validate_forest_query(X)
         if not getattr(self, "_device_affine", True):
             if is_torch_cuda_tensor(X):
                 X = X.cpu().numpy()
@@ -776,6 +800,30 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         return validate_data(self.transformer_, X=X, reset=False, dtype=_QUERY_DTYPES, order="C",
                              ensure_all_finite=False)
 
+    def _validate_forest_query(self, X):
+        """Tree-node spaces: the checks of ``transform``'s ``validate_data`` (feature names / count; finiteness and the
+        float32 range on the device), the rows kept at their own width.  ``apply`` converts them to float32 in one
+        rounding; every kept type reaches float32 exactly that way through float64, 64-bit integers do not (two
+        roundings above 2^53), so those are converted to float32 here, as ``apply`` would."""
+        name = type(self.transformer_).__name__
+        if is_torch_cuda_tensor(X):
+            import torch
+
+            d_in = self.regressor_.engine_.d_in
+            if X.ndim != 2 or X.shape[1] != d_in:
+                raise ValueError(f"X has {X.shape[-1]} features, but {name} is expecting {d_in} features as input.")
+            return X.to(torch.float32) if X.dtype in (torch.int64, getattr(torch, "uint64", torch.int64)) else X
+        X = validate_data(self.transformer_, X=X, reset=False, dtype=_QUERY_DTYPES + [np.int64, np.uint64], order="C",
+                          ensure_all_finite=False)
+        return X.astype(np.float32) if X.dtype in (np.int64, np.uint64) else X
+
+    def _host_result(self, X, out):
+        """Tree-node spaces answered CUDA-tensor queries with host arrays before their map moved to the device: so they
+        still do."""
+        if getattr(self, "_device_forest", False) and is_torch_cuda_tensor(X):
+            return tuple(None if a is None else a.cpu().numpy() for a in out) if isinstance(out, tuple) else out.cpu().numpy()
+        return out
+
     def kneighbors(self, X=None, n_neighbors=None, return_distance=True, return_dataframe_index=False,
                    use_deterministic_ordering=True):
         """REF _base.py:285-344."""
@@ -784,9 +832,9 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         k = reg._resolve_k(n_neighbors)
         if X is not None:
             X = self._validate_raw_query(X)
-        dist, idx = reg._kneighbors_engine(X, k, apply_affine=X is not None and self._device_affine,
-                                           use_deterministic_ordering=use_deterministic_ordering,
-                                           owner=self.transformer_)
+        dist, idx = self._host_result(X, reg._kneighbors_engine(X, k, apply_affine=X is not None and self._map_on_device(),
+                                                                use_deterministic_ordering=use_deterministic_ordering,
+                                                                owner=self.transformer_))
         return reg._finish_kneighbors(dist, idx, return_distance, return_dataframe_index)
 
     def predict(self, X):
@@ -795,8 +843,8 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         check_is_fitted(self, "regressor_")
         if X is not None:
             X = self._validate_raw_query(X)
-        return self.regressor_._predict_engine(X, apply_affine=X is not None and self._device_affine,
-                                               owner=self.transformer_)
+        return self._host_result(X, self.regressor_._predict_engine(X, apply_affine=X is not None and self._map_on_device(),
+                                                                    owner=self.transformer_))
 
     def kneighbors_chunks(self, tiles, n_neighbors=None, return_distance=True, return_dataframe_index=False,
                           use_deterministic_ordering=True, out=None):
@@ -806,7 +854,7 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         reg = self.regressor_
         k = reg._resolve_k(n_neighbors)
         o = None if out is None else (out[0], out[1], None)
-        dist, idx, _ = reg._stream_tiles(tiles, self._validate_raw_query, k, apply_affine=self._device_affine, weights=None,
+        dist, idx, _ = reg._stream_tiles(tiles, self._validate_raw_query, k, apply_affine=self._map_on_device(), weights=None,
                                          return_distance=return_distance,
                                          use_deterministic_ordering=use_deterministic_ordering, out=o,
                                          owner=self.transformer_)
@@ -815,7 +863,7 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
     def predict_chunks(self, tiles, out=None):
         """``predict`` over an iterable of untransformed host tiles as one streamed call."""
         check_is_fitted(self, "regressor_")
-        return self.regressor_._predict_chunks(tiles, self._validate_raw_query, apply_affine=self._device_affine,
+        return self.regressor_._predict_chunks(tiles, self._validate_raw_query, apply_affine=self._map_on_device(),
                                                out=out, owner=self.transformer_)
 
     def score(self, X, y):

@@ -66,6 +66,7 @@ class KNNEngine:
         self.t = self._index.t
         self.d_in = self.d
         self.has_affine = False
+        self.has_forest = False
 
     def close(self):
         self._index.close()
@@ -78,6 +79,31 @@ class KNNEngine:
     def set_hamming_weights(self, w):
         """Per-column weights of the weighted-Hamming search over tree node ids (``formula="hamming"``)."""
         self._index.set_hamming_weights(w)
+
+    def set_forest(self, image):
+        """Install the query-time forest map: ``image`` as ``TreeNodeTransformer.forest_image()`` returns it.  Hamming
+        calls with ``apply_affine=True`` then take raw feature rows and map them through the forests on the device."""
+        self._index.set_forest(image["d_in"], image["tree_offset"], image["threshold"], image["feature"],
+                               image["left"], image["right"])
+        self.d_in = int(image["d_in"])
+        self.has_forest = True
+
+    def forest_apply(self, X):
+        """Node ids ``(nq, n_trees)`` float64 of the raw rows ``X`` (numpy -> numpy, torch.cuda -> torch.cuda)."""
+        if is_torch_cuda_tensor(X):
+            import torch
+
+            qdt = _native.dtype_code(X.dtype) or 0
+            X = self._as_device_rows(X, True, qdt)
+            out = torch.empty((X.shape[0], self.d), dtype=torch.float64, device=X.device)
+            if X.shape[0]:
+                torch.cuda.current_stream(X.device).synchronize()  # (the call runs on the default stream)
+                self._index.forest_apply_device(X.data_ptr(), X.shape[0], qdt, out.data_ptr())
+            return out
+        qdt = _native.dtype_code(X.dtype) or 0
+        X = np.ascontiguousarray(X) if qdt else np.ascontiguousarray(X, dtype=np.float64)
+        self._check_columns(X, True)
+        return self._index.forest_apply_host(X, qdt)
 
     def stats(self) -> dict:
         return self._index.stats()
@@ -95,11 +121,15 @@ class KNNEngine:
             apply_affine=apply_affine, weight_mode=weight_mode, row_offset=row_offset,
             check_finite=check_finite, query_dtype=query_dtype)
 
-    def query_dtype_code(self, X, formula="expanded") -> int:
+    def query_dtype_code(self, X, formula="expanded", apply_affine=False) -> int:
         """The sknnr_dtype under which the rows of ``X`` can be handed to the library as they are (float32, int16, uint16,
         uint8, int32: widened by the kernel that reads them, exactly), or 0 = float64 (convert first): narrow rows need
-        the MFMA envelope (d <= 128) and a Euclidean formula."""
-        if X is None or formula == "hamming" or self.d > 128:
+        the MFMA envelope (d <= 128) and a Euclidean formula, or the forest map (Hamming with ``apply_affine``)."""
+        if X is None:
+            return 0
+        if formula == "hamming":
+            return (_native.dtype_code(X.dtype) or 0) if apply_affine and self.has_forest else 0
+        if self.d > 128:
             return 0
         return _native.dtype_code(X.dtype) or 0
 
@@ -129,7 +159,7 @@ class KNNEngine:
         into (torch.cuda input only), e.g. this rank's slot of an all-gather buffer.
         ``check_finite``: the kernels that read ``X`` also test it for NaN / infinity and the call
         raises ``HipBackendError(ERR_NONFINITE)`` (for CUDA tensors this synchronises the stream)."""
-        qdt = self.query_dtype_code(X, formula)
+        qdt = self.query_dtype_code(X, formula, apply_affine)
         opts = self._opts(k, exclude_self=exclude_self, deterministic=deterministic,
                           decimals=decimals, formula=formula,
                           apply_affine=apply_affine and X is not None, row_offset=row_offset,
@@ -200,7 +230,7 @@ class KNNEngine:
         if weights not in _WEIGHT_MODES:
             raise ValueError(f"weights not recognized: should be 'uniform', 'distance', or a callable; got {weights!r}")
         mode = _WEIGHT_MODES[weights]
-        qdt = self.query_dtype_code(X, formula)
+        qdt = self.query_dtype_code(X, formula, apply_affine)
         opts = self._opts(k, exclude_self=exclude_self, deterministic=deterministic, decimals=decimals,
                           formula=formula, apply_affine=apply_affine and X is not None,
                           weight_mode=mode, row_offset=row_offset, check_finite=check_finite and X is not None,

@@ -59,6 +59,8 @@ EXPORTED_SYMBOLS = (
     "sknnr_index_destroy",
     "sknnr_index_set_affine",
     "sknnr_index_set_hamming_weights",
+    "sknnr_index_set_forest",
+    "sknnr_forest_apply",
     "sknnr_affine_transform",
     "sknnr_index_shape",
     "sknnr_get_stats",
@@ -165,6 +167,8 @@ def load(build_if_missing: bool = False):
     lib.sknnr_index_destroy.restype = None
     lib.sknnr_index_set_affine.argtypes = [vp, c_int32, vp, vp, vp]
     lib.sknnr_index_set_hamming_weights.argtypes = [vp, vp, c_int32]
+    lib.sknnr_index_set_forest.argtypes = [vp, c_int32, c_int32, vp, vp, vp, vp, vp]
+    lib.sknnr_forest_apply.argtypes = [vp, vp, c_int64, c_int32, c_int32, vp]
     lib.sknnr_affine_transform.argtypes = [vp, c_int64, c_int32, vp, vp, vp, c_int32, vp, c_int32]
     lib.sknnr_index_shape.argtypes = [vp, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32),
                                       POINTER(c_int32), POINTER(c_int32)]
@@ -269,6 +273,31 @@ class Index:
     def set_hamming_weights(self, w):
         w = _c_f64(w).reshape(-1)
         check(load().sknnr_index_set_hamming_weights(self.handle, _host_ptr(w), w.size))
+
+    def set_forest(self, d_in, tree_offset, threshold, feature, left, right):
+        """Install the query-time forest map (sknnr_index_set_forest): the flattened trees of
+        ``TreeNodeTransformer.forest_image()``, one tree per column of the node-id rows."""
+        off = np.ascontiguousarray(tree_offset, dtype=np.int64)
+        thr = _c_f64(threshold)
+        feat, lc, rc = (np.ascontiguousarray(a, dtype=np.int32) for a in (feature, left, right))
+        n_nodes = int(off[-1]) if off.size else 0
+        if off.ndim != 1 or off.size < 2 or any(a.shape != (n_nodes,) for a in (thr, feat, lc, rc)):
+            raise ValueError("tree_offset must hold n_trees + 1 offsets and the node arrays tree_offset[-1] entries")
+        check(load().sknnr_index_set_forest(self.handle, int(d_in), off.size - 1, _host_ptr(off), _host_ptr(thr),
+                                            _host_ptr(feat), _host_ptr(lc), _host_ptr(rc)))
+        self.d_in = int(d_in)
+
+    def forest_apply_host(self, q, query_dtype=0):
+        """Node ids ``(nq, n_trees)`` float64 of the raw rows ``q`` through the installed forests (sknnr_forest_apply)."""
+        q = _c_rows(q, QueryOpts(query_dtype=int(query_dtype)))
+        out = np.empty((q.shape[0], self.d), dtype=np.float64)
+        check(load().sknnr_forest_apply(self.handle, _host_ptr(q), q.shape[0], int(query_dtype), MEM_HOST,
+                                        _host_ptr(out)))
+        return out
+
+    def forest_apply_device(self, q_ptr, nq, query_dtype, out_ptr):
+        check(load().sknnr_forest_apply(self.handle, c_void_p(q_ptr or None), nq, int(query_dtype), MEM_DEVICE,
+                                        c_void_p(out_ptr or None)))
 
     def stats(self) -> dict:
         st = Stats()

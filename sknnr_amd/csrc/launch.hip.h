@@ -1,15 +1,16 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
-// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING), templates where they are instantiated.
+// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST), templates where they are instantiated.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "bucket.hip.h"
 #include "coarse2.hip.h"
 #include "exact.hip.h"
+#include "forest.hip.h"
 #include "hamming.hip.h"
 
 namespace sknnr {
@@ -40,6 +41,10 @@ hipError_t hamming_coarse(const HammingArgs& a, hipStream_t st);
 hipError_t hamming_rescore(const HammingRescoreArgs& a, hipStream_t st);
 // full float64 distance rows of selected queries (sknnr_hamming_distances)
 hipError_t hamming_distance_rows(const HammingRowsArgs& a, hipStream_t st);
+
+// ---- k_forest.hip --------------------------------------------------------------------------------------------------------
+// raw query rows -> float64 node ids of every tree of the handle's forests (RFNN / GBNN query-time map)
+hipError_t forest_apply(const ForestArgs& a, hipStream_t st);
 
 // ---- k_coarse1.hip / k_coarse2.hip: the MFMA pre-filters ----------------------------------------------------------------
 struct Coarse1Launch {

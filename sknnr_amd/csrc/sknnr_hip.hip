@@ -236,6 +236,14 @@ struct sknnr_index {
     DevBuf<double> center, scale, proj;  // proj padded to (d_in, 16*ks) when ks > 0 else (d_in, d)
     bool has_center = false, has_scale = false, has_proj = false;
 
+    // query-time forest map of RFNN / GBNN (forest.hip.h): raw rows -> node ids, one column per tree
+    bool has_forest = false;
+    int f_d_in = 0;
+    DevBuf<int4> f_nodes;
+    DevBuf<long> f_off;
+    DevBuf<int> f_depth;
+    DevBuf<double> f_ids;  // workspace: node ids of one chunk of a call's rows
+
     DevBuf<double> hw;       // weighted-Hamming weights (one per column), set by sknnr_index_set_hamming_weights
     double hw_sum = 0.0;
     bool has_hw = false;
@@ -312,8 +320,9 @@ struct sknnr_index {
         w_out.reset();
         (void)hipSetDevice(device);
         for (auto* b : {&center, &scale, &proj, &ref64, &refT, &rn64, &y64, &mu_dev, &xt, &qnc, &xstage,
-                        &dist_stage, &pred_stage})
+                        &dist_stage, &pred_stage, &f_ids})
             b->release();
+        f_nodes.release(); f_off.release(); f_depth.release();
         rimg.release();
         perm.release();
         perm2.release();
@@ -371,7 +380,7 @@ extern "C" int sknnr_index_shape(const sknnr_index* ix, int64_t* n_ref, int32_t*
     if (n_ref) *n_ref = ix->n_ref;
     if (d) *d = ix->d;
     if (t) *t = ix->t;
-    if (d_in) *d_in = ix->has_affine ? ix->d_in : ix->d;
+    if (d_in) *d_in = ix->has_affine ? ix->d_in : (ix->has_forest ? ix->f_d_in : ix->d);
     if (device) *device = ix->device;
     return SKNNR_OK;
 }
@@ -1027,6 +1036,66 @@ extern "C" int sknnr_index_set_hamming_weights(sknnr_index* ix, const double* w,
     return SKNNR_OK;
 }
 
+extern "C" int sknnr_index_set_forest(sknnr_index* ix, int32_t d_in, int32_t n_trees, const int64_t* tree_offset,
+                                      const double* threshold, const int32_t* feature, const int32_t* left,
+                                      const int32_t* right) {
+    if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (d_in < 1) return fail(SKNNR_ERR_INVALID, "d_in must be >= 1");
+    if (n_trees != ix->d) return fail(SKNNR_ERR_INVALID, "the forests have %d trees, the node-id rows %d columns", n_trees, ix->d);
+    if (!tree_offset || !threshold || !feature || !left || !right) return fail(SKNNR_ERR_INVALID, "NULL forest array");
+    if (tree_offset[0] != 0) return fail(SKNNR_ERR_INVALID, "tree_offset[0] must be 0");
+    for (int t = 0; t < n_trees; ++t)
+        if (tree_offset[t + 1] <= tree_offset[t] || tree_offset[t + 1] - tree_offset[t] > 0x7fffffffL)
+            return fail(SKNNR_ERR_INVALID, "tree %d has %ld nodes", t, (long)(tree_offset[t + 1] - tree_offset[t]));
+    // Termination and bounds of the device walk: children after their parent and inside the tree, features inside the
+    // row.  Depths follow in one pass (a child's depth is final once every node before it is done).
+    const long n_nodes = (long)tree_offset[n_trees];
+    std::vector<int4> nodes((size_t)n_nodes);
+    std::vector<int> depth((size_t)n_trees, 0), node_depth;
+    for (int t = 0; t < n_trees; ++t) {
+        const long base = (long)tree_offset[t];
+        const int n_t = (int)(tree_offset[t + 1] - base);
+        node_depth.assign((size_t)n_t, 0);
+        for (int i = 0; i < n_t; ++i) {
+            const long g = base + i;
+            const int l = left[g], r = right[g];
+            if (l == -1 && r == -1) {
+                nodes[(size_t)g] = int4{0, 0, -1, -1};
+                depth[(size_t)t] = std::max(depth[(size_t)t], node_depth[(size_t)i]);
+                continue;
+            }
+            if (l <= i || r <= i || l >= n_t || r >= n_t)
+                return fail(SKNNR_ERR_INVALID, "tree %d, node %d: children (%d, %d) must lie in (%d, %d)", t, i, l, r, i, n_t);
+            if (feature[g] < 0 || feature[g] >= d_in)
+                return fail(SKNNR_ERR_INVALID, "tree %d, node %d: feature %d outside [0, %d)", t, i, feature[g], d_in);
+            const double thr = threshold[g];
+            if (thr != thr) return fail(SKNNR_ERR_INVALID, "tree %d, node %d: threshold is NaN", t, i);
+            // the largest float32 <= thr (forest.hip.h: the float32 compare is then the reference's float64 one)
+            float f = (float)thr;
+            if ((double)f > thr) f = std::nextafter(f, -std::numeric_limits<float>::infinity());
+            int fb;
+            std::memcpy(&fb, &f, 4);
+            nodes[(size_t)g] = int4{fb, feature[g], l, r};
+            node_depth[(size_t)l] = std::max(node_depth[(size_t)l], node_depth[(size_t)i] + 1);
+            node_depth[(size_t)r] = std::max(node_depth[(size_t)r], node_depth[(size_t)i] + 1);
+        }
+    }
+    std::vector<long> off(tree_offset, tree_offset + n_trees);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());  // a call still running may be reading the previous forests
+    ix->has_forest = false;
+    HIP_TRY(ix->f_nodes.ensure((size_t)n_nodes));
+    HIP_TRY(ix->f_off.ensure((size_t)n_trees));
+    HIP_TRY(ix->f_depth.ensure((size_t)n_trees));
+    HIP_TRY(hipMemcpy(ix->f_nodes.p, nodes.data(), (size_t)n_nodes * sizeof(int4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ix->f_off.p, off.data(), (size_t)n_trees * sizeof(long), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ix->f_depth.p, depth.data(), (size_t)n_trees * sizeof(int), hipMemcpyHostToDevice));
+    ix->f_d_in = d_in;
+    ix->has_forest = true;
+    return SKNNR_OK;
+}
+
 extern "C" int sknnr_affine_transform(const double* x, int64_t n, int32_t d_in, const double* center,
                                       const double* scale, const double* proj, int32_t d, double* out,
                                       int32_t device) {
@@ -1150,7 +1219,9 @@ extern "C" int sknnr_reset_stats(sknnr_index* ix) {
 
 static int nonfinite_error(int bits) {
     if (bits & 1) return fail(SKNNR_ERR_NONFINITE, "Input X contains NaN.");
-    return fail(SKNNR_ERR_NONFINITE, "Input X contains infinity or a value too large for dtype('float64').");
+    if (bits & 2) return fail(SKNNR_ERR_NONFINITE, "Input X contains infinity or a value too large for dtype('float64').");
+    // (bit 2, the forest map only: a value that is infinite as float32 -- forest.apply's own check)
+    return fail(SKNNR_ERR_NONFINITE, "Input X contains infinity or a value too large for dtype('float32').");
 }
 
 // Read and clear the handle's non-finite flag; the caller has synchronised the stream that set it.
@@ -1386,6 +1457,16 @@ int launch_scan(sknnr_index* ix, const SelectArgs& s, const int* list, const int
     return launch_scan_formula(ix, a, max_items, chunked, sh, st);
 }
 
+// Does a call with these opts map its rows through the handle's forests (apply_affine on a Hamming call)?
+bool uses_forest(const sknnr_index* ix, const sknnr_query_opts* o) {
+    return o->apply_affine && o->formula == SKNNR_FORMULA_HAMMING && ix->has_forest;
+}
+// Columns of the caller's query rows: d_in of the query-time map in use (affine or forest), else d.
+int query_cols(const sknnr_index* ix, const sknnr_query_opts* o) {
+    if (!o->apply_affine) return ix->d;
+    return uses_forest(ix, o) ? ix->f_d_in : ix->d_in;
+}
+
 struct CallCtx {
     sknnr_index* ix;
     const sknnr_query_opts* o;
@@ -1397,7 +1478,8 @@ int validate_call(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
     if (!o) return fail(SKNNR_ERR_INVALID, "opts is NULL");
     if (o->query_dtype < 0 || o->query_dtype >= kDtypeCount) return fail(SKNNR_ERR_INVALID, "unknown query_dtype %d", o->query_dtype);
-    if (o->query_dtype != SKNNR_DTYPE_F64 && q) {
+    const bool forest_map = uses_forest(ix, o);  // (the forest kernel reads every sknnr_dtype)
+    if (o->query_dtype != SKNNR_DTYPE_F64 && q && !forest_map) {
         // narrow rows are widened by the query preparation kernel, which exists inside the MFMA envelope only
         if (ix->ks == 0) return fail(SKNNR_ERR_UNSUPPORTED, "query_dtype %d needs d <= 128 (d = %d): pass float64 rows", o->query_dtype, ix->d);
         if (o->formula == SKNNR_FORMULA_HAMMING) return fail(SKNNR_ERR_UNSUPPORTED, "node ids are float64: query_dtype must be 0 with formula = HAMMING");
@@ -1420,13 +1502,13 @@ int validate_call(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_
                     "Expected n_neighbors <= n_samples_fit, but n_neighbors = %d, n_samples_fit = %ld, n_samples = %ld",
                     o->n_neighbors, n_fit, (long)nq);
     }
-    if (o->apply_affine && !ix->has_affine)
+    if (o->apply_affine && !ix->has_affine && !forest_map)
         return fail(SKNNR_ERR_INVALID, "apply_affine is set but no affine map was installed");
     if (o->formula != SKNNR_FORMULA_EXPANDED && o->formula != SKNNR_FORMULA_DIRECT && o->formula != SKNNR_FORMULA_HAMMING)
         return fail(SKNNR_ERR_INVALID, "unknown formula %d", o->formula);
     if (o->formula == SKNNR_FORMULA_HAMMING) {
         if (!ix->has_hw) return fail(SKNNR_ERR_INVALID, "formula = HAMMING needs sknnr_index_set_hamming_weights first");
-        if (o->apply_affine) return fail(SKNNR_ERR_INVALID, "node ids are not mapped by an affine transform");
+        if (o->apply_affine && !forest_map) return fail(SKNNR_ERR_INVALID, "node ids are not mapped by an affine transform");
     }
     if (o->n_neighbors + (o->exclude_self ? 1 : 0) > kScanMaxKK)
         return fail(SKNNR_ERR_UNSUPPORTED, "n_neighbors = %d exceeds the HIP backend's limit of %d", o->n_neighbors,
@@ -1438,8 +1520,11 @@ int validate_call(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_
 // Device-resident core: nq rows at xdev (raw if affine else transformed), outputs on device.
 // raw / id_offset: shard candidates (sknnr_shard_candidates): squared values ascending by (value, index), indices +
 // id_offset, no post-steps
+int run_forest(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opts* o, double* d_dist, long* d_idx,
+               hipStream_t st);
 int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opts* o, double* d_dist,
                long* d_idx, hipStream_t st, int raw = 0, long id_offset = 0) {
+    if (xdev && uses_forest(ix, o)) return run_forest(ix, xdev, nq, o, d_dist, d_idx, st);
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
     const bool affine = o->apply_affine != 0 && xdev != nullptr;
     const bool self_rows = xdev == nullptr;
@@ -1715,6 +1800,53 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
     return SKNNR_OK;
 }
 
+// Rows of one forest-map chunk: the node ids of at most 2^18 rows (the integer Hamming pre-filter's chunk) and 4 GiB.  A
+// call thus never holds more ids than the (nq, n_trees) matrix a call on node ids is handed.
+long forest_chunk_rows(int n_trees) {
+    const long by_bytes = (4L << 30) / (8L * std::max(n_trees, 1));
+    return std::max<long>(kFtRows, std::min<long>(1L << 18, by_bytes) / kFtRows * kFtRows);
+}
+
+ForestArgs forest_args(const sknnr_index* ix, const void* x, long n, int x_dtype, double* out, int* status) {
+    ForestArgs a{};
+    a.x = x;
+    a.x_dtype = x_dtype;
+    a.nq = n;
+    a.d_in = ix->f_d_in;
+    a.nodes = ix->f_nodes.p;
+    a.tree_off = ix->f_off.p;
+    a.tree_depth = ix->f_depth.p;
+    a.n_trees = ix->d;
+    a.out = out;
+    a.status = status;
+    return a;
+}
+
+// Raw rows through the forest map, chunk by chunk: the forest kernel writes the chunk's node ids into the workspace, then
+// the chunk is an ordinary call on node ids (Hamming pre-filter, re-score, exact scan, post-steps) at its global rows.
+int run_forest(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opts* o, double* d_dist, long* d_idx,
+               hipStream_t st) {
+    if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));  // f_ids belongs to the workspace
+    const long chunk = forest_chunk_rows(ix->d);
+    HIP_TRY(ix->f_ids.ensure((size_t)std::min(chunk, nq) * ix->d));
+    const size_t row_bytes = (size_t)ix->f_d_in * dtype_bytes(o->query_dtype);
+    const int k = o->n_neighbors;
+    for (long c0 = 0; c0 < nq; c0 += chunk) {
+        const long n = std::min(chunk, nq - c0);
+        const ForestArgs fa = forest_args(ix, (const char*)xdev + (size_t)c0 * row_bytes, n, o->query_dtype, ix->f_ids.p,
+                                          o->check_finite ? ix->status.p : nullptr);
+        HIP_TRY(launch::forest_apply(fa, st));
+        sknnr_query_opts oc = *o;
+        oc.apply_affine = 0;
+        oc.query_dtype = SKNNR_DTYPE_F64;
+        oc.check_finite = 0;  // (node ids are finite; the forest kernel has checked the rows)
+        oc.row_offset = o->row_offset + c0;
+        int rc = run_device(ix, ix->f_ids.p, n, &oc, d_dist ? d_dist + c0 * k : nullptr, d_idx + c0 * k, st);
+        if (rc) return rc;
+    }
+    return SKNNR_OK;
+}
+
 }  // namespace
 
 // ----------------------------------------------------------------------------------------
@@ -1816,7 +1948,7 @@ int pipe_open(HostPipe& p, sknnr_index* ix, const sknnr_query_opts* o, bool want
     p.want_pred = want_pred;
     p.k = o->n_neighbors;
     p.t = ix->t;
-    p.d_x = o->apply_affine ? ix->d_in : ix->d;
+    p.d_x = query_cols(ix, o);
     p.x_esz = (size_t)dtype_bytes(o->query_dtype);
     // (each object on its own: a creation that failed half way is completed by the next call, never skipped)
     for (hipStream_t* h : {&ix->st_h2d, &ix->st_run, &ix->st_d2h})
@@ -2132,6 +2264,47 @@ int run_self_rows(sknnr_index* ix, long nq, const sknnr_query_opts* o, double* o
 }  // namespace
 
 // ----------------------------------------------------------------------------------------
+// the forest map alone
+// ----------------------------------------------------------------------------------------
+extern "C" int sknnr_forest_apply(sknnr_index* ix, const void* q, int64_t nq, int32_t query_dtype, int32_t mem,
+                                  double* out_ids) {
+    if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (!ix->has_forest) return fail(SKNNR_ERR_INVALID, "sknnr_forest_apply needs sknnr_index_set_forest first");
+    if (query_dtype < 0 || query_dtype >= kDtypeCount) return fail(SKNNR_ERR_INVALID, "unknown query_dtype %d", query_dtype);
+    if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
+    if (nq == 0) return SKNNR_OK;
+    if (!q || !out_ids) return fail(SKNNR_ERR_INVALID, "q / out_ids is NULL");
+    if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());  // (the default stream: calls of the handle on other streams are done first)
+    DevBuf<int> status;
+    HIP_TRY(status.ensure(1));
+    HIP_TRY(hipMemset(status.p, 0, sizeof(int)));
+    const size_t row_bytes = (size_t)ix->f_d_in * dtype_bytes(query_dtype);
+    if (mem == SKNNR_MEM_DEVICE) {
+        HIP_TRY(launch::forest_apply(forest_args(ix, q, nq, query_dtype, out_ids, status.p), nullptr));
+    } else {
+        const long chunk = forest_chunk_rows(ix->d);
+        const long cap = std::min<long>(chunk, nq);
+        DevBuf<char> dq;
+        DevBuf<double> dout;
+        HIP_TRY(dq.ensure((size_t)cap * row_bytes));
+        HIP_TRY(dout.ensure((size_t)cap * ix->d));
+        for (long c0 = 0; c0 < nq; c0 += chunk) {
+            const long n = std::min(chunk, nq - c0);
+            HIP_TRY(hipMemcpy(dq.p, (const char*)q + (size_t)c0 * row_bytes, (size_t)n * row_bytes, hipMemcpyHostToDevice));
+            HIP_TRY(launch::forest_apply(forest_args(ix, dq.p, n, query_dtype, dout.p, status.p), nullptr));
+            HIP_TRY(hipMemcpy(out_ids + (size_t)c0 * ix->d, dout.p, (size_t)n * ix->d * sizeof(double), hipMemcpyDeviceToHost));
+        }
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    int bits = 0;
+    HIP_TRY(hipMemcpy(&bits, status.p, sizeof bits, hipMemcpyDeviceToHost));
+    return bits ? nonfinite_error(bits) : SKNNR_OK;
+}
+
+// ----------------------------------------------------------------------------------------
 // kneighbors
 // ----------------------------------------------------------------------------------------
 extern "C" int sknnr_kneighbors(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o,
@@ -2222,6 +2395,7 @@ extern "C" int sknnr_shard_candidates(sknnr_index* ix, const double* q, int64_t 
     int rc = validate_call(ix, q, nq, o, out_idx);
     if (rc) return rc;
     if (o->query_dtype != SKNNR_DTYPE_F64) return fail(SKNNR_ERR_UNSUPPORTED, "the sharded entry points take float64 rows (query_dtype = 0)");
+    if (uses_forest(ix, o)) return fail(SKNNR_ERR_UNSUPPORTED, "the sharded entry points take node ids: the forest map is not applied there");
     if (!q || o->exclude_self)
         return fail(SKNNR_ERR_INVALID, "shard candidates are searched for given rows: the caller adds the self slot (n_neighbors + 1) and the merge drops it");
     if (!out_val && nq > 0) return fail(SKNNR_ERR_INVALID, "out_val is NULL");
@@ -2335,6 +2509,7 @@ extern "C" int sknnr_merge_shards(sknnr_index* ix, const double* q, int64_t nq, 
     int rc = validate_call(ix, q, nq, o, out_idx);
     if (rc) return rc;
     if (o->query_dtype != SKNNR_DTYPE_F64) return fail(SKNNR_ERR_UNSUPPORTED, "the sharded entry points take float64 rows (query_dtype = 0)");
+    if (uses_forest(ix, o)) return fail(SKNNR_ERR_UNSUPPORTED, "the sharded entry points take node ids: the forest map is not applied there");
     if (n_shards < 1 || n_shards > 64) return fail(SKNNR_ERR_INVALID, "n_shards must be in [1, 64], got %d", n_shards);
     if ((!shard_val || !shard_idx) && nq > 0) return fail(SKNNR_ERR_INVALID, "shard candidate arrays are NULL");
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);

@@ -400,7 +400,8 @@ class RefShardedKNN:
             reg._check_reference_ties_supported("RefShardedKNN")
             k = reg._resolve_k(n_neighbors)
             if X is not None:
-                X = (self.estimator._validate_raw_query(X) if transformed else reg._validate_query(X))
+                # (tree-node spaces: node ids from the host transform; the sharded entry points do not apply the forest map)
+                X = (self.estimator._validate_raw_query(X, host_ids=True) if transformed else reg._validate_query(X))
         else:
             k = int(n_neighbors)
         kk = k + (1 if X is None else 0)

@@ -5,7 +5,9 @@ Public surface (class names, constructor parameters, fitted attributes, feature 
 /root/reference/src/sknnr/transformers/_tree_node_transformer.py, _rfnode_transformer.py and
 _gbnode_transformer.py.  Growing the forests and ``apply`` are scikit-learn's (host, outside the hot
 path); what the GPU sees is the int64 node-id matrix these classes emit and
-the per-tree weights, which feed the weighted-Hamming search (``SKNNR_FORMULA_HAMMING``).
+the per-tree weights, which feed the weighted-Hamming search (``SKNNR_FORMULA_HAMMING``).  For query
+rows, ``forest_image()`` hands the fitted trees themselves to the device (``sknnr_index_set_forest``),
+which then walks raw rows down every tree as ``apply`` does; ``transform`` stays scikit-learn's.
 """
 
 from __future__ import annotations
@@ -20,7 +22,7 @@ from sklearn.ensemble import (
 )
 from sklearn.utils.validation import check_array, check_is_fitted, validate_data
 
-__all__ = ["TreeNodeTransformer", "RFNodeTransformer", "GBNodeTransformer"]
+__all__ = ["TreeNodeTransformer", "RFNodeTransformer", "GBNodeTransformer", "check_forest_image"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -78,6 +80,47 @@ def _target_plan(y):
     return plan
 
 
+def check_forest_image(image) -> np.ndarray:
+    """The structure check ``sknnr_index_set_forest`` applies before a forest reaches the device, on the host: every tree
+    has a node, every internal node's children come after it and inside its tree, its feature is one of the ``d_in``
+    columns and its threshold is not NaN; leaves have both children -1.  Returns each tree's depth (edges on its longest
+    root-to-leaf path), the bound of the device walk; raises ``ValueError`` otherwise."""
+    off = np.asarray(image["tree_offset"], dtype=np.int64)
+    d_in = int(image["d_in"])
+    thr = np.asarray(image["threshold"], dtype=np.float64)
+    feat, left, right = (np.asarray(image[k], dtype=np.int64) for k in ("feature", "left", "right"))
+    if off.ndim != 1 or off.size < 2 or off[0] != 0 or np.any(np.diff(off) < 1):
+        raise ValueError("tree_offset must start at 0 and give every tree at least one node")
+    depths = np.zeros(off.size - 1, dtype=np.int64)
+    for t in range(off.size - 1):
+        a, b = off[t], off[t + 1]
+        lc, rc, f, th = left[a:b], right[a:b], feat[a:b], thr[a:b]
+        own = np.arange(b - a)
+        leaf = (lc == -1) & (rc == -1)
+        inner = ~leaf
+        if np.any((lc[inner] <= own[inner]) | (rc[inner] <= own[inner]) | (lc[inner] >= b - a) | (rc[inner] >= b - a)):
+            raise ValueError(f"tree {t}: a child id is not after its parent inside the tree")
+        if np.any((f[inner] < 0) | (f[inner] >= d_in)):
+            raise ValueError(f"tree {t}: a feature lies outside [0, {d_in})")
+        if np.any(np.isnan(th[inner])):
+            raise ValueError(f"tree {t}: a threshold is NaN")
+        depth = np.zeros(b - a, dtype=np.int64)
+        for i in np.flatnonzero(inner):  # parents before children: one pass
+            depth[lc[i]] = max(depth[lc[i]], depth[i] + 1)
+            depth[rc[i]] = max(depth[rc[i]], depth[i] + 1)
+        depths[t] = depth.max()
+    return depths
+
+
+def _forest_trees(forest):
+    """The fitted trees of one ensemble in the column order of ``transform``: a random forest's in ``estimators_``
+    order; a boosted ensemble's (stages, classes) grid class-major, as ``apply``'s (n, stages, classes) is reshaped."""
+    est = forest.estimators_
+    if isinstance(est, np.ndarray) and est.ndim == 2:
+        return [est[s, c] for c in range(est.shape[1]) for s in range(est.shape[0])]
+    return list(est)
+
+
 class TreeNodeTransformer(TransformerMixin, BaseEstimator):
     """Shared machinery: fit one tree ensemble per target, transform = node ids of every tree."""
 
@@ -122,6 +165,24 @@ class TreeNodeTransformer(TransformerMixin, BaseEstimator):
 
     def fit_transform(self, X, y):
         return self.fit(X, y).transform(X)
+
+    def forest_image(self) -> dict:
+        """Every fitted tree, flattened in the column order of ``transform`` -- the counterpart of the ordination
+        transformers' ``affine_params()``.  ``d_in``: features of a raw row; ``tree_offset`` (n_trees + 1): tree ``t``
+        owns nodes ``[tree_offset[t], tree_offset[t + 1])``; ``threshold`` (float64), ``feature``, ``left``, ``right``
+        (int32): the trees' ``tree_`` arrays one after another, child ids local to their tree (-1: leaf).  The device
+        walks a row down tree ``t`` as ``apply`` does and writes the node id to column ``t``."""
+        check_is_fitted(self)
+        trees = [tree.tree_ for forest in self.estimators_ for tree in _forest_trees(forest)]
+        counts = np.array([t.node_count for t in trees], dtype=np.int64)
+        return {
+            "d_in": int(self.n_features_in_),
+            "tree_offset": np.concatenate([[0], np.cumsum(counts)]).astype(np.int64),
+            "threshold": np.concatenate([t.threshold for t in trees]).astype(np.float64),
+            "feature": np.concatenate([t.feature for t in trees]).astype(np.int32),
+            "left": np.concatenate([t.children_left for t in trees]).astype(np.int32),
+            "right": np.concatenate([t.children_right for t in trees]).astype(np.int32),
+        }
 
     def __sklearn_tags__(self):
         tags = super().__sklearn_tags__()
