@@ -93,7 +93,14 @@ typedef enum sknnr_dtype {
 typedef enum sknnr_weight_mode {
     SKNNR_WEIGHTS_UNIFORM = 0,  /* np.mean over the k neighbours  (SKL/neighbors/_regression.py:254-255) */
     SKNNR_WEIGHTS_DISTANCE = 1, /* 1/d, rows containing d == 0 become a 0/1 mask (SKL/neighbors/_base.py:113-119) */
-    SKNNR_WEIGHTS_EXPLICIT = 2  /* caller supplies w (nq, k): result of a Python callable on the distances */
+    SKNNR_WEIGHTS_EXPLICIT = 2, /* caller supplies w (nq, k): result of a Python callable on the distances */
+    /* A weight_mode argument is one of the three above in its low byte, optionally OR-ed with flag bits that name the
+     * dtype numpy reduces in (the values themselves always travel as float64, holding the float32 ones exactly): */
+    SKNNR_WEIGHTS_BASE_MASK = 0xff,
+    SKNNR_WEIGHTS_F32_TARGETS = 0x100, /* the targets are float32: the uniform mean runs in binary32 (np.mean keeps the
+                                          dtype); with F32_WEIGHTS also y * w, its sum and the quotient.  Distance
+                                          weights ignore it (1 / d is float64, so everything promotes) */
+    SKNNR_WEIGHTS_F32_WEIGHTS = 0x200  /* EXPLICIT only: w is float32, np.sum(w, axis=1) runs in binary32 */
 } sknnr_weight_mode;
 
 typedef struct sknnr_index sknnr_index; /* opaque handle */
@@ -111,7 +118,7 @@ typedef struct sknnr_query_opts {
                               go through the affine map (REF _base.py:236-239) -- or, with formula = HAMMING on a
                               handle with a forest (sknnr_index_set_forest), through the forests, which turn them
                               into node ids; 0 = already transformed (d columns) */
-    int32_t weight_mode;   /* predict only: sknnr_weight_mode */
+    int32_t weight_mode;   /* predict only: sknnr_weight_mode, with its F32_TARGETS flag */
     int32_t check_finite;  /* 1 = the kernels that read the query rows also test them for NaN / infinity
                               (what validate_data(ensure_all_finite=True) does on the host in the reference).
                               Host-memory calls then fail with SKNNR_ERR_NONFINITE; device-memory calls stay
@@ -276,6 +283,10 @@ int sknnr_predict(sknnr_index* index, const void* q, int64_t nq, const sknnr_que
  * The reduction alone, from neighbours already found (needed when `weights` is a Python
  * callable: the host evaluates it on the distances and passes w).
  *   dist : (nq, k) or NULL for uniform;  idx : (nq, k);  w : (nq, k) for SKNNR_WEIGHTS_EXPLICIT
+ *   k    : at most 192, the largest k of a search (SKNNR_ERR_UNSUPPORTED above)
+ * Sums are numpy's, bit for bit: np.sum over k is its pairwise sum (8 partial sums; above 128 terms split at
+ * n/2 - (n/2) % 8), and so is the uniform mean of one target; the uniform mean of t >= 2 targets adds the k rows in
+ * order.  The result is the float64 value, or the float32 value scikit-learn returns widened exactly.
  */
 int sknnr_predict_from_neighbors(sknnr_index* index, const double* dist, const int64_t* idx,
                                  const double* w, int64_t nq, int32_t k, int32_t weight_mode,

@@ -237,7 +237,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
     def _build_engine(self):
         y2 = self._y.reshape(-1, 1) if self._y.ndim == 1 else self._y
-        self._engine = KNNEngine(self._fit_X, np.asarray(y2, dtype=np.float64), device=self._device)
+        self._engine = KNNEngine(self._fit_X, np.asarray(y2, dtype=np.float64), device=self._device,
+                                 target_dtype=self._y.dtype)
         if getattr(self, "effective_metric_", "euclidean") == "hamming":
             self._engine.set_hamming_weights(self._hamming_w)
         if self._affine is not None:
@@ -507,12 +508,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 if cuda:
                     dev = dist.device
                     dist, idx = dist.cpu().numpy(), idx.cpu().numpy()
-                if callable(weights):
-                    w = np.asarray(weights(dist), dtype=np.float64)
-                    pred = self.engine_._index.predict_from_neighbors_host(dist, idx, w, _native.WEIGHTS_EXPLICIT)
-                else:
-                    mode = _native.WEIGHTS_DISTANCE if weights == "distance" else _native.WEIGHTS_UNIFORM
-                    pred = self.engine_._index.predict_from_neighbors_host(dist, idx, None, mode)
+                pred = self.engine_.predict_from_neighbors(dist, idx, "uniform" if weights is None else weights)
                 if cuda:
                     import torch
 
@@ -664,7 +660,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
     def predict_chunks(self, tiles, out=None):
         """``predict`` over an iterable of host tiles as one streamed call; ``out``: preallocated
-        ``(n_rows, n_targets)`` float64 array (e.g. a memmap)."""
+        ``(n_rows, n_targets)`` float64 array (e.g. a memmap; float32 results are held exactly)."""
         check_is_fitted(self, "_fit_X")
         return self._predict_chunks(tiles, self._validate_query, apply_affine=False, out=out, owner=None)
 
@@ -679,13 +675,15 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 row += t.shape[0]
             pred = np.concatenate([p.reshape(len(p), -1) for p in preds]) if preds else np.empty((0, self.engine_.t))
             if out is not None:
-                out[:len(pred)] = pred
+                out[:len(pred)] = pred.reshape((len(pred),) + out.shape[1:])  # (out is 1-D for a 1-D y)
                 pred = out[:len(pred)]
         else:
             o = None if out is None else (None, None, out.reshape(out.shape[0], -1))
             _, _, pred = self._stream_tiles(tiles, validate, self.n_neighbors, apply_affine=apply_affine,
                                             weights=weights, return_distance=False,
                                             use_deterministic_ordering=True, out=o, owner=owner)
+            if out is None:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
+                pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         return pred.reshape(-1) if self._y.ndim == 1 else pred
 
     def score(self, X, y, sample_weight=None):

@@ -56,14 +56,20 @@ class KNNEngine:
     ----------
     fit_X : (n_ref, d) float64, the *transformed* reference rows (the reference's ``_fit_X``)
     y : (n_ref, t) targets or None
+    target_dtype : dtype of the caller's targets when they were narrower than ``y`` (default: ``y``'s).  float32
+        targets are reduced as numpy reduces them: the uniform mean in binary32, returned as float32
+        (SKL/neighbors/_regression.py:254-255 keeps the dtype of ``_y``); other dtypes give float64.
     """
 
-    def __init__(self, fit_X, y=None, device: int | None = None):
+    def __init__(self, fit_X, y=None, device: int | None = None, target_dtype=None):
         self.device = default_device() if device is None else int(device)
         self._index = _native.Index(fit_X, y, device=self.device)
         self.n_ref = self._index.n_ref
         self.d = self._index.d
         self.t = self._index.t
+        if target_dtype is None and y is not None:
+            target_dtype = np.asarray(y).dtype
+        self.y32 = target_dtype is not None and np.dtype(target_dtype) == np.float32
         self.d_in = self.d
         self.has_affine = False
         self.has_forest = False
@@ -201,9 +207,62 @@ class KNNEngine:
         self._check_columns(X, apply_affine)
         return self._index.kneighbors_host(X, opts, return_distance=return_distance)
 
+    def weight_mode(self, weights, w32=False) -> int:
+        """The native weight mode of a ``uniform`` / ``distance`` / explicit (``"explicit"``) reduction, with the
+        flags that make it reduce in the dtypes numpy would: float32 targets, float32 explicit weights ``w32``."""
+        mode = _native.WEIGHTS_EXPLICIT if weights == "explicit" else _WEIGHT_MODES[weights]
+        if self.y32:
+            mode |= _native.WEIGHTS_F32_TARGETS
+        if w32:
+            mode |= _native.WEIGHTS_F32_WEIGHTS
+        return mode
+
+    def pred_dtype(self, weights):
+        """scikit-learn's result dtype: the float32 targets' own under uniform weights, else float64."""
+        return np.float32 if self.y32 and weights in (None, "uniform") else np.float64
+
+    def predict_from_neighbors(self, dist, idx, weights="uniform"):
+        """The reduction alone on neighbours already found: ``(dist, idx)`` numpy -> numpy or torch.cuda -> torch.cuda,
+        ``weights`` as in :meth:`predict` (a callable runs on the host, or on the tensors it is given)."""
+        if self.t < 1:
+            raise ValueError("the engine was built without targets")
+        k = idx.shape[1]
+        w, w32 = None, False
+        if callable(weights):
+            w = weights(dist)
+            if not hasattr(w, "dtype"):
+                w = np.asarray(w)
+            w32 = str(getattr(w, "dtype", "")) in ("float32", "torch.float32")
+            if tuple(w.shape) != tuple(dist.shape):
+                raise ValueError("the weights callable must return an array shaped like its input")
+            mode = self.weight_mode("explicit", w32)
+        elif weights in _WEIGHT_MODES:
+            mode = self.weight_mode(weights)
+        else:
+            raise ValueError(f"weights not recognized: should be 'uniform', 'distance', or a callable; got {weights!r}")
+        out_dtype = np.float64 if w is not None else self.pred_dtype(weights)
+        if is_torch_cuda_tensor(idx):
+            import torch
+
+            idx = idx.to(torch.int64).contiguous()
+            dist = None if dist is None else dist.to(torch.float64).contiguous()
+            if w is not None:
+                w = torch.as_tensor(w, device=idx.device).to(torch.float64).contiguous()
+            pred = torch.empty((idx.shape[0], self.t), dtype=torch.float64, device=idx.device)
+            if idx.shape[0]:
+                stream = torch.cuda.current_stream(idx.device).cuda_stream
+                self._index.predict_from_neighbors_device(0 if dist is None else dist.data_ptr(), idx.data_ptr(),
+                                                          0 if w is None else w.data_ptr(), idx.shape[0], k, mode,
+                                                          pred.data_ptr(), stream)
+            return pred if out_dtype == np.float64 else pred.to(torch.float32)
+        w = None if w is None else np.asarray(w, dtype=np.float64)
+        pred = self._index.predict_from_neighbors_host(dist, idx, w, mode)
+        return pred if out_dtype == np.float64 else pred.astype(np.float32)
+
     def predict(self, X, k, weights="uniform", *, exclude_self=False, deterministic=True, decimals=10,
                 formula="expanded", apply_affine=False, row_offset=0, n_self_rows=None, check_finite=False):
-        """Weighted multi-output mean of the neighbours' targets."""
+        """Weighted multi-output mean of the neighbours' targets, in the dtype scikit-learn returns
+        (:meth:`pred_dtype`)."""
         if self.t < 1:
             raise ValueError("the engine was built without targets")
         if callable(weights):
@@ -212,24 +271,11 @@ class KNNEngine:
             dist, idx = self.kneighbors(X, k, exclude_self=exclude_self, deterministic=deterministic,
                                         decimals=decimals, formula=formula, apply_affine=apply_affine,
                                         row_offset=row_offset, n_self_rows=n_self_rows, check_finite=check_finite)
-            if is_torch_cuda_tensor(dist):
-                import torch
-
-                w = weights(dist)
-                w = torch.as_tensor(w, dtype=torch.float64, device=dist.device).contiguous()
-                pred = torch.empty((dist.shape[0], self.t), dtype=torch.float64, device=dist.device)
-                stream = torch.cuda.current_stream(dist.device).cuda_stream
-                self._index.predict_from_neighbors_device(dist.data_ptr(), idx.data_ptr(), w.data_ptr(),
-                                                          dist.shape[0], k, _native.WEIGHTS_EXPLICIT,
-                                                          pred.data_ptr(), stream)
-                return pred
-            w = np.asarray(weights(dist), dtype=np.float64)
-            if w.shape != dist.shape:
-                raise ValueError("the weights callable must return an array shaped like its input")
-            return self._index.predict_from_neighbors_host(dist, idx, w, _native.WEIGHTS_EXPLICIT)
+            return self.predict_from_neighbors(dist, idx, weights)
         if weights not in _WEIGHT_MODES:
             raise ValueError(f"weights not recognized: should be 'uniform', 'distance', or a callable; got {weights!r}")
-        mode = _WEIGHT_MODES[weights]
+        mode = self.weight_mode(weights)
+        to32 = self.pred_dtype(weights) == np.float32
         qdt = self.query_dtype_code(X, formula, apply_affine)
         opts = self._opts(k, exclude_self=exclude_self, deterministic=deterministic, decimals=decimals,
                           formula=formula, apply_affine=apply_affine and X is not None,
@@ -237,7 +283,8 @@ class KNNEngine:
                           query_dtype=qdt)
         if X is None:
             nq = self.n_ref - row_offset if n_self_rows is None else int(n_self_rows)
-            return self._index.predict_host(None, opts, nq=nq)
+            pred = self._index.predict_host(None, opts, nq=nq)
+            return pred.astype(np.float32) if to32 else pred
         if is_torch_cuda_tensor(X):
             import torch
 
@@ -249,10 +296,11 @@ class KNNEngine:
                 self._index.predict_device(X.data_ptr(), nq, opts, pred.data_ptr(), 0, 0, stream)
                 if check_finite:
                     self._index.check_finite(stream)
-            return pred
+            return pred.to(torch.float32) if to32 else pred
         X = np.ascontiguousarray(X) if qdt else np.ascontiguousarray(X, dtype=np.float64)
         self._check_columns(X, apply_affine)
-        return self._index.predict_host(X, opts)
+        pred = self._index.predict_host(X, opts)
+        return pred.astype(np.float32) if to32 else pred
 
     # ---- reference-sharded search (sknnr_amd.distributed.RefShardedKNN) ------------------------------------
     def shard_candidates(self, X, kk, *, formula="expanded", apply_affine=False, index_offset=0, check_finite=False):
@@ -307,13 +355,14 @@ class KNNEngine:
                     formula="expanded", apply_affine=False, row_offset=0, check_finite=False, query_dtype=0):
         """A :class:`sknnr_amd._native.QueryStream` over host tiles: ``push(tile)`` keeps the PCIe
         pipeline full across tiles and carries the global row offset.  ``weights`` (``"uniform"`` /
-        ``"distance"``) also asks for predictions."""
+        ``"distance"``) also asks for predictions: float64 arrays, holding binary32 values where
+        :meth:`pred_dtype` is float32."""
         want_pred = weights is not None
         if want_pred and weights not in _WEIGHT_MODES:
             raise ValueError("a stream predicts with 'uniform' or 'distance' weights only")
         opts = self._opts(k, exclude_self=False, deterministic=deterministic, decimals=decimals,
                           formula=formula, apply_affine=apply_affine,
-                          weight_mode=_WEIGHT_MODES[weights] if want_pred else _native.WEIGHTS_UNIFORM,
+                          weight_mode=self.weight_mode(weights) if want_pred else _native.WEIGHTS_UNIFORM,
                           row_offset=row_offset, check_finite=check_finite, query_dtype=query_dtype)
         return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred)
 

@@ -23,6 +23,9 @@ FORMULA_HAMMING = 2
 WEIGHTS_UNIFORM = 0
 WEIGHTS_DISTANCE = 1
 WEIGHTS_EXPLICIT = 2
+# flag bits OR-ed into a weight mode (include/sknnr_hip.h): the dtype scikit-learn reduces in
+WEIGHTS_F32_TARGETS = 0x100
+WEIGHTS_F32_WEIGHTS = 0x200
 
 ERR_INVALID = -1
 ERR_K_TOO_LARGE = -2

@@ -1298,9 +1298,17 @@ __global__ void __launch_bounds__(256) scan_merge_kernel(ScanArgs a, int grid_wg
 }
 
 // ---------------------------------------------------------------------------------------
-// predict_kernel: one thread per (query, output).
+// predict_kernel (k <= 8), predict_wide_kernel (k > 8), predict32_kernel (binary32): one thread per (query, output).
 // KNeighborsRegressor.predict  SKL/neighbors/_regression.py:224-268
 // _get_weights                 SKL/neighbors/_base.py:81-124
+//
+// Summation contract: every sum is the one numpy evaluates, bit for bit (tests/test_predict_reduction_*.py).
+//  - np.sum(w, axis=1) and np.sum(y[idx, j] * w, axis=1) on (nq, k): numpy's pairwise sum over k (np_sum).
+//  - uniform, t == 1: np.mean(y[idx], axis=1) on (nq, k, 1): numpy drops the unit axis -> the pairwise sum again.
+//  - uniform, t >= 2: np.mean on (nq, k, t) adds the k slices one after another (sequential), then divides once.
+//  - float32 targets under uniform weights: the same orders in binary32, the mean rounded to binary32; float32
+//    explicit weights: the denominator in binary32 (with float32 targets also y * w and the numerator, as numpy
+//    promotes).  predict32_kernel; the caller turns the values to float32 where scikit-learn returns float32.
 // ---------------------------------------------------------------------------------------
 struct PredictArgs {
     const double* y;     // (n_ref, t)
@@ -1308,31 +1316,54 @@ struct PredictArgs {
     const long* idx;     // (nq, k)
     const double* w;     // (nq, k) explicit weights or null
     long nq;
-    int k;
+    int k;               // at most kScanMaxKK (np_sum's single split)
     int t;
-    int mode;            // sknnr_weight_mode
+    int mode;            // sknnr_weight_mode without its flag bits: 0 uniform, 1 distance, 2 explicit
+    int y32;             // predict32_kernel: the targets are binary32 values (uniform mean / explicit y * w in binary32)
+    int w32;             // predict32_kernel: the explicit weights are binary32 values (denominator in binary32)
     double* out;         // (nq, t)
 };
 
-// numpy's pairwise sum of n < 128 doubles (8 partial sums), so that the k-term sums come
-// out bit-identical to np.sum(..., axis=1).
-template <typename F>
-__device__ __forceinline__ double np_sum(int n, F term) {
+// numpy's pairwise sum (pairwise_sum_DOUBLE / _FLOAT, numpy/_core/src/umath/loops_utils.h.src) of n <= 128 terms
+// term(lo) .. term(lo + n - 1): fewer than 8 added in order, else 8 partial sums, their tree, then the tail.
+template <typename T, typename F>
+__device__ __forceinline__ T np_sum_block(int lo, int n, F term) {
     if (n < 8) {
-        double r = term(0);
-        for (int i = 1; i < n; ++i) r = r + term(i);
+        T r = term(lo);
+        for (int i = 1; i < n; ++i) r = r + term(lo + i);
         return r;
     }
-    double r[8];
+    T r[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = term(j);
+    for (int j = 0; j < 8; ++j) r[j] = term(lo + j);
     int i = 8;
     for (; i < n - (n % 8); i += 8) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = r[j] + term(i + j);
+        for (int j = 0; j < 8; ++j) r[j] = r[j] + term(lo + i + j);
     }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res = res + term(i);
+    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) res = res + term(lo + i);
+    return res;
+}
+
+// np.sum over n terms: above 128 numpy splits at n2 = n/2 - (n/2) % 8 and sums both runs the same way.  One level
+// is exact while both runs stay <= 128 terms (n <= 242); n is a k, at most kScanMaxKK = 192.  The runs are a loop
+// around ONE copy of the block: two inlined copies cost predict_kernel a quarter more registers and its occupancy.
+template <typename T, typename F>
+__device__ __forceinline__ T np_sum(int n, F term) {
+    int n2 = n;
+    if (n > 128) {
+        n2 = n / 2;
+        n2 -= n2 % 8;
+    }
+    T res = 0;
+#pragma nounroll
+    for (int lo = 0; lo < n;) {
+        const int len = lo == 0 ? n2 : n - n2;
+        const T s = np_sum_block<T>(lo, len, term);
+        res = lo == 0 ? s : res + s;
+        lo += len;
+    }
     return res;
 }
 
@@ -1347,6 +1378,8 @@ __device__ __forceinline__ double np_sum_small(int n, const double (&v)[8]) {
 }
 
 #ifdef SKNNR_KERNELS_EXACT
+// k <= 8, the common case.  predict_wide_kernel answers k > 8: a kernel of its own, so that the registers of its
+// pairwise sums do not lower this one's occupancy (one kernel for both: 76 -> 84 VGPRs, C3's predict 19 % slower).
 __global__ void __launch_bounds__(256) predict_kernel(PredictArgs a) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= a.nq * a.t) return;
@@ -1355,10 +1388,10 @@ __global__ void __launch_bounds__(256) predict_kernel(PredictArgs a) {
     const long* ids = a.idx + q * a.k;
     const double* dd = a.dist ? a.dist + q * a.k : nullptr;
     const double* ww = a.w ? a.w + q * a.k : nullptr;
-    if (a.k <= 8) {
-        // The common case: all k indices, then all k target rows (random 8-byte gathers from
-        // L2 / Infinity Cache) and distances are requested before the first use; a loop that waits
-        // for index i, then row i, is bound by 2k memory latencies.  Same summation order as below.
+    {
+        // All k indices, then all k target rows (random 8-byte gathers from L2 / Infinity Cache) and
+        // distances are requested before the first use; a loop that waits for index i, then row i, is
+        // bound by 2k memory latencies.  Same summation order as predict_wide_kernel.
         long id[8];
         double yv[8], wv[8];
 #pragma unroll
@@ -1368,7 +1401,7 @@ __global__ void __launch_bounds__(256) predict_kernel(PredictArgs a) {
             yv[i] = a.y[id[i] * a.t + tt];
             wv[i] = a.mode == 0 ? 1.0 : (a.mode == 2 ? (i < a.k ? ww[i] : 0.0) : (i < a.k ? dd[i] : 1.0));
         }
-        if (a.mode == 0) {
+        if (a.mode == 0 && a.t > 1) {
             double acc = yv[0];
 #pragma unroll
             for (int i = 1; i < 8; ++i)
@@ -1376,6 +1409,7 @@ __global__ void __launch_bounds__(256) predict_kernel(PredictArgs a) {
             a.out[e] = acc / (double)a.k;
             return;
         }
+        // (uniform with t == 1 goes on with weights 1.0: the pairwise sum of y * 1.0 == y over the sum of k ones, k)
         if (a.mode == 1) {
             bool any_zero = false;
 #pragma unroll
@@ -1387,10 +1421,19 @@ __global__ void __launch_bounds__(256) predict_kernel(PredictArgs a) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) nv[i] = yv[i] * wv[i];
         a.out[e] = np_sum_small(a.k, nv) / np_sum_small(a.k, wv);
-        return;
     }
-    if (a.mode == 0) {
-        // np.mean(_y[neigh_ind], axis=1): slices added in order, then one division
+}
+
+__global__ void __launch_bounds__(256) predict_wide_kernel(PredictArgs a) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.nq * a.t) return;
+    const long q = e / a.t;
+    const int tt = (int)(e - q * a.t);
+    const long* ids = a.idx + q * a.k;
+    const double* dd = a.dist ? a.dist + q * a.k : nullptr;
+    const double* ww = a.w ? a.w + q * a.k : nullptr;
+    if (a.mode == 0 && a.t > 1) {
+        // np.mean(_y[neigh_ind], axis=1) of (nq, k, t): the slices in order, then one division
         double acc = a.y[ids[0] * a.t + tt];
         for (int i = 1; i < a.k; ++i) acc = acc + a.y[ids[i] * a.t + tt];
         a.out[e] = acc / (double)a.k;
@@ -1400,13 +1443,46 @@ __global__ void __launch_bounds__(256) predict_kernel(PredictArgs a) {
     if (a.mode == 1)
         for (int i = 0; i < a.k; ++i) any_zero |= (dd[i] == 0.0);
     auto weight = [&](int i) -> double {
+        if (a.mode == 0) return 1.0;
         if (a.mode == 2) return ww[i];
         if (any_zero) return dd[i] == 0.0 ? 1.0 : 0.0;
         return 1.0 / dd[i];
     };
-    const double num = np_sum(a.k, [&](int i) { return a.y[ids[i] * a.t + tt] * weight(i); });
-    const double den = np_sum(a.k, [&](int i) { return weight(i); });
+    const double num = np_sum<double>(a.k, [&](int i) { return a.y[ids[i] * a.t + tt] * weight(i); });
+    const double den = np_sum<double>(a.k, [&](int i) { return weight(i); });
     a.out[e] = num / den;
+}
+
+// The binary32 reductions (a.mode 0 with y32, or 2 with w32).  The float values arrive widened to float64 and are
+// narrowed back exactly; adds and products run in float (round to nearest even, like numpy's float32 loops).  A
+// binary32 quotient is the float64 quotient rounded to float: rounding twice is exact for 53 >= 2 * 24 + 2 bits.
+__global__ void __launch_bounds__(256) predict32_kernel(PredictArgs a) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.nq * a.t) return;
+    const long q = e / a.t;
+    const int tt = (int)(e - q * a.t);
+    const long* ids = a.idx + q * a.k;
+    auto yf = [&](int i) { return (float)a.y[ids[i] * a.t + tt]; };
+    if (a.mode == 0) {
+        float acc;
+        if (a.t == 1) {
+            acc = np_sum<float>(a.k, yf);
+        } else {
+            acc = yf(0);
+            for (int i = 1; i < a.k; ++i) acc = acc + yf(i);
+        }
+        a.out[e] = (double)(float)((double)acc / (double)a.k);
+        return;
+    }
+    const double* ww = a.w + q * a.k;
+    const float den = np_sum<float>(a.k, [&](int i) { return (float)ww[i]; });
+    if (a.y32) {
+        const float num = np_sum<float>(a.k, [&](int i) { return yf(i) * (float)ww[i]; });
+        a.out[e] = (double)(float)((double)num / (double)den);
+        return;
+    }
+    const double num = np_sum<double>(a.k, [&](int i) { return a.y[ids[i] * a.t + tt] * ww[i]; });
+    a.out[e] = num / (double)den;
 }
 #endif  // SKNNR_KERNELS_EXACT
 

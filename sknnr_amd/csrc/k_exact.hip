@@ -124,7 +124,12 @@ hipError_t pack_shards(const double* val, const long* idx, long nq, int n_shards
 
 hipError_t predict(const PredictArgs& a, hipStream_t st) {
     const long total = a.nq * a.t;
-    predict_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(a);
+    if ((a.mode == 0 && a.y32) || (a.mode == 2 && a.w32))
+        predict32_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(a);
+    else if (a.k <= 8)
+        predict_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(a);
+    else
+        predict_wide_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(a);
     return hipGetLastError();
 }
 

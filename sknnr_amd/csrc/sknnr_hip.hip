@@ -1511,8 +1511,9 @@ int validate_call(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_
         if (o->apply_affine && !forest_map) return fail(SKNNR_ERR_INVALID, "node ids are not mapped by an affine transform");
     }
     if (o->n_neighbors + (o->exclude_self ? 1 : 0) > kScanMaxKK)
-        return fail(SKNNR_ERR_UNSUPPORTED, "n_neighbors = %d exceeds the HIP backend's limit of %d", o->n_neighbors,
-                    kScanMaxKK - 1);
+        return fail(SKNNR_ERR_UNSUPPORTED, "n_neighbors = %d exceeds the HIP backend's limit of %d%s", o->n_neighbors,
+                    kScanMaxKK - (o->exclude_self ? 1 : 0),
+                    o->exclude_self ? " with X=None (the query rows' own rows are searched too)" : "");
     if (std::abs(o->decimals) > 300) return fail(SKNNR_ERR_INVALID, "decimals out of range");
     return SKNNR_OK;
 }
@@ -2547,6 +2548,15 @@ extern "C" int sknnr_merge_shards(sknnr_index* ix, const double* q, int64_t nq, 
 // ----------------------------------------------------------------------------------------
 // predict
 // ----------------------------------------------------------------------------------------
+// A weight_mode: one sknnr_weight_mode in the low byte, flag bits above it.  explicit_ok: SKNNR_WEIGHTS_EXPLICIT (and
+// its F32_WEIGHTS flag) allowed.
+static bool weight_mode_ok(int mode, bool explicit_ok) {
+    const int base = mode & SKNNR_WEIGHTS_BASE_MASK, flags = mode & ~SKNNR_WEIGHTS_BASE_MASK;
+    if (flags & ~(SKNNR_WEIGHTS_F32_TARGETS | SKNNR_WEIGHTS_F32_WEIGHTS)) return false;
+    if (base == SKNNR_WEIGHTS_EXPLICIT) return explicit_ok;
+    return (base == SKNNR_WEIGHTS_UNIFORM || base == SKNNR_WEIGHTS_DISTANCE) && !(flags & SKNNR_WEIGHTS_F32_WEIGHTS);
+}
+
 static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, const double* w, long nq, int k,
                           int mode, double* out, hipStream_t st) {
     PredictArgs a{};
@@ -2557,7 +2567,9 @@ static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, 
     a.nq = nq;
     a.k = k;
     a.t = ix->t;
-    a.mode = mode;
+    a.mode = mode & SKNNR_WEIGHTS_BASE_MASK;
+    a.y32 = (mode & SKNNR_WEIGHTS_F32_TARGETS) ? 1 : 0;
+    a.w32 = (mode & SKNNR_WEIGHTS_F32_WEIGHTS) ? 1 : 0;
     a.out = out;
     HIP_TRY(launch::predict(a, st));
     // the reduction may read the handle's staging buffers: it is now the workspace's last user
@@ -2572,9 +2584,13 @@ extern "C" int sknnr_predict_from_neighbors(sknnr_index* ix, const double* dist,
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
     if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
     if (nq < 0 || k < 1 || !idx || !out_pred) return fail(SKNNR_ERR_INVALID, "bad argument");
-    if (mode == SKNNR_WEIGHTS_DISTANCE && !dist) return fail(SKNNR_ERR_INVALID, "distance weights need dist");
-    if (mode == SKNNR_WEIGHTS_EXPLICIT && !w) return fail(SKNNR_ERR_INVALID, "explicit weights need w");
-    if (mode < 0 || mode > 2) return fail(SKNNR_ERR_INVALID, "unknown weight mode %d", mode);
+    if (!weight_mode_ok(mode, true)) return fail(SKNNR_ERR_INVALID, "unknown weight mode %d", mode);
+    if ((mode & SKNNR_WEIGHTS_BASE_MASK) == SKNNR_WEIGHTS_DISTANCE && !dist)
+        return fail(SKNNR_ERR_INVALID, "distance weights need dist");
+    if ((mode & SKNNR_WEIGHTS_BASE_MASK) == SKNNR_WEIGHTS_EXPLICIT && !w)
+        return fail(SKNNR_ERR_INVALID, "explicit weights need w");
+    if (k > kScanMaxKK)  // the reduction follows numpy's pairwise sum up to this many terms
+        return fail(SKNNR_ERR_UNSUPPORTED, "k = %d exceeds the HIP backend's limit of %d", k, kScanMaxKK);
     if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
     if (nq == 0) return SKNNR_OK;
     std::lock_guard<std::mutex> lock(ix->mtx);
@@ -2607,9 +2623,9 @@ extern "C" int sknnr_predict(sknnr_index* ix, const void* q, int64_t nq, const s
     if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
     if (!o) return fail(SKNNR_ERR_INVALID, "opts is NULL");
     if (!out_pred && nq > 0) return fail(SKNNR_ERR_INVALID, "out_pred is NULL");
-    if (o->weight_mode == SKNNR_WEIGHTS_EXPLICIT)
+    if ((o->weight_mode & SKNNR_WEIGHTS_BASE_MASK) == SKNNR_WEIGHTS_EXPLICIT)
         return fail(SKNNR_ERR_INVALID, "explicit weights go through sknnr_predict_from_neighbors");
-    if (o->weight_mode != SKNNR_WEIGHTS_UNIFORM && o->weight_mode != SKNNR_WEIGHTS_DISTANCE)
+    if (!weight_mode_ok(o->weight_mode, false))
         return fail(SKNNR_ERR_INVALID, "unknown weight mode %d", o->weight_mode);
     static int64_t dummy_idx;
     int rc = validate_call(ix, q, nq, o, out_idx ? out_idx : &dummy_idx);
@@ -2663,7 +2679,7 @@ extern "C" int sknnr_stream_begin(sknnr_index* ix, const sknnr_query_opts* o, in
     if (o->exclude_self) return fail(SKNNR_ERR_INVALID, "a stream answers pushed rows: exclude_self is not available");
     if (want_pred) {
         if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
-        if (o->weight_mode != SKNNR_WEIGHTS_UNIFORM && o->weight_mode != SKNNR_WEIGHTS_DISTANCE)
+        if (!weight_mode_ok(o->weight_mode, false))
             return fail(SKNNR_ERR_INVALID, "a stream predicts with uniform or distance weights only");
     }
     std::lock_guard<std::mutex> lock(ix->mtx);

@@ -336,7 +336,7 @@ def test_gbnn_on_synthetic_rows_matches_the_reference(N, O):
     keep = rows_without(len(q), ties)
     assert keep.sum() >= len(q) - 8, ties  # real-valued tree weights: boundary ties are rare
     np.testing.assert_allclose(pred[keep], g["pred"][keep], rtol=1e-5, atol=1e-8)
-    np.testing.assert_allclose(pred, O.predict(y, dist, idx, "uniform"), rtol=1e-12)
+    np.testing.assert_array_equal(pred, O.predict(y, dist, idx, "uniform"))
     dist, idx = ix.kneighbors_host(None, ix.make_opts(5, formula=N.FORMULA_HAMMING, exclude_self=True), nq=len(ref))
     assert_hamming_neighbors_match(idx, dist, g["ref_nn"], g["ref_dist"], ref, ref, w, row_offset_self=0)
     ix.close()

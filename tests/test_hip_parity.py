@@ -283,20 +283,31 @@ def test_errors_follow_the_reference(N):
     ix.close()
 
 
-@pytest.mark.parametrize("weights", ["uniform", "distance", yaimpute_weights])
-@pytest.mark.parametrize("k", [1, 5, 7, 12])
-def test_predict_matches_oracle(N, O, weights, k):
+def _predict_matches_oracle(O, weights, k, t):
     from sknnr_amd._engine import KNNEngine
 
-    x_ref, y, x_q = _synth(1500, 400, 16, t=9, n_dup_queries=16)
+    x_ref, y, x_q = _synth(1500, 400, 16, t=t, n_dup_queries=16)
     eng = KNNEngine(x_ref, y)
     pred = eng.predict(x_q, k, weights)
     od, oi = O.kneighbors(x_ref, x_q, k, "expanded")
-    np.testing.assert_allclose(pred, O.predict(y, od, oi, weights), rtol=1e-12, atol=0)
+    np.testing.assert_array_equal(pred, O.predict(y, od, oi, weights))
     pred = eng.predict(None, k, weights, exclude_self=True)
     od, oi = O.kneighbors(x_ref, None, k, "expanded")
-    np.testing.assert_allclose(pred, O.predict(y, od, oi, weights), rtol=1e-12, atol=0)
+    np.testing.assert_array_equal(pred, O.predict(y, od, oi, weights))
     eng.close()
+
+
+@pytest.mark.parametrize("weights", ["uniform", "distance", yaimpute_weights])
+@pytest.mark.parametrize("k", [1, 5, 7, 12])
+def test_predict_matches_oracle(N, O, weights, k):
+    _predict_matches_oracle(O, weights, k, t=9)
+
+
+@pytest.mark.parametrize("weights", ["uniform", "distance", yaimpute_weights])
+@pytest.mark.parametrize("k", [1, 5, 7, 12])
+def test_predict_matches_oracle_one_target(N, O, weights, k):
+    """t = 1: numpy's pairwise mean over k (the (nq, k, 1) layout), not the sequential one of t >= 2."""
+    _predict_matches_oracle(O, weights, k, t=1)
 
 
 def test_affine_transform_and_fused_query_transform(N, O):
@@ -355,7 +366,7 @@ def test_torch_device_tensors_round_trip(N, O):
     np.testing.assert_array_equal(idx.cpu().numpy(), oi)
     np.testing.assert_array_equal(dist.cpu().numpy(), od)
     pred = eng.predict(xq, 5, "distance")
-    np.testing.assert_allclose(pred.cpu().numpy(), O.predict(y, od, oi, "distance"), rtol=1e-12, atol=0)
+    np.testing.assert_array_equal(pred.cpu().numpy(), O.predict(y, od, oi, "distance"))
     ids = eng.crosswalk(idx, np.arange(3000, dtype=np.int64) + 100000)
     np.testing.assert_array_equal(ids.cpu().numpy(), oi + 100000)
     eng.close()
@@ -449,7 +460,7 @@ def test_host_buffer_pipeline_matches_device_path(N, O):
         od, oi = O.kneighbors(x_ref, xq[a:b], k, "expanded", row_offset=a)
         np.testing.assert_array_equal(idx[a:b], oi)
         np.testing.assert_array_equal(dist[a:b], od)
-        np.testing.assert_allclose(pred[a:b], O.predict(y, od, oi, "distance"), rtol=1e-12, atol=0)
+        np.testing.assert_array_equal(pred[a:b], O.predict(y, od, oi, "distance"))
     ix.close()
     eng.close()
 
