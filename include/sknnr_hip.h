@@ -388,6 +388,20 @@ int sknnr_crosswalk(const int64_t* table, int64_t n_table, const int64_t* idx, i
 int sknnr_debug_coarse_matrix(sknnr_index* index, const double* q, int64_t nq, float* out,
                               double* out_qnorm, double* out_scale, double* out_eps);
 
+/*
+ * Which Euclidean pre-filter launches the most recent call on the handle made (its last device chunk), so that a test
+ * can prove it reached the kernel instance it names.  Host memory, no device work:
+ *   out[0] generation: 0 = no Euclidean pre-filter ran (exact scan only, or Hamming), 1 = coarse_kernel,
+ *          2 = coarse2_kernel
+ *   out[1] K-steps (16 features each)          out[2] list length M
+ *   out[3] rank beyond the list E (0: the list holds kk + 1, with sentinels; always 0 for generation 1)
+ *   out[4] waves per workgroup of the bulk launch (0: no bulk launch)
+ *   out[5] rows given to the bulk launch       out[6] rows given to the 4-wave thin launch (generation 2)
+ *   out[7] cell depth of the bucketed query order (0: plain order)
+ * Every search call zeroes the record first.
+ */
+int sknnr_debug_last_prefilter(const sknnr_index* index, int64_t out[8]);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -81,6 +81,7 @@ EXPORTED_SYMBOLS = (
     "sknnr_stream_end",
     "sknnr_crosswalk",
     "sknnr_debug_coarse_matrix",
+    "sknnr_debug_last_prefilter",
 )
 
 
@@ -192,6 +193,7 @@ def load(build_if_missing: bool = False):
     lib.sknnr_crosswalk.argtypes = [vp, c_int64, vp, c_int64, vp, c_int32, c_int32, vp]
     lib.sknnr_debug_coarse_matrix.argtypes = [vp, vp, c_int64, vp, vp, POINTER(c_double),
                                               POINTER(c_double)]
+    lib.sknnr_debug_last_prefilter.argtypes = [vp, POINTER(c_int64)]
     _lib = lib
     return lib
 
@@ -434,6 +436,16 @@ class Index:
         check(load().sknnr_debug_coarse_matrix(self.handle, _host_ptr(q), nq, _host_ptr(out),
                                                _host_ptr(qn), byref(s), byref(eps)))
         return out, qn, s.value, eps.value
+
+    PREFILTER_FIELDS = ("generation", "ks", "m_list", "rank_extra", "bulk_waves", "bulk_rows", "thin_rows", "cell_depth")
+
+    def debug_last_prefilter(self) -> dict:
+        """The Euclidean pre-filter launches of the last call's last device chunk (sknnr_debug_last_prefilter):
+        generation (0: none, 1: coarse_kernel, 2: coarse2_kernel), K-steps, list length, rank beyond the list, waves of the
+        bulk launch, rows of the bulk and of the 4-wave thin launch, cell depth of the query order (0: plain order)."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_prefilter(self.handle, out))
+        return dict(zip(self.PREFILTER_FIELDS, (int(v) for v in out)))
 
 
 class QueryStream:

@@ -299,6 +299,9 @@ struct sknnr_index {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     long bulk_rows_done = 0;  // rows whose pre-filter was complete at ev_fork (0: no fork in the last launch)
     hipEvent_t ev_bulk_end = nullptr;  // the call record's end-of-pre-filter event; recorded at the fork when there is one
+    // the Euclidean pre-filter launches of the last device chunk of the last call (sknnr_debug_last_prefilter):
+    // generation, KS, list length, rank beyond the list, bulk waves, bulk rows, thin rows, cell depth
+    int64_t last_prefilter[8] = {};
     bool stream_open = false;  // a sknnr_stream owns the host pipeline's slots
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
@@ -1298,6 +1301,8 @@ int launch_coarse(sknnr_index* ix, long nq_pad, int m_list, int kk, hipStream_t 
     if (launch::coarse1(ix->ks, m_list, L, st, &e) == launch::kNoInstance)
         return fail(SKNNR_ERR_UNSUPPORTED, "no coarse kernel for ks = %d, list length %d", ix->ks, m_list);
     HIP_TRY(e);
+    int64_t* r = ix->last_prefilter;
+    r[0] = 1, r[1] = ix->ks, r[2] = m_list, r[3] = 0, r[4] = coarse_waves(ix->ks, m_list), r[5] = nq_pad;
     return SKNNR_OK;
 }
 
@@ -1320,6 +1325,14 @@ int launch_coarse2_waves(sknnr_index* ix, int m_list, int waves, long row0, long
         return fail(SKNNR_ERR_UNSUPPORTED, "no second-generation coarse kernel for ks = %d, list length %d, %d waves, rank + %d", ix->ks,
                     m_list, waves, extra);
     HIP_TRY(e);
+    int64_t* r = ix->last_prefilter;
+    r[0] = 2, r[1] = ix->ks, r[2] = m_list, r[3] = extra;
+    if (waves == kCoarse2TailWaves) {
+        r[6] += rows;
+    } else {
+        r[4] = waves;
+        r[5] += rows;
+    }
     return SKNNR_OK;
 }
 
@@ -1525,6 +1538,7 @@ int run_forest(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
                hipStream_t st);
 int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opts* o, double* d_dist,
                long* d_idx, hipStream_t st, int raw = 0, long id_offset = 0) {
+    std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);
     if (xdev && uses_forest(ix, o)) return run_forest(ix, xdev, nq, o, d_dist, d_idx, st);
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
     const bool affine = o->apply_affine != 0 && xdev != nullptr;
@@ -1655,6 +1669,8 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
         }
         ix->bulk_rows_done = 0;
         ix->ev_bulk_end = ev.second;
+        std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);  // (this chunk's launches only)
+        ix->last_prefilter[7] = bucketed ? ix->cell_depth : 0;
         {
             // matrix work issued / algorithmic (rows of the launch cancel): K-steps x tiles swept over d x n_ref
             const long tiles = v2 ? (long)ix->n_stages2 * tiles_per_stage2(ix->ks) +
@@ -2446,6 +2462,7 @@ int merge_shards_formula(sknnr_index* ix, const SelectArgs& call, int n_shards, 
 // Device-resident core of sknnr_merge_shards.
 int merge_shards_device(sknnr_index* ix, const double* xdev, long nq, const sknnr_query_opts* o, int n_shards,
                         const double* shard_val, const long* shard_idx, double* d_dist, long* d_idx, hipStream_t st) {
+    std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);  // (no pre-filter runs on this path)
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
     const bool affine = o->apply_affine != 0 && xdev != nullptr;
     const bool self_rows = xdev == nullptr;
@@ -2793,5 +2810,13 @@ extern "C" int sknnr_debug_coarse_matrix(sknnr_index* ix, const double* q, int64
     if (e != hipSuccess) return fail(SKNNR_ERR_HIP, "debug matrix failed: %s", hipGetErrorString(e));
     if (out_scale) *out_scale = ix->s;
     if (out_eps) *out_eps = eps_units(ix->ks) * std::ldexp(1.0, -24);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_prefilter(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::copy(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), out);
     return SKNNR_OK;
 }

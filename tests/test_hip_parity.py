@@ -164,9 +164,11 @@ def test_larger_k(N, O, k):
 @pytest.mark.parametrize("d", [20, 40, 64, 72, 96, 112, 128])   # 16-wide K-steps 2..8: light / medium / heavy geometries
 @pytest.mark.parametrize("k", [2, 6, 10, 20])                    # list lengths 6, 8, 16, 32
 def test_every_launch_geometry(N, O, d, k):
-    """Each (feature width, list length) pair selects its own workgroup shape, q-blocks per wave, LDS
-    stage size and insertion code (coarse.hip.h, launch geometry): targets and the X=None self query
-    must equal the oracle for all of them."""
+    """Each (feature width, list length) pair of the FIRST-generation pre-filter selects its own workgroup
+    shape, q-blocks per wave, LDS stage size and insertion code (coarse.hip.h, launch geometry): targets and
+    the X=None self query must equal the oracle for all of them.  2,600 reference rows are below the
+    second-generation kernel's minimum (use_coarse2), so every case here runs coarse_kernel; the
+    coarse2_kernel instances are pinned in tests/test_prefilter_instances_gpu.py."""
     x_ref, y, x_q = _synth(2600, 1100, d, n_dup_refs=12, n_dup_queries=8)
     ix = N.Index(x_ref, y)
     dist, idx = ix.kneighbors_host(x_q, ix.make_opts(k))
