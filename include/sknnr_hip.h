@@ -402,6 +402,30 @@ int sknnr_debug_coarse_matrix(sknnr_index* index, const double* q, int64_t nq, f
  */
 int sknnr_debug_last_prefilter(const sknnr_index* index, int64_t out[8]);
 
+/*
+ * Debug only.  The integer pre-filter of the weighted-Hamming search (formula HAMMING) that the most recent call on the
+ * handle ran, so that a test can prove which path served it:
+ *   out[0] 1 = the integer pre-filter ran, 0 = it did not (every row went to the float64 exact scan; then out[1 .. 7] = 0)
+ *   out[1] kk, the neighbours searched (k, + 1 for X=None)
+ *   out[2] 1 = the candidate lists are seeded and compacted (kk >= 8)
+ *   out[3] rows of the seeding pass (0 without compaction)
+ *   out[4] band, in 16-bit weight units (trees + 2)
+ *   out[5] tree pairs                          out[6] device chunks of the call (2^18 rows each)
+ *   out[7] rows the integer path handed to the exact scan over the whole call (read from the device, synchronously)
+ * Every search call zeroes the record first.  Under the forest map (sknnr_index_set_forest) a call runs in forest chunks
+ * and the record describes the last of them.
+ */
+int sknnr_debug_last_hamming(const sknnr_index* index, int64_t out[8]);
+
+/*
+ * Debug only.  The candidate lists the integer Hamming pre-filter wrote for the first n rows of the last device chunk of
+ * the most recent call (n at most that chunk's rows; SKNNR_ERR_INVALID when the pre-filter did not run).  Host memory:
+ *   cnt (n)       candidates per row, -1 = the row went to the exact scan (list overflow, or ids outside 16 bits)
+ *   ids (n, 192)  row i's candidates in ascending order in ids[192 i .. 192 i + cnt[i] - 1]; the other slots are stale
+ * Synchronises the device.
+ */
+int sknnr_debug_hamming_candidates(const sknnr_index* index, int32_t* cnt, int32_t* ids, int64_t n);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

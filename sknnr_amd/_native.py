@@ -82,6 +82,8 @@ EXPORTED_SYMBOLS = (
     "sknnr_crosswalk",
     "sknnr_debug_coarse_matrix",
     "sknnr_debug_last_prefilter",
+    "sknnr_debug_last_hamming",
+    "sknnr_debug_hamming_candidates",
 )
 
 
@@ -194,6 +196,8 @@ def load(build_if_missing: bool = False):
     lib.sknnr_debug_coarse_matrix.argtypes = [vp, vp, c_int64, vp, vp, POINTER(c_double),
                                               POINTER(c_double)]
     lib.sknnr_debug_last_prefilter.argtypes = [vp, POINTER(c_int64)]
+    lib.sknnr_debug_last_hamming.argtypes = [vp, POINTER(c_int64)]
+    lib.sknnr_debug_hamming_candidates.argtypes = [vp, vp, vp, c_int64]
     _lib = lib
     return lib
 
@@ -446,6 +450,24 @@ class Index:
         out = (c_int64 * 8)()
         check(load().sknnr_debug_last_prefilter(self.handle, out))
         return dict(zip(self.PREFILTER_FIELDS, (int(v) for v in out)))
+
+    HAMMING_FIELDS = ("ran", "kk", "compacts", "seed_rows", "band", "tree_pairs", "chunks", "handed_to_scan")
+
+    def debug_last_hamming(self) -> dict:
+        """Debug only: the integer Hamming pre-filter of the last call (sknnr_debug_last_hamming): whether it ran, kk,
+        compaction on, rows of the seeding pass, band, tree pairs, device chunks, and the rows it handed to the exact scan
+        over the call (all zero when it did not run).  Under the forest map: the last forest chunk."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_hamming(self.handle, out))
+        return dict(zip(self.HAMMING_FIELDS, (int(v) for v in out)))
+
+    def debug_hamming_candidates(self, n: int):
+        """Debug only: ``(cnt, ids)`` the integer Hamming pre-filter wrote for the first ``n`` rows of the last call's last
+        device chunk (sknnr_debug_hamming_candidates); ``ids`` is ``(n, 192)``, row i's candidates in ``ids[i, :cnt[i]]``."""
+        cnt = np.empty(n, dtype=np.int32)
+        ids = np.empty((n, 192), dtype=np.int32)
+        check(load().sknnr_debug_hamming_candidates(self.handle, _host_ptr(cnt), _host_ptr(ids), int(n)))
+        return cnt, ids
 
 
 class QueryStream:

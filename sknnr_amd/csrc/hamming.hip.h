@@ -17,7 +17,8 @@
 //                               (distance, index) exactly as exact_scan_kernel<2> does it over all rows, post-steps.
 //
 // Exactness: |D^ - S sum_t w_t [.]| <= T / 2 (rounding of the weights), the float64 evaluation of the true sum is
-// off by less than 2^-40 of a weight unit; so D^_a + band < D^_b with band = T + 2 implies d_a < d_b in the reference's
+// off by at most about T^2 2^-53 65535 weight units (1e-4 at the largest T served, 3,584); so D^_a + band < D^_b with
+// band = T + 2 implies d_a < d_b in the reference's
 // arithmetic, and a row that is NOT within band of the kk-th smallest D^ has kk rows strictly closer than itself:
 // the kk nearest by (distance, index) are always among the candidates.  A query with more candidates than the list
 // holds, or with an id that is not a 16-bit integer, goes to exact_scan_kernel<2> (fail list), as uncertified rows do
@@ -103,6 +104,15 @@ __device__ __forceinline__ void ham_sload(u32x16& q, uint32_t& w, const uint32_t
 // many neighbours: the candidate lists are seeded and compacted (hamming_coarse_kernel), which takes 12 KB more LDS
 __host__ __device__ constexpr bool ham_compacts(int kk) { return kk >= 8; }
 __host__ __device__ constexpr size_t hamming_coarse_lds(int kk) { return ham_compacts(kk) ? (size_t)16 * 192 * sizeof(unsigned) : 0; }
+// rows of the seeding pass (see hamming_coarse_kernel): n_ref / 16 in whole 256-row steps, at least one step and at most
+// 4,096 rows, never more than the reference set; 0 when the lists are not compacted
+__host__ __device__ constexpr int ham_seed_rows(int n_ref, int kk) {
+    if (!ham_compacts(kk)) return 0;
+    int rows = n_ref / 16;
+    rows = rows > 4096 ? 4096 : (rows < 256 ? 256 : rows);
+    rows = rows / 256 * 256;
+    return rows < n_ref ? rows : n_ref;
+}
 
 struct HammingArgs {
     const uint32_t* rimg;   // [tp][n_ref_pad] two 16-bit ids per dword
@@ -166,7 +176,7 @@ __global__ void __launch_bounds__(kHamWaves * 64) hamming_coarse_kernel(HammingA
     // filled up in the first few hundred rows whatever its length (kk = 16: a fifth of the queries, kk = 32: nearly all fell
     // to the float64 scan).  A first pass over a prefix of the rows only ranks (no candidates): its kk-th smallest value
     // bounds the final one from above, and the real sweep starts with it.
-    const int seed_rows = compacts ? min(a.n_ref, max(256, min(4096, a.n_ref / 16)) / 256 * 256) : 0;
+    const int seed_rows = ham_seed_rows(a.n_ref, KK);
     const uint32_t* qbase = a.qimg + q0;  // + p * nq_pad: 16 consecutive dwords, workgroup-uniform
     uint32_t ones = 0x00010001u;
     asm volatile("" : "+v"(ones));  // (a vector register, loaded once)
@@ -422,7 +432,7 @@ __global__ void __launch_bounds__(256) hamming_rescore_kernel(HammingRescoreArgs
         return;
     }
     // this lane's eight trees of every chunk of the query, as four dwords of 16-bit ids
-    constexpr int kMaxChunks = 8;  // 4,096 trees
+    constexpr int kMaxChunks = 8;  // room for 4,096 trees; the LDS bound of hamming_rescore_lds serves at most 3,584 (7 chunks)
     uint4 qv[kMaxChunks];
     const double* x = s.xq + q * T;
 #pragma unroll

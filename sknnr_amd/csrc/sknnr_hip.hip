@@ -302,6 +302,11 @@ struct sknnr_index {
     // the Euclidean pre-filter launches of the last device chunk of the last call (sknnr_debug_last_prefilter):
     // generation, KS, list length, rank beyond the list, bulk waves, bulk rows, thin rows, cell depth
     int64_t last_prefilter[8] = {};
+    // the integer Hamming pre-filter of the last call (sknnr_debug_last_hamming): ran, kk, compacts, seed rows, band,
+    // tree pairs, device chunks (out[7], the rows handed to the exact scan, is read from fail_count when asked); rows of
+    // its last device chunk, whose candidate lists h_cand_cnt / h_cand_id still hold (sknnr_debug_hamming_candidates)
+    int64_t last_hamming[8] = {};
+    long last_hamming_rows = 0;
     bool stream_open = false;  // a sknnr_stream owns the host pipeline's slots
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
@@ -1008,7 +1013,9 @@ extern "C" int sknnr_index_set_hamming_weights(sknnr_index* ix, const double* w,
         for (int i = 0; i < n; ++i) wmax = std::max(wmax, w[i]);
         std::vector<uint32_t> wq((size_t)tp, 0u);
         for (int i = 0; i < n; ++i) {
-            const uint32_t q16 = (uint32_t)std::min(65535.0, std::floor(w[i] * (65535.0 / wmax) + 0.5));
+            // (w / wmax first: it is in [0, 1] for any weights, where 65535 / wmax overflows to inf once
+            //  wmax < 65535 / DBL_MAX and every weight, zeros included (0 inf = NaN), came out as 65535)
+            const uint32_t q16 = (uint32_t)std::min(65535.0, std::floor(w[i] / wmax * 65535.0 + 0.5));
             wq[(size_t)i / 2] |= q16 << (16 * (i & 1));
         }
         HIP_TRY(ix->h_wq.ensure((size_t)tp));
@@ -1034,7 +1041,9 @@ extern "C" int sknnr_index_set_hamming_weights(sknnr_index* ix, const double* w,
         }
         ix->h_tp = tp;
         ix->h_ref_pad = ref_pad;
-        ix->h16_ok = !any_bad && rows_ok;  // (more than 4,096 trees: the float64 scan)
+        // (more than 3,584 trees: the float64 scan -- the re-score's dynamic LDS, 16 ceil(T / 2) + 16,384 ceil(T / 512)
+        //  bytes, passes 150 KiB at T = 3,585; the 4,096 above is the re-score's register image, never the binding limit)
+        ix->h16_ok = !any_bad && rows_ok;
     }
     return SKNNR_OK;
 }
@@ -1539,6 +1548,8 @@ int run_forest(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
 int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opts* o, double* d_dist,
                long* d_idx, hipStream_t st, int raw = 0, long id_offset = 0) {
     std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);
+    std::fill(std::begin(ix->last_hamming), std::end(ix->last_hamming), 0);
+    ix->last_hamming_rows = 0;
     if (xdev && uses_forest(ix, o)) return run_forest(ix, xdev, nq, o, d_dist, d_idx, st);
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
     const bool affine = o->apply_affine != 0 && xdev != nullptr;
@@ -1758,8 +1769,12 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
         HIP_TRY(ix->h_cand_id.ensure((size_t)cap_q * kHamCand));
         HIP_TRY(ix->fail_list.ensure(nq));
         HIP_TRY(hipMemsetAsync(ix->fail_count.p, 0, 16, st));
+        const int64_t rec[7] = {1, kk, ham_compacts(kk) ? 1 : 0, ham_seed_rows((int)ix->n_ref, kk), (int64_t)ix->d + 2,
+                                ix->h_tp, (nq + chunk_q - 1) / chunk_q};
+        std::copy(std::begin(rec), std::end(rec), ix->last_hamming);
         for (long c0 = 0; c0 < nq; c0 += chunk_q) {
             const long n = std::min(chunk_q, nq - c0);
+            ix->last_hamming_rows = n;
             const long n_pad = (n + 255) / 256 * 256;
             HIP_TRY(launch::hamming_pack(xq_call + c0 * ix->d, n, n_pad, ix->d, ix->h_tp, ix->h_qimg.p, ix->h_bad.p, st));
             HammingArgs ha{};
@@ -2509,6 +2524,8 @@ int merge_shards_device(sknnr_index* ix, const double* xdev, long nq, const sknn
     HIP_TRY(ix->slice_i.ensure(heaps));
     HIP_TRY(ix->fail_list2.ensure((size_t)nq));
     HIP_TRY(hipMemsetAsync(ix->fail_count.p, 0, 16, st));
+    std::fill(std::begin(ix->last_hamming), std::end(ix->last_hamming), 0);  // (fail_count no longer holds its count)
+    ix->last_hamming_rows = 0;
     HIP_TRY(launch::pack_shards(shard_val, shard_idx, nq, n_shards, kk, ix->slice_v.p, ix->slice_i.p, st));
     int rc = merge_shards_formula(ix, call, n_shards, nq, st);
     if (rc) return rc;
@@ -2818,5 +2835,37 @@ extern "C" int sknnr_debug_last_prefilter(const sknnr_index* cix, int64_t out[8]
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
     std::copy(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), out);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_hamming(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::copy(std::begin(ix->last_hamming), std::end(ix->last_hamming), out);
+    out[7] = 0;
+    if (ix->last_hamming[0]) {
+        // the rows hamming_rescore_kernel put on the fail list, over every device chunk of the call (the workspace is the
+        // handle's: no later call has touched it, or the record would be zero)
+        int n_fail = 0;
+        HIP_TRY(hipSetDevice(ix->device));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(&n_fail, ix->fail_count.p, sizeof n_fail, hipMemcpyDeviceToHost));
+        out[7] = n_fail;
+    }
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_hamming_candidates(const sknnr_index* cix, int32_t* cnt, int32_t* ids, int64_t n) {
+    if (!cix || !cnt || !ids) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (!ix->last_hamming[0]) return fail(SKNNR_ERR_INVALID, "the last call did not run the integer Hamming pre-filter");
+    if (n < 0 || n > ix->last_hamming_rows)
+        return fail(SKNNR_ERR_INVALID, "n = %ld rows, the last device chunk has %ld", (long)n, ix->last_hamming_rows);
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(cnt, ix->h_cand_cnt.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ids, ix->h_cand_id.p, (size_t)n * kHamCand * sizeof(int32_t), hipMemcpyDeviceToHost));
     return SKNNR_OK;
 }
