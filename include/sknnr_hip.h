@@ -403,6 +403,18 @@ int sknnr_debug_coarse_matrix(sknnr_index* index, const double* q, int64_t nq, f
 int sknnr_debug_last_prefilter(const sknnr_index* index, int64_t out[8]);
 
 /*
+ * Debug only.  The finaliser launches of the most recent call on the handle (its last device chunk), so that a test can
+ * prove which finaliser served it:
+ *   out[0] lanes per query (0: no finaliser ran; 8: finalize_record_kernel; 16 / 32 / 64: finalize_kernel on lists)
+ *   out[1] 1 = the pre-filter filed merged candidate records and finalize_record_kernel read them, 0 = raw lists
+ *   out[2] rows the record's truncation rule (its last entry inside the re-score window) handed to the exact scan over
+ *          the whole call (read from the device, synchronously; 0 without records)
+ *   out[3] 0 (reserved)
+ * Every search call zeroes the record first.
+ */
+int sknnr_debug_last_finalize(const sknnr_index* index, int64_t out[4]);
+
+/*
  * Debug only.  The integer pre-filter of the weighted-Hamming search (formula HAMMING) that the most recent call on the
  * handle ran, so that a test can prove which path served it:
  *   out[0] 1 = the integer pre-filter ran, 0 = it did not (every row went to the float64 exact scan; then out[1 .. 7] = 0)

@@ -82,6 +82,7 @@ EXPORTED_SYMBOLS = (
     "sknnr_crosswalk",
     "sknnr_debug_coarse_matrix",
     "sknnr_debug_last_prefilter",
+    "sknnr_debug_last_finalize",
     "sknnr_debug_last_hamming",
     "sknnr_debug_hamming_candidates",
 )
@@ -196,6 +197,8 @@ def load(build_if_missing: bool = False):
     lib.sknnr_debug_coarse_matrix.argtypes = [vp, vp, c_int64, vp, vp, POINTER(c_double),
                                               POINTER(c_double)]
     lib.sknnr_debug_last_prefilter.argtypes = [vp, POINTER(c_int64)]
+    if hasattr(lib, "sknnr_debug_last_finalize"):  # (a SKNNR_HIP_LIBRARY variant built before the entry point existed)
+        lib.sknnr_debug_last_finalize.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_last_hamming.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_hamming_candidates.argtypes = [vp, vp, vp, c_int64]
     _lib = lib
@@ -450,6 +453,16 @@ class Index:
         out = (c_int64 * 8)()
         check(load().sknnr_debug_last_prefilter(self.handle, out))
         return dict(zip(self.PREFILTER_FIELDS, (int(v) for v in out)))
+
+    FINALIZE_FIELDS = ("lanes_per_query", "record", "truncated_rows", "reserved")
+
+    def debug_last_finalize(self) -> dict:
+        """Debug only: the finaliser of the last call's last device chunk (sknnr_debug_last_finalize): lanes per query
+        (8: finalize_record_kernel, 16 / 32 / 64: finalize_kernel, 0: none), whether merged candidate records were used, and
+        the rows their truncation rule handed to the exact scan over the call."""
+        out = (c_int64 * 4)()
+        check(load().sknnr_debug_last_finalize(self.handle, out))
+        return dict(zip(self.FINALIZE_FIELDS, (int(v) for v in out)))
 
     HAMMING_FIELDS = ("ran", "kk", "compacts", "seed_rows", "band", "tree_pairs", "chunks", "handed_to_scan")
 

@@ -58,6 +58,8 @@ struct CellArgs {
     unsigned char* cell;   // (n_pad) out: cell of every row (padding rows: the last cell)
     int* hist;             // [kCellMax] rows per cell (zeroed by the caller), then [kCellMax] cursors
     int* perm;             // (n_pad) out: position -> row
+    const double* qnc;     // (n_pad) |q'|^2 by row, or null
+    double* qnc_pos;       // (n_pad) out: |q'|^2 by position (finalize_record_kernel reads it beside perm, not behind it)
 };
 
 // Cell of every row, for calls whose rows no prep kernel has classified (prep_queries_direct_kernel does it on the
@@ -138,6 +140,7 @@ __global__ void __launch_bounds__(kBucketBlock) cell_scatter_kernel(CellArgs a) 
             ticket[r] = atomicAdd(&cnt[c[r]], 1);
         } else if (q < a.n_pad) {
             a.perm[q] = (int)q;  // padding rows keep their place behind the live ones
+            if (a.qnc_pos) a.qnc_pos[q] = a.qnc[q];
             a.cell[q] = (unsigned char)(n_cells - 1);
         }
     }
@@ -147,7 +150,11 @@ __global__ void __launch_bounds__(kBucketBlock) cell_scatter_kernel(CellArgs a) 
 #pragma unroll
     for (int r = 0; r < kBucketChunks; ++r) {
         const long q = ((long)blockIdx.x * kBucketChunks + r) * kBucketBlock + threadIdx.x;
-        if (q < a.nq) a.perm[first[c[r]] + base[c[r]] + ticket[r]] = (int)q;
+        if (q < a.nq) {
+            const int p = first[c[r]] + base[c[r]] + ticket[r];
+            a.perm[p] = (int)q;
+            if (a.qnc_pos) a.qnc_pos[p] = a.qnc[q];  // (the read is coalesced: the thread's own row)
+        }
     }
 }
 #endif  // SKNNR_KERNELS_EXACT

@@ -291,6 +291,9 @@ __device__ __forceinline__ void take_hit(float v, int id, float (&vals)[M], int 
     }
 }
 
+// entries of a merged candidate record (coarse2.hip.h, Coarse2Record) = lanes per query of finalize_record_kernel (exact.hip.h)
+constexpr int kRecordLen = 8;
+
 // The M-th smallest entry of the union of the two sorted M-lists owned by lanes l and l+32
 // (the two lanes that share a query): max_i min(a_i, b_{M-1-i}).  Both lanes get the same value.
 template <int M>

@@ -231,6 +231,30 @@ __device__ __forceinline__ void tile_issue_and_test(floatx16& a, floatx16& c, co
         asm volatile("v_mfma_f32_32x32x16_f16 %[c], %[h], %[q], %[c]\n\t" : [c] "+v"(c) : [h] "v"(ah[s]), [q] "v"(q[s]));
 }
 
+// Merged candidate record (round 7): where a query's two lists hold no more than kRecordLen candidates that matter
+// (kk + 1 <= kRecordLen; the instances of coarse2_record_supported below), the epilogue can file, instead of the two raw lists, the
+// kRecordLen smallest VALID entries of their union, ascending by (value, list, slot), each with its reference ROW id
+// (position -> row looked up here), and the bound pair_union_rank<M, E> of the final lists as one float (NaN: poisoned
+// query).  finalize_record_kernel (exact.hip.h) then spends kRecordLen lanes per query instead of 16 and has no
+// position -> row gather in its chain.  An entry is 8 bytes: value bits low, row id high; unused slots hold
+// (+inf, -1).  Filed by position, like the lists.  entry == nullptr: the raw lists are written.  (kRecordLen: coarse.hip.h)
+struct Coarse2Record {
+    unsigned long long* entry;  // [position][kRecordLen]
+    float* bound;               // [position]
+    const int* perm;            // image position -> reference row
+    int n_ref;
+};
+// Lists of 2 and 6 at up to two K-steps only (profiles/r07_finalize_record.txt).  At three and four K-steps the instances
+// already spill in the sweep and the extra epilogue moved their register allocation (C4, 64 features: pre-filter
+// 65.4 -> 83.4 ms).  Lists of 8 with sentinels serve 6 .. 7 neighbours: at 7 the record's last entry IS the kk + 1-th
+// candidate, the truncation rule fires whenever it lies inside the window, and the exact scan ate the gain (C3, k = 7:
+// 12,043 -> 23,386 fall-backs per 10M rows, 183 -> 178 Mq/s); the branch also took those instances from 0 / 28 to 28 / 60
+// bytes of scratch.  Without the record branch all of these compile as before.
+constexpr int kRecordMaxList = 6;
+__host__ __device__ constexpr bool coarse2_record_supported(int ks, int m, int rank_extra) {
+    return ks <= 2 && m <= kRecordMaxList && rank_extra == 0;
+}
+
 // WAVES = 16 (one workgroup of 1024 query rows per CU) for the bulk of a call; WAVES = 4 (256 rows) for the rows of a
 // last, thinly filled round of workgroups and for small calls: spread over four times as many CUs with one wave per
 // SIMD, where a wave no longer shares its matrix pipe (host side: launch_coarse2_ks).
@@ -249,7 +273,8 @@ coarse2_kernel(const char* __restrict__ rhi,    // n_stages * TPS records [hi: K
                // Query bucketing (bucket.hip.h): the kernel works on POSITIONS pos0 .. of the chunk; position p holds row
                // qperm[p] (null: the row itself).  A workgroup starts its sweep at the stage its middle row's cell names.
                int pos0, const int* __restrict__ qperm, const unsigned char* __restrict__ qcell,
-               const int* __restrict__ cell_stage) {
+               const int* __restrict__ cell_stage,
+               Coarse2Record rec) {  // rec.entry != nullptr (coarse2_record_supported only): merged records instead of lists
     constexpr int TPS = tiles_per_stage2(KS);
     constexpr int TB = tile2_bytes(KS);
     constexpr int STAGE = TPS * TB;
@@ -588,8 +613,67 @@ coarse2_kernel(const char* __restrict__ rhi,    // n_stages * TPS records [hi: K
         for (int i = 0; i < 16; ++i) atomicAdd(&coarse_counters[i], (unsigned long long)ctr[i]);
 #endif
     TSTAMP(0);
+    bool filed = false;
+    if constexpr (coarse2_record_supported(KS, M, E)) {
+        if (rec.entry) {  // (workgroup-uniform) merged candidate records instead of the lists
+            filed = true;
+            // Both q-blocks are flushed first, so that the position -> row gathers of all their entries are one round of
+            // independent loads.  A q-block's queue region is free after its last flush: it takes the block's record
+            // image, [column][slot] 8-byte entries -- pre-filled with sentinels, then every lane drops its valid entries
+            // at their rank in the union (DS operations of a wave execute in order) -- which goes out as four coalesced
+            // 512-byte stores.
+            static_assert(kQueueCap * 512 >= 32 * kRecordLen * 8, "the record image fits the queue region");
 #pragma unroll
-    for (int qb = 0; qb < NQB; ++qb) {
+            for (int qb = 0; qb < NQB; ++qb) flush_wave(qb);
+            int slot_of[NQB][M], row_of[NQB][M];  // rank in the union (kRecordLen: not filed), reference row
+#pragma unroll
+            for (int qb = 0; qb < NQB; ++qb) {
+                bool ok[M];
+                float pv[M];  // the partner's entries, NaN where they are not valid (no comparison holds)
+#pragma unroll
+                for (int i = 0; i < M; ++i) {
+                    ok[i] = idxs[qb][i] >= 0 && idxs[qb][i] < rec.n_ref;
+                    pv[i] = __shfl_xor(ok[i] ? vals[qb][i] : __builtin_nanf(""), 32, 64);
+                }
+                int ahead = 0;  // valid entries of this list before slot i
+#pragma unroll
+                for (int i = 0; i < M; ++i) {
+                    const float v = vals[qb][i];
+                    int r = ahead;  // rank by (value, list, slot): list 0 goes first among equal values
+#pragma unroll
+                    for (int j = 0; j < M; ++j) r += (half == 0 ? pv[j] < v : pv[j] <= v) ? 1 : 0;
+                    const bool file = ok[i] && r < kRecordLen;
+                    slot_of[qb][i] = file ? r : kRecordLen;
+                    row_of[qb][i] = file ? rec.perm[idxs[qb][i]] : -1;
+                    ahead += ok[i] ? 1 : 0;
+                }
+            }
+#pragma unroll
+            for (int qb = 0; qb < NQB; ++qb) {
+                const unsigned rimg = qwave + (unsigned)qb * (kQueueCap * 512u);  // this lane's 8 bytes of every 512
+                const unsigned rcol = rimg - (unsigned)lane * 8u + (unsigned)(lane & 31) * (kRecordLen * 8u);
+                const unsigned long long none = 0xffffffff7f800000ull;  // (+inf, -1)
+#pragma unroll
+                for (int j = 0; j < kRecordLen / 2; ++j)
+                    asm volatile("ds_write_b64 %0, %1" ::"v"(rcol + (unsigned)(half * (kRecordLen / 2) + j) * 8u), "v"(none) : "memory");
+#pragma unroll
+                for (int i = 0; i < M; ++i)
+                    if (slot_of[qb][i] < kRecordLen) queue_store(rcol + (unsigned)slot_of[qb][i] * 8u, vals[qb][i], row_of[qb][i]);
+                const size_t q0 = (size_t)(pos0 + (qb0 + qb) * 32);  // position of column 0
+                unsigned long long* out = rec.entry + q0 * kRecordLen + lane;
+#pragma unroll
+                for (int t = 0; t < 32 * kRecordLen / 64; ++t) out[t * 64] = queue_load(rimg + (unsigned)t * 512u);
+                // the bound the finaliser would recompute from the raw lists: the last threshold update's own expression;
+                // a poisoned query (dropped hits) must fail the certificate: a NaN bound never certifies
+                const float u = pair_union_rank<M, E>(vals[qb]);
+                const int mine = loose[qb] != loose[qb] ? 1 : 0;
+                const bool bad = (mine | __shfl_xor(mine, 32, 64)) != 0;
+                if (half == 0) rec.bound[q0 + lane] = bad ? __builtin_nanf("") : u;
+            }
+        }
+    }
+#pragma unroll
+    for (int qb = 0; qb < NQB && !filed; ++qb) {
         flush_wave(qb);
         // (the lists are filed under the POSITION of the chunk -- the row itself unless the call is bucketed: consecutive lanes
         //  write consecutive lists, and the finaliser reads them without waiting for the position -> row table, round 4)

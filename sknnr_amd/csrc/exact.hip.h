@@ -461,6 +461,12 @@ struct FinalizeArgs {
     // holds row qperm[p] of the chunk; every per-row array is then indexed by that row.  Null: position = row.
     const int* qperm;
     long pos0;
+    // Merged candidate records (coarse2.hip.h, Coarse2Record; finalize_record_kernel): filed by position like the lists.
+    // Null: the two raw lists above.
+    const unsigned long long* rec;  // [position][kRecordLen]: value bits low, reference row high; (+inf, -1) = none
+    const float* rec_bound;         // [position] the bound t_min (pair_union_rank of the final lists), NaN = poisoned
+    const double* qnc_pos;          // [position] |q'|^2 (cell_scatter_kernel; plain order: qnc itself)
+    int* trunc_count;               // rows the truncation rule sent to the exact scan
 };
 
 // Lane exchange inside the group of LPQ lanes that share a query.  A group is LPQ/16 DPP rows:
@@ -469,8 +475,26 @@ struct FinalizeArgs {
 // a VALU move with no LDS traffic and no wait.  N = 1 .. LPQ-1 visits every other lane of the group
 // exactly once; only the multiset of peers matters to the callers, which send the peer's lane
 // number along the same way when they need it.
+// LPQ = 8 (finalize_record_kernel): the row rotation does not close over 8 lanes; peer N is lane ^ N instead, DPP moves
+// only -- quad_perm for N = 1 .. 3, and for N = 4 .. 7 the same three (and the identity) applied to the half-row mirror
+// (lane ^ 7) of the value.
+constexpr int kDppQuadXor[4] = {0xE4, 0xB1, 0x4E, 0x1B};  // quad_perm [0,1,2,3], [1,0,3,2], [2,3,0,1], [3,2,1,0]
+constexpr int kDppRowHalfMirror = 0x141;
+__device__ __forceinline__ int half_mirror8(int v) { return __builtin_amdgcn_update_dpp(0, v, kDppRowHalfMirror, 0xf, 0xf, false); }
+template <int N>
+__device__ __forceinline__ int peer8_i(int v, int mirror) {
+    static_assert(N >= 1 && N < 8, "a peer of an 8-lane group");
+    if constexpr (N < 4) {
+        return __builtin_amdgcn_update_dpp(0, v, kDppQuadXor[N], 0xf, 0xf, false);
+    } else if constexpr (N < 7) {
+        return __builtin_amdgcn_update_dpp(0, mirror, kDppQuadXor[7 - N], 0xf, 0xf, false);
+    } else {
+        return mirror;
+    }
+}
 template <int LPQ, int N>
 __device__ __forceinline__ int peer_i(int v, int c) {
+    if constexpr (LPQ == 8) return peer8_i<N>(v, half_mirror8(v));
     constexpr int B = N / 16, R = N % 16;
     const int vb = B ? __shfl_xor(v, 16 * B, LPQ) : v;
     if constexpr (R != 0) {
@@ -497,14 +521,16 @@ __device__ __forceinline__ double peer_d(double v, int c) {
 // block, fetched once), from which peer N = 16 b + r is a DPP rotation of copy b.
 template <int LPQ>
 struct PeersI {
-    int blk[LPQ / 16];
+    int blk[LPQ == 8 ? 2 : LPQ / 16];  // (LPQ = 8: the value and its half-row mirror)
     __device__ __forceinline__ explicit PeersI(int v) {
         blk[0] = v;
+        if constexpr (LPQ == 8) blk[1] = half_mirror8(v);
 #pragma unroll
         for (int b = 1; b < LPQ / 16; ++b) blk[b] = __shfl_xor(v, 16 * b, LPQ);
     }
     template <int N>
     __device__ __forceinline__ int get() const {
+        if constexpr (LPQ == 8) return peer8_i<N>(blk[0], blk[1]);
         constexpr int B = N / 16, R = N % 16;
         if constexpr (R != 0) {
             return __builtin_amdgcn_update_dpp(0, blk[B], 0x120 + R, 0xf, 0xf, false);
@@ -604,6 +630,10 @@ __device__ __forceinline__ bool group_any(bool flag, int gbase) {
 __host__ __device__ constexpr size_t finalize_row_bytes(int d) { return (size_t)d * 8 + 16; }
 __host__ __device__ constexpr size_t finalize_lds_bytes(int m_tmpl, int d) { return (size_t)(256 / (2 * m_tmpl)) * finalize_row_bytes(d); }
 
+template <int LPQ, bool RECORD>
+__device__ __forceinline__ void finalize_core(const FinalizeArgs& a, long q, int c, bool live, const double* xrow, int id, bool valid,
+                                              float cv, double qn, double tau_c, double t_min);
+
 template <int M>
 __global__ void __launch_bounds__(256) finalize_kernel(FinalizeArgs a) {
     constexpr int LPQ = 2 * M;
@@ -638,18 +668,43 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeArgs a) {
     //  dependent gathers, list -> row id -> row, not on their number)
     const int id = valid ? a.perm[pos_img] : -1;
 
-    // Only candidates whose pre-filter value is within 2 eps of the kk-th smallest one can be
-    // among the kk nearest (or tie with them); the others are strictly farther than kk
-    // candidates and are not gathered.
     const double qn = a.qnc[q];
-    const double nrm = sqrt(qn) + a.ymax;
-    const double eps = a.eps_c * nrm * nrm;
     const float cve = valid ? cv : INFINITY;
     // the kk-th smallest pre-filter value of the group: the smallest value that at least kk values do not exceed
     int n_le = 1;
     const PeersF<LPQ> cve_of(cve);
     for_each_peer<LPQ>([&](auto n) { n_le += cve_of.template get<n.value>() <= cve; });
     const double tau_c = group_min<LPQ>(n_le >= s.kk ? (double)cve : INFINITY, c);
+    // Bound on everything outside the lists: the m_list-th smallest entry of the two lists together
+    // (sentinels included), max_i min(a_i, b_{m-1-i}) -- the value the pre-filter's rejections were
+    // tested against last (coarse.hip.h, pair_union_rank_m).
+    // With rank_extra = E > 0 the rejections were tested against rank m + E,
+    //     max(a_{E-1}, b_{E-1}, max_{i = E .. m-1} min(a_i, b_{m+E-1-i})),
+    // and the two lists were kept as one pool (coarse2.hip.h, pair_union_rank): what they dropped is >= the final
+    // threshold or >= the larger of their last entries, which no rank of the union exceeds.
+    const int ex = a.rank_extra;
+    const float cv_raw = has_slot ? cv : INFINITY;
+    const bool paired = has_slot && slot >= ex;
+    const int partner = M + (paired ? a.m_list + ex - 1 - slot : 0);
+    const float cv_partner = __shfl(cv_raw, partner, LPQ);
+    double t_pair = (list == 0 && paired) ? (double)fminf(cv_raw, cv_partner) : -INFINITY;
+    if (ex > 0 && has_slot && slot == ex - 1) t_pair = (double)cv_raw;
+    const double t_min = group_max<LPQ>(t_pair, c);
+    finalize_core<LPQ, false>(a, q, c, live, xrow, id, valid, cv, qn, tau_c, t_min);
+}
+
+// The finaliser from the candidate on: one candidate per lane (reference row `id`, pre-filter value `cv`), the kk-th
+// smallest pre-filter value `tau_c` of the group and the bound `t_min` on everything the pre-filter let go of.
+// RECORD: the group holds a merged record that may be a truncated union (finalize_record_kernel).
+template <int LPQ, bool RECORD>
+__device__ __forceinline__ void finalize_core(const FinalizeArgs& a, long q, int c, bool live, const double* xrow, int id, bool valid,
+                                              float cv, double qn, double tau_c, double t_min) {
+    const SelectArgs& s = a.s;
+    // Only candidates whose pre-filter value is within 2 eps of the kk-th smallest one can be
+    // among the kk nearest (or tie with them); the others are strictly farther than kk
+    // candidates and are not gathered.
+    const double nrm = sqrt(qn) + a.ymax;
+    const double eps = a.eps_c * nrm * nrm;
     // ... and the reference ranks by its rounded float64 expression: two rows closer than twice its noise
     // may come out in either order, so the window widens by that much (in scaled units).
     const double nr = nrm * a.inv_s + a.mu2;
@@ -675,25 +730,17 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeArgs a) {
 
     // certificate: every reference outside the lists has a float64 d2 above tau
     const double tau = group_min<LPQ>(rank >= s.kk - 1 ? d2 : INFINITY, c);
-    // Bound on everything outside the lists: the m_list-th smallest entry of the two lists together
-    // (sentinels included), max_i min(a_i, b_{m-1-i}) -- the value the pre-filter's rejections were
-    // tested against last (coarse.hip.h, pair_union_rank_m).
-    // With rank_extra = E > 0 the rejections were tested against rank m + E,
-    //     max(a_{E-1}, b_{E-1}, max_{i = E .. m-1} min(a_i, b_{m+E-1-i})),
-    // and the two lists were kept as one pool (coarse2.hip.h, pair_union_rank): what they dropped is >= the final
-    // threshold or >= the larger of their last entries, which no rank of the union exceeds.
-    const int ex = a.rank_extra;
-    const float cv_raw = has_slot ? cv : INFINITY;
-    const bool paired = has_slot && slot >= ex;
-    const int partner = M + (paired ? a.m_list + ex - 1 - slot : 0);
-    const float cv_partner = __shfl(cv_raw, partner, LPQ);
-    double t_pair = (list == 0 && paired) ? (double)fminf(cv_raw, cv_partner) : -INFINITY;
-    if (ex > 0 && has_slot && slot == ex - 1) t_pair = (double)cv_raw;
-    const double t_min = group_max<LPQ>(t_pair, c);
     // true d2 of every outside row >= (qn + t_min - eps) / s^2; the value the reference ranks it by is at
     // most `noise` below that.  qn = +inf (image overflow) and NaN inputs fail the comparison.
     const double bound = (qn + t_min - eps) * a.inv_s2 - noise;
     bool certified = (n_usable >= s.kk) && (tau < INFINITY) && (bound > tau);
+    // A record keeps the LPQ smallest entries of the union: when the last of them is itself inside the window, entries
+    // behind it may be too and are not here -- the exact scan answers the query.
+    bool truncated = false;
+    if constexpr (RECORD) {
+        truncated = group_any<LPQ>(c == LPQ - 1 && need, (int)(threadIdx.x & 63) & ~(LPQ - 1));
+        if (truncated) certified = false;
+    }
     // Exactly tied float64 distances: which tied row the reference keeps at the k-th slot (and,
     // without deterministic ordering, in which order it lists tied rows) depends on its heap's
     // history -- such queries are replayed by exact_scan_kernel.
@@ -762,8 +809,46 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeArgs a) {
     if (live && c == 0 && !certified) {
         const int slot = atomicAdd(a.fail_count, 1);
         a.fail_list[slot] = a.fail_base + (int)q;
+        if (RECORD && truncated) atomicAdd(a.trunc_count, 1);
     }
 }
+
+// ---------------------------------------------------------------------------------------
+// finalize_record_kernel: kRecordLen lanes per query on the merged record the pre-filter's epilogue filed
+// (coarse2.hip.h, Coarse2Record) -- half the waves of finalize_kernel<8>, and a chain of two dependent loads instead of
+// three: (position -> row, |q'|^2 by position, record entry, bound), then (query row, reference row, its norm).
+// Everything from the candidate on is finalize_core, shared with finalize_kernel.
+// ---------------------------------------------------------------------------------------
+#ifdef SKNNR_KERNELS_EXACT
+__global__ void __launch_bounds__(256) finalize_record_kernel(FinalizeArgs a) {
+    constexpr int LPQ = kRecordLen;
+    const SelectArgs& s = a.s;
+    const long gt = (long)blockIdx.x * 256 + threadIdx.x;
+    long q = gt / LPQ;
+    const int c = (int)(gt % LPQ);
+    const bool live = q < s.nq;
+    if (!live) q = s.nq - 1;  // keep the lane for the exchanges; it writes nothing
+    const long q_list = a.qperm ? a.pos0 + q : q;
+    const unsigned long long e = a.rec[q_list * LPQ + c];
+    const float t_min = a.rec_bound[q_list];
+    const double qn = a.qnc_pos[q_list];
+    if (a.qperm) q = a.qperm[q_list];
+
+    extern __shared__ __attribute__((aligned(16))) char fin_lds[];
+    double* xrow = (double*)(fin_lds + (size_t)(threadIdx.x / LPQ) * finalize_row_bytes(s.d));
+    for (int i = c; i < s.d; i += LPQ) xrow[i] = s.xq[q * s.d + i];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();  // (a group lies inside one wave; DS operations of a wave execute in order)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    const int id = (int)(unsigned)(e >> 32);
+    const float cv = __uint_as_float((unsigned)e);
+    const bool valid = id >= 0 && id < s.n_ref;
+    // the record is ascending with the valid entries first: its slot kk - 1 is the kk-th smallest pre-filter value
+    const double tau_c = (double)__shfl(valid ? cv : INFINITY, s.kk - 1, LPQ);
+    finalize_core<LPQ, true>(a, q, c, live, xrow, id, valid, cv, qn, tau_c, (double)t_min);
+}
+#endif  // SKNNR_KERNELS_EXACT
 
 // ---------------------------------------------------------------------------------------
 // exact_scan_kernel: the reference's engine itself, one workgroup per query.

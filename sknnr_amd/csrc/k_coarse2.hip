@@ -21,11 +21,12 @@ hipError_t go(const launch::Coarse2Launch& L, hipStream_t st) {
     constexpr size_t sh = 2 * (size_t)tiles_per_stage2(KS) * tile2_bytes(KS) + (size_t)WAVES * queue2_bytes_per_wave();
     static_assert(kRowQuantum % QPB == 0, "query rows are padded to multiples of kRowQuantum");
     static_assert(sh <= 160 * 1024, "LDS budget");
+    if (L.rec.entry && !coarse2_record_supported(KS, M, E)) return hipErrorInvalidValue;
     auto kern = coarse2_kernel<KS, M, WAVES, E>;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
     if (e != hipSuccess) return e;
     kern<<<dim3((unsigned)(L.rows / QPB)), dim3(WAVES * 64), sh, st>>>(L.rhi, L.rlo, L.n_stages, L.qimg, L.qnc, L.skip_scale, L.n_sentinel,
-                                                                   L.cand_val, L.cand_idx, L.pos0, L.qperm, L.qcell, L.cell_stage);
+                                                                   L.cand_val, L.cand_idx, L.pos0, L.qperm, L.qcell, L.cell_stage, L.rec);
     return hipGetLastError();
 }
 

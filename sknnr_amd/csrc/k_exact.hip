@@ -84,8 +84,12 @@ hipError_t cell_scatter(const CellArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+int finalize_lanes(const FinalizeArgs& f) { return f.rec ? kRecordLen : (f.m_list <= 8 ? 16 : (f.m_list <= 16 ? 32 : 64)); }
+
 hipError_t finalize(const FinalizeArgs& f, long n, hipStream_t st) {
-    if (f.m_list <= 8) {
+    if (f.rec) {  // merged candidate records (coarse2.hip.h): 8 lanes per query
+        finalize_record_kernel<<<dim3((unsigned)((n * kRecordLen + 255) / 256)), dim3(256), finalize_lds_bytes(kRecordLen / 2, f.s.d), st>>>(f);
+    } else if (f.m_list <= 8) {
         finalize_kernel<8><<<dim3((unsigned)((n * 16 + 255) / 256)), dim3(256), finalize_lds_bytes(8, f.s.d), st>>>(f);
     } else if (f.m_list <= 16) {  // (lists of 12 and 16: 32 lanes per query)
         finalize_kernel<16><<<dim3((unsigned)((n * 32 + 255) / 256)), dim3(256), finalize_lds_bytes(16, f.s.d), st>>>(f);

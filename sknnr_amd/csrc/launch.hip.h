@@ -24,7 +24,8 @@ hipError_t check_finite(const double* x, long n_el, int* status, hipStream_t st)
 hipError_t cell_assign(const CellArgs& a, hipStream_t st);
 hipError_t cell_count(const CellArgs& a, hipStream_t st);
 hipError_t cell_scatter(const CellArgs& a, hipStream_t st);
-hipError_t finalize(const FinalizeArgs& f, long n, hipStream_t st);
+hipError_t finalize(const FinalizeArgs& f, long n, hipStream_t st);  // f.rec != nullptr: finalize_record_kernel
+int finalize_lanes(const FinalizeArgs& f);                             // lanes per query of that launch
 hipError_t exact_scan(int formula, bool chunked, const ScanArgs& a, long blocks, size_t lds_bytes, hipStream_t st);
 hipError_t scan_merge(int formula, const ScanArgs& a, long blocks, size_t lds_bytes, int grid_wg_of_scan, int forced_slices,
                       hipStream_t st);
@@ -73,6 +74,7 @@ struct Coarse2Launch {
     const unsigned char* qcell;
     const int* cell_stage;
     long rows;  // positions [pos0, pos0 + rows) of the chunk (a multiple of the workgroup's rows)
+    Coarse2Record rec;  // rec.entry != nullptr: merged candidate records instead of the lists (coarse2_record_supported)
 };
 constexpr int kNoInstance = -1;  // the (ks, list length, waves, rank) combination has no compiled kernel
 // return 0 and *err = the launch status, or kNoInstance

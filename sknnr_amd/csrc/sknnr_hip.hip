@@ -270,6 +270,10 @@ struct sknnr_index {
     DevBuf<uint4> qimg;
     DevBuf<float> cand_val;
     DevBuf<int> cand_idx, fail_list, fail_count, fail_list2, slice_i;
+    // merged candidate records (coarse2.hip.h, Coarse2Record) and |q'|^2 by position, in place of cand_val / cand_idx
+    DevBuf<unsigned long long> rec;
+    DevBuf<float> rec_bound;
+    DevBuf<double> qnc_pos;
     DevBuf<double> slice_v;  // sliced exact scans: the slice heaps (exact.hip.h, scan_slices)
     DevBuf<int> status;            // bit 0: a query value was NaN, bit 1: infinite (since the last poll)
     DevBuf<long long> fail_total;  // running count of certificate failures (device)
@@ -302,6 +306,9 @@ struct sknnr_index {
     // the Euclidean pre-filter launches of the last device chunk of the last call (sknnr_debug_last_prefilter):
     // generation, KS, list length, rank beyond the list, bulk waves, bulk rows, thin rows, cell depth
     int64_t last_prefilter[8] = {};
+    // the finaliser launches of the last device chunk of the last call (sknnr_debug_last_finalize): lanes per query, record
+    // path (the rows its truncation rule sent to the exact scan are read from fail_count[3] when asked)
+    int64_t last_finalize[2] = {};
     // the integer Hamming pre-filter of the last call (sknnr_debug_last_hamming): ran, kk, compacts, seed rows, band,
     // tree pairs, device chunks (out[7], the rows handed to the exact scan, is read from fail_count when asked); rows of
     // its last device chunk, whose candidate lists h_cand_cnt / h_cand_id still hold (sknnr_debug_hamming_candidates)
@@ -340,6 +347,7 @@ struct sknnr_index {
         qimg.release();
         cand_val.release();
         cand_idx.release();
+        rec.release(); rec_bound.release(); qnc_pos.release();
         fail_list.release();
         fail_count.release();
         fail_total.release();
@@ -1318,7 +1326,19 @@ int launch_coarse(sknnr_index* ix, long nq_pad, int m_list, int kk, hipStream_t 
 constexpr int kCoarse2TailWaves = 4;  // workgroup size (waves) of the thin-round variant
 constexpr int kCusPerDevice = 256;
 
-int launch_coarse2_waves(sknnr_index* ix, int m_list, int waves, long row0, long rows, int kk, hipStream_t st) {
+// The finaliser works from merged candidate records (coarse2.hip.h, Coarse2Record; finalize_record_kernel) where the
+// second-generation kernel has an instance that files them (coarse2_record_supported: lists of 2 and 6 with sentinels, up to
+// two K-steps -- up to 5 neighbours searched on up to 32 features).
+// SKNNR_FINALIZE_RECORD=0 keeps the lists and finalize_kernel<8> (A/B runs).
+bool use_record(int ks, int m_list, int kk, bool v2, int raw) {
+    static const bool enabled = [] {
+        const char* e = std::getenv("SKNNR_FINALIZE_RECORD");
+        return !(e && std::atoi(e) == 0);
+    }();
+    return enabled && v2 && !raw && coarse2_record_supported(ks, m_list, coarse2_rank_extra(m_list, kk));
+}
+
+int launch_coarse2_waves(sknnr_index* ix, int m_list, int waves, long row0, long rows, int kk, bool record, hipStream_t st) {
     // more neighbours than a list holds: thresholds of rank M + E, no sentinels (coarse2_rank_extra)
     const int extra = coarse2_rank_extra(m_list, kk);
     if (extra != 0 && !((m_list == 16 && kk <= kCoarse2MaxKK16) || (m_list == 12 && kk <= kCoarse2MaxKK12) || (m_list == 8 && kk <= kCoarse2MaxKK8) || (m_list == 6 && kk <= kCoarse2MaxKK6)))
@@ -1328,7 +1348,8 @@ int launch_coarse2_waves(sknnr_index* ix, int m_list, int waves, long row0, long
     launch::Coarse2Launch L{ix->rhi2.p, ix->rlo2.p, ix->n_stages2, ix->qimg.p, ix->qnc.p, (float)(std::ldexp(1.0, -9) * ix->ymax * 1.02),
                             extra != 0 ? 0 : m_list - (kk + 1), ix->cand_val.p, ix->cand_idx.p, (int)row0,
                             bucketed ? ix->qperm.p : nullptr, bucketed ? ix->qcell.p : nullptr,
-                            bucketed ? ix->cell_stage.p : nullptr, rows};
+                            bucketed ? ix->cell_stage.p : nullptr, rows,
+                            Coarse2Record{record ? ix->rec.p : nullptr, ix->rec_bound.p, ix->perm2.p, (int)ix->n_ref}};
     hipError_t e = hipSuccess;
     if (launch::coarse2(ix->ks, m_list, waves, extra, L, st, &e) == launch::kNoInstance)
         return fail(SKNNR_ERR_UNSUPPORTED, "no second-generation coarse kernel for ks = %d, list length %d, %d waves, rank + %d", ix->ks,
@@ -1351,7 +1372,7 @@ int launch_coarse2_waves(sknnr_index* ix, int m_list, int waves, long row0, long
 // the CUs' worth) go to 4-wave workgroups instead: four times as many CUs, one wave per SIMD.
 // `rows`: the live rows of the chunk -- its padding rows (up to kRowQuantum - 1 of them, behind the live ones also in a
 // bucketed call) get no workgroups of their own: a 262,144-row call is 256 workgroups, not 258 with a thin round of two.
-int launch_coarse2(sknnr_index* ix, long rows, int m_list, int kk, hipStream_t st) {
+int launch_coarse2(sknnr_index* ix, long rows, int m_list, int kk, bool record, hipStream_t st) {
     if (!coarse2_supported(ix->ks, m_list))
         return fail(SKNNR_ERR_UNSUPPORTED, "no second-generation coarse kernel for ks = %d, list length %d", ix->ks, m_list);
     const int BULK_WAVES = coarse2_waves(ix->ks, m_list);
@@ -1367,7 +1388,7 @@ int launch_coarse2(sknnr_index* ix, long rows, int m_list, int kk, hipStream_t s
     const long bulk_rows = (n_wg - tail_wg) * QPB;
     ix->bulk_rows_done = 0;
     if (bulk_rows > 0) {
-        int rc = launch_coarse2_waves(ix, m_list, BULK_WAVES, 0, bulk_rows, kk, st);
+        int rc = launch_coarse2_waves(ix, m_list, BULK_WAVES, 0, bulk_rows, kk, record, st);
         if (rc) return rc;
         if (tail_wg > 0 && ix->ev_fork) {  // the caller finalises these rows beside the thin round
             if (ix->ev_bulk_end) {  // the timed region ends here: the thin round shares the device from now on
@@ -1380,7 +1401,7 @@ int launch_coarse2(sknnr_index* ix, long rows, int m_list, int kk, hipStream_t s
     }
     if (tail_wg > 0) {
         const long tail_rows = std::min(tail_wg * QPB, (rows - bulk_rows + QPB_TAIL - 1) / QPB_TAIL * QPB_TAIL);
-        return launch_coarse2_waves(ix, m_list, kCoarse2TailWaves, bulk_rows, tail_rows, kk, st);
+        return launch_coarse2_waves(ix, m_list, kCoarse2TailWaves, bulk_rows, tail_rows, kk, record, st);
     }
     return SKNNR_OK;
 }
@@ -1549,6 +1570,7 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
                long* d_idx, hipStream_t st, int raw = 0, long id_offset = 0) {
     std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);
     std::fill(std::begin(ix->last_hamming), std::end(ix->last_hamming), 0);
+    std::fill(std::begin(ix->last_finalize), std::end(ix->last_finalize), 0);
     ix->last_hamming_rows = 0;
     if (xdev && uses_forest(ix, o)) return run_forest(ix, xdev, nq, o, d_dist, d_idx, st);
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
@@ -1585,9 +1607,16 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
         HIP_TRY(ix->qcell.ensure((size_t)cap_pad));
         HIP_TRY(ix->qperm.ensure((size_t)cap_pad));
     }
-    if (coarse) {
+    const bool record = coarse && use_record(ix->ks, coarse_list_len(ix, kk), kk, use_coarse2(ix, coarse_list_len(ix, kk)), raw);
+    if (record) {
+        HIP_TRY(ix->rec.ensure((size_t)cap_pad * kRecordLen));
+        HIP_TRY(ix->rec_bound.ensure((size_t)cap_pad));
+        if (ix->cell_depth > 0) HIP_TRY(ix->qnc_pos.ensure((size_t)cap_pad));
+    } else if (coarse) {
         HIP_TRY(ix->cand_val.ensure((size_t)cap_pad * 2 * coarse_list_len(ix, kk)));
         HIP_TRY(ix->cand_idx.ensure((size_t)cap_pad * 2 * coarse_list_len(ix, kk)));
+    }
+    if (coarse) {
         HIP_TRY(ix->fail_list.ensure(nq));
         HIP_TRY(hipMemsetAsync(ix->fail_count.p, 0, 16, st));
     }
@@ -1667,6 +1696,8 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
             ca.cell = ix->qcell.p;
             ca.hist = ix->cell_hist.p;
             ca.perm = ix->qperm.p;
+            ca.qnc = ix->qnc.p;
+            ca.qnc_pos = record ? ix->qnc_pos.p : nullptr;
             HIP_TRY(hipMemsetAsync(ix->cell_hist.p, 0, 2 * kCellMax * sizeof(int), st));
             if (!cells_done) HIP_TRY(launch::cell_assign(ca, st));
             HIP_TRY(launch::cell_count(ca, st));
@@ -1689,7 +1720,7 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
                                   : (long)ix->n_stages * tiles_per_stage(ix->ks);
             ix->stats.mfma_executed_ratio = (double)tiles * 32.0 * (16.0 * ix->ks) / ((double)ix->n_ref * ix->d);
         }
-        int rc = v2 ? launch_coarse2(ix, n, coarse_list_len(ix, kk), kk, st)
+        int rc = v2 ? launch_coarse2(ix, n, coarse_list_len(ix, kk), kk, record, st)
                     : launch_coarse(ix, n_pad, coarse_list_len(ix, kk), kk, st);
         if (rc) return rc;
         if (ix->ev_bulk_end) HIP_TRY(hipEventRecord(ev.second, st));  // (no fork: the whole pre-filter is timed)
@@ -1708,6 +1739,12 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
         f.perm = v2 ? ix->perm2.p : ix->perm.p;
         f.qnc = ix->qnc.p;
         f.qperm = bucketed ? ix->qperm.p : nullptr;
+        if (record) {
+            f.rec = ix->rec.p;
+            f.rec_bound = ix->rec_bound.p;
+            f.qnc_pos = bucketed ? ix->qnc_pos.p : ix->qnc.p;
+            f.trunc_count = ix->fail_count.p + 3;
+        }
         f.m_list = coarse_list_len(ix, kk);
         f.rank_extra = coarse_rank_extra(f.m_list, kk);
         f.inv_s2 = 1.0 / (ix->s * ix->s);
@@ -1735,12 +1772,20 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
             g.s.row_offset = f.s.row_offset + r0;
             g.s.out_dist = f.s.out_dist ? f.s.out_dist + r0 * o->n_neighbors : nullptr;
             g.s.out_idx = f.s.out_idx + r0 * o->n_neighbors;
-            g.cand_val = f.cand_val + (size_t)r0 * 2 * f.m_list;
-            g.cand_idx = f.cand_idx + (size_t)r0 * 2 * f.m_list;
+            if (record) {
+                g.rec = f.rec + (size_t)r0 * kRecordLen;
+                g.rec_bound = f.rec_bound + r0;
+                g.qnc_pos = f.qnc_pos + r0;
+            } else {
+                g.cand_val = f.cand_val + (size_t)r0 * 2 * f.m_list;
+                g.cand_idx = f.cand_idx + (size_t)r0 * 2 * f.m_list;
+            }
             g.qnc = f.qnc + r0;
             g.fail_base = f.fail_base + (int)r0;
             launch_finalize(g, rows, s_);
         };
+        ix->last_finalize[0] = launch::finalize_lanes(f);
+        ix->last_finalize[1] = record ? 1 : 0;
         const long done = v2 ? std::min<long>(ix->bulk_rows_done, n) : 0;
         if (done > 0) {
             // fork: the rows of the bulk launch are finalised on the side stream while the thin round runs here
@@ -2835,6 +2880,25 @@ extern "C" int sknnr_debug_last_prefilter(const sknnr_index* cix, int64_t out[8]
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
     std::copy(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), out);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_finalize(const sknnr_index* cix, int64_t out[4]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    out[0] = ix->last_finalize[0];
+    out[1] = ix->last_finalize[1];
+    out[2] = out[3] = 0;
+    if (ix->last_finalize[1]) {
+        // the rows the truncation rule put on the fail list, over every device chunk of the call (the workspace is the
+        // handle's: no later call has touched it, or the record would be zero)
+        int n_trunc = 0;
+        HIP_TRY(hipSetDevice(ix->device));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(&n_trunc, ix->fail_count.p + 3, sizeof n_trunc, hipMemcpyDeviceToHost));
+        out[2] = n_trunc;
+    }
     return SKNNR_OK;
 }
 
