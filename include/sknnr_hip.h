@@ -430,6 +430,23 @@ int sknnr_debug_last_finalize(const sknnr_index* index, int64_t out[4]);
 int sknnr_debug_last_hamming(const sknnr_index* index, int64_t out[8]);
 
 /*
+ * Debug only.  The float64 exact scan of the most recent call on the handle (the scan sequence of its last device chunk:
+ * exact_scan_kernel, and for a call that may be sliced scan_merge_kernel and the sequential replay), so that a test can
+ * prove which launch served it:
+ *   out[0] 0 = no scan ran (then out[1 .. 7] = 0), else formula + 1
+ *   out[1] 1 = the column-chunked instantiation ran (d > 1024)
+ *   out[2] kk, the neighbours searched (k, + 1 for X=None)
+ *   out[3] workgroups of the first scan launch    out[4] its dynamic LDS bytes
+ *   out[5] rows offered to the scan: the call's rows, or the rows on the fail list (read from the device, synchronously)
+ *   out[6] slices the reference rows of a pass are split into for that count (1 = not sliced): computed on the host from
+ *          out[5] with the kernels' own scan_slices, not read back from the device
+ *   out[7] rows the slice merge filed for the sequential replay (read from the device, synchronously)
+ * After sknnr_merge_shards: out[3], out[4] describe the replay scan, out[6] is n_shards and out[7] the rows replayed.
+ * Every search call zeroes the record first.
+ */
+int sknnr_debug_last_scan(const sknnr_index* index, int64_t out[8]);
+
+/*
  * Debug only.  The candidate lists the integer Hamming pre-filter wrote for the first n rows of the last device chunk of
  * the most recent call (n at most that chunk's rows; SKNNR_ERR_INVALID when the pre-filter did not run).  Host memory:
  *   cnt (n)       candidates per row, -1 = the row went to the exact scan (list overflow, or ids outside 16 bits)

@@ -84,6 +84,7 @@ EXPORTED_SYMBOLS = (
     "sknnr_debug_last_prefilter",
     "sknnr_debug_last_finalize",
     "sknnr_debug_last_hamming",
+    "sknnr_debug_last_scan",
     "sknnr_debug_hamming_candidates",
 )
 
@@ -200,6 +201,8 @@ def load(build_if_missing: bool = False):
     if hasattr(lib, "sknnr_debug_last_finalize"):  # (a SKNNR_HIP_LIBRARY variant built before the entry point existed)
         lib.sknnr_debug_last_finalize.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_last_hamming.argtypes = [vp, POINTER(c_int64)]
+    if hasattr(lib, "sknnr_debug_last_scan"):  # (likewise)
+        lib.sknnr_debug_last_scan.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_hamming_candidates.argtypes = [vp, vp, vp, c_int64]
     _lib = lib
     return lib
@@ -473,6 +476,17 @@ class Index:
         out = (c_int64 * 8)()
         check(load().sknnr_debug_last_hamming(self.handle, out))
         return dict(zip(self.HAMMING_FIELDS, (int(v) for v in out)))
+
+    SCAN_FIELDS = ("formula_plus_1", "chunked", "kk", "workgroups", "lds_bytes", "rows", "slices", "replayed_rows")
+
+    def debug_last_scan(self) -> dict:
+        """Debug only: the float64 exact scan of the last call (sknnr_debug_last_scan): formula + 1 (0: no scan ran), the
+        column-chunked instantiation, kk, workgroups and dynamic LDS bytes of the first scan launch, rows offered (the
+        call's, or the fail list's device count), slices per pass (1: not sliced; the shard count after a shard merge), and
+        the rows the merge filed for the sequential replay."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_scan(self.handle, out))
+        return dict(zip(self.SCAN_FIELDS, (int(v) for v in out)))
 
     def debug_hamming_candidates(self, n: int):
         """Debug only: ``(cnt, ids)`` the integer Hamming pre-filter wrote for the first ``n`` rows of the last call's last

@@ -314,6 +314,11 @@ struct sknnr_index {
     // its last device chunk, whose candidate lists h_cand_cnt / h_cand_id still hold (sknnr_debug_hamming_candidates)
     int64_t last_hamming[8] = {};
     long last_hamming_rows = 0;
+    // the exact scan of the last call (sknnr_debug_last_scan): formula + 1, chunked, kk, workgroups and LDS bytes of the
+    // first scan launch, rows offered (host count; -1: the fail list's device count, read from fail_count[0] when asked),
+    // slices (0: whatever scan_slices gives for the count, worked out when asked; else fixed: 1 = the call cannot be
+    // sliced, or the shard count of a shard merge), 1 = count2 (fail_count[2]) holds the rows filed for the replay
+    int64_t last_scan[8] = {};
     bool stream_open = false;  // a sknnr_stream owns the host pipeline's slots
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
@@ -1472,6 +1477,9 @@ int launch_scan_formula(sknnr_index* ix, const ScanArgs& a0, long max_items, boo
     const long passes = (max_items + nq_pass - 1) / nq_pass;
     // (sliced mode needs the whole grid even for one pass; otherwise one workgroup per pass is enough)
     const long blocks = may_slice ? kScanGridWg : std::max<long>(1, std::min<long>(passes, kScanGridWg));
+    const int64_t rec[8] = {s.formula + 1, chunked ? 1 : 0, s.kk, blocks, (int64_t)sh, a0.list ? -1 : max_items, may_slice ? 0 : 1,
+                            may_slice ? 1 : 0};
+    std::copy(std::begin(rec), std::end(rec), ix->last_scan);
     HIP_TRY(launch::exact_scan(s.formula, chunked, a, blocks, sh, st));
     if (!may_slice) return SKNNR_OK;
     // one wave per sliced query (none if the scan was not sliced: the kernel returns at once)
@@ -1571,6 +1579,7 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
     std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);
     std::fill(std::begin(ix->last_hamming), std::end(ix->last_hamming), 0);
     std::fill(std::begin(ix->last_finalize), std::end(ix->last_finalize), 0);
+    std::fill(std::begin(ix->last_scan), std::end(ix->last_scan), 0);
     ix->last_hamming_rows = 0;
     if (xdev && uses_forest(ix, o)) return run_forest(ix, xdev, nq, o, d_dist, d_idx, st);
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
@@ -2515,6 +2524,8 @@ int merge_shards_formula(sknnr_index* ix, const SelectArgs& call, int n_shards, 
     const bool chunked = call.d > kScanColChunk;
     const int nq_pass = scan_nq(call.formula);
     const long blocks = std::max<long>(1, std::min<long>((nq + nq_pass - 1) / nq_pass, kScanGridWg));
+    const int64_t rec[8] = {call.formula + 1, chunked ? 1 : 0, call.kk, blocks, (int64_t)sh, nq, n_shards, 1};
+    std::copy(std::begin(rec), std::end(rec), ix->last_scan);
     HIP_TRY(launch::exact_scan(call.formula, chunked, b, blocks, sh, st));
     return SKNNR_OK;
 }
@@ -2523,6 +2534,7 @@ int merge_shards_formula(sknnr_index* ix, const SelectArgs& call, int n_shards, 
 int merge_shards_device(sknnr_index* ix, const double* xdev, long nq, const sknnr_query_opts* o, int n_shards,
                         const double* shard_val, const long* shard_idx, double* d_dist, long* d_idx, hipStream_t st) {
     std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);  // (no pre-filter runs on this path)
+    std::fill(std::begin(ix->last_scan), std::end(ix->last_scan), 0);
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
     const bool affine = o->apply_affine != 0 && xdev != nullptr;
     const bool self_rows = xdev == nullptr;
@@ -2917,6 +2929,28 @@ extern "C" int sknnr_debug_last_hamming(const sknnr_index* cix, int64_t out[8]) 
         HIP_TRY(hipMemcpy(&n_fail, ix->fail_count.p, sizeof n_fail, hipMemcpyDeviceToHost));
         out[7] = n_fail;
     }
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_scan(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    const int64_t* r = ix->last_scan;
+    std::copy(r, r + 8, out);
+    out[7] = 0;
+    if (!r[0]) return SKNNR_OK;
+    if (r[5] < 0 || r[7]) {
+        // the counts the kernels worked from (the workspace is the handle's: no later call has touched it, or the record
+        // would be zero): rows on the fail list, rows scan_merge_kernel filed for the sequential replay
+        int cnt[3] = {0, 0, 0};
+        HIP_TRY(hipSetDevice(ix->device));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(cnt, ix->fail_count.p, sizeof cnt, hipMemcpyDeviceToHost));
+        if (r[5] < 0) out[5] = cnt[0];
+        if (r[7]) out[7] = cnt[2];
+    }
+    if (!r[6]) out[6] = scan_slices(out[5], scan_nq((int)r[0] - 1), (int)ix->n_ref, (int)r[2], (int)r[3]);
     return SKNNR_OK;
 }
 
