@@ -455,6 +455,46 @@ int sknnr_debug_last_scan(const sknnr_index* index, int64_t out[8]);
  */
 int sknnr_debug_hamming_candidates(const sknnr_index* index, int32_t* cnt, int32_t* ids, int64_t n);
 
+/*
+ * Debug only.  The query preparation launch (prep_queries_direct_kernel / prep_queries_kernel) of the most recent call on
+ * the handle (its last device chunk), so that a test can prove which kernel prepared its rows.  Host memory, no device work:
+ *   out[0] 0 = no preparation kernel ran (then out[1 .. 7] = 0), 1 = prep_queries_direct_kernel, 2 = prep_queries_kernel (LDS)
+ *   out[1] rows per block (256; the LDS kernel: 256 / 128 / 64 by the width of the input rows)
+ *   out[2] element type of the rows (sknnr_dtype)
+ *   out[3] live rows of the chunk              out[4] rows with the padding (a multiple of 6144)
+ *   out[5] 1 = the kernel wrote the float64 transformed rows (an affine map, or rows narrower than float64)
+ *   out[6] who named the rows' cells: 0 = nobody (the call was not bucketed), 1 = the preparation kernel,
+ *          2 = cell_assign_kernel
+ *   out[7] bits of the affine map in use: 1 center, 2 scale, 4 proj
+ * Every search call zeroes the record first.
+ */
+int sknnr_debug_last_prep(const sknnr_index* index, int64_t out[8]);
+
+/*
+ * Debug only.  What the preparation and bucketing kernels wrote for the last device chunk of the most recent call, copied
+ * from the handle's workspace (n at most that chunk's padded rows, out[4] above).  Host memory; each pointer may be NULL:
+ *   qimg    (n, 64 ks bytes)  f16 hi / lo image rows: [hi | lo][K-step][K half] pieces of 16 bytes (8 halves)
+ *   qnc     (n)               |s (q - mu)|^2, +inf for a row whose image overflows f16, 0 on padding rows
+ *   xt      (min(n, live rows), d) the float64 transformed rows
+ *   cell    (n)               cell of every row (padding rows: the last cell)
+ *   perm    (n)               position -> row of the bucketed order
+ *   qnc_pos (n)               qnc by position
+ * SKNNR_ERR_INVALID when no preparation kernel ran, or for a buffer the call did not fill (xt without a transform; cell and
+ * perm on a call that was not bucketed; qnc_pos unless the bucketed call filed candidate records).  Synchronises the device.
+ */
+int sknnr_debug_query_prep(const sknnr_index* index, int64_t n, void* qimg, double* qnc, double* xt, uint8_t* cell,
+                           int32_t* perm, double* qnc_pos);
+
+/*
+ * Debug only.  The host-built constants the preparation and bucketing kernels read; each pointer may be NULL:
+ *   mu (16 ks) zero-padded centre of the image      s: its power-of-two scale
+ *   cell_depth: levels of the cell tree (0: none; then axes, centre and thr are left alone)
+ *   axes (cell_depth, d)    centre (d)    thr (2^cell_depth - 1), node n of level l at 2^l - 1 + n
+ * SKNNR_ERR_UNSUPPORTED when the index has no image (d > 128).
+ */
+int sknnr_debug_image_constants(const sknnr_index* index, double* mu, double* s, int32_t* cell_depth, float* axes,
+                                float* centre, float* thr);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -51,6 +51,10 @@ def _load():
         _f64p, ctypes.c_int64, ctypes.c_int32, _f64p, _f64p, _f64p, ctypes.c_int32, _f64p,
     ]
     lib.oracle_row_norms.argtypes = [_f64p, ctypes.c_int64, ctypes.c_int32, _f64p]
+    _f32p = ctypes.POINTER(ctypes.c_float)
+    lib.oracle_cell_assign.argtypes = [
+        _f64p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _f32p, _f32p, _f32p, ctypes.POINTER(ctypes.c_uint8),
+    ]
     for name in ("oracle_argkmin_expanded", "oracle_argkmin_direct"):
         getattr(lib, name).argtypes = [
             _f64p, ctypes.c_int64, _f64p, ctypes.c_int64, ctypes.c_int32,
@@ -99,6 +103,21 @@ def row_norms(X) -> np.ndarray:
     X = _c64(X)
     out = np.empty(X.shape[0], dtype=np.float64)
     _load().oracle_row_norms(_ptr(X), X.shape[0], X.shape[1], _ptr(out))
+    return out
+
+
+def cell_assign(X, axes, centre, thr) -> np.ndarray:
+    """Cell of every row of ``X`` (float64, transformed) in the median-split tree ``axes`` (depth, d), ``centre`` (d),
+    ``thr`` (2^depth - 1), all float32: the float32 fmaf chains and the descent of sknnr_amd/csrc/bucket.hip.h."""
+    X = _c64(X)
+    axes, centre, thr = (np.ascontiguousarray(a, dtype=np.float32) for a in (axes, centre, thr))
+    depth, d = axes.shape
+    if X.shape[1] != d or centre.shape != (d,) or thr.shape != ((1 << depth) - 1,) or not 1 <= depth <= 8:
+        raise ValueError("tree shape mismatch")
+    out = np.empty(X.shape[0], dtype=np.uint8)
+    f32p = ctypes.POINTER(ctypes.c_float)
+    _load().oracle_cell_assign(_ptr(X), X.shape[0], d, depth, _ptr(axes, f32p), _ptr(centre, f32p), _ptr(thr, f32p),
+                               _ptr(out, ctypes.POINTER(ctypes.c_uint8)))
     return out
 
 

@@ -86,6 +86,9 @@ EXPORTED_SYMBOLS = (
     "sknnr_debug_last_hamming",
     "sknnr_debug_last_scan",
     "sknnr_debug_hamming_candidates",
+    "sknnr_debug_last_prep",
+    "sknnr_debug_query_prep",
+    "sknnr_debug_image_constants",
 )
 
 
@@ -204,6 +207,10 @@ def load(build_if_missing: bool = False):
     if hasattr(lib, "sknnr_debug_last_scan"):  # (likewise)
         lib.sknnr_debug_last_scan.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_hamming_candidates.argtypes = [vp, vp, vp, c_int64]
+    if hasattr(lib, "sknnr_debug_last_prep"):  # (likewise)
+        lib.sknnr_debug_last_prep.argtypes = [vp, POINTER(c_int64)]
+        lib.sknnr_debug_query_prep.argtypes = [vp, c_int64, vp, vp, vp, vp, vp, vp]
+        lib.sknnr_debug_image_constants.argtypes = [vp, vp, POINTER(c_double), POINTER(c_int32), vp, vp, vp]
     _lib = lib
     return lib
 
@@ -495,6 +502,56 @@ class Index:
         ids = np.empty((n, 192), dtype=np.int32)
         check(load().sknnr_debug_hamming_candidates(self.handle, _host_ptr(cnt), _host_ptr(ids), int(n)))
         return cnt, ids
+
+    PREP_FIELDS = ("kernel", "rows_per_block", "x_dtype", "nq", "nq_pad", "xt_written", "cells_by", "affine_bits")
+
+    def debug_last_prep(self) -> dict:
+        """Debug only: the query preparation launch of the last call's last device chunk (sknnr_debug_last_prep): kernel
+        (0: none, 1: prep_queries_direct_kernel, 2: prep_queries_kernel), rows per block, element type, live and padded
+        rows, whether the transformed rows were written, who named the cells (0: not bucketed, 1: the preparation kernel,
+        2: cell_assign_kernel) and the parts of the affine map in use (1 center | 2 scale | 4 proj)."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_prep(self.handle, out))
+        return dict(zip(self.PREP_FIELDS, (int(v) for v in out)))
+
+    def debug_query_prep(self, n: int, want=("qimg", "qnc", "xt", "cell", "perm", "qnc_pos")) -> dict:
+        """Debug only: what the preparation and bucketing kernels wrote for the first ``n`` rows (positions) of the last
+        call's last device chunk (sknnr_debug_query_prep), the buffers named in ``want``: ``qimg`` (n, 64 ks) uint8,
+        ``qnc`` (n), ``xt`` (min(n, live rows), d), ``cell`` (n) uint8, ``perm`` (n) int32, ``qnc_pos`` (n)."""
+        n = int(n)
+        ks = (self.d + 15) // 16
+        nq = self.debug_last_prep()["nq"]
+        out = {}
+        if "qimg" in want:
+            out["qimg"] = np.empty((n, 64 * ks), dtype=np.uint8)
+        if "qnc" in want:
+            out["qnc"] = np.empty(n, dtype=np.float64)
+        if "xt" in want:
+            out["xt"] = np.empty((min(n, nq), self.d), dtype=np.float64)
+        if "cell" in want:
+            out["cell"] = np.empty(n, dtype=np.uint8)
+        if "perm" in want:
+            out["perm"] = np.empty(n, dtype=np.int32)
+        if "qnc_pos" in want:
+            out["qnc_pos"] = np.empty(n, dtype=np.float64)
+        check(load().sknnr_debug_query_prep(self.handle, n, *(_host_ptr(out.get(name)) for name in
+                                                              ("qimg", "qnc", "xt", "cell", "perm", "qnc_pos"))))
+        return out
+
+    def debug_image_constants(self) -> dict:
+        """Debug only: the host-built constants of the preparation and bucketing kernels (sknnr_debug_image_constants):
+        ``mu`` (16 ks), ``s``, ``cell_depth``, and with a cell tree ``axes`` (depth, d), ``centre`` (d), ``thr`` (2^depth - 1)
+        float32 (without one: empty arrays)."""
+        ks = (self.d + 15) // 16
+        mu = np.empty(16 * ks, dtype=np.float64)
+        s, depth = c_double(), c_int32()
+        check(load().sknnr_debug_image_constants(self.handle, _host_ptr(mu), byref(s), byref(depth), None, None, None))
+        axes = np.empty((depth.value, self.d), dtype=np.float32)
+        centre = np.empty(self.d if depth.value else 0, dtype=np.float32)
+        thr = np.empty((1 << depth.value) - 1, dtype=np.float32)
+        check(load().sknnr_debug_image_constants(self.handle, None, None, None, _host_ptr(axes), _host_ptr(centre),
+                                                 _host_ptr(thr)))
+        return dict(mu=mu, s=s.value, cell_depth=int(depth.value), axes=axes, centre=centre, thr=thr)
 
 
 class QueryStream:

@@ -319,6 +319,13 @@ struct sknnr_index {
     // slices (0: whatever scan_slices gives for the count, worked out when asked; else fixed: 1 = the call cannot be
     // sliced, or the shard count of a shard merge), 1 = count2 (fail_count[2]) holds the rows filed for the replay
     int64_t last_scan[8] = {};
+    // the query preparation of the last device chunk of the last call (sknnr_debug_last_prep): kernel (1 direct, 2 LDS), rows
+    // per block, x_dtype, live rows, padded rows, xt written, who named the cells (1 the prep kernel, 2 cell_assign_kernel),
+    // bits center | scale << 1 | proj << 2; and what of that chunk the workspace holds (sknnr_debug_query_prep): its
+    // transformed rows, the cells and the permutation, |q'|^2 by position
+    int64_t last_prep[8] = {};
+    const double* last_prep_xt = nullptr;
+    bool last_prep_bucketed = false, last_prep_qnc_pos = false;
     bool stream_open = false;  // a sknnr_stream owns the host pipeline's slots
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
@@ -1295,23 +1302,36 @@ int launch_prep(sknnr_index* ix, const void* x, long nq, long nq_pad, bool affin
     a.qnc = ix->qnc.p;
     const int ldx = a.d_in | 1;
     const size_t lim = 150 * 1024;
+    int64_t* r = ix->last_prep;
+    std::fill(r, r + 8, 0);
+    ix->last_prep_xt = nullptr;
+    ix->last_prep_bucketed = ix->last_prep_qnc_pos = false;
+    r[2] = x_dtype, r[3] = nq, r[4] = nq_pad, r[5] = xt ? 1 : 0;
+    r[7] = (a.center ? 1 : 0) | (a.scale ? 2 : 0) | (a.proj ? 4 : 0);
     if (ix->ks <= 4 && !std::getenv("SKNNR_PREP_LDS")) {
         // narrow feature spaces: register-resident kernel (no LDS, high occupancy)
         if (cells && ix->cell_depth > 0) {
             a.tree = CellTreeDev{ix->cell_axes.p, ix->cell_centre.p, ix->cell_thr.p, ix->cell_depth};
             a.cell = ix->qcell.p;
             if (cells_done) *cells_done = true;
+            r[6] = 1;
         }
         HIP_TRY(launch::prep_direct(a, st));
+        r[0] = 1, r[1] = 256;
     } else if ((size_t)256 * ldx * 8 <= lim) {
         HIP_TRY(launch::prep_lds(256, a, st));
+        r[0] = 2, r[1] = 256;
     } else if ((size_t)128 * ldx * 8 <= lim) {
         HIP_TRY(launch::prep_lds(128, a, st));
+        r[0] = 2, r[1] = 128;
     } else if ((size_t)64 * ldx * 8 <= lim) {
         HIP_TRY(launch::prep_lds(64, a, st));
+        r[0] = 2, r[1] = 64;
     } else {
+        std::fill(r, r + 8, 0);
         return fail(SKNNR_ERR_UNSUPPORTED, "d_in = %d is too wide for the query preparation kernel (max 299)", a.d_in);
     }
+    ix->last_prep_xt = xt;
     return SKNNR_OK;
 }
 
@@ -1580,6 +1600,7 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
     std::fill(std::begin(ix->last_hamming), std::end(ix->last_hamming), 0);
     std::fill(std::begin(ix->last_finalize), std::end(ix->last_finalize), 0);
     std::fill(std::begin(ix->last_scan), std::end(ix->last_scan), 0);
+    std::fill(std::begin(ix->last_prep), std::end(ix->last_prep), 0);
     ix->last_hamming_rows = 0;
     if (xdev && uses_forest(ix, o)) return run_forest(ix, xdev, nq, o, d_dist, d_idx, st);
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
@@ -1711,6 +1732,9 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
             if (!cells_done) HIP_TRY(launch::cell_assign(ca, st));
             HIP_TRY(launch::cell_count(ca, st));
             HIP_TRY(launch::cell_scatter(ca, st));
+            if (!cells_done) ix->last_prep[6] = 2;
+            ix->last_prep_bucketed = true;
+            ix->last_prep_qnc_pos = record;
         }
         HIP_TRY(hipEventRecord(ev.first, st));
         if (v2 && !ix->st_side && !std::getenv("SKNNR_NO_SIDE_STREAM")) {
@@ -2535,6 +2559,7 @@ int merge_shards_device(sknnr_index* ix, const double* xdev, long nq, const sknn
                         const double* shard_val, const long* shard_idx, double* d_dist, long* d_idx, hipStream_t st) {
     std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);  // (no pre-filter runs on this path)
     std::fill(std::begin(ix->last_scan), std::end(ix->last_scan), 0);
+    std::fill(std::begin(ix->last_prep), std::end(ix->last_prep), 0);
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
     const bool affine = o->apply_affine != 0 && xdev != nullptr;
     const bool self_rows = xdev == nullptr;
@@ -2965,5 +2990,54 @@ extern "C" int sknnr_debug_hamming_candidates(const sknnr_index* cix, int32_t* c
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(cnt, ix->h_cand_cnt.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(ids, ix->h_cand_id.p, (size_t)n * kHamCand * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_prep(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::copy(std::begin(ix->last_prep), std::end(ix->last_prep), out);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_query_prep(const sknnr_index* cix, int64_t n, void* qimg, double* qnc, double* xt, uint8_t* cell,
+                                      int32_t* perm, double* qnc_pos) {
+    if (!cix) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    const int64_t* r = ix->last_prep;
+    if (!r[0]) return fail(SKNNR_ERR_INVALID, "the last call ran no query preparation kernel");
+    if (n < 0 || n > r[4]) return fail(SKNNR_ERR_INVALID, "n = %ld rows, the last device chunk has %ld with its padding", (long)n, (long)r[4]);
+    if (xt && !ix->last_prep_xt) return fail(SKNNR_ERR_INVALID, "the last call wrote no transformed rows");
+    if ((cell || perm) && !ix->last_prep_bucketed) return fail(SKNNR_ERR_INVALID, "the last call was not bucketed");
+    if (qnc_pos && !ix->last_prep_qnc_pos) return fail(SKNNR_ERR_INVALID, "the last call filed no |q'|^2 by position");
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t rows = (size_t)n;
+    if (qimg) HIP_TRY(hipMemcpy(qimg, ix->qimg.p, rows * 64 * ix->ks, hipMemcpyDeviceToHost));
+    if (qnc) HIP_TRY(hipMemcpy(qnc, ix->qnc.p, rows * sizeof(double), hipMemcpyDeviceToHost));
+    if (xt) HIP_TRY(hipMemcpy(xt, ix->last_prep_xt, (size_t)std::min<int64_t>(n, r[3]) * ix->d * sizeof(double), hipMemcpyDeviceToHost));
+    if (cell) HIP_TRY(hipMemcpy(cell, ix->qcell.p, rows, hipMemcpyDeviceToHost));
+    if (perm) HIP_TRY(hipMemcpy(perm, ix->qperm.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (qnc_pos) HIP_TRY(hipMemcpy(qnc_pos, ix->qnc_pos.p, rows * sizeof(double), hipMemcpyDeviceToHost));
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_image_constants(const sknnr_index* cix, double* mu, double* s, int32_t* cell_depth, float* axes,
+                                           float* centre, float* thr) {
+    if (!cix) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (ix->ks == 0) return fail(SKNNR_ERR_UNSUPPORTED, "no coarse image (d > 128)");
+    if (mu) std::copy(ix->mu.begin(), ix->mu.begin() + 16 * ix->ks, mu);
+    if (s) *s = ix->s;
+    if (cell_depth) *cell_depth = ix->cell_depth;
+    if ((axes || centre || thr) && ix->cell_depth > 0) {
+        HIP_TRY(hipSetDevice(ix->device));
+        if (axes) HIP_TRY(hipMemcpy(axes, ix->cell_axes.p, (size_t)ix->cell_depth * ix->d * sizeof(float), hipMemcpyDeviceToHost));
+        if (centre) HIP_TRY(hipMemcpy(centre, ix->cell_centre.p, (size_t)ix->d * sizeof(float), hipMemcpyDeviceToHost));
+        if (thr) HIP_TRY(hipMemcpy(thr, ix->cell_thr.p, (((size_t)1 << ix->cell_depth) - 1) * sizeof(float), hipMemcpyDeviceToHost));
+    }
     return SKNNR_OK;
 }
