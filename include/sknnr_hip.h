@@ -447,6 +447,15 @@ int sknnr_debug_last_hamming(const sknnr_index* index, int64_t out[8]);
 int sknnr_debug_last_scan(const sknnr_index* index, int64_t out[8]);
 
 /*
+ * Debug only: the rescue re-sweep of the last call -- the rows the finalisers listed, swept again under the bound their
+ * re-scored candidates give before the float64 scan sees what is left: launched (0: the call was not served, all zero up
+ * to out[6]), K-steps, rows offered (= the growth of exact_fallbacks), rows without a threshold (not rescuable), rows with
+ * more than 16 references under their bound (overflowed), rows rescued, rows handed on to the exact scan; out[7]: rows
+ * rescued by the handle since creation or the last sknnr_reset_stats.  Synchronises the device.
+ */
+int sknnr_debug_last_rescue(const sknnr_index* index, int64_t out[8]);
+
+/*
  * Debug only.  The candidate lists the integer Hamming pre-filter wrote for the first n rows of the last device chunk of
  * the most recent call (n at most that chunk's rows; SKNNR_ERR_INVALID when the pre-filter did not run).  Host memory:
  *   cnt (n)       candidates per row, -1 = the row went to the exact scan (list overflow, or ids outside 16 bits)

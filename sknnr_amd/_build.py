@@ -34,7 +34,7 @@ UNITS = [
     ("k_coarse2_b", "k_coarse2.hip", ["-DSKNNR_C2_PART=1"]),
 ]
 SOURCES = sorted({u[1] for u in UNITS})
-HEADERS = ["launch.hip.h", "coarse.hip.h", "coarse2.hip.h", "bucket.hip.h", "hamming.hip.h", "exact.hip.h", "forest.hip.h",
+HEADERS = ["launch.hip.h", "coarse.hip.h", "coarse2.hip.h", "bucket.hip.h", "hamming.hip.h", "exact.hip.h", "rescue.hip.h", "forest.hip.h",
            "../../include/sknnr_hip.h"]
 
 HIPCC_FLAGS = [

@@ -85,6 +85,7 @@ EXPORTED_SYMBOLS = (
     "sknnr_debug_last_finalize",
     "sknnr_debug_last_hamming",
     "sknnr_debug_last_scan",
+    "sknnr_debug_last_rescue",
     "sknnr_debug_hamming_candidates",
     "sknnr_debug_last_prep",
     "sknnr_debug_query_prep",
@@ -206,6 +207,8 @@ def load(build_if_missing: bool = False):
     lib.sknnr_debug_last_hamming.argtypes = [vp, POINTER(c_int64)]
     if hasattr(lib, "sknnr_debug_last_scan"):  # (likewise)
         lib.sknnr_debug_last_scan.argtypes = [vp, POINTER(c_int64)]
+    if hasattr(lib, "sknnr_debug_last_rescue"):  # (likewise)
+        lib.sknnr_debug_last_rescue.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_hamming_candidates.argtypes = [vp, vp, vp, c_int64]
     if hasattr(lib, "sknnr_debug_last_prep"):  # (likewise)
         lib.sknnr_debug_last_prep.argtypes = [vp, POINTER(c_int64)]
@@ -324,7 +327,10 @@ class Index:
     def stats(self) -> dict:
         st = Stats()
         check(load().sknnr_get_stats(self.handle, byref(st)))
-        return st.as_dict()
+        out = st.as_dict()
+        if hasattr(load(), "sknnr_debug_last_rescue"):
+            out["rescued_rows"] = self.debug_last_rescue()["rescued_total"]
+        return out
 
     def reset_stats(self):
         check(load().sknnr_reset_stats(self.handle))
@@ -494,6 +500,16 @@ class Index:
         out = (c_int64 * 8)()
         check(load().sknnr_debug_last_scan(self.handle, out))
         return dict(zip(self.SCAN_FIELDS, (int(v) for v in out)))
+
+    RESCUE_FIELDS = ("launched", "ks", "offered", "not_rescuable", "overflowed", "rescued", "handed_on", "rescued_total")
+
+    def debug_last_rescue(self) -> dict:
+        """Debug only: the rescue re-sweep of the last call (sknnr_debug_last_rescue): whether it was launched, K-steps, the
+        rows the finalisers listed (offered), those without a threshold, those with more than 16 rows under their bound,
+        the rows rescued and the rows handed on to the exact scan; and the rows rescued since the last reset_stats()."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_rescue(self.handle, out))
+        return dict(zip(self.RESCUE_FIELDS, (int(v) for v in out)))
 
     def debug_hamming_candidates(self, n: int):
         """Debug only: ``(cnt, ids)`` the integer Hamming pre-filter wrote for the first ``n`` rows of the last call's last

@@ -467,7 +467,26 @@ struct FinalizeArgs {
     const float* rec_bound;         // [position] the bound t_min (pair_union_rank of the final lists), NaN = poisoned
     const double* qnc_pos;          // [position] |q'|^2 (cell_scatter_kernel; plain order: qnc itself)
     int* trunc_count;               // rows the truncation rule sent to the exact scan
+    // Rescue re-sweep (rescue.hip.h): beside every fail_list entry, the threshold under which the rows that can still decide
+    // the query lie (rescue_threshold; NaN: not rescuable).  Null: not written.
+    float* fail_thr;
 };
+
+// The rescue threshold of an uncertified query that holds kk re-scored candidates: the smallest float t_resc, rounded up and
+// one ulp above that, with
+//     (qn + t_resc - eps) * inv_s2 - noise > tau
+// -- the certificate's own inequality (finalize_core) with t_resc in the place of t_min.  A row whose pre-filter value is at or
+// above t_resc is then farther than tau, the kk-th re-scored distance, by the certificate's argument: only rows below it can be
+// among the kk nearest or tie with them.  NaN where no float satisfies the inequality as coded (tau or qn not finite,
+// cancellation around zero).
+__device__ __forceinline__ float rescue_threshold(double qn, double tau, double eps, double noise, double s2, double inv_s2) {
+    const double t0 = ((tau + noise) * s2 + eps) - qn;
+    float t = (float)t0;
+    if (!((double)t > t0)) t = nextafterf(t, INFINITY);
+    t = nextafterf(t, INFINITY);
+    const bool ok = (qn + (double)t - eps) * inv_s2 - noise > tau;
+    return ok && t < INFINITY && qn < INFINITY && tau < INFINITY ? t : __builtin_nanf("");
+}
 
 // Lane exchange inside the group of LPQ lanes that share a query.  A group is LPQ/16 DPP rows:
 // peer N = 16 b + r is reached by one ds_bpermute (lane ^ 16 b; identical calls are merged by the
@@ -755,7 +774,20 @@ __device__ __forceinline__ void finalize_core(const FinalizeArgs& a, long q, int
                                (s.deterministic ? c == s.kk - 1 : c < s.kk);  // across the boundary / involving a kept row
         // (raw shard candidates are listed by (value, index); which of the rows tied at a shard's last slot it lists is
         //  settled by the merge, which sees that the shard's list is full and ends at the boundary value)
-        if (!s.raw && group_any<LPQ>(tied_here, gbase)) certified = false;
+        const bool tied = group_any<LPQ>(tied_here, gbase);
+        if (!s.raw && tied) certified = false;
+        // The row goes to the fail list here, while the certificate's terms are at hand (the rare path: the hot path below
+        // keeps its registers).  With kk usable candidates, a finite bound tau and no exact tie among them the row is
+        // rescuable: only reference rows under rescue_threshold can still matter to it.
+        if (live && c == 0 && !certified) {
+            const int slot = atomicAdd(a.fail_count, 1);
+            a.fail_list[slot] = a.fail_base + (int)q;
+            if (a.fail_thr) {
+                const bool rescuable = n_usable >= s.kk && tau < INFINITY && qn < INFINITY && !tied;
+                a.fail_thr[slot] = rescuable ? rescue_threshold(qn, tau, eps, noise, a.s2, a.inv_s2) : __builtin_nanf("");
+            }
+            if (RECORD && truncated) atomicAdd(a.trunc_count, 1);
+        }
     }
 
     // X=None: drop the row's own index, or the first entry when it is absent
@@ -805,11 +837,6 @@ __device__ __forceinline__ void finalize_core(const FinalizeArgs& a, long q, int
     if (live && chosen) {
         if (s.out_dist) s.out_dist[q * s.k + pos] = dist;
         s.out_idx[q * s.k + pos] = id + s.id_offset;
-    }
-    if (live && c == 0 && !certified) {
-        const int slot = atomicAdd(a.fail_count, 1);
-        a.fail_list[slot] = a.fail_base + (int)q;
-        if (RECORD && truncated) atomicAdd(a.trunc_count, 1);
     }
 }
 

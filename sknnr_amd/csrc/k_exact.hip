@@ -1,5 +1,5 @@
-// k_exact.hip -- kernel translation unit: query preparation, bucketing, finaliser, exact scan / merge, predict and the
-// small gather kernels (exact.hip.h, bucket.hip.h), behind the launchers of launch.hip.h.
+// k_exact.hip -- kernel translation unit: query preparation, bucketing, finaliser, rescue re-sweep, exact scan / merge, predict
+// and the small gather kernels (exact.hip.h, rescue.hip.h, bucket.hip.h), behind the launchers of launch.hip.h.
 #define SKNNR_KERNELS_EXACT 1  // this unit defines the non-template kernels of exact.hip.h and bucket.hip.h
 #include <cstdint>
 #include <cstdlib>
@@ -146,6 +146,27 @@ hipError_t crosswalk(const long* table, const long* idx, long n, long* out, hipS
 
 hipError_t add_counter(const int* cnt, long long* total, hipStream_t st) {
     add_counter_kernel<<<dim3(1), dim3(1), 0, st>>>(cnt, total);
+    return hipGetLastError();
+}
+
+template <int KS>
+hipError_t rescue_ks(const RescueArgs& a, hipStream_t st) {
+    rescue_kernel<KS><<<dim3(kRescueGrid), dim3(kRescueWaves * 64), rescue_lds_bytes(a.f.s.d), st>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t rescue(int ks, const RescueArgs& a, hipStream_t st) {
+    switch (ks) {
+        case 1: return rescue_ks<1>(a, st);
+        case 2: return rescue_ks<2>(a, st);
+        case 3: return rescue_ks<3>(a, st);
+        case 4: return rescue_ks<4>(a, st);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t rescue_account(const int* listed, const int* state, long long* total, hipStream_t st) {
+    rescue_account_kernel<<<dim3(1), dim3(1), 0, st>>>(listed, state, total);
     return hipGetLastError();
 }
 

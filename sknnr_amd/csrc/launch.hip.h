@@ -12,6 +12,7 @@
 #include "exact.hip.h"
 #include "forest.hip.h"
 #include "hamming.hip.h"
+#include "rescue.hip.h"
 
 namespace sknnr {
 namespace launch {
@@ -34,6 +35,9 @@ hipError_t pack_shards(const double* val, const long* idx, long nq, int n_shards
 hipError_t predict(const PredictArgs& a, hipStream_t st);
 hipError_t crosswalk(const long* table, const long* idx, long n, long* out, hipStream_t st);
 hipError_t add_counter(const int* cnt, long long* total, hipStream_t st);
+// the rescue re-sweep of the listed rows of one device chunk (rescue.hip.h; ks <= 4) and the call's totals behind it
+hipError_t rescue(int ks, const RescueArgs& a, hipStream_t st);
+hipError_t rescue_account(const int* listed, const int* state, long long* total, hipStream_t st);
 
 // ---- k_hamming.hip ------------------------------------------------------------------------------------------------------
 hipError_t hamming_pack(const double* xq, long nq, long nq_pad, int t, int tp, uint32_t* qimg, int* q_bad, hipStream_t st);

@@ -275,6 +275,13 @@ struct sknnr_index {
     DevBuf<float> rec_bound;
     DevBuf<double> qnc_pos;
     DevBuf<double> slice_v;  // sliced exact scans: the slice heaps (exact.hip.h, scan_slices)
+    // Rescue re-sweep (rescue.hip.h): the thresholds beside fail_list, the second list (what the exact scan still sees) and the
+    // call's device words; fail_total[1] is the running count of rescued rows.  SKNNR_RESCUE=0 (read when the index is
+    // created) keeps every listed row on the exact scan (A/B runs).
+    DevBuf<float> fail_thr;
+    DevBuf<int> resc_list, resc_state;
+    bool rescue_enabled = true;
+    int64_t last_rescue[2] = {};  // the last call (sknnr_debug_last_rescue): launched, KS; the counts are read from resc_state
     DevBuf<int> status;            // bit 0: a query value was NaN, bit 1: infinite (since the last poll)
     DevBuf<long long> fail_total;  // running count of certificate failures (device)
     DevBuf<long> idx_stage;
@@ -362,6 +369,7 @@ struct sknnr_index {
         rec.release(); rec_bound.release(); qnc_pos.release();
         fail_list.release();
         fail_count.release();
+        fail_thr.release(); resc_list.release(); resc_state.release();
         fail_total.release();
         status.release();
         idx_stage.release();
@@ -962,6 +970,11 @@ extern "C" int sknnr_index_create(const double* ref, int64_t n_ref, int32_t d, c
     }
 
     HIP_TRY(ix->fail_count.ensure(4));
+    HIP_TRY(ix->resc_state.ensure(kRescueWords));
+    {
+        const char* e = std::getenv("SKNNR_RESCUE");
+        ix->rescue_enabled = !(e && std::atoi(e) == 0);
+    }
     HIP_TRY(ix->fail_total.ensure(2));
     HIP_TRY(hipMemset(ix->fail_total.p, 0, 16));
     HIP_TRY(ix->status.ensure(4));
@@ -1600,6 +1613,7 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
     std::fill(std::begin(ix->last_hamming), std::end(ix->last_hamming), 0);
     std::fill(std::begin(ix->last_finalize), std::end(ix->last_finalize), 0);
     std::fill(std::begin(ix->last_scan), std::end(ix->last_scan), 0);
+    std::fill(std::begin(ix->last_rescue), std::end(ix->last_rescue), 0);
     std::fill(std::begin(ix->last_prep), std::end(ix->last_prep), 0);
     ix->last_hamming_rows = 0;
     if (xdev && uses_forest(ix, o)) return run_forest(ix, xdev, nq, o, d_dist, d_idx, st);
@@ -1649,6 +1663,17 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
     if (coarse) {
         HIP_TRY(ix->fail_list.ensure(nq));
         HIP_TRY(hipMemsetAsync(ix->fail_count.p, 0, 16, st));
+    }
+    // Rows the finalisers list are first swept again under their rescue thresholds (rescue.hip.h), behind the
+    // second-generation pre-filter (its hi image and query image are what the sweep reads) and up to kRescueMaxKK neighbours
+    // searched (the finish has 16 lanes per row); the exact scan then sees the second list only.
+    const bool rescue = coarse && ix->rescue_enabled && !raw && kk <= kRescueMaxKK && use_coarse2(ix, coarse_list_len(ix, kk));
+    if (rescue) {
+        HIP_TRY(ix->fail_thr.ensure(nq));
+        HIP_TRY(ix->resc_list.ensure(nq));
+        HIP_TRY(hipMemsetAsync(ix->resc_state.p, 0, kRescueWords * sizeof(int), st));
+        ix->last_rescue[0] = 1;
+        ix->last_rescue[1] = ix->ks;
     }
 
     SelectArgs call{};
@@ -1789,6 +1814,7 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
         f.mu2 = o->formula == SKNNR_FORMULA_EXPANDED ? 2.0 * ix->mu_norm : 0.0;
         f.fail_list = ix->fail_list.p;
         f.fail_count = ix->fail_count.p;
+        f.fail_thr = rescue ? ix->fail_thr.p : nullptr;
         f.fail_base = (int)c0;
         // rows [r0, r0 + rows) of the chunk (the kernel indexes everything by the row inside its window); bucketed
         // calls: POSITIONS [r0, r0 + rows) of the chunk, the kernel maps them to rows of the chunk
@@ -1832,6 +1858,31 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
         } else {
             finalize_rows(0, n, st);
             HIP_TRY(hipGetLastError());
+        }
+        if (rescue) {
+            // the rows listed for this chunk, while its query image is in the workspace: one fixed-size launch that reads the
+            // count on the device
+            RescueArgs ra{};
+            ra.f = f;
+            ra.f.s = call;  // finalize_core works on call-relative rows here, as the list names them
+            ra.f.fail_list = ix->resc_list.p;
+            ra.f.fail_count = ix->resc_state.p + kRescueHanded;
+            ra.f.fail_thr = nullptr;
+            ra.f.fail_base = 0;
+            ra.f.rec = nullptr;
+            ra.f.qperm = nullptr;
+            ra.rhi = ix->rhi2.p;
+            ra.n_tiles = ix->n_stages2 * tiles_per_stage2(ix->ks);
+            ra.perm = ix->perm2.p;
+            ra.qimg = ix->qimg.p;
+            ra.qnc = ix->qnc.p;
+            ra.row0 = (int)c0;
+            ra.skip_scale = (float)(std::ldexp(1.0, -9) * ix->ymax * 1.02);  // (launch_coarse2_waves)
+            ra.list = ix->fail_list.p;
+            ra.thr = ix->fail_thr.p;
+            ra.count = ix->fail_count.p;
+            ra.state = ix->resc_state.p;
+            HIP_TRY(launch::rescue(ix->ks, ra, st));
         }
     }
     // Weighted Hamming on 16-bit ids: integer pre-filter, float64 re-score of the candidates (hamming.hip.h); the queries
@@ -1889,12 +1940,14 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
     }
     // One exact scan per call: the rows the finaliser could not certify (call-relative ids), or
     // every row when the call is outside the MFMA envelope.
-    int rc = (coarse || ham_int) ? launch_scan(ix, call, ix->fail_list.p, ix->fail_count.p, nq, st)
-                                 : launch_scan(ix, call, nullptr, nullptr, nq, st);
+    int rc = rescue ? launch_scan(ix, call, ix->resc_list.p, ix->resc_state.p + kRescueHanded, nq, st)
+             : (coarse || ham_int) ? launch_scan(ix, call, ix->fail_list.p, ix->fail_count.p, nq, st)
+                                   : launch_scan(ix, call, nullptr, nullptr, nq, st);
     if (rc) return rc;
     if (coarse) {
         // keep a running total on the device; sknnr_get_stats reads it (no sync here)
-        HIP_TRY(launch::add_counter(ix->fail_count.p, ix->fail_total.p, st));
+        if (rescue) HIP_TRY(launch::rescue_account(ix->fail_count.p, ix->resc_state.p, ix->fail_total.p, st));
+        else HIP_TRY(launch::add_counter(ix->fail_count.p, ix->fail_total.p, st));
         ix->stats.coarse_queries += nq;
     } else {
         // (weighted Hamming: the rows the integer pre-filter could not serve -- list overflow, ids beyond 16 bits -- count as
@@ -2559,6 +2612,7 @@ int merge_shards_device(sknnr_index* ix, const double* xdev, long nq, const sknn
                         const double* shard_val, const long* shard_idx, double* d_dist, long* d_idx, hipStream_t st) {
     std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);  // (no pre-filter runs on this path)
     std::fill(std::begin(ix->last_scan), std::end(ix->last_scan), 0);
+    std::fill(std::begin(ix->last_rescue), std::end(ix->last_rescue), 0);
     std::fill(std::begin(ix->last_prep), std::end(ix->last_prep), 0);
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
     const bool affine = o->apply_affine != 0 && xdev != nullptr;
@@ -2973,9 +3027,38 @@ extern "C" int sknnr_debug_last_scan(const sknnr_index* cix, int64_t out[8]) {
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(cnt, ix->fail_count.p, sizeof cnt, hipMemcpyDeviceToHost));
         if (r[5] < 0) out[5] = cnt[0];
+        if (r[5] < 0 && ix->last_rescue[0]) {  // the scan consumed the rescue's second list
+            int handed = 0;
+            HIP_TRY(hipMemcpy(&handed, ix->resc_state.p + kRescueHanded, sizeof handed, hipMemcpyDeviceToHost));
+            out[5] = handed;
+        }
         if (r[7]) out[7] = cnt[2];
     }
     if (!r[6]) out[6] = scan_slices(out[5], scan_nq((int)r[0] - 1), (int)ix->n_ref, (int)r[2], (int)r[3]);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_rescue(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::fill(out, out + 8, 0);
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());
+    long long total[2] = {0, 0};
+    HIP_TRY(hipMemcpy(total, ix->fail_total.p, sizeof total, hipMemcpyDeviceToHost));
+    out[7] = total[1];
+    if (!ix->last_rescue[0]) return SKNNR_OK;
+    // (the workspace is the handle's: no later call has touched it, or the record would be zero)
+    int w[kRescueWords];
+    HIP_TRY(hipMemcpy(w, ix->resc_state.p, sizeof w, hipMemcpyDeviceToHost));
+    out[0] = 1;
+    out[1] = ix->last_rescue[1];
+    out[2] = w[kRescueOffered];
+    out[3] = w[kRescueNoThr];
+    out[4] = w[kRescueOverflow];
+    out[5] = w[kRescueOffered] - w[kRescueHanded];
+    out[6] = w[kRescueHanded];
     return SKNNR_OK;
 }
 
