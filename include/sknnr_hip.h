@@ -367,6 +367,58 @@ int sknnr_stream_push(sknnr_stream* stream, const void* q, int64_t nq, double* o
 int sknnr_stream_flush(sknnr_stream* stream);
 int sknnr_stream_end(sknnr_stream* stream, int64_t* rows_pushed);
 
+/* ---- nodata rows (raster masks) ------------------------------------------------------------ */
+
+/*
+ * Real rasters carry nodata: pixels outside the study area, cloud and water masks, per-band sentinels such as -32768 or
+ * 255.  The reference has no notion of them; its user drops those pixels first -- valid = (X != nodata).all(1);
+ * est.kneighbors(X[valid]) -- and scatters the answers back.  The entry points below do the three steps on the device
+ * (sknnr_amd/csrc/mask.hip.h): mask, stable compaction, the ordinary search on the packed rows, expansion.
+ *
+ *   nodata : HOST, (d_in) float64, one value per RAW input column (the columns the call reads, before any affine map or
+ *            forest map).  A row is masked when any column, widened exactly to float64, equals its nodata value; a NaN
+ *            entry means "NaN in that column is nodata".
+ *   Valid rows are answered exactly as the unmasked call answers X[valid], bit for bit; row positions (key 2 of the
+ *   reorder, REF _base.py:171) count valid rows only, over the whole logical call.
+ *   Masked rows get fill_index in out_idx and NaN in out_dist / out_pred.  They are not tested for finiteness and cost
+ *   no search work (sknnr_stats.queries grows by the valid rows only).
+ *
+ * sknnr_mask_rows: the mask alone, no handle.  q (nq, d_in) rows of query_dtype and out_valid (nq) uint8, 1 = valid, in
+ *   `mem` on `device`; *out_n_valid (host) the number of valid rows.  Returns when both are written.
+ * sknnr_kneighbors_masked / sknnr_predict_masked: the arguments of sknnr_kneighbors / sknnr_predict plus nodata,
+ *   fill_index and *out_n_valid (host, optional).  q must be given and opts->exclude_self must be 0.  The host reads the
+ *   valid count (one 8-byte copy) before it enqueues the search, so device-memory calls synchronise `stream` once; a
+ *   fully valid tile is searched in place, a fully masked one only filled.  The sharded entry points take no mask.
+ * sknnr_stream_set_nodata: allowed only before the first push (SKNNR_ERR_INVALID afterwards).  Every pushed tile is
+ *   then masked behind its host-to-device copy, and the stream carries the running count of VALID rows as the row
+ *   offset.  Results reach the host in full layout, fills included.  sknnr_stream_end's rows_pushed stays the pushed
+ *   rows; sknnr_stream_valid_rows gives the valid ones submitted so far.
+ */
+int sknnr_mask_rows(const void* q, int64_t nq, int32_t d_in, int32_t query_dtype, const double* nodata, int32_t device,
+                    int32_t mem, void* stream, uint8_t* out_valid, int64_t* out_n_valid);
+int sknnr_kneighbors_masked(sknnr_index* index, const void* q, int64_t nq, const sknnr_query_opts* opts,
+                            const double* nodata, int64_t fill_index, double* out_dist, int64_t* out_idx, int32_t mem,
+                            void* stream, int64_t* out_n_valid);
+int sknnr_predict_masked(sknnr_index* index, const void* q, int64_t nq, const sknnr_query_opts* opts,
+                         const double* nodata, int64_t fill_index, double* out_pred, double* out_dist, int64_t* out_idx,
+                         int32_t mem, void* stream, int64_t* out_n_valid);
+int sknnr_stream_set_nodata(sknnr_stream* stream, const double* nodata, int64_t fill_index);
+int sknnr_stream_valid_rows(const sknnr_stream* stream, int64_t* out_valid_rows);
+
+/*
+ * Debug only.  The nodata front end of the most recent call on the handle (its last tile), so that a test can prove
+ * which path served it.  Host memory, no device work:
+ *   out[0] 1 = the mask ran, 0 = it did not (then out[1 .. 7] = 0)
+ *   out[1] rows of the last tile                out[2] its valid rows
+ *   out[3] 1 = every row valid: searched in place, no compaction or expansion; 2 = every row masked: the fill alone;
+ *          0 = compacted, searched, expanded
+ *   out[4] workgroups of row_mask_kernel        out[5] bytes of a row
+ *   out[6] valid rows of the whole call, or of the stream so far
+ *   out[7] 0
+ * Every search call zeroes the record first.
+ */
+int sknnr_debug_last_mask(const sknnr_index* index, int64_t out[8]);
+
 /*
  * Dataframe-index crosswalk: out[i] = table[idx[i]].
  * Replaces self.dataframe_index_in_[neigh_ind] (REF _base.py:177-180) for int64 plot IDs.

@@ -63,6 +63,28 @@ def _effective_metric(metric, p, metric_params):
         f"metric={metric!r} is not supported by the MI355X backend (Euclidean metric only)")
 
 
+def normalize_nodata(nodata, n_features, dtype):
+    """The ``nodata`` argument of the streamed calls as float64 ``(n_features,)``: a scalar stands for every column, a
+    sequence gives one value per RAW input column (before any affine or forest map).  A row is masked when any column
+    equals its value; a NaN entry means "NaN in that column is nodata", which only float rows can hold: for an integer
+    ``dtype`` it is refused."""
+    try:
+        arr = np.asarray(nodata, dtype=np.float64)
+    except (TypeError, ValueError) as err:
+        raise ValueError(f"nodata must be a number or a sequence of {n_features} numbers, got {nodata!r}") from err
+    if arr.ndim == 0:
+        arr = np.full(n_features, float(arr), dtype=np.float64)
+    elif arr.ndim != 1 or arr.shape[0] != n_features:
+        raise ValueError(f"nodata must be a scalar or hold one value per input column: expected {n_features}, "
+                         f"got shape {arr.shape}")
+    if np.dtype(dtype).kind in "iub":
+        bad = np.flatnonzero(np.isnan(arr))
+        if bad.size:
+            raise ValueError(f"nodata for column {int(bad[0])} is NaN, but the rows are {np.dtype(dtype)}: an integer "
+                             "column cannot hold NaN")
+    return np.ascontiguousarray(arr)
+
+
 def _resolve_fit_method(algorithm, n_ref, d, k):
     """Which of the reference's engines -- hence which float64 distance expression -- the
     ``algorithm`` setting selects (SKL/neighbors/_base.py:620-648)."""
@@ -534,13 +556,27 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         return self._predict_engine(X, apply_affine=False)
 
     # -- streamed tiles (raster ingestion; REF docs/pages/usage.md:101-128) --------------------
+    def _check_nodata_supported(self, nodata):
+        """The nodata mask runs in front of the device search of a native stream; the paths that answer tile by tile on
+        the host refuse it."""
+        if nodata is None:
+            return
+        if self._numpy_ties():
+            raise NotImplementedError("nodata is not supported under hamming_tie_policy('numpy'): tied rows are chosen "
+                                      "on the host, tile by tile; use the default policy 'lowest_index'")
+        if self._tree_ties():
+            raise NotImplementedError("nodata is not supported under tree_tie_policy('tree'): tied rows are chosen on "
+                                      "the host, tile by tile; use the default policy 'lowest_index'")
+
     def _stream_tiles(self, tiles, validate, k, *, apply_affine, weights, return_distance,
-                      use_deterministic_ordering, out, owner):
+                      use_deterministic_ordering, out, owner, nodata=None, fill_index=-1):
         """Push host tiles through one native query stream.  Returns (dist, idx, pred) arrays over all
-        pushed rows (pieces of ``out`` when given, else concatenated)."""
+        pushed rows (pieces of ``out`` when given, else concatenated).  ``nodata`` (float64, one value per column of the
+        validated tiles): rows holding one are masked on the device and get ``fill_index`` / NaN."""
         eng = self.engine_
         want_pred = weights is not None
         t_cols = eng.t
+        self._check_nodata_supported(nodata)
         if self._reference_ties():
             # the reference's choice among tied rows is made on the host, per call: tile by tile, positions carried
             parts, row = [], 0
@@ -584,10 +620,13 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                     # the element type of the first tile is the stream's (narrow rasters travel at their own width)
                     code = eng.query_dtype_code(tile, self._formula(), apply_affine)
                     stream_dtype = tile.dtype if code else np.dtype(np.float64)
+                    if nodata is not None:  # (a NaN entry needs rows that can hold NaN)
+                        nodata = normalize_nodata(nodata, tile.shape[1], stream_dtype)
                     stream = eng.open_stream(k, weights=weights, want_dist=return_distance,
                                              deterministic=use_deterministic_ordering,
                                              decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula(),
-                                             apply_affine=apply_affine, check_finite=True, query_dtype=code)
+                                             apply_affine=apply_affine, check_finite=True, query_dtype=code,
+                                             nodata=nodata, fill_index=fill_index)
                 if tile.dtype != stream_dtype:
                     if stream_dtype != np.float64:
                         raise ValueError(f"the tiles of one streamed call must share an element type: got {tile.dtype} "
@@ -631,26 +670,48 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 cat(2, t_cols, np.float64) if want_pred else None)
 
     def kneighbors_chunks(self, tiles, n_neighbors=None, return_distance=True, return_dataframe_index=False,
-                          use_deterministic_ordering=True, out=None):
+                          use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1):
         """``kneighbors`` over an iterable of host tiles ``(n_i, n_features)`` -- windows of a raster,
         slices of a ``numpy.memmap`` -- as ONE logical call: the copy-in / kernels / copy-out pipeline
         stays full across tiles and row positions count over all tiles, so the result equals
         ``kneighbors(np.concatenate(tiles))`` bit for bit.  ``out=(dist, idx)`` (``dist`` may be None):
-        preallocated arrays (e.g. memmaps) that receive the rows in order."""
+        preallocated arrays (e.g. memmaps) that receive the rows in order.
+
+        ``nodata``: a scalar, or one value per input column (NaN: "NaN in that column").  Rows in which any column
+        equals its nodata value are masked on the device: they cost no search, are not tested for finiteness and get
+        ``fill_index`` (as index or dataframe id) and NaN distances; the other rows get exactly what
+        ``kneighbors(X[valid])`` returns, row positions counting valid rows only."""
         check_is_fitted(self, "_fit_X")
         k = self._resolve_k(n_neighbors)
+        if nodata is not None:
+            nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
         o = None if out is None else (out[0], out[1], None)
+        # (dataframe ids: masked rows travel as -1, which no row index equals, and take fill_index after the crosswalk)
         dist, idx, _ = self._stream_tiles(tiles, self._validate_query, k, apply_affine=False, weights=None,
                                           return_distance=return_distance,
-                                          use_deterministic_ordering=use_deterministic_ordering, out=o, owner=None)
-        return self._finish_chunks(dist, idx, return_distance, return_dataframe_index)
+                                          use_deterministic_ordering=use_deterministic_ordering, out=o, owner=None,
+                                          nodata=nodata, fill_index=-1 if return_dataframe_index else fill_index)
+        return self._finish_chunks(dist, idx, return_distance, return_dataframe_index,
+                                   fill_index=None if nodata is None else fill_index)
 
-    def _finish_chunks(self, dist, idx, return_distance, return_dataframe_index):
+    def _finish_chunks(self, dist, idx, return_distance, return_dataframe_index, fill_index=None):
+        """``fill_index`` (a masked call): rows whose index is -1 are nodata rows and get it instead of a table entry."""
         if return_dataframe_index:
             msg = "Dataframe indexes can only be returned when fitted with a dataframe."
             check_is_fitted(self, "dataframe_index_in_", msg=msg)
             table = self.dataframe_index_in_
-            if table.dtype == np.int64:
+            if fill_index is not None:
+                if table.dtype == np.int64:
+                    step = 1 << 22
+                    for a in range(0, idx.shape[0], step):
+                        blk = idx[a:a + step]
+                        masked = blk < 0
+                        idx[a:a + step] = np.where(masked, fill_index, table[np.where(masked, 0, blk)])
+                else:
+                    masked = idx < 0
+                    idx = table[np.where(masked, 0, idx)]
+                    idx[masked] = fill_index
+            elif table.dtype == np.int64:
                 step = 1 << 22  # in place, block by block: idx may be a memmap larger than memory
                 for a in range(0, idx.shape[0], step):
                     idx[a:a + step] = table[idx[a:a + step]]
@@ -658,14 +719,20 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 idx = table[idx]
         return (dist, idx) if return_distance else idx
 
-    def predict_chunks(self, tiles, out=None):
+    def predict_chunks(self, tiles, out=None, nodata=None):
         """``predict`` over an iterable of host tiles as one streamed call; ``out``: preallocated
-        ``(n_rows, n_targets)`` float64 array (e.g. a memmap; float32 results are held exactly)."""
+        ``(n_rows, n_targets)`` float64 array (e.g. a memmap; float32 results are held exactly).  ``nodata`` as in
+        :meth:`kneighbors_chunks`: masked rows are predicted NaN."""
         check_is_fitted(self, "_fit_X")
-        return self._predict_chunks(tiles, self._validate_query, apply_affine=False, out=out, owner=None)
+        if nodata is not None:
+            nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
+        return self._predict_chunks(tiles, self._validate_query, apply_affine=False, out=out, owner=None, nodata=nodata)
 
-    def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner):
+    def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None):
         weights = "uniform" if self.weights is None else self.weights
+        if callable(weights) and nodata is not None:
+            raise NotImplementedError("nodata is not supported with callable weights: the callable runs on the host "
+                                      "between the search and the reduction, tile by tile; use 'uniform' or 'distance'")
         if callable(weights):  # a Python callable runs between the search and the reduction: tile by tile
             # (the reorder's second key is the row's position in the WHOLE call: carry it from tile to tile)
             preds, row = [], 0
@@ -681,7 +748,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             o = None if out is None else (None, None, out.reshape(out.shape[0], -1))
             _, _, pred = self._stream_tiles(tiles, validate, self.n_neighbors, apply_affine=apply_affine,
                                             weights=weights, return_distance=False,
-                                            use_deterministic_ordering=True, out=o, owner=owner)
+                                            use_deterministic_ordering=True, out=o, owner=owner, nodata=nodata)
             if out is None:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
                 pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         return pred.reshape(-1) if self._y.ndim == 1 else pred
@@ -844,25 +911,40 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         return self._host_result(X, self.regressor_._predict_engine(X, apply_affine=X is not None and self._map_on_device(),
                                                                     owner=self.transformer_))
 
+    def _raw_nodata(self, nodata):
+        """``nodata`` of a streamed call, one value per UNTRANSFORMED input column: the mask reads the raw rows, so they
+        must reach the engine raw (affine map or forests on the device)."""
+        if nodata is None:
+            return None
+        if not self._map_on_device():
+            raise NotImplementedError(f"nodata is not supported by {type(self).__name__}: its transformer runs on the "
+                                      "host, so the raw rows never reach the device")
+        return normalize_nodata(nodata, self.regressor_.engine_.d_in, np.float64)
+
     def kneighbors_chunks(self, tiles, n_neighbors=None, return_distance=True, return_dataframe_index=False,
-                          use_deterministic_ordering=True, out=None):
+                          use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1):
         """``kneighbors`` over an iterable of untransformed host tiles as one streamed call (see
-        :meth:`RawKNNRegressor.kneighbors_chunks`); each tile is transformed on the device."""
+        :meth:`RawKNNRegressor.kneighbors_chunks`, also for ``nodata`` / ``fill_index``: the nodata values are those of
+        the untransformed columns); each tile is transformed on the device."""
         check_is_fitted(self, "regressor_")
         reg = self.regressor_
         k = reg._resolve_k(n_neighbors)
+        nodata = self._raw_nodata(nodata)
         o = None if out is None else (out[0], out[1], None)
         dist, idx, _ = reg._stream_tiles(tiles, self._validate_raw_query, k, apply_affine=self._map_on_device(), weights=None,
                                          return_distance=return_distance,
                                          use_deterministic_ordering=use_deterministic_ordering, out=o,
-                                         owner=self.transformer_)
-        return reg._finish_chunks(dist, idx, return_distance, return_dataframe_index)
+                                         owner=self.transformer_, nodata=nodata,
+                                         fill_index=-1 if return_dataframe_index else fill_index)
+        return reg._finish_chunks(dist, idx, return_distance, return_dataframe_index,
+                                  fill_index=None if nodata is None else fill_index)
 
-    def predict_chunks(self, tiles, out=None):
-        """``predict`` over an iterable of untransformed host tiles as one streamed call."""
+    def predict_chunks(self, tiles, out=None, nodata=None):
+        """``predict`` over an iterable of untransformed host tiles as one streamed call (``nodata``: masked rows are
+        predicted NaN, see :meth:`RawKNNRegressor.kneighbors_chunks`)."""
         check_is_fitted(self, "regressor_")
         return self.regressor_._predict_chunks(tiles, self._validate_raw_query, apply_affine=self._map_on_device(),
-                                               out=out, owner=self.transformer_)
+                                               out=out, owner=self.transformer_, nodata=self._raw_nodata(nodata))
 
     def score(self, X, y):
         """REF _base.py:350-352."""

@@ -158,13 +158,22 @@ class KNNEngine:
 
     def kneighbors(self, X, k, *, exclude_self=False, deterministic=True, decimals=10,
                    formula="expanded", apply_affine=False, row_offset=0, n_self_rows=None,
-                   return_distance=True, out=None, check_finite=False):
+                   return_distance=True, out=None, check_finite=False, nodata=None, fill_index=-1):
         """Neighbours of the rows of ``X`` (numpy -> numpy, torch.cuda -> torch.cuda), or of
         the reference rows ``[row_offset, row_offset + n_self_rows)`` when ``X`` is None.
         ``out=(dist, idx)``: contiguous float64 / int64 CUDA tensors of shape ``(nq, k)`` to write
         into (torch.cuda input only), e.g. this rank's slot of an all-gather buffer.
         ``check_finite``: the kernels that read ``X`` also test it for NaN / infinity and the call
-        raises ``HipBackendError(ERR_NONFINITE)`` (for CUDA tensors this synchronises the stream)."""
+        raises ``HipBackendError(ERR_NONFINITE)`` (for CUDA tensors this synchronises the stream).
+        ``nodata`` (float64, one value per column of ``X``; NaN: "is NaN"): rows holding a nodata value are masked on the
+        device -- they get ``fill_index`` / NaN and cost no search -- and the others are answered as ``X[valid]`` would
+        be (for CUDA tensors the stream is synchronised once, to read the valid count)."""
+        if nodata is not None:
+            if X is None:
+                raise ValueError("nodata needs query rows: X=None has none")
+            nodata = np.ascontiguousarray(nodata, dtype=np.float64).reshape(-1)
+            if nodata.size != X.shape[1]:
+                raise ValueError(f"nodata must hold one value per column of X ({X.shape[1]}), got {nodata.size}")
         qdt = self.query_dtype_code(X, formula, apply_affine)
         opts = self._opts(k, exclude_self=exclude_self, deterministic=deterministic,
                           decimals=decimals, formula=formula,
@@ -195,9 +204,13 @@ class KNNEngine:
                 dist = torch.empty((nq, k), dtype=torch.float64, device=X.device) if return_distance else None
             if nq:
                 stream = torch.cuda.current_stream(X.device).cuda_stream
-                self._index.kneighbors_device(X.data_ptr(), nq, opts,
-                                              dist.data_ptr() if dist is not None else 0,
-                                              idx.data_ptr(), stream)
+                if nodata is not None:
+                    self._index.kneighbors_masked_device(X.data_ptr(), nq, opts, nodata, fill_index,
+                                                         dist.data_ptr() if dist is not None else 0, idx.data_ptr(), stream)
+                else:
+                    self._index.kneighbors_device(X.data_ptr(), nq, opts,
+                                                  dist.data_ptr() if dist is not None else 0,
+                                                  idx.data_ptr(), stream)
                 if check_finite:
                     self._index.check_finite(stream)
             return dist, idx
@@ -205,6 +218,8 @@ class KNNEngine:
             raise ValueError("out= is only supported for torch.cuda inputs")
         X = np.ascontiguousarray(X) if qdt else np.ascontiguousarray(X, dtype=np.float64)
         self._check_columns(X, apply_affine)
+        if nodata is not None:
+            return self._index.kneighbors_masked_host(X, opts, nodata, fill_index, return_distance=return_distance)[:2]
         return self._index.kneighbors_host(X, opts, return_distance=return_distance)
 
     def weight_mode(self, weights, w32=False) -> int:
@@ -260,11 +275,20 @@ class KNNEngine:
         return pred if out_dtype == np.float64 else pred.astype(np.float32)
 
     def predict(self, X, k, weights="uniform", *, exclude_self=False, deterministic=True, decimals=10,
-                formula="expanded", apply_affine=False, row_offset=0, n_self_rows=None, check_finite=False):
+                formula="expanded", apply_affine=False, row_offset=0, n_self_rows=None, check_finite=False,
+                nodata=None):
         """Weighted multi-output mean of the neighbours' targets, in the dtype scikit-learn returns
-        (:meth:`pred_dtype`)."""
+        (:meth:`pred_dtype`).  ``nodata`` as in :meth:`kneighbors`: masked rows are predicted NaN."""
         if self.t < 1:
             raise ValueError("the engine was built without targets")
+        if nodata is not None:
+            if X is None:
+                raise ValueError("nodata needs query rows: X=None has none")
+            if callable(weights):
+                raise NotImplementedError("nodata is not supported with callable weights")
+            nodata = np.ascontiguousarray(nodata, dtype=np.float64).reshape(-1)
+            if nodata.size != X.shape[1]:
+                raise ValueError(f"nodata must hold one value per column of X ({X.shape[1]}), got {nodata.size}")
         if callable(weights):
             # A Python callable cannot run on the device: find the neighbours on the GPU, let
             # the callable map the (nq, k) distances to weights on the host, reduce on the GPU.
@@ -293,13 +317,16 @@ class KNNEngine:
             pred = torch.empty((nq, self.t), dtype=torch.float64, device=X.device)
             if nq:
                 stream = torch.cuda.current_stream(X.device).cuda_stream
-                self._index.predict_device(X.data_ptr(), nq, opts, pred.data_ptr(), 0, 0, stream)
+                if nodata is not None:
+                    self._index.predict_masked_device(X.data_ptr(), nq, opts, nodata, -1, pred.data_ptr(), 0, 0, stream)
+                else:
+                    self._index.predict_device(X.data_ptr(), nq, opts, pred.data_ptr(), 0, 0, stream)
                 if check_finite:
                     self._index.check_finite(stream)
             return pred.to(torch.float32) if to32 else pred
         X = np.ascontiguousarray(X) if qdt else np.ascontiguousarray(X, dtype=np.float64)
         self._check_columns(X, apply_affine)
-        pred = self._index.predict_host(X, opts)
+        pred = self._index.predict_masked_host(X, opts, nodata)[0] if nodata is not None else self._index.predict_host(X, opts)
         return pred.astype(np.float32) if to32 else pred
 
     # ---- reference-sharded search (sknnr_amd.distributed.RefShardedKNN) ------------------------------------
@@ -352,11 +379,13 @@ class KNNEngine:
         return self._index.merge_shards_host(X, opts, shard_val, shard_idx, nq=nq)
 
     def open_stream(self, k, *, weights=None, want_dist=True, deterministic=True, decimals=10,
-                    formula="expanded", apply_affine=False, row_offset=0, check_finite=False, query_dtype=0):
+                    formula="expanded", apply_affine=False, row_offset=0, check_finite=False, query_dtype=0,
+                    nodata=None, fill_index=-1):
         """A :class:`sknnr_amd._native.QueryStream` over host tiles: ``push(tile)`` keeps the PCIe
         pipeline full across tiles and carries the global row offset.  ``weights`` (``"uniform"`` /
         ``"distance"``) also asks for predictions: float64 arrays, holding binary32 values where
-        :meth:`pred_dtype` is float32."""
+        :meth:`pred_dtype` is float32.  ``nodata`` (float64, one value per column of the tiles): every tile is masked on
+        the device, masked rows get ``fill_index`` / NaN and the row offset counts valid rows only."""
         want_pred = weights is not None
         if want_pred and weights not in _WEIGHT_MODES:
             raise ValueError("a stream predicts with 'uniform' or 'distance' weights only")
@@ -364,7 +393,7 @@ class KNNEngine:
                           formula=formula, apply_affine=apply_affine,
                           weight_mode=self.weight_mode(weights) if want_pred else _native.WEIGHTS_UNIFORM,
                           row_offset=row_offset, check_finite=check_finite, query_dtype=query_dtype)
-        return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred)
+        return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred, nodata=nodata, fill_index=fill_index)
 
     def hamming_distances(self, X, rows=None):
         """Full weighted-Hamming distance rows of ``X[rows]`` (``X`` None: of the fitted rows) from the device."""

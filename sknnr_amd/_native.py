@@ -79,6 +79,12 @@ EXPORTED_SYMBOLS = (
     "sknnr_stream_push",
     "sknnr_stream_flush",
     "sknnr_stream_end",
+    "sknnr_mask_rows",
+    "sknnr_kneighbors_masked",
+    "sknnr_predict_masked",
+    "sknnr_stream_set_nodata",
+    "sknnr_stream_valid_rows",
+    "sknnr_debug_last_mask",
     "sknnr_crosswalk",
     "sknnr_debug_coarse_matrix",
     "sknnr_debug_last_prefilter",
@@ -191,6 +197,14 @@ def load(build_if_missing: bool = False):
     lib.sknnr_stream_push.argtypes = [vp, vp, c_int64, vp, vp, vp]
     lib.sknnr_stream_flush.argtypes = [vp]
     lib.sknnr_stream_end.argtypes = [vp, POINTER(c_int64)]
+    lib.sknnr_mask_rows.argtypes = [vp, c_int64, c_int32, c_int32, vp, c_int32, c_int32, vp, vp, POINTER(c_int64)]
+    lib.sknnr_kneighbors_masked.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), vp, c_int64, vp, vp, c_int32, vp,
+                                            POINTER(c_int64)]
+    lib.sknnr_predict_masked.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), vp, c_int64, vp, vp, vp, c_int32, vp,
+                                         POINTER(c_int64)]
+    lib.sknnr_stream_set_nodata.argtypes = [vp, vp, c_int64]
+    lib.sknnr_stream_valid_rows.argtypes = [vp, POINTER(c_int64)]
+    lib.sknnr_debug_last_mask.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_kneighbors.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), vp, vp, c_int32, vp]
     lib.sknnr_predict.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), vp, vp, vp, c_int32, vp]
     lib.sknnr_predict_from_neighbors.argtypes = [vp, vp, vp, vp, c_int64, c_int32, c_int32, vp,
@@ -348,8 +362,17 @@ class Index:
         (synchronises ``stream``); raises :class:`HipBackendError` (``ERR_NONFINITE``)."""
         check(load().sknnr_check_finite(self.handle, c_void_p(stream or None)))
 
-    def open_stream(self, opts: QueryOpts, want_dist=True, want_pred=False) -> "QueryStream":
-        return QueryStream(self, opts, want_dist, want_pred)
+    def open_stream(self, opts: QueryOpts, want_dist=True, want_pred=False, nodata=None, fill_index=-1) -> "QueryStream":
+        """``nodata``: float64 ``(d_in,)``, one value per column of the pushed rows -- every tile is then masked on the
+        device (sknnr_stream_set_nodata) and masked rows get ``fill_index`` / NaN."""
+        stream = QueryStream(self, opts, want_dist, want_pred)
+        if nodata is not None:
+            try:
+                stream.set_nodata(nodata, fill_index)
+            except Exception:
+                stream.close()
+                raise
+        return stream
 
     # ---- host (numpy) entry points --------------------------------------------------------
     def kneighbors_host(self, q, opts: QueryOpts, nq=None, return_distance=True):
@@ -386,6 +409,64 @@ class Index:
                                                   _host_ptr(w), nq, k, int(weight_mode),
                                                   _host_ptr(pred), MEM_HOST, None))
         return pred
+
+    # ---- nodata rows (include/sknnr_hip.h, "nodata rows") -----------------------------------
+    def kneighbors_masked_host(self, q, opts: QueryOpts, nodata, fill_index=-1, return_distance=True):
+        """``(dist, idx, n_valid)`` of the rows ``q`` with the rows that hold a nodata value masked on the device: they
+        get ``fill_index`` / NaN, the others what the unmasked call gives for ``q[valid]``."""
+        q = _c_rows(q, opts)
+        nodata = _c_f64(nodata)
+        nq, k = q.shape[0], opts.n_neighbors
+        idx = np.empty((nq, k), dtype=np.int64)
+        dist = np.empty((nq, k), dtype=np.float64) if return_distance else None
+        nv = c_int64(0)
+        check(load().sknnr_kneighbors_masked(self.handle, _host_ptr(q), nq, byref(opts), _host_ptr(nodata),
+                                             int(fill_index), _host_ptr(dist), _host_ptr(idx), MEM_HOST, None, byref(nv)))
+        return dist, idx, int(nv.value)
+
+    def predict_masked_host(self, q, opts: QueryOpts, nodata, fill_index=-1, return_neighbors=False):
+        q = _c_rows(q, opts)
+        nodata = _c_f64(nodata)
+        nq, k = q.shape[0], opts.n_neighbors
+        pred = np.empty((nq, self.t), dtype=np.float64)
+        dist = idx = None
+        if return_neighbors:
+            dist = np.empty((nq, k), dtype=np.float64)
+            idx = np.empty((nq, k), dtype=np.int64)
+        nv = c_int64(0)
+        check(load().sknnr_predict_masked(self.handle, _host_ptr(q), nq, byref(opts), _host_ptr(nodata), int(fill_index),
+                                          _host_ptr(pred), _host_ptr(dist), _host_ptr(idx), MEM_HOST, None, byref(nv)))
+        return (pred, dist, idx, int(nv.value)) if return_neighbors else (pred, int(nv.value))
+
+    def kneighbors_masked_device(self, q_ptr, nq, opts: QueryOpts, nodata, fill_index, dist_ptr, idx_ptr, stream=0) -> int:
+        """Device pointers in and out (``nodata`` stays a host array); returns the valid rows.  Synchronises ``stream``
+        once, for the 8-byte read of that count."""
+        nodata = _c_f64(nodata)
+        nv = c_int64(0)
+        check(load().sknnr_kneighbors_masked(self.handle, c_void_p(q_ptr or None), nq, byref(opts), _host_ptr(nodata),
+                                             int(fill_index), c_void_p(dist_ptr or None), c_void_p(idx_ptr), MEM_DEVICE,
+                                             c_void_p(stream or None), byref(nv)))
+        return int(nv.value)
+
+    def predict_masked_device(self, q_ptr, nq, opts: QueryOpts, nodata, fill_index, pred_ptr, dist_ptr=0, idx_ptr=0,
+                              stream=0) -> int:
+        nodata = _c_f64(nodata)
+        nv = c_int64(0)
+        check(load().sknnr_predict_masked(self.handle, c_void_p(q_ptr or None), nq, byref(opts), _host_ptr(nodata),
+                                          int(fill_index), c_void_p(pred_ptr), c_void_p(dist_ptr or None),
+                                          c_void_p(idx_ptr or None), MEM_DEVICE, c_void_p(stream or None), byref(nv)))
+        return int(nv.value)
+
+    MASK_FIELDS = ("ran", "rows", "valid_rows", "path", "mask_blocks", "row_bytes", "valid_total", "reserved")
+
+    def debug_last_mask(self) -> dict:
+        """Debug only: the nodata front end of the last call's last tile (sknnr_debug_last_mask): whether the mask ran,
+        the tile's rows and valid rows, the path (1: every row valid, searched in place; 2: every row masked, the fill
+        alone; 0: compacted and expanded), workgroups of the mask kernel, bytes of a row, and the valid rows of the whole
+        call or of the stream so far."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_mask(self.handle, out))
+        return dict(zip(self.MASK_FIELDS, (int(v) for v in out)))
 
     # ---- device-pointer entry points (ints from tensor.data_ptr()) ------------------------
     def kneighbors_device(self, q_ptr, nq, opts: QueryOpts, dist_ptr, idx_ptr, stream=0):
@@ -607,6 +688,20 @@ class QueryStream:
             del self._keep[:-8]  # older tiles have left the pipeline (four slots: at most the last four pushes are pending)
         return out_idx, out_dist, out_pred
 
+    def set_nodata(self, nodata, fill_index=-1):
+        """Mask every pushed tile on the device (sknnr_stream_set_nodata; only before the first push)."""
+        nodata = _c_f64(nodata).reshape(-1)
+        cols = self._index.d_in if self._opts.apply_affine else self._index.d
+        if nodata.size != cols:
+            raise ValueError(f"nodata must hold one value per input column ({cols}), got {nodata.size}")
+        check(load().sknnr_stream_set_nodata(self._h, _host_ptr(nodata), int(fill_index)))
+
+    def valid_rows(self) -> int:
+        """Valid (unmasked) rows submitted so far; without a nodata mask, the rows pushed."""
+        n = c_int64(0)
+        check(load().sknnr_stream_valid_rows(self._h, byref(n)))
+        return int(n.value)
+
     def flush(self):
         check(load().sknnr_stream_flush(self._h))
         self._keep.clear()
@@ -667,3 +762,29 @@ def crosswalk_host(table, idx, device: int = 0):
 def crosswalk_device(table_ptr, n_table, idx_ptr, n, out_ptr, device=0, stream=0):
     check(load().sknnr_crosswalk(c_void_p(table_ptr), n_table, c_void_p(idx_ptr), n, c_void_p(out_ptr),
                                  device, MEM_DEVICE, c_void_p(stream or None)))
+
+
+def mask_rows_host(q, nodata, device: int = 0):
+    """``(valid, n_valid)``: uint8 ``(nq,)`` with 1 for every row of ``q`` none of whose columns equals its nodata value
+    (a NaN nodata value: is NaN), computed on the device (sknnr_mask_rows).  ``q`` keeps its dtype when the library reads
+    it (:data:`DTYPE_CODES`), else it is converted to float64."""
+    q = np.asarray(q)
+    code = dtype_code(q.dtype)
+    q = np.ascontiguousarray(q) if code is not None else np.ascontiguousarray(q, dtype=np.float64)
+    nodata = _c_f64(nodata).reshape(-1)
+    nq, d_in = q.shape
+    if nodata.size != d_in:
+        raise ValueError(f"nodata must hold {d_in} values, got {nodata.size}")
+    valid = np.empty(nq, dtype=np.uint8)
+    nv = c_int64(0)
+    check(load().sknnr_mask_rows(_host_ptr(q), nq, d_in, code or 0, _host_ptr(nodata), device, MEM_HOST, None,
+                                 _host_ptr(valid), byref(nv)))
+    return valid, int(nv.value)
+
+
+def mask_rows_device(q_ptr, nq, d_in, query_dtype, nodata, valid_ptr, device=0, stream=0) -> int:
+    nodata = _c_f64(nodata).reshape(-1)
+    nv = c_int64(0)
+    check(load().sknnr_mask_rows(c_void_p(q_ptr), nq, d_in, int(query_dtype), _host_ptr(nodata), device, MEM_DEVICE,
+                                 c_void_p(stream or None), c_void_p(valid_ptr), byref(nv)))
+    return int(nv.value)

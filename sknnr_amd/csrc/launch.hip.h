@@ -1,9 +1,9 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
-// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST), templates where they are instantiated.
+// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK), templates where they are instantiated.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 #include "exact.hip.h"
 #include "forest.hip.h"
 #include "hamming.hip.h"
+#include "mask.hip.h"
 #include "rescue.hip.h"
 
 namespace sknnr {
@@ -50,6 +51,13 @@ hipError_t hamming_distance_rows(const HammingRowsArgs& a, hipStream_t st);
 // ---- k_forest.hip --------------------------------------------------------------------------------------------------------
 // raw query rows -> float64 node ids of every tree of the handle's forests (RFNN / GBNN query-time map)
 hipError_t forest_apply(const ForestArgs& a, hipStream_t st);
+
+// ---- k_mask.hip: nodata rows of raster tiles (mask.hip.h) ---------------------------------------------------------------
+// row_mask_kernel, then the single-workgroup scan: a.blk becomes the exclusive scan of the block counts, *n_valid the total
+hipError_t row_mask(const MaskArgs& a, long* n_valid, hipStream_t st);
+// valid rows, as raw bytes, to their dense position (a.row_units is filled in here from row_bytes and the addresses)
+hipError_t row_compact(const CompactArgs& a, size_t row_bytes, hipStream_t st);
+hipError_t row_expand(const ExpandArgs& a, hipStream_t st);
 
 // ---- k_coarse1.hip / k_coarse2.hip: the MFMA pre-filters ----------------------------------------------------------------
 struct Coarse1Launch {

@@ -128,6 +128,25 @@ struct DevBuf {
     }
 };
 
+// Device buffers of the nodata front end (mask.hip.h) for one tile: the handle has a set for device-memory calls, every
+// slot of the host pipeline one of its own.
+struct MaskBufs {
+    DevBuf<unsigned char> valid;  // (n) 1 = valid
+    DevBuf<int> blk, rank;        // valid rows per block, then their exclusive scan; valid rows before each row
+    DevBuf<long> nvalid;          // the tile's valid rows (device word), copied to *pin_nv
+    DevBuf<char> cx;              // the packed rows
+    DevBuf<double> cd, cp;        // packed results
+    DevBuf<long> ci;
+    long* pin_nv = nullptr;       // pinned host word the 8-byte copy lands in
+    MaskBufs() = default;
+    MaskBufs(const MaskBufs&) = delete;
+    MaskBufs& operator=(const MaskBufs&) = delete;
+    ~MaskBufs() {
+        if (pin_nv) (void)hipHostFree(pin_nv);
+    }
+};
+constexpr int kMaskMaxCols = 1 << 16;  // the mask kernels index a block's elements with an int
+
 constexpr int kMaxKs = 8;              // coarse path: d <= 128
 constexpr long kChunkRows = 1L << 22;  // rows per chunk of host-side staging loops (transform entry point, X=None results)
 // Query rows per device chunk of one call (each chunk: prep -> pre-filter -> finalise, padded to kRowQuantum).
@@ -295,6 +314,7 @@ struct sknnr_index {
         DevBuf<double> dev_x, dev_d, dev_p;
         DevBuf<long> dev_i;
         hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_d2h = nullptr;
+        MaskBufs mask;  // nodata front end of the slot's tile (a pipeline with a mask only)
     } slot[kHostSlots];
     hipStream_t st_h2d = nullptr, st_run = nullptr, st_d2h = nullptr;
     std::unique_ptr<HostWorker> w_in, w_out;  // copy-in (look-ahead) and copy-out legs of the host pipeline
@@ -334,6 +354,11 @@ struct sknnr_index {
     const double* last_prep_xt = nullptr;
     bool last_prep_bucketed = false, last_prep_qnc_pos = false;
     bool stream_open = false;  // a sknnr_stream owns the host pipeline's slots
+    // nodata front end: the buffers of device-memory calls, the nodata values of one-shot calls and of the open stream,
+    // and the record of the last tile (sknnr_debug_last_mask)
+    MaskBufs mask;
+    DevBuf<double> m_nodata, s_nodata;
+    int64_t last_mask[8] = {};
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
     // a ring of call records so that several calls of one benchmark step are summed, not only the last.
@@ -1607,15 +1632,20 @@ int validate_call(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_
 // id_offset, no post-steps
 int run_forest(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opts* o, double* d_dist, long* d_idx,
                hipStream_t st);
-int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opts* o, double* d_dist,
-               long* d_idx, hipStream_t st, int raw = 0, long id_offset = 0) {
+// every search call zeroes the debug records first
+void zero_records(sknnr_index* ix) {
     std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);
     std::fill(std::begin(ix->last_hamming), std::end(ix->last_hamming), 0);
     std::fill(std::begin(ix->last_finalize), std::end(ix->last_finalize), 0);
     std::fill(std::begin(ix->last_scan), std::end(ix->last_scan), 0);
     std::fill(std::begin(ix->last_rescue), std::end(ix->last_rescue), 0);
     std::fill(std::begin(ix->last_prep), std::end(ix->last_prep), 0);
+    std::fill(std::begin(ix->last_mask), std::end(ix->last_mask), 0);
     ix->last_hamming_rows = 0;
+}
+int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opts* o, double* d_dist,
+               long* d_idx, hipStream_t st, int raw = 0, long id_offset = 0) {
+    zero_records(ix);
     if (xdev && uses_forest(ix, o)) return run_forest(ix, xdev, nq, o, d_dist, d_idx, st);
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
     const bool affine = o->apply_affine != 0 && xdev != nullptr;
@@ -2020,6 +2050,116 @@ static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, 
 
 namespace {
 
+// ---- nodata front end (mask.hip.h) --------------------------------------------------------------------------------------
+int mask_ensure(MaskBufs& m, long n, size_t row_bytes, int k, int t, bool want_dist, bool want_pred) {
+    HIP_TRY(m.valid.ensure((size_t)n));
+    HIP_TRY(m.blk.ensure((size_t)mask_blocks(n)));
+    HIP_TRY(m.rank.ensure((size_t)n));
+    HIP_TRY(m.nvalid.ensure(1));
+    if (!m.pin_nv) HIP_TRY(hipHostMalloc((void**)&m.pin_nv, sizeof(long), hipHostMallocDefault));
+    // (sized for the tile, not for its valid rows: the slot is sized before the count is known)
+    HIP_TRY(m.cx.ensure((size_t)n * row_bytes));
+    HIP_TRY(m.ci.ensure((size_t)n * k));
+    if (want_dist || want_pred) HIP_TRY(m.cd.ensure((size_t)n * k));
+    if (want_pred) HIP_TRY(m.cp.ensure((size_t)n * t));
+    return SKNNR_OK;
+}
+
+// Mask and scan of one tile on `st`, and the 8-byte copy of its valid count behind them: *m.pin_nv holds the count once
+// the caller has waited for `st` (or for an event recorded behind this).
+int mask_front(MaskBufs& m, const void* x, long n, int d_in, int x_dtype, const double* nodata_dev, hipStream_t st) {
+    MaskArgs a{};
+    a.x = x;
+    a.x_dtype = x_dtype;
+    a.nq = n;
+    a.d_in = d_in;
+    a.nodata = nodata_dev;
+    a.valid = m.valid.p;
+    a.blk = m.blk.p;
+    HIP_TRY(launch::row_mask(a, m.nvalid.p, st));
+    HIP_TRY(hipMemcpyAsync(m.pin_nv, m.nvalid.p, sizeof(long), hipMemcpyDeviceToHost, st));
+    return SKNNR_OK;
+}
+
+int mask_compact(MaskBufs& m, const void* x, long n, size_t row_bytes, hipStream_t st) {
+    CompactArgs a{};
+    a.x = x;
+    a.out = m.cx.p;
+    a.nq = n;
+    a.valid = m.valid.p;
+    a.blk_off = m.blk.p;
+    a.rank = m.rank.p;
+    HIP_TRY(launch::row_compact(a, row_bytes, st));
+    return SKNNR_OK;
+}
+
+// The search of a masked tile whose valid count nv the host knows, on `st`: in place when every row is valid, nothing but
+// the fill when none is, else on the packed rows (mask_compact has run, on `st` or in front of an event `st` waits for) and
+// expanded.  o->row_offset counts the valid rows in front of the tile.  d_pred: also predict; d_dist / d_idx may be null.
+int mask_finish(sknnr_index* ix, MaskBufs& m, const void* x, long n, long nv, const sknnr_query_opts* o, long fill_index,
+                double* d_dist, long* d_idx, double* d_pred, long valid_so_far, hipStream_t st) {
+    const int k = o->n_neighbors, t = ix->t;
+    const size_t row_bytes = (size_t)query_cols(ix, o) * dtype_bytes(o->query_dtype);
+    int rc;
+    if (nv == n) {
+        double* dd = d_dist ? d_dist : (d_pred ? m.cd.p : nullptr);
+        long* di = d_idx ? d_idx : m.ci.p;
+        if ((rc = run_device(ix, x, n, o, dd, di, st))) return rc;
+        if (d_pred && (rc = launch_predict(ix, dd, di, nullptr, n, k, o->weight_mode, d_pred, st))) return rc;
+    } else {
+        ExpandArgs e{};
+        if (nv > 0) {
+            double* cd = (d_dist || d_pred) ? m.cd.p : nullptr;
+            if ((rc = run_device(ix, m.cx.p, nv, o, cd, m.ci.p, st))) return rc;
+            if (d_pred && (rc = launch_predict(ix, cd, m.ci.p, nullptr, nv, k, o->weight_mode, m.cp.p, st))) return rc;
+            e.valid = m.valid.p;
+            e.rank = m.rank.p;
+            e.c_idx = m.ci.p;
+            e.c_dist = cd;
+            e.c_pred = m.cp.p;
+        } else {
+            zero_records(ix);  // (no search ran)
+        }
+        e.nq = n;
+        e.k = k;
+        e.t = t;
+        e.idx = d_idx;
+        e.dist = d_dist;
+        e.pred = d_pred;
+        e.fill_index = fill_index;
+        HIP_TRY(launch::row_expand(e, st));
+        HIP_TRY(hipEventRecord(ix->ev_ws, st));  // (the packed results belong to the workspace of a device-memory call)
+        ix->ws_busy = true;
+    }
+    const int64_t rec[8] = {1, n, nv, nv == n ? 1 : (nv == 0 ? 2 : 0), mask_blocks(n), (int64_t)row_bytes, valid_so_far + nv, 0};
+    std::copy(rec, rec + 8, ix->last_mask);
+    return SKNNR_OK;
+}
+
+// A masked device-memory call: mask, one 8-byte read of the valid count (synchronises `st`), then the search.
+int run_device_masked(sknnr_index* ix, const void* q, long nq, const sknnr_query_opts* o, const double* nodata,
+                      long fill_index, double* d_dist, long* d_idx, double* d_pred, hipStream_t st, int64_t* out_n_valid) {
+    const int d_x = query_cols(ix, o);
+    const size_t row_bytes = (size_t)d_x * dtype_bytes(o->query_dtype);
+    if (nq > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 query rows in one call");
+    if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));  // the mask buffers belong to the workspace
+    MaskBufs& m = ix->mask;
+    int rc = mask_ensure(m, nq, row_bytes, o->n_neighbors, ix->t, d_dist != nullptr, d_pred != nullptr);
+    if (rc) return rc;
+    HIP_TRY(ix->m_nodata.ensure((size_t)d_x));
+    HIP_TRY(hipMemcpyAsync(ix->m_nodata.p, nodata, (size_t)d_x * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = mask_front(m, q, nq, d_x, o->query_dtype, ix->m_nodata.p, st))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    const long nv = *m.pin_nv;
+    if (nv > 0 && nv < nq && (rc = mask_compact(m, q, nq, row_bytes, st))) return rc;
+    if (out_n_valid) *out_n_valid = nv;
+    return mask_finish(ix, m, q, nq, nv, o, fill_index, d_dist, d_idx, d_pred, 0, st);
+}
+
+}  // namespace
+
+namespace {
+
 constexpr long kHostChunkRows = 1L << 20;  // rows per pipeline slot (SKNNR_HOST_CHUNK_ROWS overrides)
 
 long host_chunk_rows() {
@@ -2076,6 +2216,10 @@ struct HostPipe {
     bool want_dist = false, want_idx = true, want_pred = false;
     int k = 0, t = 0, d_x = 0;
     size_t x_esz = sizeof(double);  // bytes per element of the caller's rows (opts->query_dtype)
+    // nodata front end: every tile is masked behind its host-to-device copy, and o.row_offset advances by its VALID rows
+    const double* nodata_dev = nullptr;  // (d_x) on the device, or null: no mask
+    long fill_index = -1;
+    long row_offset0 = 0;                // o.row_offset when the pipeline was opened
     struct Pending {
         bool live = false;
         long n = 0;
@@ -2113,6 +2257,7 @@ int pipe_open(HostPipe& p, sknnr_index* ix, const sknnr_query_opts* o, bool want
     p.t = ix->t;
     p.d_x = query_cols(ix, o);
     p.x_esz = (size_t)dtype_bytes(o->query_dtype);
+    p.row_offset0 = o->row_offset;
     // (each object on its own: a creation that failed half way is completed by the next call, never skipped)
     for (hipStream_t* h : {&ix->st_h2d, &ix->st_run, &ix->st_d2h})
         if (!*h) HIP_TRY(hipStreamCreateWithFlags(h, hipStreamNonBlocking));
@@ -2161,6 +2306,7 @@ int pipe_prepare_slot(HostPipe& p, int b, long n) {
     HIP_TRY(sl.dev_i.ensure((size_t)n * k));
     HIP_TRY(sl.dev_d.ensure((size_t)n * k));
     if (p.want_pred) HIP_TRY(sl.dev_p.ensure((size_t)n * t));
+    if (p.nodata_dev && (rc = mask_ensure(sl.mask, n, (size_t)d_x * p.x_esz, k, t, p.want_dist, p.want_pred))) return rc;
     return SKNNR_OK;
 }
 
@@ -2237,15 +2383,34 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
     const double t_enq = now_ms();
     p.ms_copy_in += t_enq - t_in;
     HIP_TRY(hipMemcpyAsync(sl.dev_x.p, sl.pin_x, (size_t)n * d_x * p.x_esz, hipMemcpyHostToDevice, ix->st_h2d));
+    long nv = n;  // rows the tile adds to the row offset
+    if (p.nodata_dev) {
+        // Mask (and, when some rows but not all are masked, compaction) on the copy stream behind the tile's rows: the host
+        // waits for this tile's copy and mask only -- not for the previous tile's search, which is on st_run -- and reads
+        // the valid count, on which the launches below depend.
+        if ((rc = mask_front(sl.mask, sl.dev_x.p, n, d_x, p.o.query_dtype, p.nodata_dev, ix->st_h2d))) return rc;
+        HIP_TRY(hipEventRecord(sl.ev_h2d, ix->st_h2d));
+        HIP_TRY(hipEventSynchronize(sl.ev_h2d));
+        nv = *sl.mask.pin_nv;
+        if (nv > 0 && nv < n && (rc = mask_compact(sl.mask, sl.dev_x.p, n, (size_t)d_x * p.x_esz, ix->st_h2d))) return rc;
+    }
     HIP_TRY(hipEventRecord(sl.ev_h2d, ix->st_h2d));
     // the PREVIOUS tile's results travel behind this tile's rows, on the same stream (see pipe_enqueue_d2h)
     if ((rc = pipe_enqueue_d2h(p))) return rc;
     HIP_TRY(hipStreamWaitEvent(ix->st_run, sl.ev_h2d, 0));
-    rc = run_device(ix, sl.dev_x.p, n, &p.o, sl.dev_d.p, sl.dev_i.p, ix->st_run);
-    if (rc) return rc;
-    if (p.want_pred) {
-        rc = launch_predict(ix, sl.dev_d.p, sl.dev_i.p, nullptr, n, k, p.o.weight_mode, sl.dev_p.p, ix->st_run);
+    if (p.nodata_dev) {
+        // (distances only where the slot has packed distances to expand from: mask_ensure sizes them by the same rule)
+        rc = mask_finish(ix, sl.mask, sl.dev_x.p, n, nv, &p.o, p.fill_index,
+                         p.want_dist || p.want_pred ? sl.dev_d.p : nullptr, sl.dev_i.p,
+                         p.want_pred ? sl.dev_p.p : nullptr, p.o.row_offset - p.row_offset0, ix->st_run);
         if (rc) return rc;
+    } else {
+        rc = run_device(ix, sl.dev_x.p, n, &p.o, sl.dev_d.p, sl.dev_i.p, ix->st_run);
+        if (rc) return rc;
+        if (p.want_pred) {
+            rc = launch_predict(ix, sl.dev_d.p, sl.dev_i.p, nullptr, n, k, p.o.weight_mode, sl.dev_p.p, ix->st_run);
+            if (rc) return rc;
+        }
     }
     HIP_TRY(hipEventRecord(sl.ev_done, ix->st_run));
     auto& pd = p.pending[b];
@@ -2255,7 +2420,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
     pd.oi = oi;
     pd.op = op;
     p.d2h_slot = b;  // its device-to-host copies are enqueued behind the next tile's rows, or by the flush
-    p.o.row_offset += n;
+    p.o.row_offset += nv;
     p.ms_enqueue += now_ms() - t_enq;
     static const bool workers = [] { const char* e = std::getenv("SKNNR_PIPE_WORKERS"); return !(e && std::atoi(e) == 0); }();
     if (workers && q_next && n_next > 0) {
@@ -2374,11 +2539,20 @@ struct Prefault {
     }
 };
 
+// nodata (host, one value per column of q) / fill_index / out_n_valid: the masked call; nodata == null: no mask
 int run_host_pipeline(sknnr_index* ix, const void* q, long nq, const sknnr_query_opts* o, double* out_dist,
-                      long* out_idx, double* out_pred) {
+                      long* out_idx, double* out_pred, const double* nodata = nullptr, long fill_index = -1,
+                      int64_t* out_n_valid = nullptr) {
     if (ix->stream_open) return fail(SKNNR_ERR_INVALID, "a query stream is open on this handle: end it first");
     HostPipe p;
     int rc = pipe_open(p, ix, o, out_dist != nullptr, true, out_pred != nullptr);
+    if (!rc && nodata) {
+        HIP_TRY(hipDeviceSynchronize());  // (m_nodata belongs to the workspace)
+        HIP_TRY(ix->m_nodata.ensure((size_t)p.d_x));
+        HIP_TRY(hipMemcpy(ix->m_nodata.p, nodata, (size_t)p.d_x * sizeof(double), hipMemcpyHostToDevice));
+        p.nodata_dev = ix->m_nodata.p;
+        p.fill_index = fill_index;
+    }
     Prefault pf;  // (joined when the call returns)
     if (!rc && std::getenv("SKNNR_PREFAULT")) {  // (measured: 96 ms without, 115 ms with -- the populate threads take bandwidth the copies need)
         pf.add(out_idx, (size_t)nq * o->n_neighbors * sizeof(long));
@@ -2393,6 +2567,7 @@ int run_host_pipeline(sknnr_index* ix, const void* q, long nq, const sknnr_query
         (void)hipDeviceSynchronize();  // nothing of a failed call may still be in flight on the slots
         g_last_error = msg;
     }
+    if (out_n_valid) *out_n_valid = p.o.row_offset - p.row_offset0;
     return rc;
 }
 
@@ -2483,6 +2658,84 @@ extern "C" int sknnr_kneighbors(sknnr_index* ix, const void* q, int64_t nq, cons
     return run_self_rows(ix, nq, o, out_dist, (long*)out_idx, nullptr);
 }
 
+
+// ----------------------------------------------------------------------------------------
+// nodata rows: the mask alone, and the masked calls
+// ----------------------------------------------------------------------------------------
+extern "C" int sknnr_mask_rows(const void* q, int64_t nq, int32_t d_in, int32_t query_dtype, const double* nodata,
+                               int32_t device, int32_t mem, void* stream, uint8_t* out_valid, int64_t* out_n_valid) {
+    if (query_dtype < 0 || query_dtype >= kDtypeCount) return fail(SKNNR_ERR_INVALID, "unknown query_dtype %d", query_dtype);
+    if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
+    if (d_in < 1 || d_in > kMaskMaxCols) return fail(SKNNR_ERR_INVALID, "d_in = %d outside [1, %d]", d_in, kMaskMaxCols);
+    if (nq > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 rows in one call");
+    if (!nodata) return fail(SKNNR_ERR_INVALID, "nodata is NULL");
+    if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
+    if (nq == 0) {
+        if (out_n_valid) *out_n_valid = 0;
+        return SKNNR_OK;
+    }
+    if (!q || !out_valid) return fail(SKNNR_ERR_INVALID, "q / out_valid is NULL");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = mem == SKNNR_MEM_DEVICE ? (hipStream_t)stream : nullptr;
+    const size_t row_bytes = (size_t)d_in * dtype_bytes(query_dtype);
+    DevBuf<double> nd;
+    DevBuf<int> blk;
+    DevBuf<long> nv;
+    DevBuf<char> dq;
+    DevBuf<unsigned char> dvalid;
+    HIP_TRY(nd.ensure((size_t)d_in));
+    HIP_TRY(blk.ensure((size_t)mask_blocks(nq)));
+    HIP_TRY(nv.ensure(1));
+    HIP_TRY(hipMemcpy(nd.p, nodata, (size_t)d_in * sizeof(double), hipMemcpyHostToDevice));
+    MaskArgs a{};
+    a.x = q;
+    a.valid = out_valid;
+    if (mem == SKNNR_MEM_HOST) {
+        HIP_TRY(dq.ensure((size_t)nq * row_bytes));
+        HIP_TRY(dvalid.ensure((size_t)nq));
+        HIP_TRY(hipMemcpy(dq.p, q, (size_t)nq * row_bytes, hipMemcpyHostToDevice));
+        a.x = dq.p;
+        a.valid = dvalid.p;
+    }
+    a.x_dtype = query_dtype;
+    a.nq = nq;
+    a.d_in = d_in;
+    a.nodata = nd.p;
+    a.blk = blk.p;
+    HIP_TRY(launch::row_mask(a, nv.p, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    long n_valid = 0;
+    HIP_TRY(hipMemcpy(&n_valid, nv.p, sizeof n_valid, hipMemcpyDeviceToHost));
+    if (mem == SKNNR_MEM_HOST) HIP_TRY(hipMemcpy(out_valid, dvalid.p, (size_t)nq, hipMemcpyDeviceToHost));
+    if (out_n_valid) *out_n_valid = n_valid;
+    return SKNNR_OK;
+}
+
+// what the masked calls add to validate_call
+static int validate_masked(const sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, const double* nodata) {
+    if (o->exclude_self) return fail(SKNNR_ERR_INVALID, "a masked call answers the rows it is given: exclude_self is not available");
+    if (!q && nq > 0) return fail(SKNNR_ERR_INVALID, "q is NULL");
+    if (!nodata) return fail(SKNNR_ERR_INVALID, "nodata is NULL");
+    if (query_cols(ix, o) > kMaskMaxCols) return fail(SKNNR_ERR_UNSUPPORTED, "more than %d input columns with a nodata mask", kMaskMaxCols);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_kneighbors_masked(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o,
+                                       const double* nodata, int64_t fill_index, double* out_dist, int64_t* out_idx,
+                                       int32_t mem, void* stream, int64_t* out_n_valid) {
+    static const double dummy_q = 0.0;
+    int rc = validate_call(ix, q ? q : &dummy_q, nq, o, out_idx);
+    if (!rc) rc = validate_masked(ix, q, nq, o, nodata);
+    if (rc) return rc;
+    if (out_n_valid) *out_n_valid = 0;
+    if (nq == 0) return SKNNR_OK;
+    if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    if (mem == SKNNR_MEM_DEVICE)
+        return run_device_masked(ix, q, nq, o, nodata, fill_index, out_dist, (long*)out_idx, nullptr, (hipStream_t)stream, out_n_valid);
+    return run_host_pipeline(ix, q, nq, o, out_dist, (long*)out_idx, nullptr, nodata, fill_index, out_n_valid);
+}
 
 // ----------------------------------------------------------------------------------------
 // full weighted-Hamming distance rows (the reference's own choice among exactly tied rows: np.argpartition on the host)
@@ -2830,13 +3083,60 @@ extern "C" int sknnr_predict(sknnr_index* ix, const void* q, int64_t nq, const s
     return run_self_rows(ix, nq, o, out_dist, (long*)out_idx, out_pred);
 }
 
+extern "C" int sknnr_predict_masked(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o,
+                                    const double* nodata, int64_t fill_index, double* out_pred, double* out_dist,
+                                    int64_t* out_idx, int32_t mem, void* stream, int64_t* out_n_valid) {
+    if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
+    if (!o) return fail(SKNNR_ERR_INVALID, "opts is NULL");
+    if (!out_pred && nq > 0) return fail(SKNNR_ERR_INVALID, "out_pred is NULL");
+    if (!weight_mode_ok(o->weight_mode, false))
+        return fail(SKNNR_ERR_INVALID, "a masked call predicts with uniform or distance weights only (weight mode %d)", o->weight_mode);
+    static int64_t dummy_idx;
+    static const double dummy_q = 0.0;
+    int rc = validate_call(ix, q ? q : &dummy_q, nq, o, out_idx ? out_idx : &dummy_idx);
+    if (!rc) rc = validate_masked(ix, q, nq, o, nodata);
+    if (rc) return rc;
+    if (out_n_valid) *out_n_valid = 0;
+    if (nq == 0) return SKNNR_OK;
+    if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    if (mem == SKNNR_MEM_DEVICE)
+        return run_device_masked(ix, q, nq, o, nodata, fill_index, out_dist, (long*)out_idx, out_pred, (hipStream_t)stream, out_n_valid);
+    return run_host_pipeline(ix, q, nq, o, out_dist, (long*)out_idx, out_pred, nodata, fill_index, out_n_valid);
+}
+
 // ----------------------------------------------------------------------------------------
 // streamed query tiles (raster ingestion)
 // ----------------------------------------------------------------------------------------
 struct sknnr_stream {
     HostPipe pipe;
     int64_t rows_pushed = 0;
+    bool pushed = false;  // a push was accepted: the nodata mask can no longer change
 };
+
+extern "C" int sknnr_stream_set_nodata(sknnr_stream* s, const double* nodata, int64_t fill_index) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    if (!nodata) return fail(SKNNR_ERR_INVALID, "nodata is NULL");
+    HostPipe& p = s->pipe;
+    std::lock_guard<std::mutex> lock(p.ix->mtx);
+    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_nodata is allowed only before the first push");
+    if (p.d_x > kMaskMaxCols) return fail(SKNNR_ERR_UNSUPPORTED, "more than %d input columns with a nodata mask", kMaskMaxCols);
+    HIP_TRY(hipSetDevice(p.ix->device));
+    HIP_TRY(p.ix->s_nodata.ensure((size_t)p.d_x));
+    HIP_TRY(hipMemcpy(p.ix->s_nodata.p, nodata, (size_t)p.d_x * sizeof(double), hipMemcpyHostToDevice));
+    p.nodata_dev = p.ix->s_nodata.p;
+    p.fill_index = fill_index;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_valid_rows(const sknnr_stream* s, int64_t* out_valid_rows) {
+    if (!s || !out_valid_rows) return fail(SKNNR_ERR_INVALID, "stream / out_valid_rows is NULL");
+    std::lock_guard<std::mutex> lock(s->pipe.ix->mtx);
+    *out_valid_rows = s->pipe.o.row_offset - s->pipe.row_offset0;
+    return SKNNR_OK;
+}
 
 extern "C" int sknnr_stream_begin(sknnr_index* ix, const sknnr_query_opts* o, int32_t want_dist, int32_t want_pred,
                                   sknnr_stream** out) {
@@ -2879,6 +3179,7 @@ extern "C" int sknnr_stream_push(sknnr_stream* s, const void* q, int64_t nq, dou
     if (out_pred && !p.want_pred) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
     std::lock_guard<std::mutex> lock(p.ix->mtx);
     HIP_TRY(hipSetDevice(p.ix->device));
+    s->pushed = true;
     int rc = pipe_submit_rows(p, q, nq, out_dist, (long*)out_idx, out_pred);
     if (rc) {
         const std::string msg = g_last_error;
@@ -2971,6 +3272,14 @@ extern "C" int sknnr_debug_last_prefilter(const sknnr_index* cix, int64_t out[8]
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
     std::copy(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), out);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_mask(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "index / out is NULL");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::copy(std::begin(ix->last_mask), std::end(ix->last_mask), out);
     return SKNNR_OK;
 }
 
