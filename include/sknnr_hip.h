@@ -420,6 +420,34 @@ int sknnr_stream_valid_rows(const sknnr_stream* stream, int64_t* out_valid_rows)
 int sknnr_debug_last_mask(const sknnr_index* index, int64_t out[8]);
 
 /*
+ * Debug only.  The kernels of the nodata front end alone, without a handle, so that a test can compare everything they
+ * write -- not only final answers -- with a host restatement, at an alignment of its own choosing.
+ *
+ * sknnr_debug_mask_compact: mask, scan and compaction exactly as a masked device-memory call runs them, except that the
+ *   compaction is launched whatever the valid count is (0 and nq included).
+ *   q          (nq, d_in) rows of query_dtype, DEVICE memory on `device`; any address aligned to the element
+ *   nodata     (d_in) float64, host
+ *   out_packed DEVICE memory for the valid rows (nq rows always suffice); any address.  Only the first n_valid rows'
+ *              bytes are written.
+ *   out_valid  (nq) uint8, out_blk_off (ceil(nq / 256)) int32: the exclusive scan of the blocks' valid counts,
+ *   out_rank   (nq) int32: valid rows in front of each row (written for masked rows too); host, each optional
+ *   out_unit   host: bytes per copy of the compaction (1, 2, 4, 8 or 16: the largest power of two up to 16 that divides
+ *              the row size and both addresses);  out_n_valid  host: the valid rows
+ *   Returns when everything is written.
+ * sknnr_debug_expand_rows: the expansion alone on the current device.  valid (nq) uint8, rank (nq) int32, the packed
+ *   c_idx (n_valid, k) int64 / c_dist (n_valid, k) / c_pred (n_valid, t) and the full idx (nq, k) / dist (nq, k) /
+ *   pred (nq, t) are DEVICE memory.  Each output may be NULL (it is not written); valid NULL: every row is masked and the
+ *   packed arrays are not read.  With valid given, a NULL rank or a NULL packed array of a requested output is refused:
+ *   SKNNR_ERR_INVALID.  Returns when the outputs are written.
+ */
+int sknnr_debug_mask_compact(const void* q, int64_t nq, int32_t d_in, int32_t query_dtype, const double* nodata,
+                             int32_t device, void* stream, uint8_t* out_valid, int32_t* out_blk_off, int32_t* out_rank,
+                             void* out_packed, int32_t* out_unit, int64_t* out_n_valid);
+int sknnr_debug_expand_rows(int64_t nq, int32_t k, int32_t t, const uint8_t* valid, const int32_t* rank,
+                            const int64_t* c_idx, const double* c_dist, const double* c_pred, int64_t* idx, double* dist,
+                            double* pred, int64_t fill_index, void* stream);
+
+/*
  * Dataframe-index crosswalk: out[i] = table[idx[i]].
  * Replaces self.dataframe_index_in_[neigh_ind] (REF _base.py:177-180) for int64 plot IDs.
  *   table : (n_table) int64 in `mem`;  idx, out : (n) int64 in `mem`

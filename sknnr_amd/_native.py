@@ -85,6 +85,8 @@ EXPORTED_SYMBOLS = (
     "sknnr_stream_set_nodata",
     "sknnr_stream_valid_rows",
     "sknnr_debug_last_mask",
+    "sknnr_debug_mask_compact",
+    "sknnr_debug_expand_rows",
     "sknnr_crosswalk",
     "sknnr_debug_coarse_matrix",
     "sknnr_debug_last_prefilter",
@@ -205,6 +207,9 @@ def load(build_if_missing: bool = False):
     lib.sknnr_stream_set_nodata.argtypes = [vp, vp, c_int64]
     lib.sknnr_stream_valid_rows.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_last_mask.argtypes = [vp, POINTER(c_int64)]
+    lib.sknnr_debug_mask_compact.argtypes = [vp, c_int64, c_int32, c_int32, vp, c_int32, vp, vp, vp, vp, vp,
+                                             POINTER(c_int32), POINTER(c_int64)]
+    lib.sknnr_debug_expand_rows.argtypes = [c_int64, c_int32, c_int32, vp, vp, vp, vp, vp, vp, vp, vp, c_int64, vp]
     lib.sknnr_kneighbors.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), vp, vp, c_int32, vp]
     lib.sknnr_predict.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), vp, vp, vp, c_int32, vp]
     lib.sknnr_predict_from_neighbors.argtypes = [vp, vp, vp, vp, c_int64, c_int32, c_int32, vp,
@@ -788,3 +793,28 @@ def mask_rows_device(q_ptr, nq, d_in, query_dtype, nodata, valid_ptr, device=0, 
     check(load().sknnr_mask_rows(c_void_p(q_ptr), nq, d_in, int(query_dtype), _host_ptr(nodata), device, MEM_DEVICE,
                                  c_void_p(stream or None), c_void_p(valid_ptr), byref(nv)))
     return int(nv.value)
+
+
+def debug_mask_compact(q_ptr, nq, d_in, query_dtype, nodata, packed_ptr, device=0, stream=0) -> dict:
+    """Debug only: mask, scan and compaction alone on device pointers (sknnr_debug_mask_compact).  ``valid`` uint8
+    ``(nq,)``, ``blk_off`` int32 per block of 256 rows, ``rank`` int32 ``(nq,)``, ``unit`` (bytes per copy) and
+    ``n_valid``; the packed rows are written at ``packed_ptr``."""
+    nodata = _c_f64(nodata).reshape(-1)
+    if nodata.size != d_in:
+        raise ValueError(f"nodata must hold {d_in} values, got {nodata.size}")
+    valid = np.empty(nq, dtype=np.uint8)
+    blk_off = np.empty((nq + 255) // 256, dtype=np.int32)
+    rank = np.empty(nq, dtype=np.int32)
+    unit, nv = c_int32(0), c_int64(0)
+    check(load().sknnr_debug_mask_compact(c_void_p(q_ptr or None), nq, d_in, int(query_dtype), _host_ptr(nodata), device,
+                                          c_void_p(stream or None), _host_ptr(valid), _host_ptr(blk_off), _host_ptr(rank),
+                                          c_void_p(packed_ptr or None), byref(unit), byref(nv)))
+    return {"valid": valid, "blk_off": blk_off, "rank": rank, "unit": int(unit.value), "n_valid": int(nv.value)}
+
+
+def debug_expand_rows(nq, k, t, valid_ptr, rank_ptr, c_idx_ptr, c_dist_ptr, c_pred_ptr, idx_ptr, dist_ptr, pred_ptr,
+                      fill_index=-1, stream=0) -> None:
+    """Debug only: the expansion alone on device pointers (sknnr_debug_expand_rows); 0 / None is a null pointer."""
+    ptrs = [c_void_p(p or None) for p in (valid_ptr, rank_ptr, c_idx_ptr, c_dist_ptr, c_pred_ptr, idx_ptr, dist_ptr,
+                                          pred_ptr)]
+    check(load().sknnr_debug_expand_rows(nq, k, t, *ptrs, int(fill_index), c_void_p(stream or None)))

@@ -57,6 +57,8 @@ hipError_t forest_apply(const ForestArgs& a, hipStream_t st);
 hipError_t row_mask(const MaskArgs& a, long* n_valid, hipStream_t st);
 // valid rows, as raw bytes, to their dense position (a.row_units is filled in here from row_bytes and the addresses)
 hipError_t row_compact(const CompactArgs& a, size_t row_bytes, hipStream_t st);
+// bytes per copy row_compact chooses: the largest power of two up to 16 that divides row_bytes and both addresses
+int compact_unit(const void* x, const void* out, size_t row_bytes);
 hipError_t row_expand(const ExpandArgs& a, hipStream_t st);
 
 // ---- k_coarse1.hip / k_coarse2.hip: the MFMA pre-filters ----------------------------------------------------------------

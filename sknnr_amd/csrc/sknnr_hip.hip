@@ -3283,6 +3283,89 @@ extern "C" int sknnr_debug_last_mask(const sknnr_index* cix, int64_t out[8]) {
     return SKNNR_OK;
 }
 
+// The mask, the scan and the compaction alone, on the caller's device pointers (run_device_masked's sequence without the
+// search): the block offsets and the ranks, which no search result shows, come back to the host.
+extern "C" int sknnr_debug_mask_compact(const void* q, int64_t nq, int32_t d_in, int32_t query_dtype, const double* nodata,
+                                        int32_t device, void* stream, uint8_t* out_valid, int32_t* out_blk_off,
+                                        int32_t* out_rank, void* out_packed, int32_t* out_unit, int64_t* out_n_valid) {
+    if (query_dtype < 0 || query_dtype >= kDtypeCount) return fail(SKNNR_ERR_INVALID, "unknown query_dtype %d", query_dtype);
+    if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
+    if (d_in < 1 || d_in > kMaskMaxCols) return fail(SKNNR_ERR_INVALID, "d_in = %d outside [1, %d]", d_in, kMaskMaxCols);
+    if (nq > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 rows in one call");
+    if (!nodata) return fail(SKNNR_ERR_INVALID, "nodata is NULL");
+    const size_t row_bytes = (size_t)d_in * dtype_bytes(query_dtype);
+    if (out_unit) *out_unit = launch::compact_unit(q, out_packed, row_bytes);
+    if (out_n_valid) *out_n_valid = 0;
+    if (nq == 0) return SKNNR_OK;
+    if (!q || !out_packed) return fail(SKNNR_ERR_INVALID, "q / out_packed is NULL");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const long nb = mask_blocks(nq);
+    DevBuf<double> nd;
+    DevBuf<int> blk, rank;
+    DevBuf<long> nv;
+    DevBuf<unsigned char> valid;
+    HIP_TRY(nd.ensure((size_t)d_in));
+    HIP_TRY(blk.ensure((size_t)nb));
+    HIP_TRY(rank.ensure((size_t)nq));
+    HIP_TRY(nv.ensure(1));
+    HIP_TRY(valid.ensure((size_t)nq));
+    HIP_TRY(hipMemcpyAsync(nd.p, nodata, (size_t)d_in * sizeof(double), hipMemcpyHostToDevice, st));
+    MaskArgs a{};
+    a.x = q;
+    a.x_dtype = query_dtype;
+    a.nq = nq;
+    a.d_in = d_in;
+    a.nodata = nd.p;
+    a.valid = valid.p;
+    a.blk = blk.p;
+    HIP_TRY(launch::row_mask(a, nv.p, st));
+    CompactArgs c{};
+    c.x = q;
+    c.out = out_packed;
+    c.nq = nq;
+    c.valid = valid.p;
+    c.blk_off = blk.p;
+    c.rank = rank.p;
+    HIP_TRY(launch::row_compact(c, row_bytes, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    long n_valid = 0;
+    HIP_TRY(hipMemcpy(&n_valid, nv.p, sizeof n_valid, hipMemcpyDeviceToHost));
+    if (out_valid) HIP_TRY(hipMemcpy(out_valid, valid.p, (size_t)nq, hipMemcpyDeviceToHost));
+    if (out_blk_off) HIP_TRY(hipMemcpy(out_blk_off, blk.p, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost));
+    if (out_rank) HIP_TRY(hipMemcpy(out_rank, rank.p, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
+    if (out_n_valid) *out_n_valid = n_valid;
+    return SKNNR_OK;
+}
+
+// The expansion alone, on the caller's device pointers.
+extern "C" int sknnr_debug_expand_rows(int64_t nq, int32_t k, int32_t t, const uint8_t* valid, const int32_t* rank,
+                                       const int64_t* c_idx, const double* c_dist, const double* c_pred, int64_t* idx,
+                                       double* dist, double* pred, int64_t fill_index, void* stream) {
+    if (nq < 0 || nq > 0x7fffffffL) return fail(SKNNR_ERR_INVALID, "nq outside [0, 2^31 - 1]");
+    if (k < 1 || t < 1) return fail(SKNNR_ERR_INVALID, "k and t must be >= 1");
+    ExpandArgs e{};
+    e.nq = nq;
+    e.k = k;
+    e.t = t;
+    e.valid = valid;
+    e.rank = rank;
+    e.c_idx = (const long*)c_idx;
+    e.c_dist = c_dist;
+    e.c_pred = c_pred;
+    e.idx = (long*)idx;
+    e.dist = dist;
+    e.pred = pred;
+    e.fill_index = fill_index;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t err = launch::row_expand(e, st);
+    if (err == hipErrorInvalidValue)
+        return fail(SKNNR_ERR_INVALID, "an output is asked for without rank or without its packed results");
+    HIP_TRY(err);
+    HIP_TRY(hipStreamSynchronize(st));
+    return SKNNR_OK;
+}
+
 extern "C" int sknnr_debug_last_finalize(const sknnr_index* cix, int64_t out[4]) {
     if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
     sknnr_index* ix = const_cast<sknnr_index*>(cix);

@@ -1,7 +1,8 @@
 """What the nodata kernels write, restated on the host with numpy (no GPU needed).
 
 tests/test_nodata_gpu.py compares ``sknnr_mask_rows`` with ``row_mask`` bit for bit and uses ``compact`` / ``expand`` to
-state what a masked call must return; tests/test_nodata_cpu.py checks this module itself against plain boolean indexing.
+state what a masked call must return; tests/test_nodata_kernels_gpu.py compares everything each kernel writes, run alone,
+with this module; tests/test_nodata_cpu.py checks this module itself against plain boolean indexing.
 Source: sknnr_amd/csrc/mask.hip.h.
 
 - ``row_mask``: ``row_mask_kernel`` -- a row is masked when any column, widened exactly to float64, equals its nodata
@@ -9,6 +10,7 @@ Source: sknnr_amd/csrc/mask.hip.h.
 - ``exclusive_scan``: ``mask_scan_kernel`` -- block offsets and the tile's valid count.
 - ``ranks`` / ``compact``: ``row_compact_kernel`` -- rank of a row = its block's offset + the valid rows in front of it
   inside the block; valid rows are copied, as raw bytes and in order, to position rank.
+- ``compact_unit``: ``launch::compact_unit`` (k_mask.hip) -- the bytes per copy of the compaction.
 - ``expand``: ``row_expand_kernel`` -- a valid row takes row rank[row] of the packed results, a masked row the fills.
 """
 
@@ -71,9 +73,15 @@ def compact(x, valid) -> np.ndarray:
     rk = ranks(valid)
     raw = x.view(np.uint8).reshape(x.shape[0], -1)
     out = np.zeros((int(valid.sum()), raw.shape[1]), dtype=np.uint8)
-    for r in np.flatnonzero(valid):
-        out[rk[r]] = raw[r]
+    out[rk[valid]] = raw[valid]
     return out.view(x.dtype).reshape(-1, x.shape[1])
+
+
+def compact_unit(x_addr: int, out_addr: int, row_bytes: int) -> int:
+    """Bytes per copy of the compaction: the largest power of two up to 16 that divides the row size and both base
+    addresses -- the lowest set bit of their OR with 16."""
+    bits = int(x_addr) | int(out_addr) | int(row_bytes) | 16
+    return bits & -bits
 
 
 def expand(valid, packed, fill) -> np.ndarray:
@@ -82,8 +90,7 @@ def expand(valid, packed, fill) -> np.ndarray:
     packed = np.asarray(packed)
     rk = ranks(valid)
     out = np.full((valid.size,) + packed.shape[1:], fill, dtype=packed.dtype)
-    for r in np.flatnonzero(valid):
-        out[r] = packed[rk[r]]
+    out[valid] = packed[rk[valid]]
     return out
 
 

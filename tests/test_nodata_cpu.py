@@ -12,7 +12,7 @@ import pytest
 import _nodata as ND
 
 NEW_SYMBOLS = ("sknnr_mask_rows", "sknnr_kneighbors_masked", "sknnr_predict_masked", "sknnr_stream_set_nodata",
-               "sknnr_stream_valid_rows", "sknnr_debug_last_mask")
+               "sknnr_stream_valid_rows", "sknnr_debug_last_mask", "sknnr_debug_mask_compact", "sknnr_debug_expand_rows")
 
 
 def test_normalize_nodata():
@@ -78,6 +78,36 @@ def test_restated_compaction_is_plain_indexing(nq, kind):
         assert ND.expected_path(valid) == {"none": ND.PATH_IN_PLACE, "all": ND.PATH_ALL_MASKED}[kind]
 
 
+# (source address, output address, row bytes) -> bytes per copy, written out by hand: the largest power of two up to 16
+# that divides all three
+COMPACT_UNIT_TABLE = [
+    (0x7F0000000000, 0x7F0000100000, 1, 1), (0x7F0000000000, 0x7F0000100000, 3, 1), (0x7F0000000000, 0x7F0000100000, 7, 1),
+    (0x7F0000000000, 0x7F0000100000, 2, 2), (0x7F0000000000, 0x7F0000100000, 14, 2), (0x7F0000000000, 0x7F0000100000, 6, 2),
+    (0x7F0000000000, 0x7F0000100000, 4, 4), (0x7F0000000000, 0x7F0000100000, 12, 4), (0x7F0000000000, 0x7F0000100000, 28, 4),
+    (0x7F0000000000, 0x7F0000100000, 8, 8), (0x7F0000000000, 0x7F0000100000, 24, 8), (0x7F0000000000, 0x7F0000100000, 56, 8),
+    (0x7F0000000000, 0x7F0000100000, 16, 16), (0x7F0000000000, 0x7F0000100000, 48, 16),
+    (0x7F0000000000, 0x7F0000100000, 32, 16), (0x7F0000000000, 0x7F0000100000, 2048, 16),
+    (0x7F0000000000, 0x7F0000100000, 1 << 19, 16),
+    # an address less aligned than the row size lowers the unit: the source alone, the output alone, both
+    (0x7F0000000004, 0x7F0000100000, 16, 4), (0x7F0000000000, 0x7F0000100004, 16, 4), (0x7F0000000004, 0x7F0000100004, 16, 4),
+    (0x7F0000000008, 0x7F0000100000, 16, 8), (0x7F0000000008, 0x7F0000100004, 16, 4), (0x7F0000000002, 0x7F0000100008, 48, 2),
+    (0x7F0000000000, 0x7F0000100001, 4, 1), (0x7F0000000003, 0x7F0000100000, 2048, 1), (0x7F0000000001, 0x7F0000100001, 8, 1),
+    (0x7F0000000010, 0x7F0000100030, 64, 16), (0x7F0000000020, 0x7F0000100010, 24, 8), (0x7F0000000006, 0x7F0000100000, 12, 2),
+    # ... and never raises it above what the row size allows
+    (0x7F0000000010, 0x7F0000100010, 14, 2), (0x7F0000000008, 0x7F0000100008, 7, 1), (0x7F0000000100, 0x7F0000100100, 12, 4),
+    (0, 0, 5, 1), (0, 0, 16, 16), (0, 0, 40, 8),
+]
+
+
+def test_compact_unit_against_a_table_written_by_hand():
+    for x_addr, out_addr, row_bytes, want in COMPACT_UNIT_TABLE:
+        got = ND.compact_unit(x_addr, out_addr, row_bytes)
+        assert got == want, (hex(x_addr), hex(out_addr), row_bytes, got, want)
+        # what a unit must be for the kernel's typed loads and stores to be aligned and whole
+        assert x_addr % got == 0 and out_addr % got == 0 and row_bytes % got == 0 and got in (1, 2, 4, 8, 16)
+        assert got == 16 or any(v % (2 * got) for v in (x_addr, out_addr, row_bytes)), "a larger unit divides all three"
+
+
 def test_blob_mask_fraction():
     m = ND.blob_mask(100_000, 0.3, seed=1)
     assert 0.3 <= m.mean() < 0.36
@@ -98,6 +128,7 @@ def test_new_entry_points_are_exported_and_bound():
         assert callable(getattr(_native.Index, method))
     assert callable(_native.QueryStream.set_nodata) and callable(_native.QueryStream.valid_rows)
     assert callable(_native.mask_rows_host) and callable(_native.mask_rows_device)
+    assert callable(_native.debug_mask_compact) and callable(_native.debug_expand_rows)
 
 
 def test_argument_errors_without_touching_a_device():
@@ -116,3 +147,20 @@ def test_argument_errors_without_touching_a_device():
     assert lib.sknnr_stream_set_nodata(None, nd, -1) == _native.ERR_INVALID
     assert lib.sknnr_stream_valid_rows(None, ctypes.byref(nv)) == _native.ERR_INVALID
     assert lib.sknnr_debug_last_mask(None, (ctypes.c_int64 * 8)()) == _native.ERR_INVALID
+    unit = ctypes.c_int32(-1)
+    assert lib.sknnr_debug_mask_compact(None, 4, 0, 0, nd, 0, None, None, None, None, None, ctypes.byref(unit),
+                                        ctypes.byref(nv)) == _native.ERR_INVALID
+    assert lib.sknnr_debug_mask_compact(None, 4, 2, 99, nd, 0, None, None, None, None, None, ctypes.byref(unit),
+                                        ctypes.byref(nv)) == _native.ERR_INVALID
+    assert lib.sknnr_debug_mask_compact(None, -1, 2, 0, nd, 0, None, None, None, None, None, ctypes.byref(unit),
+                                        ctypes.byref(nv)) == _native.ERR_INVALID
+    assert lib.sknnr_debug_mask_compact(None, 4, 2, 0, None, 0, None, None, None, None, None, ctypes.byref(unit),
+                                        ctypes.byref(nv)) == _native.ERR_INVALID
+    # no rows: nothing is launched, the unit is still the one of (NULL, NULL, 2 x float64)
+    assert lib.sknnr_debug_mask_compact(None, 0, 2, 0, nd, 0, None, None, None, None, None, ctypes.byref(unit),
+                                        ctypes.byref(nv)) == 0 and nv.value == 0 and unit.value == 16
+    assert lib.sknnr_debug_mask_compact(None, 4, 2, 0, nd, 0, None, None, None, None, None, ctypes.byref(unit),
+                                        ctypes.byref(nv)) == _native.ERR_INVALID and b"NULL" in lib.sknnr_last_error()
+    assert lib.sknnr_debug_expand_rows(-1, 3, 2, *[None] * 8, -1, None) == _native.ERR_INVALID
+    assert lib.sknnr_debug_expand_rows(4, 0, 2, *[None] * 8, -1, None) == _native.ERR_INVALID
+    assert lib.sknnr_debug_expand_rows(4, 3, 0, *[None] * 8, -1, None) == _native.ERR_INVALID

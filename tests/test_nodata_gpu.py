@@ -10,6 +10,10 @@ is compared with the host restatement (tests/_nodata.py).
 
 from __future__ import annotations
 
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -17,6 +21,7 @@ import _nodata as ND
 
 pytestmark = pytest.mark.gpu
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_REF, K = 500, 3
 SENTINEL = {np.dtype(np.uint8): 255, np.dtype(np.int16): -32768, np.dtype(np.float32): -9999.0,
             np.dtype(np.float64): -9999.0}
@@ -211,6 +216,113 @@ def test_stream_equals_one_masked_call_and_the_yardstick(raw, N):
     yd, yi = est.kneighbors(x)
     np.testing.assert_array_equal(i3, yi)
     np.testing.assert_array_equal(d3, yd)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# more tiles than the host pipeline has slots (kHostSlots = 4): the per-slot mask buffers are reused while other tiles
+# are in flight, and regrown by a larger tile
+# ---------------------------------------------------------------------------------------------------------------------
+LONG_SIZES = (300, 1000, 1, 257, 2000, 64, 700, 256, 1500, 5)
+LONG_KINDS = ("random30", "none", "all", "alternating", "block_run", "all", "first", "none", "random30", "last")
+
+
+def long_stream_tiles(d, dtype):
+    masks = [ND.make_mask(kind, n, seed=40 + i) for i, (n, kind) in enumerate(zip(LONG_SIZES, LONG_KINDS))]
+    tiles = [queries(n, d, dtype, m, seed=60 + i) for i, (n, m) in enumerate(zip(LONG_SIZES, masks))]
+    return tiles, masks
+
+
+def test_long_stream_reuses_and_regrows_the_slots(raw):
+    d = 7
+    est = raw(d, "distance")
+    eng = est.engine_
+    tiles, masks = long_stream_tiles(d, np.int16)
+    assert len(tiles) > 2 * 4 and max(LONG_SIZES[4:]) > max(LONG_SIZES[:4])  # every slot reused twice, and regrown
+    x = np.concatenate(tiles)
+    valid = ~np.concatenate(masks)
+    nodata = np.full(d, -32768.0)
+    # kneighbors_chunks
+    dist, idx = est.kneighbors_chunks(iter(tiles), nodata=-32768, fill_index=-7)
+    check_against_yardstick(est, x, valid, dist, idx, fill_index=-7)
+    d1, i1 = eng.kneighbors(x, K, formula=est._formula(), nodata=nodata, fill_index=-7)
+    np.testing.assert_array_equal(i1, idx)
+    np.testing.assert_array_equal(d1, dist)
+    # predict_chunks
+    pred = est.predict_chunks(iter(tiles), nodata=-32768)
+    assert pred.shape == (x.shape[0], 2)
+    np.testing.assert_array_equal(pred[valid], est.predict(x[valid]))
+    assert np.isnan(pred[~valid]).all() and not np.isnan(pred[valid]).any()
+    p1 = eng.predict(x, K, "distance", formula=est._formula(), nodata=nodata)
+    np.testing.assert_array_equal(p1, pred)
+    # the native stream, neighbours and predictions at once; valid_rows() after every push
+    qdt = eng.query_dtype_code(x, est._formula(), False)
+    stream = eng.open_stream(K, weights="distance", formula=est._formula(), query_dtype=qdt, nodata=nodata, fill_index=-7)
+    outs, seen = [], 0
+    for tile, m in zip(tiles, masks):
+        outs.append(stream.push(tile))
+        seen += int((~m).sum())
+        assert stream.valid_rows() == seen
+    assert stream.close() == x.shape[0]
+    np.testing.assert_array_equal(np.concatenate([o[0] for o in outs]), idx)
+    np.testing.assert_array_equal(np.concatenate([o[1] for o in outs]), dist)
+    np.testing.assert_array_equal(np.concatenate([o[2] for o in outs]), pred)
+
+
+_CHILD = """
+import sys, numpy as np
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+import _nodata as ND
+import sknnr_amd
+K, d, nq = 3, 7, {nq}
+rng = np.random.default_rng(107)
+ref = rng.integers(0, 6, size=(500, d)).astype(np.float64)
+y = np.random.default_rng(7).standard_normal((500, 2))
+est = sknnr_amd.RawKNNRegressor(n_neighbors=K, weights="distance").fit(ref, y)
+eng = est.engine_
+masked = ND.blob_mask(nq, 0.3, seed=5, mean_len=600)
+masked[3000:8000] = True    # whole tiles without a valid row ...
+masked[10000:15000] = False  # ... and whole tiles without a masked one
+x = rng.integers(0, 6, size=(nq, d)).astype(np.int16)
+rows = np.flatnonzero(masked)
+x[rows, rng.integers(0, d, size=rows.size)] = -32768
+nodata = np.full(d, -32768.0)
+valid = ND.row_mask(x, nodata).astype(bool)
+assert (valid == ~masked).all()
+qdt = eng.query_dtype_code(x, est._formula(), False)
+kw = dict(exclude_self=False, deterministic=True, decimals=est.DISTANCE_PRECISION_DECIMALS, formula=est._formula(),
+          apply_affine=False, check_finite=True, query_dtype=qdt)
+dist, idx, n_valid = eng._index.kneighbors_masked_host(x, eng._opts(K, **kw), nodata, fill_index=-7)
+rec = eng._index.debug_last_mask()
+assert n_valid == valid.sum() and rec["ran"] == 1 and rec["valid_total"] == n_valid, (n_valid, rec)
+assert rec["rows"] <= 2048 < nq, rec  # the record describes the LAST tile: the call was cut into tiles
+pred, pd, pi, nv2 = eng._index.predict_masked_host(x, eng._opts(K, weight_mode=eng.weight_mode("distance"), **kw), nodata,
+                                                   fill_index=-7, return_neighbors=True)
+assert nv2 == n_valid
+yd, yi = est.kneighbors(x[valid])
+np.testing.assert_array_equal(idx[valid], yi)
+np.testing.assert_array_equal(dist[valid], yd)
+assert (idx[~valid] == -7).all() and np.isnan(dist[~valid]).all() and not np.isnan(dist[valid]).any()
+np.testing.assert_array_equal(pi, idx)
+np.testing.assert_array_equal(pd, dist)
+np.testing.assert_array_equal(pred[valid], est.predict(x[valid]))
+assert np.isnan(pred[~valid]).all() and not np.isnan(pred[valid]).any()
+print("ok", nq, int(n_valid), rec["rows"])
+"""
+
+
+@pytest.mark.parametrize("ramp", [True, False])
+def test_one_host_call_spanning_the_pipeline_slots(ramp):
+    """SKNNR_HOST_CHUNK_ROWS is read once per process: a child answers 20,000 rows in one masked host call with tiles of
+    at most 2,048 rows -- ten or more tiles through the four slots, once ramping up (256, 512, 1,024, then 2,048: every
+    slot's mask buffers regrown) and once without -- and compares with the yardstick itself."""
+    env = dict(os.environ, SKNNR_HOST_CHUNK_ROWS="2048")
+    env.pop("SKNNR_PIPE_NO_RAMP", None)
+    if not ramp:
+        env["SKNNR_PIPE_NO_RAMP"] = "1"
+    run = subprocess.run([sys.executable, "-c", _CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"), nq=20_000)],
+                         env=env, capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-3000:]
+    assert run.stdout.strip().splitlines()[-1].startswith("ok 20000 "), run.stdout[-500:]
 
 
 def test_dataframe_index_of_masked_rows_is_the_fill(raw):
