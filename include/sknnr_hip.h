@@ -405,6 +405,49 @@ int sknnr_predict_masked(sknnr_index* index, const void* q, int64_t nq, const sk
 int sknnr_stream_set_nodata(sknnr_stream* stream, const double* nodata, int64_t fill_index);
 int sknnr_stream_valid_rows(const sknnr_stream* stream, int64_t* out_valid_rows);
 
+/* ---- band-first tiles (raster layouts) ------------------------------------------------------ */
+
+/*
+ * Raster readers deliver a window as (bands, h, w) and raster writers want (targets, h, w); every search kernel reads
+ * packed (n, bands) rows and writes (n, k) / (n, t) rows.  The entry points below do both transpositions on the device
+ * (sknnr_amd/csrc/planes.hip.h), so that no strided pass over a tile is left to the host.
+ *
+ * sknnr_planes_to_rows: no handle.  src holds c planes of n elements of elem_bytes (1, 2, 4 or 8) each, plane j starting
+ *   j * src_stride ELEMENTS after src (src_stride >= n); dst receives the packed (n, c) rows.  Both are DEVICE memory on
+ *   `device`, at any address that is a multiple of elem_bytes.  A raw byte move: no value is widened or looked at.
+ * sknnr_rows_to_planes: the reverse for 8-byte elements (int64 indices, float64 distances and predictions): src packed
+ *   (n, c) rows, plane j of dst starting j * dst_stride elements after dst (dst_stride >= n).
+ *   Both enqueue on `stream` and return; c in [1, 65536], n below 2^31.  SKNNR_ERR_INVALID, before any device call, for
+ *   elem_bytes outside {1, 2, 4, 8}, n < 0, c < 1, a stride below n and NULL pointers; n == 0 is SKNNR_OK.
+ * sknnr_stream_push_planes: sknnr_stream_push for a band-first tile.  planes: HOST array of d_in (or d) HOST pointers,
+ *   each to nq contiguous elements of the stream's opts->query_dtype (the bands may be separate arrays); the array and the
+ *   bands may be reused as soon as the call returns.  Results are band-first too: neighbour j of the tile starts at
+ *   out_idx + j * out_stride (out_dist likewise), target j at out_pred + j * out_stride; out_stride >= nq elements.
+ *   The tile is staged with one plain copy per band, transposed behind its host-to-device copy (in front of the nodata
+ *   mask, where one is set), searched exactly as a row tile is, and its results are transposed before they leave the
+ *   device: bit for bit the rows sknnr_stream_push gives for the transposed tile.  Buffer lifetime, flush / end,
+ *   check_finite, sknnr_stream_set_nodata and the row offset are as for sknnr_stream_push.  A stream may mix both kinds
+ *   of push: each tile's results come in the layout of its own push, and row positions run on across them.
+ */
+int sknnr_planes_to_rows(const void* src, int64_t n, int32_t c, int32_t elem_bytes, int64_t src_stride, void* dst,
+                         int32_t device, void* stream);
+int sknnr_rows_to_planes(const void* src, int64_t n, int32_t c, void* dst, int64_t dst_stride, int32_t device,
+                         void* stream);
+int sknnr_stream_push_planes(sknnr_stream* stream, const void* const* planes, int64_t nq, double* out_dist,
+                             int64_t* out_idx, double* out_pred, int64_t out_stride);
+
+/*
+ * Debug only.  The last tile the handle's host pipeline submitted (host-memory calls and streams), so that a test can
+ * prove that the device transposed it, not the host.  Host memory, no device work:
+ *   out[0] 1 = its rows arrived as planes and planes_to_rows_kernel packed them on the device, 0 = a row tile
+ *   out[1] rows of the tile      out[2] its columns      out[3] bytes per element
+ *   out[4] 1 = its results left as planes (rows_to_planes_kernel), 0 = as rows
+ *   out[5] output planes written (k per index / distance output, t for predictions; 0 for a row tile)
+ *   out[6] columns one workgroup of planes_to_rows_kernel handles at that element size (0 for a row tile)
+ *   out[7] 0
+ */
+int sknnr_debug_last_planes(const sknnr_index* index, int64_t out[8]);
+
 /*
  * Debug only.  The nodata front end of the most recent call on the handle (its last tile), so that a test can prove
  * which path served it.  Host memory, no device work:

@@ -85,6 +85,49 @@ def normalize_nodata(nodata, n_features, dtype):
     return np.ascontiguousarray(arr)
 
 
+_LAYOUTS = ("rows", "bands")
+
+
+def _check_layout(layout):
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout must be 'rows' or 'bands', got {layout!r}")
+    return layout == "bands"
+
+
+def normalize_band_tile(tile, n_bands, *, forest=False, estimator="the estimator"):
+    """A band-first tile of a streamed call (``layout="bands"``) as ``(bands, n)``: ``n_bands`` 1-D C-contiguous arrays of
+    one dtype, and their length.  ``tile`` is an array ``(bands, ...)`` of any trailing shape -- ``(bands, n)``,
+    ``(bands, h, w)``; pixels are taken in C order of the trailing axes -- or a sequence of ``bands`` arrays of one shape
+    and dtype.  A band of a dtype the device does not read (:data:`_QUERY_DTYPES`) is converted to float64 (``forest``:
+    64-bit integers to float32, as ``_validate_forest_query`` does), a band that is not contiguous is copied; both band
+    by band.  Nothing is transposed on the host."""
+    if is_torch_cuda_tensor(tile) or (isinstance(tile, (list, tuple)) and any(is_torch_cuda_tensor(b) for b in tile)):
+        raise TypeError("streamed tiles are host arrays (they travel through the pinned "
+                        "PCIe pipeline); pass CUDA tensors to kneighbors() / predict()")
+    if isinstance(tile, np.ndarray):
+        if tile.ndim < 2:
+            raise ValueError(f"a band-first tile is an array (bands, ...) or a sequence of bands, got shape {tile.shape}")
+        bands = [tile[j] for j in range(tile.shape[0])]
+    else:
+        try:
+            bands = [np.asarray(b) for b in tile]
+        except TypeError as err:
+            raise ValueError("a band-first tile is an array (bands, ...) or a sequence of bands, got "
+                             f"{type(tile).__name__}") from err
+    if len(bands) != n_bands:
+        raise ValueError(f"X has {len(bands)} features, but {estimator} is expecting {n_bands} features as input.")
+    shape, dtype = bands[0].shape, bands[0].dtype
+    for j, b in enumerate(bands):
+        if b.shape != shape or b.dtype != dtype:
+            raise ValueError(f"the bands of a tile must share one shape and dtype: band {j} is {b.dtype} {b.shape}, "
+                             f"band 0 {dtype} {shape}")
+    if dtype not in _QUERY_DTYPES:
+        dtype = np.dtype(np.float32 if forest and dtype in (np.int64, np.uint64) else np.float64)
+    # (ascontiguousarray copies only a band that is strided or of another dtype; reshape of a contiguous band is a view)
+    bands = [np.ascontiguousarray(b, dtype=dtype).reshape(-1) for b in bands]
+    return bands, int(bands[0].shape[0])
+
+
 def _resolve_fit_method(algorithm, n_ref, d, k):
     """Which of the reference's engines -- hence which float64 distance expression -- the
     ``algorithm`` setting selects (SKL/neighbors/_base.py:620-648)."""
@@ -568,15 +611,34 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             raise NotImplementedError("nodata is not supported under tree_tie_policy('tree'): tied rows are chosen on "
                                       "the host, tile by tile; use the default policy 'lowest_index'")
 
+    def _check_bands_supported(self):
+        """Band-first tiles are transposed on the device, inside a native stream; the paths that answer tile by tile on
+        the host refuse them."""
+        if self._numpy_ties():
+            raise NotImplementedError("layout='bands' is not supported under hamming_tie_policy('numpy'): tied rows are "
+                                      "chosen on the host, tile by tile; use the default policy 'lowest_index'")
+        if self._tree_ties():
+            raise NotImplementedError("layout='bands' is not supported under tree_tie_policy('tree'): tied rows are "
+                                      "chosen on the host, tile by tile; use the default policy 'lowest_index'")
+
     def _stream_tiles(self, tiles, validate, k, *, apply_affine, weights, return_distance,
-                      use_deterministic_ordering, out, owner, nodata=None, fill_index=-1):
+                      use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False):
         """Push host tiles through one native query stream.  Returns (dist, idx, pred) arrays over all
         pushed rows (pieces of ``out`` when given, else concatenated).  ``nodata`` (float64, one value per column of the
-        validated tiles): rows holding one are masked on the device and get ``fill_index`` / NaN."""
+        validated tiles): rows holding one are masked on the device and get ``fill_index`` / NaN.
+
+        ``bands``: the tiles are band-first -- ``validate`` gives ``(bands, n)`` (:func:`normalize_band_tile`), the outputs
+        are ``(k, N)`` / ``(t, N)``, pixels along axis 1, and tile ``i`` lands in columns ``[row, row + n_i)``; the
+        ``out`` arrays must then share one ``N``, the stride between their planes."""
         eng = self.engine_
         want_pred = weights is not None
         t_cols = eng.t
         self._check_nodata_supported(nodata)
+        if bands:
+            self._check_bands_supported()
+            widths = {a.shape[1] for a in (out or ()) if a is not None and a.ndim == 2 and a.shape[0] > 1}
+            if len(widths) > 1:
+                raise ValueError(f"out arrays must share one number of columns (the stride between planes), got {sorted(widths)}")
         if self._reference_ties():
             # the reference's choice among tied rows is made on the host, per call: tile by tile, positions carried
             parts, row = [], 0
@@ -612,40 +674,51 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 if is_torch_cuda_tensor(tile):
                     raise TypeError("streamed tiles are host arrays (they travel through the pinned "
                                     "PCIe pipeline); pass CUDA tensors to kneighbors() / predict()")
-                tile = validate(tile)
-                n = tile.shape[0]
+                if bands:  # (``tile``: the list of 1-D bands; ``first`` stands for its element type)
+                    tile, n = validate(tile)
+                    first, n_cols = tile[0], len(tile)
+                else:
+                    tile = first = validate(tile)
+                    n, n_cols = tile.shape
                 if n == 0:
                     continue
                 if stream is None:
                     # the element type of the first tile is the stream's (narrow rasters travel at their own width)
-                    code = eng.query_dtype_code(tile, self._formula(), apply_affine)
-                    stream_dtype = tile.dtype if code else np.dtype(np.float64)
+                    code = eng.query_dtype_code(first, self._formula(), apply_affine)
+                    stream_dtype = first.dtype if code else np.dtype(np.float64)
                     if nodata is not None:  # (a NaN entry needs rows that can hold NaN)
-                        nodata = normalize_nodata(nodata, tile.shape[1], stream_dtype)
+                        nodata = normalize_nodata(nodata, n_cols, stream_dtype)
                     stream = eng.open_stream(k, weights=weights, want_dist=return_distance,
                                              deterministic=use_deterministic_ordering,
                                              decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula(),
                                              apply_affine=apply_affine, check_finite=True, query_dtype=code,
                                              nodata=nodata, fill_index=fill_index)
-                if tile.dtype != stream_dtype:
+                if first.dtype != stream_dtype:
                     if stream_dtype != np.float64:
-                        raise ValueError(f"the tiles of one streamed call must share an element type: got {tile.dtype} "
+                        raise ValueError(f"the tiles of one streamed call must share an element type: got {first.dtype} "
                                          f"after {stream_dtype}")
-                    tile = np.ascontiguousarray(tile, dtype=np.float64)
+                    tile = ([np.ascontiguousarray(b, dtype=np.float64) for b in tile] if bands
+                            else np.ascontiguousarray(tile, dtype=np.float64))
 
                 def window(arr, cols, dtype):
                     if arr is None:
                         return None
+                    if bands:  # (cols planes; the window's planes stay one full row of arr apart)
+                        if arr.ndim != 2 or arr.shape[0] != cols or arr.dtype != dtype or not arr.flags.c_contiguous \
+                                or arr.shape[1] < row + n:
+                            raise ValueError(f"out arrays must be C-contiguous, {np.dtype(dtype)}, with "
+                                             f"{cols} rows and at least {row + n} columns")
+                        return arr[:, row:row + n]
                     w = arr[row:row + n]
                     if w.shape != (n, cols) or w.dtype != dtype or not w.flags.c_contiguous:
                         raise ValueError(f"out arrays must be C-contiguous, {np.dtype(dtype)}, with "
                                          f"{cols} columns and at least {row + n} rows")
                     return w
 
-                got = stream.push(tile, out_idx=window(o_idx, k, np.int64),
-                                  out_dist=window(o_dist, k, np.float64) if return_distance else None,
-                                  out_pred=window(o_pred, t_cols, np.float64) if want_pred else None,
-                                  need_idx=not want_pred)
+                got = (stream.push_planes if bands else stream.push)(
+                    tile, out_idx=window(o_idx, k, np.int64),
+                    out_dist=window(o_dist, k, np.float64) if return_distance else None,
+                    out_pred=window(o_pred, t_cols, np.float64) if want_pred else None, need_idx=not want_pred)
                 if out is None:
                     pieces.append(got)
                 row += n
@@ -661,16 +734,16 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 except _native.HipBackendError:
                     pass
         if out is not None:
-            trim = lambda a: None if a is None else a[:row]  # noqa: E731
+            trim = lambda a: None if a is None else (a[:, :row] if bands else a[:row])  # noqa: E731
             return trim(o_dist) if return_distance else None, trim(o_idx), trim(o_pred) if want_pred else None
-        cat = lambda i, cols, dt: (np.concatenate([p[i] for p in pieces]) if pieces  # noqa: E731
-                                   else np.empty((0, cols), dtype=dt))
+        cat = lambda i, cols, dt: (np.concatenate([p[i] for p in pieces], axis=1 if bands else 0) if pieces  # noqa: E731
+                                   else np.empty((cols, 0) if bands else (0, cols), dtype=dt))
         return (cat(1, k, np.float64) if return_distance else None,
                 None if want_pred else cat(0, k, np.int64),
                 cat(2, t_cols, np.float64) if want_pred else None)
 
     def kneighbors_chunks(self, tiles, n_neighbors=None, return_distance=True, return_dataframe_index=False,
-                          use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1):
+                          use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1, layout="rows"):
         """``kneighbors`` over an iterable of host tiles ``(n_i, n_features)`` -- windows of a raster,
         slices of a ``numpy.memmap`` -- as ONE logical call: the copy-in / kernels / copy-out pipeline
         stays full across tiles and row positions count over all tiles, so the result equals
@@ -680,17 +753,27 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         ``nodata``: a scalar, or one value per input column (NaN: "NaN in that column").  Rows in which any column
         equals its nodata value are masked on the device: they cost no search, are not tested for finiteness and get
         ``fill_index`` (as index or dataframe id) and NaN distances; the other rows get exactly what
-        ``kneighbors(X[valid])`` returns, row positions counting valid rows only."""
+        ``kneighbors(X[valid])`` returns, row positions counting valid rows only.
+
+        ``layout="bands"``: every tile is band-first, as raster readers deliver a window -- an array ``(bands, ...)`` of
+        any trailing shape, or a sequence of ``bands`` arrays -- and the results are band-first too: ``(k, N)`` arrays
+        (``out``: C-contiguous ``(k, N_total)``), concatenated along the pixel axis.  Both transpositions run on the
+        device; ``[j, p]`` equals ``[p, j]`` of the row call on the transposed tiles, bit for bit."""
+        bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         k = self._resolve_k(n_neighbors)
         if nodata is not None:
             nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
         o = None if out is None else (out[0], out[1], None)
+        validate = self._validate_query
+        if bands:
+            validate = lambda t: normalize_band_tile(t, self.n_features_in_, estimator=type(self).__name__)  # noqa: E731
         # (dataframe ids: masked rows travel as -1, which no row index equals, and take fill_index after the crosswalk)
-        dist, idx, _ = self._stream_tiles(tiles, self._validate_query, k, apply_affine=False, weights=None,
+        dist, idx, _ = self._stream_tiles(tiles, validate, k, apply_affine=False, weights=None,
                                           return_distance=return_distance,
                                           use_deterministic_ordering=use_deterministic_ordering, out=o, owner=None,
-                                          nodata=nodata, fill_index=-1 if return_dataframe_index else fill_index)
+                                          nodata=nodata, fill_index=-1 if return_dataframe_index else fill_index,
+                                          bands=bands)
         return self._finish_chunks(dist, idx, return_distance, return_dataframe_index,
                                    fill_index=None if nodata is None else fill_index)
 
@@ -719,17 +802,27 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 idx = table[idx]
         return (dist, idx) if return_distance else idx
 
-    def predict_chunks(self, tiles, out=None, nodata=None):
+    def predict_chunks(self, tiles, out=None, nodata=None, layout="rows"):
         """``predict`` over an iterable of host tiles as one streamed call; ``out``: preallocated
         ``(n_rows, n_targets)`` float64 array (e.g. a memmap; float32 results are held exactly).  ``nodata`` as in
-        :meth:`kneighbors_chunks`: masked rows are predicted NaN."""
+        :meth:`kneighbors_chunks`: masked rows are predicted NaN.  ``layout="bands"``: band-first tiles as in
+        :meth:`kneighbors_chunks`, and ``(n_targets, N)`` predictions (``out``: C-contiguous ``(n_targets, N_total)``, e.g.
+        ``raster.reshape(t, H * W)`` of a memmapped output raster); ``(N,)`` for a 1-D ``y`` as ever."""
+        bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         if nodata is not None:
             nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
-        return self._predict_chunks(tiles, self._validate_query, apply_affine=False, out=out, owner=None, nodata=nodata)
+        validate = self._validate_query
+        if bands:
+            validate = lambda t: normalize_band_tile(t, self.n_features_in_, estimator=type(self).__name__)  # noqa: E731
+        return self._predict_chunks(tiles, validate, apply_affine=False, out=out, owner=None, nodata=nodata, bands=bands)
 
-    def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None):
+    def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None, bands=False):
         weights = "uniform" if self.weights is None else self.weights
+        if callable(weights) and bands:
+            raise NotImplementedError("layout='bands' is not supported with callable weights: the callable runs on the "
+                                      "host between the search and the reduction, on row-major neighbours; use "
+                                      "'uniform' or 'distance'")
         if callable(weights) and nodata is not None:
             raise NotImplementedError("nodata is not supported with callable weights: the callable runs on the host "
                                       "between the search and the reduction, tile by tile; use 'uniform' or 'distance'")
@@ -746,9 +839,12 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 pred = out[:len(pred)]
         else:
             o = None if out is None else (None, None, out.reshape(out.shape[0], -1))
+            if bands and out is not None and out.ndim == 1:  # (a 1-D y: the one target plane)
+                o = (None, None, out.reshape(1, -1))
             _, _, pred = self._stream_tiles(tiles, validate, self.n_neighbors, apply_affine=apply_affine,
                                             weights=weights, return_distance=False,
-                                            use_deterministic_ordering=True, out=o, owner=owner, nodata=nodata)
+                                            use_deterministic_ordering=True, out=o, owner=owner, nodata=nodata,
+                                            bands=bands)
             if out is None:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
                 pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         return pred.reshape(-1) if self._y.ndim == 1 else pred
@@ -921,30 +1017,48 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
                                       "host, so the raw rows never reach the device")
         return normalize_nodata(nodata, self.regressor_.engine_.d_in, np.float64)
 
+    def _band_validator(self, bands):
+        """``layout="bands"``: the tiles' bands must reach the engine raw (affine map or forests on the device), where
+        they are transposed; returns what turns a tile into ``(bands, n)``, or the row validator."""
+        if not bands:
+            return self._validate_raw_query
+        if not self._map_on_device():
+            raise NotImplementedError(f"layout='bands' is not supported by {type(self).__name__}: its transformer runs on "
+                                      "the host, on row-major rows, so the bands never reach the device")
+        d_in = self.regressor_.engine_.d_in
+        forest = getattr(self, "_device_forest", False)
+        name = type(self.transformer_).__name__ if forest else type(self).__name__
+        return lambda t: normalize_band_tile(t, d_in, forest=forest, estimator=name)
+
     def kneighbors_chunks(self, tiles, n_neighbors=None, return_distance=True, return_dataframe_index=False,
-                          use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1):
+                          use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1, layout="rows"):
         """``kneighbors`` over an iterable of untransformed host tiles as one streamed call (see
         :meth:`RawKNNRegressor.kneighbors_chunks`, also for ``nodata`` / ``fill_index``: the nodata values are those of
-        the untransformed columns); each tile is transformed on the device."""
+        the untransformed columns -- and for ``layout="bands"``); each tile is transformed on the device."""
+        bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
         reg = self.regressor_
         k = reg._resolve_k(n_neighbors)
+        validate = self._band_validator(bands)
         nodata = self._raw_nodata(nodata)
         o = None if out is None else (out[0], out[1], None)
-        dist, idx, _ = reg._stream_tiles(tiles, self._validate_raw_query, k, apply_affine=self._map_on_device(), weights=None,
+        dist, idx, _ = reg._stream_tiles(tiles, validate, k, apply_affine=self._map_on_device(), weights=None,
                                          return_distance=return_distance,
                                          use_deterministic_ordering=use_deterministic_ordering, out=o,
                                          owner=self.transformer_, nodata=nodata,
-                                         fill_index=-1 if return_dataframe_index else fill_index)
+                                         fill_index=-1 if return_dataframe_index else fill_index, bands=bands)
         return reg._finish_chunks(dist, idx, return_distance, return_dataframe_index,
                                   fill_index=None if nodata is None else fill_index)
 
-    def predict_chunks(self, tiles, out=None, nodata=None):
+    def predict_chunks(self, tiles, out=None, nodata=None, layout="rows"):
         """``predict`` over an iterable of untransformed host tiles as one streamed call (``nodata``: masked rows are
-        predicted NaN, see :meth:`RawKNNRegressor.kneighbors_chunks`)."""
+        predicted NaN; ``layout="bands"``: band-first tiles and predictions; see
+        :meth:`RawKNNRegressor.kneighbors_chunks` / :meth:`RawKNNRegressor.predict_chunks`)."""
+        bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
-        return self.regressor_._predict_chunks(tiles, self._validate_raw_query, apply_affine=self._map_on_device(),
-                                               out=out, owner=self.transformer_, nodata=self._raw_nodata(nodata))
+        return self.regressor_._predict_chunks(tiles, self._band_validator(bands), apply_affine=self._map_on_device(),
+                                               out=out, owner=self.transformer_, nodata=self._raw_nodata(nodata),
+                                               bands=bands)
 
     def score(self, X, y):
         """REF _base.py:350-352."""

@@ -84,6 +84,10 @@ EXPORTED_SYMBOLS = (
     "sknnr_predict_masked",
     "sknnr_stream_set_nodata",
     "sknnr_stream_valid_rows",
+    "sknnr_planes_to_rows",
+    "sknnr_rows_to_planes",
+    "sknnr_stream_push_planes",
+    "sknnr_debug_last_planes",
     "sknnr_debug_last_mask",
     "sknnr_debug_mask_compact",
     "sknnr_debug_expand_rows",
@@ -207,6 +211,10 @@ def load(build_if_missing: bool = False):
     lib.sknnr_stream_set_nodata.argtypes = [vp, vp, c_int64]
     lib.sknnr_stream_valid_rows.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_last_mask.argtypes = [vp, POINTER(c_int64)]
+    lib.sknnr_planes_to_rows.argtypes = [vp, c_int64, c_int32, c_int32, c_int64, vp, c_int32, vp]
+    lib.sknnr_rows_to_planes.argtypes = [vp, c_int64, c_int32, vp, c_int64, c_int32, vp]
+    lib.sknnr_stream_push_planes.argtypes = [vp, vp, c_int64, vp, vp, vp, c_int64]
+    lib.sknnr_debug_last_planes.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_mask_compact.argtypes = [vp, c_int64, c_int32, c_int32, vp, c_int32, vp, vp, vp, vp, vp,
                                              POINTER(c_int32), POINTER(c_int64)]
     lib.sknnr_debug_expand_rows.argtypes = [c_int64, c_int32, c_int32, vp, vp, vp, vp, vp, vp, vp, vp, c_int64, vp]
@@ -474,6 +482,14 @@ class Index:
         return dict(zip(self.MASK_FIELDS, (int(v) for v in out)))
 
     # ---- device-pointer entry points (ints from tensor.data_ptr()) ------------------------
+    def debug_last_planes(self) -> dict:
+        """Debug only: the last tile of the host pipeline (sknnr_debug_last_planes): whether its rows arrived as planes
+        and were packed on the device, its shape, and whether (and how many) result planes were written there."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_planes(self.handle, out))
+        keys = ("planes_in", "rows", "cols", "elem_bytes", "planes_out", "out_planes", "chunk_cols")
+        return {key: int(out[i]) for i, key in enumerate(keys)}
+
     def kneighbors_device(self, q_ptr, nq, opts: QueryOpts, dist_ptr, idx_ptr, stream=0):
         check(load().sknnr_kneighbors(self.handle, c_void_p(q_ptr or None), nq, byref(opts),
                                       c_void_p(dist_ptr or None), c_void_p(idx_ptr), MEM_DEVICE,
@@ -693,6 +709,46 @@ class QueryStream:
             del self._keep[:-8]  # older tiles have left the pipeline (four slots: at most the last four pushes are pending)
         return out_idx, out_dist, out_pred
 
+    def push_planes(self, bands, out_idx=None, out_dist=None, out_pred=None, need_idx=True):
+        """Answer a band-first tile (sknnr_stream_push_planes): ``bands`` is a sequence of 1-D C-contiguous arrays of one
+        length ``n`` and of the stream's element type, one per input column.  Returns the band-first (idx, dist, pred)
+        arrays that will hold the results: ``(k, n)`` / ``(t, n)``, fresh ones, or the ones passed in -- those may be
+        column windows ``a[:, r0:r0 + n]`` of a C-contiguous ``(k or t, N)`` array."""
+        cols = self._index.d_in if self._opts.apply_affine else self._index.d
+        want = next(dt for dt, code in DTYPE_CODES.items() if code == self._opts.query_dtype)
+        bands = list(bands)
+        if len(bands) != cols:
+            raise ValueError(f"a band-first tile needs {cols} bands, got {len(bands)}")
+        nq = bands[0].shape[0]
+        for b in bands:
+            if b.ndim != 1 or b.shape[0] != nq or b.dtype != want or not b.flags.c_contiguous:
+                raise ValueError(f"every band must be a C-contiguous ({nq},) {want} array")
+        if out_idx is None and (need_idx or not self.want_pred):
+            out_idx = np.empty((self.k, nq), dtype=np.int64)
+        if out_dist is None and self.want_dist:
+            out_dist = np.empty((self.k, nq), dtype=np.float64)
+        if out_pred is None and self.want_pred:
+            out_pred = np.empty((self._index.t, nq), dtype=np.float64)
+        strides = set()
+        for a, dt, planes in ((out_idx, np.int64, self.k), (out_dist, np.float64, self.k),
+                              (out_pred, np.float64, self._index.t)):
+            if a is None:
+                continue
+            if a.dtype != dt or a.shape != (planes, nq) or (nq > 1 and a.strides[1] != 8):
+                raise ValueError(f"output arrays must be ({planes}, {nq}) {np.dtype(dt)} with contiguous planes")
+            if planes > 1:  # (a single plane has no stride to speak of)
+                strides.add(a.strides[0])
+        if len(strides) > 1 or any(st % 8 or st < 8 * nq for st in strides):
+            raise ValueError("output arrays must share one stride between planes, of at least the tile's pixels")
+        stride = strides.pop() // 8 if strides else nq
+        ptrs = (c_void_p * cols)(*[b.ctypes.data for b in bands])
+        check(load().sknnr_stream_push_planes(self._h, ptrs, nq, _host_ptr(out_dist), _host_ptr(out_idx),
+                                              _host_ptr(out_pred), stride))
+        self._keep.append((out_idx, out_dist, out_pred))
+        if len(self._keep) > 8:
+            del self._keep[:-8]
+        return out_idx, out_dist, out_pred
+
     def set_nodata(self, nodata, fill_index=-1):
         """Mask every pushed tile on the device (sknnr_stream_set_nodata; only before the first push)."""
         nodata = _c_f64(nodata).reshape(-1)
@@ -818,3 +874,17 @@ def debug_expand_rows(nq, k, t, valid_ptr, rank_ptr, c_idx_ptr, c_dist_ptr, c_pr
     ptrs = [c_void_p(p or None) for p in (valid_ptr, rank_ptr, c_idx_ptr, c_dist_ptr, c_pred_ptr, idx_ptr, dist_ptr,
                                           pred_ptr)]
     check(load().sknnr_debug_expand_rows(nq, k, t, *ptrs, int(fill_index), c_void_p(stream or None)))
+
+
+def planes_to_rows_device(src_ptr, n, c, elem_bytes, src_stride, dst_ptr, device=0, stream=0) -> None:
+    """``c`` planes of ``n`` elements of ``elem_bytes``, ``src_stride`` elements apart, to packed ``(n, c)`` rows, on
+    device pointers (sknnr_planes_to_rows); enqueued on ``stream``."""
+    check(load().sknnr_planes_to_rows(c_void_p(src_ptr or None), n, c, elem_bytes, src_stride, c_void_p(dst_ptr or None),
+                                      device, c_void_p(stream or None)))
+
+
+def rows_to_planes_device(src_ptr, n, c, dst_ptr, dst_stride, device=0, stream=0) -> None:
+    """Packed ``(n, c)`` rows of 8-byte elements to ``c`` planes ``dst_stride`` elements apart, on device pointers
+    (sknnr_rows_to_planes); enqueued on ``stream``."""
+    check(load().sknnr_rows_to_planes(c_void_p(src_ptr or None), n, c, c_void_p(dst_ptr or None), dst_stride, device,
+                                      c_void_p(stream or None)))

@@ -1,9 +1,9 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
-// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK), templates where they are instantiated.
+// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES), templates where they are instantiated.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include "forest.hip.h"
 #include "hamming.hip.h"
 #include "mask.hip.h"
+#include "planes.hip.h"
 #include "rescue.hip.h"
 
 namespace sknnr {
@@ -60,6 +61,12 @@ hipError_t row_compact(const CompactArgs& a, size_t row_bytes, hipStream_t st);
 // bytes per copy row_compact chooses: the largest power of two up to 16 that divides row_bytes and both addresses
 int compact_unit(const void* x, const void* out, size_t row_bytes);
 hipError_t row_expand(const ExpandArgs& a, hipStream_t st);
+
+// ---- k_planes.hip: band-first tiles <-> packed rows (planes.hip.h) ------------------------------------------------------
+// a.c planes of a.n elements of elem_bytes (1, 2, 4 or 8), a.stride elements apart -> packed (n, c) rows; a raw byte move
+hipError_t planes_to_rows(const PlanesArgs& a, int elem_bytes, hipStream_t st);
+// packed (n, c) rows of 8-byte elements -> a.c planes of a.n elements, a.stride elements apart
+hipError_t rows_to_planes(const PlanesArgs& a, hipStream_t st);
 
 // ---- k_coarse1.hip / k_coarse2.hip: the MFMA pre-filters ----------------------------------------------------------------
 struct Coarse1Launch {

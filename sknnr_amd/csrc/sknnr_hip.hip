@@ -313,6 +313,9 @@ struct sknnr_index {
         double* pin_p = nullptr;  size_t pin_p_n = 0;
         DevBuf<double> dev_x, dev_d, dev_p;
         DevBuf<long> dev_i;
+        // band-first tiles (planes.hip.h): the uploaded planes in front of dev_x, the results as planes behind dev_i / dev_d / dev_p
+        DevBuf<double> dev_xp, dev_dp, dev_pp;
+        DevBuf<long> dev_ip;
         hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_d2h = nullptr;
         MaskBufs mask;  // nodata front end of the slot's tile (a pipeline with a mask only)
     } slot[kHostSlots];
@@ -359,6 +362,9 @@ struct sknnr_index {
     MaskBufs mask;
     DevBuf<double> m_nodata, s_nodata;
     int64_t last_mask[8] = {};
+    // the last tile of the host pipeline (sknnr_debug_last_planes): rows arrived as planes, rows, columns, element bytes,
+    // results left as planes, output planes written, columns per workgroup of planes_to_rows_kernel
+    int64_t last_planes[8] = {};
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
     // a ring of call records so that several calls of one benchmark step are summed, not only the last.
@@ -402,6 +408,7 @@ struct sknnr_index {
             for (void* hp : {(void*)sl.pin_x, (void*)sl.pin_d, (void*)sl.pin_i, (void*)sl.pin_p})
                 if (hp) (void)hipHostFree(hp);
             sl.dev_x.release(); sl.dev_d.release(); sl.dev_p.release(); sl.dev_i.release();
+            sl.dev_xp.release(); sl.dev_dp.release(); sl.dev_pp.release(); sl.dev_ip.release();
             for (hipEvent_t e : {sl.ev_h2d, sl.ev_done, sl.ev_d2h})
                 if (e) (void)hipEventDestroy(e);
         }
@@ -1507,7 +1514,7 @@ int coarse_list_len(const sknnr_index* ix, int kk) {
 }
 int coarse_rank_extra(int m_list, int kk) { return coarse2_rank_extra(m_list, kk); }
 
-void launch_finalize(const FinalizeArgs& f, long n, hipStream_t st) { (void)launch::finalize(f, n, st); }
+hipError_t launch_finalize(const FinalizeArgs& f, long n, hipStream_t st) { return launch::finalize(f, n, st); }
 
 constexpr int kScanGridWg = 256 * 4;  // workgroups of a scan launch (also what scan_slices splits among the passes)
 
@@ -1848,13 +1855,12 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
         f.fail_base = (int)c0;
         // rows [r0, r0 + rows) of the chunk (the kernel indexes everything by the row inside its window); bucketed
         // calls: POSITIONS [r0, r0 + rows) of the chunk, the kernel maps them to rows of the chunk
-        auto finalize_rows = [&](long r0, long rows, hipStream_t s_) {
+        auto finalize_rows = [&](long r0, long rows, hipStream_t s_) -> hipError_t {
             FinalizeArgs g = f;
             if (bucketed) {
                 g.pos0 = r0;
                 g.s.nq = rows;
-                launch_finalize(g, rows, s_);
-                return;
+                return launch_finalize(g, rows, s_);
             }
             g.s.xq = f.s.xq + r0 * ix->d;
             g.s.nq = rows;
@@ -1871,7 +1877,7 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
             }
             g.qnc = f.qnc + r0;
             g.fail_base = f.fail_base + (int)r0;
-            launch_finalize(g, rows, s_);
+            return launch_finalize(g, rows, s_);
         };
         ix->last_finalize[0] = launch::finalize_lanes(f);
         ix->last_finalize[1] = record ? 1 : 0;
@@ -1879,15 +1885,12 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
         if (done > 0) {
             // fork: the rows of the bulk launch are finalised on the side stream while the thin round runs here
             HIP_TRY(hipStreamWaitEvent(ix->st_side, ix->ev_fork, 0));
-            finalize_rows(0, done, ix->st_side);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(finalize_rows(0, done, ix->st_side));
             HIP_TRY(hipEventRecord(ix->ev_join, ix->st_side));
-            if (n > done) finalize_rows(done, n - done, st);
-            HIP_TRY(hipGetLastError());
+            if (n > done) HIP_TRY(finalize_rows(done, n - done, st));
             HIP_TRY(hipStreamWaitEvent(st, ix->ev_join, 0));  // join before anything else touches the workspace
         } else {
-            finalize_rows(0, n, st);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(finalize_rows(0, n, st));
         }
         if (rescue) {
             // the rows listed for this chunk, while its query image is in the workspace: one fixed-size launch that reads the
@@ -2191,6 +2194,40 @@ void parallel_copy(void* dst, const void* src, size_t bytes) {
     for (auto& t : th) t.join();
 }
 
+// Staging copy of a band-first tile: elements [off, off + n) of each of `c` separately held planes, packed (c, n) into
+// dst.  Plain copies, one per band (nothing is transposed on the host); a large tile's bands are shared out over a few
+// threads by the bytes of the packed destination, as parallel_copy does for rows.
+void stage_planes(void* dst, const void* const* planes, int c, size_t esz, long off, long n) {
+    const size_t seg = (size_t)n * esz, bytes = seg * c;
+    auto piece = [=](size_t a, size_t b) {  // bytes [a, b) of the packed destination
+        while (a < b) {
+            const size_t j = a / seg, within = a - j * seg, len = std::min(seg - within, b - a);
+            std::memcpy((char*)dst + a, (const char*)planes[j] + (size_t)off * esz + within, len);
+            a += len;
+        }
+    };
+    const size_t kMin = 8u << 20;
+    unsigned nt = std::min<unsigned>(8, std::max(1u, std::thread::hardware_concurrency()));
+    if (bytes < 2 * kMin) nt = 1;
+    if (nt == 1) {
+        piece(0, bytes);
+        return;
+    }
+    std::vector<std::thread> th;
+    const size_t per = ((bytes / nt) + 4095) & ~(size_t)4095;
+    for (unsigned i = 0; i < nt; ++i) {
+        const size_t a = (size_t)i * per;
+        if (a >= bytes) break;
+        th.emplace_back(piece, a, std::min(a + per, bytes));
+    }
+    for (auto& t : th) t.join();
+}
+// The copy-out counterpart: `c` segments of n 8-byte elements, packed in src, to dst + j * stride.
+void unstage_planes(void* dst, const void* src, int c, long n, long stride) {
+    for (int j = 0; j < c; ++j)
+        parallel_copy((char*)dst + (size_t)j * stride * 8, (const char*)src + (size_t)j * n * 8, (size_t)n * 8);
+}
+
 template <typename T>
 int ensure_pinned(T*& p, size_t& have, size_t want) {
     if (p && have >= want) return SKNNR_OK;
@@ -2226,6 +2263,8 @@ struct HostPipe {
         double* od = nullptr;
         long* oi = nullptr;
         double* op = nullptr;
+        bool planes = false;   // the tile was pushed band-first: its results leave as planes, out_stride elements apart
+        long out_stride = 0;
         std::future<int> out_done;  // copy-out job of the slot's tile (w_out)
     } pending[kHostSlots];
     int slot_of = 0;
@@ -2291,7 +2330,7 @@ int pipe_drain(HostPipe& p, int b) {
 }
 
 // Drain slot b and size its pinned / device buffers for a tile of n rows.
-int pipe_prepare_slot(HostPipe& p, int b, long n) {
+int pipe_prepare_slot(HostPipe& p, int b, long n, bool planes = false) {
     sknnr_index* ix = p.ix;
     auto& sl = ix->slot[b];
     int rc = pipe_drain(p, b);  // the slot's previous tile must have left before its buffers are reused
@@ -2307,6 +2346,12 @@ int pipe_prepare_slot(HostPipe& p, int b, long n) {
     HIP_TRY(sl.dev_d.ensure((size_t)n * k));
     if (p.want_pred) HIP_TRY(sl.dev_p.ensure((size_t)n * t));
     if (p.nodata_dev && (rc = mask_ensure(sl.mask, n, (size_t)d_x * p.x_esz, k, t, p.want_dist, p.want_pred))) return rc;
+    if (planes) {  // (band-first tiles only: the uploaded planes, and the results as planes)
+        HIP_TRY(sl.dev_xp.ensure(x_f64));
+        HIP_TRY(sl.dev_ip.ensure((size_t)n * k));
+        if (p.want_dist) HIP_TRY(sl.dev_dp.ensure((size_t)n * k));
+        if (p.want_pred) HIP_TRY(sl.dev_pp.ensure((size_t)n * t));
+    }
     return SKNNR_OK;
 }
 
@@ -2331,9 +2376,11 @@ int pipe_enqueue_d2h(HostPipe& p) {
     static const bool one_stream = [] { const char* e = std::getenv("SKNNR_PIPE_ONE_STREAM"); return !(e && std::atoi(e) == 0); }();
     hipStream_t st = one_stream ? ix->st_h2d : ix->st_d2h;
     HIP_TRY(hipStreamWaitEvent(st, sl.ev_done, 0));
-    if (oi) HIP_TRY(hipMemcpyAsync(sl.pin_i, sl.dev_i.p, (size_t)n * k * sizeof(long), hipMemcpyDeviceToHost, st));
-    if (od) HIP_TRY(hipMemcpyAsync(sl.pin_d, sl.dev_d.p, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (op) HIP_TRY(hipMemcpyAsync(sl.pin_p, sl.dev_p.p, (size_t)n * t * sizeof(double), hipMemcpyDeviceToHost, st));
+    const bool planes = pd.planes;  // (then the plane buffers hold the results, packed (k or t, n))
+    const long out_stride = pd.out_stride;
+    if (oi) HIP_TRY(hipMemcpyAsync(sl.pin_i, planes ? sl.dev_ip.p : sl.dev_i.p, (size_t)n * k * sizeof(long), hipMemcpyDeviceToHost, st));
+    if (od) HIP_TRY(hipMemcpyAsync(sl.pin_d, planes ? sl.dev_dp.p : sl.dev_d.p, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (op) HIP_TRY(hipMemcpyAsync(sl.pin_p, planes ? sl.dev_pp.p : sl.dev_p.p, (size_t)n * t * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(sl.ev_d2h, st));
     // the copy-out leg: wait for the tile's device-to-host copies, then pinned -> the caller's arrays (w_out, in order)
     static const bool workers = [] { const char* e = std::getenv("SKNNR_PIPE_WORKERS"); return !(e && std::atoi(e) == 0); }();
@@ -2344,6 +2391,12 @@ int pipe_enqueue_d2h(HostPipe& p) {
         const double *pin_d = sl.pin_d, *pin_p = sl.pin_p;
         auto job = [=]() -> int {
             if (hipSetDevice(device) != hipSuccess || hipEventSynchronize(ev) != hipSuccess) return SKNNR_ERR_HIP;
+            if (planes) {  // k (or t) contiguous segments of n elements, each to its plane of the caller's array
+                if (oi) unstage_planes(oi, pin_i, k, n, out_stride);
+                if (od) unstage_planes(od, pin_d, k, n, out_stride);
+                if (op) unstage_planes(op, pin_p, t, n, out_stride);
+                return SKNNR_OK;
+            }
             if (oi) parallel_copy(oi, pin_i, (size_t)n * k * sizeof(long));
             if (od) parallel_copy(od, pin_d, (size_t)n * k * sizeof(double));
             if (op) parallel_copy(op, pin_p, (size_t)n * t * sizeof(double));
@@ -2363,8 +2416,11 @@ int pipe_enqueue_d2h(HostPipe& p) {
 // One tile of at most host_chunk_rows() rows.  `q` may be reused by the caller as soon as this returns.
 // q_next / n_next: the tile the same call will submit next (or null): its rows are staged into the next slot's pinned
 // buffer by the copy-in worker while this tile is enqueued and the caller waits for older results.
+// planes (or null): the tile is band-first -- elements [p_off, p_off + n) of each of the d_x planes; q / q_next are then
+// the first band's segments (they name the tile for the look-ahead), and od / oi / op the first output plane's, with
+// out_stride elements between planes.  `planes` must stay valid until the next tile is submitted or the pipeline flushed.
 int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double* op, const void* q_next = nullptr,
-                long n_next = 0) {
+                long n_next = 0, const void* const* planes = nullptr, long p_off = 0, long out_stride = 0) {
     sknnr_index* ix = p.ix;
     const int b = p.slot_of;
     p.slot_of = (p.slot_of + 1) % kHostSlots;
@@ -2377,12 +2433,17 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
         p.ahead_slot = -1;
         if (rc) return rc;
     } else {
-        if ((rc = pipe_prepare_slot(p, b, n))) return rc;
-        parallel_copy(sl.pin_x, q, (size_t)n * d_x * p.x_esz);
+        if ((rc = pipe_prepare_slot(p, b, n, planes != nullptr))) return rc;
+        if (planes) stage_planes(sl.pin_x, planes, d_x, p.x_esz, p_off, n);
+        else parallel_copy(sl.pin_x, q, (size_t)n * d_x * p.x_esz);
     }
     const double t_enq = now_ms();
     p.ms_copy_in += t_enq - t_in;
-    HIP_TRY(hipMemcpyAsync(sl.dev_x.p, sl.pin_x, (size_t)n * d_x * p.x_esz, hipMemcpyHostToDevice, ix->st_h2d));
+    HIP_TRY(hipMemcpyAsync(planes ? sl.dev_xp.p : sl.dev_x.p, sl.pin_x, (size_t)n * d_x * p.x_esz, hipMemcpyHostToDevice, ix->st_h2d));
+    if (planes) {  // behind the copy, in front of the mask: dev_x as an uploaded row tile would have filled it
+        PlanesArgs pa{sl.dev_xp.p, sl.dev_x.p, n, d_x, n};
+        HIP_TRY(launch::planes_to_rows(pa, (int)p.x_esz, ix->st_h2d));
+    }
     long nv = n;  // rows the tile adds to the row offset
     if (p.nodata_dev) {
         // Mask (and, when some rows but not all are masked, compaction) on the copy stream behind the tile's rows: the host
@@ -2412,6 +2473,29 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
             if (rc) return rc;
         }
     }
+    int planes_out = 0;
+    if (planes) {  // the requested results as planes, behind everything that produces them
+        if (oi) {
+            PlanesArgs pa{sl.dev_i.p, sl.dev_ip.p, n, k, n};
+            HIP_TRY(launch::rows_to_planes(pa, ix->st_run));
+            planes_out += k;
+        }
+        if (od) {
+            PlanesArgs pa{sl.dev_d.p, sl.dev_dp.p, n, k, n};
+            HIP_TRY(launch::rows_to_planes(pa, ix->st_run));
+            planes_out += k;
+        }
+        if (op) {
+            PlanesArgs pa{sl.dev_p.p, sl.dev_pp.p, n, p.t, n};
+            HIP_TRY(launch::rows_to_planes(pa, ix->st_run));
+            planes_out += p.t;
+        }
+    }
+    {
+        const int64_t rec[8] = {planes ? 1 : 0, n, d_x, (int64_t)p.x_esz, planes ? 1 : 0, planes_out,
+                                planes ? planes_chunk_cols((int)p.x_esz) : 0, 0};
+        std::copy(std::begin(rec), std::end(rec), ix->last_planes);
+    }
     HIP_TRY(hipEventRecord(sl.ev_done, ix->st_run));
     auto& pd = p.pending[b];
     pd.live = true;
@@ -2419,6 +2503,8 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
     pd.od = od;
     pd.oi = oi;
     pd.op = op;
+    pd.planes = planes != nullptr;
+    pd.out_stride = out_stride;
     p.d2h_slot = b;  // its device-to-host copies are enqueued behind the next tile's rows, or by the flush
     p.o.row_offset += nv;
     p.ms_enqueue += now_ms() - t_enq;
@@ -2426,11 +2512,12 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
     if (workers && q_next && n_next > 0) {
         // the copy-in leg of the next tile (w_in): its slot is drained and sized here, on this thread
         const int b2 = p.slot_of;
-        if ((rc = pipe_prepare_slot(p, b2, n_next))) return rc;
+        if ((rc = pipe_prepare_slot(p, b2, n_next, planes != nullptr))) return rc;
         double* dst = ix->slot[b2].pin_x;
-        const size_t bytes = (size_t)n_next * d_x * p.x_esz;
+        const size_t bytes = (size_t)n_next * d_x * p.x_esz, esz = p.x_esz;
         p.ahead_done = ix->w_in->post([=]() -> int {
-            parallel_copy(dst, q_next, bytes);
+            if (planes) stage_planes(dst, planes, d_x, esz, p_off + n, n_next);
+            else parallel_copy(dst, q_next, bytes);
             return SKNNR_OK;
         });
         p.ahead_q = q_next;
@@ -2442,9 +2529,14 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
 // Submit `nq` rows in tiles of at most host_chunk_rows().  A pipeline that starts empty ramps up: the device waits for
 // the first tile's staging copy and host-to-device transfer (7 ms for a 1M-row tile) with nothing to do, so the first
 // tiles are an eighth, a quarter and a half of the regular size.
-int pipe_submit_rows(HostPipe& p, const void* q_, long nq, double* od, long* oi, double* op) {
-    const char* q = (const char*)q_;
-    const size_t row_bytes = (size_t)p.d_x * p.x_esz;
+// planes (or null): a band-first push -- q_ is ignored, a tile [c0, c1) is that segment of every band, and its results go
+// to od / oi / op + j * out_stride + c0 for output plane j.
+int pipe_submit_rows(HostPipe& p, const void* q_, long nq, double* od, long* oi, double* op,
+                     const void* const* planes = nullptr, long out_stride = 0) {
+    const char* q = planes ? (const char*)planes[0] : (const char*)q_;
+    // (bytes between the tiles of q: a band-first tile is named by the first band's segment)
+    const size_t row_bytes = planes ? p.x_esz : (size_t)p.d_x * p.x_esz;
+    const long ok = planes ? 1 : p.k, ot = planes ? 1 : p.t;  // output elements per row between tiles
     const long cap = host_chunk_rows();
     bool idle = p.d2h_slot < 0;
     for (const auto& pd : p.pending) idle = idle && !pd.live;
@@ -2465,8 +2557,9 @@ int pipe_submit_rows(HostPipe& p, const void* q_, long nq, double* od, long* oi,
     for (size_t i = 0; i < cuts.size(); ++i) {
         const long c1 = cuts[i], n = c1 - c0;
         const long n_next = i + 1 < cuts.size() ? cuts[i + 1] - c1 : 0;
-        int rc = pipe_submit(p, q + c0 * row_bytes, n, od ? od + c0 * p.k : nullptr, oi ? oi + c0 * p.k : nullptr,
-                             op ? op + c0 * p.t : nullptr, n_next ? q + c1 * row_bytes : nullptr, n_next);
+        int rc = pipe_submit(p, q + c0 * row_bytes, n, od ? od + c0 * ok : nullptr, oi ? oi + c0 * ok : nullptr,
+                             op ? op + c0 * ot : nullptr, n_next ? q + c1 * row_bytes : nullptr, n_next, planes, c0,
+                             out_stride);
         if (rc) return rc;
         c0 = c1;
     }
@@ -2708,6 +2801,41 @@ extern "C" int sknnr_mask_rows(const void* q, int64_t nq, int32_t d_in, int32_t 
     HIP_TRY(hipMemcpy(&n_valid, nv.p, sizeof n_valid, hipMemcpyDeviceToHost));
     if (mem == SKNNR_MEM_HOST) HIP_TRY(hipMemcpy(out_valid, dvalid.p, (size_t)nq, hipMemcpyDeviceToHost));
     if (out_n_valid) *out_n_valid = n_valid;
+    return SKNNR_OK;
+}
+
+// ----------------------------------------------------------------------------------------
+// band-first tiles: the two transpositions alone, on device pointers
+// ----------------------------------------------------------------------------------------
+static int validate_planes(const void* src, int64_t n, int32_t c, int32_t elem_bytes, int64_t stride, const void* dst) {
+    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8)
+        return fail(SKNNR_ERR_INVALID, "elem_bytes = %d: must be 1, 2, 4 or 8", elem_bytes);
+    if (n < 0) return fail(SKNNR_ERR_INVALID, "n must be >= 0");
+    if (c < 1 || c > kMaskMaxCols) return fail(SKNNR_ERR_INVALID, "c = %d outside [1, %d]", c, kMaskMaxCols);
+    if (stride < n) return fail(SKNNR_ERR_INVALID, "the stride between planes (%lld) is below n (%lld)", (long long)stride, (long long)n);
+    if (n == 0) return SKNNR_OK;
+    if (!src || !dst) return fail(SKNNR_ERR_INVALID, "src / dst is NULL");
+    if (n > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 pixels in one call");
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_planes_to_rows(const void* src, int64_t n, int32_t c, int32_t elem_bytes, int64_t src_stride, void* dst,
+                                    int32_t device, void* stream) {
+    int rc = validate_planes(src, n, c, elem_bytes, src_stride, dst);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(device));
+    PlanesArgs a{src, dst, n, c, src_stride};
+    HIP_TRY(launch::planes_to_rows(a, elem_bytes, (hipStream_t)stream));
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_rows_to_planes(const void* src, int64_t n, int32_t c, void* dst, int64_t dst_stride, int32_t device,
+                                    void* stream) {
+    int rc = validate_planes(src, n, c, 8, dst_stride, dst);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(device));
+    PlanesArgs a{src, dst, n, c, dst_stride};
+    HIP_TRY(launch::rows_to_planes(a, (hipStream_t)stream));
     return SKNNR_OK;
 }
 
@@ -3192,6 +3320,35 @@ extern "C" int sknnr_stream_push(sknnr_stream* s, const void* q, int64_t nq, dou
     return SKNNR_OK;
 }
 
+extern "C" int sknnr_stream_push_planes(sknnr_stream* s, const void* const* planes, int64_t nq, double* out_dist,
+                                        int64_t* out_idx, double* out_pred, int64_t out_stride) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
+    if (nq == 0) return SKNNR_OK;
+    if (!planes) return fail(SKNNR_ERR_INVALID, "planes is NULL");
+    HostPipe& p = s->pipe;
+    for (int j = 0; j < p.d_x; ++j)
+        if (!planes[j]) return fail(SKNNR_ERR_INVALID, "planes[%d] is NULL", j);
+    if (!out_idx && !out_pred) return fail(SKNNR_ERR_INVALID, "a push needs out_idx or out_pred");
+    if (out_dist && !p.want_dist) return fail(SKNNR_ERR_INVALID, "the stream was opened without distances");
+    if (out_pred && !p.want_pred) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
+    if (out_stride < nq) return fail(SKNNR_ERR_INVALID, "out_stride (%lld) is below nq (%lld)", (long long)out_stride, (long long)nq);
+    if (p.d_x > kMaskMaxCols) return fail(SKNNR_ERR_UNSUPPORTED, "more than %d input columns in a band-first push", kMaskMaxCols);
+    std::lock_guard<std::mutex> lock(p.ix->mtx);
+    HIP_TRY(hipSetDevice(p.ix->device));
+    s->pushed = true;
+    int rc = pipe_submit_rows(p, nullptr, nq, out_dist, (long*)out_idx, out_pred, planes, out_stride);
+    if (rc) {
+        const std::string msg = g_last_error;
+        pipe_abort(p);
+        (void)hipDeviceSynchronize();
+        g_last_error = msg;
+        return rc;
+    }
+    s->rows_pushed += nq;
+    return SKNNR_OK;
+}
+
 extern "C" int sknnr_stream_flush(sknnr_stream* s) {
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     std::lock_guard<std::mutex> lock(s->pipe.ix->mtx);
@@ -3280,6 +3437,14 @@ extern "C" int sknnr_debug_last_mask(const sknnr_index* cix, int64_t out[8]) {
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
     std::copy(std::begin(ix->last_mask), std::end(ix->last_mask), out);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_planes(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "index / out is NULL");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::copy(std::begin(ix->last_planes), std::end(ix->last_planes), out);
     return SKNNR_OK;
 }
 
