@@ -436,6 +436,68 @@ int sknnr_rows_to_planes(const void* src, int64_t n, int32_t c, void* dst, int64
 int sknnr_stream_push_planes(sknnr_stream* stream, const void* const* planes, int64_t nq, double* out_dist,
                              int64_t* out_idx, double* out_pred, int64_t out_stride);
 
+/* ---- typed outputs (rasters stored as int16 / uint8 / float32 / int32) -------------------------- */
+
+/*
+ * Output rasters are stored narrow, with a scale factor and a nodata value; plot-id rasters are int32.  The entry points
+ * below convert a result tile to that type ON THE DEVICE (sknnr_amd/csrc/narrow.hip.h), so that only the narrow bytes
+ * cross PCIe and are copied on the host.  The conversions, exactly (tests/_narrow.py restates them in numpy):
+ *   values (float64) -> SKNNR_DTYPE_F32: x = v, or x = v * scale[j] + offset[j] for column j, as two float64 roundings
+ *     (never a fused multiply-add); NaN gives (float)fill when a fill is set; else the C cast, round to nearest even:
+ *     overflow gives +-inf, NaN stays NaN, and without scale / offset -0.0 keeps its sign.
+ *   values -> SKNNR_DTYPE_I16 / U16 / U8 / I32: x as above; NaN is tested FIRST and gives fill (0 when no fill is set:
+ *     set one wherever NaN can occur); otherwise rint(x), half to even, then the clamp to the type's [min, max] -- so
+ *     +-inf clamp -- then the cast.  The clamp does NOT avoid the fill value: a valid pixel may come to equal it.
+ *   indices (int64) -> SKNNR_DTYPE_I32: plain narrowing; the caller guarantees that every index (and fill_index) fits.
+ *
+ * sknnr_narrow: no handle.  src: DEVICE memory, a packed (n, c) tile of float64 (kind SKNNR_NARROW_VALUE) or int64
+ *   (SKNNR_NARROW_INDEX).  dst: DEVICE memory of dst_dtype elements, at any element-aligned address: packed (n, c) rows
+ *   when dst_stride == 0, else c planes of n elements, plane j starting j * dst_stride ELEMENTS after dst (dst_stride
+ *   >= n) -- transposed and converted in one pass.  scale / offset: DEVICE arrays of c float64 each, or both NULL.
+ *   has_fill / fill: the value NaN becomes; it must be representable in dst_dtype.  Enqueues on `stream` and returns;
+ *   *out_wide (optional) = 1 when the launch converted 4 destination elements per lane -- chosen from the addresses, the
+ *   stride and the count -- 0 for one element per lane.  c in [1, 65536], n below 2^31.  SKNNR_ERR_INVALID, before any
+ *   device call, for an unknown or impossible (kind, dst_dtype) pair, n < 0, c out of range, a non-zero stride below n,
+ *   scale without offset (or either, or a fill, with indices), a fill that dst_dtype cannot hold, and NULL src / dst;
+ *   n == 0 is SKNNR_OK.
+ * sknnr_stream_set_output: the element types in which a stream's results leave the device.  0 (SKNNR_DTYPE_F64) means
+ *   "as ever" for that output (int64 indices, float64 distances and predictions); idx_dtype accepts 0 or I32,
+ *   dist_dtype 0 or F32, pred_dtype 0 or F32 / I16 / U16 / U8 / I32.  pred_scale / pred_offset: HOST arrays of t float64
+ *   each (both or neither), uploaded once; has_pred_fill / pred_fill: what a NaN prediction (a nodata row) becomes.
+ *   Allowed only before the first push.  A stream on which it was never called enqueues exactly what it did before the
+ *   entry point existed.
+ * sknnr_stream_push_typed / sknnr_stream_push_planes_typed: sknnr_stream_push / sknnr_stream_push_planes with the
+ *   outputs as void*: HOST arrays of the types set by sknnr_stream_set_output ((nq, k) / (nq, t), or planes out_stride
+ *   ELEMENTS of the output's own type apart).  On a stream without typed outputs they are the plain pushes; the plain
+ *   pushes, whose signatures promise int64 / float64, return SKNNR_ERR_INVALID on a stream with typed outputs.  The
+ *   conversion runs behind the search, the reduction, the nodata expansion (so fill_index is already in the tile) and in
+ *   the transposition's place; device-to-host copies, pinned buffers and the host copy move nq * cols * sizeof(type).
+ */
+#define SKNNR_NARROW_VALUE 0
+#define SKNNR_NARROW_INDEX 1
+int sknnr_narrow(const void* src, int32_t kind, int64_t n, int32_t c, void* dst, int32_t dst_dtype, int64_t dst_stride,
+                 const double* scale, const double* offset, int32_t has_fill, double fill, int32_t device, void* stream,
+                 int32_t* out_wide);
+int sknnr_stream_set_output(sknnr_stream* stream, int32_t idx_dtype, int32_t dist_dtype, int32_t pred_dtype,
+                            const double* pred_scale, const double* pred_offset, int32_t has_pred_fill,
+                            double pred_fill);
+int sknnr_stream_push_typed(sknnr_stream* stream, const void* q, int64_t nq, void* out_dist, void* out_idx,
+                            void* out_pred);
+int sknnr_stream_push_planes_typed(sknnr_stream* stream, const void* const* planes, int64_t nq, void* out_dist,
+                                   void* out_idx, void* out_pred, int64_t out_stride);
+
+/*
+ * Debug only.  The output side of the last tile the handle's host pipeline submitted, so that a test can prove that the
+ * device converted it and that only the narrow bytes were copied.  Host memory, no device work:
+ *   out[0] 1 = a conversion kernel ran for the tile, 0 = none did (no typed output)
+ *   out[1] rows of the tile
+ *   out[2] / out[3] / out[4] sknnr_dtype of the indices / distances / predictions (0 = int64 / float64)
+ *   out[5] bytes the tile's device-to-host copies moved (0 until they are enqueued: behind the next tile, or by a flush)
+ *   out[6] outputs whose conversion took the 4-elements-per-lane path: bit 0 indices, bit 1 distances, bit 2 predictions
+ *   out[7] 0
+ */
+int sknnr_debug_last_narrow(const sknnr_index* index, int64_t out[8]);
+
 /*
  * Debug only.  The last tile the handle's host pipeline submitted (host-memory calls and streams), so that a test can
  * prove that the device transposed it, not the host.  Host memory, no device work:

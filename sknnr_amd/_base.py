@@ -88,6 +88,67 @@ def normalize_nodata(nodata, n_features, dtype):
 _LAYOUTS = ("rows", "bands")
 
 
+# typed outputs of the streamed calls: what the device narrows to (include/sknnr_hip.h, "typed outputs")
+_OUT_VALUE_DTYPES = tuple(np.dtype(t) for t in (np.float32, np.int16, np.uint16, np.uint8, np.int32))
+
+
+def _narrow_dtype(dt, wide, allowed, name):
+    """``dt`` as a numpy dtype the device narrows ``wide`` results to; None for None or ``wide`` itself (as ever)."""
+    if dt is None:
+        return None
+    try:
+        dt = np.dtype(dt)
+    except TypeError:
+        raise ValueError(f"{name}={dt!r} is not a numpy dtype") from None
+    if dt == np.dtype(wide):
+        return None
+    if dt not in allowed:
+        raise ValueError(f"{name}={dt} is not supported: use {', '.join(str(a) for a in allowed)} or {np.dtype(wide)}")
+    return dt
+
+
+def _representable(value, dt) -> bool:
+    """Can ``value`` be stored in ``dt`` exactly (NaN: in a float type)?"""
+    dt = np.dtype(dt)
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        return False
+    if dt.kind == "f":
+        return bool(np.isnan(value) or float(dt.type(value)) == value) if np.isfinite(value) or np.isnan(value) else True
+    info = np.iinfo(dt)
+    return bool(np.isfinite(value) and value == np.rint(value) and info.min <= value <= info.max)
+
+
+def normalize_typed_output(out_dtype, scale, offset, out_nodata, n_targets, masked):
+    """The ``output`` arguments of a typed prediction stream (:meth:`sknnr_amd._native.QueryStream.set_output`), or None
+    when the predictions leave as ever.  ``masked``: the call has a ``nodata`` mask, so NaN predictions occur."""
+    dt = _narrow_dtype(out_dtype, np.float64, _OUT_VALUE_DTYPES, "out_dtype")
+    if dt is None:
+        for name, v in (("scale", scale), ("offset", offset), ("out_nodata", out_nodata)):
+            if v is not None:
+                raise ValueError(f"{name} needs out_dtype: float64 predictions leave as they are computed")
+        return None
+    if scale is not None or offset is not None:
+        def per_target(v, default, name):
+            v = np.full(n_targets, default, dtype=np.float64) if v is None else np.asarray(v, dtype=np.float64).reshape(-1)
+            if v.size == 1:
+                v = np.full(n_targets, v[0], dtype=np.float64)
+            if v.size != n_targets:
+                raise ValueError(f"{name} must be a scalar or hold one value per target ({n_targets}), got {v.size}")
+            return np.ascontiguousarray(v)
+        scale, offset = per_target(scale, 1.0, "scale"), per_target(offset, 0.0, "offset")
+    if out_nodata is None:
+        if dt.kind != "f" and masked:
+            raise ValueError(f"out_nodata is required with nodata and out_dtype={dt}: an integer type has no NaN for "
+                             "the masked rows")
+    elif not _representable(out_nodata, dt):
+        raise ValueError(f"out_nodata={out_nodata!r} is not representable in out_dtype={dt}")
+    elif dt.kind == "f" and np.isnan(float(out_nodata)):
+        out_nodata = None  # (NaN stays NaN)
+    return dict(pred_dtype=dt, scale=scale, offset=offset, fill=None if out_nodata is None else float(out_nodata))
+
+
 def _check_layout(layout):
     if layout not in _LAYOUTS:
         raise ValueError(f"layout must be 'rows' or 'bands', got {layout!r}")
@@ -621,18 +682,38 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             raise NotImplementedError("layout='bands' is not supported under tree_tie_policy('tree'): tied rows are "
                                       "chosen on the host, tile by tile; use the default policy 'lowest_index'")
 
+    def _check_typed_supported(self, output):
+        """Typed outputs are converted on the device, inside a native stream; the paths that answer tile by tile on the
+        host refuse them."""
+        if not output:
+            return
+        if self._numpy_ties():
+            raise NotImplementedError("typed outputs are not supported under hamming_tie_policy('numpy'): tied rows are "
+                                      "chosen on the host, tile by tile; use the default policy 'lowest_index'")
+        if self._tree_ties():
+            raise NotImplementedError("typed outputs are not supported under tree_tie_policy('tree'): tied rows are "
+                                      "chosen on the host, tile by tile; use the default policy 'lowest_index'")
+
     def _stream_tiles(self, tiles, validate, k, *, apply_affine, weights, return_distance,
-                      use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False):
+                      use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False, output=None):
         """Push host tiles through one native query stream.  Returns (dist, idx, pred) arrays over all
         pushed rows (pieces of ``out`` when given, else concatenated).  ``nodata`` (float64, one value per column of the
         validated tiles): rows holding one are masked on the device and get ``fill_index`` / NaN.
 
         ``bands``: the tiles are band-first -- ``validate`` gives ``(bands, n)`` (:func:`normalize_band_tile`), the outputs
         are ``(k, N)`` / ``(t, N)``, pixels along axis 1, and tile ``i`` lands in columns ``[row, row + n_i)``; the
-        ``out`` arrays must then share one ``N``, the stride between their planes."""
+        ``out`` arrays must then share one ``N``, the stride between their planes.
+
+        ``output``: keyword arguments of :meth:`sknnr_amd._native.QueryStream.set_output` -- the results are narrowed on
+        the device and the arrays (``out`` included) have those element types."""
+        self._check_typed_supported(output)
         eng = self.engine_
         want_pred = weights is not None
         t_cols = eng.t
+        output = {key: v for key, v in (output or {}).items() if v is not None}
+        idx_dt = np.dtype(output.get("index_dtype", np.int64))
+        dist_dt = np.dtype(output.get("distance_dtype", np.float64))
+        pred_dt = np.dtype(output.get("pred_dtype", np.float64))
         self._check_nodata_supported(nodata)
         if bands:
             self._check_bands_supported()
@@ -692,7 +773,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              deterministic=use_deterministic_ordering,
                                              decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula(),
                                              apply_affine=apply_affine, check_finite=True, query_dtype=code,
-                                             nodata=nodata, fill_index=fill_index)
+                                             nodata=nodata, fill_index=fill_index, output=output)
                 if first.dtype != stream_dtype:
                     if stream_dtype != np.float64:
                         raise ValueError(f"the tiles of one streamed call must share an element type: got {first.dtype} "
@@ -716,9 +797,9 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                     return w
 
                 got = (stream.push_planes if bands else stream.push)(
-                    tile, out_idx=window(o_idx, k, np.int64),
-                    out_dist=window(o_dist, k, np.float64) if return_distance else None,
-                    out_pred=window(o_pred, t_cols, np.float64) if want_pred else None, need_idx=not want_pred)
+                    tile, out_idx=window(o_idx, k, idx_dt),
+                    out_dist=window(o_dist, k, dist_dt) if return_distance else None,
+                    out_pred=window(o_pred, t_cols, pred_dt) if want_pred else None, need_idx=not want_pred)
                 if out is None:
                     pieces.append(got)
                 row += n
@@ -738,12 +819,33 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             return trim(o_dist) if return_distance else None, trim(o_idx), trim(o_pred) if want_pred else None
         cat = lambda i, cols, dt: (np.concatenate([p[i] for p in pieces], axis=1 if bands else 0) if pieces  # noqa: E731
                                    else np.empty((cols, 0) if bands else (0, cols), dtype=dt))
-        return (cat(1, k, np.float64) if return_distance else None,
-                None if want_pred else cat(0, k, np.int64),
-                cat(2, t_cols, np.float64) if want_pred else None)
+        return (cat(1, k, dist_dt) if return_distance else None,
+                None if want_pred else cat(0, k, idx_dt),
+                cat(2, t_cols, pred_dt) if want_pred else None)
+
+    def _neighbor_output(self, index_dtype, distance_dtype, return_distance, return_dataframe_index, fill_index, masked):
+        """The ``output`` arguments of a typed neighbour stream, or None; every refusal comes before any device work."""
+        idt = _narrow_dtype(index_dtype, np.int64, (np.dtype(np.int32),), "index_dtype")
+        ddt = _narrow_dtype(distance_dtype, np.float64, (np.dtype(np.float32),), "distance_dtype")
+        if not return_distance:
+            ddt = None
+        if idt is not None:
+            if masked and not _representable(fill_index, idt):
+                raise ValueError(f"fill_index={fill_index!r} is not representable in index_dtype={idt}")
+            if return_dataframe_index:
+                msg = "Dataframe indexes can only be returned when fitted with a dataframe."
+                check_is_fitted(self, "dataframe_index_in_", msg=msg)
+                table = np.asarray(self.dataframe_index_in_)
+                info = np.iinfo(idt)
+                if table.dtype.kind not in "iu" or (table.size and (table.min() < info.min or table.max() > info.max)):
+                    raise ValueError(f"index_dtype={idt} with return_dataframe_index=True needs integer dataframe ids "
+                                     f"inside [{info.min}, {info.max}]")
+        out = dict(index_dtype=idt, distance_dtype=ddt)
+        return out if idt is not None or ddt is not None else None
 
     def kneighbors_chunks(self, tiles, n_neighbors=None, return_distance=True, return_dataframe_index=False,
-                          use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1, layout="rows"):
+                          use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1, layout="rows",
+                          index_dtype=None, distance_dtype=None):
         """``kneighbors`` over an iterable of host tiles ``(n_i, n_features)`` -- windows of a raster,
         slices of a ``numpy.memmap`` -- as ONE logical call: the copy-in / kernels / copy-out pipeline
         stays full across tiles and row positions count over all tiles, so the result equals
@@ -758,12 +860,19 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         ``layout="bands"``: every tile is band-first, as raster readers deliver a window -- an array ``(bands, ...)`` of
         any trailing shape, or a sequence of ``bands`` arrays -- and the results are band-first too: ``(k, N)`` arrays
         (``out``: C-contiguous ``(k, N_total)``), concatenated along the pixel axis.  Both transpositions run on the
-        device; ``[j, p]`` equals ``[p, j]`` of the row call on the transposed tiles, bit for bit."""
+        device; ``[j, p]`` equals ``[p, j]`` of the row call on the transposed tiles, bit for bit.
+
+        ``index_dtype=np.int32`` / ``distance_dtype=np.float32``: the results are narrowed on the device (plain
+        narrowing; the C cast, round to nearest even) and only the narrow bytes cross PCIe; ``out`` arrays then have those
+        types.  ``fill_index`` and, with ``return_dataframe_index``, every dataframe id must fit int32; the id crosswalk
+        runs on the host, in place, at int32."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         k = self._resolve_k(n_neighbors)
         if nodata is not None:
             nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
+        output = self._neighbor_output(index_dtype, distance_dtype, return_distance, return_dataframe_index, fill_index,
+                                       nodata is not None)
         o = None if out is None else (out[0], out[1], None)
         validate = self._validate_query
         if bands:
@@ -773,7 +882,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                           return_distance=return_distance,
                                           use_deterministic_ordering=use_deterministic_ordering, out=o, owner=None,
                                           nodata=nodata, fill_index=-1 if return_dataframe_index else fill_index,
-                                          bands=bands)
+                                          bands=bands, output=output)
         return self._finish_chunks(dist, idx, return_distance, return_dataframe_index,
                                    fill_index=None if nodata is None else fill_index)
 
@@ -784,7 +893,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             check_is_fitted(self, "dataframe_index_in_", msg=msg)
             table = self.dataframe_index_in_
             if fill_index is not None:
-                if table.dtype == np.int64:
+                if table.dtype == np.int64 or idx.dtype == np.int32:  # (int32: the ids were checked to fit)
                     step = 1 << 22
                     for a in range(0, idx.shape[0], step):
                         blk = idx[a:a + step]
@@ -794,7 +903,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                     masked = idx < 0
                     idx = table[np.where(masked, 0, idx)]
                     idx[masked] = fill_index
-            elif table.dtype == np.int64:
+            elif table.dtype == np.int64 or idx.dtype == np.int32:
                 step = 1 << 22  # in place, block by block: idx may be a memmap larger than memory
                 for a in range(0, idx.shape[0], step):
                     idx[a:a + step] = table[idx[a:a + step]]
@@ -802,12 +911,20 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 idx = table[idx]
         return (dist, idx) if return_distance else idx
 
-    def predict_chunks(self, tiles, out=None, nodata=None, layout="rows"):
+    def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
+                       out_nodata=None):
         """``predict`` over an iterable of host tiles as one streamed call; ``out``: preallocated
         ``(n_rows, n_targets)`` float64 array (e.g. a memmap; float32 results are held exactly).  ``nodata`` as in
         :meth:`kneighbors_chunks`: masked rows are predicted NaN.  ``layout="bands"``: band-first tiles as in
         :meth:`kneighbors_chunks`, and ``(n_targets, N)`` predictions (``out``: C-contiguous ``(n_targets, N_total)``, e.g.
-        ``raster.reshape(t, H * W)`` of a memmapped output raster); ``(N,)`` for a 1-D ``y`` as ever."""
+        ``raster.reshape(t, H * W)`` of a memmapped output raster); ``(N,)`` for a 1-D ``y`` as ever.
+
+        ``out_dtype`` (float32, int16, uint16, uint8 or int32): the type the raster is stored in.  The device converts
+        the predictions and only the narrow bytes cross PCIe; ``out`` must have that dtype.  ``scale`` / ``offset``
+        (scalars or one value per target): the stored value is ``rint(pred * scale + offset)`` -- two float64 roundings,
+        half to even -- clamped to the type's range (float32: ``pred * scale + offset`` rounded to float32, no ``rint``).
+        Masked rows get ``out_nodata``, which must be representable in ``out_dtype``, is required for an integer type
+        with ``nodata`` and defaults to NaN for float32.  The clamp does not avoid the nodata value."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         if nodata is not None:
@@ -815,10 +932,18 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         validate = self._validate_query
         if bands:
             validate = lambda t: normalize_band_tile(t, self.n_features_in_, estimator=type(self).__name__)  # noqa: E731
-        return self._predict_chunks(tiles, validate, apply_affine=False, out=out, owner=None, nodata=nodata, bands=bands)
+        return self._predict_chunks(tiles, validate, apply_affine=False, out=out, owner=None, nodata=nodata, bands=bands,
+                                    typed=(out_dtype, scale, offset, out_nodata))
 
-    def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None, bands=False):
+    def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None, bands=False, typed=None):
         weights = "uniform" if self.weights is None else self.weights
+        output = None
+        if typed is not None:
+            n_targets = 1 if self._y.ndim == 1 else self._y.shape[1]
+            output = normalize_typed_output(*typed, n_targets, nodata is not None)
+        if callable(weights) and output:
+            raise NotImplementedError("typed outputs are not supported with callable weights: the callable runs on the "
+                                      "host between the search and the reduction, tile by tile; use 'uniform' or 'distance'")
         if callable(weights) and bands:
             raise NotImplementedError("layout='bands' is not supported with callable weights: the callable runs on the "
                                       "host between the search and the reduction, on row-major neighbours; use "
@@ -844,8 +969,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             _, _, pred = self._stream_tiles(tiles, validate, self.n_neighbors, apply_affine=apply_affine,
                                             weights=weights, return_distance=False,
                                             use_deterministic_ordering=True, out=o, owner=owner, nodata=nodata,
-                                            bands=bands)
-            if out is None:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
+                                            bands=bands, output=output)
+            if out is None and not output:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
                 pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         return pred.reshape(-1) if self._y.ndim == 1 else pred
 
@@ -1031,34 +1156,41 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         return lambda t: normalize_band_tile(t, d_in, forest=forest, estimator=name)
 
     def kneighbors_chunks(self, tiles, n_neighbors=None, return_distance=True, return_dataframe_index=False,
-                          use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1, layout="rows"):
+                          use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1, layout="rows",
+                          index_dtype=None, distance_dtype=None):
         """``kneighbors`` over an iterable of untransformed host tiles as one streamed call (see
         :meth:`RawKNNRegressor.kneighbors_chunks`, also for ``nodata`` / ``fill_index``: the nodata values are those of
-        the untransformed columns -- and for ``layout="bands"``); each tile is transformed on the device."""
+        the untransformed columns -- for ``layout="bands"`` and for ``index_dtype`` / ``distance_dtype``); each tile is
+        transformed on the device."""
         bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
         reg = self.regressor_
         k = reg._resolve_k(n_neighbors)
         validate = self._band_validator(bands)
         nodata = self._raw_nodata(nodata)
+        output = reg._neighbor_output(index_dtype, distance_dtype, return_distance, return_dataframe_index, fill_index,
+                                      nodata is not None)
         o = None if out is None else (out[0], out[1], None)
         dist, idx, _ = reg._stream_tiles(tiles, validate, k, apply_affine=self._map_on_device(), weights=None,
                                          return_distance=return_distance,
                                          use_deterministic_ordering=use_deterministic_ordering, out=o,
                                          owner=self.transformer_, nodata=nodata,
-                                         fill_index=-1 if return_dataframe_index else fill_index, bands=bands)
+                                         fill_index=-1 if return_dataframe_index else fill_index, bands=bands,
+                                         output=output)
         return reg._finish_chunks(dist, idx, return_distance, return_dataframe_index,
                                   fill_index=None if nodata is None else fill_index)
 
-    def predict_chunks(self, tiles, out=None, nodata=None, layout="rows"):
+    def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
+                       out_nodata=None):
         """``predict`` over an iterable of untransformed host tiles as one streamed call (``nodata``: masked rows are
-        predicted NaN; ``layout="bands"``: band-first tiles and predictions; see
+        predicted NaN; ``layout="bands"``: band-first tiles and predictions; ``out_dtype`` / ``scale`` / ``offset`` /
+        ``out_nodata``: predictions converted on the device to the type the raster is stored in; see
         :meth:`RawKNNRegressor.kneighbors_chunks` / :meth:`RawKNNRegressor.predict_chunks`)."""
         bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
         return self.regressor_._predict_chunks(tiles, self._band_validator(bands), apply_affine=self._map_on_device(),
                                                out=out, owner=self.transformer_, nodata=self._raw_nodata(nodata),
-                                               bands=bands)
+                                               bands=bands, typed=(out_dtype, scale, offset, out_nodata))
 
     def score(self, X, y):
         """REF _base.py:350-352."""

@@ -380,12 +380,13 @@ class KNNEngine:
 
     def open_stream(self, k, *, weights=None, want_dist=True, deterministic=True, decimals=10,
                     formula="expanded", apply_affine=False, row_offset=0, check_finite=False, query_dtype=0,
-                    nodata=None, fill_index=-1):
+                    nodata=None, fill_index=-1, output=None):
         """A :class:`sknnr_amd._native.QueryStream` over host tiles: ``push(tile)`` keeps the PCIe
         pipeline full across tiles and carries the global row offset.  ``weights`` (``"uniform"`` /
         ``"distance"``) also asks for predictions: float64 arrays, holding binary32 values where
         :meth:`pred_dtype` is float32.  ``nodata`` (float64, one value per column of the tiles): every tile is masked on
-        the device, masked rows get ``fill_index`` / NaN and the row offset counts valid rows only."""
+        the device, masked rows get ``fill_index`` / NaN and the row offset counts valid rows only.  ``output``: keyword
+        arguments of :meth:`sknnr_amd._native.QueryStream.set_output` (typed results, narrowed on the device)."""
         want_pred = weights is not None
         if want_pred and weights not in _WEIGHT_MODES:
             raise ValueError("a stream predicts with 'uniform' or 'distance' weights only")
@@ -393,7 +394,8 @@ class KNNEngine:
                           formula=formula, apply_affine=apply_affine,
                           weight_mode=self.weight_mode(weights) if want_pred else _native.WEIGHTS_UNIFORM,
                           row_offset=row_offset, check_finite=check_finite, query_dtype=query_dtype)
-        return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred, nodata=nodata, fill_index=fill_index)
+        return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred, nodata=nodata, fill_index=fill_index,
+                                       output=output)
 
     def hamming_distances(self, X, rows=None):
         """Full weighted-Hamming distance rows of ``X[rows]`` (``X`` None: of the fitted rows) from the device."""

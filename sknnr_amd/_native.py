@@ -88,6 +88,11 @@ EXPORTED_SYMBOLS = (
     "sknnr_rows_to_planes",
     "sknnr_stream_push_planes",
     "sknnr_debug_last_planes",
+    "sknnr_narrow",
+    "sknnr_stream_set_output",
+    "sknnr_stream_push_typed",
+    "sknnr_stream_push_planes_typed",
+    "sknnr_debug_last_narrow",
     "sknnr_debug_last_mask",
     "sknnr_debug_mask_compact",
     "sknnr_debug_expand_rows",
@@ -215,6 +220,12 @@ def load(build_if_missing: bool = False):
     lib.sknnr_rows_to_planes.argtypes = [vp, c_int64, c_int32, vp, c_int64, c_int32, vp]
     lib.sknnr_stream_push_planes.argtypes = [vp, vp, c_int64, vp, vp, vp, c_int64]
     lib.sknnr_debug_last_planes.argtypes = [vp, POINTER(c_int64)]
+    lib.sknnr_narrow.argtypes = [vp, c_int32, c_int64, c_int32, vp, c_int32, c_int64, vp, vp, c_int32, c_double, c_int32, vp,
+                                 POINTER(c_int32)]
+    lib.sknnr_stream_set_output.argtypes = [vp, c_int32, c_int32, c_int32, vp, vp, c_int32, c_double]
+    lib.sknnr_stream_push_typed.argtypes = [vp, vp, c_int64, vp, vp, vp]
+    lib.sknnr_stream_push_planes_typed.argtypes = [vp, vp, c_int64, vp, vp, vp, c_int64]
+    lib.sknnr_debug_last_narrow.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_mask_compact.argtypes = [vp, c_int64, c_int32, c_int32, vp, c_int32, vp, vp, vp, vp, vp,
                                              POINTER(c_int32), POINTER(c_int64)]
     lib.sknnr_debug_expand_rows.argtypes = [c_int64, c_int32, c_int32, vp, vp, vp, vp, vp, vp, vp, vp, c_int64, vp]
@@ -375,16 +386,20 @@ class Index:
         (synchronises ``stream``); raises :class:`HipBackendError` (``ERR_NONFINITE``)."""
         check(load().sknnr_check_finite(self.handle, c_void_p(stream or None)))
 
-    def open_stream(self, opts: QueryOpts, want_dist=True, want_pred=False, nodata=None, fill_index=-1) -> "QueryStream":
+    def open_stream(self, opts: QueryOpts, want_dist=True, want_pred=False, nodata=None, fill_index=-1,
+                    output=None) -> "QueryStream":
         """``nodata``: float64 ``(d_in,)``, one value per column of the pushed rows -- every tile is then masked on the
-        device (sknnr_stream_set_nodata) and masked rows get ``fill_index`` / NaN."""
+        device (sknnr_stream_set_nodata) and masked rows get ``fill_index`` / NaN.  ``output``: keyword arguments of
+        :meth:`QueryStream.set_output` -- the results then leave the device at those types."""
         stream = QueryStream(self, opts, want_dist, want_pred)
-        if nodata is not None:
-            try:
+        try:
+            if nodata is not None:
                 stream.set_nodata(nodata, fill_index)
-            except Exception:
-                stream.close()
-                raise
+            if output:
+                stream.set_output(**output)
+        except Exception:
+            stream.close()
+            raise
         return stream
 
     # ---- host (numpy) entry points --------------------------------------------------------
@@ -480,6 +495,17 @@ class Index:
         out = (c_int64 * 8)()
         check(load().sknnr_debug_last_mask(self.handle, out))
         return dict(zip(self.MASK_FIELDS, (int(v) for v in out)))
+
+    NARROW_FIELDS = ("ran", "rows", "idx_dtype", "dist_dtype", "pred_dtype", "d2h_bytes", "wide_mask", "reserved")
+
+    def debug_last_narrow(self) -> dict:
+        """Debug only: the output side of the last tile of the host pipeline (sknnr_debug_last_narrow): whether a
+        conversion kernel ran, the tile's rows, the sknnr_dtype of indices / distances / predictions (0: int64 / float64),
+        the bytes its device-to-host copies moved, and which outputs took the 4-elements-per-lane path (bit 0 indices,
+        1 distances, 2 predictions)."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_narrow(self.handle, out))
+        return dict(zip(self.NARROW_FIELDS, (int(v) for v in out)))
 
     # ---- device-pointer entry points (ints from tensor.data_ptr()) ------------------------
     def debug_last_planes(self) -> dict:
@@ -684,6 +710,9 @@ class QueryStream:
         self.k = opts.n_neighbors
         self._opts = opts
         self.want_dist, self.want_pred = bool(want_dist), bool(want_pred)
+        # element types of the results (set_output narrows them)
+        self.idx_dtype, self.dist_dtype, self.pred_dtype = np.dtype(np.int64), np.dtype(np.float64), np.dtype(np.float64)
+        self._typed = False
         check(load().sknnr_stream_begin(index.handle, byref(opts), int(self.want_dist), int(self.want_pred),
                                         byref(self._h)))
 
@@ -693,17 +722,17 @@ class QueryStream:
         q = _c_rows(q, self._opts)
         nq = q.shape[0]
         if out_idx is None and (need_idx or not self.want_pred):
-            out_idx = np.empty((nq, self.k), dtype=np.int64)
+            out_idx = np.empty((nq, self.k), dtype=self.idx_dtype)
         if out_dist is None and self.want_dist:
-            out_dist = np.empty((nq, self.k), dtype=np.float64)
+            out_dist = np.empty((nq, self.k), dtype=self.dist_dtype)
         if out_pred is None and self.want_pred:
-            out_pred = np.empty((nq, self._index.t), dtype=np.float64)
-        for a, dt, cols in ((out_idx, np.int64, self.k), (out_dist, np.float64, self.k),
-                            (out_pred, np.float64, self._index.t)):
+            out_pred = np.empty((nq, self._index.t), dtype=self.pred_dtype)
+        for a, dt, cols in ((out_idx, self.idx_dtype, self.k), (out_dist, self.dist_dtype, self.k),
+                            (out_pred, self.pred_dtype, self._index.t)):
             if a is not None and (a.dtype != dt or not a.flags.c_contiguous or a.shape != (nq, cols)):
                 raise ValueError(f"output arrays must be C-contiguous ({nq}, {cols}) {np.dtype(dt)}")
-        check(load().sknnr_stream_push(self._h, _host_ptr(q), nq, _host_ptr(out_dist), _host_ptr(out_idx),
-                                       _host_ptr(out_pred)))
+        push = load().sknnr_stream_push_typed if self._typed else load().sknnr_stream_push
+        check(push(self._h, _host_ptr(q), nq, _host_ptr(out_dist), _host_ptr(out_idx), _host_ptr(out_pred)))
         self._keep.append((out_idx, out_dist, out_pred))
         if len(self._keep) > 8:
             del self._keep[:-8]  # older tiles have left the pipeline (four slots: at most the last four pushes are pending)
@@ -724,26 +753,26 @@ class QueryStream:
             if b.ndim != 1 or b.shape[0] != nq or b.dtype != want or not b.flags.c_contiguous:
                 raise ValueError(f"every band must be a C-contiguous ({nq},) {want} array")
         if out_idx is None and (need_idx or not self.want_pred):
-            out_idx = np.empty((self.k, nq), dtype=np.int64)
+            out_idx = np.empty((self.k, nq), dtype=self.idx_dtype)
         if out_dist is None and self.want_dist:
-            out_dist = np.empty((self.k, nq), dtype=np.float64)
+            out_dist = np.empty((self.k, nq), dtype=self.dist_dtype)
         if out_pred is None and self.want_pred:
-            out_pred = np.empty((self._index.t, nq), dtype=np.float64)
-        strides = set()
-        for a, dt, planes in ((out_idx, np.int64, self.k), (out_dist, np.float64, self.k),
-                              (out_pred, np.float64, self._index.t)):
+            out_pred = np.empty((self._index.t, nq), dtype=self.pred_dtype)
+        strides = set()  # (in ELEMENTS of each output's own type: the outputs share the pixel axis, not the byte count)
+        for a, dt, planes in ((out_idx, self.idx_dtype, self.k), (out_dist, self.dist_dtype, self.k),
+                              (out_pred, self.pred_dtype, self._index.t)):
             if a is None:
                 continue
-            if a.dtype != dt or a.shape != (planes, nq) or (nq > 1 and a.strides[1] != 8):
+            if a.dtype != dt or a.shape != (planes, nq) or (nq > 1 and a.strides[1] != dt.itemsize):
                 raise ValueError(f"output arrays must be ({planes}, {nq}) {np.dtype(dt)} with contiguous planes")
             if planes > 1:  # (a single plane has no stride to speak of)
-                strides.add(a.strides[0])
-        if len(strides) > 1 or any(st % 8 or st < 8 * nq for st in strides):
+                strides.add(a.strides[0] / dt.itemsize)
+        if len(strides) > 1 or any(st != int(st) or st < nq for st in strides):
             raise ValueError("output arrays must share one stride between planes, of at least the tile's pixels")
-        stride = strides.pop() // 8 if strides else nq
+        stride = int(strides.pop()) if strides else nq
         ptrs = (c_void_p * cols)(*[b.ctypes.data for b in bands])
-        check(load().sknnr_stream_push_planes(self._h, ptrs, nq, _host_ptr(out_dist), _host_ptr(out_idx),
-                                              _host_ptr(out_pred), stride))
+        push = load().sknnr_stream_push_planes_typed if self._typed else load().sknnr_stream_push_planes
+        check(push(self._h, ptrs, nq, _host_ptr(out_dist), _host_ptr(out_idx), _host_ptr(out_pred), stride))
         self._keep.append((out_idx, out_dist, out_pred))
         if len(self._keep) > 8:
             del self._keep[:-8]
@@ -756,6 +785,34 @@ class QueryStream:
         if nodata.size != cols:
             raise ValueError(f"nodata must hold one value per input column ({cols}), got {nodata.size}")
         check(load().sknnr_stream_set_nodata(self._h, _host_ptr(nodata), int(fill_index)))
+
+    def set_output(self, index_dtype=None, distance_dtype=None, pred_dtype=None, scale=None, offset=None, fill=None):
+        """The element types in which the results leave the device (sknnr_stream_set_output; only before the first
+        push): ``index_dtype`` int32, ``distance_dtype`` float32, ``pred_dtype`` float32 / int16 / uint16 / uint8 / int32;
+        None (or the wide type) leaves an output as it is.  ``scale`` / ``offset``: float64 ``(t,)`` each, both or
+        neither -- the stored prediction is ``rint(pred * scale + offset)`` (no ``rint`` for float32), clamped to the
+        type's range; ``fill``: what a NaN prediction becomes.  Pushes then take and return arrays of those types."""
+        def code(dt, wide):
+            dt = np.dtype(wide if dt is None else dt)
+            if dt == np.dtype(wide):
+                return dt, 0
+            if not DTYPE_CODES.get(dt):
+                raise ValueError(f"{dt} is no narrow output type of the library")
+            return dt, DTYPE_CODES[dt]
+        idt, ic = code(index_dtype, np.int64)
+        ddt, dc = code(distance_dtype, np.float64)
+        pdt, pc = code(pred_dtype, np.float64)
+        if (scale is None) != (offset is None):
+            raise ValueError("scale and offset come together")
+        t = self._index.t
+        if scale is not None:
+            scale, offset = _c_f64(scale).reshape(-1), _c_f64(offset).reshape(-1)
+            if scale.size != t or offset.size != t:
+                raise ValueError(f"scale and offset must hold one value per target ({t})")
+        check(load().sknnr_stream_set_output(self._h, ic, dc, pc, _host_ptr(scale), _host_ptr(offset),
+                                             int(fill is not None), float(0.0 if fill is None else fill)))
+        self.idx_dtype, self.dist_dtype, self.pred_dtype = idt, ddt, pdt
+        self._typed = bool(ic or dc or pc)
 
     def valid_rows(self) -> int:
         """Valid (unmasked) rows submitted so far; without a nodata mask, the rows pushed."""
@@ -888,3 +945,19 @@ def rows_to_planes_device(src_ptr, n, c, dst_ptr, dst_stride, device=0, stream=0
     (sknnr_rows_to_planes); enqueued on ``stream``."""
     check(load().sknnr_rows_to_planes(c_void_p(src_ptr or None), n, c, c_void_p(dst_ptr or None), dst_stride, device,
                                       c_void_p(stream or None)))
+
+
+NARROW_VALUE, NARROW_INDEX = 0, 1
+
+
+def narrow_device(src_ptr, kind, n, c, dst_ptr, dst_dtype, dst_stride=0, scale_ptr=0, offset_ptr=0, fill=None, device=0,
+                  stream=0) -> bool:
+    """A packed ``(n, c)`` float64 (``NARROW_VALUE``) or int64 (``NARROW_INDEX``) tile to ``dst_dtype`` (a numpy dtype or
+    a sknnr_dtype code), packed rows (``dst_stride`` 0) or ``c`` planes ``dst_stride`` elements apart, on device pointers
+    (sknnr_narrow); enqueued on ``stream``.  Returns whether the launch took the 4-elements-per-lane path."""
+    code = dst_dtype if isinstance(dst_dtype, int) else DTYPE_CODES.get(np.dtype(dst_dtype), -1)
+    wide = c_int32(0)
+    check(load().sknnr_narrow(c_void_p(src_ptr or None), int(kind), n, c, c_void_p(dst_ptr or None), code, dst_stride,
+                              c_void_p(scale_ptr or None), c_void_p(offset_ptr or None), int(fill is not None),
+                              float(0.0 if fill is None else fill), device, c_void_p(stream or None), byref(wide)))
+    return bool(wide.value)

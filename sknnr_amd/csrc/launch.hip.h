@@ -1,11 +1,13 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
-// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES), templates where they are instantiated.
+// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW), templates where they are instantiated.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "bucket.hip.h"
 #include "coarse2.hip.h"
@@ -13,6 +15,7 @@
 #include "forest.hip.h"
 #include "hamming.hip.h"
 #include "mask.hip.h"
+#include "narrow.hip.h"
 #include "planes.hip.h"
 #include "rescue.hip.h"
 
@@ -67,6 +70,13 @@ hipError_t row_expand(const ExpandArgs& a, hipStream_t st);
 hipError_t planes_to_rows(const PlanesArgs& a, int elem_bytes, hipStream_t st);
 // packed (n, c) rows of 8-byte elements -> a.c planes of a.n elements, a.stride elements apart
 hipError_t rows_to_planes(const PlanesArgs& a, hipStream_t st);
+
+// ---- k_narrow.hip: result tiles to the raster's storage type (narrow.hip.h) ----------------------------------------------
+// packed (n, c) float64 (kind kNarrowValue) or int64 (kNarrowIndex) -> dst_dtype (a sknnr_dtype), packed or as planes
+// (a.stride); `wide` must satisfy narrow_wide_ok.  hipErrorInvalidValue for an impossible type pair.
+hipError_t narrow(const NarrowArgs& a, int kind, int dst_dtype, bool wide, hipStream_t st);
+// bytes per destination element of that pair, 0 when there is no such conversion
+int narrow_dst_bytes(int kind, int dst_dtype);
 
 // ---- k_coarse1.hip / k_coarse2.hip: the MFMA pre-filters ----------------------------------------------------------------
 struct Coarse1Launch {

@@ -316,6 +316,8 @@ struct sknnr_index {
         // band-first tiles (planes.hip.h): the uploaded planes in front of dev_x, the results as planes behind dev_i / dev_d / dev_p
         DevBuf<double> dev_xp, dev_dp, dev_pp;
         DevBuf<long> dev_ip;
+        // typed outputs (narrow.hip.h): the results at the stream's output types, packed rows or planes, in 8-byte units
+        DevBuf<unsigned long long> nar_i, nar_d, nar_p;
         hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_d2h = nullptr;
         MaskBufs mask;  // nodata front end of the slot's tile (a pipeline with a mask only)
     } slot[kHostSlots];
@@ -365,6 +367,11 @@ struct sknnr_index {
     // the last tile of the host pipeline (sknnr_debug_last_planes): rows arrived as planes, rows, columns, element bytes,
     // results left as planes, output planes written, columns per workgroup of planes_to_rows_kernel
     int64_t last_planes[8] = {};
+    // typed outputs of the open stream: the per-target scale / offset on the device, and the record of the last tile of
+    // the host pipeline (sknnr_debug_last_narrow): conversion ran, rows, the three output types, bytes its device-to-host
+    // copies moved, outputs that took the wide path (bit 0 indices, 1 distances, 2 predictions)
+    DevBuf<double> s_scale, s_offset;
+    int64_t last_narrow[8] = {};
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
     // a ring of call records so that several calls of one benchmark step are summed, not only the last.
@@ -409,6 +416,7 @@ struct sknnr_index {
                 if (hp) (void)hipHostFree(hp);
             sl.dev_x.release(); sl.dev_d.release(); sl.dev_p.release(); sl.dev_i.release();
             sl.dev_xp.release(); sl.dev_dp.release(); sl.dev_pp.release(); sl.dev_ip.release();
+            sl.nar_i.release(); sl.nar_d.release(); sl.nar_p.release();
             for (hipEvent_t e : {sl.ev_h2d, sl.ev_done, sl.ev_d2h})
                 if (e) (void)hipEventDestroy(e);
         }
@@ -2222,10 +2230,10 @@ void stage_planes(void* dst, const void* const* planes, int c, size_t esz, long 
     }
     for (auto& t : th) t.join();
 }
-// The copy-out counterpart: `c` segments of n 8-byte elements, packed in src, to dst + j * stride.
-void unstage_planes(void* dst, const void* src, int c, long n, long stride) {
+// The copy-out counterpart: `c` segments of n elements of esz bytes, packed in src, to dst + j * stride.
+void unstage_planes(void* dst, const void* src, int c, long n, long stride, size_t esz) {
     for (int j = 0; j < c; ++j)
-        parallel_copy((char*)dst + (size_t)j * stride * 8, (const char*)src + (size_t)j * n * 8, (size_t)n * 8);
+        parallel_copy((char*)dst + (size_t)j * stride * esz, (const char*)src + (size_t)j * n * esz, (size_t)n * esz);
 }
 
 template <typename T>
@@ -2257,6 +2265,13 @@ struct HostPipe {
     const double* nodata_dev = nullptr;  // (d_x) on the device, or null: no mask
     long fill_index = -1;
     long row_offset0 = 0;                // o.row_offset when the pipeline was opened
+    // typed outputs (sknnr_stream_set_output): the sknnr_dtype of each output, 0 = as computed (int64 / float64), and the
+    // bytes of one element; the predictions' per-target scale / offset (device, or null), and their NaN fill
+    int dt_i = 0, dt_d = 0, dt_p = 0;
+    size_t esz_i = 8, esz_d = 8, esz_p = 8;
+    const double *pred_scale = nullptr, *pred_offset = nullptr;
+    int has_pred_fill = 0;
+    double pred_fill = 0.0;
     struct Pending {
         bool live = false;
         long n = 0;
@@ -2338,9 +2353,15 @@ int pipe_prepare_slot(HostPipe& p, int b, long n, bool planes = false) {
     const int k = p.k, t = p.t, d_x = p.d_x;
     const size_t x_f64 = ((size_t)n * d_x * p.x_esz + 7) / 8;  // the tile's rows, in 8-byte units
     if ((rc = ensure_pinned(sl.pin_x, sl.pin_x_n, x_f64))) return rc;
-    if ((rc = ensure_pinned(sl.pin_i, sl.pin_i_n, (size_t)n * k))) return rc;
-    if (p.want_dist && (rc = ensure_pinned(sl.pin_d, sl.pin_d_n, (size_t)n * k))) return rc;
-    if (p.want_pred && (rc = ensure_pinned(sl.pin_p, sl.pin_p_n, (size_t)n * t))) return rc;
+    // (the outputs leave at their own width: 8-byte units of n * cols * element bytes; n * cols without typed outputs)
+    const size_t u_i = ((size_t)n * k * p.esz_i + 7) / 8, u_d = ((size_t)n * k * p.esz_d + 7) / 8,
+                 u_p = ((size_t)n * t * p.esz_p + 7) / 8;
+    if ((rc = ensure_pinned(sl.pin_i, sl.pin_i_n, u_i))) return rc;
+    if (p.want_dist && (rc = ensure_pinned(sl.pin_d, sl.pin_d_n, u_d))) return rc;
+    if (p.want_pred && (rc = ensure_pinned(sl.pin_p, sl.pin_p_n, u_p))) return rc;
+    if (p.dt_i) HIP_TRY(sl.nar_i.ensure(u_i));
+    if (p.dt_d && p.want_dist) HIP_TRY(sl.nar_d.ensure(u_d));
+    if (p.dt_p && p.want_pred) HIP_TRY(sl.nar_p.ensure(u_p));
     HIP_TRY(sl.dev_x.ensure(x_f64));
     HIP_TRY(sl.dev_i.ensure((size_t)n * k));
     HIP_TRY(sl.dev_d.ensure((size_t)n * k));
@@ -2348,9 +2369,9 @@ int pipe_prepare_slot(HostPipe& p, int b, long n, bool planes = false) {
     if (p.nodata_dev && (rc = mask_ensure(sl.mask, n, (size_t)d_x * p.x_esz, k, t, p.want_dist, p.want_pred))) return rc;
     if (planes) {  // (band-first tiles only: the uploaded planes, and the results as planes)
         HIP_TRY(sl.dev_xp.ensure(x_f64));
-        HIP_TRY(sl.dev_ip.ensure((size_t)n * k));
-        if (p.want_dist) HIP_TRY(sl.dev_dp.ensure((size_t)n * k));
-        if (p.want_pred) HIP_TRY(sl.dev_pp.ensure((size_t)n * t));
+        if (!p.dt_i) HIP_TRY(sl.dev_ip.ensure((size_t)n * k));
+        if (p.want_dist && !p.dt_d) HIP_TRY(sl.dev_dp.ensure((size_t)n * k));
+        if (p.want_pred && !p.dt_p) HIP_TRY(sl.dev_pp.ensure((size_t)n * t));
     }
     return SKNNR_OK;
 }
@@ -2378,9 +2399,15 @@ int pipe_enqueue_d2h(HostPipe& p) {
     HIP_TRY(hipStreamWaitEvent(st, sl.ev_done, 0));
     const bool planes = pd.planes;  // (then the plane buffers hold the results, packed (k or t, n))
     const long out_stride = pd.out_stride;
-    if (oi) HIP_TRY(hipMemcpyAsync(sl.pin_i, planes ? sl.dev_ip.p : sl.dev_i.p, (size_t)n * k * sizeof(long), hipMemcpyDeviceToHost, st));
-    if (od) HIP_TRY(hipMemcpyAsync(sl.pin_d, planes ? sl.dev_dp.p : sl.dev_d.p, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (op) HIP_TRY(hipMemcpyAsync(sl.pin_p, planes ? sl.dev_pp.p : sl.dev_p.p, (size_t)n * t * sizeof(double), hipMemcpyDeviceToHost, st));
+    // (a typed output leaves from its narrow buffer, rows or planes alike, at its own element size)
+    const size_t esz_i = p.esz_i, esz_d = p.esz_d, esz_p = p.esz_p;
+    const void* src_i = p.dt_i ? (const void*)sl.nar_i.p : planes ? (const void*)sl.dev_ip.p : (const void*)sl.dev_i.p;
+    const void* src_d = p.dt_d ? (const void*)sl.nar_d.p : planes ? (const void*)sl.dev_dp.p : (const void*)sl.dev_d.p;
+    const void* src_p = p.dt_p ? (const void*)sl.nar_p.p : planes ? (const void*)sl.dev_pp.p : (const void*)sl.dev_p.p;
+    if (oi) HIP_TRY(hipMemcpyAsync(sl.pin_i, src_i, (size_t)n * k * esz_i, hipMemcpyDeviceToHost, st));
+    if (od) HIP_TRY(hipMemcpyAsync(sl.pin_d, src_d, (size_t)n * k * esz_d, hipMemcpyDeviceToHost, st));
+    if (op) HIP_TRY(hipMemcpyAsync(sl.pin_p, src_p, (size_t)n * t * esz_p, hipMemcpyDeviceToHost, st));
+    ix->last_narrow[5] = (int64_t)((oi ? (size_t)n * k * esz_i : 0) + (od ? (size_t)n * k * esz_d : 0) + (op ? (size_t)n * t * esz_p : 0));
     HIP_TRY(hipEventRecord(sl.ev_d2h, st));
     // the copy-out leg: wait for the tile's device-to-host copies, then pinned -> the caller's arrays (w_out, in order)
     static const bool workers = [] { const char* e = std::getenv("SKNNR_PIPE_WORKERS"); return !(e && std::atoi(e) == 0); }();
@@ -2392,14 +2419,14 @@ int pipe_enqueue_d2h(HostPipe& p) {
         auto job = [=]() -> int {
             if (hipSetDevice(device) != hipSuccess || hipEventSynchronize(ev) != hipSuccess) return SKNNR_ERR_HIP;
             if (planes) {  // k (or t) contiguous segments of n elements, each to its plane of the caller's array
-                if (oi) unstage_planes(oi, pin_i, k, n, out_stride);
-                if (od) unstage_planes(od, pin_d, k, n, out_stride);
-                if (op) unstage_planes(op, pin_p, t, n, out_stride);
+                if (oi) unstage_planes(oi, pin_i, k, n, out_stride, esz_i);
+                if (od) unstage_planes(od, pin_d, k, n, out_stride, esz_d);
+                if (op) unstage_planes(op, pin_p, t, n, out_stride, esz_p);
                 return SKNNR_OK;
             }
-            if (oi) parallel_copy(oi, pin_i, (size_t)n * k * sizeof(long));
-            if (od) parallel_copy(od, pin_d, (size_t)n * k * sizeof(double));
-            if (op) parallel_copy(op, pin_p, (size_t)n * t * sizeof(double));
+            if (oi) parallel_copy(oi, pin_i, (size_t)n * k * esz_i);
+            if (od) parallel_copy(od, pin_d, (size_t)n * k * esz_d);
+            if (op) parallel_copy(op, pin_p, (size_t)n * t * esz_p);
             return SKNNR_OK;
         };
         if (workers) {
@@ -2473,23 +2500,38 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
             if (rc) return rc;
         }
     }
-    int planes_out = 0;
-    if (planes) {  // the requested results as planes, behind everything that produces them
-        if (oi) {
-            PlanesArgs pa{sl.dev_i.p, sl.dev_ip.p, n, k, n};
+    // The requested results in the form they leave in, behind everything that produces them: a typed output is converted
+    // (and, band-first, transposed in the same pass) into its narrow buffer; an untyped band-first one is transposed; an
+    // untyped row output leaves from where it was computed, with no kernel here.
+    int planes_out = 0, wide_mask = 0, narrowed = 0;
+    auto emit = [&](bool want, int dt, int kind, const void* rows, void* nar, void* as_planes, int cols, int bit) -> int {
+        if (!want) return SKNNR_OK;
+        if (dt) {
+            NarrowArgs na{rows, nar, n, cols, planes ? n : 0, nullptr, nullptr, 0, 0.0};
+            if (bit == 4) {
+                na.scale = p.pred_scale;
+                na.offset = p.pred_offset;
+                na.has_fill = p.has_pred_fill;
+                na.fill = p.pred_fill;
+            }
+            const bool wide = narrow_wide_ok(rows, nar, launch::narrow_dst_bytes(kind, dt), n, cols, na.stride);
+            HIP_TRY(launch::narrow(na, kind, dt, wide, ix->st_run));
+            narrowed = 1;
+            if (wide) wide_mask |= bit;
+            if (planes) planes_out += cols;
+        } else if (planes) {
+            PlanesArgs pa{rows, as_planes, n, cols, n};
             HIP_TRY(launch::rows_to_planes(pa, ix->st_run));
-            planes_out += k;
+            planes_out += cols;
         }
-        if (od) {
-            PlanesArgs pa{sl.dev_d.p, sl.dev_dp.p, n, k, n};
-            HIP_TRY(launch::rows_to_planes(pa, ix->st_run));
-            planes_out += k;
-        }
-        if (op) {
-            PlanesArgs pa{sl.dev_p.p, sl.dev_pp.p, n, p.t, n};
-            HIP_TRY(launch::rows_to_planes(pa, ix->st_run));
-            planes_out += p.t;
-        }
+        return SKNNR_OK;
+    };
+    if ((rc = emit(oi != nullptr, p.dt_i, kNarrowIndex, sl.dev_i.p, sl.nar_i.p, sl.dev_ip.p, k, 1))) return rc;
+    if ((rc = emit(od != nullptr, p.dt_d, kNarrowValue, sl.dev_d.p, sl.nar_d.p, sl.dev_dp.p, k, 2))) return rc;
+    if ((rc = emit(op != nullptr, p.dt_p, kNarrowValue, sl.dev_p.p, sl.nar_p.p, sl.dev_pp.p, p.t, 4))) return rc;
+    {
+        const int64_t rec[8] = {narrowed, n, p.dt_i, p.dt_d, p.dt_p, 0, wide_mask, 0};  // ([5]: pipe_enqueue_d2h)
+        std::copy(std::begin(rec), std::end(rec), ix->last_narrow);
     }
     {
         const int64_t rec[8] = {planes ? 1 : 0, n, d_x, (int64_t)p.x_esz, planes ? 1 : 0, planes_out,
@@ -2557,9 +2599,11 @@ int pipe_submit_rows(HostPipe& p, const void* q_, long nq, double* od, long* oi,
     for (size_t i = 0; i < cuts.size(); ++i) {
         const long c1 = cuts[i], n = c1 - c0;
         const long n_next = i + 1 < cuts.size() ? cuts[i + 1] - c1 : 0;
-        int rc = pipe_submit(p, q + c0 * row_bytes, n, od ? od + c0 * ok : nullptr, oi ? oi + c0 * ok : nullptr,
-                             op ? op + c0 * ot : nullptr, n_next ? q + c1 * row_bytes : nullptr, n_next, planes, c0,
-                             out_stride);
+        // (the output pointers are addresses of elements of the stream's output types: advanced in bytes)
+        int rc = pipe_submit(p, q + c0 * row_bytes, n, od ? (double*)((char*)od + c0 * ok * p.esz_d) : nullptr,
+                             oi ? (long*)((char*)oi + c0 * ok * p.esz_i) : nullptr,
+                             op ? (double*)((char*)op + c0 * ot * p.esz_p) : nullptr,
+                             n_next ? q + c1 * row_bytes : nullptr, n_next, planes, c0, out_stride);
         if (rc) return rc;
         c0 = c1;
     }
@@ -2836,6 +2880,48 @@ extern "C" int sknnr_rows_to_planes(const void* src, int64_t n, int32_t c, void*
     HIP_TRY(hipSetDevice(device));
     PlanesArgs a{src, dst, n, c, dst_stride};
     HIP_TRY(launch::rows_to_planes(a, (hipStream_t)stream));
+    return SKNNR_OK;
+}
+
+// ----------------------------------------------------------------------------------------
+// typed outputs: the conversion alone, on device pointers
+// ----------------------------------------------------------------------------------------
+// `fill` as an element of a narrow output type: an integer inside the type's range, or any float32 value
+static bool narrow_fill_ok(int dtype, double fill) {
+    if (dtype == SKNNR_DTYPE_F32) return fill != fill || (double)(float)fill == fill;
+    double lo, hi;
+    switch (dtype) {
+        case SKNNR_DTYPE_I16: lo = -32768.0, hi = 32767.0; break;
+        case SKNNR_DTYPE_U16: lo = 0.0, hi = 65535.0; break;
+        case SKNNR_DTYPE_U8: lo = 0.0, hi = 255.0; break;
+        case SKNNR_DTYPE_I32: lo = -2147483648.0, hi = 2147483647.0; break;
+        default: return false;
+    }
+    return fill >= lo && fill <= hi && std::nearbyint(fill) == fill;
+}
+
+extern "C" int sknnr_narrow(const void* src, int32_t kind, int64_t n, int32_t c, void* dst, int32_t dst_dtype,
+                            int64_t dst_stride, const double* scale, const double* offset, int32_t has_fill, double fill,
+                            int32_t device, void* stream, int32_t* out_wide) {
+    if (out_wide) *out_wide = 0;
+    const int esz = launch::narrow_dst_bytes(kind, dst_dtype);
+    if (!esz) return fail(SKNNR_ERR_INVALID, "no conversion of kind %d to sknnr_dtype %d", kind, dst_dtype);
+    if (n < 0) return fail(SKNNR_ERR_INVALID, "n must be >= 0");
+    if (c < 1 || c > kMaskMaxCols) return fail(SKNNR_ERR_INVALID, "c = %d outside [1, %d]", c, kMaskMaxCols);
+    if (dst_stride != 0 && dst_stride < n)
+        return fail(SKNNR_ERR_INVALID, "the stride between planes (%lld) is below n (%lld)", (long long)dst_stride, (long long)n);
+    if (!scale != !offset) return fail(SKNNR_ERR_INVALID, "scale and offset come together");
+    if (kind == kNarrowIndex && (scale || has_fill)) return fail(SKNNR_ERR_INVALID, "indices take no scale / offset and no fill");
+    if (has_fill && kind == kNarrowValue && !narrow_fill_ok(dst_dtype, fill))
+        return fail(SKNNR_ERR_INVALID, "fill = %.17g is not representable in sknnr_dtype %d", fill, dst_dtype);
+    if (n == 0) return SKNNR_OK;
+    if (!src || !dst) return fail(SKNNR_ERR_INVALID, "src / dst is NULL");
+    if (n > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 pixels in one call");
+    HIP_TRY(hipSetDevice(device));
+    NarrowArgs a{src, dst, n, c, dst_stride, scale, offset, has_fill != 0, fill};
+    const bool wide = narrow_wide_ok(src, dst, esz, n, c, dst_stride);
+    HIP_TRY(launch::narrow(a, kind, dst_dtype, wide, (hipStream_t)stream));
+    if (out_wide) *out_wide = wide ? 1 : 0;
     return SKNNR_OK;
 }
 
@@ -3259,6 +3345,47 @@ extern "C" int sknnr_stream_set_nodata(sknnr_stream* s, const double* nodata, in
     return SKNNR_OK;
 }
 
+extern "C" int sknnr_stream_set_output(sknnr_stream* s, int32_t idx_dtype, int32_t dist_dtype, int32_t pred_dtype,
+                                       const double* pred_scale, const double* pred_offset, int32_t has_pred_fill,
+                                       double pred_fill) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    if (idx_dtype != SKNNR_DTYPE_F64 && idx_dtype != SKNNR_DTYPE_I32)
+        return fail(SKNNR_ERR_INVALID, "idx_dtype = %d: indices leave as int64 (0) or int32 (SKNNR_DTYPE_I32)", idx_dtype);
+    if (dist_dtype != SKNNR_DTYPE_F64 && dist_dtype != SKNNR_DTYPE_F32)
+        return fail(SKNNR_ERR_INVALID, "dist_dtype = %d: distances leave as float64 (0) or float32 (SKNNR_DTYPE_F32)", dist_dtype);
+    if (pred_dtype < SKNNR_DTYPE_F64 || pred_dtype > SKNNR_DTYPE_I32)
+        return fail(SKNNR_ERR_INVALID, "pred_dtype = %d is no sknnr_dtype", pred_dtype);
+    if (!pred_scale != !pred_offset) return fail(SKNNR_ERR_INVALID, "pred_scale and pred_offset come together");
+    if (pred_dtype == SKNNR_DTYPE_F64 && (pred_scale || has_pred_fill))
+        return fail(SKNNR_ERR_INVALID, "a scale / offset or a fill needs a narrow pred_dtype");
+    if (has_pred_fill && !narrow_fill_ok(pred_dtype, pred_fill))
+        return fail(SKNNR_ERR_INVALID, "pred_fill = %.17g is not representable in pred_dtype %d", pred_fill, pred_dtype);
+    HostPipe& p = s->pipe;
+    if (dist_dtype && !p.want_dist) return fail(SKNNR_ERR_INVALID, "the stream was opened without distances");
+    if (pred_dtype && !p.want_pred) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
+    std::lock_guard<std::mutex> lock(p.ix->mtx);
+    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_output is allowed only before the first push");
+    p.pred_scale = p.pred_offset = nullptr;
+    if (pred_scale) {
+        HIP_TRY(hipSetDevice(p.ix->device));
+        HIP_TRY(p.ix->s_scale.ensure((size_t)p.t));
+        HIP_TRY(p.ix->s_offset.ensure((size_t)p.t));
+        HIP_TRY(hipMemcpy(p.ix->s_scale.p, pred_scale, (size_t)p.t * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(p.ix->s_offset.p, pred_offset, (size_t)p.t * sizeof(double), hipMemcpyHostToDevice));
+        p.pred_scale = p.ix->s_scale.p;
+        p.pred_offset = p.ix->s_offset.p;
+    }
+    p.dt_i = idx_dtype;
+    p.dt_d = dist_dtype;
+    p.dt_p = pred_dtype;
+    p.esz_i = (size_t)dtype_bytes(idx_dtype);
+    p.esz_d = (size_t)dtype_bytes(dist_dtype);
+    p.esz_p = (size_t)dtype_bytes(pred_dtype);
+    p.has_pred_fill = has_pred_fill != 0;
+    p.pred_fill = pred_fill;
+    return SKNNR_OK;
+}
+
 extern "C" int sknnr_stream_valid_rows(const sknnr_stream* s, int64_t* out_valid_rows) {
     if (!s || !out_valid_rows) return fail(SKNNR_ERR_INVALID, "stream / out_valid_rows is NULL");
     std::lock_guard<std::mutex> lock(s->pipe.ix->mtx);
@@ -3295,8 +3422,16 @@ extern "C" int sknnr_stream_begin(sknnr_index* ix, const sknnr_query_opts* o, in
     return SKNNR_OK;
 }
 
-extern "C" int sknnr_stream_push(sknnr_stream* s, const void* q, int64_t nq, double* out_dist, int64_t* out_idx,
-                                 double* out_pred) {
+static bool stream_typed(const sknnr_stream* s) { return s->pipe.dt_i || s->pipe.dt_d || s->pipe.dt_p; }
+static const char* const kTypedStreamMsg =
+    "the stream has typed outputs (sknnr_stream_set_output): use sknnr_stream_push_typed / sknnr_stream_push_planes_typed";
+
+extern "C" int sknnr_stream_push_typed(sknnr_stream* s, const void* q, int64_t nq, void* out_dist_, void* out_idx_,
+                                       void* out_pred_) {
+    // (from here on the outputs are addresses only: their element types are the stream's, see pipe_enqueue_d2h)
+    double* out_dist = (double*)out_dist_;
+    int64_t* out_idx = (int64_t*)out_idx_;
+    double* out_pred = (double*)out_pred_;
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
     if (nq == 0) return SKNNR_OK;
@@ -3320,8 +3455,17 @@ extern "C" int sknnr_stream_push(sknnr_stream* s, const void* q, int64_t nq, dou
     return SKNNR_OK;
 }
 
-extern "C" int sknnr_stream_push_planes(sknnr_stream* s, const void* const* planes, int64_t nq, double* out_dist,
-                                        int64_t* out_idx, double* out_pred, int64_t out_stride) {
+extern "C" int sknnr_stream_push(sknnr_stream* s, const void* q, int64_t nq, double* out_dist, int64_t* out_idx,
+                                 double* out_pred) {
+    if (s && stream_typed(s)) return fail(SKNNR_ERR_INVALID, "%s", kTypedStreamMsg);
+    return sknnr_stream_push_typed(s, q, nq, out_dist, out_idx, out_pred);
+}
+
+extern "C" int sknnr_stream_push_planes_typed(sknnr_stream* s, const void* const* planes, int64_t nq, void* out_dist_,
+                                              void* out_idx_, void* out_pred_, int64_t out_stride) {
+    double* out_dist = (double*)out_dist_;
+    int64_t* out_idx = (int64_t*)out_idx_;
+    double* out_pred = (double*)out_pred_;
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
     if (nq == 0) return SKNNR_OK;
@@ -3347,6 +3491,12 @@ extern "C" int sknnr_stream_push_planes(sknnr_stream* s, const void* const* plan
     }
     s->rows_pushed += nq;
     return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_push_planes(sknnr_stream* s, const void* const* planes, int64_t nq, double* out_dist,
+                                        int64_t* out_idx, double* out_pred, int64_t out_stride) {
+    if (s && stream_typed(s)) return fail(SKNNR_ERR_INVALID, "%s", kTypedStreamMsg);
+    return sknnr_stream_push_planes_typed(s, planes, nq, out_dist, out_idx, out_pred, out_stride);
 }
 
 extern "C" int sknnr_stream_flush(sknnr_stream* s) {
@@ -3437,6 +3587,14 @@ extern "C" int sknnr_debug_last_mask(const sknnr_index* cix, int64_t out[8]) {
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
     std::copy(std::begin(ix->last_mask), std::end(ix->last_mask), out);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_narrow(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "index / out is NULL");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::copy(std::begin(ix->last_narrow), std::end(ix->last_narrow), out);
     return SKNNR_OK;
 }
 
