@@ -292,6 +292,55 @@ int sknnr_predict_from_neighbors(sknnr_index* index, const double* dist, const i
                                  const double* w, int64_t nq, int32_t k, int32_t weight_mode,
                                  double* out_pred, int32_t mem, void* stream);
 
+/* ---- per-target neighbour summaries ------------------------------------------------------------- */
+
+/*
+ * One statistic per target column, reduced on the device from the k neighbours of a query in the order sknnr_kneighbors
+ * returns them (sknnr_amd/csrc/summary.hip.h; tests/_neighbor_stats.py restates the definitions in numpy).  v_i =
+ * y[idx_i, j]; w_i: the weights of sknnr_predict (uniform 1.0; distance 1 / d_i, a row holding d == 0 becomes its 0 / 1
+ * mask; explicit as given).  All arithmetic is float64; np_sum is numpy's pairwise sum over the k axis.
+ *   MEAN    : the value sknnr_predict gives that column, bit for bit (same kernels)
+ *   MODE    : scikit-learn's weighted_mode as KNeighborsClassifier.predict applies it: per distinct label c the vote is
+ *             np_sum_i(v_i == c ? w_i : 0.0); the largest vote wins, the smaller label on equal votes; the result is the
+ *             label.  Labels are compared as float64 values.  A row whose votes are all zero (explicit weights) gives NaN.
+ *   MIN/MAX : of v_i; weights are ignored
+ *   NEAREST : v_0
+ *   STD     : sqrt(np_sum_i((w_i * (v_i - m)) * (v_i - m)) / np_sum_i(w_i)), m = the float64 weighted mean of that column
+ *             as sknnr_predict computes it for float64 targets
+ */
+enum sknnr_statistic {
+    SKNNR_STAT_MEAN = 0,
+    SKNNR_STAT_MODE = 1,
+    SKNNR_STAT_MIN = 2,
+    SKNNR_STAT_MAX = 3,
+    SKNNR_STAT_NEAREST = 4,
+    SKNNR_STAT_STD = 5
+};
+
+/*
+ * The reduction alone: sknnr_predict_from_neighbors with a statistic per target.  Same argument rules.
+ *   stat : (t) int32 sknnr_statistic codes, HOST memory whatever `mem` is; NULL or an unknown code: SKNNR_ERR_INVALID
+ *   out  : (nq, t) float64 in `mem`
+ * The MEAN columns come from the predict kernels; the other columns from one further launch (none for an all-MEAN table).
+ */
+int sknnr_summarize_from_neighbors(sknnr_index* index, const double* dist, const int64_t* idx, const double* w,
+                                   int64_t nq, int32_t k, int32_t weight_mode, const int32_t* stat, double* out,
+                                   int32_t mem, void* stream);
+
+/* Search plus reduction: sknnr_predict with a statistic per target (stat as above), opts->exclude_self included. */
+int sknnr_summarize(sknnr_index* index, const void* q, int64_t nq, const sknnr_query_opts* opts, const int32_t* stat,
+                    double* out, double* out_dist, int64_t* out_idx, int32_t mem, void* stream);
+
+/*
+ * Debug only.  The last reduction the handle launched (predict or summary entry, one-shot or streamed tile).  Host
+ * memory, no device work:
+ *   out[0] summary kernel of that reduction: 0 none ran, 1 the register path (k <= 8), 2 the wide path
+ *   out[1] rows      out[2] columns the summary kernel handled      out[3] k
+ *   out[4] 1 = the predict kernels ran (some column is a mean, or no statistics were given)
+ *   out[5] t      out[6] weight mode without its flags      out[7] 0
+ */
+int sknnr_debug_last_summary(const sknnr_index* index, int64_t out[8]);
+
 /*
  * Full weighted-Hamming distance rows: out[i, j] = distance between query row rows[i] and reference row j, in the
  * reference's float64 arithmetic (sknnr_formula, SKNNR_FORMULA_HAMMING) -- the matrix the reference's brute search
@@ -403,6 +452,15 @@ int sknnr_predict_masked(sknnr_index* index, const void* q, int64_t nq, const sk
                          const double* nodata, int64_t fill_index, double* out_pred, double* out_dist, int64_t* out_idx,
                          int32_t mem, void* stream, int64_t* out_n_valid);
 int sknnr_stream_set_nodata(sknnr_stream* stream, const double* nodata, int64_t fill_index);
+
+/*
+ * sknnr_stream_set_statistics: the stream's predictions become per-target summaries (enum sknnr_statistic): stat is a
+ * HOST array of t codes, t the handle's number of targets.  Allowed after sknnr_stream_begin and before the first push;
+ * SKNNR_ERR_INVALID on a stream opened without predictions, after a push, or with another t.  The summary is written
+ * where the prediction is: masked rows, band-first results and typed outputs treat it alike.  A stream without this call
+ * (or with an all-MEAN table) enqueues exactly what it did before.
+ */
+int sknnr_stream_set_statistics(sknnr_stream* stream, const int32_t* stat, int32_t t);
 int sknnr_stream_valid_rows(const sknnr_stream* stream, int64_t* out_valid_rows);
 
 /* ---- band-first tiles (raster layouts) ------------------------------------------------------ */

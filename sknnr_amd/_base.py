@@ -149,6 +149,24 @@ def normalize_typed_output(out_dtype, scale, offset, out_nodata, n_targets, mask
     return dict(pred_dtype=dt, scale=scale, offset=offset, fill=None if out_nodata is None else float(out_nodata))
 
 
+def normalize_statistic(statistic, n_targets):
+    """``statistic`` of ``summarize`` / ``predict_chunks`` -- one name of ``_native.STATISTICS`` or one name per target
+    -- as the int32 codes the engine takes; every refusal comes before any device work."""
+    names = [statistic] * n_targets if isinstance(statistic, str) else statistic
+    try:
+        names = list(names)
+    except TypeError:
+        raise ValueError(f"statistic must be a name or a sequence of names, one per target, got {statistic!r}") from None
+    for name in names:
+        if not isinstance(name, str):
+            raise ValueError(f"statistic entries must be strings, got {name!r}")
+        if name not in _native.STATISTICS:
+            raise ValueError(f"unknown statistic {name!r}: use one of {', '.join(_native.STATISTICS)}")
+    if len(names) != n_targets:
+        raise ValueError(f"statistic must be one name or hold one name per target ({n_targets}), got {len(names)}")
+    return np.array([_native.STATISTICS[name] for name in names], dtype=np.int32)
+
+
 def _check_layout(layout):
     if layout not in _LAYOUTS:
         raise ValueError(f"layout must be 'rows' or 'bands', got {layout!r}")
@@ -659,6 +677,53 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             X = self._validate_query(X)
         return self._predict_engine(X, apply_affine=False)
 
+    def _n_targets(self) -> int:
+        return 1 if self._y.ndim == 1 else self._y.shape[1]
+
+    def _summarize_engine(self, X, stat, *, apply_affine, row_offset=0, n_self_rows=None, owner=None):
+        """:meth:`_predict_engine` with the statistic codes ``stat`` in place of the mean; always float64."""
+        weights = "uniform" if self.weights is None else self.weights
+        try:
+            if self._reference_ties():
+                # as _predict_engine: the policy's own neighbours, then the reduction on the device
+                dist, idx = self._kneighbors_reference_ties(X, self.n_neighbors, True, row_offset, n_self_rows,
+                                                            apply_affine)
+                cuda = is_torch_cuda_tensor(dist)
+                if cuda:
+                    dev = dist.device
+                    dist, idx = dist.cpu().numpy(), idx.cpu().numpy()
+                out = self.engine_.summarize_from_neighbors(dist, idx, weights, stat)
+                if cuda:
+                    import torch
+
+                    out = torch.as_tensor(out, device=dev)
+            else:
+                out = self.engine_.summarize(
+                    X, self.n_neighbors, weights, stat, exclude_self=X is None, deterministic=True,
+                    decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula(), apply_affine=apply_affine,
+                    row_offset=row_offset, n_self_rows=n_self_rows, check_finite=X is not None)
+        except _native.HipBackendError as err:
+            _reraise(err, owner if owner is not None else self)
+        return out.reshape(-1) if self._y.ndim == 1 else out
+
+    def summarize(self, X=None, statistic="mean"):
+        """A summary of each query's neighbours per target, reduced on the device from the neighbours ``kneighbors``
+        finds (deterministic ordering on, as ``predict``); ``X=None`` summarises every fitted row's neighbours, itself
+        excluded.  ``statistic``: one name, or one name per target -- ``"mean"`` (what ``predict`` gives, bit for bit), ``"mode"``
+        (scikit-learn's ``KNeighborsClassifier.predict``: per distinct label the vote is the pairwise sum of the weights
+        of the neighbours that carry it; the largest vote wins, the smaller label on equal votes; labels are the float64
+        values in ``y``; all votes zero under a weights callable: NaN), ``"min"`` / ``"max"`` (of the neighbours' values,
+        weights ignored), ``"nearest"`` (the first neighbour's value) and ``"std"`` (the weighted population standard
+        deviation ``sqrt(sum((w * (v - m)) * (v - m)) / sum(w))`` around the float64 weighted mean ``m``, both sums
+        numpy's pairwise sums over the k neighbours).  Weights are those of ``predict``: 1, ``1 / d`` (a row holding
+        ``d == 0`` becomes its 0 / 1 mask) or the callable's; all arithmetic is float64.  Returns float64 ``(n, t)``, ``(n,)`` for a 1-D
+        ``y``; numpy in gives numpy out, CUDA tensors in give CUDA tensors out."""
+        check_is_fitted(self, "_fit_X")
+        stat = normalize_statistic(statistic, self._n_targets())
+        if X is not None:
+            X = self._validate_query(X)
+        return self._summarize_engine(X, stat, apply_affine=False)
+
     # -- streamed tiles (raster ingestion; REF docs/pages/usage.md:101-128) --------------------
     def _check_nodata_supported(self, nodata):
         """The nodata mask runs in front of the device search of a native stream; the paths that answer tile by tile on
@@ -695,7 +760,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                       "chosen on the host, tile by tile; use the default policy 'lowest_index'")
 
     def _stream_tiles(self, tiles, validate, k, *, apply_affine, weights, return_distance,
-                      use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False, output=None):
+                      use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False, output=None,
+                      statistic=None):
         """Push host tiles through one native query stream.  Returns (dist, idx, pred) arrays over all
         pushed rows (pieces of ``out`` when given, else concatenated).  ``nodata`` (float64, one value per column of the
         validated tiles): rows holding one are masked on the device and get ``fill_index`` / NaN.
@@ -705,7 +771,10 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         ``out`` arrays must then share one ``N``, the stride between their planes.
 
         ``output``: keyword arguments of :meth:`sknnr_amd._native.QueryStream.set_output` -- the results are narrowed on
-        the device and the arrays (``out`` included) have those element types."""
+        the device and the arrays (``out`` included) have those element types.
+
+        ``statistic``: int32 codes (:func:`normalize_statistic`), one per target -- the predictions are those summaries
+        of the neighbours instead of the mean."""
         self._check_typed_supported(output)
         eng = self.engine_
         want_pred = weights is not None
@@ -727,7 +796,11 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 tile = validate(tile)
                 if tile.shape[0] == 0:
                     continue
-                if want_pred:
+                if want_pred and statistic is not None:
+                    parts.append((None, None, np.reshape(self._summarize_engine(tile, statistic, apply_affine=apply_affine,
+                                                                                 row_offset=row, owner=owner),
+                                                         (tile.shape[0], -1))))
+                elif want_pred:
                     parts.append((None, None, np.reshape(self._predict_engine(tile, apply_affine=apply_affine, row_offset=row,
                                                                                owner=owner), (tile.shape[0], -1))))
                 else:
@@ -773,7 +846,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              deterministic=use_deterministic_ordering,
                                              decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula(),
                                              apply_affine=apply_affine, check_finite=True, query_dtype=code,
-                                             nodata=nodata, fill_index=fill_index, output=output)
+                                             nodata=nodata, fill_index=fill_index, output=output, statistic=statistic)
                 if first.dtype != stream_dtype:
                     if stream_dtype != np.float64:
                         raise ValueError(f"the tiles of one streamed call must share an element type: got {first.dtype} "
@@ -912,7 +985,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         return (dist, idx) if return_distance else idx
 
     def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
-                       out_nodata=None):
+                       out_nodata=None, statistic=None):
         """``predict`` over an iterable of host tiles as one streamed call; ``out``: preallocated
         ``(n_rows, n_targets)`` float64 array (e.g. a memmap; float32 results are held exactly).  ``nodata`` as in
         :meth:`kneighbors_chunks`: masked rows are predicted NaN.  ``layout="bands"``: band-first tiles as in
@@ -924,18 +997,34 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         (scalars or one value per target): the stored value is ``rint(pred * scale + offset)`` -- two float64 roundings,
         half to even -- clamped to the type's range (float32: ``pred * scale + offset`` rounded to float32, no ``rint``).
         Masked rows get ``out_nodata``, which must be representable in ``out_dtype``, is required for an integer type
-        with ``nodata`` and defaults to NaN for float32.  The clamp does not avoid the nodata value."""
+        with ``nodata`` and defaults to NaN for float32.  The clamp does not avoid the nodata value.
+
+        ``statistic`` (one name, or one name per target): what is reduced from each pixel's neighbours on the device in
+        place of the mean, as :meth:`summarize` defines it -- ``"mean"`` (what ``predict`` gives, bit for bit), ``"mode"``
+        (scikit-learn's ``KNeighborsClassifier.predict``: per distinct label the vote is the pairwise sum of the weights
+        of the neighbours that carry it; the largest vote wins, the smaller label on equal votes; labels are the float64
+        values in ``y``; all votes zero under a weights callable: NaN), ``"min"`` / ``"max"`` (of the neighbours' values,
+        weights ignored), ``"nearest"`` (the first neighbour's value) and ``"std"`` (the weighted population standard
+        deviation ``sqrt(sum((w * (v - m)) * (v - m)) / sum(w))`` around the float64 weighted mean ``m``, both sums
+        numpy's pairwise sums over the k neighbours).  Weights are those of ``predict``: 1, ``1 / d`` (a row holding
+        ``d == 0`` becomes its 0 / 1 mask) or the callable's; all arithmetic is float64.  The result equals ``summarize(np.concatenate(tiles),
+        statistic)`` bit for bit (float64 unless ``out_dtype`` says otherwise) and is written where the prediction is, so
+        ``nodata``, ``layout``, ``out`` and the typed outputs apply unchanged; e.g. ``statistic=["mean", "mean", "mode"]``
+        maps two continuous attributes and a class code in one call."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
+        if statistic is not None:
+            statistic = normalize_statistic(statistic, self._n_targets())
         if nodata is not None:
             nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
         validate = self._validate_query
         if bands:
             validate = lambda t: normalize_band_tile(t, self.n_features_in_, estimator=type(self).__name__)  # noqa: E731
         return self._predict_chunks(tiles, validate, apply_affine=False, out=out, owner=None, nodata=nodata, bands=bands,
-                                    typed=(out_dtype, scale, offset, out_nodata))
+                                    typed=(out_dtype, scale, offset, out_nodata), statistic=statistic)
 
-    def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None, bands=False, typed=None):
+    def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None, bands=False, typed=None,
+                        statistic=None):
         weights = "uniform" if self.weights is None else self.weights
         output = None
         if typed is not None:
@@ -956,7 +1045,10 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             preds, row = [], 0
             for t in tiles:
                 t = validate(t)
-                preds.append(self._predict_engine(t, apply_affine=apply_affine, row_offset=row, owner=owner))
+                if statistic is not None:
+                    preds.append(self._summarize_engine(t, statistic, apply_affine=apply_affine, row_offset=row, owner=owner))
+                else:
+                    preds.append(self._predict_engine(t, apply_affine=apply_affine, row_offset=row, owner=owner))
                 row += t.shape[0]
             pred = np.concatenate([p.reshape(len(p), -1) for p in preds]) if preds else np.empty((0, self.engine_.t))
             if out is not None:
@@ -969,8 +1061,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             _, _, pred = self._stream_tiles(tiles, validate, self.n_neighbors, apply_affine=apply_affine,
                                             weights=weights, return_distance=False,
                                             use_deterministic_ordering=True, out=o, owner=owner, nodata=nodata,
-                                            bands=bands, output=output)
-            if out is None and not output:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
+                                            bands=bands, output=output, statistic=statistic)
+            if out is None and not output and statistic is None:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
                 pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         return pred.reshape(-1) if self._y.ndim == 1 else pred
 
@@ -1132,6 +1224,17 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         return self._host_result(X, self.regressor_._predict_engine(X, apply_affine=X is not None and self._map_on_device(),
                                                                     owner=self.transformer_))
 
+    def summarize(self, X=None, statistic="mean"):
+        """Per-target summaries of each query's neighbours (:meth:`RawKNNRegressor.summarize`, also for the definitions
+        of ``statistic``); ``X=None``: of every fitted row's neighbours, itself excluded."""
+        check_is_fitted(self, "regressor_")
+        reg = self.regressor_
+        stat = normalize_statistic(statistic, reg._n_targets())
+        if X is not None:
+            X = self._validate_raw_query(X)
+        return self._host_result(X, reg._summarize_engine(X, stat, apply_affine=X is not None and self._map_on_device(),
+                                                          owner=self.transformer_))
+
     def _raw_nodata(self, nodata):
         """``nodata`` of a streamed call, one value per UNTRANSFORMED input column: the mask reads the raw rows, so they
         must reach the engine raw (affine map or forests on the device)."""
@@ -1181,16 +1284,20 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
                                   fill_index=None if nodata is None else fill_index)
 
     def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
-                       out_nodata=None):
+                       out_nodata=None, statistic=None):
         """``predict`` over an iterable of untransformed host tiles as one streamed call (``nodata``: masked rows are
         predicted NaN; ``layout="bands"``: band-first tiles and predictions; ``out_dtype`` / ``scale`` / ``offset`` /
-        ``out_nodata``: predictions converted on the device to the type the raster is stored in; see
+        ``out_nodata``: predictions converted on the device to the type the raster is stored in; ``statistic``: one name
+        or one per target -- mean, mode, min, max, nearest, std of the neighbours in place of the mean; see
         :meth:`RawKNNRegressor.kneighbors_chunks` / :meth:`RawKNNRegressor.predict_chunks`)."""
         bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
+        if statistic is not None:
+            statistic = normalize_statistic(statistic, self.regressor_._n_targets())
         return self.regressor_._predict_chunks(tiles, self._band_validator(bands), apply_affine=self._map_on_device(),
                                                out=out, owner=self.transformer_, nodata=self._raw_nodata(nodata),
-                                               bands=bands, typed=(out_dtype, scale, offset, out_nodata))
+                                               bands=bands, typed=(out_dtype, scale, offset, out_nodata),
+                                               statistic=statistic)
 
     def score(self, X, y):
         """REF _base.py:350-352."""

@@ -274,6 +274,89 @@ class KNNEngine:
         pred = self._index.predict_from_neighbors_host(dist, idx, w, mode)
         return pred if out_dtype == np.float64 else pred.astype(np.float32)
 
+    def summarize_from_neighbors(self, dist, idx, weights, stat):
+        """Per-target statistics (``stat``: one ``_native.STATISTICS`` code per target) of neighbours already found:
+        :meth:`predict_from_neighbors` with the mean replaced column by column.  Always float64 ``(nq, t)``.  Explicit
+        weights that are negative or not finite are refused."""
+        if self.t < 1:
+            raise ValueError("the engine was built without targets")
+        k = idx.shape[1]
+        w = None
+        cuda = is_torch_cuda_tensor(idx)
+        if callable(weights):
+            w = weights(dist)
+            if not hasattr(w, "dtype"):
+                w = np.asarray(w)
+            w32 = str(getattr(w, "dtype", "")) in ("float32", "torch.float32")
+            if tuple(w.shape) != tuple(dist.shape):
+                raise ValueError("the weights callable must return an array shaped like its input")
+            if is_torch_cuda_tensor(w):
+                bad = bool(((w < 0) | ~w.isfinite()).any())
+            else:
+                wh = np.asarray(w)
+                bad = bool(np.any(wh < 0) or not np.all(np.isfinite(wh)))
+            if bad:
+                raise ValueError("the weights callable returned negative or non-finite weights: the neighbour summaries "
+                                 "are defined for finite weights >= 0")
+            mode = self.weight_mode("explicit", w32)
+        elif weights in _WEIGHT_MODES:
+            mode = self.weight_mode(weights)
+        else:
+            raise ValueError(f"weights not recognized: should be 'uniform', 'distance', or a callable; got {weights!r}")
+        if cuda:
+            import torch
+
+            idx = idx.to(torch.int64).contiguous()
+            dist = None if dist is None else dist.to(torch.float64).contiguous()
+            if w is not None:
+                w = torch.as_tensor(w, device=idx.device).to(torch.float64).contiguous()
+            out = torch.empty((idx.shape[0], self.t), dtype=torch.float64, device=idx.device)
+            if idx.shape[0]:
+                stream = torch.cuda.current_stream(idx.device).cuda_stream
+                self._index.summarize_from_neighbors_device(0 if dist is None else dist.data_ptr(), idx.data_ptr(),
+                                                            0 if w is None else w.data_ptr(), idx.shape[0], k, mode,
+                                                            stat, out.data_ptr(), stream)
+            return out
+        w = None if w is None else np.asarray(w, dtype=np.float64)
+        return self._index.summarize_from_neighbors_host(dist, idx, w, mode, stat)
+
+    def summarize(self, X, k, weights, stat, *, exclude_self=False, deterministic=True, decimals=10,
+                  formula="expanded", apply_affine=False, row_offset=0, n_self_rows=None, check_finite=False):
+        """Search plus per-target statistics: :meth:`predict` with ``stat`` (one ``_native.STATISTICS`` code per target)
+        choosing what is reduced from the neighbours.  Always float64 ``(nq, t)``."""
+        if self.t < 1:
+            raise ValueError("the engine was built without targets")
+        if callable(weights):  # (as predict: the callable maps the distances to weights on the host)
+            dist, idx = self.kneighbors(X, k, exclude_self=exclude_self, deterministic=deterministic,
+                                        decimals=decimals, formula=formula, apply_affine=apply_affine,
+                                        row_offset=row_offset, n_self_rows=n_self_rows, check_finite=check_finite)
+            return self.summarize_from_neighbors(dist, idx, weights, stat)
+        if weights not in _WEIGHT_MODES:
+            raise ValueError(f"weights not recognized: should be 'uniform', 'distance', or a callable; got {weights!r}")
+        qdt = self.query_dtype_code(X, formula, apply_affine)
+        opts = self._opts(k, exclude_self=exclude_self, deterministic=deterministic, decimals=decimals,
+                          formula=formula, apply_affine=apply_affine and X is not None,
+                          weight_mode=self.weight_mode(weights), row_offset=row_offset,
+                          check_finite=check_finite and X is not None, query_dtype=qdt)
+        if X is None:
+            nq = self.n_ref - row_offset if n_self_rows is None else int(n_self_rows)
+            return self._index.summarize_host(None, opts, stat, nq=nq)
+        if is_torch_cuda_tensor(X):
+            import torch
+
+            X = self._as_device_rows(X, apply_affine, qdt)
+            nq = X.shape[0]
+            out = torch.empty((nq, self.t), dtype=torch.float64, device=X.device)
+            if nq:
+                stream = torch.cuda.current_stream(X.device).cuda_stream
+                self._index.summarize_device(X.data_ptr(), nq, opts, stat, out.data_ptr(), stream)
+                if check_finite:
+                    self._index.check_finite(stream)
+            return out
+        X = np.ascontiguousarray(X) if qdt else np.ascontiguousarray(X, dtype=np.float64)
+        self._check_columns(X, apply_affine)
+        return self._index.summarize_host(X, opts, stat)
+
     def predict(self, X, k, weights="uniform", *, exclude_self=False, deterministic=True, decimals=10,
                 formula="expanded", apply_affine=False, row_offset=0, n_self_rows=None, check_finite=False,
                 nodata=None):
@@ -380,13 +463,15 @@ class KNNEngine:
 
     def open_stream(self, k, *, weights=None, want_dist=True, deterministic=True, decimals=10,
                     formula="expanded", apply_affine=False, row_offset=0, check_finite=False, query_dtype=0,
-                    nodata=None, fill_index=-1, output=None):
+                    nodata=None, fill_index=-1, output=None, statistic=None):
         """A :class:`sknnr_amd._native.QueryStream` over host tiles: ``push(tile)`` keeps the PCIe
         pipeline full across tiles and carries the global row offset.  ``weights`` (``"uniform"`` /
         ``"distance"``) also asks for predictions: float64 arrays, holding binary32 values where
         :meth:`pred_dtype` is float32.  ``nodata`` (float64, one value per column of the tiles): every tile is masked on
         the device, masked rows get ``fill_index`` / NaN and the row offset counts valid rows only.  ``output``: keyword
-        arguments of :meth:`sknnr_amd._native.QueryStream.set_output` (typed results, narrowed on the device)."""
+        arguments of :meth:`sknnr_amd._native.QueryStream.set_output` (typed results, narrowed on the device).
+        ``statistic``: one ``_native.STATISTICS`` code per target; the predictions become those summaries of the
+        neighbours (:meth:`summarize`), written where the predictions are."""
         want_pred = weights is not None
         if want_pred and weights not in _WEIGHT_MODES:
             raise ValueError("a stream predicts with 'uniform' or 'distance' weights only")
@@ -394,8 +479,10 @@ class KNNEngine:
                           formula=formula, apply_affine=apply_affine,
                           weight_mode=self.weight_mode(weights) if want_pred else _native.WEIGHTS_UNIFORM,
                           row_offset=row_offset, check_finite=check_finite, query_dtype=query_dtype)
+        if statistic is not None and not want_pred:
+            raise ValueError("statistics need a stream that predicts: pass weights")
         return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred, nodata=nodata, fill_index=fill_index,
-                                       output=output)
+                                       output=output, statistic=statistic)
 
     def hamming_distances(self, X, rows=None):
         """Full weighted-Hamming distance rows of ``X[rows]`` (``X`` None: of the fitted rows) from the device."""

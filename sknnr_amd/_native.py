@@ -27,6 +27,9 @@ WEIGHTS_EXPLICIT = 2
 WEIGHTS_F32_TARGETS = 0x100
 WEIGHTS_F32_WEIGHTS = 0x200
 
+# sknnr_statistic (include/sknnr_hip.h): the per-target summaries of the neighbours
+STATISTICS = {"mean": 0, "mode": 1, "min": 2, "max": 3, "nearest": 4, "std": 5}
+
 ERR_INVALID = -1
 ERR_K_TOO_LARGE = -2
 ERR_NO_TARGETS = -3
@@ -72,6 +75,10 @@ EXPORTED_SYMBOLS = (
     "sknnr_kneighbors",
     "sknnr_predict",
     "sknnr_predict_from_neighbors",
+    "sknnr_summarize_from_neighbors",
+    "sknnr_summarize",
+    "sknnr_stream_set_statistics",
+    "sknnr_debug_last_summary",
     "sknnr_hamming_distances",
     "sknnr_shard_candidates",
     "sknnr_merge_shards",
@@ -233,6 +240,11 @@ def load(build_if_missing: bool = False):
     lib.sknnr_predict.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), vp, vp, vp, c_int32, vp]
     lib.sknnr_predict_from_neighbors.argtypes = [vp, vp, vp, vp, c_int64, c_int32, c_int32, vp,
                                                  c_int32, vp]
+    if hasattr(lib, "sknnr_summarize"):  # (a SKNNR_HIP_LIBRARY variant built before the entry points existed)
+        lib.sknnr_summarize_from_neighbors.argtypes = [vp, vp, vp, vp, c_int64, c_int32, c_int32, vp, vp, c_int32, vp]
+        lib.sknnr_summarize.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), vp, vp, vp, vp, c_int32, vp]
+        lib.sknnr_stream_set_statistics.argtypes = [vp, vp, c_int32]
+        lib.sknnr_debug_last_summary.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_hamming_distances.argtypes = [vp, vp, c_int64, vp, c_int64, vp, c_int32, vp]
     lib.sknnr_shard_candidates.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int64, vp, vp, c_int32, vp]
     lib.sknnr_merge_shards.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int32, vp, vp, vp, vp, c_int32, vp]
@@ -271,6 +283,11 @@ def _host_ptr(a):
 
 def _c_f64(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _c_stat(stat):
+    """Statistic codes (``STATISTICS`` values) as the C entry points read them, or None."""
+    return None if stat is None else np.ascontiguousarray(stat, dtype=np.int32).reshape(-1)
 
 
 def _c_rows(a, opts):
@@ -387,16 +404,19 @@ class Index:
         check(load().sknnr_check_finite(self.handle, c_void_p(stream or None)))
 
     def open_stream(self, opts: QueryOpts, want_dist=True, want_pred=False, nodata=None, fill_index=-1,
-                    output=None) -> "QueryStream":
+                    output=None, statistic=None) -> "QueryStream":
         """``nodata``: float64 ``(d_in,)``, one value per column of the pushed rows -- every tile is then masked on the
         device (sknnr_stream_set_nodata) and masked rows get ``fill_index`` / NaN.  ``output``: keyword arguments of
-        :meth:`QueryStream.set_output` -- the results then leave the device at those types."""
+        :meth:`QueryStream.set_output` -- the results then leave the device at those types.  ``statistic``: one
+        ``STATISTICS`` code per target (:meth:`QueryStream.set_statistics`) -- the predictions become those summaries."""
         stream = QueryStream(self, opts, want_dist, want_pred)
         try:
             if nodata is not None:
                 stream.set_nodata(nodata, fill_index)
             if output:
                 stream.set_output(**output)
+            if statistic is not None:
+                stream.set_statistics(statistic)
         except Exception:
             stream.close()
             raise
@@ -437,6 +457,48 @@ class Index:
                                                   _host_ptr(w), nq, k, int(weight_mode),
                                                   _host_ptr(pred), MEM_HOST, None))
         return pred
+
+    # ---- per-target neighbour summaries (include/sknnr_hip.h) --------------------------------
+    def summarize_host(self, q, opts: QueryOpts, stat, nq=None):
+        """Search plus per-target statistic (sknnr_summarize) on host rows, or on the index's own rows (``q`` None)."""
+        q = _c_rows(q, opts)
+        if q is not None:
+            nq = q.shape[0]
+        stat = _c_stat(stat)
+        out = np.empty((nq, self.t), dtype=np.float64)
+        check(load().sknnr_summarize(self.handle, _host_ptr(q), nq, byref(opts), _host_ptr(stat), _host_ptr(out),
+                                     None, None, MEM_HOST, None))
+        return out
+
+    def summarize_device(self, q_ptr, nq, opts: QueryOpts, stat, out_ptr, stream=0):
+        stat = _c_stat(stat)
+        check(load().sknnr_summarize(self.handle, c_void_p(q_ptr or None), nq, byref(opts), _host_ptr(stat),
+                                     c_void_p(out_ptr), None, None, MEM_DEVICE, c_void_p(stream or None)))
+
+    def summarize_from_neighbors_host(self, dist, idx, w, weight_mode, stat):
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        dist, w, stat = _c_f64(dist), _c_f64(w), _c_stat(stat)
+        nq, k = idx.shape
+        out = np.empty((nq, self.t), dtype=np.float64)
+        check(load().sknnr_summarize_from_neighbors(self.handle, _host_ptr(dist), _host_ptr(idx), _host_ptr(w), nq, k,
+                                                    int(weight_mode), _host_ptr(stat), _host_ptr(out), MEM_HOST, None))
+        return out
+
+    def summarize_from_neighbors_device(self, dist_ptr, idx_ptr, w_ptr, nq, k, weight_mode, stat, out_ptr, stream=0):
+        """Device pointers in and out; ``stat`` stays a host array of codes."""
+        stat = _c_stat(stat)
+        check(load().sknnr_summarize_from_neighbors(
+            self.handle, c_void_p(dist_ptr or None), c_void_p(idx_ptr), c_void_p(w_ptr or None), nq, k,
+            int(weight_mode), _host_ptr(stat), c_void_p(out_ptr), MEM_DEVICE, c_void_p(stream or None)))
+
+    SUMMARY_FIELDS = ("path", "rows", "cols", "k", "predict_ran", "t", "weight_mode", "reserved")
+
+    def debug_last_summary(self) -> dict:
+        """Debug only: the last reduction of the handle (sknnr_debug_last_summary): the summary kernel that ran (0 none,
+        1 registers, 2 wide), rows, the columns it handled, k, and whether the predict kernels ran."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_summary(self.handle, out))
+        return dict(zip(self.SUMMARY_FIELDS, (int(v) for v in out)))
 
     # ---- nodata rows (include/sknnr_hip.h, "nodata rows") -----------------------------------
     def kneighbors_masked_host(self, q, opts: QueryOpts, nodata, fill_index=-1, return_distance=True):
@@ -785,6 +847,12 @@ class QueryStream:
         if nodata.size != cols:
             raise ValueError(f"nodata must hold one value per input column ({cols}), got {nodata.size}")
         check(load().sknnr_stream_set_nodata(self._h, _host_ptr(nodata), int(fill_index)))
+
+    def set_statistics(self, stat):
+        """One statistic code per target (sknnr_stream_set_statistics; only before the first push): the stream's
+        predictions become those summaries of the neighbours."""
+        stat = _c_stat(stat)
+        check(load().sknnr_stream_set_statistics(self._h, _host_ptr(stat), int(stat.size)))
 
     def set_output(self, index_dtype=None, distance_dtype=None, pred_dtype=None, scale=None, offset=None, fill=None):
         """The element types in which the results leave the device (sknnr_stream_set_output; only before the first

@@ -166,6 +166,31 @@ long chunk_rows(int ks, int m_list) {
     return std::max<long>(kRowQuantum, rows / kRowQuantum * kRowQuantum);
 }
 constexpr int kScanMaxKK = 192;
+static_assert(kSummaryMaxK == kScanMaxKK, "the summary kernels follow np_sum up to the largest k of a search");
+// The per-target statistics of one call or stream (summary.hip.h): the columns that are not the mean, as the device table
+// the summary kernels read (columns, then codes), and how many columns stay with the predict kernels.
+struct SummaryPlan {
+    int nc = 0;
+    int n_mean = 0;
+    const int* tab = nullptr;
+};
+// (t) sknnr_statistic codes -> the host image of the table; false: an unknown code, reported in *bad
+bool summary_table(const int32_t* stat, int t, std::vector<int>& tab, int* bad) {
+    std::vector<int> cols, codes;
+    for (int j = 0; j < t; ++j) {
+        if (stat[j] < 0 || stat[j] >= kStatCount) {
+            *bad = j;
+            return false;
+        }
+        if (stat[j] != kStatMean) {
+            cols.push_back(j);
+            codes.push_back(stat[j]);
+        }
+    }
+    tab = cols;
+    tab.insert(tab.end(), codes.begin(), codes.end());
+    return true;
+}
 // Error bound of the split contraction, in units of 2^-24 (|q'| + max|r'|)^2 -- derived in DESIGN.md
 // section 2 from the measured arithmetic of v_mfma_f32_32x32x16_f16 (scripts/microbench/
 // mfma_f16_numerics.hip, profiles/r02_mfma_f16_numerics.txt: per instruction two groups of eight exact
@@ -372,6 +397,13 @@ struct sknnr_index {
     // copies moved, outputs that took the wide path (bit 0 indices, 1 distances, 2 predictions)
     DevBuf<double> s_scale, s_offset;
     int64_t last_narrow[8] = {};
+    // per-target statistics (summary.hip.h).  `summary`: the plan of the call in progress, set and cleared under mtx
+    // (SummaryScope), read by launch_predict; null: every column is the mean.  The device tables of a one-shot call
+    // (c_stat, a workspace buffer behind ev_ws) and of the open stream (s_stat); the record of the last reduction
+    // (sknnr_debug_last_summary).
+    const SummaryPlan* summary = nullptr;
+    DevBuf<int> c_stat, s_stat;
+    int64_t last_summary[8] = {};
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
     // a ring of call records so that several calls of one benchmark step are summed, not only the last.
@@ -2059,6 +2091,16 @@ int run_forest(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
 static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, const double* w, long nq, int k,
                           int mode, double* out, hipStream_t st);
 
+// The plan of the call in progress for as long as the scope lives; the caller holds ix->mtx.
+struct SummaryScope {
+    sknnr_index* ix;
+    const SummaryPlan* before;
+    SummaryScope(sknnr_index* ix_, const SummaryPlan* plan) : ix(ix_), before(ix_->summary) { ix->summary = plan; }
+    ~SummaryScope() { ix->summary = before; }
+    SummaryScope(const SummaryScope&) = delete;
+    SummaryScope& operator=(const SummaryScope&) = delete;
+};
+
 namespace {
 
 // ---- nodata front end (mask.hip.h) --------------------------------------------------------------------------------------
@@ -2272,6 +2314,9 @@ struct HostPipe {
     const double *pred_scale = nullptr, *pred_offset = nullptr;
     int has_pred_fill = 0;
     double pred_fill = 0.0;
+    // per-target statistics (sknnr_stream_set_statistics): the reductions of this pipeline's tiles follow `stat`
+    bool has_stat = false;
+    SummaryPlan stat;
     struct Pending {
         bool live = false;
         long n = 0;
@@ -2486,6 +2531,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
     // the PREVIOUS tile's results travel behind this tile's rows, on the same stream (see pipe_enqueue_d2h)
     if ((rc = pipe_enqueue_d2h(p))) return rc;
     HIP_TRY(hipStreamWaitEvent(ix->st_run, sl.ev_h2d, 0));
+    SummaryScope scope(ix, p.has_stat ? &p.stat : ix->summary);  // (a one-shot call's plan is already in place)
     if (p.nodata_dev) {
         // (distances only where the slot has packed distances to expand from: mask_ensure sizes them by the same rule)
         rc = mask_finish(ix, sl.mask, sl.dev_x.p, n, nv, &p.o, p.fill_index,
@@ -3194,32 +3240,86 @@ static bool weight_mode_ok(int mode, bool explicit_ok) {
     return (base == SKNNR_WEIGHTS_UNIFORM || base == SKNNR_WEIGHTS_DISTANCE) && !(flags & SKNNR_WEIGHTS_F32_WEIGHTS);
 }
 
+// The table of a one-shot call into the handle's c_stat.  The buffer belongs to the workspace: the previous reduction may
+// still read it, so wait for the workspace's last user first.
+static int summary_upload(sknnr_index* ix, const std::vector<int>& tab, SummaryPlan& plan) {
+    plan.nc = (int)tab.size() / 2;
+    plan.n_mean = ix->t - plan.nc;
+    plan.tab = nullptr;
+    if (!plan.nc) return SKNNR_OK;
+    if (ix->ws_busy) HIP_TRY(hipEventSynchronize(ix->ev_ws));
+    HIP_TRY(ix->c_stat.ensure(tab.size()));
+    HIP_TRY(hipMemcpy(ix->c_stat.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    plan.tab = ix->c_stat.p;
+    return SKNNR_OK;
+}
+
+// The reduction of one launch's rows: the predict kernels give every column its mean unless no column wants it, then the
+// summary kernel overwrites the columns of ix->summary (the call's or the stream's statistics; null: all mean).
 static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, const double* w, long nq, int k,
                           int mode, double* out, hipStream_t st) {
-    PredictArgs a{};
-    a.y = ix->y64.p;
-    a.dist = dist;
-    a.idx = idx;
-    a.w = w;
-    a.nq = nq;
-    a.k = k;
-    a.t = ix->t;
-    a.mode = mode & SKNNR_WEIGHTS_BASE_MASK;
-    a.y32 = (mode & SKNNR_WEIGHTS_F32_TARGETS) ? 1 : 0;
-    a.w32 = (mode & SKNNR_WEIGHTS_F32_WEIGHTS) ? 1 : 0;
-    a.out = out;
-    HIP_TRY(launch::predict(a, st));
+    const SummaryPlan* sp = ix->summary;
+    const bool means = !sp || sp->n_mean > 0;
+    if (means) {
+        PredictArgs a{};
+        a.y = ix->y64.p;
+        a.dist = dist;
+        a.idx = idx;
+        a.w = w;
+        a.nq = nq;
+        a.k = k;
+        a.t = ix->t;
+        a.mode = mode & SKNNR_WEIGHTS_BASE_MASK;
+        a.y32 = (mode & SKNNR_WEIGHTS_F32_TARGETS) ? 1 : 0;
+        a.w32 = (mode & SKNNR_WEIGHTS_F32_WEIGHTS) ? 1 : 0;
+        a.out = out;
+        HIP_TRY(launch::predict(a, st));
+    }
+    const int nc = sp ? sp->nc : 0;
+    if (nc) {
+        SummaryArgs a{};
+        a.y = ix->y64.p;
+        a.dist = dist;
+        a.idx = idx;
+        a.w = w;
+        a.nq = nq;
+        a.k = k;
+        a.t = ix->t;
+        a.mode = mode & SKNNR_WEIGHTS_BASE_MASK;
+        a.tab = sp->tab;
+        a.nc = nc;
+        a.out = out;
+        HIP_TRY(launch::summary(a, st));
+    }
+    const int64_t rec[8] = {nc ? (k <= kSummarySmallK ? 1 : 2) : 0, nq, nc, k, means ? 1 : 0, ix->t,
+                            mode & SKNNR_WEIGHTS_BASE_MASK, 0};
+    std::copy(std::begin(rec), std::end(rec), ix->last_summary);
     // the reduction may read the handle's staging buffers: it is now the workspace's last user
     HIP_TRY(hipEventRecord(ix->ev_ws, st));
     ix->ws_busy = true;
     return SKNNR_OK;
 }
 
-extern "C" int sknnr_predict_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w,
-                                            int64_t nq, int32_t k, int32_t mode, double* out_pred, int32_t mem,
-                                            void* stream) {
+// A summary entry's statistics, checked before any device work: stat must be given and hold sknnr_statistic codes.
+static int summary_check(const sknnr_index* ix, const int32_t* stat, std::vector<int>& tab) {
+    if (!stat) return fail(SKNNR_ERR_INVALID, "stat is NULL");
+    int bad = 0;
+    if (!summary_table(stat, ix->t, tab, &bad))
+        return fail(SKNNR_ERR_INVALID, "stat[%d] = %d is no sknnr_statistic", bad, stat[bad]);
+    return SKNNR_OK;
+}
+
+// sknnr_predict_from_neighbors (summarize false) and sknnr_summarize_from_neighbors
+static int reduce_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w, int64_t nq,
+                                 int32_t k, int32_t mode, bool summarize, const int32_t* stat, double* out_pred,
+                                 int32_t mem, void* stream) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
     if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
+    std::vector<int> tab;
+    if (summarize) {
+        const int rc = summary_check(ix, stat, tab);
+        if (rc) return rc;
+    }
     if (nq < 0 || k < 1 || !idx || !out_pred) return fail(SKNNR_ERR_INVALID, "bad argument");
     if (!weight_mode_ok(mode, true)) return fail(SKNNR_ERR_INVALID, "unknown weight mode %d", mode);
     if ((mode & SKNNR_WEIGHTS_BASE_MASK) == SKNNR_WEIGHTS_DISTANCE && !dist)
@@ -3232,6 +3332,12 @@ extern "C" int sknnr_predict_from_neighbors(sknnr_index* ix, const double* dist,
     if (nq == 0) return SKNNR_OK;
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
+    SummaryPlan plan;
+    if (summarize) {
+        const int rc = summary_upload(ix, tab, plan);
+        if (rc) return rc;
+    }
+    SummaryScope scope(ix, summarize ? &plan : nullptr);
     if (mem == SKNNR_MEM_DEVICE)
         return launch_predict(ix, dist, (const long*)idx, w, nq, k, mode, out_pred, (hipStream_t)stream);
     hipStream_t st = nullptr;
@@ -3254,10 +3360,29 @@ extern "C" int sknnr_predict_from_neighbors(sknnr_index* ix, const double* dist,
     return SKNNR_OK;
 }
 
-extern "C" int sknnr_predict(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, double* out_pred,
-                             double* out_dist, int64_t* out_idx, int32_t mem, void* stream) {
+extern "C" int sknnr_predict_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w,
+                                            int64_t nq, int32_t k, int32_t mode, double* out_pred, int32_t mem,
+                                            void* stream) {
+    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, false, nullptr, out_pred, mem, stream);
+}
+
+extern "C" int sknnr_summarize_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w,
+                                              int64_t nq, int32_t k, int32_t mode, const int32_t* stat, double* out,
+                                              int32_t mem, void* stream) {
+    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, true, stat, out, mem, stream);
+}
+
+// sknnr_predict (summarize false) and sknnr_summarize
+static int search_and_reduce(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, bool summarize,
+                             const int32_t* stat, double* out_pred, double* out_dist, int64_t* out_idx, int32_t mem,
+                             void* stream) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
     if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
+    std::vector<int> tab;
+    if (summarize) {
+        const int rc0 = summary_check(ix, stat, tab);
+        if (rc0) return rc0;
+    }
     if (!o) return fail(SKNNR_ERR_INVALID, "opts is NULL");
     if (!out_pred && nq > 0) return fail(SKNNR_ERR_INVALID, "out_pred is NULL");
     if ((o->weight_mode & SKNNR_WEIGHTS_BASE_MASK) == SKNNR_WEIGHTS_EXPLICIT)
@@ -3272,6 +3397,9 @@ extern "C" int sknnr_predict(sknnr_index* ix, const void* q, int64_t nq, const s
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
     const int k = o->n_neighbors;
+    SummaryPlan plan;
+    if (summarize && (rc = summary_upload(ix, tab, plan))) return rc;
+    SummaryScope scope(ix, summarize ? &plan : nullptr);
 
     if (mem == SKNNR_MEM_DEVICE) {
         hipStream_t st = (hipStream_t)stream;
@@ -3295,6 +3423,16 @@ extern "C" int sknnr_predict(sknnr_index* ix, const void* q, int64_t nq, const s
     }
     if (q) return run_host_pipeline(ix, q, nq, o, out_dist, (long*)out_idx, out_pred);
     return run_self_rows(ix, nq, o, out_dist, (long*)out_idx, out_pred);
+}
+
+extern "C" int sknnr_predict(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, double* out_pred,
+                             double* out_dist, int64_t* out_idx, int32_t mem, void* stream) {
+    return search_and_reduce(ix, q, nq, o, false, nullptr, out_pred, out_dist, out_idx, mem, stream);
+}
+
+extern "C" int sknnr_summarize(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, const int32_t* stat,
+                               double* out, double* out_dist, int64_t* out_idx, int32_t mem, void* stream) {
+    return search_and_reduce(ix, q, nq, o, true, stat, out, out_dist, out_idx, mem, stream);
 }
 
 extern "C" int sknnr_predict_masked(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o,
@@ -3342,6 +3480,29 @@ extern "C" int sknnr_stream_set_nodata(sknnr_stream* s, const double* nodata, in
     HIP_TRY(hipMemcpy(p.ix->s_nodata.p, nodata, (size_t)p.d_x * sizeof(double), hipMemcpyHostToDevice));
     p.nodata_dev = p.ix->s_nodata.p;
     p.fill_index = fill_index;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_set_statistics(sknnr_stream* s, const int32_t* stat, int32_t t) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    HostPipe& p = s->pipe;
+    if (!p.want_pred) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
+    if (t != p.t) return fail(SKNNR_ERR_INVALID, "t = %d: the handle has %d targets", t, p.t);
+    std::vector<int> tab;
+    int rc = summary_check(p.ix, stat, tab);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(p.ix->mtx);
+    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_statistics is allowed only before the first push");
+    p.stat = SummaryPlan{};
+    p.stat.nc = (int)tab.size() / 2;
+    p.stat.n_mean = p.t - p.stat.nc;
+    if (p.stat.nc) {
+        HIP_TRY(hipSetDevice(p.ix->device));
+        HIP_TRY(p.ix->s_stat.ensure(tab.size()));
+        HIP_TRY(hipMemcpy(p.ix->s_stat.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+        p.stat.tab = p.ix->s_stat.p;
+    }
+    p.has_stat = p.stat.nc > 0;  // (an all-mean table: the stream enqueues what it did without one)
     return SKNNR_OK;
 }
 
@@ -3595,6 +3756,14 @@ extern "C" int sknnr_debug_last_narrow(const sknnr_index* cix, int64_t out[8]) {
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
     std::copy(std::begin(ix->last_narrow), std::end(ix->last_narrow), out);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_summary(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "bad argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::copy(std::begin(ix->last_summary), std::end(ix->last_summary), out);
     return SKNNR_OK;
 }
 
