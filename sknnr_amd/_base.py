@@ -725,39 +725,19 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         return self._summarize_engine(X, stat, apply_affine=False)
 
     # -- streamed tiles (raster ingestion; REF docs/pages/usage.md:101-128) --------------------
-    def _check_nodata_supported(self, nodata):
-        """The nodata mask runs in front of the device search of a native stream; the paths that answer tile by tile on
-        the host refuse it."""
-        if nodata is None:
-            return
-        if self._numpy_ties():
-            raise NotImplementedError("nodata is not supported under hamming_tie_policy('numpy'): tied rows are chosen "
-                                      "on the host, tile by tile; use the default policy 'lowest_index'")
-        if self._tree_ties():
-            raise NotImplementedError("nodata is not supported under tree_tie_policy('tree'): tied rows are chosen on "
-                                      "the host, tile by tile; use the default policy 'lowest_index'")
-
-    def _check_bands_supported(self):
-        """Band-first tiles are transposed on the device, inside a native stream; the paths that answer tile by tile on
-        the host refuse them."""
-        if self._numpy_ties():
-            raise NotImplementedError("layout='bands' is not supported under hamming_tie_policy('numpy'): tied rows are "
-                                      "chosen on the host, tile by tile; use the default policy 'lowest_index'")
-        if self._tree_ties():
-            raise NotImplementedError("layout='bands' is not supported under tree_tie_policy('tree'): tied rows are "
-                                      "chosen on the host, tile by tile; use the default policy 'lowest_index'")
-
-    def _check_typed_supported(self, output):
-        """Typed outputs are converted on the device, inside a native stream; the paths that answer tile by tile on the
+    def _check_stream_supported(self, feature):
+        """The nodata mask, the band-first transposes and the typed conversions (``feature``: "nodata is", "layout='bands'
+        is", "typed outputs are") run on the device, inside a native stream; the paths that answer tile by tile on the
         host refuse them."""
-        if not output:
-            return
-        if self._numpy_ties():
-            raise NotImplementedError("typed outputs are not supported under hamming_tie_policy('numpy'): tied rows are "
-                                      "chosen on the host, tile by tile; use the default policy 'lowest_index'")
-        if self._tree_ties():
-            raise NotImplementedError("typed outputs are not supported under tree_tie_policy('tree'): tied rows are "
-                                      "chosen on the host, tile by tile; use the default policy 'lowest_index'")
+        for policy, on in (("hamming_tie_policy('numpy')", self._numpy_ties()), ("tree_tie_policy('tree')", self._tree_ties())):
+            if on:
+                raise NotImplementedError(f"{feature} not supported under {policy}: tied rows are chosen on the host, "
+                                          "tile by tile; use the default policy 'lowest_index'")
+
+    @staticmethod
+    def _refuse_callable_weights(feature, how="tile by tile"):
+        raise NotImplementedError(f"{feature} not supported with callable weights: the callable runs on the host between "
+                                  f"the search and the reduction, {how}; use 'uniform' or 'distance'")
 
     def _stream_tiles(self, tiles, validate, k, *, apply_affine, weights, return_distance,
                       use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False, output=None,
@@ -775,7 +755,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
         ``statistic``: int32 codes (:func:`normalize_statistic`), one per target -- the predictions are those summaries
         of the neighbours instead of the mean."""
-        self._check_typed_supported(output)
+        if output:
+            self._check_stream_supported("typed outputs are")
         eng = self.engine_
         want_pred = weights is not None
         t_cols = eng.t
@@ -783,9 +764,10 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         idx_dt = np.dtype(output.get("index_dtype", np.int64))
         dist_dt = np.dtype(output.get("distance_dtype", np.float64))
         pred_dt = np.dtype(output.get("pred_dtype", np.float64))
-        self._check_nodata_supported(nodata)
+        if nodata is not None:
+            self._check_stream_supported("nodata is")
         if bands:
-            self._check_bands_supported()
+            self._check_stream_supported("layout='bands' is")
             widths = {a.shape[1] for a in (out or ()) if a is not None and a.ndim == 2 and a.shape[0] > 1}
             if len(widths) > 1:
                 raise ValueError(f"out arrays must share one number of columns (the stride between planes), got {sorted(widths)}")
@@ -1031,15 +1013,11 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             n_targets = 1 if self._y.ndim == 1 else self._y.shape[1]
             output = normalize_typed_output(*typed, n_targets, nodata is not None)
         if callable(weights) and output:
-            raise NotImplementedError("typed outputs are not supported with callable weights: the callable runs on the "
-                                      "host between the search and the reduction, tile by tile; use 'uniform' or 'distance'")
+            self._refuse_callable_weights("typed outputs are")
         if callable(weights) and bands:
-            raise NotImplementedError("layout='bands' is not supported with callable weights: the callable runs on the "
-                                      "host between the search and the reduction, on row-major neighbours; use "
-                                      "'uniform' or 'distance'")
+            self._refuse_callable_weights("layout='bands' is", "on row-major neighbours")
         if callable(weights) and nodata is not None:
-            raise NotImplementedError("nodata is not supported with callable weights: the callable runs on the host "
-                                      "between the search and the reduction, tile by tile; use 'uniform' or 'distance'")
+            self._refuse_callable_weights("nodata is")
         if callable(weights):  # a Python callable runs between the search and the reduction: tile by tile
             # (the reorder's second key is the row's position in the WHOLE call: carry it from tile to tile)
             preds, row = [], 0

@@ -778,27 +778,40 @@ class QueryStream:
         check(load().sknnr_stream_begin(index.handle, byref(opts), int(self.want_dist), int(self.want_pred),
                                         byref(self._h)))
 
+    def _push(self, native, tile, nq, planes, out_idx, out_dist, out_pred, need_idx):
+        """Push one tile of ``nq`` pixels through ``native`` (a row push, or with ``planes`` a band-first one): the missing
+        outputs are allocated, the given ones validated -- ``(nq, cols)`` rows, or ``(cols, nq)`` planes that share one
+        stride -- and all of them kept alive while the tile may be in the pipeline."""
+        outs, strides = [], set()  # (strides in ELEMENTS of each output's own type: the outputs share the pixel axis, not the byte count)
+        for a, dt, cols, wanted in ((out_idx, self.idx_dtype, self.k, need_idx or not self.want_pred),
+                                    (out_dist, self.dist_dtype, self.k, self.want_dist),
+                                    (out_pred, self.pred_dtype, self._index.t, self.want_pred)):
+            if a is None and wanted:
+                a = np.empty((cols, nq) if planes else (nq, cols), dtype=dt)
+            if a is not None and planes:
+                if a.dtype != dt or a.shape != (cols, nq) or (nq > 1 and a.strides[1] != dt.itemsize):
+                    raise ValueError(f"output arrays must be ({cols}, {nq}) {np.dtype(dt)} with contiguous planes")
+                if cols > 1:  # (a single plane has no stride to speak of)
+                    strides.add(a.strides[0] / dt.itemsize)
+            elif a is not None and (a.dtype != dt or not a.flags.c_contiguous or a.shape != (nq, cols)):
+                raise ValueError(f"output arrays must be C-contiguous ({nq}, {cols}) {np.dtype(dt)}")
+            outs.append(a)
+        if len(strides) > 1 or any(st != int(st) or st < nq for st in strides):
+            raise ValueError("output arrays must share one stride between planes, of at least the tile's pixels")
+        out_idx, out_dist, out_pred = outs
+        stride = (int(strides.pop()) if strides else nq,) if planes else ()
+        check(native(self._h, tile, nq, _host_ptr(out_dist), _host_ptr(out_idx), _host_ptr(out_pred), *stride))
+        self._keep.append(outs)
+        if len(self._keep) > 8:
+            del self._keep[:-8]  # older tiles have left the pipeline (four slots: at most the last four pushes are pending)
+        return out_idx, out_dist, out_pred
+
     def push(self, q, out_idx=None, out_dist=None, out_pred=None, need_idx=True):
         """Answer the rows of ``q``; returns the (idx, dist, pred) arrays that will hold the results
         (the ones passed in, or fresh ones; ``need_idx=False`` with predictions skips the indices)."""
         q = _c_rows(q, self._opts)
-        nq = q.shape[0]
-        if out_idx is None and (need_idx or not self.want_pred):
-            out_idx = np.empty((nq, self.k), dtype=self.idx_dtype)
-        if out_dist is None and self.want_dist:
-            out_dist = np.empty((nq, self.k), dtype=self.dist_dtype)
-        if out_pred is None and self.want_pred:
-            out_pred = np.empty((nq, self._index.t), dtype=self.pred_dtype)
-        for a, dt, cols in ((out_idx, self.idx_dtype, self.k), (out_dist, self.dist_dtype, self.k),
-                            (out_pred, self.pred_dtype, self._index.t)):
-            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or a.shape != (nq, cols)):
-                raise ValueError(f"output arrays must be C-contiguous ({nq}, {cols}) {np.dtype(dt)}")
-        push = load().sknnr_stream_push_typed if self._typed else load().sknnr_stream_push
-        check(push(self._h, _host_ptr(q), nq, _host_ptr(out_dist), _host_ptr(out_idx), _host_ptr(out_pred)))
-        self._keep.append((out_idx, out_dist, out_pred))
-        if len(self._keep) > 8:
-            del self._keep[:-8]  # older tiles have left the pipeline (four slots: at most the last four pushes are pending)
-        return out_idx, out_dist, out_pred
+        native = load().sknnr_stream_push_typed if self._typed else load().sknnr_stream_push
+        return self._push(native, _host_ptr(q), q.shape[0], False, out_idx, out_dist, out_pred, need_idx)
 
     def push_planes(self, bands, out_idx=None, out_dist=None, out_pred=None, need_idx=True):
         """Answer a band-first tile (sknnr_stream_push_planes): ``bands`` is a sequence of 1-D C-contiguous arrays of one
@@ -814,31 +827,9 @@ class QueryStream:
         for b in bands:
             if b.ndim != 1 or b.shape[0] != nq or b.dtype != want or not b.flags.c_contiguous:
                 raise ValueError(f"every band must be a C-contiguous ({nq},) {want} array")
-        if out_idx is None and (need_idx or not self.want_pred):
-            out_idx = np.empty((self.k, nq), dtype=self.idx_dtype)
-        if out_dist is None and self.want_dist:
-            out_dist = np.empty((self.k, nq), dtype=self.dist_dtype)
-        if out_pred is None and self.want_pred:
-            out_pred = np.empty((self._index.t, nq), dtype=self.pred_dtype)
-        strides = set()  # (in ELEMENTS of each output's own type: the outputs share the pixel axis, not the byte count)
-        for a, dt, planes in ((out_idx, self.idx_dtype, self.k), (out_dist, self.dist_dtype, self.k),
-                              (out_pred, self.pred_dtype, self._index.t)):
-            if a is None:
-                continue
-            if a.dtype != dt or a.shape != (planes, nq) or (nq > 1 and a.strides[1] != dt.itemsize):
-                raise ValueError(f"output arrays must be ({planes}, {nq}) {np.dtype(dt)} with contiguous planes")
-            if planes > 1:  # (a single plane has no stride to speak of)
-                strides.add(a.strides[0] / dt.itemsize)
-        if len(strides) > 1 or any(st != int(st) or st < nq for st in strides):
-            raise ValueError("output arrays must share one stride between planes, of at least the tile's pixels")
-        stride = int(strides.pop()) if strides else nq
         ptrs = (c_void_p * cols)(*[b.ctypes.data for b in bands])
-        push = load().sknnr_stream_push_planes_typed if self._typed else load().sknnr_stream_push_planes
-        check(push(self._h, ptrs, nq, _host_ptr(out_dist), _host_ptr(out_idx), _host_ptr(out_pred), stride))
-        self._keep.append((out_idx, out_dist, out_pred))
-        if len(self._keep) > 8:
-            del self._keep[:-8]
-        return out_idx, out_dist, out_pred
+        native = load().sknnr_stream_push_planes_typed if self._typed else load().sknnr_stream_push_planes
+        return self._push(native, ptrs, nq, True, out_idx, out_dist, out_pred, need_idx)
 
     def set_nodata(self, nodata, fill_index=-1):
         """Mask every pushed tile on the device (sknnr_stream_set_nodata; only before the first push)."""

@@ -4,12 +4,30 @@
 // the per-chunk launch sequence  prep -> coarse (MFMA) -> finalize -> exact_scan,
 // staging for host buffers, error reporting.  No CPU path computes results: if a
 // device call fails the function fails.
+#include <cstddef>
+
+// ----------------------------------------------------------------------------------------
+// the outputs of the host pipeline: one lane each
+// ----------------------------------------------------------------------------------------
+// What the host pipeline hands to the caller, in the order the debug records use (bit `1 << lane` of last_narrow's wide mask).
+enum { kLaneIdx = 0, kLaneDist = 1, kLanePred = 2, kLanes = 3 };
+
+// The byte arithmetic of a lane: `cols` columns (k, k, t) of `esz` bytes per element (8 unless the output is typed).  No HIP
+// here: scripts/lane_arithmetic_check.cpp compiles this section alone (SKNNR_LANE_ARITHMETIC_ONLY), under the sanitizers.
+inline size_t lane_bytes(long n, int cols, size_t esz) { return (size_t)n * cols * esz; }               // a tile of n rows
+inline size_t lane_units(long n, int cols, size_t esz) { return (lane_bytes(n, cols, esz) + 7) / 8; }  // ... in 8-byte words
+// Where tile [c0, ...) starts in the caller's array: packed (N, cols) rows, or planes -- there the tile is a segment of
+// every plane, and the address is that of the first plane's.
+inline size_t lane_tile_offset(long c0, int cols, size_t esz, bool planes) { return (size_t)c0 * (planes ? 1 : cols) * esz; }
+
+#ifndef SKNNR_LANE_ARITHMETIC_ONLY
 #include "../../include/sknnr_hip.h"
 
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -216,6 +234,7 @@ constexpr double eps_units2(int ks) { return 12.0 + 2.0 * ks; }
 // the handle
 // ----------------------------------------------------------------------------------------
 constexpr int kHostSlots = 4;  // tiles in flight in the host-buffer pipeline
+using Word = unsigned long long;  // the 8-byte unit of the pipeline's output buffers
 
 // One background host thread that runs posted jobs in order (the host-buffer pipeline's copy-in and copy-out legs:
 // the staging memcpys used to sit in the enqueueing thread, in series with it -- profiles/r02_host_path_probe.txt).
@@ -333,16 +352,17 @@ struct sknnr_index {
     // host-buffer pipeline: pinned staging + device staging, kHostSlots slots; three streams
     struct HostSlot {
         double* pin_x = nullptr;  size_t pin_x_n = 0;
-        double* pin_d = nullptr;  size_t pin_d_n = 0;
-        long* pin_i = nullptr;    size_t pin_i_n = 0;
-        double* pin_p = nullptr;  size_t pin_p_n = 0;
-        DevBuf<double> dev_x, dev_d, dev_p;
-        DevBuf<long> dev_i;
-        // band-first tiles (planes.hip.h): the uploaded planes in front of dev_x, the results as planes behind dev_i / dev_d / dev_p
-        DevBuf<double> dev_xp, dev_dp, dev_pp;
-        DevBuf<long> dev_ip;
-        // typed outputs (narrow.hip.h): the results at the stream's output types, packed rows or planes, in 8-byte units
-        DevBuf<unsigned long long> nar_i, nar_d, nar_p;
+        DevBuf<double> dev_x;
+        DevBuf<double> dev_xp;  // band-first tiles (planes.hip.h): the uploaded planes, in front of dev_x
+        // One output (kLaneIdx / kLaneDist / kLanePred), all in 8-byte words: int64 indices, float64 values, packed narrow elements.
+        struct Lane {
+            Word* pin = nullptr;  size_t pin_n = 0;  // pinned: what the device-to-host copy fills
+            DevBuf<Word> dev;     // (n, cols) as the search / the reduction writes it
+            DevBuf<Word> planes;  // band-first tiles: (cols, n) behind dev
+            DevBuf<Word> nar;     // typed outputs (narrow.hip.h): the stream's output type, packed rows or planes
+            long* i64() const { return (long*)dev.p; }
+            double* f64() const { return (double*)dev.p; }
+        } lane[kLanes];
         hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_d2h = nullptr;
         MaskBufs mask;  // nodata front end of the slot's tile (a pipeline with a mask only)
     } slot[kHostSlots];
@@ -444,11 +464,12 @@ struct sknnr_index {
         status.release();
         idx_stage.release();
         for (auto& sl : slot) {
-            for (void* hp : {(void*)sl.pin_x, (void*)sl.pin_d, (void*)sl.pin_i, (void*)sl.pin_p})
-                if (hp) (void)hipHostFree(hp);
-            sl.dev_x.release(); sl.dev_d.release(); sl.dev_p.release(); sl.dev_i.release();
-            sl.dev_xp.release(); sl.dev_dp.release(); sl.dev_pp.release(); sl.dev_ip.release();
-            sl.nar_i.release(); sl.nar_d.release(); sl.nar_p.release();
+            if (sl.pin_x) (void)hipHostFree(sl.pin_x);
+            sl.dev_x.release(); sl.dev_xp.release();
+            for (auto& ln : sl.lane) {
+                if (ln.pin) (void)hipHostFree(ln.pin);
+                ln.dev.release(); ln.planes.release(); ln.nar.release();
+            }
             for (hipEvent_t e : {sl.ev_h2d, sl.ev_done, sl.ev_d2h})
                 if (e) (void)hipEventDestroy(e);
         }
@@ -2300,29 +2321,33 @@ int ensure_pinned(T*& p, size_t& have, size_t want) {
 struct HostPipe {
     sknnr_index* ix = nullptr;
     sknnr_query_opts o{};        // o.row_offset advances with every submitted tile
-    bool want_dist = false, want_idx = true, want_pred = false;
     int k = 0, t = 0, d_x = 0;
+    // One output (kLaneIdx / kLaneDist / kLanePred) as this pipeline delivers it; pipe_open and sknnr_stream_set_output fill these in.
+    struct Lane {
+        bool want = false;        // the pipeline delivers it (a push may still leave a wanted lane out)
+        bool search_out = false;  // the search writes its device buffer: sized whether the lane is wanted or not
+        int cols = 0;             // k, k, t
+        int kind = kNarrowValue;  // the conversion's source kind (narrow.hip.h)
+        int dtype = 0;            // sknnr_dtype of a typed output (sknnr_stream_set_output), 0 = as computed (int64 / float64)
+        size_t esz = 8;           // bytes of one element
+        // predictions only: the per-target scale / offset of their conversion (device, or null), and their NaN fill
+        const double *scale = nullptr, *offset = nullptr;
+        int has_fill = 0;
+        double fill = 0.0;
+    } lane[kLanes];
+    bool mask_dist = false;  // the masked path is handed the distance buffer: distances leave, or the reduction reads them
     size_t x_esz = sizeof(double);  // bytes per element of the caller's rows (opts->query_dtype)
     // nodata front end: every tile is masked behind its host-to-device copy, and o.row_offset advances by its VALID rows
     const double* nodata_dev = nullptr;  // (d_x) on the device, or null: no mask
     long fill_index = -1;
     long row_offset0 = 0;                // o.row_offset when the pipeline was opened
-    // typed outputs (sknnr_stream_set_output): the sknnr_dtype of each output, 0 = as computed (int64 / float64), and the
-    // bytes of one element; the predictions' per-target scale / offset (device, or null), and their NaN fill
-    int dt_i = 0, dt_d = 0, dt_p = 0;
-    size_t esz_i = 8, esz_d = 8, esz_p = 8;
-    const double *pred_scale = nullptr, *pred_offset = nullptr;
-    int has_pred_fill = 0;
-    double pred_fill = 0.0;
     // per-target statistics (sknnr_stream_set_statistics): the reductions of this pipeline's tiles follow `stat`
     bool has_stat = false;
     SummaryPlan stat;
     struct Pending {
         bool live = false;
         long n = 0;
-        double* od = nullptr;
-        long* oi = nullptr;
-        double* op = nullptr;
+        void* out[kLanes] = {};  // the caller's arrays (the tile's first element; null: not asked for in this push)
         bool planes = false;   // the tile was pushed band-first: its results leave as planes, out_stride elements apart
         long out_stride = 0;
         std::future<int> out_done;  // copy-out job of the slot's tile (w_out)
@@ -2344,16 +2369,24 @@ bool pipe_trace() {
     static const bool v = std::getenv("SKNNR_PIPE_TRACE") != nullptr;
     return v;
 }
+// SKNNR_PIPE_WORKERS=0 (A/B runs): no copy-in look-ahead, and the copy-out jobs run on the calling thread
+bool pipe_workers() {
+    static const bool v = [] { const char* e = std::getenv("SKNNR_PIPE_WORKERS"); return !(e && std::atoi(e) == 0); }();
+    return v;
+}
 
-int pipe_open(HostPipe& p, sknnr_index* ix, const sknnr_query_opts* o, bool want_dist, bool want_idx, bool want_pred) {
+int pipe_open(HostPipe& p, sknnr_index* ix, const sknnr_query_opts* o, bool want_dist, bool want_pred) {
     p = HostPipe{};
     p.ix = ix;
     p.o = *o;
-    p.want_dist = want_dist;
-    p.want_idx = want_idx;
-    p.want_pred = want_pred;
     p.k = o->n_neighbors;
     p.t = ix->t;
+    // The indices are always wanted (so their pinned buffer is sized even for pushes that leave them out), and the search
+    // writes indices and distances whether or not the distances leave.
+    p.lane[kLaneIdx] = {true, true, p.k, kNarrowIndex};  // (want, search_out, cols, kind)
+    p.lane[kLaneDist] = {want_dist, true, p.k, kNarrowValue};
+    p.lane[kLanePred] = {want_pred, false, p.t, kNarrowValue};
+    p.mask_dist = want_dist || want_pred;
     p.d_x = query_cols(ix, o);
     p.x_esz = (size_t)dtype_bytes(o->query_dtype);
     p.row_offset0 = o->row_offset;
@@ -2395,29 +2428,22 @@ int pipe_prepare_slot(HostPipe& p, int b, long n, bool planes = false) {
     auto& sl = ix->slot[b];
     int rc = pipe_drain(p, b);  // the slot's previous tile must have left before its buffers are reused
     if (rc) return rc;
-    const int k = p.k, t = p.t, d_x = p.d_x;
-    const size_t x_f64 = ((size_t)n * d_x * p.x_esz + 7) / 8;  // the tile's rows, in 8-byte units
+    const size_t x_f64 = ((size_t)n * p.d_x * p.x_esz + 7) / 8;  // the tile's rows, in 8-byte units
     if ((rc = ensure_pinned(sl.pin_x, sl.pin_x_n, x_f64))) return rc;
-    // (the outputs leave at their own width: 8-byte units of n * cols * element bytes; n * cols without typed outputs)
-    const size_t u_i = ((size_t)n * k * p.esz_i + 7) / 8, u_d = ((size_t)n * k * p.esz_d + 7) / 8,
-                 u_p = ((size_t)n * t * p.esz_p + 7) / 8;
-    if ((rc = ensure_pinned(sl.pin_i, sl.pin_i_n, u_i))) return rc;
-    if (p.want_dist && (rc = ensure_pinned(sl.pin_d, sl.pin_d_n, u_d))) return rc;
-    if (p.want_pred && (rc = ensure_pinned(sl.pin_p, sl.pin_p_n, u_p))) return rc;
-    if (p.dt_i) HIP_TRY(sl.nar_i.ensure(u_i));
-    if (p.dt_d && p.want_dist) HIP_TRY(sl.nar_d.ensure(u_d));
-    if (p.dt_p && p.want_pred) HIP_TRY(sl.nar_p.ensure(u_p));
     HIP_TRY(sl.dev_x.ensure(x_f64));
-    HIP_TRY(sl.dev_i.ensure((size_t)n * k));
-    HIP_TRY(sl.dev_d.ensure((size_t)n * k));
-    if (p.want_pred) HIP_TRY(sl.dev_p.ensure((size_t)n * t));
-    if (p.nodata_dev && (rc = mask_ensure(sl.mask, n, (size_t)d_x * p.x_esz, k, t, p.want_dist, p.want_pred))) return rc;
-    if (planes) {  // (band-first tiles only: the uploaded planes, and the results as planes)
-        HIP_TRY(sl.dev_xp.ensure(x_f64));
-        if (!p.dt_i) HIP_TRY(sl.dev_ip.ensure((size_t)n * k));
-        if (p.want_dist && !p.dt_d) HIP_TRY(sl.dev_dp.ensure((size_t)n * k));
-        if (p.want_pred && !p.dt_p) HIP_TRY(sl.dev_pp.ensure((size_t)n * t));
+    if (planes) HIP_TRY(sl.dev_xp.ensure(x_f64));  // (band-first tiles only: the uploaded planes)
+    for (int l = 0; l < kLanes; ++l) {
+        const HostPipe::Lane& ln = p.lane[l];
+        auto& sb = sl.lane[l];
+        // (a wanted output leaves at its own width: 8-byte units of n * cols * element bytes; n * cols without a type)
+        const size_t wide = (size_t)n * ln.cols, units = lane_units(n, ln.cols, ln.esz);
+        if (ln.want && (rc = ensure_pinned(sb.pin, sb.pin_n, units))) return rc;
+        if (ln.want || ln.search_out) HIP_TRY(sb.dev.ensure(wide));
+        if (ln.want && ln.dtype) HIP_TRY(sb.nar.ensure(units));
+        if (ln.want && !ln.dtype && planes) HIP_TRY(sb.planes.ensure(wide));  // (the untyped results as planes)
     }
+    if (p.nodata_dev && (rc = mask_ensure(sl.mask, n, (size_t)p.d_x * p.x_esz, p.k, p.t, p.lane[kLaneDist].want, p.lane[kLanePred].want)))
+        return rc;
     return SKNNR_OK;
 }
 
@@ -2435,46 +2461,47 @@ int pipe_enqueue_d2h(HostPipe& p) {
     auto& sl = ix->slot[b];
     auto& pd = p.pending[b];
     const long n = pd.n;
-    const int k = p.k, t = p.t;
-    double* od = pd.od;
-    long* oi = pd.oi;
-    double* op = pd.op;
     static const bool one_stream = [] { const char* e = std::getenv("SKNNR_PIPE_ONE_STREAM"); return !(e && std::atoi(e) == 0); }();
     hipStream_t st = one_stream ? ix->st_h2d : ix->st_d2h;
     HIP_TRY(hipStreamWaitEvent(st, sl.ev_done, 0));
-    const bool planes = pd.planes;  // (then the plane buffers hold the results, packed (k or t, n))
+    const bool planes = pd.planes;  // (then the plane buffers hold the untyped results, packed (k or t, n))
     const long out_stride = pd.out_stride;
-    // (a typed output leaves from its narrow buffer, rows or planes alike, at its own element size)
-    const size_t esz_i = p.esz_i, esz_d = p.esz_d, esz_p = p.esz_p;
-    const void* src_i = p.dt_i ? (const void*)sl.nar_i.p : planes ? (const void*)sl.dev_ip.p : (const void*)sl.dev_i.p;
-    const void* src_d = p.dt_d ? (const void*)sl.nar_d.p : planes ? (const void*)sl.dev_dp.p : (const void*)sl.dev_d.p;
-    const void* src_p = p.dt_p ? (const void*)sl.nar_p.p : planes ? (const void*)sl.dev_pp.p : (const void*)sl.dev_p.p;
-    if (oi) HIP_TRY(hipMemcpyAsync(sl.pin_i, src_i, (size_t)n * k * esz_i, hipMemcpyDeviceToHost, st));
-    if (od) HIP_TRY(hipMemcpyAsync(sl.pin_d, src_d, (size_t)n * k * esz_d, hipMemcpyDeviceToHost, st));
-    if (op) HIP_TRY(hipMemcpyAsync(sl.pin_p, src_p, (size_t)n * t * esz_p, hipMemcpyDeviceToHost, st));
-    ix->last_narrow[5] = (int64_t)((oi ? (size_t)n * k * esz_i : 0) + (od ? (size_t)n * k * esz_d : 0) + (op ? (size_t)n * t * esz_p : 0));
+    struct Leg {  // one requested output on its way out: the caller's array (null: none), the pinned bytes, the lane's shape
+        void* dst;
+        const void* pin;
+        int cols;
+        size_t esz;
+    };
+    std::array<Leg, kLanes> legs{};
+    size_t moved = 0;
+    for (int l = 0; l < kLanes; ++l) {
+        if (!pd.out[l]) continue;
+        const HostPipe::Lane& ln = p.lane[l];
+        const auto& sb = sl.lane[l];
+        // (a typed output leaves from its narrow buffer, rows or planes alike, at its own element size)
+        const void* src = ln.dtype ? sb.nar.p : planes ? sb.planes.p : sb.dev.p;
+        const size_t bytes = lane_bytes(n, ln.cols, ln.esz);
+        HIP_TRY(hipMemcpyAsync(sb.pin, src, bytes, hipMemcpyDeviceToHost, st));
+        moved += bytes;
+        legs[l] = Leg{pd.out[l], sb.pin, ln.cols, ln.esz};
+    }
+    ix->last_narrow[5] = (int64_t)moved;
     HIP_TRY(hipEventRecord(sl.ev_d2h, st));
     // the copy-out leg: wait for the tile's device-to-host copies, then pinned -> the caller's arrays (w_out, in order)
-    static const bool workers = [] { const char* e = std::getenv("SKNNR_PIPE_WORKERS"); return !(e && std::atoi(e) == 0); }();
     {
         const int device = ix->device;
         hipEvent_t ev = sl.ev_d2h;
-        const long* pin_i = sl.pin_i;
-        const double *pin_d = sl.pin_d, *pin_p = sl.pin_p;
         auto job = [=]() -> int {
             if (hipSetDevice(device) != hipSuccess || hipEventSynchronize(ev) != hipSuccess) return SKNNR_ERR_HIP;
-            if (planes) {  // k (or t) contiguous segments of n elements, each to its plane of the caller's array
-                if (oi) unstage_planes(oi, pin_i, k, n, out_stride, esz_i);
-                if (od) unstage_planes(od, pin_d, k, n, out_stride, esz_d);
-                if (op) unstage_planes(op, pin_p, t, n, out_stride, esz_p);
-                return SKNNR_OK;
+            for (const Leg& g : legs) {
+                if (!g.dst) continue;
+                // (planes: k (or t) contiguous segments of n elements, each to its plane of the caller's array)
+                if (planes) unstage_planes(g.dst, g.pin, g.cols, n, out_stride, g.esz);
+                else parallel_copy(g.dst, g.pin, lane_bytes(n, g.cols, g.esz));
             }
-            if (oi) parallel_copy(oi, pin_i, (size_t)n * k * esz_i);
-            if (od) parallel_copy(od, pin_d, (size_t)n * k * esz_d);
-            if (op) parallel_copy(op, pin_p, (size_t)n * t * esz_p);
             return SKNNR_OK;
         };
-        if (workers) {
+        if (pipe_workers()) {
             pd.out_done = ix->w_out->post(job);
         } else {  // (A/B: the round-2 behaviour -- the copy runs on this thread when the slot is drained)
             std::packaged_task<int()> task(job);
@@ -2489,14 +2516,19 @@ int pipe_enqueue_d2h(HostPipe& p) {
 // q_next / n_next: the tile the same call will submit next (or null): its rows are staged into the next slot's pinned
 // buffer by the copy-in worker while this tile is enqueued and the caller waits for older results.
 // planes (or null): the tile is band-first -- elements [p_off, p_off + n) of each of the d_x planes; q / q_next are then
-// the first band's segments (they name the tile for the look-ahead), and od / oi / op the first output plane's, with
+// the first band's segments (they name the tile for the look-ahead), and out[] the first output plane's, with
 // out_stride elements between planes.  `planes` must stay valid until the next tile is submitted or the pipeline flushed.
-int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double* op, const void* q_next = nullptr,
+// out[l]: where lane l's results of this tile go, in the lane's own element type (null: not asked for).
+int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], const void* q_next = nullptr,
                 long n_next = 0, const void* const* planes = nullptr, long p_off = 0, long out_stride = 0) {
     sknnr_index* ix = p.ix;
     const int b = p.slot_of;
     p.slot_of = (p.slot_of + 1) % kHostSlots;
     auto& sl = ix->slot[b];
+    const auto& idx = sl.lane[kLaneIdx];
+    const auto& dist = sl.lane[kLaneDist];
+    const auto& pred = sl.lane[kLanePred];
+    const bool want_pred = p.lane[kLanePred].want;
     const int k = p.k, d_x = p.d_x;
     int rc;
     const double t_in = now_ms();
@@ -2534,15 +2566,14 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
     SummaryScope scope(ix, p.has_stat ? &p.stat : ix->summary);  // (a one-shot call's plan is already in place)
     if (p.nodata_dev) {
         // (distances only where the slot has packed distances to expand from: mask_ensure sizes them by the same rule)
-        rc = mask_finish(ix, sl.mask, sl.dev_x.p, n, nv, &p.o, p.fill_index,
-                         p.want_dist || p.want_pred ? sl.dev_d.p : nullptr, sl.dev_i.p,
-                         p.want_pred ? sl.dev_p.p : nullptr, p.o.row_offset - p.row_offset0, ix->st_run);
+        rc = mask_finish(ix, sl.mask, sl.dev_x.p, n, nv, &p.o, p.fill_index, p.mask_dist ? dist.f64() : nullptr, idx.i64(),
+                         want_pred ? pred.f64() : nullptr, p.o.row_offset - p.row_offset0, ix->st_run);
         if (rc) return rc;
     } else {
-        rc = run_device(ix, sl.dev_x.p, n, &p.o, sl.dev_d.p, sl.dev_i.p, ix->st_run);
+        rc = run_device(ix, sl.dev_x.p, n, &p.o, dist.f64(), idx.i64(), ix->st_run);
         if (rc) return rc;
-        if (p.want_pred) {
-            rc = launch_predict(ix, sl.dev_d.p, sl.dev_i.p, nullptr, n, k, p.o.weight_mode, sl.dev_p.p, ix->st_run);
+        if (want_pred) {
+            rc = launch_predict(ix, dist.f64(), idx.i64(), nullptr, n, k, p.o.weight_mode, pred.f64(), ix->st_run);
             if (rc) return rc;
         }
     }
@@ -2550,33 +2581,26 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
     // (and, band-first, transposed in the same pass) into its narrow buffer; an untyped band-first one is transposed; an
     // untyped row output leaves from where it was computed, with no kernel here.
     int planes_out = 0, wide_mask = 0, narrowed = 0;
-    auto emit = [&](bool want, int dt, int kind, const void* rows, void* nar, void* as_planes, int cols, int bit) -> int {
-        if (!want) return SKNNR_OK;
-        if (dt) {
-            NarrowArgs na{rows, nar, n, cols, planes ? n : 0, nullptr, nullptr, 0, 0.0};
-            if (bit == 4) {
-                na.scale = p.pred_scale;
-                na.offset = p.pred_offset;
-                na.has_fill = p.has_pred_fill;
-                na.fill = p.pred_fill;
-            }
-            const bool wide = narrow_wide_ok(rows, nar, launch::narrow_dst_bytes(kind, dt), n, cols, na.stride);
-            HIP_TRY(launch::narrow(na, kind, dt, wide, ix->st_run));
+    for (int l = 0; l < kLanes; ++l) {
+        if (!out[l]) continue;
+        const HostPipe::Lane& ln = p.lane[l];
+        const auto& sb = sl.lane[l];
+        if (ln.dtype) {
+            NarrowArgs na{sb.dev.p, sb.nar.p, n, ln.cols, planes ? n : 0, ln.scale, ln.offset, ln.has_fill, ln.fill};
+            const bool wide = narrow_wide_ok(na.src, na.dst, launch::narrow_dst_bytes(ln.kind, ln.dtype), n, ln.cols, na.stride);
+            HIP_TRY(launch::narrow(na, ln.kind, ln.dtype, wide, ix->st_run));
             narrowed = 1;
-            if (wide) wide_mask |= bit;
-            if (planes) planes_out += cols;
+            if (wide) wide_mask |= 1 << l;
+            if (planes) planes_out += ln.cols;
         } else if (planes) {
-            PlanesArgs pa{rows, as_planes, n, cols, n};
+            PlanesArgs pa{sb.dev.p, sb.planes.p, n, ln.cols, n};
             HIP_TRY(launch::rows_to_planes(pa, ix->st_run));
-            planes_out += cols;
+            planes_out += ln.cols;
         }
-        return SKNNR_OK;
-    };
-    if ((rc = emit(oi != nullptr, p.dt_i, kNarrowIndex, sl.dev_i.p, sl.nar_i.p, sl.dev_ip.p, k, 1))) return rc;
-    if ((rc = emit(od != nullptr, p.dt_d, kNarrowValue, sl.dev_d.p, sl.nar_d.p, sl.dev_dp.p, k, 2))) return rc;
-    if ((rc = emit(op != nullptr, p.dt_p, kNarrowValue, sl.dev_p.p, sl.nar_p.p, sl.dev_pp.p, p.t, 4))) return rc;
+    }
     {
-        const int64_t rec[8] = {narrowed, n, p.dt_i, p.dt_d, p.dt_p, 0, wide_mask, 0};  // ([5]: pipe_enqueue_d2h)
+        const int64_t rec[8] = {narrowed, n, p.lane[kLaneIdx].dtype, p.lane[kLaneDist].dtype, p.lane[kLanePred].dtype, 0,
+                                wide_mask, 0};  // ([5]: pipe_enqueue_d2h)
         std::copy(std::begin(rec), std::end(rec), ix->last_narrow);
     }
     {
@@ -2588,16 +2612,13 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
     auto& pd = p.pending[b];
     pd.live = true;
     pd.n = n;
-    pd.od = od;
-    pd.oi = oi;
-    pd.op = op;
+    std::copy(out, out + kLanes, pd.out);
     pd.planes = planes != nullptr;
     pd.out_stride = out_stride;
     p.d2h_slot = b;  // its device-to-host copies are enqueued behind the next tile's rows, or by the flush
     p.o.row_offset += nv;
     p.ms_enqueue += now_ms() - t_enq;
-    static const bool workers = [] { const char* e = std::getenv("SKNNR_PIPE_WORKERS"); return !(e && std::atoi(e) == 0); }();
-    if (workers && q_next && n_next > 0) {
+    if (pipe_workers() && q_next && n_next > 0) {
         // the copy-in leg of the next tile (w_in): its slot is drained and sized here, on this thread
         const int b2 = p.slot_of;
         if ((rc = pipe_prepare_slot(p, b2, n_next, planes != nullptr))) return rc;
@@ -2618,13 +2639,12 @@ int pipe_submit(HostPipe& p, const void* q, long n, double* od, long* oi, double
 // the first tile's staging copy and host-to-device transfer (7 ms for a 1M-row tile) with nothing to do, so the first
 // tiles are an eighth, a quarter and a half of the regular size.
 // planes (or null): a band-first push -- q_ is ignored, a tile [c0, c1) is that segment of every band, and its results go
-// to od / oi / op + j * out_stride + c0 for output plane j.
-int pipe_submit_rows(HostPipe& p, const void* q_, long nq, double* od, long* oi, double* op,
-                     const void* const* planes = nullptr, long out_stride = 0) {
+// to out[l] + j * out_stride + c0 (in elements of lane l) for output plane j.
+int pipe_submit_rows(HostPipe& p, const void* q_, long nq, void* const out[kLanes], const void* const* planes = nullptr,
+                     long out_stride = 0) {
     const char* q = planes ? (const char*)planes[0] : (const char*)q_;
     // (bytes between the tiles of q: a band-first tile is named by the first band's segment)
     const size_t row_bytes = planes ? p.x_esz : (size_t)p.d_x * p.x_esz;
-    const long ok = planes ? 1 : p.k, ot = planes ? 1 : p.t;  // output elements per row between tiles
     const long cap = host_chunk_rows();
     bool idle = p.d2h_slot < 0;
     for (const auto& pd : p.pending) idle = idle && !pd.live;
@@ -2645,11 +2665,11 @@ int pipe_submit_rows(HostPipe& p, const void* q_, long nq, double* od, long* oi,
     for (size_t i = 0; i < cuts.size(); ++i) {
         const long c1 = cuts[i], n = c1 - c0;
         const long n_next = i + 1 < cuts.size() ? cuts[i + 1] - c1 : 0;
-        // (the output pointers are addresses of elements of the stream's output types: advanced in bytes)
-        int rc = pipe_submit(p, q + c0 * row_bytes, n, od ? (double*)((char*)od + c0 * ok * p.esz_d) : nullptr,
-                             oi ? (long*)((char*)oi + c0 * ok * p.esz_i) : nullptr,
-                             op ? (double*)((char*)op + c0 * ot * p.esz_p) : nullptr,
-                             n_next ? q + c1 * row_bytes : nullptr, n_next, planes, c0, out_stride);
+        void* tile_out[kLanes];
+        for (int l = 0; l < kLanes; ++l)
+            tile_out[l] = out[l] ? (char*)out[l] + lane_tile_offset(c0, p.lane[l].cols, p.lane[l].esz, planes != nullptr) : nullptr;
+        int rc = pipe_submit(p, q + c0 * row_bytes, n, tile_out, n_next ? q + c1 * row_bytes : nullptr, n_next, planes, c0,
+                             out_stride);
         if (rc) return rc;
         c0 = c1;
     }
@@ -2698,6 +2718,16 @@ void pipe_abort(HostPipe& p) {
     }
 }
 
+// The way out of a failed submit or flush: the error's message survives the clean-up, and nothing of the failed call is
+// still in flight on the slots when the caller hears of it.
+int pipe_fail(HostPipe& p, int rc) {
+    const std::string msg = g_last_error;
+    pipe_abort(p);
+    (void)hipDeviceSynchronize();
+    g_last_error = msg;
+    return rc;
+}
+
 // Fresh output arrays (numpy's np.empty) are untouched memory: the first write to every page is a fault, and the
 // copy-out leg would take them one by one in the middle of the pipeline.  MADV_POPULATE_WRITE (Linux >= 5.14) makes the
 // pages present and writable without changing what they hold, so it may run beside the copies; a few threads, because
@@ -2723,12 +2753,12 @@ struct Prefault {
 };
 
 // nodata (host, one value per column of q) / fill_index / out_n_valid: the masked call; nodata == null: no mask
-int run_host_pipeline(sknnr_index* ix, const void* q, long nq, const sknnr_query_opts* o, double* out_dist,
-                      long* out_idx, double* out_pred, const double* nodata = nullptr, long fill_index = -1,
-                      int64_t* out_n_valid = nullptr) {
+int run_host_pipeline(sknnr_index* ix, const void* q, long nq, const sknnr_query_opts* o, void* out_dist, void* out_idx,
+                      void* out_pred, const double* nodata = nullptr, long fill_index = -1, int64_t* out_n_valid = nullptr) {
     if (ix->stream_open) return fail(SKNNR_ERR_INVALID, "a query stream is open on this handle: end it first");
+    void* const out[kLanes] = {out_idx, out_dist, out_pred};  // (lane order)
     HostPipe p;
-    int rc = pipe_open(p, ix, o, out_dist != nullptr, true, out_pred != nullptr);
+    int rc = pipe_open(p, ix, o, out_dist != nullptr, out_pred != nullptr);
     if (!rc && nodata) {
         HIP_TRY(hipDeviceSynchronize());  // (m_nodata belongs to the workspace)
         HIP_TRY(ix->m_nodata.ensure((size_t)p.d_x));
@@ -2738,18 +2768,11 @@ int run_host_pipeline(sknnr_index* ix, const void* q, long nq, const sknnr_query
     }
     Prefault pf;  // (joined when the call returns)
     if (!rc && std::getenv("SKNNR_PREFAULT")) {  // (measured: 96 ms without, 115 ms with -- the populate threads take bandwidth the copies need)
-        pf.add(out_idx, (size_t)nq * o->n_neighbors * sizeof(long));
-        pf.add(out_dist, (size_t)nq * o->n_neighbors * sizeof(double));
-        pf.add(out_pred, (size_t)nq * ix->t * sizeof(double));
+        for (int l = 0; l < kLanes; ++l) pf.add(out[l], lane_bytes(nq, p.lane[l].cols, p.lane[l].esz));
     }
-    if (!rc) rc = pipe_submit_rows(p, q, nq, out_dist, out_idx, out_pred);
+    if (!rc) rc = pipe_submit_rows(p, q, nq, out);
     if (!rc) rc = pipe_flush(p);
-    if (rc) {
-        const std::string msg = g_last_error;
-        pipe_abort(p);
-        (void)hipDeviceSynchronize();  // nothing of a failed call may still be in flight on the slots
-        g_last_error = msg;
-    }
+    if (rc) pipe_fail(p, rc);
     if (out_n_valid) *out_n_valid = p.o.row_offset - p.row_offset0;
     return rc;
 }
@@ -2837,7 +2860,7 @@ extern "C" int sknnr_kneighbors(sknnr_index* ix, const void* q, int64_t nq, cons
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
     if (mem == SKNNR_MEM_DEVICE) return run_device(ix, q, nq, o, out_dist, (long*)out_idx, (hipStream_t)stream);
-    if (q) return run_host_pipeline(ix, q, nq, o, out_dist, (long*)out_idx, nullptr);
+    if (q) return run_host_pipeline(ix, q, nq, o, out_dist, out_idx, nullptr);
     return run_self_rows(ix, nq, o, out_dist, (long*)out_idx, nullptr);
 }
 
@@ -2994,7 +3017,7 @@ extern "C" int sknnr_kneighbors_masked(sknnr_index* ix, const void* q, int64_t n
     HIP_TRY(hipSetDevice(ix->device));
     if (mem == SKNNR_MEM_DEVICE)
         return run_device_masked(ix, q, nq, o, nodata, fill_index, out_dist, (long*)out_idx, nullptr, (hipStream_t)stream, out_n_valid);
-    return run_host_pipeline(ix, q, nq, o, out_dist, (long*)out_idx, nullptr, nodata, fill_index, out_n_valid);
+    return run_host_pipeline(ix, q, nq, o, out_dist, out_idx, nullptr, nodata, fill_index, out_n_valid);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -3421,7 +3444,7 @@ static int search_and_reduce(sknnr_index* ix, const void* q, int64_t nq, const s
         if (rc) return rc;
         return launch_predict(ix, dd, di, nullptr, nq, k, o->weight_mode, out_pred, st);
     }
-    if (q) return run_host_pipeline(ix, q, nq, o, out_dist, (long*)out_idx, out_pred);
+    if (q) return run_host_pipeline(ix, q, nq, o, out_dist, out_idx, out_pred);
     return run_self_rows(ix, nq, o, out_dist, (long*)out_idx, out_pred);
 }
 
@@ -3456,7 +3479,7 @@ extern "C" int sknnr_predict_masked(sknnr_index* ix, const void* q, int64_t nq, 
     HIP_TRY(hipSetDevice(ix->device));
     if (mem == SKNNR_MEM_DEVICE)
         return run_device_masked(ix, q, nq, o, nodata, fill_index, out_dist, (long*)out_idx, out_pred, (hipStream_t)stream, out_n_valid);
-    return run_host_pipeline(ix, q, nq, o, out_dist, (long*)out_idx, out_pred, nodata, fill_index, out_n_valid);
+    return run_host_pipeline(ix, q, nq, o, out_dist, out_idx, out_pred, nodata, fill_index, out_n_valid);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -3486,7 +3509,7 @@ extern "C" int sknnr_stream_set_nodata(sknnr_stream* s, const double* nodata, in
 extern "C" int sknnr_stream_set_statistics(sknnr_stream* s, const int32_t* stat, int32_t t) {
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     HostPipe& p = s->pipe;
-    if (!p.want_pred) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
+    if (!p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
     if (t != p.t) return fail(SKNNR_ERR_INVALID, "t = %d: the handle has %d targets", t, p.t);
     std::vector<int> tab;
     int rc = summary_check(p.ix, stat, tab);
@@ -3522,28 +3545,28 @@ extern "C" int sknnr_stream_set_output(sknnr_stream* s, int32_t idx_dtype, int32
     if (has_pred_fill && !narrow_fill_ok(pred_dtype, pred_fill))
         return fail(SKNNR_ERR_INVALID, "pred_fill = %.17g is not representable in pred_dtype %d", pred_fill, pred_dtype);
     HostPipe& p = s->pipe;
-    if (dist_dtype && !p.want_dist) return fail(SKNNR_ERR_INVALID, "the stream was opened without distances");
-    if (pred_dtype && !p.want_pred) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
+    if (dist_dtype && !p.lane[kLaneDist].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without distances");
+    if (pred_dtype && !p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
     std::lock_guard<std::mutex> lock(p.ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_output is allowed only before the first push");
-    p.pred_scale = p.pred_offset = nullptr;
+    HostPipe::Lane& pl = p.lane[kLanePred];
+    pl.scale = pl.offset = nullptr;
     if (pred_scale) {
         HIP_TRY(hipSetDevice(p.ix->device));
         HIP_TRY(p.ix->s_scale.ensure((size_t)p.t));
         HIP_TRY(p.ix->s_offset.ensure((size_t)p.t));
         HIP_TRY(hipMemcpy(p.ix->s_scale.p, pred_scale, (size_t)p.t * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(p.ix->s_offset.p, pred_offset, (size_t)p.t * sizeof(double), hipMemcpyHostToDevice));
-        p.pred_scale = p.ix->s_scale.p;
-        p.pred_offset = p.ix->s_offset.p;
+        pl.scale = p.ix->s_scale.p;
+        pl.offset = p.ix->s_offset.p;
     }
-    p.dt_i = idx_dtype;
-    p.dt_d = dist_dtype;
-    p.dt_p = pred_dtype;
-    p.esz_i = (size_t)dtype_bytes(idx_dtype);
-    p.esz_d = (size_t)dtype_bytes(dist_dtype);
-    p.esz_p = (size_t)dtype_bytes(pred_dtype);
-    p.has_pred_fill = has_pred_fill != 0;
-    p.pred_fill = pred_fill;
+    const int32_t dtype[kLanes] = {idx_dtype, dist_dtype, pred_dtype};  // (lane order)
+    for (int l = 0; l < kLanes; ++l) {
+        p.lane[l].dtype = dtype[l];
+        p.lane[l].esz = (size_t)dtype_bytes(dtype[l]);
+    }
+    pl.has_fill = has_pred_fill != 0;
+    pl.fill = pred_fill;
     return SKNNR_OK;
 }
 
@@ -3573,7 +3596,7 @@ extern "C" int sknnr_stream_begin(sknnr_index* ix, const sknnr_query_opts* o, in
     HIP_TRY(hipSetDevice(ix->device));
     sknnr_stream* s = new (std::nothrow) sknnr_stream();
     if (!s) return fail(SKNNR_ERR_INVALID, "out of host memory");
-    rc = pipe_open(s->pipe, ix, o, want_dist != 0, true, want_pred != 0);
+    rc = pipe_open(s->pipe, ix, o, want_dist != 0, want_pred != 0);
     if (rc) {
         delete s;
         return rc;
@@ -3583,37 +3606,40 @@ extern "C" int sknnr_stream_begin(sknnr_index* ix, const sknnr_query_opts* o, in
     return SKNNR_OK;
 }
 
-static bool stream_typed(const sknnr_stream* s) { return s->pipe.dt_i || s->pipe.dt_d || s->pipe.dt_p; }
+static bool stream_typed(const sknnr_stream* s) {
+    for (const auto& ln : s->pipe.lane)
+        if (ln.dtype) return true;
+    return false;
+}
 static const char* const kTypedStreamMsg =
     "the stream has typed outputs (sknnr_stream_set_output): use sknnr_stream_push_typed / sknnr_stream_push_planes_typed";
 
-extern "C" int sknnr_stream_push_typed(sknnr_stream* s, const void* q, int64_t nq, void* out_dist_, void* out_idx_,
-                                       void* out_pred_) {
-    // (from here on the outputs are addresses only: their element types are the stream's, see pipe_enqueue_d2h)
-    double* out_dist = (double*)out_dist_;
-    int64_t* out_idx = (int64_t*)out_idx_;
-    double* out_pred = (double*)out_pred_;
+// The body of every push: nq rows at q, or (planes non-null) nq pixels of every band; outs[l] is where lane l's results go
+// (null: not asked for), in elements of the stream's type for that lane, band-first with out_stride elements between planes.
+// The entry points check what is theirs alone and leave s and nq to this function.
+static int stream_push(sknnr_stream* s, const void* q, const void* const* planes, int64_t nq, void* const outs[kLanes],
+                       int64_t out_stride) {
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
     if (nq == 0) return SKNNR_OK;
-    if (!q) return fail(SKNNR_ERR_INVALID, "q is NULL");
     HostPipe& p = s->pipe;
-    if (!out_idx && !out_pred) return fail(SKNNR_ERR_INVALID, "a push needs out_idx or out_pred");
-    if (out_dist && !p.want_dist) return fail(SKNNR_ERR_INVALID, "the stream was opened without distances");
-    if (out_pred && !p.want_pred) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
+    if (!outs[kLaneIdx] && !outs[kLanePred]) return fail(SKNNR_ERR_INVALID, "a push needs out_idx or out_pred");
+    if (outs[kLaneDist] && !p.lane[kLaneDist].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without distances");
+    if (outs[kLanePred] && !p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
     std::lock_guard<std::mutex> lock(p.ix->mtx);
     HIP_TRY(hipSetDevice(p.ix->device));
     s->pushed = true;
-    int rc = pipe_submit_rows(p, q, nq, out_dist, (long*)out_idx, out_pred);
-    if (rc) {
-        const std::string msg = g_last_error;
-        pipe_abort(p);
-        (void)hipDeviceSynchronize();
-        g_last_error = msg;
-        return rc;
-    }
+    const int rc = pipe_submit_rows(p, q, nq, outs, planes, out_stride);
+    if (rc) return pipe_fail(p, rc);
     s->rows_pushed += nq;
     return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_push_typed(sknnr_stream* s, const void* q, int64_t nq, void* out_dist, void* out_idx,
+                                       void* out_pred) {
+    if (s && nq > 0 && !q) return fail(SKNNR_ERR_INVALID, "q is NULL");
+    void* const outs[kLanes] = {out_idx, out_dist, out_pred};  // (lane order)
+    return stream_push(s, q, nullptr, nq, outs, 0);
 }
 
 extern "C" int sknnr_stream_push(sknnr_stream* s, const void* q, int64_t nq, double* out_dist, int64_t* out_idx,
@@ -3622,36 +3648,18 @@ extern "C" int sknnr_stream_push(sknnr_stream* s, const void* q, int64_t nq, dou
     return sknnr_stream_push_typed(s, q, nq, out_dist, out_idx, out_pred);
 }
 
-extern "C" int sknnr_stream_push_planes_typed(sknnr_stream* s, const void* const* planes, int64_t nq, void* out_dist_,
-                                              void* out_idx_, void* out_pred_, int64_t out_stride) {
-    double* out_dist = (double*)out_dist_;
-    int64_t* out_idx = (int64_t*)out_idx_;
-    double* out_pred = (double*)out_pred_;
-    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
-    if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
-    if (nq == 0) return SKNNR_OK;
-    if (!planes) return fail(SKNNR_ERR_INVALID, "planes is NULL");
-    HostPipe& p = s->pipe;
-    for (int j = 0; j < p.d_x; ++j)
-        if (!planes[j]) return fail(SKNNR_ERR_INVALID, "planes[%d] is NULL", j);
-    if (!out_idx && !out_pred) return fail(SKNNR_ERR_INVALID, "a push needs out_idx or out_pred");
-    if (out_dist && !p.want_dist) return fail(SKNNR_ERR_INVALID, "the stream was opened without distances");
-    if (out_pred && !p.want_pred) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
-    if (out_stride < nq) return fail(SKNNR_ERR_INVALID, "out_stride (%lld) is below nq (%lld)", (long long)out_stride, (long long)nq);
-    if (p.d_x > kMaskMaxCols) return fail(SKNNR_ERR_UNSUPPORTED, "more than %d input columns in a band-first push", kMaskMaxCols);
-    std::lock_guard<std::mutex> lock(p.ix->mtx);
-    HIP_TRY(hipSetDevice(p.ix->device));
-    s->pushed = true;
-    int rc = pipe_submit_rows(p, nullptr, nq, out_dist, (long*)out_idx, out_pred, planes, out_stride);
-    if (rc) {
-        const std::string msg = g_last_error;
-        pipe_abort(p);
-        (void)hipDeviceSynchronize();
-        g_last_error = msg;
-        return rc;
+extern "C" int sknnr_stream_push_planes_typed(sknnr_stream* s, const void* const* planes, int64_t nq, void* out_dist,
+                                              void* out_idx, void* out_pred, int64_t out_stride) {
+    if (s && nq > 0) {
+        if (!planes) return fail(SKNNR_ERR_INVALID, "planes is NULL");
+        const int d_x = s->pipe.d_x;
+        for (int j = 0; j < d_x; ++j)
+            if (!planes[j]) return fail(SKNNR_ERR_INVALID, "planes[%d] is NULL", j);
+        if (out_stride < nq) return fail(SKNNR_ERR_INVALID, "out_stride (%lld) is below nq (%lld)", (long long)out_stride, (long long)nq);
+        if (d_x > kMaskMaxCols) return fail(SKNNR_ERR_UNSUPPORTED, "more than %d input columns in a band-first push", kMaskMaxCols);
     }
-    s->rows_pushed += nq;
-    return SKNNR_OK;
+    void* const outs[kLanes] = {out_idx, out_dist, out_pred};  // (lane order)
+    return stream_push(s, nullptr, planes, nq, outs, out_stride);
 }
 
 extern "C" int sknnr_stream_push_planes(sknnr_stream* s, const void* const* planes, int64_t nq, double* out_dist,
@@ -4008,3 +4016,5 @@ extern "C" int sknnr_debug_image_constants(const sknnr_index* cix, double* mu, d
     }
     return SKNNR_OK;
 }
+
+#endif  // SKNNR_LANE_ARITHMETIC_ONLY

@@ -337,3 +337,107 @@ def test_parent_path_is_untouched(E):
     want_d, want_i = est.kneighbors(x[valid].astype(np.float64))
     np.testing.assert_array_equal(idx[valid], want_i)
     np.testing.assert_array_equal(dist[valid], want_d)
+
+
+_ALL_LANES_CHILD = r"""
+import sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+import numpy as np
+import torch
+import sknnr_amd
+import _narrow as NR
+import test_raster_layout_gpu as RL
+K, T, D, N_REF, NODATA = 5, 3, 7, 400, 5
+rng = np.random.default_rng(21)
+y = np.stack([rng.standard_normal(N_REF) * 50.0 + 100.0, rng.integers(0, 5, size=N_REF) * 40.0 + 3.0,
+              rng.random(N_REF) * 200.0], axis=1)
+est = sknnr_amd.RawKNNRegressor(n_neighbors=K, weights="distance").fit(RL.lattice(N_REF, D, 107).astype(np.uint8), y)
+sizes = (1, 300, 1024, 2500, 7000)  # (7,000 pixels: seven tiles of at most 1,024 through the four slots)
+bands, rows = RL.band_tiles(seed=30, sizes=sizes)
+total = sum(sizes)
+X = np.concatenate(rows).astype(np.float64)
+valid = ~(X == NODATA).any(axis=1)
+ends = np.cumsum(sizes)
+partly = [0 < valid[e - n:e].sum() < n for n, e in zip(sizes, ends)]
+assert sum(partly) >= 3 and not all(partly), partly
+# the yardsticks: untiled float64 calls on device tensors (they do not pass through the host pipeline)
+dev = lambda a: torch.as_tensor(a, device="cuda")
+host = lambda a: a.cpu().numpy()
+stat = ["mean", "mode", "max"]
+d_v, i_v = (host(a) for a in est.kneighbors(dev(X[valid])))
+want_d, want_i, want_s = np.full((total, K), np.nan), np.full((total, K), -7, dtype=np.int64), np.full((total, T), np.nan)
+want_d[valid], want_i[valid], want_s[valid] = d_v, i_v, host(est.summarize(dev(X[valid]), stat))
+all_d, all_i = (host(a) for a in est.kneighbors(dev(X)))
+all_p = host(est.predict(dev(X)))
+index = est.engine_._index
+
+# (a) neighbours: band-first, masked, int32 / float32, into the caller's arrays
+row_d, row_i = est.kneighbors_chunks(iter([r.astype(np.float64) for r in rows]), nodata=NODATA, fill_index=-7)
+np.testing.assert_array_equal(row_i, want_i)
+np.testing.assert_array_equal(row_d, want_d)
+out_d, out_i = np.full((K, total), 9, dtype=np.float32), np.full((K, total), 9, dtype=np.int32)
+est.kneighbors_chunks(iter(bands), layout="bands", nodata=NODATA, fill_index=-7, index_dtype=np.int32,
+                      distance_dtype=np.float32, out=(out_d, out_i))
+np.testing.assert_array_equal(out_i, NR.narrow_indices(want_i).T)
+np.testing.assert_array_equal(out_d, NR.narrow_values(want_d, np.float32).T)
+assert (out_i[:, ~valid] == -7).all() and np.isnan(out_d[:, ~valid]).all() and not np.isnan(out_d[:, valid]).any()
+rec = index.debug_last_narrow()
+assert rec["ran"] == 1 and rec["rows"] <= 1024 and (rec["idx_dtype"], rec["dist_dtype"], rec["pred_dtype"]) == (5, 1, 0), rec
+assert rec["d2h_bytes"] == rec["rows"] * K * (4 + 4), rec
+
+# (b) summaries: band-first, masked, int16 with a scale and an offset per target
+scale, offset = np.array([10.0, 1.0, 0.25]), np.array([0.5, -3.0, 100.0])
+out_p = np.zeros((T, total), dtype=np.int16)
+est.predict_chunks(iter(bands), layout="bands", nodata=NODATA, out=out_p, out_dtype=np.int16, scale=scale, offset=offset,
+                   out_nodata=-32768, statistic=stat)
+np.testing.assert_array_equal(out_p, NR.narrow_values(want_s, np.int16, scale, offset, -32768).T)
+assert (out_p[:, ~valid] == -32768).all()
+rec = index.debug_last_narrow()
+assert (rec["idx_dtype"], rec["dist_dtype"], rec["pred_dtype"]) == (0, 0, 2) and rec["d2h_bytes"] == rec["rows"] * T * 2, rec
+
+# (c) one stream, three typed outputs of three shapes and three widths, rows and planes in turn
+scale, offset = np.array([1.0, 0.5, 0.75]), np.array([0.0, 10.0, -5.0])
+eng = est.engine_
+stream = eng.open_stream(K, weights="distance", want_dist=True, decimals=est.DISTANCE_PRECISION_DECIMALS,
+                         formula=est._formula(), check_finite=True, query_dtype=eng.query_dtype_code(rows[0], est._formula(), False),
+                         output=dict(index_dtype=np.int32, distance_dtype=np.float32, pred_dtype=np.uint8, scale=scale,
+                                     offset=offset))
+got, row = [], 0
+for i, (b, r) in enumerate(zip(bands, rows)):
+    n = r.shape[0]
+    if i % 2:
+        got.append((False, row, n) + stream.push(r))
+    else:
+        got.append((True, row, n) + stream.push_planes([np.asarray(b[j]).reshape(-1) for j in range(D)]))
+    row += n
+rec = index.debug_last_narrow()
+assert (rec["idx_dtype"], rec["dist_dtype"], rec["pred_dtype"]) == (5, 1, 4) and rec["rows"] <= 1024, rec
+assert stream.close() == total
+assert index.debug_last_narrow()["d2h_bytes"] == rec["rows"] * (K * 4 + K * 4 + T * 1)
+for planes, r0, n, idx, dist, pred in got:
+    fix = (lambda a: a.T) if planes else (lambda a: a)
+    assert (idx.dtype, dist.dtype, pred.dtype) == (np.int32, np.float32, np.uint8)
+    assert idx.shape == dist.shape == ((K, n) if planes else (n, K)) and pred.shape == ((T, n) if planes else (n, T))
+    np.testing.assert_array_equal(fix(idx), NR.narrow_indices(all_i[r0:r0 + n]))
+    np.testing.assert_array_equal(fix(dist), NR.narrow_values(all_d[r0:r0 + n], np.float32))
+    np.testing.assert_array_equal(fix(pred), NR.narrow_values(all_p[r0:r0 + n], np.uint8, scale, offset))
+print("ok", total, int(valid.sum()))
+"""
+
+
+def test_all_lanes_differ():
+    """The three outputs differ in everything at once -- k = 5 against t = 3 columns, 4 / 4 / 1 and 4 / 4 / 2 bytes per
+    element -- band-first, masked and with per-target statistics, through more pipeline tiles than slots
+    (SKNNR_HOST_CHUNK_ROWS=1024, read once per process: a child runs it).  Every expectation is an untiled float64 call
+    on device tensors, narrowed by tests/_narrow.py."""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, SKNNR_HOST_CHUNK_ROWS="1024")
+    env.pop("SKNNR_PIPE_NO_RAMP", None)
+    run = subprocess.run([sys.executable, "-c", _ALL_LANES_CHILD.format(root=root, tests=os.path.join(root, "tests"))],
+                         env=env, capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-3000:]
+    assert run.stdout.strip().splitlines()[-1].startswith("ok 10825 "), run.stdout[-500:]
