@@ -530,6 +530,26 @@ int sknnr_stream_push_planes(sknnr_stream* stream, const void* const* planes, in
  *   pushes, whose signatures promise int64 / float64, return SKNNR_ERR_INVALID on a stream with typed outputs.  The
  *   conversion runs behind the search, the reduction, the nodata expansion (so fill_index is already in the tile) and in
  *   the transposition's place; device-to-host copies, pinned buffers and the host copy move nq * cols * sizeof(type).
+ *
+ * Dataframe ids on the device.  A plot-id raster holds the ids of the reference rows, not their positions; the index
+ * conversion looks them up on its way out, so that the host never walks the output again:
+ *   indices (int64) with an id table -> v < 0 ? fill_id : table[v], tested on the source value BEFORE the load, then
+ *     the plain narrowing to SKNNR_DTYPE_I32 (the caller guarantees that every table entry and fill_id fits) or, for
+ *     dst_dtype 0, no narrowing: int64 ids, lookup only, in the same single pass (tests/_id_table.py restates it).
+ * sknnr_narrow_ids: sknnr_narrow for index tiles with a lookup; no handle, every pointer DEVICE memory.  src: packed
+ *   (n, c) int64; table: n_table int64; dst / dst_stride as for sknnr_narrow, dst_dtype 0 (int64) or SKNNR_DTYPE_I32.
+ *   has_fill / fill_id: what a negative source value becomes; without has_fill it passes through unchanged.  A
+ *   NON-NEGATIVE source value at or above n_table is a caller error that the kernel does not test for: it reads
+ *   outside the table.  *out_wide as for sknnr_narrow (an int64 destination takes the wide path when it is 32-byte
+ *   aligned).  SKNNR_ERR_INVALID, before any device call, for a NULL table, n_table < 1, another dst_dtype, and the
+ *   cases sknnr_narrow refuses (n < 0, c out of range, a non-zero stride below n, NULL src / dst); n == 0 is SKNNR_OK.
+ * sknnr_stream_set_id_table: table is a HOST array of n_table int64, uploaded once; n_table must be the handle's number
+ *   of reference rows.  Allowed only before the first push (SKNNR_ERR_INVALID afterwards, and for another n_table).
+ *   From then on the index output of every tile leaves through the conversion kernel with the table -- int64 or, with
+ *   idx_dtype SKNNR_DTYPE_I32, int32; rows or planes; masked or not -- and holds ids.  The fill_index of
+ *   sknnr_stream_set_nodata stays what the nodata expansion writes into the tile: pass a negative one (-1), and the
+ *   lookup gives those pixels fill_id.  A stream on which it is never called enqueues exactly what it did before the
+ *   entry point existed.
  */
 #define SKNNR_NARROW_VALUE 0
 #define SKNNR_NARROW_INDEX 1
@@ -539,6 +559,10 @@ int sknnr_narrow(const void* src, int32_t kind, int64_t n, int32_t c, void* dst,
 int sknnr_stream_set_output(sknnr_stream* stream, int32_t idx_dtype, int32_t dist_dtype, int32_t pred_dtype,
                             const double* pred_scale, const double* pred_offset, int32_t has_pred_fill,
                             double pred_fill);
+int sknnr_narrow_ids(const int64_t* src, int64_t n, int32_t c, const int64_t* table, int64_t n_table, int32_t has_fill,
+                     int64_t fill_id, void* dst, int32_t dst_dtype, int64_t dst_stride, int32_t device, void* stream,
+                     int32_t* out_wide);
+int sknnr_stream_set_id_table(sknnr_stream* stream, const int64_t* table, int64_t n_table, int64_t fill_id);
 int sknnr_stream_push_typed(sknnr_stream* stream, const void* q, int64_t nq, void* out_dist, void* out_idx,
                             void* out_pred);
 int sknnr_stream_push_planes_typed(sknnr_stream* stream, const void* const* planes, int64_t nq, void* out_dist,
@@ -547,12 +571,12 @@ int sknnr_stream_push_planes_typed(sknnr_stream* stream, const void* const* plan
 /*
  * Debug only.  The output side of the last tile the handle's host pipeline submitted, so that a test can prove that the
  * device converted it and that only the narrow bytes were copied.  Host memory, no device work:
- *   out[0] 1 = a conversion kernel ran for the tile, 0 = none did (no typed output)
+ *   out[0] 1 = a conversion kernel ran for the tile, 0 = none did (no typed output and no id table)
  *   out[1] rows of the tile
  *   out[2] / out[3] / out[4] sknnr_dtype of the indices / distances / predictions (0 = int64 / float64)
  *   out[5] bytes the tile's device-to-host copies moved (0 until they are enqueued: behind the next tile, or by a flush)
  *   out[6] outputs whose conversion took the 4-elements-per-lane path: bit 0 indices, bit 1 distances, bit 2 predictions
- *   out[7] 0
+ *   out[7] 1 = the tile's indices were crosswalked on the device (sknnr_stream_set_id_table), 0 = they left as row indices
  */
 int sknnr_debug_last_narrow(const sknnr_index* index, int64_t out[8]);
 

@@ -207,6 +207,13 @@ def normalize_band_tile(tile, n_bands, *, forest=False, estimator="the estimator
     return bands, int(bands[0].shape[0])
 
 
+def _empty_row_tile(tile) -> bool:
+    """A row tile ``(0, n_features)``: a window that holds no pixel.  A streamed call skips it, as it skips an empty
+    band-first tile, before scikit-learn's validation, which refuses arrays without rows."""
+    shape = getattr(tile, "shape", None)
+    return shape is not None and len(shape) == 2 and shape[0] == 0
+
+
 def _resolve_fit_method(algorithm, n_ref, d, k):
     """Which of the reference's engines -- hence which float64 distance expression -- the
     ``algorithm`` setting selects (SKL/neighbors/_base.py:620-648)."""
@@ -741,7 +748,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
     def _stream_tiles(self, tiles, validate, k, *, apply_affine, weights, return_distance,
                       use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False, output=None,
-                      statistic=None):
+                      statistic=None, id_table=None, fill_id=-1, neighbors=False):
         """Push host tiles through one native query stream.  Returns (dist, idx, pred) arrays over all
         pushed rows (pieces of ``out`` when given, else concatenated).  ``nodata`` (float64, one value per column of the
         validated tiles): rows holding one are masked on the device and get ``fill_index`` / NaN.
@@ -754,7 +761,14 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         the device and the arrays (``out`` included) have those element types.
 
         ``statistic``: int32 codes (:func:`normalize_statistic`), one per target -- the predictions are those summaries
-        of the neighbours instead of the mean."""
+        of the neighbours instead of the mean.
+
+        ``id_table`` (:meth:`_device_id_table`): int64 dataframe ids, one per reference row -- the indices leave the
+        device as ``id_table[idx]``, and with a mask ``fill_index`` must be -1: those rows get ``fill_id``.
+
+        ``neighbors`` (with ``weights``): the indices (and, with ``return_distance``, the distances) the predictions are
+        reduced from are delivered beside them, from the same stream; an output without an array in ``out`` is
+        collected and concatenated."""
         if output:
             self._check_stream_supported("typed outputs are")
         eng = self.engine_
@@ -775,6 +789,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             # the reference's choice among tied rows is made on the host, per call: tile by tile, positions carried
             parts, row = [], 0
             for tile in tiles:
+                if _empty_row_tile(tile):
+                    continue
                 tile = validate(tile)
                 if tile.shape[0] == 0:
                     continue
@@ -810,6 +826,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 if is_torch_cuda_tensor(tile):
                     raise TypeError("streamed tiles are host arrays (they travel through the pinned "
                                     "PCIe pipeline); pass CUDA tensors to kneighbors() / predict()")
+                if not bands and _empty_row_tile(tile):
+                    continue
                 if bands:  # (``tile``: the list of 1-D bands; ``first`` stands for its element type)
                     tile, n = validate(tile)
                     first, n_cols = tile[0], len(tile)
@@ -828,7 +846,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              deterministic=use_deterministic_ordering,
                                              decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula(),
                                              apply_affine=apply_affine, check_finite=True, query_dtype=code,
-                                             nodata=nodata, fill_index=fill_index, output=output, statistic=statistic)
+                                             nodata=nodata, fill_index=fill_index, output=output, statistic=statistic,
+                                             **({} if id_table is None else dict(id_table=id_table, fill_id=fill_id)))
                 if first.dtype != stream_dtype:
                     if stream_dtype != np.float64:
                         raise ValueError(f"the tiles of one streamed call must share an element type: got {first.dtype} "
@@ -854,8 +873,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 got = (stream.push_planes if bands else stream.push)(
                     tile, out_idx=window(o_idx, k, idx_dt),
                     out_dist=window(o_dist, k, dist_dt) if return_distance else None,
-                    out_pred=window(o_pred, t_cols, pred_dt) if want_pred else None, need_idx=not want_pred)
-                if out is None:
+                    out_pred=window(o_pred, t_cols, pred_dt) if want_pred else None, need_idx=neighbors or not want_pred)
+                if out is None or neighbors:
                     pieces.append(got)
                 row += n
             if stream is not None:
@@ -869,11 +888,15 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                     stream.close()
                 except _native.HipBackendError:
                     pass
-        if out is not None:
-            trim = lambda a: None if a is None else (a[:, :row] if bands else a[:row])  # noqa: E731
+        trim = lambda a: None if a is None else (a[:, :row] if bands else a[:row])  # noqa: E731
+        if out is not None and not neighbors:
             return trim(o_dist) if return_distance else None, trim(o_idx), trim(o_pred) if want_pred else None
         cat = lambda i, cols, dt: (np.concatenate([p[i] for p in pieces], axis=1 if bands else 0) if pieces  # noqa: E731
                                    else np.empty((cols, 0) if bands else (0, cols), dtype=dt))
+        if neighbors:  # (each output from its array in ``out`` where there is one, else collected)
+            pick = lambda o_, i, cols, dt: trim(o_) if o_ is not None else cat(i, cols, dt)  # noqa: E731
+            return (pick(o_dist, 1, k, dist_dt) if return_distance else None, pick(o_idx, 0, k, idx_dt),
+                    pick(o_pred, 2, t_cols, pred_dt))
         return (cat(1, k, dist_dt) if return_distance else None,
                 None if want_pred else cat(0, k, idx_dt),
                 cat(2, t_cols, pred_dt) if want_pred else None)
@@ -898,6 +921,19 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         out = dict(index_dtype=idt, distance_dtype=ddt)
         return out if idt is not None or ddt is not None else None
 
+    def _device_id_table(self, return_dataframe_index):
+        """The dataframe ids as the int64 table a stream looks its indices up in on the device, or None: row indices
+        were asked for, the labels are no integers of at most 64 bits (the rule of :meth:`_finish_kneighbors`; those are
+        looked up on the host), or a reference tie policy answers tile by tile on the host."""
+        if not return_dataframe_index:
+            return None
+        msg = "Dataframe indexes can only be returned when fitted with a dataframe."
+        check_is_fitted(self, "dataframe_index_in_", msg=msg)
+        table = np.asarray(self.dataframe_index_in_)
+        if table.dtype.kind not in "iu" or table.dtype.itemsize > 8 or table.dtype == np.uint64 or self._reference_ties():
+            return None
+        return np.ascontiguousarray(table.astype(np.int64, copy=False))
+
     def kneighbors_chunks(self, tiles, n_neighbors=None, return_distance=True, return_dataframe_index=False,
                           use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1, layout="rows",
                           index_dtype=None, distance_dtype=None):
@@ -919,8 +955,12 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
         ``index_dtype=np.int32`` / ``distance_dtype=np.float32``: the results are narrowed on the device (plain
         narrowing; the C cast, round to nearest even) and only the narrow bytes cross PCIe; ``out`` arrays then have those
-        types.  ``fill_index`` and, with ``return_dataframe_index``, every dataframe id must fit int32; the id crosswalk
-        runs on the host, in place, at int32."""
+        types.  ``fill_index`` and, with ``return_dataframe_index``, every dataframe id must fit int32.
+
+        ``return_dataframe_index=True`` with integer dataframe ids (at most 64 bits, not uint64): the ids are looked up
+        on the device, inside the conversion every tile's indices leave through, so ``out`` receives ids (int64, or
+        int32 with ``index_dtype``) and the host never walks the output again; other labels (strings, ...) and the
+        host-side tie policies are looked up on the host afterwards, as before."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         k = self._resolve_k(n_neighbors)
@@ -932,22 +972,28 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         validate = self._validate_query
         if bands:
             validate = lambda t: normalize_band_tile(t, self.n_features_in_, estimator=type(self).__name__)  # noqa: E731
-        # (dataframe ids: masked rows travel as -1, which no row index equals, and take fill_index after the crosswalk)
+        # (dataframe ids: masked rows travel as -1, which no row index equals, and take fill_index in the crosswalk)
+        table = self._device_id_table(return_dataframe_index)
         dist, idx, _ = self._stream_tiles(tiles, validate, k, apply_affine=False, weights=None,
                                           return_distance=return_distance,
                                           use_deterministic_ordering=use_deterministic_ordering, out=o, owner=None,
                                           nodata=nodata, fill_index=-1 if return_dataframe_index else fill_index,
-                                          bands=bands, output=output)
+                                          bands=bands, output=output, id_table=table, fill_id=fill_index)
         return self._finish_chunks(dist, idx, return_distance, return_dataframe_index,
-                                   fill_index=None if nodata is None else fill_index)
+                                   fill_index=None if nodata is None else fill_index, on_device=table is not None)
 
-    def _finish_chunks(self, dist, idx, return_distance, return_dataframe_index, fill_index=None):
-        """``fill_index`` (a masked call): rows whose index is -1 are nodata rows and get it instead of a table entry."""
+    def _finish_chunks(self, dist, idx, return_distance, return_dataframe_index, fill_index=None, on_device=False):
+        """``fill_index`` (a masked call): rows whose index is -1 are nodata rows and get it instead of a table entry.
+        ``on_device``: the stream looked the ids up already (:meth:`_device_id_table`), fill included; what is left is
+        the one ``astype`` of a table that is not int64, as in :meth:`_finish_kneighbors`."""
         if return_dataframe_index:
             msg = "Dataframe indexes can only be returned when fitted with a dataframe."
             check_is_fitted(self, "dataframe_index_in_", msg=msg)
             table = self.dataframe_index_in_
-            if fill_index is not None:
+            if on_device:
+                if idx.dtype == np.int64:  # (an int32 output keeps its type, as the in-place host lookup did)
+                    idx = idx.astype(table.dtype, copy=False)
+            elif fill_index is not None:
                 if table.dtype == np.int64 or idx.dtype == np.int32:  # (int32: the ids were checked to fit)
                     step = 1 << 22
                     for a in range(0, idx.shape[0], step):
@@ -966,8 +1012,29 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 idx = table[idx]
         return (dist, idx) if return_distance else idx
 
+    @staticmethod
+    def _neighbor_request(return_neighbors, return_distance, return_dataframe_index, neighbors_out, fill_index,
+                          index_dtype, distance_dtype):
+        """The neighbour keywords of ``predict_chunks`` as one dict, or None without ``return_neighbors``; any of them
+        without it is refused, before any device work."""
+        if return_neighbors:
+            if neighbors_out is not None and len(neighbors_out) != 2:
+                raise ValueError("neighbors_out must be (dist, idx); dist may be None")
+            return dict(return_distance=bool(return_distance), return_dataframe_index=bool(return_dataframe_index),
+                        neighbors_out=neighbors_out, fill_index=fill_index, index_dtype=index_dtype,
+                        distance_dtype=distance_dtype)
+        for name, given in (("neighbors_out", neighbors_out is not None), ("return_distance", return_distance is not True),
+                            ("return_dataframe_index", return_dataframe_index is not False),
+                            ("fill_index", fill_index != -1), ("index_dtype", index_dtype is not None),
+                            ("distance_dtype", distance_dtype is not None)):
+            if given:
+                raise ValueError(f"{name} needs return_neighbors=True: predictions alone have no neighbour outputs")
+        return None
+
     def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
-                       out_nodata=None, statistic=None):
+                       out_nodata=None, statistic=None, return_neighbors=False, return_distance=True,
+                       return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
+                       distance_dtype=None):
         """``predict`` over an iterable of host tiles as one streamed call; ``out``: preallocated
         ``(n_rows, n_targets)`` float64 array (e.g. a memmap; float32 results are held exactly).  ``nodata`` as in
         :meth:`kneighbors_chunks`: masked rows are predicted NaN.  ``layout="bands"``: band-first tiles as in
@@ -992,9 +1059,23 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         ``d == 0`` becomes its 0 / 1 mask) or the callable's; all arithmetic is float64.  The result equals ``summarize(np.concatenate(tiles),
         statistic)`` bit for bit (float64 unless ``out_dtype`` says otherwise) and is written where the prediction is, so
         ``nodata``, ``layout``, ``out`` and the typed outputs apply unchanged; e.g. ``statistic=["mean", "mean", "mode"]``
-        maps two continuous attributes and a class code in one call."""
+        maps two continuous attributes and a class code in one call.
+
+        ``return_neighbors=True``: the neighbours the predictions are reduced from (``n_neighbors`` of them,
+        deterministic ordering) are delivered beside them from the SAME search -- the call returns ``(pred, dist, idx)``,
+        or ``(pred, idx)`` with ``return_distance=False`` -- so a plot-id raster, a distance raster and the attribute
+        rasters cost one pass, not ``kneighbors_chunks`` and then ``predict_chunks``.  ``return_dataframe_index``,
+        ``fill_index``, ``index_dtype`` and ``distance_dtype`` are those of :meth:`kneighbors_chunks`, and ``dist`` /
+        ``idx`` equal its results with the same ``nodata`` and ``layout`` bit for bit; ``neighbors_out=(dist, idx)``
+        (``dist`` may be None) are preallocated arrays under the rules of its ``out`` -- with ``layout="bands"`` they
+        share ``N`` with ``out``, and the arrays come all or none: the planes of one tile leave with one stride.  An
+        output without an array is collected tile by tile and returned concatenated.  ``pred`` is what the call returns without ``return_neighbors``.  Callable weights
+        and the host-side tie policies are refused; so is any of these keywords without ``return_neighbors=True``."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
+        neighbors = self._neighbor_request(return_neighbors, return_distance, return_dataframe_index, neighbors_out,
+                                           fill_index, index_dtype, distance_dtype)
+        extra = {} if neighbors is None else dict(neighbors=neighbors)
         if statistic is not None:
             statistic = normalize_statistic(statistic, self._n_targets())
         if nodata is not None:
@@ -1003,15 +1084,22 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         if bands:
             validate = lambda t: normalize_band_tile(t, self.n_features_in_, estimator=type(self).__name__)  # noqa: E731
         return self._predict_chunks(tiles, validate, apply_affine=False, out=out, owner=None, nodata=nodata, bands=bands,
-                                    typed=(out_dtype, scale, offset, out_nodata), statistic=statistic)
+                                    typed=(out_dtype, scale, offset, out_nodata), statistic=statistic, **extra)
 
     def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None, bands=False, typed=None,
-                        statistic=None):
+                        statistic=None, neighbors=None):
+        """``neighbors``: :meth:`_neighbor_request`, or None -- predictions alone, exactly as before the keyword existed."""
         weights = "uniform" if self.weights is None else self.weights
         output = None
         if typed is not None:
             n_targets = 1 if self._y.ndim == 1 else self._y.shape[1]
             output = normalize_typed_output(*typed, n_targets, nodata is not None)
+        if neighbors is not None:
+            if callable(weights):
+                self._refuse_callable_weights("return_neighbors is")
+            return self._predict_chunks_neighbors(tiles, validate, weights, neighbors, apply_affine=apply_affine, out=out,
+                                                  owner=owner, nodata=nodata, bands=bands, output=output,
+                                                  statistic=statistic)
         if callable(weights) and output:
             self._refuse_callable_weights("typed outputs are")
         if callable(weights) and bands:
@@ -1043,6 +1131,34 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             if out is None and not output and statistic is None:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
                 pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         return pred.reshape(-1) if self._y.ndim == 1 else pred
+
+    def _predict_chunks_neighbors(self, tiles, validate, weights, neighbors, *, apply_affine, out, owner, nodata, bands,
+                                  output, statistic):
+        """``predict_chunks(return_neighbors=True)``: one stream with all three outputs.  ``output``: the predictions'
+        typed output (or None); the neighbours' types and the id table are worked out here, as ``kneighbors_chunks``
+        does, every refusal before any device work."""
+        self._check_stream_supported("return_neighbors is")
+        return_distance, ids, fill_index = (neighbors[key] for key in ("return_distance", "return_dataframe_index", "fill_index"))
+        n_output = self._neighbor_output(neighbors["index_dtype"], neighbors["distance_dtype"], return_distance, ids,
+                                         fill_index, nodata is not None)
+        table = self._device_id_table(ids)
+        o_dist, o_idx = neighbors["neighbors_out"] or (None, None)
+        o_pred = None if out is None else out.reshape(out.shape[0], -1)
+        if bands and out is not None and out.ndim == 1:  # (a 1-D y: the one target plane)
+            o_pred = out.reshape(1, -1)
+        o = None if (o_dist is None and o_idx is None and o_pred is None) else (o_dist, o_idx, o_pred)
+        merged = {**(output or {}), **(n_output or {})} or None
+        dist, idx, pred = self._stream_tiles(tiles, validate, self.n_neighbors, apply_affine=apply_affine, weights=weights,
+                                             return_distance=return_distance, use_deterministic_ordering=True, out=o,
+                                             owner=owner, nodata=nodata, fill_index=-1 if ids else fill_index, bands=bands,
+                                             output=merged, statistic=statistic, id_table=table, fill_id=fill_index,
+                                             neighbors=True)
+        if out is None and not output and statistic is None:  # (as without neighbours: float32 where scikit-learn returns it)
+            pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
+        pred = pred.reshape(-1) if self._y.ndim == 1 else pred
+        found = self._finish_chunks(dist, idx, return_distance, ids, fill_index=None if nodata is None else fill_index,
+                                    on_device=table is not None)
+        return (pred, *found) if return_distance else (pred, found)
 
     def score(self, X, y, sample_weight=None):
         """R^2 of ``predict(X)`` (``X`` may be None as in REF _base.py:40)."""
@@ -1252,30 +1368,37 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         output = reg._neighbor_output(index_dtype, distance_dtype, return_distance, return_dataframe_index, fill_index,
                                       nodata is not None)
         o = None if out is None else (out[0], out[1], None)
+        table = reg._device_id_table(return_dataframe_index)
         dist, idx, _ = reg._stream_tiles(tiles, validate, k, apply_affine=self._map_on_device(), weights=None,
                                          return_distance=return_distance,
                                          use_deterministic_ordering=use_deterministic_ordering, out=o,
                                          owner=self.transformer_, nodata=nodata,
                                          fill_index=-1 if return_dataframe_index else fill_index, bands=bands,
-                                         output=output)
+                                         output=output, id_table=table, fill_id=fill_index)
         return reg._finish_chunks(dist, idx, return_distance, return_dataframe_index,
-                                  fill_index=None if nodata is None else fill_index)
+                                  fill_index=None if nodata is None else fill_index, on_device=table is not None)
 
     def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
-                       out_nodata=None, statistic=None):
+                       out_nodata=None, statistic=None, return_neighbors=False, return_distance=True,
+                       return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
+                       distance_dtype=None):
         """``predict`` over an iterable of untransformed host tiles as one streamed call (``nodata``: masked rows are
         predicted NaN; ``layout="bands"``: band-first tiles and predictions; ``out_dtype`` / ``scale`` / ``offset`` /
         ``out_nodata``: predictions converted on the device to the type the raster is stored in; ``statistic``: one name
-        or one per target -- mean, mode, min, max, nearest, std of the neighbours in place of the mean; see
+        or one per target -- mean, mode, min, max, nearest, std of the neighbours in place of the mean;
+        ``return_neighbors=True`` and the neighbour keywords: ``(pred, dist, idx)`` from one search; see
         :meth:`RawKNNRegressor.kneighbors_chunks` / :meth:`RawKNNRegressor.predict_chunks`)."""
         bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
+        neighbors = self.regressor_._neighbor_request(return_neighbors, return_distance, return_dataframe_index,
+                                                      neighbors_out, fill_index, index_dtype, distance_dtype)
+        extra = {} if neighbors is None else dict(neighbors=neighbors)
         if statistic is not None:
             statistic = normalize_statistic(statistic, self.regressor_._n_targets())
         return self.regressor_._predict_chunks(tiles, self._band_validator(bands), apply_affine=self._map_on_device(),
                                                out=out, owner=self.transformer_, nodata=self._raw_nodata(nodata),
                                                bands=bands, typed=(out_dtype, scale, offset, out_nodata),
-                                               statistic=statistic)
+                                               statistic=statistic, **extra)
 
     def score(self, X, y):
         """REF _base.py:350-352."""

@@ -463,7 +463,7 @@ class KNNEngine:
 
     def open_stream(self, k, *, weights=None, want_dist=True, deterministic=True, decimals=10,
                     formula="expanded", apply_affine=False, row_offset=0, check_finite=False, query_dtype=0,
-                    nodata=None, fill_index=-1, output=None, statistic=None):
+                    nodata=None, fill_index=-1, output=None, statistic=None, id_table=None, fill_id=-1):
         """A :class:`sknnr_amd._native.QueryStream` over host tiles: ``push(tile)`` keeps the PCIe
         pipeline full across tiles and carries the global row offset.  ``weights`` (``"uniform"`` /
         ``"distance"``) also asks for predictions: float64 arrays, holding binary32 values where
@@ -471,7 +471,9 @@ class KNNEngine:
         the device, masked rows get ``fill_index`` / NaN and the row offset counts valid rows only.  ``output``: keyword
         arguments of :meth:`sknnr_amd._native.QueryStream.set_output` (typed results, narrowed on the device).
         ``statistic``: one ``_native.STATISTICS`` code per target; the predictions become those summaries of the
-        neighbours (:meth:`summarize`), written where the predictions are."""
+        neighbours (:meth:`summarize`), written where the predictions are.  ``id_table`` (int64, one dataframe id per
+        reference row): the indices leave as ``id_table[idx]``, looked up on the device; keep ``fill_index`` negative,
+        and masked rows get ``fill_id``."""
         want_pred = weights is not None
         if want_pred and weights not in _WEIGHT_MODES:
             raise ValueError("a stream predicts with 'uniform' or 'distance' weights only")
@@ -482,7 +484,7 @@ class KNNEngine:
         if statistic is not None and not want_pred:
             raise ValueError("statistics need a stream that predicts: pass weights")
         return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred, nodata=nodata, fill_index=fill_index,
-                                       output=output, statistic=statistic)
+                                       output=output, statistic=statistic, id_table=id_table, fill_id=fill_id)
 
     def hamming_distances(self, X, rows=None):
         """Full weighted-Hamming distance rows of ``X[rows]`` (``X`` None: of the fitted rows) from the device."""

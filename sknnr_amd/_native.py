@@ -97,6 +97,8 @@ EXPORTED_SYMBOLS = (
     "sknnr_debug_last_planes",
     "sknnr_narrow",
     "sknnr_stream_set_output",
+    "sknnr_narrow_ids",
+    "sknnr_stream_set_id_table",
     "sknnr_stream_push_typed",
     "sknnr_stream_push_planes_typed",
     "sknnr_debug_last_narrow",
@@ -230,6 +232,9 @@ def load(build_if_missing: bool = False):
     lib.sknnr_narrow.argtypes = [vp, c_int32, c_int64, c_int32, vp, c_int32, c_int64, vp, vp, c_int32, c_double, c_int32, vp,
                                  POINTER(c_int32)]
     lib.sknnr_stream_set_output.argtypes = [vp, c_int32, c_int32, c_int32, vp, vp, c_int32, c_double]
+    lib.sknnr_narrow_ids.argtypes = [vp, c_int64, c_int32, vp, c_int64, c_int32, c_int64, vp, c_int32, c_int64, c_int32, vp,
+                                     POINTER(c_int32)]
+    lib.sknnr_stream_set_id_table.argtypes = [vp, vp, c_int64, c_int64]
     lib.sknnr_stream_push_typed.argtypes = [vp, vp, c_int64, vp, vp, vp]
     lib.sknnr_stream_push_planes_typed.argtypes = [vp, vp, c_int64, vp, vp, vp, c_int64]
     lib.sknnr_debug_last_narrow.argtypes = [vp, POINTER(c_int64)]
@@ -404,11 +409,13 @@ class Index:
         check(load().sknnr_check_finite(self.handle, c_void_p(stream or None)))
 
     def open_stream(self, opts: QueryOpts, want_dist=True, want_pred=False, nodata=None, fill_index=-1,
-                    output=None, statistic=None) -> "QueryStream":
+                    output=None, statistic=None, id_table=None, fill_id=-1) -> "QueryStream":
         """``nodata``: float64 ``(d_in,)``, one value per column of the pushed rows -- every tile is then masked on the
         device (sknnr_stream_set_nodata) and masked rows get ``fill_index`` / NaN.  ``output``: keyword arguments of
         :meth:`QueryStream.set_output` -- the results then leave the device at those types.  ``statistic``: one
-        ``STATISTICS`` code per target (:meth:`QueryStream.set_statistics`) -- the predictions become those summaries."""
+        ``STATISTICS`` code per target (:meth:`QueryStream.set_statistics`) -- the predictions become those summaries.
+        ``id_table`` / ``fill_id``: :meth:`QueryStream.set_id_table` -- the indices leave as those ids; ``fill_index``
+        must then be negative, and masked rows get ``fill_id``."""
         stream = QueryStream(self, opts, want_dist, want_pred)
         try:
             if nodata is not None:
@@ -417,6 +424,8 @@ class Index:
                 stream.set_output(**output)
             if statistic is not None:
                 stream.set_statistics(statistic)
+            if id_table is not None:
+                stream.set_id_table(id_table, fill_id)
         except Exception:
             stream.close()
             raise
@@ -563,8 +572,8 @@ class Index:
     def debug_last_narrow(self) -> dict:
         """Debug only: the output side of the last tile of the host pipeline (sknnr_debug_last_narrow): whether a
         conversion kernel ran, the tile's rows, the sknnr_dtype of indices / distances / predictions (0: int64 / float64),
-        the bytes its device-to-host copies moved, and which outputs took the 4-elements-per-lane path (bit 0 indices,
-        1 distances, 2 predictions)."""
+        the bytes its device-to-host copies moved, which outputs took the 4-elements-per-lane path (bit 0 indices,
+        1 distances, 2 predictions), and, under the field's old name ``reserved``, whether its indices were crosswalked to dataframe ids on the device."""
         out = (c_int64 * 8)()
         check(load().sknnr_debug_last_narrow(self.handle, out))
         return dict(zip(self.NARROW_FIELDS, (int(v) for v in out)))
@@ -873,6 +882,13 @@ class QueryStream:
         self.idx_dtype, self.dist_dtype, self.pred_dtype = idt, ddt, pdt
         self._typed = bool(ic or dc or pc)
 
+    def set_id_table(self, table, fill_id=-1):
+        """Dataframe ids on the device (sknnr_stream_set_id_table; only before the first push): ``table`` holds one
+        int64 id per reference row, and the index output of every tile leaves as ``table[idx]``, negative indices (the
+        ``fill_index`` of a nodata mask) as ``fill_id`` -- in the stream's index type, whose range they must fit."""
+        table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1)
+        check(load().sknnr_stream_set_id_table(self._h, _host_ptr(table), int(table.size), int(fill_id)))
+
     def valid_rows(self) -> int:
         """Valid (unmasked) rows submitted so far; without a nodata mask, the rows pushed."""
         n = c_int64(0)
@@ -1019,4 +1035,19 @@ def narrow_device(src_ptr, kind, n, c, dst_ptr, dst_dtype, dst_stride=0, scale_p
     check(load().sknnr_narrow(c_void_p(src_ptr or None), int(kind), n, c, c_void_p(dst_ptr or None), code, dst_stride,
                               c_void_p(scale_ptr or None), c_void_p(offset_ptr or None), int(fill is not None),
                               float(0.0 if fill is None else fill), device, c_void_p(stream or None), byref(wide)))
+    return bool(wide.value)
+
+
+def narrow_ids_device(src_ptr, n, c, table_ptr, n_table, dst_ptr, dst_dtype, dst_stride=0, fill_id=None, device=0,
+                      stream=0) -> bool:
+    """A packed ``(n, c)`` int64 index tile to the ids ``table[idx]`` (``fill_id`` for negatives; None: they pass through),
+    as int64 or int32, packed rows (``dst_stride`` 0) or ``c`` planes ``dst_stride`` elements apart, on device pointers
+    (sknnr_narrow_ids); enqueued on ``stream``.  Returns whether the launch took the 4-elements-per-lane path."""
+    code = dst_dtype if isinstance(dst_dtype, int) else {np.dtype(np.int64): 0}.get(
+        np.dtype(dst_dtype), DTYPE_CODES.get(np.dtype(dst_dtype), -1))
+    wide = c_int32(0)
+    check(load().sknnr_narrow_ids(c_void_p(src_ptr or None), n, c, c_void_p(table_ptr or None), n_table,
+                                  int(fill_id is not None), int(0 if fill_id is None else fill_id),
+                                  c_void_p(dst_ptr or None), code, dst_stride, device, c_void_p(stream or None),
+                                  byref(wide)))
     return bool(wide.value)

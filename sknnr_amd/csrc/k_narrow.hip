@@ -25,8 +25,8 @@ hipError_t narrow_launch(const NarrowArgs& a, bool wide, hipStream_t st) {
 }
 }  // namespace
 
-int narrow_dst_bytes(int kind, int dst_dtype) {
-    if (kind == kNarrowIndex) return dst_dtype == 5 ? 4 : 0;
+int narrow_dst_bytes(int kind, int dst_dtype, bool table) {
+    if (kind == kNarrowIndex) return dst_dtype == 5 ? 4 : (dst_dtype == 0 && table ? 8 : 0);  // (int64: lookup only)
     if (kind != kNarrowValue) return 0;
     switch (dst_dtype) {
         case 1: return 4;  // float32
@@ -39,12 +39,14 @@ int narrow_dst_bytes(int kind, int dst_dtype) {
 }
 
 hipError_t narrow(const NarrowArgs& a, int kind, int dst_dtype, bool wide, hipStream_t st) {
-    const int esz = narrow_dst_bytes(kind, dst_dtype);
+    if (a.table && kind != kNarrowIndex) return hipErrorInvalidValue;
+    const int esz = narrow_dst_bytes(kind, dst_dtype, a.table != nullptr);
     if (!esz || a.n < 0 || a.c < 1 || (a.stride != 0 && a.stride < a.n) || !a.src || !a.dst || !a.scale != !a.offset)
         return hipErrorInvalidValue;
     if (wide && !narrow_wide_ok(a.src, a.dst, esz, a.n, a.c, a.stride)) return hipErrorInvalidValue;
     if (a.n == 0) return hipSuccess;
-    if (kind == kNarrowIndex) return narrow_launch<long, int32_t>(a, wide, st);
+    if (kind == kNarrowIndex)
+        return dst_dtype == 0 ? narrow_launch<long, long>(a, wide, st) : narrow_launch<long, int32_t>(a, wide, st);
     switch (dst_dtype) {
         case 1: return narrow_launch<double, float>(a, wide, st);
         case 2: return narrow_launch<double, int16_t>(a, wide, st);

@@ -74,10 +74,11 @@ hipError_t rows_to_planes(const PlanesArgs& a, hipStream_t st);
 
 // ---- k_narrow.hip: result tiles to the raster's storage type (narrow.hip.h) ----------------------------------------------
 // packed (n, c) float64 (kind kNarrowValue) or int64 (kNarrowIndex) -> dst_dtype (a sknnr_dtype), packed or as planes
-// (a.stride); `wide` must satisfy narrow_wide_ok.  hipErrorInvalidValue for an impossible type pair.
+// (a.stride); `wide` must satisfy narrow_wide_ok.  With a.table (indices only) every element is looked up first, and
+// dst_dtype 0 (int64) is a pair too.  hipErrorInvalidValue for an impossible type pair.
 hipError_t narrow(const NarrowArgs& a, int kind, int dst_dtype, bool wide, hipStream_t st);
-// bytes per destination element of that pair, 0 when there is no such conversion
-int narrow_dst_bytes(int kind, int dst_dtype);
+// bytes per destination element of that pair, 0 when there is no such conversion; `table`: the launch has an id table
+int narrow_dst_bytes(int kind, int dst_dtype, bool table = false);
 
 // ---- k_summary.hip: per-target neighbour summaries (summary.hip.h) ----------------------------------------------------------
 // the columns of a.tab (none of them `mean`) of every query; k <= kSummarySmallK: summary_kernel, else summary_wide_kernel

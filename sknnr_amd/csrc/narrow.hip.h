@@ -12,12 +12,21 @@
 //                       NaN can occur); otherwise rint(x) (half to even), then the clamp to the type's [min, max] (so
 //                       +-inf clamp), then the cast.  The clamp does not step around the fill value.
 //   indices -> int32    plain narrowing of int64; the host guarantees that every value fits.
+//   indices, id table   (NarrowArgs::table: the dataframe ids of the reference rows) v < 0 ? fill_id : table[v] FIRST -- the
+//                       sign is tested before the load, on the int64 source value, and without has_fill a negative
+//                       passes through as it is -- then the plain narrowing, or none at all: with a table the destination
+//                       may be int64 too (lookup only), so that an untyped id output takes the same single pass.  A
+//                       non-negative value at or above the table's length is a caller error that no kernel tests for.
+//                       The table is read through plain global loads: n_ref int64, a few hundred KB, resident in L2.
+//                       tests/_id_table.py restates the lookup.
 //
 // Access width.  The element path handles one element per lane and is right at any element-aligned address, as the
 // kernels of planes.hip.h are.  The wide path has a lane convert 4 consecutive destination elements: packed, two 16-byte
 // loads and one store of 4 * sizeof(D) bytes; planes, 4 consecutive pixels of one plane (a wave writes 256 consecutive
 // pixels of a plane).  The HOST chooses it from the addresses, the stride and the count (narrow_wide_ok, as compact_unit
 // does for the compaction); inside a wide launch the last, incomplete group of 4 goes element by element.
+// An int64 destination (id table only) takes the wide path under the same rule with 8-byte elements: 32 bytes per lane,
+// which gfx950 writes as two global_store_dwordx4, and a 32-byte aligned destination.
 // Offsets into global memory are 64-bit throughout.  LDS of the plane form: 256 rows x 16 columns of 8 bytes at a pitch
 // of 17, 34 KiB, as rows_to_planes_kernel.
 #pragma once
@@ -45,6 +54,9 @@ struct NarrowArgs {
     const double* offset;
     int has_fill;
     double fill;  // representable in the destination type (the host checks)
+    // index sources only: the id table (device, or null: no lookup) and what a negative index becomes when has_fill
+    const long* table;
+    long fill_id;
 };
 
 // The host's choice of the wide path: every 4-element store must be aligned to its own size.
@@ -93,7 +105,8 @@ __device__ __forceinline__ D narrow_one(double v, int j, const NarrowArgs& a) {
     }
 }
 template <typename D>
-__device__ __forceinline__ D narrow_one(long v, int, const NarrowArgs&) {
+__device__ __forceinline__ D narrow_one(long v, int, const NarrowArgs& a) {
+    if (a.table) v = v < 0 ? (a.has_fill ? a.fill_id : v) : a.table[v];
     return (D)v;
 }
 

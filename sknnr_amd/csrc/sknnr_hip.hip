@@ -414,8 +414,10 @@ struct sknnr_index {
     int64_t last_planes[8] = {};
     // typed outputs of the open stream: the per-target scale / offset on the device, and the record of the last tile of
     // the host pipeline (sknnr_debug_last_narrow): conversion ran, rows, the three output types, bytes its device-to-host
-    // copies moved, outputs that took the wide path (bit 0 indices, 1 distances, 2 predictions)
+    // copies moved, outputs that took the wide path (bit 0 indices, 1 distances, 2 predictions), indices crosswalked on
+    // the device; and the open stream's id table (sknnr_stream_set_id_table)
     DevBuf<double> s_scale, s_offset;
+    DevBuf<long> s_id_table;
     int64_t last_narrow[8] = {};
     // per-target statistics (summary.hip.h).  `summary`: the plan of the call in progress, set and cleared under mtx
     // (SummaryScope), read by launch_predict; null: every column is the mean.  The device tables of a one-shot call
@@ -2334,6 +2336,11 @@ struct HostPipe {
         const double *scale = nullptr, *offset = nullptr;
         int has_fill = 0;
         double fill = 0.0;
+        // indices only: the id table of their conversion (device, or null: row indices leave) and what a negative becomes
+        const long* table = nullptr;
+        long fill_id = 0;
+        // the lane leaves through the conversion kernel, from its narrow buffer: typed, or the index lane with a table
+        bool converts() const { return dtype != 0 || table != nullptr; }
     } lane[kLanes];
     bool mask_dist = false;  // the masked path is handed the distance buffer: distances leave, or the reduction reads them
     size_t x_esz = sizeof(double);  // bytes per element of the caller's rows (opts->query_dtype)
@@ -2439,8 +2446,8 @@ int pipe_prepare_slot(HostPipe& p, int b, long n, bool planes = false) {
         const size_t wide = (size_t)n * ln.cols, units = lane_units(n, ln.cols, ln.esz);
         if (ln.want && (rc = ensure_pinned(sb.pin, sb.pin_n, units))) return rc;
         if (ln.want || ln.search_out) HIP_TRY(sb.dev.ensure(wide));
-        if (ln.want && ln.dtype) HIP_TRY(sb.nar.ensure(units));
-        if (ln.want && !ln.dtype && planes) HIP_TRY(sb.planes.ensure(wide));  // (the untyped results as planes)
+        if (ln.want && ln.converts()) HIP_TRY(sb.nar.ensure(units));
+        if (ln.want && !ln.converts() && planes) HIP_TRY(sb.planes.ensure(wide));  // (the untyped results as planes)
     }
     if (p.nodata_dev && (rc = mask_ensure(sl.mask, n, (size_t)p.d_x * p.x_esz, p.k, p.t, p.lane[kLaneDist].want, p.lane[kLanePred].want)))
         return rc;
@@ -2478,8 +2485,8 @@ int pipe_enqueue_d2h(HostPipe& p) {
         if (!pd.out[l]) continue;
         const HostPipe::Lane& ln = p.lane[l];
         const auto& sb = sl.lane[l];
-        // (a typed output leaves from its narrow buffer, rows or planes alike, at its own element size)
-        const void* src = ln.dtype ? sb.nar.p : planes ? sb.planes.p : sb.dev.p;
+        // (a converted output leaves from its narrow buffer, rows or planes alike, at its own element size)
+        const void* src = ln.converts() ? sb.nar.p : planes ? sb.planes.p : sb.dev.p;
         const size_t bytes = lane_bytes(n, ln.cols, ln.esz);
         HIP_TRY(hipMemcpyAsync(sb.pin, src, bytes, hipMemcpyDeviceToHost, st));
         moved += bytes;
@@ -2577,19 +2584,22 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
             if (rc) return rc;
         }
     }
-    // The requested results in the form they leave in, behind everything that produces them: a typed output is converted
-    // (and, band-first, transposed in the same pass) into its narrow buffer; an untyped band-first one is transposed; an
+    // The requested results in the form they leave in, behind everything that produces them: a typed output, and the
+    // indices of a stream with an id table, typed or not, is converted (and, band-first, transposed in the same pass) into
+    // its narrow buffer; an untyped band-first one is transposed; an
     // untyped row output leaves from where it was computed, with no kernel here.
-    int planes_out = 0, wide_mask = 0, narrowed = 0;
+    int planes_out = 0, wide_mask = 0, narrowed = 0, crosswalked = 0;
     for (int l = 0; l < kLanes; ++l) {
         if (!out[l]) continue;
         const HostPipe::Lane& ln = p.lane[l];
         const auto& sb = sl.lane[l];
-        if (ln.dtype) {
-            NarrowArgs na{sb.dev.p, sb.nar.p, n, ln.cols, planes ? n : 0, ln.scale, ln.offset, ln.has_fill, ln.fill};
-            const bool wide = narrow_wide_ok(na.src, na.dst, launch::narrow_dst_bytes(ln.kind, ln.dtype), n, ln.cols, na.stride);
+        if (ln.converts()) {
+            NarrowArgs na{sb.dev.p, sb.nar.p, n, ln.cols, planes ? n : 0, ln.scale, ln.offset, ln.has_fill, ln.fill, ln.table, ln.fill_id};
+            const int dst_bytes = launch::narrow_dst_bytes(ln.kind, ln.dtype, ln.table != nullptr);
+            const bool wide = narrow_wide_ok(na.src, na.dst, dst_bytes, n, ln.cols, na.stride);
             HIP_TRY(launch::narrow(na, ln.kind, ln.dtype, wide, ix->st_run));
             narrowed = 1;
+            if (ln.table) crosswalked = 1;
             if (wide) wide_mask |= 1 << l;
             if (planes) planes_out += ln.cols;
         } else if (planes) {
@@ -2600,7 +2610,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     }
     {
         const int64_t rec[8] = {narrowed, n, p.lane[kLaneIdx].dtype, p.lane[kLaneDist].dtype, p.lane[kLanePred].dtype, 0,
-                                wide_mask, 0};  // ([5]: pipe_enqueue_d2h)
+                                wide_mask, crosswalked};  // ([5]: pipe_enqueue_d2h)
         std::copy(std::begin(rec), std::end(rec), ix->last_narrow);
     }
     {
@@ -2990,6 +3000,29 @@ extern "C" int sknnr_narrow(const void* src, int32_t kind, int64_t n, int32_t c,
     NarrowArgs a{src, dst, n, c, dst_stride, scale, offset, has_fill != 0, fill};
     const bool wide = narrow_wide_ok(src, dst, esz, n, c, dst_stride);
     HIP_TRY(launch::narrow(a, kind, dst_dtype, wide, (hipStream_t)stream));
+    if (out_wide) *out_wide = wide ? 1 : 0;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_narrow_ids(const int64_t* src, int64_t n, int32_t c, const int64_t* table, int64_t n_table,
+                                int32_t has_fill, int64_t fill_id, void* dst, int32_t dst_dtype, int64_t dst_stride,
+                                int32_t device, void* stream, int32_t* out_wide) {
+    if (out_wide) *out_wide = 0;
+    const int esz = launch::narrow_dst_bytes(kNarrowIndex, dst_dtype, true);
+    if (!esz) return fail(SKNNR_ERR_INVALID, "dst_dtype = %d: ids leave as int64 (0) or int32 (SKNNR_DTYPE_I32)", dst_dtype);
+    if (!table) return fail(SKNNR_ERR_INVALID, "table is NULL");
+    if (n_table < 1) return fail(SKNNR_ERR_INVALID, "n_table must be >= 1");
+    if (n < 0) return fail(SKNNR_ERR_INVALID, "n must be >= 0");
+    if (c < 1 || c > kMaskMaxCols) return fail(SKNNR_ERR_INVALID, "c = %d outside [1, %d]", c, kMaskMaxCols);
+    if (dst_stride != 0 && dst_stride < n)
+        return fail(SKNNR_ERR_INVALID, "the stride between planes (%lld) is below n (%lld)", (long long)dst_stride, (long long)n);
+    if (n == 0) return SKNNR_OK;
+    if (!src || !dst) return fail(SKNNR_ERR_INVALID, "src / dst is NULL");
+    if (n > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 pixels in one call");
+    HIP_TRY(hipSetDevice(device));
+    NarrowArgs a{src, dst, n, c, dst_stride, nullptr, nullptr, has_fill != 0, 0.0, (const long*)table, (long)fill_id};
+    const bool wide = narrow_wide_ok(src, dst, esz, n, c, dst_stride);
+    HIP_TRY(launch::narrow(a, kNarrowIndex, dst_dtype, wide, (hipStream_t)stream));
     if (out_wide) *out_wide = wide ? 1 : 0;
     return SKNNR_OK;
 }
@@ -3567,6 +3600,24 @@ extern "C" int sknnr_stream_set_output(sknnr_stream* s, int32_t idx_dtype, int32
     }
     pl.has_fill = has_pred_fill != 0;
     pl.fill = pred_fill;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_set_id_table(sknnr_stream* s, const int64_t* table, int64_t n_table, int64_t fill_id) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    if (!table) return fail(SKNNR_ERR_INVALID, "table is NULL");
+    HostPipe& p = s->pipe;
+    if (n_table != p.ix->n_ref)
+        return fail(SKNNR_ERR_INVALID, "n_table = %lld: the handle has %lld reference rows", (long long)n_table, (long long)p.ix->n_ref);
+    std::lock_guard<std::mutex> lock(p.ix->mtx);
+    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_id_table is allowed only before the first push");
+    HIP_TRY(hipSetDevice(p.ix->device));
+    HIP_TRY(p.ix->s_id_table.ensure((size_t)n_table));
+    HIP_TRY(hipMemcpy(p.ix->s_id_table.p, table, (size_t)n_table * sizeof(long), hipMemcpyHostToDevice));
+    HostPipe::Lane& il = p.lane[kLaneIdx];
+    il.table = p.ix->s_id_table.p;
+    il.has_fill = 1;  // (every negative index of a tile is the nodata expansion's fill_index)
+    il.fill_id = fill_id;
     return SKNNR_OK;
 }
 
