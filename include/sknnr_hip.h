@@ -732,6 +732,20 @@ int sknnr_debug_last_rescue(const sknnr_index* index, int64_t out[8]);
 int sknnr_debug_hamming_candidates(const sknnr_index* index, int32_t* cnt, int32_t* ids, int64_t n);
 
 /*
+ * Debug only.  The candidate lists the first-generation Euclidean pre-filter (coarse_kernel) wrote for the first n rows of
+ * the last device chunk of the most recent call, as stored (n at most that chunk's rows with their padding), M = out[2] of
+ * sknnr_debug_last_prefilter.
+ * Host memory:
+ *   val  (n, 2, M) float32  ranking values: the list of the lane half that owns image positions p % 8 < 4, then the other's
+ *   pos  (n, 2, M) int32    image positions, -1 = no row (a leading sentinel, value -FLT_MAX, or an unused slot, FLT_MAX)
+ *   perm (n_ref)   int32    image position -> reference row of the first-generation image
+ * SKNNR_ERR_UNSUPPORTED when the last call ran no Euclidean pre-filter, filed merged candidate records instead of lists, or
+ * ran the second-generation kernel (its lists are filed by position of a bucketed call, in positions of its own image);
+ * SKNNR_ERR_INVALID on a NULL argument or n beyond the chunk.  Reads only; synchronises the device.
+ */
+int sknnr_debug_coarse_candidates(const sknnr_index* index, int64_t n, float* val, int32_t* pos, int32_t* perm);
+
+/*
  * Debug only.  The query preparation launch (prep_queries_direct_kernel / prep_queries_kernel) of the most recent call on
  * the handle (its last device chunk), so that a test can prove which kernel prepared its rows.  Host memory, no device work:
  *   out[0] 0 = no preparation kernel ran (then out[1 .. 7] = 0), 1 = prep_queries_direct_kernel, 2 = prep_queries_kernel (LDS)

@@ -113,6 +113,7 @@ EXPORTED_SYMBOLS = (
     "sknnr_debug_last_scan",
     "sknnr_debug_last_rescue",
     "sknnr_debug_hamming_candidates",
+    "sknnr_debug_coarse_candidates",
     "sknnr_debug_last_prep",
     "sknnr_debug_query_prep",
     "sknnr_debug_image_constants",
@@ -265,6 +266,7 @@ def load(build_if_missing: bool = False):
     if hasattr(lib, "sknnr_debug_last_rescue"):  # (likewise)
         lib.sknnr_debug_last_rescue.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_hamming_candidates.argtypes = [vp, vp, vp, c_int64]
+    lib.sknnr_debug_coarse_candidates.argtypes = [vp, c_int64, vp, vp, vp]
     if hasattr(lib, "sknnr_debug_last_prep"):  # (likewise)
         lib.sknnr_debug_last_prep.argtypes = [vp, POINTER(c_int64)]
         lib.sknnr_debug_query_prep.argtypes = [vp, c_int64, vp, vp, vp, vp, vp, vp]
@@ -717,6 +719,17 @@ class Index:
         ids = np.empty((n, 192), dtype=np.int32)
         check(load().sknnr_debug_hamming_candidates(self.handle, _host_ptr(cnt), _host_ptr(ids), int(n)))
         return cnt, ids
+
+    def debug_coarse_candidates(self, n: int):
+        """Debug only: ``(val, pos, perm)`` the first-generation Euclidean pre-filter wrote for the first ``n`` rows of the last call's last
+        device chunk (sknnr_debug_coarse_candidates): ``(n, 2, M)`` float32 ranking values and int32 image positions as
+        stored (lane half 0's list first; -1: sentinel or unused slot), and the first-generation position -> row table."""
+        m = self.debug_last_prefilter()["m_list"]
+        val = np.empty((n, 2, m), dtype=np.float32)
+        pos = np.empty((n, 2, m), dtype=np.int32)
+        perm = np.empty(self.n_ref, dtype=np.int32)
+        check(load().sknnr_debug_coarse_candidates(self.handle, int(n), _host_ptr(val), _host_ptr(pos), _host_ptr(perm)))
+        return val, pos, perm
 
     PREP_FIELDS = ("kernel", "rows_per_block", "x_dtype", "nq", "nq_pad", "xt_written", "cells_by", "affine_bits")
 

@@ -4019,6 +4019,30 @@ extern "C" int sknnr_debug_hamming_candidates(const sknnr_index* cix, int32_t* c
     return SKNNR_OK;
 }
 
+extern "C" int sknnr_debug_coarse_candidates(const sknnr_index* cix, int64_t n, float* val, int32_t* pos, int32_t* perm) {
+    if (!cix || !val || !pos || !perm) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    const int64_t* r = ix->last_prefilter;
+    if (!r[0]) return fail(SKNNR_ERR_UNSUPPORTED, "the last call ran no Euclidean pre-filter");
+    if (ix->last_finalize[1]) return fail(SKNNR_ERR_UNSUPPORTED, "the last call filed merged candidate records, not lists");
+    // (coarse2_kernel files its lists by position of a bucketed call and in positions of its own image: nothing reads them yet)
+    if (r[0] != 1) return fail(SKNNR_ERR_UNSUPPORTED, "the last call ran the second-generation pre-filter: its lists are not served");
+    // (the workspace is the handle's: no later call has touched it, or the record would be zero)
+    const int64_t rows = r[5];
+    if (n < 0 || n > rows)
+        return fail(SKNNR_ERR_INVALID, "n = %ld rows, the last device chunk has %ld with its padding", (long)n, (long)rows);
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t entries = (size_t)n * 2 * (size_t)r[2];
+    if (entries) {
+        HIP_TRY(hipMemcpy(val, ix->cand_val.p, entries * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(pos, ix->cand_idx.p, entries * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(hipMemcpy(perm, ix->perm.p, (size_t)ix->n_ref * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return SKNNR_OK;
+}
+
 extern "C" int sknnr_debug_last_prep(const sknnr_index* cix, int64_t out[8]) {
     if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
     sknnr_index* ix = const_cast<sknnr_index*>(cix);

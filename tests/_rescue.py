@@ -10,11 +10,17 @@ CAP = 16  # kRescueCap: candidates per listed row (sknnr_amd/csrc/rescue.hip.h)
 F32_INF = np.float32(np.inf)
 
 
-def certificate_terms(qn, ymax, s, d, ks, mu2):
-    """eps and noise of finalize_core for a query with |q'|^2 = qn: second-generation eps_c = (12 + 2 ks) 2^-24."""
+def eps_units(ks, generation=2):
+    """The certificate's error budget in units of 2^-24 (sknnr_hip.hip: eps_units, first generation; eps_units2, second)."""
+    return 11.0 + 6.0 * ks if generation == 1 else 12.0 + 2.0 * ks
+
+
+def certificate_terms(qn, ymax, s, d, ks, mu2, generation=2):
+    """eps and noise of finalize_core for a query with |q'|^2 = qn (scalars or arrays): eps_c = eps_units 2^-24, by default
+    the second generation's (12 + 2 ks)."""
     qn, ymax, s, mu2 = (np.float64(v) for v in (qn, ymax, s, mu2))
     nrm = np.sqrt(qn) + ymax
-    eps = np.float64((12.0 + 2.0 * ks) * 2.0 ** -24) * nrm * nrm
+    eps = np.float64(eps_units(ks, generation) * 2.0 ** -24) * nrm * nrm
     nr = nrm * (np.float64(1.0) / s) + mu2
     noise = np.float64((d + 4) * 2.0 ** -53) * nr * nr
     return eps, noise

@@ -86,8 +86,56 @@ def test_argument_errors_without_touching_a_device(native):
     assert lib.sknnr_stream_push(None, None, 1, None, None, None) == native.ERR_INVALID
     assert lib.sknnr_stream_flush(None) == native.ERR_INVALID
     assert lib.sknnr_hamming_distances(None, None, 0, None, 1, None, 0, None) == native.ERR_INVALID
+    assert lib.sknnr_debug_coarse_candidates(None, 1, None, None, None) == native.ERR_INVALID
+    assert b"NULL" in lib.sknnr_last_error()
     assert lib.sknnr_stream_end(None, None) == 0  # NULL is allowed
     lib.sknnr_index_destroy(None)  # NULL is allowed
+
+
+@pytest.mark.gpu
+def test_coarse_candidates_errors(native):
+    """sknnr_debug_coarse_candidates: the lists of the last chunk with its padding rows; INVALID on a NULL output or beyond
+    the chunk; UNSUPPORTED after a call that ran no pre-filter, filed merged candidate records or ran the second-generation kernel."""
+    from sknnr_amd import synth
+
+    lib = native.load()
+    x_ref, _, x_q = synth.make_problem(1_300, 100, 13, t=1)
+    ix = native.Index(x_ref)
+    try:
+        ix.kneighbors_host(x_q, ix.make_opts(5))
+        assert ix.debug_last_prefilter()["generation"] == 1 and ix.debug_last_finalize()["record"] == 0
+        val, pos, perm = ix.debug_coarse_candidates(6_144)  # the padding rows are the chunk's too
+        assert val.shape == pos.shape == (6_144, 2, 6) and sorted(perm.tolist()) == list(range(1_300))
+        # (5 neighbours on lists of 6: no sentinel, and 650 rows on either lane half fill both lists of a live row)
+        assert (pos[:100] >= 0).all() and (pos[:100] < 1_300).all() and np.isfinite(val[:100]).all()
+        with pytest.raises(native.HipBackendError, match="the last device chunk has 6144") as e:
+            ix.debug_coarse_candidates(6_145)
+        assert e.value.code == native.ERR_INVALID
+        for args in ((None, pos, perm), (val, None, perm), (val, pos, None)):
+            ptrs = [None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in args]
+            assert lib.sknnr_debug_coarse_candidates(ix.handle, 1, *ptrs) == native.ERR_INVALID
+        ix.kneighbors_host(x_q, ix.make_opts(40))  # more neighbours than the pre-filter serves: the exact scan alone
+        assert ix.debug_last_prefilter()["generation"] == 0
+        with pytest.raises(native.HipBackendError, match="no Euclidean pre-filter") as e:
+            ix.debug_coarse_candidates(1)
+        assert e.value.code == native.ERR_UNSUPPORTED
+    finally:
+        ix.close()
+    x_ref, _, x_q = synth.make_problem(4_000, 100, 13, t=1)
+    ix = native.Index(x_ref)
+    try:
+        ix.kneighbors_host(x_q, ix.make_opts(5))
+        assert ix.debug_last_finalize()["record"] == 1
+        with pytest.raises(native.HipBackendError, match="merged candidate records") as e:
+            ix.debug_coarse_candidates(1)
+        assert e.value.code == native.ERR_UNSUPPORTED
+        ix.kneighbors_host(x_q, ix.make_opts(7))  # second-generation lists of 8: filed by position, not served
+        assert ix.debug_last_prefilter()["generation"] == 2 and ix.debug_last_finalize()["record"] == 0
+        with pytest.raises(native.HipBackendError, match="second-generation") as e:
+            ix.debug_coarse_candidates(1)
+        assert e.value.code == native.ERR_UNSUPPORTED
+    finally:
+        ix.close()
 
 
 @pytest.mark.skipif("__import__('sknnr_amd')._native.device_count() > 0")

@@ -146,10 +146,12 @@ def test_larger_k(N, O, k):
     x_ref, y, x_q = _synth(700, 300, 20)
     ix = N.Index(x_ref, y)
     dist, idx = ix.kneighbors_host(x_q, ix.make_opts(k))
+    assert ix.debug_last_prefilter()["generation"] == (1 if k <= 31 else 0)
     od, oi = O.kneighbors(x_ref, x_q, k, "expanded")
     np.testing.assert_array_equal(idx, oi)
     np.testing.assert_array_equal(dist, od)
     dist, idx = ix.kneighbors_host(None, ix.make_opts(k, exclude_self=True), nq=700)
+    assert ix.debug_last_prefilter()["generation"] == (1 if k + 1 <= 31 else 0)
     od, oi = O.kneighbors(x_ref, None, k, "expanded")
     np.testing.assert_array_equal(idx, oi)
     np.testing.assert_array_equal(dist, od)
@@ -172,10 +174,12 @@ def test_every_launch_geometry(N, O, d, k):
     x_ref, y, x_q = _synth(2600, 1100, d, n_dup_refs=12, n_dup_queries=8)
     ix = N.Index(x_ref, y)
     dist, idx = ix.kneighbors_host(x_q, ix.make_opts(k))
+    assert ix.debug_last_prefilter()["generation"] == 1
     od, oi = O.kneighbors(x_ref, x_q, k, "expanded")
     np.testing.assert_array_equal(idx, oi)
     np.testing.assert_array_equal(dist, od)
     dist, idx = ix.kneighbors_host(None, ix.make_opts(k, exclude_self=True), nq=2600)
+    assert ix.debug_last_prefilter()["generation"] == 1
     od, oi = O.kneighbors(x_ref, None, k, "expanded")
     np.testing.assert_array_equal(idx, oi)
     np.testing.assert_array_equal(dist, od)
@@ -265,6 +269,7 @@ def test_tiny_reference_sets(N, O, n_ref):
     ix = N.Index(x_ref, y)
     for k in sorted({1, min(3, n_ref), n_ref if n_ref <= 7 else 5}):
         dist, idx = ix.kneighbors_host(x_q, ix.make_opts(k))
+        assert ix.debug_last_prefilter()["generation"] == 1
         od, oi = O.kneighbors(x_ref, x_q, k, "expanded")
         np.testing.assert_array_equal(idx, oi)
         np.testing.assert_array_equal(dist, od)
