@@ -103,6 +103,18 @@ typedef enum sknnr_weight_mode {
     SKNNR_WEIGHTS_F32_WEIGHTS = 0x200  /* EXPLICIT only: w is float32, np.sum(w, axis=1) runs in binary32 */
 } sknnr_weight_mode;
 
+/* Distance-weight laws: w = law(d) evaluated ON THE DEVICE between the search and the reduction (opts->weight_law), in
+ * place of a Python weights callable on the host.  All float64, every + - * / one IEEE rounding (never fused), so the
+ * weights are numpy's bit for bit (sknnr_amd/csrc/weights.hip.h; sknnr_amd/weights.py states them in numpy).  p0 is the
+ * law's parameter (sknnr_index_set_weight_law_params), finite and > 0; p1 is unused so far. */
+typedef enum sknnr_weight_law {
+    SKNNR_LAW_NONE = 0,            /* no law: the call does what it did before the field existed */
+    SKNNR_LAW_INVERSE = 1,         /* 1 / (p0 + d)           yaImpute's weighting at p0 = 1 */
+    SKNNR_LAW_INVERSE_SQUARED = 2, /* 1 / (p0 + d * d) */
+    SKNNR_LAW_TRIANGULAR = 3,      /* max(0, 1 - d / p0)     compact: a row may be all zero, its prediction is NaN */
+    SKNNR_LAW_EPANECHNIKOV = 4     /* max(0, 1 - (d / p0)^2) compact, likewise */
+} sknnr_weight_law;
+
 typedef struct sknnr_index sknnr_index; /* opaque handle */
 
 /* Per-call options of kneighbors/predict.  Zero-initialise, then set fields. */
@@ -126,7 +138,11 @@ typedef struct sknnr_query_opts {
     int32_t query_dtype;   /* sknnr_dtype of the query rows `q` (0 = float64).  Other types need the MFMA envelope
                               (d <= 128) and a Euclidean formula, or the forest map (formula = HAMMING with
                               apply_affine = 1); they are widened by the kernel that reads them */
-    int32_t reserved_;     /* keep 0 */
+    int32_t weight_law;    /* predict / summarize / streams only: sknnr_weight_law, 0 = none (the field was reserved_,
+                              kept 0).  Non-zero: weight_mode must be SKNNR_WEIGHTS_EXPLICIT (F32_TARGETS allowed,
+                              F32_WEIGHTS not: the laws are float64) and the law must be the one whose parameters the
+                              handle holds (sknnr_index_set_weight_law_params), else SKNNR_ERR_INVALID.  The weights
+                              are then computed on the device from the call's own distances.  Ignored by kneighbors */
     int64_t row_offset;    /* position of query row 0 inside the logical call: key 2 of the reorder is
                               |idx - row| with row counted over the whole call (REF _base.py:171), so a
                               shard or chunk must carry its global offset */
@@ -235,6 +251,16 @@ int sknnr_affine_transform(const double* x, int64_t n, int32_t d_in, const doubl
                            const double* scale, const double* proj, int32_t d, double* out,
                            int32_t device);
 
+/*
+ * The distance-weight law of the handle and its two float64 parameters (they do not fit sknnr_query_opts).  Replaces
+ * KNeighborsRegressor(weights=<callable>) (SKL/neighbors/_base.py:121-127 calls it on the (nq, k) distances) for the laws
+ * of sknnr_weight_law.  A later call whose opts->weight_law is non-zero must name this law and uses these parameters.
+ *   law : SKNNR_LAW_INVERSE .. SKNNR_LAW_EPANECHNIKOV, or SKNNR_LAW_NONE to clear;  p0 finite and > 0;  p1 finite
+ * SKNNR_ERR_INVALID for an unknown law or a bad parameter, and -- unless law and parameters are the ones already held --
+ * while a stream is open on the handle (its tiles read them).
+ */
+int sknnr_index_set_weight_law_params(sknnr_index* index, int32_t law, double p0, double p1);
+
 /* Read back sizes: any pointer may be NULL. */
 int sknnr_index_shape(const sknnr_index* index, int64_t* n_ref, int32_t* d, int32_t* t,
                       int32_t* d_in, int32_t* device);
@@ -274,7 +300,10 @@ int sknnr_kneighbors(sknnr_index* index, const void* q, int64_t nq,
  * from REF _base.py:39 (X=None, independent prediction) and :346-348.
  *   out_pred : (nq, t) float64 in `mem`
  *   out_dist, out_idx : optional (nq, k) outputs of the underlying kneighbors (NULL to skip)
- * With opts->weight_mode == SKNNR_WEIGHTS_EXPLICIT use sknnr_predict_from_neighbors instead.
+ * With opts->weight_mode == SKNNR_WEIGHTS_EXPLICIT use sknnr_predict_from_neighbors instead -- unless opts->weight_law
+ * names the handle's distance-weight law: the weights are then law(out_dist) computed on the device (one further launch
+ * over nq * k elements into a workspace buffer) and the reduction is the explicit one.  The same holds for
+ * sknnr_summarize, sknnr_predict_masked (the law sees the valid rows' distances) and a stream opened with predictions.
  */
 int sknnr_predict(sknnr_index* index, const void* q, int64_t nq, const sknnr_query_opts* opts,
                   double* out_pred, double* out_dist, int64_t* out_idx, int32_t mem, void* stream);
@@ -340,6 +369,24 @@ int sknnr_summarize(sknnr_index* index, const void* q, int64_t nq, const sknnr_q
  *   out[5] t      out[6] weight mode without its flags      out[7] 0
  */
 int sknnr_debug_last_summary(const sknnr_index* index, int64_t out[8]);
+
+/*
+ * Debug only.  The weight-law side of the last reduction the handle launched (the call sknnr_debug_last_summary
+ * describes), so that a test can prove that the device made the weights.  Host memory, no device work:
+ *   out[0] sknnr_weight_law of that reduction (0: none; then out[1 .. 3] describe the reduction all the same)
+ *   out[1] rows      out[2] k      out[3] 1 = weight_law_kernel ran for it, 0 = it did not
+ *   out[4 .. 7] 0
+ */
+int sknnr_debug_last_weight_law(const sknnr_index* index, int64_t out[8]);
+
+/*
+ * Debug only.  The law kernel alone, no handle: out[e] = law(dist[e]) for n elements with parameters p0, p1; dist and
+ * out in `mem` (host: staged; device: on `device`, default stream).  Returns when out is written.  SKNNR_ERR_INVALID for
+ * an unknown law (SKNNR_LAW_NONE included), n < 0 and NULL pointers; n == 0 is SKNNR_OK.  The parameters are not
+ * checked: the kernel evaluates the expressions as they stand.
+ */
+int sknnr_debug_weight_law(int32_t law, double p0, double p1, const double* dist, int64_t n, double* out, int32_t mem,
+                           int32_t device);
 
 /*
  * Full weighted-Hamming distance rows: out[i, j] = distance between query row rows[i] and reference row j, in the

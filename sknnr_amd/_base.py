@@ -26,6 +26,7 @@ from sklearn.utils.validation import _is_arraylike, check_is_fitted, validate_da
 
 from . import _config, _native
 from ._engine import KNNEngine, default_device, is_torch_cuda_tensor
+from .weights import DistanceWeights
 
 # Element types query rows may keep on their way to the device (include/sknnr_hip.h, sknnr_dtype): the kernel that reads
 # them widens to float64, exactly -- the reference's host-side conversion (validate_data(dtype=FLOAT_DTYPES) followed by
@@ -744,7 +745,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
     @staticmethod
     def _refuse_callable_weights(feature, how="tile by tile"):
         raise NotImplementedError(f"{feature} not supported with callable weights: the callable runs on the host between "
-                                  f"the search and the reduction, {how}; use 'uniform' or 'distance'")
+                                  f"the search and the reduction, {how}; use 'uniform', 'distance' or a law of "
+                                  "sknnr_amd.weights (evaluated on the device)")
 
     def _stream_tiles(self, tiles, validate, k, *, apply_affine, weights, return_distance,
                       use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False, output=None,
@@ -1070,7 +1072,12 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         (``dist`` may be None) are preallocated arrays under the rules of its ``out`` -- with ``layout="bands"`` they
         share ``N`` with ``out``, and the arrays come all or none: the planes of one tile leave with one stride.  An
         output without an array is collected tile by tile and returned concatenated.  ``pred`` is what the call returns without ``return_neighbors``.  Callable weights
-        and the host-side tie policies are refused; so is any of these keywords without ``return_neighbors=True``."""
+        and the host-side tie policies are refused; so is any of these keywords without ``return_neighbors=True``.
+
+        An estimator whose ``weights`` is a law of :mod:`sknnr_amd.weights` (``InverseDistance``, ...) is not a
+        "callable" in the sense above: the device evaluates the law, and every keyword here applies as for
+        ``weights="distance"``.  A compact law (``Triangular``, ``Epanechnikov``) predicts NaN where all k neighbours lie
+        at or beyond its bandwidth, so an integer ``out_dtype`` then needs ``out_nodata`` even without ``nodata``."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         neighbors = self._neighbor_request(return_neighbors, return_distance, return_dataframe_index, neighbors_out,
@@ -1090,23 +1097,28 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                         statistic=None, neighbors=None):
         """``neighbors``: :meth:`_neighbor_request`, or None -- predictions alone, exactly as before the keyword existed."""
         weights = "uniform" if self.weights is None else self.weights
+        # A distance-weight law (sknnr_amd.weights) is evaluated on the device inside the stream, so it goes wherever
+        # "distance" goes; any other callable runs on the host and keeps every refusal below.
+        law = isinstance(weights, DistanceWeights)
+        host_callable = callable(weights) and not law
         output = None
         if typed is not None:
             n_targets = 1 if self._y.ndim == 1 else self._y.shape[1]
-            output = normalize_typed_output(*typed, n_targets, nodata is not None)
+            # (a compact law can give an all-zero row: NaN predictions occur without any mask)
+            output = normalize_typed_output(*typed, n_targets, nodata is not None or (law and weights.can_vanish))
         if neighbors is not None:
-            if callable(weights):
+            if host_callable:
                 self._refuse_callable_weights("return_neighbors is")
             return self._predict_chunks_neighbors(tiles, validate, weights, neighbors, apply_affine=apply_affine, out=out,
                                                   owner=owner, nodata=nodata, bands=bands, output=output,
                                                   statistic=statistic)
-        if callable(weights) and output:
+        if host_callable and output:
             self._refuse_callable_weights("typed outputs are")
-        if callable(weights) and bands:
+        if host_callable and bands:
             self._refuse_callable_weights("layout='bands' is", "on row-major neighbours")
-        if callable(weights) and nodata is not None:
+        if host_callable and nodata is not None:
             self._refuse_callable_weights("nodata is")
-        if callable(weights):  # a Python callable runs between the search and the reduction: tile by tile
+        if host_callable:  # a Python callable runs between the search and the reduction: tile by tile
             # (the reorder's second key is the row's position in the WHOLE call: carry it from tile to tile)
             preds, row = [], 0
             for t in tiles:

@@ -13,6 +13,7 @@ import os
 import numpy as np
 
 from . import _native
+from .weights import DistanceWeights
 
 __all__ = ["KNNEngine", "default_device", "set_default_device", "is_torch_cuda_tensor"]
 
@@ -73,6 +74,7 @@ class KNNEngine:
         self.d_in = self.d
         self.has_affine = False
         self.has_forest = False
+        self._law_key = None  # (law code, p0, p1) the handle holds: weight_law()
 
     def close(self):
         self._index.close()
@@ -119,13 +121,13 @@ class KNNEngine:
 
     # ------------------------------------------------------------------------------------
     def _opts(self, k, *, exclude_self, deterministic, decimals, formula, apply_affine,
-              weight_mode=_native.WEIGHTS_UNIFORM, row_offset=0, check_finite=False, query_dtype=0):
+              weight_mode=_native.WEIGHTS_UNIFORM, row_offset=0, check_finite=False, query_dtype=0, weight_law=0):
         return self._index.make_opts(
             k, exclude_self=exclude_self, deterministic=deterministic, decimals=decimals,
             formula={"direct": _native.FORMULA_DIRECT, "hamming": _native.FORMULA_HAMMING}.get(
                 formula, _native.FORMULA_EXPANDED),
             apply_affine=apply_affine, weight_mode=weight_mode, row_offset=row_offset,
-            check_finite=check_finite, query_dtype=query_dtype)
+            check_finite=check_finite, query_dtype=query_dtype, weight_law=weight_law)
 
     def query_dtype_code(self, X, formula="expanded", apply_affine=False) -> int:
         """The sknnr_dtype under which the rows of ``X`` can be handed to the library as they are (float32, int16, uint16,
@@ -232,6 +234,18 @@ class KNNEngine:
             mode |= _native.WEIGHTS_F32_WEIGHTS
         return mode
 
+    def weight_law(self, weights) -> int:
+        """The native code of a :class:`sknnr_amd.weights.DistanceWeights` instance -- its parameters are then on the
+        handle (uploaded when they change) and a call made with ``weight_mode("explicit")`` and this code evaluates the
+        law on the device -- or 0 for anything else (strings, plain callables)."""
+        if not isinstance(weights, DistanceWeights):
+            return 0
+        key = (weights.code, *weights.params)
+        if key != self._law_key:
+            self._index.set_weight_law_params(*key)
+            self._law_key = key
+        return weights.code
+
     def pred_dtype(self, weights):
         """scikit-learn's result dtype: the float32 targets' own under uniform weights, else float64."""
         return np.float32 if self.y32 and weights in (None, "uniform") else np.float64
@@ -326,18 +340,19 @@ class KNNEngine:
         choosing what is reduced from the neighbours.  Always float64 ``(nq, t)``."""
         if self.t < 1:
             raise ValueError("the engine was built without targets")
-        if callable(weights):  # (as predict: the callable maps the distances to weights on the host)
+        law = self.weight_law(weights)  # (a distance-weight law: the device evaluates it, in the single call below)
+        if callable(weights) and not law:  # (as predict: the callable maps the distances to weights on the host)
             dist, idx = self.kneighbors(X, k, exclude_self=exclude_self, deterministic=deterministic,
                                         decimals=decimals, formula=formula, apply_affine=apply_affine,
                                         row_offset=row_offset, n_self_rows=n_self_rows, check_finite=check_finite)
             return self.summarize_from_neighbors(dist, idx, weights, stat)
-        if weights not in _WEIGHT_MODES:
+        if not law and weights not in _WEIGHT_MODES:
             raise ValueError(f"weights not recognized: should be 'uniform', 'distance', or a callable; got {weights!r}")
         qdt = self.query_dtype_code(X, formula, apply_affine)
         opts = self._opts(k, exclude_self=exclude_self, deterministic=deterministic, decimals=decimals,
                           formula=formula, apply_affine=apply_affine and X is not None,
-                          weight_mode=self.weight_mode(weights), row_offset=row_offset,
-                          check_finite=check_finite and X is not None, query_dtype=qdt)
+                          weight_mode=self.weight_mode("explicit" if law else weights), row_offset=row_offset,
+                          check_finite=check_finite and X is not None, query_dtype=qdt, weight_law=law)
         if X is None:
             nq = self.n_ref - row_offset if n_self_rows is None else int(n_self_rows)
             return self._index.summarize_host(None, opts, stat, nq=nq)
@@ -361,33 +376,37 @@ class KNNEngine:
                 formula="expanded", apply_affine=False, row_offset=0, n_self_rows=None, check_finite=False,
                 nodata=None):
         """Weighted multi-output mean of the neighbours' targets, in the dtype scikit-learn returns
-        (:meth:`pred_dtype`).  ``nodata`` as in :meth:`kneighbors`: masked rows are predicted NaN."""
+        (:meth:`pred_dtype`).  ``nodata`` as in :meth:`kneighbors`: masked rows are predicted NaN.  ``weights``:
+        ``"uniform"``, ``"distance"``, a :class:`sknnr_amd.weights.DistanceWeights` law (one device call: the law kernel
+        makes the weights from the call's own distances) or any other callable (search, the callable on the host,
+        reduction: three steps)."""
         if self.t < 1:
             raise ValueError("the engine was built without targets")
         if nodata is not None:
             if X is None:
                 raise ValueError("nodata needs query rows: X=None has none")
-            if callable(weights):
+            if callable(weights) and not isinstance(weights, DistanceWeights):
                 raise NotImplementedError("nodata is not supported with callable weights")
             nodata = np.ascontiguousarray(nodata, dtype=np.float64).reshape(-1)
             if nodata.size != X.shape[1]:
                 raise ValueError(f"nodata must hold one value per column of X ({X.shape[1]}), got {nodata.size}")
-        if callable(weights):
+        law = self.weight_law(weights)  # (a distance-weight law: the device evaluates it, in the single call below)
+        if callable(weights) and not law:
             # A Python callable cannot run on the device: find the neighbours on the GPU, let
             # the callable map the (nq, k) distances to weights on the host, reduce on the GPU.
             dist, idx = self.kneighbors(X, k, exclude_self=exclude_self, deterministic=deterministic,
                                         decimals=decimals, formula=formula, apply_affine=apply_affine,
                                         row_offset=row_offset, n_self_rows=n_self_rows, check_finite=check_finite)
             return self.predict_from_neighbors(dist, idx, weights)
-        if weights not in _WEIGHT_MODES:
+        if not law and weights not in _WEIGHT_MODES:
             raise ValueError(f"weights not recognized: should be 'uniform', 'distance', or a callable; got {weights!r}")
-        mode = self.weight_mode(weights)
-        to32 = self.pred_dtype(weights) == np.float32
+        mode = self.weight_mode("explicit" if law else weights)
+        to32 = self.pred_dtype(weights) == np.float32  # (a law's result is float64, as any callable's)
         qdt = self.query_dtype_code(X, formula, apply_affine)
         opts = self._opts(k, exclude_self=exclude_self, deterministic=deterministic, decimals=decimals,
                           formula=formula, apply_affine=apply_affine and X is not None,
                           weight_mode=mode, row_offset=row_offset, check_finite=check_finite and X is not None,
-                          query_dtype=qdt)
+                          query_dtype=qdt, weight_law=law)
         if X is None:
             nq = self.n_ref - row_offset if n_self_rows is None else int(n_self_rows)
             pred = self._index.predict_host(None, opts, nq=nq)
@@ -466,7 +485,8 @@ class KNNEngine:
                     nodata=None, fill_index=-1, output=None, statistic=None, id_table=None, fill_id=-1):
         """A :class:`sknnr_amd._native.QueryStream` over host tiles: ``push(tile)`` keeps the PCIe
         pipeline full across tiles and carries the global row offset.  ``weights`` (``"uniform"`` /
-        ``"distance"``) also asks for predictions: float64 arrays, holding binary32 values where
+        ``"distance"`` / a :class:`sknnr_amd.weights.DistanceWeights` law, evaluated on the device tile by tile) also
+        asks for predictions: float64 arrays, holding binary32 values where
         :meth:`pred_dtype` is float32.  ``nodata`` (float64, one value per column of the tiles): every tile is masked on
         the device, masked rows get ``fill_index`` / NaN and the row offset counts valid rows only.  ``output``: keyword
         arguments of :meth:`sknnr_amd._native.QueryStream.set_output` (typed results, narrowed on the device).
@@ -475,12 +495,14 @@ class KNNEngine:
         reference row): the indices leave as ``id_table[idx]``, looked up on the device; keep ``fill_index`` negative,
         and masked rows get ``fill_id``."""
         want_pred = weights is not None
-        if want_pred and weights not in _WEIGHT_MODES:
-            raise ValueError("a stream predicts with 'uniform' or 'distance' weights only")
+        law = self.weight_law(weights)  # (a distance-weight law: every tile's weights are made on the device)
+        if want_pred and not law and weights not in _WEIGHT_MODES:
+            raise ValueError("a stream predicts with 'uniform' or 'distance' weights, or a sknnr_amd.weights law, only")
         opts = self._opts(k, exclude_self=False, deterministic=deterministic, decimals=decimals,
                           formula=formula, apply_affine=apply_affine,
-                          weight_mode=self.weight_mode(weights) if want_pred else _native.WEIGHTS_UNIFORM,
-                          row_offset=row_offset, check_finite=check_finite, query_dtype=query_dtype)
+                          weight_mode=(self.weight_mode("explicit" if law else weights) if want_pred
+                                       else _native.WEIGHTS_UNIFORM),
+                          row_offset=row_offset, check_finite=check_finite, query_dtype=query_dtype, weight_law=law)
         if statistic is not None and not want_pred:
             raise ValueError("statistics need a stream that predicts: pass weights")
         return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred, nodata=nodata, fill_index=fill_index,

@@ -30,6 +30,11 @@ WEIGHTS_F32_WEIGHTS = 0x200
 # sknnr_statistic (include/sknnr_hip.h): the per-target summaries of the neighbours
 STATISTICS = {"mean": 0, "mode": 1, "min": 2, "max": 3, "nearest": 4, "std": 5}
 
+# sknnr_weight_law (include/sknnr_hip.h): the distance-weight laws the device evaluates, by the header's short names; the
+# classes of sknnr_amd.weights carry theirs as ``name`` / ``code``
+WEIGHT_LAWS = {"inverse": 1, "inverse_squared": 2, "triangular": 3, "epanechnikov": 4}
+WEIGHT_LAW_NONE = 0
+
 ERR_INVALID = -1
 ERR_K_TOO_LARGE = -2
 ERR_NO_TARGETS = -3
@@ -68,6 +73,7 @@ EXPORTED_SYMBOLS = (
     "sknnr_index_set_forest",
     "sknnr_forest_apply",
     "sknnr_affine_transform",
+    "sknnr_index_set_weight_law_params",
     "sknnr_index_shape",
     "sknnr_get_stats",
     "sknnr_reset_stats",
@@ -79,6 +85,8 @@ EXPORTED_SYMBOLS = (
     "sknnr_summarize",
     "sknnr_stream_set_statistics",
     "sknnr_debug_last_summary",
+    "sknnr_debug_last_weight_law",
+    "sknnr_debug_weight_law",
     "sknnr_hamming_distances",
     "sknnr_shard_candidates",
     "sknnr_merge_shards",
@@ -131,7 +139,7 @@ class QueryOpts(ctypes.Structure):
         ("weight_mode", c_int32),
         ("check_finite", c_int32),
         ("query_dtype", c_int32),
-        ("reserved_", c_int32),
+        ("weight_law", c_int32),  # sknnr_weight_law, 0 = none (the field was reserved_)
         ("row_offset", c_int64),
     ]
 
@@ -251,6 +259,9 @@ def load(build_if_missing: bool = False):
         lib.sknnr_summarize.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), vp, vp, vp, vp, c_int32, vp]
         lib.sknnr_stream_set_statistics.argtypes = [vp, vp, c_int32]
         lib.sknnr_debug_last_summary.argtypes = [vp, POINTER(c_int64)]
+    lib.sknnr_index_set_weight_law_params.argtypes = [vp, c_int32, c_double, c_double]
+    lib.sknnr_debug_last_weight_law.argtypes = [vp, POINTER(c_int64)]
+    lib.sknnr_debug_weight_law.argtypes = [c_int32, c_double, c_double, vp, c_int64, vp, c_int32, c_int32]
     lib.sknnr_hamming_distances.argtypes = [vp, vp, c_int64, vp, c_int64, vp, c_int32, vp]
     lib.sknnr_shard_candidates.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int64, vp, vp, c_int32, vp]
     lib.sknnr_merge_shards.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int32, vp, vp, vp, vp, c_int32, vp]
@@ -400,10 +411,18 @@ class Index:
     @staticmethod
     def make_opts(k, exclude_self=False, deterministic=True, decimals=10, formula=FORMULA_EXPANDED,
                   apply_affine=False, weight_mode=WEIGHTS_UNIFORM, row_offset=0,
-                  check_finite=False, query_dtype=0) -> QueryOpts:
+                  check_finite=False, query_dtype=0, weight_law=WEIGHT_LAW_NONE) -> QueryOpts:
+        """``weight_law``: a ``WEIGHT_LAWS`` code -- the predictions' weights are that law of the call's distances,
+        computed on the device with the parameters of :meth:`set_weight_law_params`; ``weight_mode`` is then
+        ``WEIGHTS_EXPLICIT`` (with ``WEIGHTS_F32_TARGETS`` where it applies)."""
         return QueryOpts(int(k), int(bool(exclude_self)), int(bool(deterministic)), int(decimals),
                          int(formula), int(bool(apply_affine)), int(weight_mode), int(bool(check_finite)),
-                         int(query_dtype), 0, int(row_offset))
+                         int(query_dtype), int(weight_law), int(row_offset))
+
+    def set_weight_law_params(self, law: int, p0: float = 0.0, p1: float = 0.0) -> None:
+        """The handle's distance-weight law (a ``WEIGHT_LAWS`` code, 0 clears) and its two float64 parameters
+        (sknnr_index_set_weight_law_params); calls whose opts name the law use them."""
+        check(load().sknnr_index_set_weight_law_params(self.handle, int(law), float(p0), float(p1)))
 
     def check_finite(self, stream=0) -> None:
         """Poll the non-finite-input flag of device-memory calls made with ``check_finite``
@@ -510,6 +529,15 @@ class Index:
         out = (c_int64 * 8)()
         check(load().sknnr_debug_last_summary(self.handle, out))
         return dict(zip(self.SUMMARY_FIELDS, (int(v) for v in out)))
+
+    WEIGHT_LAW_FIELDS = ("law", "rows", "k", "ran", "r4", "r5", "r6", "r7")
+
+    def debug_last_weight_law(self) -> dict:
+        """Debug only: the weight-law side of the last reduction of the handle (sknnr_debug_last_weight_law): the law's
+        code (0 none), rows, k, and whether the law kernel ran for it."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_weight_law(self.handle, out))
+        return dict(zip(self.WEIGHT_LAW_FIELDS, (int(v) for v in out)))
 
     # ---- nodata rows (include/sknnr_hip.h, "nodata rows") -----------------------------------
     def kneighbors_masked_host(self, q, opts: QueryOpts, nodata, fill_index=-1, return_distance=True):
@@ -968,6 +996,22 @@ def crosswalk_host(table, idx, device: int = 0):
 def crosswalk_device(table_ptr, n_table, idx_ptr, n, out_ptr, device=0, stream=0):
     check(load().sknnr_crosswalk(c_void_p(table_ptr), n_table, c_void_p(idx_ptr), n, c_void_p(out_ptr),
                                  device, MEM_DEVICE, c_void_p(stream or None)))
+
+
+def debug_weight_law_host(law: int, p0: float, p1: float, dist, device: int = 0) -> np.ndarray:
+    """Debug only: the law kernel alone (sknnr_debug_weight_law) on a host array of distances of any shape; float64
+    weights of that shape."""
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    out = np.empty_like(dist)
+    check(load().sknnr_debug_weight_law(int(law), float(p0), float(p1), _host_ptr(dist), dist.size, _host_ptr(out),
+                                        MEM_HOST, device))
+    return out
+
+
+def debug_weight_law_device(law: int, p0: float, p1: float, dist_ptr, n, out_ptr, device: int = 0) -> None:
+    """The same on device pointers (default stream; returns when ``out`` is written)."""
+    check(load().sknnr_debug_weight_law(int(law), float(p0), float(p1), c_void_p(dist_ptr or None), int(n),
+                                        c_void_p(out_ptr or None), MEM_DEVICE, device))
 
 
 def mask_rows_host(q, nodata, device: int = 0):

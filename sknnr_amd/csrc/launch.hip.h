@@ -1,9 +1,9 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_weights.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
-// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY), templates where they are instantiated.
+// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_WEIGHTS), templates where they are instantiated.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +19,7 @@
 #include "planes.hip.h"
 #include "rescue.hip.h"
 #include "summary.hip.h"
+#include "weights.hip.h"
 
 namespace sknnr {
 namespace launch {
@@ -83,6 +84,10 @@ int narrow_dst_bytes(int kind, int dst_dtype, bool table = false);
 // ---- k_summary.hip: per-target neighbour summaries (summary.hip.h) ----------------------------------------------------------
 // the columns of a.tab (none of them `mean`) of every query; k <= kSummarySmallK: summary_kernel, else summary_wide_kernel
 hipError_t summary(const SummaryArgs& a, hipStream_t st);
+
+// ---- k_weights.hip: distance-weight laws (weights.hip.h) ------------------------------------------------------------------
+// a.w[e] = law(a.dist[e]) for a.n elements; hipErrorInvalidValue for an unknown law
+hipError_t weight_law(const WeightLawArgs& a, hipStream_t st);
 
 // ---- k_coarse1.hip / k_coarse2.hip: the MFMA pre-filters ----------------------------------------------------------------
 struct Coarse1Launch {

@@ -426,6 +426,13 @@ struct sknnr_index {
     const SummaryPlan* summary = nullptr;
     DevBuf<int> c_stat, s_stat;
     int64_t last_summary[8] = {};
+    // distance-weight laws (weights.hip.h): the handle's law and its parameters (sknnr_index_set_weight_law_params), the
+    // weights launch_predict computes for a call that names the law (a workspace buffer behind ev_ws), and the record of
+    // the last reduction (sknnr_debug_last_weight_law): law, rows, k, kernel ran
+    int law_code = 0;
+    double law_p0 = 0.0, law_p1 = 0.0;
+    DevBuf<double> law_w;
+    int64_t last_law[8] = {};
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
     // a ring of call records so that several calls of one benchmark step are summed, not only the last.
@@ -2112,7 +2119,7 @@ int run_forest(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
 // host-buffer pipeline
 // ----------------------------------------------------------------------------------------
 static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, const double* w, long nq, int k,
-                          int mode, double* out, hipStream_t st);
+                          int mode, int law, double* out, hipStream_t st);
 
 // The plan of the call in progress for as long as the scope lives; the caller holds ix->mtx.
 struct SummaryScope {
@@ -2181,13 +2188,13 @@ int mask_finish(sknnr_index* ix, MaskBufs& m, const void* x, long n, long nv, co
         double* dd = d_dist ? d_dist : (d_pred ? m.cd.p : nullptr);
         long* di = d_idx ? d_idx : m.ci.p;
         if ((rc = run_device(ix, x, n, o, dd, di, st))) return rc;
-        if (d_pred && (rc = launch_predict(ix, dd, di, nullptr, n, k, o->weight_mode, d_pred, st))) return rc;
+        if (d_pred && (rc = launch_predict(ix, dd, di, nullptr, n, k, o->weight_mode, o->weight_law, d_pred, st))) return rc;
     } else {
         ExpandArgs e{};
         if (nv > 0) {
             double* cd = (d_dist || d_pred) ? m.cd.p : nullptr;
             if ((rc = run_device(ix, m.cx.p, nv, o, cd, m.ci.p, st))) return rc;
-            if (d_pred && (rc = launch_predict(ix, cd, m.ci.p, nullptr, nv, k, o->weight_mode, m.cp.p, st))) return rc;
+            if (d_pred && (rc = launch_predict(ix, cd, m.ci.p, nullptr, nv, k, o->weight_mode, o->weight_law, m.cp.p, st))) return rc;
             e.valid = m.valid.p;
             e.rank = m.rank.p;
             e.c_idx = m.ci.p;
@@ -2580,7 +2587,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
         rc = run_device(ix, sl.dev_x.p, n, &p.o, dist.f64(), idx.i64(), ix->st_run);
         if (rc) return rc;
         if (want_pred) {
-            rc = launch_predict(ix, dist.f64(), idx.i64(), nullptr, n, k, p.o.weight_mode, pred.f64(), ix->st_run);
+            rc = launch_predict(ix, dist.f64(), idx.i64(), nullptr, n, k, p.o.weight_mode, p.o.weight_law, pred.f64(), ix->st_run);
             if (rc) return rc;
         }
     }
@@ -2802,7 +2809,7 @@ int run_self_rows(sknnr_index* ix, long nq, const sknnr_query_opts* o, double* o
         int rc = run_device(ix, nullptr, n, &oc, ix->dist_stage.p, ix->idx_stage.p, st);
         if (rc) return rc;
         if (out_pred) {
-            rc = launch_predict(ix, ix->dist_stage.p, ix->idx_stage.p, nullptr, n, k, o->weight_mode, ix->pred_stage.p, st);
+            rc = launch_predict(ix, ix->dist_stage.p, ix->idx_stage.p, nullptr, n, k, o->weight_mode, o->weight_law, ix->pred_stage.p, st);
             if (rc) return rc;
             HIP_TRY(hipMemcpyAsync(out_pred + c0 * ix->t, ix->pred_stage.p, (size_t)n * ix->t * sizeof(double), hipMemcpyDeviceToHost, st));
         }
@@ -3296,6 +3303,75 @@ static bool weight_mode_ok(int mode, bool explicit_ok) {
     return (base == SKNNR_WEIGHTS_UNIFORM || base == SKNNR_WEIGHTS_DISTANCE) && !(flags & SKNNR_WEIGHTS_F32_WEIGHTS);
 }
 
+// The distance-weight law of a predicting call: 0 = none (the caller goes on with the checks it always made), 1 = a law
+// that may run (explicit base mode, F32_TARGETS at most, the law the handle holds parameters for), else the failure's status.
+static int weight_law_check(const sknnr_index* ix, const sknnr_query_opts* o) {
+    if (o->weight_law == kLawNone) return 0;
+    if (o->weight_law < 0 || o->weight_law >= kLawCount)
+        return fail(SKNNR_ERR_INVALID, "unknown weight law %d", o->weight_law);
+    if ((o->weight_mode & SKNNR_WEIGHTS_BASE_MASK) != SKNNR_WEIGHTS_EXPLICIT ||
+        (o->weight_mode & ~SKNNR_WEIGHTS_BASE_MASK & ~SKNNR_WEIGHTS_F32_TARGETS))
+        return fail(SKNNR_ERR_INVALID, "a weight law takes weight mode SKNNR_WEIGHTS_EXPLICIT (with F32_TARGETS at most), got %d",
+                    o->weight_mode);
+    if (o->weight_law != ix->law_code)
+        return fail(SKNNR_ERR_INVALID, "opts->weight_law = %d, but the handle holds the parameters of law %d "
+                    "(sknnr_index_set_weight_law_params)", o->weight_law, ix->law_code);
+    return 1;
+}
+
+extern "C" int sknnr_index_set_weight_law_params(sknnr_index* ix, int32_t law, double p0, double p1) {
+    if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (law < 0 || law >= kLawCount) return fail(SKNNR_ERR_INVALID, "unknown weight law %d", law);
+    if (law != kLawNone && !(std::isfinite(p0) && p0 > 0.0 && std::isfinite(p1)))
+        return fail(SKNNR_ERR_INVALID, "weight law %d: p0 must be finite and > 0 and p1 finite (got %g, %g)", law, p0, p1);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (law == ix->law_code && p0 == ix->law_p0 && p1 == ix->law_p1) return SKNNR_OK;
+    if (ix->stream_open)
+        return fail(SKNNR_ERR_INVALID, "a query stream is open on this handle: its tiles read the weight law's parameters");
+    ix->law_code = law;
+    ix->law_p0 = law != kLawNone ? p0 : 0.0;
+    ix->law_p1 = law != kLawNone ? p1 : 0.0;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_weight_law(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "index / out is NULL");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::copy(std::begin(ix->last_law), std::end(ix->last_law), out);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_weight_law(int32_t law, double p0, double p1, const double* dist, int64_t n, double* out,
+                                      int32_t mem, int32_t device) {
+    if (law <= kLawNone || law >= kLawCount) return fail(SKNNR_ERR_INVALID, "unknown weight law %d", law);
+    if (n < 0) return fail(SKNNR_ERR_INVALID, "n must be >= 0");
+    if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
+    if (n == 0) return SKNNR_OK;
+    if (!dist || !out) return fail(SKNNR_ERR_INVALID, "dist / out is NULL");
+    HIP_TRY(hipSetDevice(device));
+    WeightLawArgs a{};
+    a.n = n;
+    a.law = law;
+    a.p0 = p0;
+    a.p1 = p1;
+    DevBuf<double> dd, dw;  // (host memory: freed by their destructors on every return path)
+    if (mem == SKNNR_MEM_HOST) {
+        HIP_TRY(dd.ensure((size_t)n));
+        HIP_TRY(dw.ensure((size_t)n));
+        HIP_TRY(hipMemcpy(dd.p, dist, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        a.dist = dd.p;
+        a.w = dw.p;
+    } else {
+        a.dist = dist;
+        a.w = out;
+    }
+    HIP_TRY(launch::weight_law(a, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if (mem == SKNNR_MEM_HOST) HIP_TRY(hipMemcpy(out, dw.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return SKNNR_OK;
+}
+
 // The table of a one-shot call into the handle's c_stat.  The buffer belongs to the workspace: the previous reduction may
 // still read it, so wait for the workspace's last user first.
 static int summary_upload(sknnr_index* ix, const std::vector<int>& tab, SummaryPlan& plan) {
@@ -3312,8 +3388,29 @@ static int summary_upload(sknnr_index* ix, const std::vector<int>& tab, SummaryP
 
 // The reduction of one launch's rows: the predict kernels give every column its mean unless no column wants it, then the
 // summary kernel overwrites the columns of ix->summary (the call's or the stream's statistics; null: all mean).
+//
+// law (sknnr_weight_law of the call's opts; kLawNone: nothing here changes): the weights are law(dist), written by
+// weight_law_kernel into the handle's law_w in front of the reduction, which then is the explicit one on that buffer
+// (the F32_TARGETS flag stays).  law_w belongs to the workspace: `st` first waits for the workspace's last user.
 static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, const double* w, long nq, int k,
-                          int mode, double* out, hipStream_t st) {
+                          int mode, int law, double* out, hipStream_t st) {
+    if (law != kLawNone) {
+        if (!dist) return fail(SKNNR_ERR_INVALID, "a distance-weight law needs the distances");
+        if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));
+        HIP_TRY(ix->law_w.ensure((size_t)nq * k));
+        WeightLawArgs wa{};
+        wa.dist = dist;
+        wa.w = ix->law_w.p;
+        wa.n = nq * k;
+        wa.law = law;
+        wa.p0 = ix->law_p0;
+        wa.p1 = ix->law_p1;
+        HIP_TRY(launch::weight_law(wa, st));
+        w = ix->law_w.p;
+        mode = SKNNR_WEIGHTS_EXPLICIT | (mode & SKNNR_WEIGHTS_F32_TARGETS);
+    }
+    const int64_t law_rec[8] = {law, nq, k, law != kLawNone ? 1 : 0, 0, 0, 0, 0};
+    std::copy(std::begin(law_rec), std::end(law_rec), ix->last_law);
     const SummaryPlan* sp = ix->summary;
     const bool means = !sp || sp->n_mean > 0;
     if (means) {
@@ -3395,7 +3492,7 @@ static int reduce_from_neighbors(sknnr_index* ix, const double* dist, const int6
     }
     SummaryScope scope(ix, summarize ? &plan : nullptr);
     if (mem == SKNNR_MEM_DEVICE)
-        return launch_predict(ix, dist, (const long*)idx, w, nq, k, mode, out_pred, (hipStream_t)stream);
+        return launch_predict(ix, dist, (const long*)idx, w, nq, k, mode, kLawNone, out_pred, (hipStream_t)stream);
     hipStream_t st = nullptr;
     DevBuf<double> dd, dw, dout;  // freed by their destructors on every return path
     DevBuf<long> di;
@@ -3410,7 +3507,7 @@ static int reduce_from_neighbors(sknnr_index* ix, const double* dist, const int6
         HIP_TRY(dw.ensure((size_t)nq * k));
         HIP_TRY(hipMemcpy(dw.p, w, (size_t)nq * k * sizeof(double), hipMemcpyHostToDevice));
     }
-    int rc = launch_predict(ix, dist ? dd.p : nullptr, di.p, w ? dw.p : nullptr, nq, k, mode, dout.p, st);
+    int rc = launch_predict(ix, dist ? dd.p : nullptr, di.p, w ? dw.p : nullptr, nq, k, mode, kLawNone, dout.p, st);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(out_pred, dout.p, (size_t)nq * ix->t * sizeof(double), hipMemcpyDeviceToHost));
     return SKNNR_OK;
@@ -3441,10 +3538,14 @@ static int search_and_reduce(sknnr_index* ix, const void* q, int64_t nq, const s
     }
     if (!o) return fail(SKNNR_ERR_INVALID, "opts is NULL");
     if (!out_pred && nq > 0) return fail(SKNNR_ERR_INVALID, "out_pred is NULL");
-    if ((o->weight_mode & SKNNR_WEIGHTS_BASE_MASK) == SKNNR_WEIGHTS_EXPLICIT)
-        return fail(SKNNR_ERR_INVALID, "explicit weights go through sknnr_predict_from_neighbors");
-    if (!weight_mode_ok(o->weight_mode, false))
-        return fail(SKNNR_ERR_INVALID, "unknown weight mode %d", o->weight_mode);
+    const int law = weight_law_check(ix, o);
+    if (law < 0) return law;
+    if (!law) {
+        if ((o->weight_mode & SKNNR_WEIGHTS_BASE_MASK) == SKNNR_WEIGHTS_EXPLICIT)
+            return fail(SKNNR_ERR_INVALID, "explicit weights go through sknnr_predict_from_neighbors");
+        if (!weight_mode_ok(o->weight_mode, false))
+            return fail(SKNNR_ERR_INVALID, "unknown weight mode %d", o->weight_mode);
+    }
     static int64_t dummy_idx;
     int rc = validate_call(ix, q, nq, o, out_idx ? out_idx : &dummy_idx);
     if (rc) return rc;
@@ -3475,7 +3576,7 @@ static int search_and_reduce(sknnr_index* ix, const void* q, int64_t nq, const s
         }
         rc = run_device(ix, q, nq, o, dd, di, st);
         if (rc) return rc;
-        return launch_predict(ix, dd, di, nullptr, nq, k, o->weight_mode, out_pred, st);
+        return launch_predict(ix, dd, di, nullptr, nq, k, o->weight_mode, o->weight_law, out_pred, st);
     }
     if (q) return run_host_pipeline(ix, q, nq, o, out_dist, out_idx, out_pred);
     return run_self_rows(ix, nq, o, out_dist, (long*)out_idx, out_pred);
@@ -3498,7 +3599,9 @@ extern "C" int sknnr_predict_masked(sknnr_index* ix, const void* q, int64_t nq, 
     if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
     if (!o) return fail(SKNNR_ERR_INVALID, "opts is NULL");
     if (!out_pred && nq > 0) return fail(SKNNR_ERR_INVALID, "out_pred is NULL");
-    if (!weight_mode_ok(o->weight_mode, false))
+    const int law = weight_law_check(ix, o);
+    if (law < 0) return law;
+    if (!law && !weight_mode_ok(o->weight_mode, false))
         return fail(SKNNR_ERR_INVALID, "a masked call predicts with uniform or distance weights only (weight mode %d)", o->weight_mode);
     static int64_t dummy_idx;
     static const double dummy_q = 0.0;
@@ -3639,7 +3742,9 @@ extern "C" int sknnr_stream_begin(sknnr_index* ix, const sknnr_query_opts* o, in
     if (o->exclude_self) return fail(SKNNR_ERR_INVALID, "a stream answers pushed rows: exclude_self is not available");
     if (want_pred) {
         if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
-        if (!weight_mode_ok(o->weight_mode, false))
+        const int law = weight_law_check(ix, o);
+        if (law < 0) return law;
+        if (!law && !weight_mode_ok(o->weight_mode, false))
             return fail(SKNNR_ERR_INVALID, "a stream predicts with uniform or distance weights only");
     }
     std::lock_guard<std::mutex> lock(ix->mtx);
