@@ -370,6 +370,58 @@ int sknnr_summarize(sknnr_index* index, const void* q, int64_t nq, const sknnr_q
  */
 int sknnr_debug_last_summary(const sknnr_index* index, int64_t out[8]);
 
+/* ---- output plans: many statistics per target from one search --------------------------------- */
+
+/*
+ * An output plan is n_out entries (cols[e], stat[e], param[e]), 1 <= n_out <= 1024 (a sanity cap on the row width):
+ *   cols[e]  : a target column in [0, t); it may repeat and come in any order
+ *   stat[e]  : a sknnr_statistic code, or SKNNR_STAT_QUANTILE
+ *   param[e] : float64 parameter, read for SKNNR_STAT_QUANTILE only (0 otherwise)
+ * Output plane e of a query holds that statistic of that target over the query's k neighbours, in the order
+ * sknnr_kneighbors returns them and with the weights sknnr_predict uses -- all reduced in one pass behind one search
+ * (sknnr_amd/csrc/plan.hip.h; tests/_output_plans.py restates the definitions in numpy).  An entry with one of the six
+ * sknnr_statistic codes equals that column of sknnr_summarize with that statistic bit for bit (MEAN: the predict
+ * kernels' value, float32-target flag included).
+ *   QUANTILE : param = q, 0 <= q <= 1 and finite.  numpy's weighted inverted_cdf,
+ *              np.quantile(v, q, method="inverted_cdf", weights=w) of numpy >= 2.0:
+ *                1. order the k pairs (v_i, w_i) by (v_i, i) ascending (a stable sort by value; -0.0 == 0.0)
+ *                2. c_0 = w_(0), c_a = c_(a-1) + w_(a): a sequential float64 running sum in sorted order; total = c_(k-1)
+ *                3. cdf_a = c_a / total, one division each
+ *                4. the result is v_(a*), a* the first a with cdf_a != 0.0 and cdf_a >= q; k - 1 when there is none
+ *                5. total not > 0 (a compact law whose weights all vanish, explicit all-zero weights): NaN, as MEAN
+ *              The median is (QUANTILE, 0.5).  The code is kept out of enum sknnr_statistic because the per-target
+ *              tables of sknnr_summarize* / sknnr_stream_set_statistics do not take it: they have no parameter.
+ */
+enum sknnr_plan_statistic { SKNNR_STAT_QUANTILE = 6 };
+
+/*
+ * The reduction alone: sknnr_summarize_from_neighbors with an output plan.  Same argument rules.
+ *   cols / stat / param : HOST arrays of n_out, whatever `mem` is
+ *   out                 : (nq, n_out) float64 in `mem`
+ * SKNNR_ERR_INVALID before any device work, the message naming the entry: a NULL array, n_out outside [1, 1024], a column
+ * outside [0, t), an unknown code, a q outside [0, 1] or not finite.
+ * The predict kernels run (into a buffer of the handle) only if some entry is a MEAN; then one launch writes every entry.
+ */
+int sknnr_summarize_plan_from_neighbors(sknnr_index* index, const double* dist, const int64_t* idx, const double* w,
+                                        int64_t nq, int32_t k, int32_t weight_mode, const int32_t* cols,
+                                        const int32_t* stat, const double* param, int32_t n_out, double* out, int32_t mem,
+                                        void* stream);
+
+/* Search plus reduction: sknnr_summarize with an output plan; opts->exclude_self and opts->weight_law as there. */
+int sknnr_summarize_plan(sknnr_index* index, const void* q, int64_t nq, const sknnr_query_opts* opts, const int32_t* cols,
+                         const int32_t* stat, const double* param, int32_t n_out, double* out, double* out_dist,
+                         int64_t* out_idx, int32_t mem, void* stream);
+
+/*
+ * Debug only.  The plan side of the last reduction the handle launched (the call sknnr_debug_last_summary describes).
+ * Host memory, no device work:
+ *   out[0] 1 = the plan kernel ran for it (0: a reduction without a plan; the rest is 0 then)
+ *   out[1] its path: 1 the register path (k <= 8), 2 the wide path
+ *   out[2] rows      out[3] n_out      out[4] k
+ *   out[5] entries that are means      out[6] 1 = the predict kernels ran for them      out[7] 0
+ */
+int sknnr_debug_last_plan(const sknnr_index* index, int64_t out[8]);
+
 /*
  * Debug only.  The weight-law side of the last reduction the handle launched (the call sknnr_debug_last_summary
  * describes), so that a test can prove that the device made the weights.  Host memory, no device work:
@@ -508,6 +560,16 @@ int sknnr_stream_set_nodata(sknnr_stream* stream, const double* nodata, int64_t 
  * (or with an all-MEAN table) enqueues exactly what it did before.
  */
 int sknnr_stream_set_statistics(sknnr_stream* stream, const int32_t* stat, int32_t t);
+/*
+ * sknnr_stream_set_plan: the stream's predictions become the n_out planes of an output plan (cols / stat / param: HOST
+ * arrays, as sknnr_summarize_plan).  Allowed after sknnr_stream_begin and before the first push, on a stream opened with
+ * predictions, and before a sknnr_stream_set_output that gives a scale / offset; mutually exclusive with
+ * sknnr_stream_set_statistics (whichever comes second is SKNNR_ERR_INVALID).  From then on the prediction lane has n_out
+ * columns: sknnr_stream_push* expect out_pred of (nq, n_out), the band-first pushes n_out planes, and
+ * sknnr_stream_set_output's pred_scale / pred_offset hold one value per output plane.  Masked rows are NaN (or the fill)
+ * across all n_out planes.
+ */
+int sknnr_stream_set_plan(sknnr_stream* stream, const int32_t* cols, const int32_t* stat, const double* param, int32_t n_out);
 int sknnr_stream_valid_rows(const sknnr_stream* stream, int64_t* out_valid_rows);
 
 /* ---- band-first tiles (raster layouts) ------------------------------------------------------ */
@@ -568,7 +630,7 @@ int sknnr_stream_push_planes(sknnr_stream* stream, const void* const* planes, in
  * sknnr_stream_set_output: the element types in which a stream's results leave the device.  0 (SKNNR_DTYPE_F64) means
  *   "as ever" for that output (int64 indices, float64 distances and predictions); idx_dtype accepts 0 or I32,
  *   dist_dtype 0 or F32, pred_dtype 0 or F32 / I16 / U16 / U8 / I32.  pred_scale / pred_offset: HOST arrays of t float64
- *   each (both or neither), uploaded once; has_pred_fill / pred_fill: what a NaN prediction (a nodata row) becomes.
+ *   each (n_out each on a stream with an output plan, sknnr_stream_set_plan; both or neither), uploaded once; has_pred_fill / pred_fill: what a NaN prediction (a nodata row) becomes.
  *   Allowed only before the first push.  A stream on which it was never called enqueues exactly what it did before the
  *   entry point existed.
  * sknnr_stream_push_typed / sknnr_stream_push_planes_typed: sknnr_stream_push / sknnr_stream_push_planes with the

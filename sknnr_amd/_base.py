@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import numbers
 from abc import ABC, abstractmethod
+from typing import NamedTuple
 
 import numpy as np
 from sklearn.base import BaseEstimator, MultiOutputMixin, RegressorMixin
@@ -166,6 +167,107 @@ def normalize_statistic(statistic, n_targets):
     if len(names) != n_targets:
         raise ValueError(f"statistic must be one name or hold one name per target ({n_targets}), got {len(names)}")
     return np.array([_native.STATISTICS[name] for name in names], dtype=np.int32)
+
+
+class OutputPlan(NamedTuple):
+    """An output plan as the engine takes it (``cols`` int32, ``codes`` int32 of ``_native.PLAN_STATISTICS``, ``params``
+    float64, one entry per output plane).  ``per_target``: it stands for a ``statistic=`` argument -- entry j is target j
+    -- and the result keeps that argument's shape rules; else the result is always 2-D."""
+    cols: np.ndarray
+    codes: np.ndarray
+    params: np.ndarray
+    per_target: bool = False
+
+    @property
+    def n_out(self) -> int:
+        return int(self.cols.size)
+
+    @property
+    def arrays(self):
+        return self.cols, self.codes, self.params
+
+
+def _is_quantile_spec(s) -> bool:
+    return (isinstance(s, (tuple, list)) and len(s) == 2 and isinstance(s[0], str) and s[0] == "quantile"
+            and isinstance(s[1], numbers.Real) and not isinstance(s[1], bool))
+
+
+def _plan_statistic(s, where, median=True):
+    """One statistic of a plan entry -- one of the six names, ``"median"`` (unless ``median`` is off) or
+    ``("quantile", q)`` -- as (code, param)."""
+    if _is_quantile_spec(s):
+        q = float(s[1])
+        if not (0.0 <= q <= 1.0):  # (NaN fails both comparisons)
+            raise ValueError(f"{where}: a quantile's q must lie in [0, 1], got {s[1]!r}")
+        return _native.PLAN_STATISTICS["quantile"], q
+    if median and isinstance(s, str) and s == "median":
+        return _native.PLAN_STATISTICS["quantile"], 0.5
+    if isinstance(s, str) and s in _native.STATISTICS:
+        return _native.STATISTICS[s], 0.0
+    raise ValueError(f"{where}: unknown statistic {s!r}: use one of {', '.join(_native.STATISTICS)}"
+                     f"{', ' + repr('median') if median else ''} or ('quantile', q)")
+
+
+def normalize_outputs(outputs, n_targets):
+    """``outputs`` of ``summarize`` / ``predict_chunks`` -- a sequence of ``(target, statistic)`` pairs: ``target`` an
+    integer column position (it may repeat, in any order), ``statistic`` one of the ``_native.STATISTICS`` names,
+    ``"median"`` or ``("quantile", q)`` with ``0 <= q <= 1`` -- as the ``(cols int32, codes int32, params float64)``
+    arrays the engine takes; every refusal comes before any device work."""
+    if isinstance(outputs, str):
+        raise ValueError(f"outputs must be a sequence of (target, statistic) pairs, got {outputs!r}")
+    try:
+        entries = list(outputs)
+    except TypeError:
+        raise ValueError(f"outputs must be a sequence of (target, statistic) pairs, got {outputs!r}") from None
+    if not entries:
+        raise ValueError("outputs must hold at least one (target, statistic) pair")
+    if len(entries) > _native.PLAN_MAX_OUT:
+        raise ValueError(f"outputs must hold at most {_native.PLAN_MAX_OUT} entries, got {len(entries)}")
+    cols, codes, params = [], [], []
+    for e, entry in enumerate(entries):
+        if isinstance(entry, str) or not isinstance(entry, (tuple, list)) or len(entry) != 2:
+            raise ValueError(f"outputs[{e}] must be a (target, statistic) pair, got {entry!r}")
+        target, stat = entry
+        if isinstance(target, bool) or not isinstance(target, numbers.Integral):
+            raise ValueError(f"outputs[{e}]: the target must be an integer column position, got {target!r}")
+        if not 0 <= int(target) < n_targets:
+            raise ValueError(f"outputs[{e}]: target {int(target)} is outside [0, {n_targets})")
+        code, param = _plan_statistic(stat, f"outputs[{e}]")
+        cols.append(int(target))
+        codes.append(code)
+        params.append(param)
+    return np.array(cols, dtype=np.int32), np.array(codes, dtype=np.int32), np.array(params, dtype=np.float64)
+
+
+def resolve_statistic(statistic, outputs, n_targets):
+    """What ``summarize`` / ``predict_chunks`` reduce: ``statistic`` as the int32 codes of :func:`normalize_statistic`
+    when no entry is a ``("quantile", q)`` (the per-target path, unchanged, with its refusals -- ``"median"`` among them:
+    in ``statistic`` the median is spelled ``("quantile", 0.5)``), an :class:`OutputPlan` for ``outputs`` or for a
+    ``statistic`` that holds ``("quantile", q)`` entries (the plan ``[(0, s0), ..., (t-1, s_(t-1))]``), or None when
+    neither is given."""
+    if outputs is not None:
+        if statistic is not None:
+            raise ValueError("outputs and statistic cannot be given together: outputs names the statistic of every plane")
+        return OutputPlan(*normalize_outputs(outputs, n_targets))
+    if statistic is None:
+        return None
+    new = _is_quantile_spec
+    if new(statistic):
+        names = [statistic] * n_targets
+    elif isinstance(statistic, str):
+        return normalize_statistic(statistic, n_targets)
+    else:
+        try:
+            names = list(statistic)
+        except TypeError:
+            return normalize_statistic(statistic, n_targets)
+        if not any(new(s) or (isinstance(s, (tuple, list)) and len(s) > 0 and s[0] == "quantile") for s in names):
+            return normalize_statistic(names, n_targets)
+    if len(names) != n_targets:
+        raise ValueError(f"statistic must be one name or hold one name per target ({n_targets}), got {len(names)}")
+    pairs = [_plan_statistic(s, f"statistic[{j}]", median=False) for j, s in enumerate(names)]
+    return OutputPlan(np.arange(n_targets, dtype=np.int32), np.array([c for c, _ in pairs], dtype=np.int32),
+                      np.array([q for _, q in pairs], dtype=np.float64), per_target=True)
 
 
 def _check_layout(layout):
@@ -689,8 +791,10 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         return 1 if self._y.ndim == 1 else self._y.shape[1]
 
     def _summarize_engine(self, X, stat, *, apply_affine, row_offset=0, n_self_rows=None, owner=None):
-        """:meth:`_predict_engine` with the statistic codes ``stat`` in place of the mean; always float64."""
+        """:meth:`_predict_engine` with the statistic codes ``stat`` in place of the mean; always float64.  ``stat`` may be
+        an :class:`OutputPlan`: the result then is ``(n, n_out)``, 1-D only for a per-target plan of a 1-D ``y``."""
         weights = "uniform" if self.weights is None else self.weights
+        plan = stat if isinstance(stat, OutputPlan) else None
         try:
             if self._reference_ties():
                 # as _predict_engine: the policy's own neighbours, then the reduction on the device
@@ -700,21 +804,27 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 if cuda:
                     dev = dist.device
                     dist, idx = dist.cpu().numpy(), idx.cpu().numpy()
-                out = self.engine_.summarize_from_neighbors(dist, idx, weights, stat)
+                if plan is not None:
+                    out = self.engine_.summarize_plan_from_neighbors(dist, idx, weights, plan.arrays)
+                else:
+                    out = self.engine_.summarize_from_neighbors(dist, idx, weights, stat)
                 if cuda:
                     import torch
 
                     out = torch.as_tensor(out, device=dev)
             else:
-                out = self.engine_.summarize(
-                    X, self.n_neighbors, weights, stat, exclude_self=X is None, deterministic=True,
+                out = (self.engine_.summarize if plan is None else self.engine_.summarize_plan)(
+                    X, self.n_neighbors, weights, stat if plan is None else plan.arrays, exclude_self=X is None,
+                    deterministic=True,
                     decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula(), apply_affine=apply_affine,
                     row_offset=row_offset, n_self_rows=n_self_rows, check_finite=X is not None)
         except _native.HipBackendError as err:
             _reraise(err, owner if owner is not None else self)
+        if plan is not None and not plan.per_target:
+            return out
         return out.reshape(-1) if self._y.ndim == 1 else out
 
-    def summarize(self, X=None, statistic="mean"):
+    def summarize(self, X=None, statistic=None, outputs=None):
         """A summary of each query's neighbours per target, reduced on the device from the neighbours ``kneighbors``
         finds (deterministic ordering on, as ``predict``); ``X=None`` summarises every fitted row's neighbours, itself
         excluded.  ``statistic``: one name, or one name per target -- ``"mean"`` (what ``predict`` gives, bit for bit), ``"mode"``
@@ -725,9 +835,22 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         deviation ``sqrt(sum((w * (v - m)) * (v - m)) / sum(w))`` around the float64 weighted mean ``m``, both sums
         numpy's pairwise sums over the k neighbours).  Weights are those of ``predict``: 1, ``1 / d`` (a row holding
         ``d == 0`` becomes its 0 / 1 mask) or the callable's; all arithmetic is float64.  Returns float64 ``(n, t)``, ``(n,)`` for a 1-D
-        ``y``; numpy in gives numpy out, CUDA tensors in give CUDA tensors out."""
+        ``y``; numpy in gives numpy out, CUDA tensors in give CUDA tensors out.  Without ``statistic`` and ``outputs`` the
+        statistic is ``"mean"``.
+
+        A ``statistic`` entry may also be ``("quantile", q)``, ``0 <= q <= 1`` (the median is ``("quantile", 0.5)``): numpy's weighted
+        ``inverted_cdf`` quantile of the neighbours' values, ``np.quantile(v, q, method="inverted_cdf", weights=w)`` --
+        the values in stable ascending order, the weights' sequential running sum divided by its total, and the first
+        value whose share is non-zero and at least ``q`` (NaN where the weights sum to 0).
+
+        ``outputs`` (instead of ``statistic``): a sequence of ``(target, statistic)`` pairs -- ``target`` an integer
+        column position that may repeat, ``statistic`` any of the above or ``"median"`` -- all reduced from ONE search, e.g.
+        ``[(0, "mean"), (0, "std"), (0, ("quantile", .1)), (0, ("quantile", .9))]``.  Returns float64 ``(n, n_out)``,
+        always 2-D; a plane with one of the six names equals that column of ``summarize(X, statistic=name)`` bit for bit."""
         check_is_fitted(self, "_fit_X")
-        stat = normalize_statistic(statistic, self._n_targets())
+        if statistic is None and outputs is None:
+            statistic = "mean"
+        stat = resolve_statistic(statistic, outputs, self._n_targets())
         if X is not None:
             X = self._validate_query(X)
         return self._summarize_engine(X, stat, apply_affine=False)
@@ -775,7 +898,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             self._check_stream_supported("typed outputs are")
         eng = self.engine_
         want_pred = weights is not None
-        t_cols = eng.t
+        plan = statistic if isinstance(statistic, OutputPlan) else None  # (the prediction lane then has n_out columns)
+        t_cols = eng.t if plan is None else plan.n_out
         output = {key: v for key, v in (output or {}).items() if v is not None}
         idx_dt = np.dtype(output.get("index_dtype", np.int64))
         dist_dt = np.dtype(output.get("distance_dtype", np.float64))
@@ -848,7 +972,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              deterministic=use_deterministic_ordering,
                                              decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula(),
                                              apply_affine=apply_affine, check_finite=True, query_dtype=code,
-                                             nodata=nodata, fill_index=fill_index, output=output, statistic=statistic,
+                                             nodata=nodata, fill_index=fill_index, output=output,
+                                             **(dict(statistic=statistic) if plan is None else dict(plan=plan.arrays)),
                                              **({} if id_table is None else dict(id_table=id_table, fill_id=fill_id)))
                 if first.dtype != stream_dtype:
                     if stream_dtype != np.float64:
@@ -1036,7 +1161,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
     def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
                        out_nodata=None, statistic=None, return_neighbors=False, return_distance=True,
                        return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
-                       distance_dtype=None):
+                       distance_dtype=None, outputs=None):
         """``predict`` over an iterable of host tiles as one streamed call; ``out``: preallocated
         ``(n_rows, n_targets)`` float64 array (e.g. a memmap; float32 results are held exactly).  ``nodata`` as in
         :meth:`kneighbors_chunks`: masked rows are predicted NaN.  ``layout="bands"``: band-first tiles as in
@@ -1061,7 +1186,14 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         ``d == 0`` becomes its 0 / 1 mask) or the callable's; all arithmetic is float64.  The result equals ``summarize(np.concatenate(tiles),
         statistic)`` bit for bit (float64 unless ``out_dtype`` says otherwise) and is written where the prediction is, so
         ``nodata``, ``layout``, ``out`` and the typed outputs apply unchanged; e.g. ``statistic=["mean", "mean", "mode"]``
-        maps two continuous attributes and a class code in one call.
+        maps two continuous attributes and a class code in one call.  An entry may also be ``("quantile", q)``
+        (:meth:`summarize`).
+
+        ``outputs`` (instead of ``statistic``): a sequence of ``(target, statistic)`` pairs as in :meth:`summarize` -- the
+        ``n_out`` planes are all reduced inside the one streamed search, e.g. an attribute's mean, q10 and q90 and a class
+        mode.  The result is ``(N, n_out)``, ``(n_out, N)`` with ``layout="bands"``, always 2-D, and equals
+        ``summarize(np.concatenate(tiles), outputs=outputs)`` bit for bit; ``out``, ``out_dtype``, ``scale`` / ``offset``
+        (scalars or one value per output plane), ``out_nodata``, ``nodata`` and ``return_neighbors`` apply unchanged.
 
         ``return_neighbors=True``: the neighbours the predictions are reduced from (``n_neighbors`` of them,
         deterministic ordering) are delivered beside them from the SAME search -- the call returns ``(pred, dist, idx)``,
@@ -1083,8 +1215,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         neighbors = self._neighbor_request(return_neighbors, return_distance, return_dataframe_index, neighbors_out,
                                            fill_index, index_dtype, distance_dtype)
         extra = {} if neighbors is None else dict(neighbors=neighbors)
-        if statistic is not None:
-            statistic = normalize_statistic(statistic, self._n_targets())
+        statistic = resolve_statistic(statistic, outputs, self._n_targets())
         if nodata is not None:
             nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
         validate = self._validate_query
@@ -1102,8 +1233,10 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         law = isinstance(weights, DistanceWeights)
         host_callable = callable(weights) and not law
         output = None
+        plan = statistic if isinstance(statistic, OutputPlan) else None
+        flat = self._y.ndim == 1 and (plan is None or plan.per_target)  # the result is 1-D
         if typed is not None:
-            n_targets = 1 if self._y.ndim == 1 else self._y.shape[1]
+            n_targets = plan.n_out if plan is not None else (1 if self._y.ndim == 1 else self._y.shape[1])
             # (a compact law can give an all-zero row: NaN predictions occur without any mask)
             output = normalize_typed_output(*typed, n_targets, nodata is not None or (law and weights.can_vanish))
         if neighbors is not None:
@@ -1128,7 +1261,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 else:
                     preds.append(self._predict_engine(t, apply_affine=apply_affine, row_offset=row, owner=owner))
                 row += t.shape[0]
-            pred = np.concatenate([p.reshape(len(p), -1) for p in preds]) if preds else np.empty((0, self.engine_.t))
+            pred = (np.concatenate([p.reshape(len(p), -1) for p in preds]) if preds
+                    else np.empty((0, self.engine_.t if plan is None else plan.n_out)))
             if out is not None:
                 out[:len(pred)] = pred.reshape((len(pred),) + out.shape[1:])  # (out is 1-D for a 1-D y)
                 pred = out[:len(pred)]
@@ -1142,7 +1276,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                             bands=bands, output=output, statistic=statistic)
             if out is None and not output and statistic is None:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
                 pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
-        return pred.reshape(-1) if self._y.ndim == 1 else pred
+        return pred.reshape(-1) if flat else pred
 
     def _predict_chunks_neighbors(self, tiles, validate, weights, neighbors, *, apply_affine, out, owner, nodata, bands,
                                   output, statistic):
@@ -1167,7 +1301,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              neighbors=True)
         if out is None and not output and statistic is None:  # (as without neighbours: float32 where scikit-learn returns it)
             pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
-        pred = pred.reshape(-1) if self._y.ndim == 1 else pred
+        if self._y.ndim == 1 and not (isinstance(statistic, OutputPlan) and not statistic.per_target):
+            pred = pred.reshape(-1)
         found = self._finish_chunks(dist, idx, return_distance, ids, fill_index=None if nodata is None else fill_index,
                                     on_device=table is not None)
         return (pred, *found) if return_distance else (pred, found)
@@ -1330,12 +1465,15 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         return self._host_result(X, self.regressor_._predict_engine(X, apply_affine=X is not None and self._map_on_device(),
                                                                     owner=self.transformer_))
 
-    def summarize(self, X=None, statistic="mean"):
+    def summarize(self, X=None, statistic=None, outputs=None):
         """Per-target summaries of each query's neighbours (:meth:`RawKNNRegressor.summarize`, also for the definitions
-        of ``statistic``); ``X=None``: of every fitted row's neighbours, itself excluded."""
+        of ``statistic`` and of ``outputs``, the ``(target, statistic)`` pairs reduced from one search); ``X=None``: of
+        every fitted row's neighbours, itself excluded."""
         check_is_fitted(self, "regressor_")
         reg = self.regressor_
-        stat = normalize_statistic(statistic, reg._n_targets())
+        if statistic is None and outputs is None:
+            statistic = "mean"
+        stat = resolve_statistic(statistic, outputs, reg._n_targets())
         if X is not None:
             X = self._validate_raw_query(X)
         return self._host_result(X, reg._summarize_engine(X, stat, apply_affine=X is not None and self._map_on_device(),
@@ -1393,11 +1531,12 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
     def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
                        out_nodata=None, statistic=None, return_neighbors=False, return_distance=True,
                        return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
-                       distance_dtype=None):
+                       distance_dtype=None, outputs=None):
         """``predict`` over an iterable of untransformed host tiles as one streamed call (``nodata``: masked rows are
         predicted NaN; ``layout="bands"``: band-first tiles and predictions; ``out_dtype`` / ``scale`` / ``offset`` /
         ``out_nodata``: predictions converted on the device to the type the raster is stored in; ``statistic``: one name
-        or one per target -- mean, mode, min, max, nearest, std of the neighbours in place of the mean;
+        or one per target -- mean, mode, min, max, nearest, std or ("quantile", q) of the neighbours in place of the
+        mean; ``outputs``: ``(target, statistic)`` pairs instead, ``n_out`` planes from the one search;
         ``return_neighbors=True`` and the neighbour keywords: ``(pred, dist, idx)`` from one search; see
         :meth:`RawKNNRegressor.kneighbors_chunks` / :meth:`RawKNNRegressor.predict_chunks`)."""
         bands = _check_layout(layout)
@@ -1405,8 +1544,7 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         neighbors = self.regressor_._neighbor_request(return_neighbors, return_distance, return_dataframe_index,
                                                       neighbors_out, fill_index, index_dtype, distance_dtype)
         extra = {} if neighbors is None else dict(neighbors=neighbors)
-        if statistic is not None:
-            statistic = normalize_statistic(statistic, self.regressor_._n_targets())
+        statistic = resolve_statistic(statistic, outputs, self.regressor_._n_targets())
         return self.regressor_._predict_chunks(tiles, self._band_validator(bands), apply_affine=self._map_on_device(),
                                                out=out, owner=self.transformer_, nodata=self._raw_nodata(nodata),
                                                bands=bands, typed=(out_dtype, scale, offset, out_nodata),

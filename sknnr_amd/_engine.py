@@ -292,6 +292,15 @@ class KNNEngine:
         """Per-target statistics (``stat``: one ``_native.STATISTICS`` code per target) of neighbours already found:
         :meth:`predict_from_neighbors` with the mean replaced column by column.  Always float64 ``(nq, t)``.  Explicit
         weights that are negative or not finite are refused."""
+        return self._summarize_from_neighbors(dist, idx, weights, stat, None)
+
+    def summarize_plan_from_neighbors(self, dist, idx, weights, plan):
+        """An output plan (``plan``: ``(cols, codes, params)`` as :func:`sknnr_amd._base.normalize_outputs` gives them) of
+        neighbours already found: :meth:`summarize_from_neighbors` with ``n_out`` planes, each one statistic of one target.
+        Always float64 ``(nq, n_out)``; the same refusal of negative or non-finite explicit weights."""
+        return self._summarize_from_neighbors(dist, idx, weights, None, plan)
+
+    def _summarize_from_neighbors(self, dist, idx, weights, stat, plan):
         if self.t < 1:
             raise ValueError("the engine was built without targets")
         k = idx.shape[1]
@@ -324,20 +333,40 @@ class KNNEngine:
             dist = None if dist is None else dist.to(torch.float64).contiguous()
             if w is not None:
                 w = torch.as_tensor(w, device=idx.device).to(torch.float64).contiguous()
-            out = torch.empty((idx.shape[0], self.t), dtype=torch.float64, device=idx.device)
+            width = self.t if plan is None else len(plan[0])
+            out = torch.empty((idx.shape[0], width), dtype=torch.float64, device=idx.device)
             if idx.shape[0]:
                 stream = torch.cuda.current_stream(idx.device).cuda_stream
-                self._index.summarize_from_neighbors_device(0 if dist is None else dist.data_ptr(), idx.data_ptr(),
-                                                            0 if w is None else w.data_ptr(), idx.shape[0], k, mode,
-                                                            stat, out.data_ptr(), stream)
+                args = (0 if dist is None else dist.data_ptr(), idx.data_ptr(), 0 if w is None else w.data_ptr(),
+                        idx.shape[0], k, mode)
+                if plan is None:
+                    self._index.summarize_from_neighbors_device(*args, stat, out.data_ptr(), stream)
+                else:
+                    self._index.summarize_plan_from_neighbors_device(*args, plan, out.data_ptr(), stream)
             return out
         w = None if w is None else np.asarray(w, dtype=np.float64)
+        if plan is not None:
+            return self._index.summarize_plan_from_neighbors_host(dist, idx, w, mode, plan)
         return self._index.summarize_from_neighbors_host(dist, idx, w, mode, stat)
 
     def summarize(self, X, k, weights, stat, *, exclude_self=False, deterministic=True, decimals=10,
                   formula="expanded", apply_affine=False, row_offset=0, n_self_rows=None, check_finite=False):
         """Search plus per-target statistics: :meth:`predict` with ``stat`` (one ``_native.STATISTICS`` code per target)
         choosing what is reduced from the neighbours.  Always float64 ``(nq, t)``."""
+        return self._summarize(X, k, weights, stat, None, exclude_self=exclude_self, deterministic=deterministic,
+                               decimals=decimals, formula=formula, apply_affine=apply_affine, row_offset=row_offset,
+                               n_self_rows=n_self_rows, check_finite=check_finite)
+
+    def summarize_plan(self, X, k, weights, plan, *, exclude_self=False, deterministic=True, decimals=10,
+                       formula="expanded", apply_affine=False, row_offset=0, n_self_rows=None, check_finite=False):
+        """Search plus output plan: :meth:`summarize` with ``n_out`` planes ``(cols, codes, params)``, all reduced behind
+        the one search.  Always float64 ``(nq, n_out)``."""
+        return self._summarize(X, k, weights, None, plan, exclude_self=exclude_self, deterministic=deterministic,
+                               decimals=decimals, formula=formula, apply_affine=apply_affine, row_offset=row_offset,
+                               n_self_rows=n_self_rows, check_finite=check_finite)
+
+    def _summarize(self, X, k, weights, stat, plan, *, exclude_self, deterministic, decimals, formula, apply_affine,
+                   row_offset, n_self_rows, check_finite):
         if self.t < 1:
             raise ValueError("the engine was built without targets")
         law = self.weight_law(weights)  # (a distance-weight law: the device evaluates it, in the single call below)
@@ -345,7 +374,7 @@ class KNNEngine:
             dist, idx = self.kneighbors(X, k, exclude_self=exclude_self, deterministic=deterministic,
                                         decimals=decimals, formula=formula, apply_affine=apply_affine,
                                         row_offset=row_offset, n_self_rows=n_self_rows, check_finite=check_finite)
-            return self.summarize_from_neighbors(dist, idx, weights, stat)
+            return self._summarize_from_neighbors(dist, idx, weights, stat, plan)
         if not law and weights not in _WEIGHT_MODES:
             raise ValueError(f"weights not recognized: should be 'uniform', 'distance', or a callable; got {weights!r}")
         qdt = self.query_dtype_code(X, formula, apply_affine)
@@ -355,21 +384,28 @@ class KNNEngine:
                           check_finite=check_finite and X is not None, query_dtype=qdt, weight_law=law)
         if X is None:
             nq = self.n_ref - row_offset if n_self_rows is None else int(n_self_rows)
+            if plan is not None:
+                return self._index.summarize_plan_host(None, opts, plan, nq=nq)
             return self._index.summarize_host(None, opts, stat, nq=nq)
         if is_torch_cuda_tensor(X):
             import torch
 
             X = self._as_device_rows(X, apply_affine, qdt)
             nq = X.shape[0]
-            out = torch.empty((nq, self.t), dtype=torch.float64, device=X.device)
+            out = torch.empty((nq, self.t if plan is None else len(plan[0])), dtype=torch.float64, device=X.device)
             if nq:
                 stream = torch.cuda.current_stream(X.device).cuda_stream
-                self._index.summarize_device(X.data_ptr(), nq, opts, stat, out.data_ptr(), stream)
+                if plan is None:
+                    self._index.summarize_device(X.data_ptr(), nq, opts, stat, out.data_ptr(), stream)
+                else:
+                    self._index.summarize_plan_device(X.data_ptr(), nq, opts, plan, out.data_ptr(), stream)
                 if check_finite:
                     self._index.check_finite(stream)
             return out
         X = np.ascontiguousarray(X) if qdt else np.ascontiguousarray(X, dtype=np.float64)
         self._check_columns(X, apply_affine)
+        if plan is not None:
+            return self._index.summarize_plan_host(X, opts, plan)
         return self._index.summarize_host(X, opts, stat)
 
     def predict(self, X, k, weights="uniform", *, exclude_self=False, deterministic=True, decimals=10,
@@ -482,7 +518,7 @@ class KNNEngine:
 
     def open_stream(self, k, *, weights=None, want_dist=True, deterministic=True, decimals=10,
                     formula="expanded", apply_affine=False, row_offset=0, check_finite=False, query_dtype=0,
-                    nodata=None, fill_index=-1, output=None, statistic=None, id_table=None, fill_id=-1):
+                    nodata=None, fill_index=-1, output=None, statistic=None, id_table=None, fill_id=-1, plan=None):
         """A :class:`sknnr_amd._native.QueryStream` over host tiles: ``push(tile)`` keeps the PCIe
         pipeline full across tiles and carries the global row offset.  ``weights`` (``"uniform"`` /
         ``"distance"`` / a :class:`sknnr_amd.weights.DistanceWeights` law, evaluated on the device tile by tile) also
@@ -493,7 +529,8 @@ class KNNEngine:
         ``statistic``: one ``_native.STATISTICS`` code per target; the predictions become those summaries of the
         neighbours (:meth:`summarize`), written where the predictions are.  ``id_table`` (int64, one dataframe id per
         reference row): the indices leave as ``id_table[idx]``, looked up on the device; keep ``fill_index`` negative,
-        and masked rows get ``fill_id``."""
+        and masked rows get ``fill_id``.  ``plan``: an output plan ``(cols, codes, params)`` instead of ``statistic``; the
+        prediction lane then holds its ``n_out`` planes (:meth:`summarize_plan`)."""
         want_pred = weights is not None
         law = self.weight_law(weights)  # (a distance-weight law: every tile's weights are made on the device)
         if want_pred and not law and weights not in _WEIGHT_MODES:
@@ -505,8 +542,12 @@ class KNNEngine:
                           row_offset=row_offset, check_finite=check_finite, query_dtype=query_dtype, weight_law=law)
         if statistic is not None and not want_pred:
             raise ValueError("statistics need a stream that predicts: pass weights")
+        if plan is not None and not want_pred:
+            raise ValueError("an output plan needs a stream that predicts: pass weights")
+        if plan is not None and statistic is not None:
+            raise ValueError("a stream takes statistic or an output plan, not both")
         return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred, nodata=nodata, fill_index=fill_index,
-                                       output=output, statistic=statistic, id_table=id_table, fill_id=fill_id)
+                                       output=output, statistic=statistic, id_table=id_table, fill_id=fill_id, plan=plan)
 
     def hamming_distances(self, X, rows=None):
         """Full weighted-Hamming distance rows of ``X[rows]`` (``X`` None: of the fitted rows) from the device."""

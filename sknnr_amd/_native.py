@@ -29,6 +29,10 @@ WEIGHTS_F32_WEIGHTS = 0x200
 
 # sknnr_statistic (include/sknnr_hip.h): the per-target summaries of the neighbours
 STATISTICS = {"mean": 0, "mode": 1, "min": 2, "max": 3, "nearest": 4, "std": 5}
+# the statistics of an output plan's entries: those, and SKNNR_STAT_QUANTILE with its parameter q.  (A table of its own:
+# the per-target tables of sknnr_summarize* / sknnr_stream_set_statistics take the six names above only.)
+PLAN_STATISTICS = {**STATISTICS, "quantile": 6}
+PLAN_MAX_OUT = 1024
 
 # sknnr_weight_law (include/sknnr_hip.h): the distance-weight laws the device evaluates, by the header's short names; the
 # classes of sknnr_amd.weights carry theirs as ``name`` / ``code``
@@ -85,6 +89,10 @@ EXPORTED_SYMBOLS = (
     "sknnr_summarize",
     "sknnr_stream_set_statistics",
     "sknnr_debug_last_summary",
+    "sknnr_summarize_plan_from_neighbors",
+    "sknnr_summarize_plan",
+    "sknnr_stream_set_plan",
+    "sknnr_debug_last_plan",
     "sknnr_debug_last_weight_law",
     "sknnr_debug_weight_law",
     "sknnr_hamming_distances",
@@ -259,6 +267,12 @@ def load(build_if_missing: bool = False):
         lib.sknnr_summarize.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), vp, vp, vp, vp, c_int32, vp]
         lib.sknnr_stream_set_statistics.argtypes = [vp, vp, c_int32]
         lib.sknnr_debug_last_summary.argtypes = [vp, POINTER(c_int64)]
+    if hasattr(lib, "sknnr_summarize_plan"):
+        lib.sknnr_summarize_plan_from_neighbors.argtypes = [vp, vp, vp, vp, c_int64, c_int32, c_int32, vp, vp, vp, c_int32,
+                                                            vp, c_int32, vp]
+        lib.sknnr_summarize_plan.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), vp, vp, vp, c_int32, vp, vp, vp, c_int32, vp]
+        lib.sknnr_stream_set_plan.argtypes = [vp, vp, vp, vp, c_int32]
+        lib.sknnr_debug_last_plan.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_index_set_weight_law_params.argtypes = [vp, c_int32, c_double, c_double]
     lib.sknnr_debug_last_weight_law.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_weight_law.argtypes = [c_int32, c_double, c_double, vp, c_int64, vp, c_int32, c_int32]
@@ -306,6 +320,18 @@ def _c_f64(a):
 def _c_stat(stat):
     """Statistic codes (``STATISTICS`` values) as the C entry points read them, or None."""
     return None if stat is None else np.ascontiguousarray(stat, dtype=np.int32).reshape(-1)
+
+
+def _c_plan(plan):
+    """An output plan ``(cols, codes, params)`` as the C entry points read it: int32, int32 and float64 host arrays of one
+    length (``PLAN_STATISTICS`` codes)."""
+    cols, codes, params = plan
+    cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+    codes = np.ascontiguousarray(codes, dtype=np.int32).reshape(-1)
+    params = np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
+    if not (cols.size == codes.size == params.size):
+        raise ValueError("an output plan's columns, codes and parameters must have one length")
+    return cols, codes, params
 
 
 def _c_rows(a, opts):
@@ -430,15 +456,19 @@ class Index:
         check(load().sknnr_check_finite(self.handle, c_void_p(stream or None)))
 
     def open_stream(self, opts: QueryOpts, want_dist=True, want_pred=False, nodata=None, fill_index=-1,
-                    output=None, statistic=None, id_table=None, fill_id=-1) -> "QueryStream":
+                    output=None, statistic=None, id_table=None, fill_id=-1, plan=None) -> "QueryStream":
         """``nodata``: float64 ``(d_in,)``, one value per column of the pushed rows -- every tile is then masked on the
         device (sknnr_stream_set_nodata) and masked rows get ``fill_index`` / NaN.  ``output``: keyword arguments of
         :meth:`QueryStream.set_output` -- the results then leave the device at those types.  ``statistic``: one
         ``STATISTICS`` code per target (:meth:`QueryStream.set_statistics`) -- the predictions become those summaries.
         ``id_table`` / ``fill_id``: :meth:`QueryStream.set_id_table` -- the indices leave as those ids; ``fill_index``
-        must then be negative, and masked rows get ``fill_id``."""
+        must then be negative, and masked rows get ``fill_id``.  ``plan``: an output plan ``(cols, codes, params)``
+        (:meth:`QueryStream.set_plan`; not together with ``statistic``) -- the prediction lane then holds its planes, and
+        ``output``'s ``scale`` / ``offset`` one value per plane."""
         stream = QueryStream(self, opts, want_dist, want_pred)
         try:
+            if plan is not None:  # (first: it sets the width set_output's scale / offset must have)
+                stream.set_plan(plan)
             if nodata is not None:
                 stream.set_nodata(nodata, fill_index)
             if output:
@@ -520,6 +550,53 @@ class Index:
         check(load().sknnr_summarize_from_neighbors(
             self.handle, c_void_p(dist_ptr or None), c_void_p(idx_ptr), c_void_p(w_ptr or None), nq, k,
             int(weight_mode), _host_ptr(stat), c_void_p(out_ptr), MEM_DEVICE, c_void_p(stream or None)))
+
+    # ---- output plans (include/sknnr_hip.h) ------------------------------------------------------
+    def summarize_plan_host(self, q, opts: QueryOpts, plan, nq=None):
+        """Search plus output plan (sknnr_summarize_plan) on host rows, or on the index's own rows (``q`` None):
+        ``(nq, n_out)`` float64.  ``plan``: ``(cols, codes, params)``."""
+        q = _c_rows(q, opts)
+        if q is not None:
+            nq = q.shape[0]
+        cols, codes, params = _c_plan(plan)
+        out = np.empty((nq, cols.size), dtype=np.float64)
+        check(load().sknnr_summarize_plan(self.handle, _host_ptr(q), nq, byref(opts), _host_ptr(cols), _host_ptr(codes),
+                                          _host_ptr(params), int(cols.size), _host_ptr(out), None, None, MEM_HOST, None))
+        return out
+
+    def summarize_plan_device(self, q_ptr, nq, opts: QueryOpts, plan, out_ptr, stream=0):
+        cols, codes, params = _c_plan(plan)
+        check(load().sknnr_summarize_plan(self.handle, c_void_p(q_ptr or None), nq, byref(opts), _host_ptr(cols),
+                                          _host_ptr(codes), _host_ptr(params), int(cols.size), c_void_p(out_ptr), None, None,
+                                          MEM_DEVICE, c_void_p(stream or None)))
+
+    def summarize_plan_from_neighbors_host(self, dist, idx, w, weight_mode, plan):
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        dist, w = _c_f64(dist), _c_f64(w)
+        cols, codes, params = _c_plan(plan)
+        nq, k = idx.shape
+        out = np.empty((nq, cols.size), dtype=np.float64)
+        check(load().sknnr_summarize_plan_from_neighbors(
+            self.handle, _host_ptr(dist), _host_ptr(idx), _host_ptr(w), nq, k, int(weight_mode), _host_ptr(cols),
+            _host_ptr(codes), _host_ptr(params), int(cols.size), _host_ptr(out), MEM_HOST, None))
+        return out
+
+    def summarize_plan_from_neighbors_device(self, dist_ptr, idx_ptr, w_ptr, nq, k, weight_mode, plan, out_ptr, stream=0):
+        """Device pointers in and out; the plan stays host arrays."""
+        cols, codes, params = _c_plan(plan)
+        check(load().sknnr_summarize_plan_from_neighbors(
+            self.handle, c_void_p(dist_ptr or None), c_void_p(idx_ptr), c_void_p(w_ptr or None), nq, k, int(weight_mode),
+            _host_ptr(cols), _host_ptr(codes), _host_ptr(params), int(cols.size), c_void_p(out_ptr), MEM_DEVICE,
+            c_void_p(stream or None)))
+
+    PLAN_FIELDS = ("ran", "path", "rows", "n_out", "k", "n_mean", "predict_ran", "reserved")
+
+    def debug_last_plan(self) -> dict:
+        """Debug only: the plan side of the last reduction of the handle (sknnr_debug_last_plan): whether the plan kernel
+        ran, its path (1 registers, 2 wide), rows, n_out, k, the mean entries, and whether the predict kernels ran."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_plan(self.handle, out))
+        return dict(zip(self.PLAN_FIELDS, (int(v) for v in out)))
 
     SUMMARY_FIELDS = ("path", "rows", "cols", "k", "predict_ran", "t", "weight_mode", "reserved")
 
@@ -825,6 +902,7 @@ class QueryStream:
         # element types of the results (set_output narrows them)
         self.idx_dtype, self.dist_dtype, self.pred_dtype = np.dtype(np.int64), np.dtype(np.float64), np.dtype(np.float64)
         self._typed = False
+        self.pred_cols = index.t  # columns of the prediction lane (set_plan widens it)
         check(load().sknnr_stream_begin(index.handle, byref(opts), int(self.want_dist), int(self.want_pred),
                                         byref(self._h)))
 
@@ -835,7 +913,7 @@ class QueryStream:
         outs, strides = [], set()  # (strides in ELEMENTS of each output's own type: the outputs share the pixel axis, not the byte count)
         for a, dt, cols, wanted in ((out_idx, self.idx_dtype, self.k, need_idx or not self.want_pred),
                                     (out_dist, self.dist_dtype, self.k, self.want_dist),
-                                    (out_pred, self.pred_dtype, self._index.t, self.want_pred)):
+                                    (out_pred, self.pred_dtype, self.pred_cols, self.want_pred)):
             if a is None and wanted:
                 a = np.empty((cols, nq) if planes else (nq, cols), dtype=dt)
             if a is not None and planes:
@@ -895,6 +973,14 @@ class QueryStream:
         stat = _c_stat(stat)
         check(load().sknnr_stream_set_statistics(self._h, _host_ptr(stat), int(stat.size)))
 
+    def set_plan(self, plan):
+        """An output plan ``(cols, codes, params)`` (sknnr_stream_set_plan; only before the first push, before
+        :meth:`set_output`, and not together with :meth:`set_statistics`): the stream's predictions become its ``n_out``
+        planes -- pushes take and return ``(nq, n_out)`` rows or ``(n_out, nq)`` planes."""
+        cols, codes, params = _c_plan(plan)
+        check(load().sknnr_stream_set_plan(self._h, _host_ptr(cols), _host_ptr(codes), _host_ptr(params), int(cols.size)))
+        self.pred_cols = int(cols.size)
+
     def set_output(self, index_dtype=None, distance_dtype=None, pred_dtype=None, scale=None, offset=None, fill=None):
         """The element types in which the results leave the device (sknnr_stream_set_output; only before the first
         push): ``index_dtype`` int32, ``distance_dtype`` float32, ``pred_dtype`` float32 / int16 / uint16 / uint8 / int32;
@@ -913,7 +999,7 @@ class QueryStream:
         pdt, pc = code(pred_dtype, np.float64)
         if (scale is None) != (offset is None):
             raise ValueError("scale and offset come together")
-        t = self._index.t
+        t = self.pred_cols
         if scale is not None:
             scale, offset = _c_f64(scale).reshape(-1), _c_f64(offset).reshape(-1)
             if scale.size != t or offset.size != t:

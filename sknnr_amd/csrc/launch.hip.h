@@ -1,9 +1,9 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_weights.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
-// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_WEIGHTS), templates where they are instantiated.
+// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS), templates where they are instantiated.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +16,7 @@
 #include "hamming.hip.h"
 #include "mask.hip.h"
 #include "narrow.hip.h"
+#include "plan.hip.h"
 #include "planes.hip.h"
 #include "rescue.hip.h"
 #include "summary.hip.h"
@@ -84,6 +85,11 @@ int narrow_dst_bytes(int kind, int dst_dtype, bool table = false);
 // ---- k_summary.hip: per-target neighbour summaries (summary.hip.h) ----------------------------------------------------------
 // the columns of a.tab (none of them `mean`) of every query; k <= kSummarySmallK: summary_kernel, else summary_wide_kernel
 hipError_t summary(const SummaryArgs& a, hipStream_t st);
+
+// ---- k_plan.hip: output plans (plan.hip.h) ------------------------------------------------------------------------------------
+// the a.n_out entries of every query into (nq, n_out); k <= kSummarySmallK: plan_kernel, else plan_wide_kernel.  a.mean
+// must hold the predict kernels' (nq, t) output when an entry is kStatMean (the caller's business: no kernel tests for it).
+hipError_t plan(const PlanArgs& a, hipStream_t st);
 
 // ---- k_weights.hip: distance-weight laws (weights.hip.h) ------------------------------------------------------------------
 // a.w[e] = law(a.dist[e]) for a.n elements; hipErrorInvalidValue for an unknown law

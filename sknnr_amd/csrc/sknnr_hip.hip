@@ -209,6 +209,24 @@ bool summary_table(const int32_t* stat, int t, std::vector<int>& tab, int* bad) 
     tab.insert(tab.end(), codes.begin(), codes.end());
     return true;
 }
+// An output plan of one call or stream (plan.hip.h): the device arrays plan_kernel reads, and how many entries are means
+// (the predict kernels run into the handle's mean_stage for them).  The prediction lane is n_out wide while one is set.
+struct OutputPlan {
+    int n_out = 0;
+    int n_mean = 0;
+    const int* cols = nullptr;
+    const int* codes = nullptr;
+    const double* param = nullptr;
+};
+// The host image of a plan's device arrays: n_out parameters, then (as ints) n_out columns and n_out codes.
+std::vector<double> plan_image(const int32_t* cols, const int32_t* stat, const double* param, int n_out) {
+    std::vector<double> img((size_t)2 * n_out, 0.0);
+    std::copy(param, param + n_out, img.begin());
+    int* ints = (int*)(img.data() + n_out);
+    std::copy(cols, cols + n_out, ints);
+    std::copy(stat, stat + n_out, ints + n_out);
+    return img;
+}
 // Error bound of the split contraction, in units of 2^-24 (|q'| + max|r'|)^2 -- derived in DESIGN.md
 // section 2 from the measured arithmetic of v_mfma_f32_32x32x16_f16 (scripts/microbench/
 // mfma_f16_numerics.hip, profiles/r02_mfma_f16_numerics.txt: per instruction two groups of eight exact
@@ -426,6 +444,15 @@ struct sknnr_index {
     const SummaryPlan* summary = nullptr;
     DevBuf<int> c_stat, s_stat;
     int64_t last_summary[8] = {};
+    // output plans (plan.hip.h).  `plan`: the plan of the call in progress, set and cleared under mtx (PlanScope), read by
+    // launch_predict and by whatever sizes the prediction lane (pred_cols); null: the lane holds the t targets.  The device
+    // arrays of a one-shot call (c_plan, a workspace buffer behind ev_ws) and of the open stream (s_plan); the (rows, t)
+    // means the predict kernels write for a plan's `mean` entries (mean_stage, behind ev_ws too); the record of the last
+    // reduction (sknnr_debug_last_plan): plan kernel ran, path (1 register, 2 wide), rows, n_out, k, mean entries, predict
+    // kernels ran.
+    const OutputPlan* plan = nullptr;
+    DevBuf<double> c_plan, s_plan, mean_stage;
+    int64_t last_plan[8] = {};
     // distance-weight laws (weights.hip.h): the handle's law and its parameters (sknnr_index_set_weight_law_params), the
     // weights launch_predict computes for a call that names the law (a workspace buffer behind ev_ws), and the record of
     // the last reduction (sknnr_debug_last_weight_law): law, rows, k, kernel ran
@@ -2130,6 +2157,17 @@ struct SummaryScope {
     SummaryScope(const SummaryScope&) = delete;
     SummaryScope& operator=(const SummaryScope&) = delete;
 };
+// The output plan of the call in progress, in the same way.
+struct PlanScope {
+    sknnr_index* ix;
+    const OutputPlan* before;
+    PlanScope(sknnr_index* ix_, const OutputPlan* plan) : ix(ix_), before(ix_->plan) { ix->plan = plan; }
+    ~PlanScope() { ix->plan = before; }
+    PlanScope(const PlanScope&) = delete;
+    PlanScope& operator=(const PlanScope&) = delete;
+};
+// Columns of a prediction row of the call in progress: the plan's entries, or the t targets.
+static inline int pred_cols(const sknnr_index* ix) { return ix->plan ? ix->plan->n_out : ix->t; }
 
 namespace {
 
@@ -2181,7 +2219,7 @@ int mask_compact(MaskBufs& m, const void* x, long n, size_t row_bytes, hipStream
 // expanded.  o->row_offset counts the valid rows in front of the tile.  d_pred: also predict; d_dist / d_idx may be null.
 int mask_finish(sknnr_index* ix, MaskBufs& m, const void* x, long n, long nv, const sknnr_query_opts* o, long fill_index,
                 double* d_dist, long* d_idx, double* d_pred, long valid_so_far, hipStream_t st) {
-    const int k = o->n_neighbors, t = ix->t;
+    const int k = o->n_neighbors, t = pred_cols(ix);  // (the prediction rows' width: the plan's entries, or the targets)
     const size_t row_bytes = (size_t)query_cols(ix, o) * dtype_bytes(o->query_dtype);
     int rc;
     if (nv == n) {
@@ -2227,7 +2265,7 @@ int run_device_masked(sknnr_index* ix, const void* q, long nq, const sknnr_query
     if (nq > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 query rows in one call");
     if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));  // the mask buffers belong to the workspace
     MaskBufs& m = ix->mask;
-    int rc = mask_ensure(m, nq, row_bytes, o->n_neighbors, ix->t, d_dist != nullptr, d_pred != nullptr);
+    int rc = mask_ensure(m, nq, row_bytes, o->n_neighbors, pred_cols(ix), d_dist != nullptr, d_pred != nullptr);
     if (rc) return rc;
     HIP_TRY(ix->m_nodata.ensure((size_t)d_x));
     HIP_TRY(hipMemcpyAsync(ix->m_nodata.p, nodata, (size_t)d_x * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2356,8 +2394,11 @@ struct HostPipe {
     long fill_index = -1;
     long row_offset0 = 0;                // o.row_offset when the pipeline was opened
     // per-target statistics (sknnr_stream_set_statistics): the reductions of this pipeline's tiles follow `stat`
-    bool has_stat = false;
+    bool has_stat = false, stat_set = false;  // (stat_set: the call was made, even with an all-mean table)
     SummaryPlan stat;
+    // output plan (sknnr_stream_set_plan): the prediction lane is plan.n_out wide and the reductions follow `plan`
+    bool has_plan = false;
+    OutputPlan plan;
     struct Pending {
         bool live = false;
         long n = 0;
@@ -2399,7 +2440,7 @@ int pipe_open(HostPipe& p, sknnr_index* ix, const sknnr_query_opts* o, bool want
     // writes indices and distances whether or not the distances leave.
     p.lane[kLaneIdx] = {true, true, p.k, kNarrowIndex};  // (want, search_out, cols, kind)
     p.lane[kLaneDist] = {want_dist, true, p.k, kNarrowValue};
-    p.lane[kLanePred] = {want_pred, false, p.t, kNarrowValue};
+    p.lane[kLanePred] = {want_pred, false, pred_cols(ix), kNarrowValue};  // (a one-shot call's plan is already in place)
     p.mask_dist = want_dist || want_pred;
     p.d_x = query_cols(ix, o);
     p.x_esz = (size_t)dtype_bytes(o->query_dtype);
@@ -2456,7 +2497,7 @@ int pipe_prepare_slot(HostPipe& p, int b, long n, bool planes = false) {
         if (ln.want && ln.converts()) HIP_TRY(sb.nar.ensure(units));
         if (ln.want && !ln.converts() && planes) HIP_TRY(sb.planes.ensure(wide));  // (the untyped results as planes)
     }
-    if (p.nodata_dev && (rc = mask_ensure(sl.mask, n, (size_t)p.d_x * p.x_esz, p.k, p.t, p.lane[kLaneDist].want, p.lane[kLanePred].want)))
+    if (p.nodata_dev && (rc = mask_ensure(sl.mask, n, (size_t)p.d_x * p.x_esz, p.k, p.lane[kLanePred].cols, p.lane[kLaneDist].want, p.lane[kLanePred].want)))
         return rc;
     return SKNNR_OK;
 }
@@ -2578,6 +2619,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     if ((rc = pipe_enqueue_d2h(p))) return rc;
     HIP_TRY(hipStreamWaitEvent(ix->st_run, sl.ev_h2d, 0));
     SummaryScope scope(ix, p.has_stat ? &p.stat : ix->summary);  // (a one-shot call's plan is already in place)
+    PlanScope plan_scope(ix, p.has_plan ? &p.plan : ix->plan);
     if (p.nodata_dev) {
         // (distances only where the slot has packed distances to expand from: mask_ensure sizes them by the same rule)
         rc = mask_finish(ix, sl.mask, sl.dev_x.p, n, nv, &p.o, p.fill_index, p.mask_dist ? dist.f64() : nullptr, idx.i64(),
@@ -2798,12 +2840,12 @@ int run_host_pipeline(sknnr_index* ix, const void* q, long nq, const sknnr_query
 // travel.  Runs on the default stream, chunk by chunk.
 int run_self_rows(sknnr_index* ix, long nq, const sknnr_query_opts* o, double* out_dist, long* out_idx, double* out_pred) {
     hipStream_t st = nullptr;
-    const int k = o->n_neighbors;
+    const int k = o->n_neighbors, pc = pred_cols(ix);
     for (long c0 = 0; c0 < nq; c0 += kChunkRows) {
         const long n = std::min<long>(kChunkRows, nq - c0);
         HIP_TRY(ix->dist_stage.ensure((size_t)n * k));
         HIP_TRY(ix->idx_stage.ensure((size_t)n * k));
-        if (out_pred) HIP_TRY(ix->pred_stage.ensure((size_t)n * ix->t));
+        if (out_pred) HIP_TRY(ix->pred_stage.ensure((size_t)n * pc));
         sknnr_query_opts oc = *o;
         oc.row_offset = o->row_offset + c0;
         int rc = run_device(ix, nullptr, n, &oc, ix->dist_stage.p, ix->idx_stage.p, st);
@@ -2811,7 +2853,7 @@ int run_self_rows(sknnr_index* ix, long nq, const sknnr_query_opts* o, double* o
         if (out_pred) {
             rc = launch_predict(ix, ix->dist_stage.p, ix->idx_stage.p, nullptr, n, k, o->weight_mode, o->weight_law, ix->pred_stage.p, st);
             if (rc) return rc;
-            HIP_TRY(hipMemcpyAsync(out_pred + c0 * ix->t, ix->pred_stage.p, (size_t)n * ix->t * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out_pred + c0 * pc, ix->pred_stage.p, (size_t)n * pc * sizeof(double), hipMemcpyDeviceToHost, st));
         }
         if (out_dist)
             HIP_TRY(hipMemcpyAsync(out_dist + c0 * k, ix->dist_stage.p, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -3411,6 +3453,53 @@ static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, 
     }
     const int64_t law_rec[8] = {law, nq, k, law != kLawNone ? 1 : 0, 0, 0, 0, 0};
     std::copy(std::begin(law_rec), std::end(law_rec), ix->last_law);
+    if (const OutputPlan* op = ix->plan) {
+        // An output plan: `out` is (nq, n_out).  The unchanged predict kernels give the plan's `mean` entries their values
+        // through the handle's (nq, t) mean_stage -- a workspace buffer, so `st` first waits for the workspace's last user
+        // -- and plan_kernel writes every entry.
+        const bool means = op->n_mean > 0;
+        if (means) {
+            if (ix->ws_busy && law == kLawNone) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));
+            HIP_TRY(ix->mean_stage.ensure((size_t)nq * ix->t));
+            PredictArgs a{};
+            a.y = ix->y64.p;
+            a.dist = dist;
+            a.idx = idx;
+            a.w = w;
+            a.nq = nq;
+            a.k = k;
+            a.t = ix->t;
+            a.mode = mode & SKNNR_WEIGHTS_BASE_MASK;
+            a.y32 = (mode & SKNNR_WEIGHTS_F32_TARGETS) ? 1 : 0;
+            a.w32 = (mode & SKNNR_WEIGHTS_F32_WEIGHTS) ? 1 : 0;
+            a.out = ix->mean_stage.p;
+            HIP_TRY(launch::predict(a, st));
+        }
+        PlanArgs a{};
+        a.y = ix->y64.p;
+        a.dist = dist;
+        a.idx = idx;
+        a.w = w;
+        a.nq = nq;
+        a.k = k;
+        a.t = ix->t;
+        a.mode = mode & SKNNR_WEIGHTS_BASE_MASK;
+        a.cols = op->cols;
+        a.codes = op->codes;
+        a.param = op->param;
+        a.n_out = op->n_out;
+        a.mean = means ? ix->mean_stage.p : nullptr;
+        a.out = out;
+        HIP_TRY(launch::plan(a, st));
+        const int64_t prec[8] = {1, k <= kSummarySmallK ? 1 : 2, nq, op->n_out, k, op->n_mean, means ? 1 : 0, 0};
+        std::copy(std::begin(prec), std::end(prec), ix->last_plan);
+        const int64_t srec[8] = {0, nq, 0, k, means ? 1 : 0, ix->t, mode & SKNNR_WEIGHTS_BASE_MASK, 0};  // (no summary kernel)
+        std::copy(std::begin(srec), std::end(srec), ix->last_summary);
+        HIP_TRY(hipEventRecord(ix->ev_ws, st));
+        ix->ws_busy = true;
+        return SKNNR_OK;
+    }
+    std::fill(std::begin(ix->last_plan), std::end(ix->last_plan), 0);  // (host record only: no plan kernel in this reduction)
     const SummaryPlan* sp = ix->summary;
     const bool means = !sp || sp->n_mean > 0;
     if (means) {
@@ -3462,15 +3551,62 @@ static int summary_check(const sknnr_index* ix, const int32_t* stat, std::vector
     return SKNNR_OK;
 }
 
-// sknnr_predict_from_neighbors (summarize false) and sknnr_summarize_from_neighbors
+// An output plan as a caller hands it over (host arrays of n_out entries), checked before any device work.
+struct PlanSpec {
+    const int32_t* cols;
+    const int32_t* stat;
+    const double* param;
+    int32_t n_out;
+};
+static int plan_check(const sknnr_index* ix, const PlanSpec& ps, int* n_mean) {
+    if (!ps.cols || !ps.stat || !ps.param) return fail(SKNNR_ERR_INVALID, "cols / stat / param is NULL");
+    if (ps.n_out < 1 || ps.n_out > kPlanMaxOut)
+        return fail(SKNNR_ERR_INVALID, "n_out = %d outside [1, %d]", ps.n_out, kPlanMaxOut);
+    *n_mean = 0;
+    for (int e = 0; e < ps.n_out; ++e) {
+        if (ps.cols[e] < 0 || ps.cols[e] >= ix->t)
+            return fail(SKNNR_ERR_INVALID, "cols[%d] = %d: the handle has %d targets", e, ps.cols[e], ix->t);
+        if (ps.stat[e] < 0 || ps.stat[e] >= kPlanStatCount)
+            return fail(SKNNR_ERR_INVALID, "stat[%d] = %d is no sknnr_statistic", e, ps.stat[e]);
+        if (ps.stat[e] == kStatQuantile && !(ps.param[e] >= 0.0 && ps.param[e] <= 1.0))
+            return fail(SKNNR_ERR_INVALID, "param[%d] = %g: a quantile's q lies in [0, 1]", e, ps.param[e]);
+        if (ps.stat[e] == kStatMean) ++*n_mean;
+    }
+    return SKNNR_OK;
+}
+// The plan's arrays into `buf` (the handle's c_plan: a workspace buffer, so the caller has waited for the workspace's last
+// user; or the open stream's s_plan).
+static int plan_upload(DevBuf<double>& buf, const PlanSpec& ps, int n_mean, OutputPlan& plan) {
+    const std::vector<double> img = plan_image(ps.cols, ps.stat, ps.param, ps.n_out);
+    HIP_TRY(buf.ensure(img.size()));
+    HIP_TRY(hipMemcpy(buf.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+    plan.n_out = ps.n_out;
+    plan.n_mean = n_mean;
+    plan.param = buf.p;
+    plan.cols = (const int*)(buf.p + ps.n_out);
+    plan.codes = plan.cols + ps.n_out;
+    return SKNNR_OK;
+}
+static int plan_upload_call(sknnr_index* ix, const PlanSpec& ps, int n_mean, OutputPlan& plan) {
+    if (ix->ws_busy) HIP_TRY(hipEventSynchronize(ix->ev_ws));
+    return plan_upload(ix->c_plan, ps, n_mean, plan);
+}
+
+// sknnr_predict_from_neighbors (summarize false, ps null), sknnr_summarize_from_neighbors (summarize) and
+// sknnr_summarize_plan_from_neighbors (ps: out_pred is (nq, n_out))
 static int reduce_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w, int64_t nq,
-                                 int32_t k, int32_t mode, bool summarize, const int32_t* stat, double* out_pred,
-                                 int32_t mem, void* stream) {
+                                 int32_t k, int32_t mode, bool summarize, const int32_t* stat, const PlanSpec* ps,
+                                 double* out_pred, int32_t mem, void* stream) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
     if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
     std::vector<int> tab;
     if (summarize) {
         const int rc = summary_check(ix, stat, tab);
+        if (rc) return rc;
+    }
+    int n_mean = 0;
+    if (ps) {
+        const int rc = plan_check(ix, *ps, &n_mean);
         if (rc) return rc;
     }
     if (nq < 0 || k < 1 || !idx || !out_pred) return fail(SKNNR_ERR_INVALID, "bad argument");
@@ -3491,13 +3627,20 @@ static int reduce_from_neighbors(sknnr_index* ix, const double* dist, const int6
         if (rc) return rc;
     }
     SummaryScope scope(ix, summarize ? &plan : nullptr);
+    OutputPlan oplan;
+    if (ps) {
+        const int rc = plan_upload_call(ix, *ps, n_mean, oplan);
+        if (rc) return rc;
+    }
+    PlanScope plan_scope(ix, ps ? &oplan : nullptr);
+    const int pc = pred_cols(ix);
     if (mem == SKNNR_MEM_DEVICE)
         return launch_predict(ix, dist, (const long*)idx, w, nq, k, mode, kLawNone, out_pred, (hipStream_t)stream);
     hipStream_t st = nullptr;
     DevBuf<double> dd, dw, dout;  // freed by their destructors on every return path
     DevBuf<long> di;
     HIP_TRY(di.ensure((size_t)nq * k));
-    HIP_TRY(dout.ensure((size_t)nq * ix->t));
+    HIP_TRY(dout.ensure((size_t)nq * pc));
     HIP_TRY(hipMemcpy(di.p, idx, (size_t)nq * k * sizeof(long), hipMemcpyHostToDevice));
     if (dist) {
         HIP_TRY(dd.ensure((size_t)nq * k));
@@ -3509,31 +3652,44 @@ static int reduce_from_neighbors(sknnr_index* ix, const double* dist, const int6
     }
     int rc = launch_predict(ix, dist ? dd.p : nullptr, di.p, w ? dw.p : nullptr, nq, k, mode, kLawNone, dout.p, st);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_pred, dout.p, (size_t)nq * ix->t * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_pred, dout.p, (size_t)nq * pc * sizeof(double), hipMemcpyDeviceToHost));
     return SKNNR_OK;
 }
 
 extern "C" int sknnr_predict_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w,
                                             int64_t nq, int32_t k, int32_t mode, double* out_pred, int32_t mem,
                                             void* stream) {
-    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, false, nullptr, out_pred, mem, stream);
+    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, false, nullptr, nullptr, out_pred, mem, stream);
 }
 
 extern "C" int sknnr_summarize_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w,
                                               int64_t nq, int32_t k, int32_t mode, const int32_t* stat, double* out,
                                               int32_t mem, void* stream) {
-    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, true, stat, out, mem, stream);
+    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, true, stat, nullptr, out, mem, stream);
 }
 
-// sknnr_predict (summarize false) and sknnr_summarize
+extern "C" int sknnr_summarize_plan_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w,
+                                                   int64_t nq, int32_t k, int32_t mode, const int32_t* cols,
+                                                   const int32_t* stat, const double* param, int32_t n_out, double* out,
+                                                   int32_t mem, void* stream) {
+    const PlanSpec ps{cols, stat, param, n_out};
+    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, false, nullptr, &ps, out, mem, stream);
+}
+
+// sknnr_predict (summarize false, ps null), sknnr_summarize (summarize) and sknnr_summarize_plan (ps: out_pred is (nq, n_out))
 static int search_and_reduce(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, bool summarize,
-                             const int32_t* stat, double* out_pred, double* out_dist, int64_t* out_idx, int32_t mem,
-                             void* stream) {
+                             const int32_t* stat, const PlanSpec* ps, double* out_pred, double* out_dist, int64_t* out_idx,
+                             int32_t mem, void* stream) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
     if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
     std::vector<int> tab;
     if (summarize) {
         const int rc0 = summary_check(ix, stat, tab);
+        if (rc0) return rc0;
+    }
+    int n_mean = 0;
+    if (ps) {
+        const int rc0 = plan_check(ix, *ps, &n_mean);
         if (rc0) return rc0;
     }
     if (!o) return fail(SKNNR_ERR_INVALID, "opts is NULL");
@@ -3557,6 +3713,9 @@ static int search_and_reduce(sknnr_index* ix, const void* q, int64_t nq, const s
     SummaryPlan plan;
     if (summarize && (rc = summary_upload(ix, tab, plan))) return rc;
     SummaryScope scope(ix, summarize ? &plan : nullptr);
+    OutputPlan oplan;
+    if (ps && (rc = plan_upload_call(ix, *ps, n_mean, oplan))) return rc;
+    PlanScope plan_scope(ix, ps ? &oplan : nullptr);
 
     if (mem == SKNNR_MEM_DEVICE) {
         hipStream_t st = (hipStream_t)stream;
@@ -3584,12 +3743,19 @@ static int search_and_reduce(sknnr_index* ix, const void* q, int64_t nq, const s
 
 extern "C" int sknnr_predict(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, double* out_pred,
                              double* out_dist, int64_t* out_idx, int32_t mem, void* stream) {
-    return search_and_reduce(ix, q, nq, o, false, nullptr, out_pred, out_dist, out_idx, mem, stream);
+    return search_and_reduce(ix, q, nq, o, false, nullptr, nullptr, out_pred, out_dist, out_idx, mem, stream);
 }
 
 extern "C" int sknnr_summarize(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, const int32_t* stat,
                                double* out, double* out_dist, int64_t* out_idx, int32_t mem, void* stream) {
-    return search_and_reduce(ix, q, nq, o, true, stat, out, out_dist, out_idx, mem, stream);
+    return search_and_reduce(ix, q, nq, o, true, stat, nullptr, out, out_dist, out_idx, mem, stream);
+}
+
+extern "C" int sknnr_summarize_plan(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o,
+                                    const int32_t* cols, const int32_t* stat, const double* param, int32_t n_out, double* out,
+                                    double* out_dist, int64_t* out_idx, int32_t mem, void* stream) {
+    const PlanSpec ps{cols, stat, param, n_out};
+    return search_and_reduce(ix, q, nq, o, false, nullptr, &ps, out, out_dist, out_idx, mem, stream);
 }
 
 extern "C" int sknnr_predict_masked(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o,
@@ -3652,6 +3818,8 @@ extern "C" int sknnr_stream_set_statistics(sknnr_stream* s, const int32_t* stat,
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(p.ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_statistics is allowed only before the first push");
+    if (p.has_plan) return fail(SKNNR_ERR_INVALID, "the stream has an output plan (sknnr_stream_set_plan): it takes no per-target statistics");
+    p.stat_set = true;
     p.stat = SummaryPlan{};
     p.stat.nc = (int)tab.size() / 2;
     p.stat.n_mean = p.t - p.stat.nc;
@@ -3662,6 +3830,27 @@ extern "C" int sknnr_stream_set_statistics(sknnr_stream* s, const int32_t* stat,
         p.stat.tab = p.ix->s_stat.p;
     }
     p.has_stat = p.stat.nc > 0;  // (an all-mean table: the stream enqueues what it did without one)
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_set_plan(sknnr_stream* s, const int32_t* cols, const int32_t* stat, const double* param,
+                                     int32_t n_out) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    HostPipe& p = s->pipe;
+    if (!p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
+    const PlanSpec ps{cols, stat, param, n_out};
+    int n_mean = 0;
+    int rc = plan_check(p.ix, ps, &n_mean);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(p.ix->mtx);
+    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan is allowed only before the first push");
+    if (p.stat_set) return fail(SKNNR_ERR_INVALID, "the stream has per-target statistics (sknnr_stream_set_statistics): it takes no output plan");
+    if (p.lane[kLanePred].scale)
+        return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan comes before sknnr_stream_set_output: the scale / offset hold one value per output plane");
+    HIP_TRY(hipSetDevice(p.ix->device));
+    if ((rc = plan_upload(p.ix->s_plan, ps, n_mean, p.plan))) return rc;
+    p.has_plan = true;
+    p.lane[kLanePred].cols = n_out;  // from now on the prediction lane is n_out wide
     return SKNNR_OK;
 }
 
@@ -3689,10 +3878,11 @@ extern "C" int sknnr_stream_set_output(sknnr_stream* s, int32_t idx_dtype, int32
     pl.scale = pl.offset = nullptr;
     if (pred_scale) {
         HIP_TRY(hipSetDevice(p.ix->device));
-        HIP_TRY(p.ix->s_scale.ensure((size_t)p.t));
-        HIP_TRY(p.ix->s_offset.ensure((size_t)p.t));
-        HIP_TRY(hipMemcpy(p.ix->s_scale.p, pred_scale, (size_t)p.t * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(p.ix->s_offset.p, pred_offset, (size_t)p.t * sizeof(double), hipMemcpyHostToDevice));
+        const size_t pc = (size_t)p.lane[kLanePred].cols;  // (one value per output plane: the plan's entries, or the targets)
+        HIP_TRY(p.ix->s_scale.ensure(pc));
+        HIP_TRY(p.ix->s_offset.ensure(pc));
+        HIP_TRY(hipMemcpy(p.ix->s_scale.p, pred_scale, pc * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(p.ix->s_offset.p, pred_offset, pc * sizeof(double), hipMemcpyHostToDevice));
         pl.scale = p.ix->s_scale.p;
         pl.offset = p.ix->s_offset.p;
     }
@@ -3928,6 +4118,14 @@ extern "C" int sknnr_debug_last_summary(const sknnr_index* cix, int64_t out[8]) 
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
     std::copy(std::begin(ix->last_summary), std::end(ix->last_summary), out);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_plan(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "index / out is NULL");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::copy(std::begin(ix->last_plan), std::end(ix->last_plan), out);
     return SKNNR_OK;
 }
 

@@ -48,76 +48,72 @@ __device__ __forceinline__ void summary_vote(double vote, double label, double& 
     }
 }
 
-#ifdef SKNNR_KERNELS_SUMMARY
-// k <= 8: indices, then target values and weights, requested before the first use and held in registers (as predict_kernel).
-__global__ void __launch_bounds__(256) summary_kernel(SummaryArgs a) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= a.nq * a.nc) return;
-    const long q = e / a.nc;
-    const int c = (int)(e - q * a.nc);
-    const int tt = a.tab[c], code = a.tab[a.nc + c];
-    const long* ids = a.idx + q * a.k;
-    const double* dd = a.dist ? a.dist + q * a.k : nullptr;
-    const double* ww = a.w ? a.w + q * a.k : nullptr;
+// ---- the statistics' bodies, shared by the kernels below and by plan_kernel / plan_wide_kernel (plan.hip.h) ---------------
+// k <= kSummarySmallK: the query's indices, then target column tt's values and the raw weights (1, the given weight, or the
+// DISTANCE: summary_small_weights turns it into predict's weight), requested before the first use and held in registers
+// (as predict_kernel).  Slots i >= k repeat neighbour 0's value and hold a neutral weight.
+__device__ __forceinline__ void summary_small_load(const double* y, const long* ids, const double* dd, const double* ww,
+                                                   int k, int t, int mode, int tt, double (&yv)[8], double (&wv)[8]) {
     long id[8];
-    double yv[8], wv[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) id[i] = i < a.k ? ids[i] : ids[0];
+    for (int i = 0; i < 8; ++i) id[i] = i < k ? ids[i] : ids[0];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        yv[i] = a.y[id[i] * a.t + tt];
-        wv[i] = a.mode == 0 ? 1.0 : (a.mode == 2 ? (i < a.k ? ww[i] : 0.0) : (i < a.k ? dd[i] : 1.0));
+        yv[i] = y[id[i] * t + tt];
+        wv[i] = mode == 0 ? 1.0 : (mode == 2 ? (i < k ? ww[i] : 0.0) : (i < k ? dd[i] : 1.0));
     }
-    double* out = a.out + q * a.t + tt;
-    if (code == kStatNearest) {
-        *out = yv[0];
-        return;
+}
+// distance weights: 1/d, or the row's 0/1 mask where it holds d == 0 (other modes: nothing changes)
+__device__ __forceinline__ void summary_small_weights(int k, int mode, double (&wv)[8]) {
+    if (mode == 1) {
+        bool any_zero = false;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) any_zero |= (i < k) && (wv[i] == 0.0);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) wv[i] = any_zero ? (wv[i] == 0.0 ? 1.0 : 0.0) : 1.0 / wv[i];
     }
+}
+// one of the five statistics (code != kStatMean) from the registers summary_small_load filled
+__device__ __forceinline__ double summary_small_stat(int code, int k, int t, int mode, const double (&yv)[8],
+                                                     double (&wv)[8]) {
+    if (code == kStatNearest) return yv[0];
     if (code == kStatMin || code == kStatMax) {
         double r = yv[0];
 #pragma unroll
         for (int i = 1; i < 8; ++i)
-            if (i < a.k) r = code == kStatMin ? (yv[i] < r ? yv[i] : r) : (yv[i] > r ? yv[i] : r);
-        *out = r;
-        return;
+            if (i < k) r = code == kStatMin ? (yv[i] < r ? yv[i] : r) : (yv[i] > r ? yv[i] : r);
+        return r;
     }
-    if (a.mode == 1) {
-        bool any_zero = false;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) any_zero |= (i < a.k) && (wv[i] == 0.0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wv[i] = any_zero ? (wv[i] == 0.0 ? 1.0 : 0.0) : 1.0 / wv[i];
-    }
+    summary_small_weights(k, mode, wv);
     if (code == kStatMode) {
         double best_vote = 0.0, best_label = __longlong_as_double(0x7ff8000000000000LL);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            bool first = i < a.k;  // one vote per first occurrence of a label
+            bool first = i < k;  // one vote per first occurrence of a label
 #pragma unroll
             for (int j = 0; j < i; ++j) first &= !(yv[j] == yv[i]);
             if (first) {
                 double tv[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) tv[j] = (j < a.k && yv[j] == yv[i]) ? wv[j] : 0.0;
-                summary_vote(np_sum_small(a.k, tv), yv[i], best_vote, best_label);
+                for (int j = 0; j < 8; ++j) tv[j] = (j < k && yv[j] == yv[i]) ? wv[j] : 0.0;
+                summary_vote(np_sum_small(k, tv), yv[i], best_vote, best_label);
             }
         }
-        *out = best_label;
-        return;
+        return best_label;
     }
     // kStatStd
     double m;
-    if (a.mode == 0 && a.t > 1) {
+    if (mode == 0 && t > 1) {
         double acc = yv[0];
 #pragma unroll
         for (int i = 1; i < 8; ++i)
-            if (i < a.k) acc = acc + yv[i];
-        m = acc / (double)a.k;
+            if (i < k) acc = acc + yv[i];
+        m = acc / (double)k;
     } else {
         double nv[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) nv[i] = yv[i] * wv[i];
-        m = np_sum_small(a.k, nv) / np_sum_small(a.k, wv);
+        m = np_sum_small(k, nv) / np_sum_small(k, wv);
     }
     double sv[8];
 #pragma unroll
@@ -125,72 +121,98 @@ __global__ void __launch_bounds__(256) summary_kernel(SummaryArgs a) {
         const double dv = yv[i] - m;
         sv[i] = (wv[i] * dv) * dv;
     }
-    *out = sqrt(np_sum_small(a.k, sv) / np_sum_small(a.k, wv));
+    return sqrt(np_sum_small(k, sv) / np_sum_small(k, wv));
 }
 
-// k up to kSummaryMaxK.  Labels and weights are re-read from L2 (the query's k indices and the target values they point at
-// were fetched by this very thread a moment ago); `mode` votes once per first occurrence of a label.
+// k up to kSummaryMaxK: a query's labels of column tt and its weights, re-read from L2 on every use (the query's k
+// indices and the target values they point at were fetched by this very thread a moment ago).
+struct SummaryRow {
+    const double* y;
+    const long* ids;
+    const double* dd;
+    const double* ww;
+    int k, t, mode, tt;
+    bool any_zero;  // distance weights: the row holds d == 0 (summary_row_zero)
+    __device__ __forceinline__ double label(int i) const { return y[ids[i] * t + tt]; }
+    __device__ __forceinline__ double weight(int i) const {
+        if (mode == 0) return 1.0;
+        if (mode == 2) return ww[i];
+        if (any_zero) return dd[i] == 0.0 ? 1.0 : 0.0;
+        return 1.0 / dd[i];
+    }
+};
+__device__ __forceinline__ bool summary_row_zero(const SummaryRow& r) {
+    bool any_zero = false;
+    if (r.mode == 1)
+        for (int i = 0; i < r.k; ++i) any_zero |= (r.dd[i] == 0.0);
+    return any_zero;
+}
+// one of the five statistics (code != kStatMean); `mode` votes once per first occurrence of a label
+__device__ __forceinline__ double summary_wide_stat(int code, SummaryRow& r) {
+    const int k = r.k;
+    if (code == kStatNearest) return r.label(0);
+    if (code == kStatMin || code == kStatMax) {
+        double m = r.label(0);
+        for (int i = 1; i < k; ++i) {
+            const double v = r.label(i);
+            m = code == kStatMin ? (v < m ? v : m) : (v > m ? v : m);
+        }
+        return m;
+    }
+    r.any_zero = summary_row_zero(r);
+    if (code == kStatMode) {
+        double best_vote = 0.0, best_label = __longlong_as_double(0x7ff8000000000000LL);
+        for (int i = 0; i < k; ++i) {
+            const double ci = r.label(i);
+            bool first = true;
+            for (int j = 0; j < i && first; ++j) first = !(r.label(j) == ci);
+            if (!first) continue;
+            const double vote = np_sum<double>(k, [&](int j) { return r.label(j) == ci ? r.weight(j) : 0.0; });
+            summary_vote(vote, ci, best_vote, best_label);
+        }
+        return best_label;
+    }
+    // kStatStd
+    const double den = np_sum<double>(k, [&](int i) { return r.weight(i); });
+    double m;
+    if (r.mode == 0 && r.t > 1) {
+        double acc = r.label(0);
+        for (int i = 1; i < k; ++i) acc = acc + r.label(i);
+        m = acc / (double)k;
+    } else {
+        m = np_sum<double>(k, [&](int i) { return r.label(i) * r.weight(i); }) / den;
+    }
+    const double ss = np_sum<double>(k, [&](int i) {
+        const double dv = r.label(i) - m;
+        return (r.weight(i) * dv) * dv;
+    });
+    return sqrt(ss / den);
+}
+
+#ifdef SKNNR_KERNELS_SUMMARY
+// k <= 8: summary_small_load, then summary_small_stat on the registers.
+__global__ void __launch_bounds__(256) summary_kernel(SummaryArgs a) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.nq * a.nc) return;
+    const long q = e / a.nc;
+    const int c = (int)(e - q * a.nc);
+    const int tt = a.tab[c], code = a.tab[a.nc + c];
+    double yv[8], wv[8];
+    summary_small_load(a.y, a.idx + q * a.k, a.dist ? a.dist + q * a.k : nullptr, a.w ? a.w + q * a.k : nullptr, a.k, a.t,
+                       a.mode, tt, yv, wv);
+    a.out[q * a.t + tt] = summary_small_stat(code, a.k, a.t, a.mode, yv, wv);
+}
+
+// k up to kSummaryMaxK: summary_wide_stat on the row.
 __global__ void __launch_bounds__(256) summary_wide_kernel(SummaryArgs a) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= a.nq * a.nc) return;
     const long q = e / a.nc;
     const int c = (int)(e - q * a.nc);
     const int tt = a.tab[c], code = a.tab[a.nc + c];
-    const long* ids = a.idx + q * a.k;
-    const double* dd = a.dist ? a.dist + q * a.k : nullptr;
-    const double* ww = a.w ? a.w + q * a.k : nullptr;
-    double* out = a.out + q * a.t + tt;
-    auto label = [&](int i) -> double { return a.y[ids[i] * a.t + tt]; };
-    if (code == kStatNearest) {
-        *out = label(0);
-        return;
-    }
-    if (code == kStatMin || code == kStatMax) {
-        double r = label(0);
-        for (int i = 1; i < a.k; ++i) {
-            const double v = label(i);
-            r = code == kStatMin ? (v < r ? v : r) : (v > r ? v : r);
-        }
-        *out = r;
-        return;
-    }
-    bool any_zero = false;
-    if (a.mode == 1)
-        for (int i = 0; i < a.k; ++i) any_zero |= (dd[i] == 0.0);
-    auto weight = [&](int i) -> double {
-        if (a.mode == 0) return 1.0;
-        if (a.mode == 2) return ww[i];
-        if (any_zero) return dd[i] == 0.0 ? 1.0 : 0.0;
-        return 1.0 / dd[i];
-    };
-    if (code == kStatMode) {
-        double best_vote = 0.0, best_label = __longlong_as_double(0x7ff8000000000000LL);
-        for (int i = 0; i < a.k; ++i) {
-            const double ci = label(i);
-            bool first = true;
-            for (int j = 0; j < i && first; ++j) first = !(label(j) == ci);
-            if (!first) continue;
-            const double vote = np_sum<double>(a.k, [&](int j) { return label(j) == ci ? weight(j) : 0.0; });
-            summary_vote(vote, ci, best_vote, best_label);
-        }
-        *out = best_label;
-        return;
-    }
-    // kStatStd
-    const double den = np_sum<double>(a.k, [&](int i) { return weight(i); });
-    double m;
-    if (a.mode == 0 && a.t > 1) {
-        double acc = label(0);
-        for (int i = 1; i < a.k; ++i) acc = acc + label(i);
-        m = acc / (double)a.k;
-    } else {
-        m = np_sum<double>(a.k, [&](int i) { return label(i) * weight(i); }) / den;
-    }
-    const double ss = np_sum<double>(a.k, [&](int i) {
-        const double dv = label(i) - m;
-        return (weight(i) * dv) * dv;
-    });
-    *out = sqrt(ss / den);
+    SummaryRow r{a.y, a.idx + q * a.k, a.dist ? a.dist + q * a.k : nullptr, a.w ? a.w + q * a.k : nullptr, a.k, a.t, a.mode,
+                 tt, false};
+    a.out[q * a.t + tt] = summary_wide_stat(code, r);
 }
 #endif  // SKNNR_KERNELS_SUMMARY
 
