@@ -894,6 +894,24 @@ int sknnr_debug_query_prep(const sknnr_index* index, int64_t n, void* qimg, doub
 int sknnr_debug_image_constants(const sknnr_index* index, double* mu, double* s, int32_t* cell_depth, float* axes,
                                 float* centre, float* thr);
 
+/*
+ * Debug only.  The plan a search call works out before its first launch (which pre-filter, which lists, which finaliser,
+ * which passes after it), for an index of n_ref x d reference rows with a cell tree of cell_depth levels and no affine
+ * map, and a call of nq float64 rows searching kk neighbours (n_neighbors, + 1 when exclude_self is set) by `formula`.
+ * The function the calls themselves run, on the description sknnr_index_create would leave: no handle, no device, so a
+ * test can sweep the dispatch rules without a GPU.  flags: 1 exclude_self, 2 raw (shard candidates), 4 every reference id
+ * fits the integer Hamming pre-filter, 8 the rescue re-sweep is enabled.
+ *   out[0 .. 4] what sknnr_debug_last_prefilter would report of a one-chunk call: generation (0: no pre-filter), KS, list
+ *               length, rank beyond the list, cell depth of a bucketed call
+ *   out[5] 1 = the finaliser works from merged candidate records      out[6] 1 = the rescue re-sweep runs
+ *   out[7] 1 = the integer Hamming pre-filter runs                    out[8] kk
+ *   out[9] query rows per device chunk      out[10] rows of the largest chunk with its padding
+ *   out[11] 1 = float64 transformed rows are written      out[12] columns of the caller's rows      out[13] check_finite
+ *   out[14] element type of the rows (sknnr_dtype)        out[15] bits: 1 the affine map applies, 2 the rows are reference rows
+ */
+int sknnr_debug_search_plan(int64_t n_ref, int32_t d, int32_t cell_depth, int32_t kk, int64_t nq, int32_t formula,
+                            int32_t flags, int64_t out[16]);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -133,6 +133,7 @@ EXPORTED_SYMBOLS = (
     "sknnr_debug_last_prep",
     "sknnr_debug_query_prep",
     "sknnr_debug_image_constants",
+    "sknnr_debug_search_plan",
 )
 
 
@@ -296,6 +297,8 @@ def load(build_if_missing: bool = False):
         lib.sknnr_debug_last_prep.argtypes = [vp, POINTER(c_int64)]
         lib.sknnr_debug_query_prep.argtypes = [vp, c_int64, vp, vp, vp, vp, vp, vp]
         lib.sknnr_debug_image_constants.argtypes = [vp, vp, POINTER(c_double), POINTER(c_int32), vp, vp, vp]
+    if hasattr(lib, "sknnr_debug_search_plan"):  # (likewise)
+        lib.sknnr_debug_search_plan.argtypes = [c_int64, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, POINTER(c_int64)]
     _lib = lib
     return lib
 
@@ -307,6 +310,21 @@ def check(code: int) -> None:
 
 def device_count() -> int:
     return int(load().sknnr_device_count())
+
+
+SEARCH_PLAN_FIELDS = ("generation", "ks", "m_list", "rank_extra", "cell_depth", "record", "rescue", "ham_int", "kk", "chunk",
+                      "cap_pad", "to_xt", "d_x", "check_finite", "x_dtype", "row_bits")
+
+
+def debug_search_plan(n_ref: int, d: int, kk: int, nq: int, cell_depth: int = 0, formula: int = FORMULA_EXPANDED,
+                      exclude_self: bool = False, raw: bool = False, h16_ok: bool = False, rescue_enabled: bool = True) -> dict:
+    """Debug only: the plan a search call works out before its first launch (sknnr_debug_search_plan), for an index of
+    ``n_ref`` x ``d`` rows with ``cell_depth`` levels of cells and a call of ``nq`` rows searching ``kk`` neighbours
+    (k, + 1 with ``exclude_self``).  No handle, no device."""
+    flags = (1 if exclude_self else 0) | (2 if raw else 0) | (4 if h16_ok else 0) | (8 if rescue_enabled else 0)
+    out = (c_int64 * 16)()
+    check(load().sknnr_debug_search_plan(n_ref, d, cell_depth, kk, nq, formula, flags, out))
+    return dict(zip(SEARCH_PLAN_FIELDS, out))
 
 
 def _host_ptr(a):

@@ -166,6 +166,27 @@ struct MaskBufs {
 constexpr int kMaskMaxCols = 1 << 16;  // the mask kernels index a block's elements with an int
 
 constexpr int kMaxKs = 8;              // coarse path: d <= 128
+// a switch that is on unless the variable is set to 0
+inline bool env_on(const char* name) {
+    const char* e = std::getenv(name);
+    return !(e && std::atoi(e) == 0);
+}
+constexpr size_t kLdsLimit = 150 * 1024;  // LDS bytes a workgroup of any kernel here may ask for
+// rows per block of prep_queries_kernel for rows of d_in columns, by what fits the LDS (0: too wide, d_in > 299)
+inline int prep_lds_rows(int d_in) {
+    for (int bt : {256, 128, 64})
+        if ((size_t)bt * (d_in | 1) * 8 <= kLdsLimit) return bt;
+    return 0;
+}
+// rows of a device chunk with its padding (the pre-filter's workgroups and the prep kernel's blocks divide kRowQuantum)
+inline long pad_rows(long n) { return (n + kRowQuantum - 1) / kRowQuantum * kRowQuantum; }
+// Stages of the second-generation image of n_ref rows: tiles of 32 rows, rounded up to whole stages of tiles_per_stage2(ks)
+// (0: no such image -- more than four K-steps, or no coarse image at all)
+inline int image_stages2(long n_ref, int ks) {
+    if (ks < 1 || ks > 4) return 0;
+    const int tps2 = tiles_per_stage2(ks);
+    return (int)(((n_ref + 31) / 32 + tps2 - 1) / tps2);
+}
 constexpr long kChunkRows = 1L << 22;  // rows per chunk of host-side staging loops (transform entry point, X=None results)
 // Query rows per device chunk of one call (each chunk: prep -> pre-filter -> finalise, padded to kRowQuantum).
 // One launch for as many rows as a 4 GiB workspace holds, at most 2^24: every pre-filter launch ends with a
@@ -299,6 +320,37 @@ private:
     std::thread th_;  // (last member: the thread starts when everything above exists)
 };
 
+// The debug records of the search path: every search call zeroes them first (zero_records), then each stage files its own.
+struct SearchRecords {
+    // the Euclidean pre-filter launches of the last device chunk of the last call (sknnr_debug_last_prefilter):
+    // generation, KS, list length, rank beyond the list, bulk waves, bulk rows, thin rows, cell depth
+    int64_t prefilter[8] = {};
+    // the finaliser launches of the last device chunk of the last call (sknnr_debug_last_finalize): lanes per query, record
+    // path (the rows its truncation rule sent to the exact scan are read from fail_count[3] when asked)
+    int64_t finalize[2] = {};
+    // the integer Hamming pre-filter of the last call (sknnr_debug_last_hamming): ran, kk, compacts, seed rows, band,
+    // tree pairs, device chunks (out[7], the rows handed to the exact scan, is read from fail_count when asked); rows of
+    // its last device chunk, whose candidate lists h_cand_cnt / h_cand_id still hold (sknnr_debug_hamming_candidates)
+    int64_t hamming[8] = {};
+    long hamming_rows = 0;
+    // the exact scan of the last call (sknnr_debug_last_scan): formula + 1, chunked, kk, workgroups and LDS bytes of the
+    // first scan launch, rows offered (host count; -1: the fail list's device count, read from fail_count[0] when asked),
+    // slices (0: whatever scan_slices gives for the count, worked out when asked; else fixed: 1 = the call cannot be
+    // sliced, or the shard count of a shard merge), 1 = count2 (fail_count[2]) holds the rows filed for the replay
+    int64_t scan[8] = {};
+    // the query preparation of the last device chunk of the last call (sknnr_debug_last_prep): kernel (1 direct, 2 LDS), rows
+    // per block, x_dtype, live rows, padded rows, xt written, who named the cells (1 the prep kernel, 2 cell_assign_kernel),
+    // bits center | scale << 1 | proj << 2; and what of that chunk the workspace holds (sknnr_debug_query_prep): its
+    // transformed rows, the cells and the permutation, |q'|^2 by position
+    int64_t prep[8] = {};
+    const double* prep_xt = nullptr;
+    bool prep_bucketed = false, prep_qnc_pos = false;
+    // the rescue re-sweep of the last call (sknnr_debug_last_rescue): launched, KS; the counts are read from resc_state
+    int64_t rescue[2] = {};
+    // the nodata front end of the last tile (sknnr_debug_last_mask)
+    int64_t mask[8] = {};
+};
+
 struct sknnr_index {
     int device = 0;
     long n_ref = 0;
@@ -362,7 +414,6 @@ struct sknnr_index {
     DevBuf<float> fail_thr;
     DevBuf<int> resc_list, resc_state;
     bool rescue_enabled = true;
-    int64_t last_rescue[2] = {};  // the last call (sknnr_debug_last_rescue): launched, KS; the counts are read from resc_state
     DevBuf<int> status;            // bit 0: a query value was NaN, bit 1: infinite (since the last poll)
     DevBuf<long long> fail_total;  // running count of certificate failures (device)
     DevBuf<long> idx_stage;
@@ -396,37 +447,12 @@ struct sknnr_index {
     // before the exact scan).
     hipStream_t st_side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    long bulk_rows_done = 0;  // rows whose pre-filter was complete at ev_fork (0: no fork in the last launch)
-    hipEvent_t ev_bulk_end = nullptr;  // the call record's end-of-pre-filter event; recorded at the fork when there is one
-    // the Euclidean pre-filter launches of the last device chunk of the last call (sknnr_debug_last_prefilter):
-    // generation, KS, list length, rank beyond the list, bulk waves, bulk rows, thin rows, cell depth
-    int64_t last_prefilter[8] = {};
-    // the finaliser launches of the last device chunk of the last call (sknnr_debug_last_finalize): lanes per query, record
-    // path (the rows its truncation rule sent to the exact scan are read from fail_count[3] when asked)
-    int64_t last_finalize[2] = {};
-    // the integer Hamming pre-filter of the last call (sknnr_debug_last_hamming): ran, kk, compacts, seed rows, band,
-    // tree pairs, device chunks (out[7], the rows handed to the exact scan, is read from fail_count when asked); rows of
-    // its last device chunk, whose candidate lists h_cand_cnt / h_cand_id still hold (sknnr_debug_hamming_candidates)
-    int64_t last_hamming[8] = {};
-    long last_hamming_rows = 0;
-    // the exact scan of the last call (sknnr_debug_last_scan): formula + 1, chunked, kk, workgroups and LDS bytes of the
-    // first scan launch, rows offered (host count; -1: the fail list's device count, read from fail_count[0] when asked),
-    // slices (0: whatever scan_slices gives for the count, worked out when asked; else fixed: 1 = the call cannot be
-    // sliced, or the shard count of a shard merge), 1 = count2 (fail_count[2]) holds the rows filed for the replay
-    int64_t last_scan[8] = {};
-    // the query preparation of the last device chunk of the last call (sknnr_debug_last_prep): kernel (1 direct, 2 LDS), rows
-    // per block, x_dtype, live rows, padded rows, xt written, who named the cells (1 the prep kernel, 2 cell_assign_kernel),
-    // bits center | scale << 1 | proj << 2; and what of that chunk the workspace holds (sknnr_debug_query_prep): its
-    // transformed rows, the cells and the permutation, |q'|^2 by position
-    int64_t last_prep[8] = {};
-    const double* last_prep_xt = nullptr;
-    bool last_prep_bucketed = false, last_prep_qnc_pos = false;
+    SearchRecords last;  // what the last search left for the sknnr_debug_last_* entries
     bool stream_open = false;  // a sknnr_stream owns the host pipeline's slots
     // nodata front end: the buffers of device-memory calls, the nodata values of one-shot calls and of the open stream,
-    // and the record of the last tile (sknnr_debug_last_mask)
+    // (the record of the last tile is SearchRecords::mask)
     MaskBufs mask;
     DevBuf<double> m_nodata, s_nodata;
-    int64_t last_mask[8] = {};
     // the last tile of the host pipeline (sknnr_debug_last_planes): rows arrived as planes, rows, columns, element bytes,
     // results left as planes, output planes written, columns per workgroup of planes_to_rows_kernel
     int64_t last_planes[8] = {};
@@ -478,34 +504,11 @@ struct sknnr_index {
     ~sknnr_index() {
         w_in.reset();   // (joins: no job may outlive the buffers below)
         w_out.reset();
-        (void)hipSetDevice(device);
-        for (auto* b : {&center, &scale, &proj, &ref64, &refT, &rn64, &y64, &mu_dev, &xt, &qnc, &xstage,
-                        &dist_stage, &pred_stage, &f_ids})
-            b->release();
-        f_nodes.release(); f_off.release(); f_depth.release();
-        rimg.release();
-        perm.release();
-        perm2.release();
-        cell_axes.release(); cell_centre.release(); cell_thr.release(); cell_stage.release();
-        qcell.release(); qperm.release(); cell_hist.release();
-        h_rimg.release(); h_wq.release(); h_qimg.release(); h_rrow.release(); h_bad.release(); h_cand_cnt.release(); h_cand_id.release();
-        qimg.release();
-        cand_val.release();
-        cand_idx.release();
-        rec.release(); rec_bound.release(); qnc_pos.release();
-        fail_list.release();
-        fail_count.release();
-        fail_thr.release(); resc_list.release(); resc_state.release();
-        fail_total.release();
-        status.release();
-        idx_stage.release();
+        (void)hipSetDevice(device);  // (the DevBuf members free themselves behind this body)
         for (auto& sl : slot) {
             if (sl.pin_x) (void)hipHostFree(sl.pin_x);
-            sl.dev_x.release(); sl.dev_xp.release();
-            for (auto& ln : sl.lane) {
+            for (auto& ln : sl.lane)
                 if (ln.pin) (void)hipHostFree(ln.pin);
-                ln.dev.release(); ln.planes.release(); ln.nar.release();
-            }
             for (hipEvent_t e : {sl.ev_h2d, sl.ev_done, sl.ev_d2h})
                 if (e) (void)hipEventDestroy(e);
         }
@@ -984,8 +987,8 @@ extern "C" int sknnr_index_create(const double* ref, int64_t n_ref, int32_t d, c
             // second-generation kernel: hi fragments + |r'|^2 per tile (staged through LDS), lo fragments in an
             // array of their own (read from L2 by the flush only)
             const int tps2 = tiles_per_stage2(ks);
-            const long n_tiles2 = ((n_ref + 31) / 32 + tps2 - 1) / tps2 * tps2;
-            ix->n_stages2 = (int)(n_tiles2 / tps2);
+            ix->n_stages2 = image_stages2(n_ref, ks);
+            const long n_tiles2 = (long)ix->n_stages2 * tps2;
             // ... in CELL order when the kernel will serve this index (bucket.hip.h): rows sorted by the cell of a
             // median-split tree over the leading principal axes (inside a cell: by centred norm), so that a workgroup
             // whose query rows were bucketed by the same tree starts its sweep among their neighbours
@@ -1100,10 +1103,7 @@ extern "C" int sknnr_index_create(const double* ref, int64_t n_ref, int32_t d, c
 
     HIP_TRY(ix->fail_count.ensure(4));
     HIP_TRY(ix->resc_state.ensure(kRescueWords));
-    {
-        const char* e = std::getenv("SKNNR_RESCUE");
-        ix->rescue_enabled = !(e && std::atoi(e) == 0);
-    }
+    ix->rescue_enabled = env_on("SKNNR_RESCUE");
     HIP_TRY(ix->fail_total.ensure(2));
     HIP_TRY(hipMemset(ix->fail_total.p, 0, 16));
     HIP_TRY(ix->status.ensure(4));
@@ -1191,7 +1191,7 @@ extern "C" int sknnr_index_set_hamming_weights(sknnr_index* ix, const double* w,
         bool any_bad = false;
         for (int v : hb) any_bad = any_bad || v != 0;
         const int tpr = ham_row_dwords(n);
-        bool rows_ok = n <= 4096 && hamming_rescore_lds(n) <= 150 * 1024;
+        bool rows_ok = n <= 4096 && hamming_rescore_lds(n) <= kLdsLimit;
         if (rows_ok && ix->h_rrow.ensure((size_t)ix->n_ref * tpr) != hipSuccess) {
             // (the row-major image takes a KiB per row and 512 trees: when it does not fit, the float64 scan serves the index)
             (void)hipGetLastError();
@@ -1281,7 +1281,7 @@ extern "C" int sknnr_affine_transform(const double* x, int64_t n, int32_t d_in, 
     if (device < 0 || device >= n_dev) return fail(SKNNR_ERR_INVALID, "device %d out of range [0, %d)", device, n_dev);
     HIP_TRY(hipSetDevice(device));
     const int ks = (d + 15) / 16, dp = 16 * ks;
-    if ((size_t)64 * (d_in | 1) * 8 > 150 * 1024)
+    if (!prep_lds_rows(d_in))
         return fail(SKNNR_ERR_UNSUPPORTED, "d_in = %d is too wide for the transform kernel (max 299)", d_in);
     DevBuf<double> dx, dc, dsc, dpj, dout;
     int rc = SKNNR_OK;
@@ -1327,9 +1327,7 @@ extern "C" int sknnr_affine_transform(const double* x, int64_t n, int32_t d_in, 
         a.scale = scale ? dsc.p : nullptr;
         a.proj = proj ? dpj.p : nullptr;
         a.xt = dout.p;
-        const int ldx = d_in | 1;
-        const int bt = (size_t)256 * ldx * 8 <= 150 * 1024 ? 256 : ((size_t)128 * ldx * 8 <= 150 * 1024 ? 128 : 64);
-        AT_TRY(launch::prep_lds(bt, a, nullptr));
+        AT_TRY(launch::prep_lds(prep_lds_rows(d_in), a, nullptr));
         AT_TRY(hipMemcpy(out + c0 * d, dout.p, (size_t)m * d * sizeof(double), hipMemcpyDeviceToHost));
     }
 #undef AT_TRY
@@ -1420,14 +1418,44 @@ extern "C" int sknnr_check_finite(sknnr_index* ix, void* stream) {
 // ----------------------------------------------------------------------------------------
 namespace {
 
-// `cells`: also name every row's cell (query bucketing); *cells_done tells whether this kernel did (the
+// What the dispatch rules read of an index: plain numbers (sknnr_debug_search_plan fills one without a handle).
+struct IndexDesc { long n_ref; int d, ks, d_in, n_stages2, cell_depth; bool rescue_enabled, h16_ok; };
+IndexDesc describe(const sknnr_index* ix) {
+    return IndexDesc{ix->n_ref, ix->d, ix->ks, ix->d_in, ix->n_stages2, ix->cell_depth, ix->rescue_enabled, ix->h16_ok};
+}
+
+// Everything a search call decides before its first launch (plan_search, below): run_device works it out once and every
+// stage reads it.
+struct SearchPlan {
+    int kk;                  // neighbours searched: n_neighbors, + 1 for the row itself when exclude_self is set
+    bool affine, self_rows;  // the rows go through the affine map; no rows given: reference rows from row_offset on
+    // rows narrower than float64 (opts->query_dtype): the prep kernel widens them and writes the float64 rows everything
+    // after it reads (finaliser, exact scan), as it does for rows that go through the affine map
+    int x_dtype;
+    bool to_xt;
+    int d_x;                 // columns of the caller's rows
+    bool check_finite;
+    bool coarse, v2;         // the Euclidean pre-filter runs; ... the second-generation kernel (use_coarse2)
+    int m_list, rank_extra;  // list length per lane (coarse_list_len); thresholds of rank m_list + rank_extra
+    bool record;             // the finaliser works from merged candidate records (use_record)
+    bool rescue, bucketed;   // listed rows are swept again before the exact scan (rescue.hip.h); rows bucketed by cell
+    bool ham_int;            // the integer pre-filter of the weighted-Hamming search runs (hamming.hip.h)
+    long chunk, cap_pad;     // query rows per device chunk (chunk_rows); the largest chunk's rows with their padding
+};
+
+// The pre-filters skip a tile whose smallest possible value lies this far (times |q'|) above the threshold; the rescue
+// sweep uses the same scale
+float skip_scale(const sknnr_index* ix) { return (float)(std::ldexp(1.0, -9) * ix->ymax * 1.02); }
+
+// p.bucketed: also name every row's cell (query bucketing); *cells_done tells whether this kernel did (the
 // register-resident one does; otherwise the caller runs cell_assign_kernel on the transformed rows)
-int launch_prep(sknnr_index* ix, const void* x, long nq, long nq_pad, bool affine, double* xt,
-                hipStream_t st, bool check_finite = false, bool cells = false, bool* cells_done = nullptr, int x_dtype = kDtypeF64) {
+int launch_prep(sknnr_index* ix, const SearchPlan& p, const void* x, long nq, long nq_pad, double* xt, hipStream_t st,
+                bool* cells_done = nullptr) {
+    const bool affine = p.affine;
     PrepArgs a{};
-    a.x_dtype = x_dtype;
+    a.x_dtype = p.x_dtype;
     if (cells_done) *cells_done = false;
-    a.status = check_finite ? ix->status.p : nullptr;
+    a.status = p.check_finite ? ix->status.p : nullptr;
     a.x = x;
     a.nq = nq;
     a.nq_pad = nq_pad;
@@ -1442,17 +1470,15 @@ int launch_prep(sknnr_index* ix, const void* x, long nq, long nq_pad, bool affin
     a.xt = xt;
     a.qimg = ix->qimg.p;
     a.qnc = ix->qnc.p;
-    const int ldx = a.d_in | 1;
-    const size_t lim = 150 * 1024;
-    int64_t* r = ix->last_prep;
+    int64_t* r = ix->last.prep;
     std::fill(r, r + 8, 0);
-    ix->last_prep_xt = nullptr;
-    ix->last_prep_bucketed = ix->last_prep_qnc_pos = false;
-    r[2] = x_dtype, r[3] = nq, r[4] = nq_pad, r[5] = xt ? 1 : 0;
+    ix->last.prep_xt = nullptr;
+    ix->last.prep_bucketed = ix->last.prep_qnc_pos = false;
+    r[2] = p.x_dtype, r[3] = nq, r[4] = nq_pad, r[5] = xt ? 1 : 0;
     r[7] = (a.center ? 1 : 0) | (a.scale ? 2 : 0) | (a.proj ? 4 : 0);
     if (ix->ks <= 4 && !std::getenv("SKNNR_PREP_LDS")) {
         // narrow feature spaces: register-resident kernel (no LDS, high occupancy)
-        if (cells && ix->cell_depth > 0) {
+        if (p.bucketed && ix->cell_depth > 0) {
             a.tree = CellTreeDev{ix->cell_axes.p, ix->cell_centre.p, ix->cell_thr.p, ix->cell_depth};
             a.cell = ix->qcell.p;
             if (cells_done) *cells_done = true;
@@ -1460,32 +1486,27 @@ int launch_prep(sknnr_index* ix, const void* x, long nq, long nq_pad, bool affin
         }
         HIP_TRY(launch::prep_direct(a, st));
         r[0] = 1, r[1] = 256;
-    } else if ((size_t)256 * ldx * 8 <= lim) {
-        HIP_TRY(launch::prep_lds(256, a, st));
-        r[0] = 2, r[1] = 256;
-    } else if ((size_t)128 * ldx * 8 <= lim) {
-        HIP_TRY(launch::prep_lds(128, a, st));
-        r[0] = 2, r[1] = 128;
-    } else if ((size_t)64 * ldx * 8 <= lim) {
-        HIP_TRY(launch::prep_lds(64, a, st));
-        r[0] = 2, r[1] = 64;
+    } else if (const int bt = prep_lds_rows(a.d_in)) {
+        HIP_TRY(launch::prep_lds(bt, a, st));
+        r[0] = 2, r[1] = bt;
     } else {
         std::fill(r, r + 8, 0);
         return fail(SKNNR_ERR_UNSUPPORTED, "d_in = %d is too wide for the query preparation kernel (max 299)", a.d_in);
     }
-    ix->last_prep_xt = xt;
+    ix->last.prep_xt = xt;
     return SKNNR_OK;
 }
 
 // first-generation pre-filter (k_coarse1.hip)
-int launch_coarse(sknnr_index* ix, long nq_pad, int m_list, int kk, hipStream_t st) {
-    launch::Coarse1Launch L{ix->rimg.p, ix->n_stages, ix->qimg.p, ix->qnc.p, (float)(std::ldexp(1.0, -9) * ix->ymax * 1.02),
-                            m_list - (kk + 1), ix->cand_val.p, ix->cand_idx.p, nq_pad};
+int launch_coarse(sknnr_index* ix, const SearchPlan& p, long nq_pad, hipStream_t st) {
+    const int m_list = p.m_list;
+    launch::Coarse1Launch L{ix->rimg.p, ix->n_stages, ix->qimg.p, ix->qnc.p, skip_scale(ix),
+                            m_list - (p.kk + 1), ix->cand_val.p, ix->cand_idx.p, nq_pad};
     hipError_t e = hipSuccess;
     if (launch::coarse1(ix->ks, m_list, L, st, &e) == launch::kNoInstance)
         return fail(SKNNR_ERR_UNSUPPORTED, "no coarse kernel for ks = %d, list length %d", ix->ks, m_list);
     HIP_TRY(e);
-    int64_t* r = ix->last_prefilter;
+    int64_t* r = ix->last.prefilter;
     r[0] = 1, r[1] = ix->ks, r[2] = m_list, r[3] = 0, r[4] = coarse_waves(ix->ks, m_list), r[5] = nq_pad;
     return SKNNR_OK;
 }
@@ -1498,31 +1519,28 @@ constexpr int kCusPerDevice = 256;
 // two K-steps -- up to 5 neighbours searched on up to 32 features).
 // SKNNR_FINALIZE_RECORD=0 keeps the lists and finalize_kernel<8> (A/B runs).
 bool use_record(int ks, int m_list, int kk, bool v2, int raw) {
-    static const bool enabled = [] {
-        const char* e = std::getenv("SKNNR_FINALIZE_RECORD");
-        return !(e && std::atoi(e) == 0);
-    }();
+    static const bool enabled = env_on("SKNNR_FINALIZE_RECORD");
     return enabled && v2 && !raw && coarse2_record_supported(ks, m_list, coarse2_rank_extra(m_list, kk));
 }
 
-int launch_coarse2_waves(sknnr_index* ix, int m_list, int waves, long row0, long rows, int kk, bool record, hipStream_t st) {
+int launch_coarse2_waves(sknnr_index* ix, const SearchPlan& p, int waves, long row0, long rows, hipStream_t st) {
     // more neighbours than a list holds: thresholds of rank M + E, no sentinels (coarse2_rank_extra)
-    const int extra = coarse2_rank_extra(m_list, kk);
+    const int m_list = p.m_list, kk = p.kk, extra = p.rank_extra;
     if (extra != 0 && !((m_list == 16 && kk <= kCoarse2MaxKK16) || (m_list == 12 && kk <= kCoarse2MaxKK12) || (m_list == 8 && kk <= kCoarse2MaxKK8) || (m_list == 6 && kk <= kCoarse2MaxKK6)))
         return fail(SKNNR_ERR_UNSUPPORTED, "lists of %d cannot serve %d neighbours", m_list, kk);
     // positions [row0, row0 + rows) of the chunk (bucketed calls: position -> row through qperm, else the row itself)
-    const bool bucketed = ix->cell_depth > 0;
-    launch::Coarse2Launch L{ix->rhi2.p, ix->rlo2.p, ix->n_stages2, ix->qimg.p, ix->qnc.p, (float)(std::ldexp(1.0, -9) * ix->ymax * 1.02),
+    const bool bucketed = p.bucketed;
+    launch::Coarse2Launch L{ix->rhi2.p, ix->rlo2.p, ix->n_stages2, ix->qimg.p, ix->qnc.p, skip_scale(ix),
                             extra != 0 ? 0 : m_list - (kk + 1), ix->cand_val.p, ix->cand_idx.p, (int)row0,
                             bucketed ? ix->qperm.p : nullptr, bucketed ? ix->qcell.p : nullptr,
                             bucketed ? ix->cell_stage.p : nullptr, rows,
-                            Coarse2Record{record ? ix->rec.p : nullptr, ix->rec_bound.p, ix->perm2.p, (int)ix->n_ref}};
+                            Coarse2Record{p.record ? ix->rec.p : nullptr, ix->rec_bound.p, ix->perm2.p, (int)ix->n_ref}};
     hipError_t e = hipSuccess;
     if (launch::coarse2(ix->ks, m_list, waves, extra, L, st, &e) == launch::kNoInstance)
         return fail(SKNNR_ERR_UNSUPPORTED, "no second-generation coarse kernel for ks = %d, list length %d, %d waves, rank + %d", ix->ks,
                     m_list, waves, extra);
     HIP_TRY(e);
-    int64_t* r = ix->last_prefilter;
+    int64_t* r = ix->last.prefilter;
     r[0] = 2, r[1] = ix->ks, r[2] = m_list, r[3] = extra;
     if (waves == kCoarse2TailWaves) {
         r[6] += rows;
@@ -1539,53 +1557,50 @@ int launch_coarse2_waves(sknnr_index* ix, int m_list, int waves, long row0, long
 // the CUs' worth) go to 4-wave workgroups instead: four times as many CUs, one wave per SIMD.
 // `rows`: the live rows of the chunk -- its padding rows (up to kRowQuantum - 1 of them, behind the live ones also in a
 // bucketed call) get no workgroups of their own: a 262,144-row call is 256 workgroups, not 258 with a thin round of two.
-int launch_coarse2(sknnr_index* ix, long rows, int m_list, int kk, bool record, hipStream_t st) {
+// With a thin round and a side stream, the bulk launch is followed by `ev_bulk_end` (the timed region ends there: the
+// thin round shares the device from then on) and by the fork event; *fork tells the caller, who finalises the bulk rows
+// beside the thin round: the rows whose pre-filter was complete at ev_fork (0: no fork), whether ev_bulk_end was recorded.
+struct BulkFork { long rows_done = 0; bool recorded = false; };
+int launch_coarse2(sknnr_index* ix, const SearchPlan& p, long rows, hipEvent_t ev_bulk_end, BulkFork* fork, hipStream_t st) {
+    const int m_list = p.m_list;
     if (!coarse2_supported(ix->ks, m_list))
         return fail(SKNNR_ERR_UNSUPPORTED, "no second-generation coarse kernel for ks = %d, list length %d", ix->ks, m_list);
     const int BULK_WAVES = coarse2_waves(ix->ks, m_list);
     const long QPB = BULK_WAVES * kCoarse2Nqb * 32;
     const long QPB_TAIL = kCoarse2TailWaves * kCoarse2Nqb * 32;
-    static const bool split = [] {
-        const char* e = std::getenv("SKNNR_COARSE_TAIL");
-        return !(e && std::atoi(e) == 0);
-    }();
+    static const bool split = env_on("SKNNR_COARSE_TAIL");
     const long n_wg = (rows + QPB - 1) / QPB;
     long tail_wg = n_wg % kCusPerDevice;
     if (!split || tail_wg > kCusPerDevice / (BULK_WAVES / kCoarse2TailWaves)) tail_wg = 0;
     const long bulk_rows = (n_wg - tail_wg) * QPB;
-    ix->bulk_rows_done = 0;
+    *fork = BulkFork{};
     if (bulk_rows > 0) {
-        int rc = launch_coarse2_waves(ix, m_list, BULK_WAVES, 0, bulk_rows, kk, record, st);
+        int rc = launch_coarse2_waves(ix, p, BULK_WAVES, 0, bulk_rows, st);
         if (rc) return rc;
         if (tail_wg > 0 && ix->ev_fork) {  // the caller finalises these rows beside the thin round
-            if (ix->ev_bulk_end) {  // the timed region ends here: the thin round shares the device from now on
-                HIP_TRY(hipEventRecord(ix->ev_bulk_end, st));
-                ix->ev_bulk_end = nullptr;
-            }
+            HIP_TRY(hipEventRecord(ev_bulk_end, st));
+            fork->recorded = true;
             HIP_TRY(hipEventRecord(ix->ev_fork, st));
-            ix->bulk_rows_done = bulk_rows;
+            fork->rows_done = bulk_rows;
         }
     }
     if (tail_wg > 0) {
         const long tail_rows = std::min(tail_wg * QPB, (rows - bulk_rows + QPB_TAIL - 1) / QPB_TAIL * QPB_TAIL);
-        return launch_coarse2_waves(ix, m_list, kCoarse2TailWaves, bulk_rows, tail_rows, kk, record, st);
+        return launch_coarse2_waves(ix, p, kCoarse2TailWaves, bulk_rows, tail_rows, st);
     }
     return SKNNR_OK;
 }
 
 // The second-generation kernel serves the shapes of coarse2_supported() (SKNNR_COARSE_V2=0 selects the first one).
-bool use_coarse2(const sknnr_index* ix, int m_list) {
-    static const bool enabled = [] {
-        const char* e = std::getenv("SKNNR_COARSE_V2");
-        return !(e && std::atoi(e) == 0);
-    }();
+bool use_coarse2(const IndexDesc& ix, int m_list) {
+    static const bool enabled = env_on("SKNNR_COARSE_V2");
     // (small reference sets keep the first kernel: the second one needs its seeding pass -- without a starting
     // threshold the first tiles give every lane more hits per unit than its queue holds)
     // (and the flush addresses the image with 32-bit offsets)
-    const long tiles2 = (long)ix->n_stages2 * tiles_per_stage2(ix->ks);
+    const long tiles2 = (long)ix.n_stages2 * tiles_per_stage2(ix.ks);
     // (... and its flush tags a queued entry's image position, below 2^26, with the query column)
-    return enabled && tiles2 >= 2 * kSeedTiles && tiles2 * tile2_bytes(ix->ks) < (1L << 32) && tiles2 * 32 < (1L << 26) &&
-           coarse2_supported(ix->ks, m_list);
+    return enabled && tiles2 >= 2 * kSeedTiles && tiles2 * tile2_bytes(ix.ks) < (1L << 32) && tiles2 * 32 < (1L << 26) &&
+           coarse2_supported(ix.ks, m_list);
 }
 
 // List length per lane for kk neighbours searched: at least one spare slot keeps the certificate
@@ -1596,7 +1611,7 @@ int coarse_list_len(int kk) { return kk <= 1 ? 2 : (kk <= 5 ? 6 : (kk <= 7 ? 8 :
 // 8, 16 .. 23 lists of 12 and 24 .. 31 lists of 16 (up to 64 features), with thresholds of a rank beyond one list over the two lists of a query kept as one pool
 // (coarse2.hip.h, pair_union_rank, coarse2_rank_extra) -- shorter lists are cheaper to keep, lists of 8 run with 16 waves
 // per CU and no spills where lists of 16 need 12 waves, and lists of 32 exist on the first-generation kernel only.
-int coarse_list_len(const sknnr_index* ix, int kk) {
+int coarse_list_len(const IndexDesc& ix, int kk) {
     static const int enabled = [] {
         const char* e = std::getenv("SKNNR_V2_BIG_K");  // 0: off, 1: lists of 16 only, 2: and lists of 8, 3: and 6 .. 7 on lists of 6, default: all
         return e ? std::atoi(e) : 4;
@@ -1609,11 +1624,42 @@ int coarse_list_len(const sknnr_index* ix, int kk) {
     if (enabled >= 1 && kk > 15 && kk <= kCoarse2MaxKK16 && use_coarse2(ix, 16)) return 16;
     return coarse_list_len(kk);
 }
-int coarse_rank_extra(int m_list, int kk) { return coarse2_rank_extra(m_list, kk); }
 
-hipError_t launch_finalize(const FinalizeArgs& f, long n, hipStream_t st) { return launch::finalize(f, n, st); }
+// The plan of a call of nq rows (rows_given: the caller's, else reference rows) with these opts; raw: shard candidates.
+// A pure function of its arguments and of the process-static switches.
+SearchPlan plan_search(const IndexDesc& ix, const sknnr_query_opts* o, long nq, bool rows_given, int raw) {
+    static const bool scan_everything = std::getenv("SKNNR_EXACT_ONLY") != nullptr;  // development: time the float64 scan alone
+    SearchPlan p{};
+    p.kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
+    p.affine = o->apply_affine != 0 && rows_given;
+    p.self_rows = !rows_given;
+    p.x_dtype = p.self_rows ? kDtypeF64 : o->query_dtype;
+    p.to_xt = p.affine || p.x_dtype != kDtypeF64;
+    p.d_x = p.affine ? ix.d_in : ix.d;
+    p.check_finite = o->check_finite != 0 && rows_given;
+    p.coarse = ix.ks > 0 && p.kk <= kCoarseMaxKK && o->formula != SKNNR_FORMULA_HAMMING && !scan_everything;
+    p.m_list = coarse_list_len(ix, p.kk);
+    p.v2 = p.coarse && use_coarse2(ix, p.m_list);
+    p.rank_extra = coarse2_rank_extra(p.m_list, p.kk);
+    p.record = p.coarse && use_record(ix.ks, p.m_list, p.kk, p.v2, raw);
+    // Rows the finalisers list are first swept again under their rescue thresholds (rescue.hip.h), behind the
+    // second-generation pre-filter (its hi image and query image are what the sweep reads) and up to kRescueMaxKK neighbours
+    // searched (the finish has 16 lanes per row); the exact scan then sees the second list only.
+    p.rescue = p.v2 && ix.rescue_enabled && !raw && p.kk <= kRescueMaxKK;
+    p.bucketed = p.v2 && ix.cell_depth > 0;
+    // Weighted Hamming on 16-bit ids: integer pre-filter, float64 re-score of the candidates (hamming.hip.h)
+    p.ham_int = !p.coarse && o->formula == SKNNR_FORMULA_HAMMING && ix.h16_ok && p.kk <= kHamMaxKK;
+    p.chunk = chunk_rows(ix.ks, p.m_list);
+    p.cap_pad = pad_rows(std::min(p.chunk, nq));
+    return p;
+}
 
 constexpr int kScanGridWg = 256 * 4;  // workgroups of a scan launch (also what scan_slices splits among the passes)
+// shared bytes of scan_merge_kernel for kk neighbours searched
+size_t scan_merge_bytes(int kk) {
+    const int kkp = (kk + 2) & ~1, stk = (2 * kk + 4 + 1) & ~1;
+    return 4 * ((size_t)12 * kkp + (size_t)4 * stk);
+}
 
 int launch_scan_formula(sknnr_index* ix, const ScanArgs& a0, long max_items, bool chunked, size_t sh, hipStream_t st) {
     const SelectArgs& s = a0.s;
@@ -1641,14 +1687,12 @@ int launch_scan_formula(sknnr_index* ix, const ScanArgs& a0, long max_items, boo
     const long blocks = may_slice ? kScanGridWg : std::max<long>(1, std::min<long>(passes, kScanGridWg));
     const int64_t rec[8] = {s.formula + 1, chunked ? 1 : 0, s.kk, blocks, (int64_t)sh, a0.list ? -1 : max_items, may_slice ? 0 : 1,
                             may_slice ? 1 : 0};
-    std::copy(std::begin(rec), std::end(rec), ix->last_scan);
+    std::copy(std::begin(rec), std::end(rec), ix->last.scan);
     HIP_TRY(launch::exact_scan(s.formula, chunked, a, blocks, sh, st));
     if (!may_slice) return SKNNR_OK;
     // one wave per sliced query (none if the scan was not sliced: the kernel returns at once)
     const long sliced_max = std::min<long>(max_items, (long)kScanGridWg * nq_pass / 2);
-    const int kkp = (s.kk + 2) & ~1, stk = (2 * s.kk + 4 + 1) & ~1;
-    const size_t msh = 4 * ((size_t)12 * kkp + (size_t)4 * stk);
-    HIP_TRY(launch::scan_merge(s.formula, a, (sliced_max + 3) / 4, msh, (int)blocks, 0, st));
+    HIP_TRY(launch::scan_merge(s.formula, a, (sliced_max + 3) / 4, scan_merge_bytes(s.kk), (int)blocks, 0, st));
     // queries whose merged heaps are not unique (exact ties): the sequential scan, never sliced
     ScanArgs b = a0;
     b.list = ix->fail_list2.p;
@@ -1663,7 +1707,7 @@ int launch_scan_formula(sknnr_index* ix, const ScanArgs& a0, long max_items, boo
 int launch_scan(sknnr_index* ix, const SelectArgs& s, const int* list, const int* count, long max_items,
                 hipStream_t st) {
     const size_t sh = scan_block_bytes(s.d, s.kk, s.formula);
-    if (sh > 150 * 1024)
+    if (sh > kLdsLimit)
         return fail(SKNNR_ERR_UNSUPPORTED, "n_neighbors = %d with d = %d does not fit the exact scan kernel", s.k, s.d);
     ScanArgs a{s, ix->refT.p, list, count, nullptr, nullptr, nullptr, nullptr};
     const bool chunked = s.d > kScanColChunk;  // wide rows (tree node ids) are swept in column chunks
@@ -1679,13 +1723,6 @@ int query_cols(const sknnr_index* ix, const sknnr_query_opts* o) {
     if (!o->apply_affine) return ix->d;
     return uses_forest(ix, o) ? ix->f_d_in : ix->d_in;
 }
-
-struct CallCtx {
-    sknnr_index* ix;
-    const sknnr_query_opts* o;
-    int kk;
-    bool coarse;
-};
 
 int validate_call(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, int64_t* out_idx) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
@@ -1731,87 +1768,53 @@ int validate_call(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_
     return SKNNR_OK;
 }
 
-// Device-resident core: nq rows at xdev (raw if affine else transformed), outputs on device.
-// raw / id_offset: shard candidates (sknnr_shard_candidates): squared values ascending by (value, index), indices +
-// id_offset, no post-steps
 int run_forest(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opts* o, double* d_dist, long* d_idx,
                hipStream_t st);
 // every search call zeroes the debug records first
-void zero_records(sknnr_index* ix) {
-    std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);
-    std::fill(std::begin(ix->last_hamming), std::end(ix->last_hamming), 0);
-    std::fill(std::begin(ix->last_finalize), std::end(ix->last_finalize), 0);
-    std::fill(std::begin(ix->last_scan), std::end(ix->last_scan), 0);
-    std::fill(std::begin(ix->last_rescue), std::end(ix->last_rescue), 0);
-    std::fill(std::begin(ix->last_prep), std::end(ix->last_prep), 0);
-    std::fill(std::begin(ix->last_mask), std::end(ix->last_mask), 0);
-    ix->last_hamming_rows = 0;
-}
-int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opts* o, double* d_dist,
-               long* d_idx, hipStream_t st, int raw = 0, long id_offset = 0) {
-    zero_records(ix);
-    if (xdev && uses_forest(ix, o)) return run_forest(ix, xdev, nq, o, d_dist, d_idx, st);
-    const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
-    const bool affine = o->apply_affine != 0 && xdev != nullptr;
-    const bool self_rows = xdev == nullptr;
-    // rows narrower than float64 (opts->query_dtype): the prep kernel widens them and writes the float64 rows everything
-    // after it reads (finaliser, exact scan), as it does for rows that go through the affine map
-    const int x_dtype = self_rows ? kDtypeF64 : o->query_dtype;
-    const bool to_xt = affine || x_dtype != kDtypeF64;
-    static const bool scan_everything = std::getenv("SKNNR_EXACT_ONLY") != nullptr;  // development: time the float64 scan alone
-    const bool coarse = ix->ks > 0 && kk <= kCoarseMaxKK && o->formula != SKNNR_FORMULA_HAMMING && !scan_everything;
-    const int d_x = affine ? ix->d_in : ix->d;
-    if (nq > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 query rows in one call");
-    if (affine && ix->ks == 0)
-        return fail(SKNNR_ERR_UNSUPPORTED, "d = %d > 128 with an affine map is outside the HIP envelope", ix->d);
-    // the previous call may have run on another stream: its last kernel must be done with the workspace
-    if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));
-    const bool check_finite = o->check_finite != 0 && xdev != nullptr;
+void zero_records(sknnr_index* ix) { ix->last = SearchRecords{}; }
 
-    // transformed rows of the WHOLE call: the exact scan at the end reads any row of it
-    const double* xq_call = self_rows ? ix->ref64.p + o->row_offset * ix->d : (const double*)xdev;
-    if (to_xt) {
-        HIP_TRY(ix->xt.ensure((size_t)nq * ix->d));
-        xq_call = ix->xt.p;
-    }
-    const long chunk = chunk_rows(ix->ks, coarse_list_len(ix, kk));
-    const long cap = std::min(chunk, nq);
-    const long cap_pad = (cap + kRowQuantum - 1) / kRowQuantum * kRowQuantum;
-    if (coarse || to_xt) {
+// ---- the stages of run_device, in the order it runs them -----------------------------------------------------------------
+// Workspace of a call: the transformed rows of the WHOLE call (the exact scan at the end reads any row of it), the
+// per-chunk buffers at the largest chunk's padded rows, the lists; the device counters of the call start at zero.
+int ensure_workspace(sknnr_index* ix, const SearchPlan& p, long nq, hipStream_t st) {
+    if (p.to_xt) HIP_TRY(ix->xt.ensure((size_t)nq * ix->d));
+    const long cap_pad = p.cap_pad;  // the per-chunk buffers hold the largest chunk with its padding
+    if (p.coarse || p.to_xt) {
         HIP_TRY(ix->qimg.ensure((size_t)(cap_pad / 32) * 2 * ix->ks * 64));
         HIP_TRY(ix->qnc.ensure(cap_pad));
     }
-    if (coarse && ix->cell_depth > 0) {
+    if (p.coarse && ix->cell_depth > 0) {
         HIP_TRY(ix->qcell.ensure((size_t)cap_pad));
         HIP_TRY(ix->qperm.ensure((size_t)cap_pad));
     }
-    const bool record = coarse && use_record(ix->ks, coarse_list_len(ix, kk), kk, use_coarse2(ix, coarse_list_len(ix, kk)), raw);
-    if (record) {
+    if (p.record) {
         HIP_TRY(ix->rec.ensure((size_t)cap_pad * kRecordLen));
         HIP_TRY(ix->rec_bound.ensure((size_t)cap_pad));
         if (ix->cell_depth > 0) HIP_TRY(ix->qnc_pos.ensure((size_t)cap_pad));
-    } else if (coarse) {
-        HIP_TRY(ix->cand_val.ensure((size_t)cap_pad * 2 * coarse_list_len(ix, kk)));
-        HIP_TRY(ix->cand_idx.ensure((size_t)cap_pad * 2 * coarse_list_len(ix, kk)));
+    } else if (p.coarse) {
+        HIP_TRY(ix->cand_val.ensure((size_t)cap_pad * 2 * p.m_list));
+        HIP_TRY(ix->cand_idx.ensure((size_t)cap_pad * 2 * p.m_list));
     }
-    if (coarse) {
+    if (p.coarse) {
         HIP_TRY(ix->fail_list.ensure(nq));
         HIP_TRY(hipMemsetAsync(ix->fail_count.p, 0, 16, st));
     }
-    // Rows the finalisers list are first swept again under their rescue thresholds (rescue.hip.h), behind the
-    // second-generation pre-filter (its hi image and query image are what the sweep reads) and up to kRescueMaxKK neighbours
-    // searched (the finish has 16 lanes per row); the exact scan then sees the second list only.
-    const bool rescue = coarse && ix->rescue_enabled && !raw && kk <= kRescueMaxKK && use_coarse2(ix, coarse_list_len(ix, kk));
-    if (rescue) {
+    if (p.rescue) {
         HIP_TRY(ix->fail_thr.ensure(nq));
         HIP_TRY(ix->resc_list.ensure(nq));
         HIP_TRY(hipMemsetAsync(ix->resc_state.p, 0, kRescueWords * sizeof(int), st));
-        ix->last_rescue[0] = 1;
-        ix->last_rescue[1] = ix->ks;
+        ix->last.rescue[0] = 1;
+        ix->last.rescue[1] = ix->ks;
     }
+    return SKNNR_OK;
+}
 
+// What the finaliser, the re-score and the exact scan select by, for the nq rows at xq (a whole call; a chunk narrows it
+// to its window).  raw / id_offset: shard candidates.
+SelectArgs make_select_args(const sknnr_index* ix, const sknnr_query_opts* o, int kk, const double* xq, long nq, double* d_dist,
+                            long* d_idx, int raw = 0, long id_offset = 0) {
     SelectArgs call{};
-    call.xq = xq_call;
+    call.xq = xq;
     call.ref = ix->ref64.p;
     call.rn = ix->rn64.p;
     call.nq = nq;
@@ -1820,7 +1823,7 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
     call.k = o->n_neighbors;
     call.kk = kk;
     call.exclude_self = o->exclude_self ? 1 : 0;
-    call.deterministic = o->deterministic ? 1 : 0;
+    call.deterministic = o->deterministic && !raw ? 1 : 0;
     call.formula = o->formula;
     call.pow10_is_divisor = o->decimals < 0;
     call.pow10 = std::pow(10.0, std::abs(o->decimals));
@@ -1829,10 +1832,281 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
     call.hw_sum = ix->hw_sum;
     call.raw = raw;
     call.id_offset = id_offset;
-    if (raw) call.deterministic = 0;
     call.out_dist = d_dist;
     call.out_idx = d_idx;
+    return call;
+}
+// ... narrowed to rows [r0, r0 + n) of those rows: their query rows, outputs and row numbers
+SelectArgs select_window(const SelectArgs& s, long r0, long n) {
+    SelectArgs w = s;
+    w.xq = s.xq + r0 * s.d;
+    w.nq = n;
+    w.row_offset = s.row_offset + r0;
+    w.out_dist = s.out_dist ? s.out_dist + r0 * s.k : nullptr;
+    w.out_idx = s.out_idx + r0 * s.k;
+    return w;
+}
 
+// query preparation of rows [c0, c0 + n) of the call
+int prep_chunk(sknnr_index* ix, const SearchPlan& p, const SelectArgs& call, const void* xdev, long c0, long n, hipStream_t st,
+               bool* cells_done = nullptr) {
+    const void* xin = p.self_rows ? (const void*)(call.xq + c0 * ix->d)
+                                  : (const void*)((const char*)xdev + (size_t)c0 * p.d_x * dtype_bytes(p.x_dtype));
+    return launch_prep(ix, p, xin, n, pad_rows(n), p.to_xt ? ix->xt.p + c0 * ix->d : nullptr, st, cells_done);
+}
+
+// cell of every row of the chunk at xq, rows bucketed by cell: position -> row (bucket.hip.h)
+int bucket_chunk(sknnr_index* ix, const SearchPlan& p, const double* xq, long n, bool cells_done, hipStream_t st) {
+    CellArgs ca{};
+    ca.xq = xq;
+    ca.nq = n;
+    ca.n_pad = pad_rows(n);
+    ca.d = ix->d;
+    ca.depth = ix->cell_depth;
+    ca.axes = ix->cell_axes.p;
+    ca.centre = ix->cell_centre.p;
+    ca.thr = ix->cell_thr.p;
+    ca.cell = ix->qcell.p;
+    ca.hist = ix->cell_hist.p;
+    ca.perm = ix->qperm.p;
+    ca.qnc = ix->qnc.p;
+    ca.qnc_pos = p.record ? ix->qnc_pos.p : nullptr;
+    HIP_TRY(hipMemsetAsync(ix->cell_hist.p, 0, 2 * kCellMax * sizeof(int), st));
+    if (!cells_done) HIP_TRY(launch::cell_assign(ca, st));
+    HIP_TRY(launch::cell_count(ca, st));
+    HIP_TRY(launch::cell_scatter(ca, st));
+    if (!cells_done) ix->last.prep[6] = 2;
+    ix->last.prep_bucketed = true;
+    ix->last.prep_qnc_pos = p.record;
+    return SKNNR_OK;
+}
+
+// the finaliser's arguments for rows [c0, c0 + n) of the call, whose candidates the workspace holds
+FinalizeArgs finalize_args(const sknnr_index* ix, const SearchPlan& p, const SelectArgs& call, long c0, long n) {
+    FinalizeArgs f{};
+    f.s = select_window(call, c0, n);
+    f.cand_val = ix->cand_val.p;
+    f.cand_idx = ix->cand_idx.p;
+    f.perm = p.v2 ? ix->perm2.p : ix->perm.p;
+    f.qnc = ix->qnc.p;
+    f.qperm = p.bucketed ? ix->qperm.p : nullptr;
+    if (p.record) {
+        f.rec = ix->rec.p;
+        f.rec_bound = ix->rec_bound.p;
+        f.qnc_pos = p.bucketed ? ix->qnc_pos.p : ix->qnc.p;
+        f.trunc_count = ix->fail_count.p + 3;
+    }
+    f.m_list = p.m_list;
+    f.rank_extra = p.rank_extra;
+    f.inv_s2 = 1.0 / (ix->s * ix->s);
+    f.s2 = ix->s * ix->s;
+    f.inv_s = 1.0 / ix->s;
+    f.eps_c = (p.v2 ? eps_units2(ix->ks) : eps_units(ix->ks)) * std::ldexp(1.0, -24);
+    f.ymax = ix->ymax;
+    f.noise_a = (ix->d + 4) * std::ldexp(1.0, -53);
+    f.mu2 = call.formula == SKNNR_FORMULA_EXPANDED ? 2.0 * ix->mu_norm : 0.0;
+    f.fail_list = ix->fail_list.p;
+    f.fail_count = ix->fail_count.p;
+    f.fail_thr = p.rescue ? ix->fail_thr.p : nullptr;
+    f.fail_base = (int)c0;
+    return f;
+}
+
+// Finalise rows [r0, r0 + rows) of the chunk f describes (the kernel indexes everything by the row inside its window);
+// bucketed calls: POSITIONS [r0, r0 + rows) of the chunk, the kernel maps them to rows of the chunk
+hipError_t finalize_rows(const FinalizeArgs& f, const SearchPlan& p, long r0, long rows, hipStream_t st) {
+    FinalizeArgs g = f;
+    if (p.bucketed) {
+        g.pos0 = r0;
+        g.s.nq = rows;
+        return launch::finalize(g, rows, st);
+    }
+    g.s = select_window(f.s, r0, rows);
+    if (p.record) {
+        g.rec = f.rec + (size_t)r0 * kRecordLen;
+        g.rec_bound = f.rec_bound + r0;
+        g.qnc_pos = f.qnc_pos + r0;
+    } else {
+        g.cand_val = f.cand_val + (size_t)r0 * 2 * f.m_list;
+        g.cand_idx = f.cand_idx + (size_t)r0 * 2 * f.m_list;
+    }
+    g.qnc = f.qnc + r0;
+    g.fail_base = f.fail_base + (int)r0;
+    return launch::finalize(g, rows, st);
+}
+
+// the rescue sweep of the rows the finaliser of chunk f (rows from c0 of the call) has listed
+RescueArgs rescue_args(const sknnr_index* ix, const FinalizeArgs& f, const SelectArgs& call, long c0) {
+    RescueArgs ra{};
+    ra.f = f;
+    ra.f.s = call;  // finalize_core works on call-relative rows here, as the list names them
+    ra.f.fail_list = ix->resc_list.p;
+    ra.f.fail_count = ix->resc_state.p + kRescueHanded;
+    ra.f.fail_thr = nullptr;
+    ra.f.fail_base = 0;
+    ra.f.rec = nullptr;
+    ra.f.qperm = nullptr;
+    ra.rhi = ix->rhi2.p;
+    ra.n_tiles = ix->n_stages2 * tiles_per_stage2(ix->ks);
+    ra.perm = ix->perm2.p;
+    ra.qimg = ix->qimg.p;
+    ra.qnc = ix->qnc.p;
+    ra.row0 = (int)c0;
+    ra.skip_scale = skip_scale(ix);
+    ra.list = ix->fail_list.p;
+    ra.thr = ix->fail_thr.p;
+    ra.count = ix->fail_count.p;
+    ra.state = ix->resc_state.p;
+    return ra;
+}
+
+// One chunk of the Euclidean path, rows [c0, c0 + n) of the call: prep, bucketing, the timed pre-filter, the finaliser
+// (beside the pre-filter's thin round where there is one), the rescue sweep.
+int coarse_chunk(sknnr_index* ix, const SearchPlan& p, const SelectArgs& call, const void* xdev, long c0, long n,
+                 sknnr_index::CallTiming& ct, hipStream_t st) {
+    bool cells_done = false;
+    int rc = prep_chunk(ix, p, call, xdev, c0, n, st, &cells_done);
+    if (rc) return rc;
+    if (ct.coarse_used == ct.coarse.size()) {
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        ct.coarse.emplace_back(e0, e1);
+    }
+    auto& ev = ct.coarse[ct.coarse_used++];
+    if (p.bucketed && (rc = bucket_chunk(ix, p, call.xq + c0 * ix->d, n, cells_done, st))) return rc;
+    HIP_TRY(hipEventRecord(ev.first, st));
+    if (p.v2 && !ix->st_side && !std::getenv("SKNNR_NO_SIDE_STREAM")) {
+        HIP_TRY(hipStreamCreateWithFlags(&ix->st_side, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&ix->ev_fork, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&ix->ev_join, hipEventDisableTiming));
+    }
+    std::fill(std::begin(ix->last.prefilter), std::end(ix->last.prefilter), 0);  // (this chunk's launches only)
+    ix->last.prefilter[7] = p.bucketed ? ix->cell_depth : 0;
+    {
+        // matrix work issued / algorithmic (rows of the launch cancel): K-steps x tiles swept over d x n_ref
+        const long tiles2 = (long)ix->n_stages2 * tiles_per_stage2(ix->ks);
+        const long tiles = p.v2 ? tiles2 + seed_tiles_for(tiles2, tiles_per_stage2(ix->ks)) : (long)ix->n_stages * tiles_per_stage(ix->ks);
+        ix->stats.mfma_executed_ratio = (double)tiles * 32.0 * (16.0 * ix->ks) / ((double)ix->n_ref * ix->d);
+    }
+    BulkFork fork;
+    rc = p.v2 ? launch_coarse2(ix, p, n, ev.second, &fork, st) : launch_coarse(ix, p, pad_rows(n), st);
+    if (rc) return rc;
+    if (!fork.recorded) HIP_TRY(hipEventRecord(ev.second, st));  // (no fork: the whole pre-filter is timed)
+    const long done = std::min<long>(fork.rows_done, n);
+    ct.coarse_rows += done > 0 ? done : n;
+
+    const FinalizeArgs f = finalize_args(ix, p, call, c0, n);
+    ix->last.finalize[0] = launch::finalize_lanes(f);
+    ix->last.finalize[1] = p.record ? 1 : 0;
+    if (done > 0) {
+        // fork: the rows of the bulk launch are finalised on the side stream while the thin round runs here
+        HIP_TRY(hipStreamWaitEvent(ix->st_side, ix->ev_fork, 0));
+        HIP_TRY(finalize_rows(f, p, 0, done, ix->st_side));
+        HIP_TRY(hipEventRecord(ix->ev_join, ix->st_side));
+        if (n > done) HIP_TRY(finalize_rows(f, p, done, n - done, st));
+        HIP_TRY(hipStreamWaitEvent(st, ix->ev_join, 0));  // join before anything else touches the workspace
+    } else {
+        HIP_TRY(finalize_rows(f, p, 0, n, st));
+    }
+    // the rows listed for this chunk, while its query image is in the workspace: one fixed-size launch that reads the
+    // count on the device
+    if (p.rescue) HIP_TRY(launch::rescue(ix->ks, rescue_args(ix, f, call, c0), st));
+    return SKNNR_OK;
+}
+
+// Weighted Hamming on 16-bit ids: integer pre-filter, float64 re-score of the candidates (hamming.hip.h); the queries
+// it cannot serve (too many candidates, ids outside 16 bits) join the fail list of the exact scan
+int hamming_pass(sknnr_index* ix, const SearchPlan& p, const SelectArgs& call, long nq, hipStream_t st) {
+    const long chunk_q = 1L << 18;  // 768 candidate bytes per query: 200 MB per chunk
+    const long cap_q = std::min(chunk_q, nq);
+    const long cap_pad = (cap_q + 255) / 256 * 256;
+    HIP_TRY(ix->h_qimg.ensure((size_t)ix->h_tp * cap_pad));
+    HIP_TRY(ix->h_bad.ensure((size_t)cap_pad));
+    HIP_TRY(ix->h_cand_cnt.ensure((size_t)cap_q));
+    HIP_TRY(ix->h_cand_id.ensure((size_t)cap_q * kHamCand));
+    HIP_TRY(ix->fail_list.ensure(nq));
+    HIP_TRY(hipMemsetAsync(ix->fail_count.p, 0, 16, st));
+    const int64_t rec[7] = {1, p.kk, ham_compacts(p.kk) ? 1 : 0, ham_seed_rows((int)ix->n_ref, p.kk), (int64_t)ix->d + 2,
+                            ix->h_tp, (nq + chunk_q - 1) / chunk_q};
+    std::copy(std::begin(rec), std::end(rec), ix->last.hamming);
+    for (long c0 = 0; c0 < nq; c0 += chunk_q) {
+        const long n = std::min(chunk_q, nq - c0);
+        ix->last.hamming_rows = n;
+        const long n_pad = (n + 255) / 256 * 256;
+        HIP_TRY(launch::hamming_pack(call.xq + c0 * ix->d, n, n_pad, ix->d, ix->h_tp, ix->h_qimg.p, ix->h_bad.p, st));
+        HammingArgs ha{};
+        ha.rimg = ix->h_rimg.p;
+        ha.wq = ix->h_wq.p;
+        ha.qimg = ix->h_qimg.p;
+        ha.q_bad = ix->h_bad.p;
+        ha.n_ref = (int)ix->n_ref;
+        ha.n_ref_pad = ix->h_ref_pad;
+        ha.tp = ix->h_tp;
+        ha.nq = n;
+        ha.nq_pad = n_pad;
+        ha.kk = p.kk;
+        ha.band = (unsigned)ix->d + 2u;
+        ha.cand_cnt = ix->h_cand_cnt.p;
+        ha.cand_id = ix->h_cand_id.p;
+        HIP_TRY(launch::hamming_coarse(ha, st));
+        HammingRescoreArgs hr{};
+        hr.s = select_window(call, c0, n);
+        hr.cand_cnt = ix->h_cand_cnt.p;
+        hr.cand_id = ix->h_cand_id.p;
+        hr.fail_list = ix->fail_list.p;
+        hr.fail_count = ix->fail_count.p;
+        hr.fail_base = (int)c0;
+        hr.rrow = ix->h_rrow.p;
+        hr.tpr = ham_row_dwords(ix->d);
+        HIP_TRY(launch::hamming_rescore(hr, st));
+    }
+    return SKNNR_OK;
+}
+
+// One exact scan per call: the rows the finaliser could not certify (call-relative ids), or every row when the call is
+// outside the MFMA envelope.  Then the running totals, and the events that close the call.
+int scan_tail(sknnr_index* ix, const SearchPlan& p, const SelectArgs& call, long nq, sknnr_index::CallTiming& ct, hipStream_t st) {
+    int rc = p.rescue ? launch_scan(ix, call, ix->resc_list.p, ix->resc_state.p + kRescueHanded, nq, st)
+             : (p.coarse || p.ham_int) ? launch_scan(ix, call, ix->fail_list.p, ix->fail_count.p, nq, st)
+                                       : launch_scan(ix, call, nullptr, nullptr, nq, st);
+    if (rc) return rc;
+    if (p.coarse) {
+        // keep a running total on the device; sknnr_get_stats reads it (no sync here)
+        if (p.rescue) HIP_TRY(launch::rescue_account(ix->fail_count.p, ix->resc_state.p, ix->fail_total.p, st));
+        else HIP_TRY(launch::add_counter(ix->fail_count.p, ix->fail_total.p, st));
+        ix->stats.coarse_queries += nq;
+    } else {
+        // (weighted Hamming: the rows the integer pre-filter could not serve -- list overflow, ids beyond 16 bits -- count as
+        //  fallbacks too)
+        if (p.ham_int) HIP_TRY(launch::add_counter(ix->fail_count.p, ix->fail_total.p, st));
+        ix->stats.exact_only_queries += nq;
+    }
+    HIP_TRY(hipEventRecord(ct.e1, st));
+    ct.pending = true;
+    HIP_TRY(hipEventRecord(ix->ev_ws, st));
+    ix->ws_busy = true;
+    ix->stats.queries += nq;
+    return SKNNR_OK;
+}
+
+// Device-resident core: nq rows at xdev (raw if affine else transformed), outputs on device.
+// raw / id_offset: shard candidates (sknnr_shard_candidates): squared values ascending by (value, index), indices +
+// id_offset, no post-steps
+int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opts* o, double* d_dist,
+               long* d_idx, hipStream_t st, int raw = 0, long id_offset = 0) {
+    zero_records(ix);
+    if (xdev && uses_forest(ix, o)) return run_forest(ix, xdev, nq, o, d_dist, d_idx, st);
+    const SearchPlan p = plan_search(describe(ix), o, nq, xdev != nullptr, raw);
+    if (nq > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 query rows in one call");
+    if (p.affine && ix->ks == 0)
+        return fail(SKNNR_ERR_UNSUPPORTED, "d = %d > 128 with an affine map is outside the HIP envelope", ix->d);
+    // the previous call may have run on another stream: its last kernel must be done with the workspace
+    if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));
+    int rc = ensure_workspace(ix, p, nq, st);
+    if (rc) return rc;
+    const double* xq_call = p.to_xt ? ix->xt.p : (p.self_rows ? ix->ref64.p + o->row_offset * ix->d : (const double*)xdev);
+    const SelectArgs call = make_select_args(ix, o, p.kk, xq_call, nq, d_dist, d_idx, raw, id_offset);
     // timing record of this call (a ring: an old record still pending is folded into the totals first)
     sknnr_index::CallTiming& ct = ix->timing[ix->timing_next];
     ix->timing_next = (ix->timing_next + 1) % sknnr_index::kTimingRing;
@@ -1844,253 +2118,18 @@ int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
     ct.coarse_used = 0;
     ct.coarse_rows = 0;
     HIP_TRY(hipEventRecord(ct.e0, st));
-    if (check_finite && !(coarse || to_xt)) {
+    if (p.check_finite && !(p.coarse || p.to_xt)) {
         // no prep kernel reads the rows on this path: scan them here
-        const long n_el = nq * (long)d_x;
+        const long n_el = nq * (long)p.d_x;
         HIP_TRY(launch::check_finite((const double*)xdev, n_el, ix->status.p, st));
     }
-    for (long c0 = 0; c0 < nq; c0 += chunk) {
-        const long n = std::min(chunk, nq - c0);
-        const long n_pad = (n + kRowQuantum - 1) / kRowQuantum * kRowQuantum;
-        const void* xin = self_rows ? (const void*)(xq_call + c0 * ix->d)
-                                    : (const void*)((const char*)xdev + (size_t)c0 * d_x * dtype_bytes(x_dtype));
-        const bool bucketed = coarse && ix->cell_depth > 0 && use_coarse2(ix, coarse_list_len(ix, kk));
-        bool cells_done = false;
-        if (coarse || to_xt) {
-            int rc = launch_prep(ix, xin, n, n_pad, affine, to_xt ? ix->xt.p + c0 * ix->d : nullptr, st, check_finite, bucketed, &cells_done,
-                                 x_dtype);
-            if (rc) return rc;
-        }
-        if (!coarse) continue;
-
-        if (ct.coarse_used == ct.coarse.size()) {
-            hipEvent_t e0, e1;
-            HIP_TRY(hipEventCreate(&e0));
-            HIP_TRY(hipEventCreate(&e1));
-            ct.coarse.emplace_back(e0, e1);
-        }
-        auto& ev = ct.coarse[ct.coarse_used++];
-        const bool v2 = use_coarse2(ix, coarse_list_len(ix, kk));
-        if (bucketed) {
-            // cell of every row, rows bucketed by cell: position -> row (bucket.hip.h)
-            CellArgs ca{};
-            ca.xq = xq_call + c0 * ix->d;
-            ca.nq = n;
-            ca.n_pad = n_pad;
-            ca.d = ix->d;
-            ca.depth = ix->cell_depth;
-            ca.axes = ix->cell_axes.p;
-            ca.centre = ix->cell_centre.p;
-            ca.thr = ix->cell_thr.p;
-            ca.cell = ix->qcell.p;
-            ca.hist = ix->cell_hist.p;
-            ca.perm = ix->qperm.p;
-            ca.qnc = ix->qnc.p;
-            ca.qnc_pos = record ? ix->qnc_pos.p : nullptr;
-            HIP_TRY(hipMemsetAsync(ix->cell_hist.p, 0, 2 * kCellMax * sizeof(int), st));
-            if (!cells_done) HIP_TRY(launch::cell_assign(ca, st));
-            HIP_TRY(launch::cell_count(ca, st));
-            HIP_TRY(launch::cell_scatter(ca, st));
-            if (!cells_done) ix->last_prep[6] = 2;
-            ix->last_prep_bucketed = true;
-            ix->last_prep_qnc_pos = record;
-        }
-        HIP_TRY(hipEventRecord(ev.first, st));
-        if (v2 && !ix->st_side && !std::getenv("SKNNR_NO_SIDE_STREAM")) {
-            HIP_TRY(hipStreamCreateWithFlags(&ix->st_side, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&ix->ev_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&ix->ev_join, hipEventDisableTiming));
-        }
-        ix->bulk_rows_done = 0;
-        ix->ev_bulk_end = ev.second;
-        std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);  // (this chunk's launches only)
-        ix->last_prefilter[7] = bucketed ? ix->cell_depth : 0;
-        {
-            // matrix work issued / algorithmic (rows of the launch cancel): K-steps x tiles swept over d x n_ref
-            const long tiles = v2 ? (long)ix->n_stages2 * tiles_per_stage2(ix->ks) +
-                                        seed_tiles_for((long)ix->n_stages2 * tiles_per_stage2(ix->ks), tiles_per_stage2(ix->ks))
-                                  : (long)ix->n_stages * tiles_per_stage(ix->ks);
-            ix->stats.mfma_executed_ratio = (double)tiles * 32.0 * (16.0 * ix->ks) / ((double)ix->n_ref * ix->d);
-        }
-        int rc = v2 ? launch_coarse2(ix, n, coarse_list_len(ix, kk), kk, record, st)
-                    : launch_coarse(ix, n_pad, coarse_list_len(ix, kk), kk, st);
+    for (long c0 = 0; c0 < nq; c0 += p.chunk) {
+        const long n = std::min(p.chunk, nq - c0);
+        rc = p.coarse ? coarse_chunk(ix, p, call, xdev, c0, n, ct, st) : (p.to_xt ? prep_chunk(ix, p, call, xdev, c0, n, st) : SKNNR_OK);
         if (rc) return rc;
-        if (ix->ev_bulk_end) HIP_TRY(hipEventRecord(ev.second, st));  // (no fork: the whole pre-filter is timed)
-        ix->ev_bulk_end = nullptr;
-        ct.coarse_rows += ix->bulk_rows_done > 0 ? std::min<long>(ix->bulk_rows_done, n) : n;
-
-        FinalizeArgs f{};
-        f.s = call;  // this chunk's window of the call
-        f.s.xq = xq_call + c0 * ix->d;
-        f.s.nq = n;
-        f.s.row_offset = o->row_offset + c0;
-        f.s.out_dist = d_dist ? d_dist + c0 * o->n_neighbors : nullptr;
-        f.s.out_idx = d_idx + c0 * o->n_neighbors;
-        f.cand_val = ix->cand_val.p;
-        f.cand_idx = ix->cand_idx.p;
-        f.perm = v2 ? ix->perm2.p : ix->perm.p;
-        f.qnc = ix->qnc.p;
-        f.qperm = bucketed ? ix->qperm.p : nullptr;
-        if (record) {
-            f.rec = ix->rec.p;
-            f.rec_bound = ix->rec_bound.p;
-            f.qnc_pos = bucketed ? ix->qnc_pos.p : ix->qnc.p;
-            f.trunc_count = ix->fail_count.p + 3;
-        }
-        f.m_list = coarse_list_len(ix, kk);
-        f.rank_extra = coarse_rank_extra(f.m_list, kk);
-        f.inv_s2 = 1.0 / (ix->s * ix->s);
-        f.s2 = ix->s * ix->s;
-        f.inv_s = 1.0 / ix->s;
-        f.eps_c = (v2 ? eps_units2(ix->ks) : eps_units(ix->ks)) * std::ldexp(1.0, -24);
-        f.ymax = ix->ymax;
-        f.noise_a = (ix->d + 4) * std::ldexp(1.0, -53);
-        f.mu2 = o->formula == SKNNR_FORMULA_EXPANDED ? 2.0 * ix->mu_norm : 0.0;
-        f.fail_list = ix->fail_list.p;
-        f.fail_count = ix->fail_count.p;
-        f.fail_thr = rescue ? ix->fail_thr.p : nullptr;
-        f.fail_base = (int)c0;
-        // rows [r0, r0 + rows) of the chunk (the kernel indexes everything by the row inside its window); bucketed
-        // calls: POSITIONS [r0, r0 + rows) of the chunk, the kernel maps them to rows of the chunk
-        auto finalize_rows = [&](long r0, long rows, hipStream_t s_) -> hipError_t {
-            FinalizeArgs g = f;
-            if (bucketed) {
-                g.pos0 = r0;
-                g.s.nq = rows;
-                return launch_finalize(g, rows, s_);
-            }
-            g.s.xq = f.s.xq + r0 * ix->d;
-            g.s.nq = rows;
-            g.s.row_offset = f.s.row_offset + r0;
-            g.s.out_dist = f.s.out_dist ? f.s.out_dist + r0 * o->n_neighbors : nullptr;
-            g.s.out_idx = f.s.out_idx + r0 * o->n_neighbors;
-            if (record) {
-                g.rec = f.rec + (size_t)r0 * kRecordLen;
-                g.rec_bound = f.rec_bound + r0;
-                g.qnc_pos = f.qnc_pos + r0;
-            } else {
-                g.cand_val = f.cand_val + (size_t)r0 * 2 * f.m_list;
-                g.cand_idx = f.cand_idx + (size_t)r0 * 2 * f.m_list;
-            }
-            g.qnc = f.qnc + r0;
-            g.fail_base = f.fail_base + (int)r0;
-            return launch_finalize(g, rows, s_);
-        };
-        ix->last_finalize[0] = launch::finalize_lanes(f);
-        ix->last_finalize[1] = record ? 1 : 0;
-        const long done = v2 ? std::min<long>(ix->bulk_rows_done, n) : 0;
-        if (done > 0) {
-            // fork: the rows of the bulk launch are finalised on the side stream while the thin round runs here
-            HIP_TRY(hipStreamWaitEvent(ix->st_side, ix->ev_fork, 0));
-            HIP_TRY(finalize_rows(0, done, ix->st_side));
-            HIP_TRY(hipEventRecord(ix->ev_join, ix->st_side));
-            if (n > done) HIP_TRY(finalize_rows(done, n - done, st));
-            HIP_TRY(hipStreamWaitEvent(st, ix->ev_join, 0));  // join before anything else touches the workspace
-        } else {
-            HIP_TRY(finalize_rows(0, n, st));
-        }
-        if (rescue) {
-            // the rows listed for this chunk, while its query image is in the workspace: one fixed-size launch that reads the
-            // count on the device
-            RescueArgs ra{};
-            ra.f = f;
-            ra.f.s = call;  // finalize_core works on call-relative rows here, as the list names them
-            ra.f.fail_list = ix->resc_list.p;
-            ra.f.fail_count = ix->resc_state.p + kRescueHanded;
-            ra.f.fail_thr = nullptr;
-            ra.f.fail_base = 0;
-            ra.f.rec = nullptr;
-            ra.f.qperm = nullptr;
-            ra.rhi = ix->rhi2.p;
-            ra.n_tiles = ix->n_stages2 * tiles_per_stage2(ix->ks);
-            ra.perm = ix->perm2.p;
-            ra.qimg = ix->qimg.p;
-            ra.qnc = ix->qnc.p;
-            ra.row0 = (int)c0;
-            ra.skip_scale = (float)(std::ldexp(1.0, -9) * ix->ymax * 1.02);  // (launch_coarse2_waves)
-            ra.list = ix->fail_list.p;
-            ra.thr = ix->fail_thr.p;
-            ra.count = ix->fail_count.p;
-            ra.state = ix->resc_state.p;
-            HIP_TRY(launch::rescue(ix->ks, ra, st));
-        }
     }
-    // Weighted Hamming on 16-bit ids: integer pre-filter, float64 re-score of the candidates (hamming.hip.h); the queries
-    // it cannot serve (too many candidates, ids outside 16 bits) join the fail list of the exact scan below
-    const bool ham_int = !coarse && o->formula == SKNNR_FORMULA_HAMMING && ix->h16_ok && kk <= kHamMaxKK;
-    if (ham_int) {
-        const long chunk_q = 1L << 18;  // 768 candidate bytes per query: 200 MB per chunk
-        const long cap_q = std::min(chunk_q, nq);
-        const long cap_pad = (cap_q + 255) / 256 * 256;
-        HIP_TRY(ix->h_qimg.ensure((size_t)ix->h_tp * cap_pad));
-        HIP_TRY(ix->h_bad.ensure((size_t)cap_pad));
-        HIP_TRY(ix->h_cand_cnt.ensure((size_t)cap_q));
-        HIP_TRY(ix->h_cand_id.ensure((size_t)cap_q * kHamCand));
-        HIP_TRY(ix->fail_list.ensure(nq));
-        HIP_TRY(hipMemsetAsync(ix->fail_count.p, 0, 16, st));
-        const int64_t rec[7] = {1, kk, ham_compacts(kk) ? 1 : 0, ham_seed_rows((int)ix->n_ref, kk), (int64_t)ix->d + 2,
-                                ix->h_tp, (nq + chunk_q - 1) / chunk_q};
-        std::copy(std::begin(rec), std::end(rec), ix->last_hamming);
-        for (long c0 = 0; c0 < nq; c0 += chunk_q) {
-            const long n = std::min(chunk_q, nq - c0);
-            ix->last_hamming_rows = n;
-            const long n_pad = (n + 255) / 256 * 256;
-            HIP_TRY(launch::hamming_pack(xq_call + c0 * ix->d, n, n_pad, ix->d, ix->h_tp, ix->h_qimg.p, ix->h_bad.p, st));
-            HammingArgs ha{};
-            ha.rimg = ix->h_rimg.p;
-            ha.wq = ix->h_wq.p;
-            ha.qimg = ix->h_qimg.p;
-            ha.q_bad = ix->h_bad.p;
-            ha.n_ref = (int)ix->n_ref;
-            ha.n_ref_pad = ix->h_ref_pad;
-            ha.tp = ix->h_tp;
-            ha.nq = n;
-            ha.nq_pad = n_pad;
-            ha.kk = kk;
-            ha.band = (unsigned)ix->d + 2u;
-            ha.cand_cnt = ix->h_cand_cnt.p;
-            ha.cand_id = ix->h_cand_id.p;
-            HIP_TRY(launch::hamming_coarse(ha, st));
-            HammingRescoreArgs hr{};
-            hr.s = call;
-            hr.s.xq = xq_call + c0 * ix->d;
-            hr.s.nq = n;
-            hr.s.row_offset = o->row_offset + c0;
-            hr.s.out_dist = d_dist ? d_dist + c0 * o->n_neighbors : nullptr;
-            hr.s.out_idx = d_idx + c0 * o->n_neighbors;
-            hr.cand_cnt = ix->h_cand_cnt.p;
-            hr.cand_id = ix->h_cand_id.p;
-            hr.fail_list = ix->fail_list.p;
-            hr.fail_count = ix->fail_count.p;
-            hr.fail_base = (int)c0;
-            hr.rrow = ix->h_rrow.p;
-            hr.tpr = ham_row_dwords(ix->d);
-            HIP_TRY(launch::hamming_rescore(hr, st));
-        }
-    }
-    // One exact scan per call: the rows the finaliser could not certify (call-relative ids), or
-    // every row when the call is outside the MFMA envelope.
-    int rc = rescue ? launch_scan(ix, call, ix->resc_list.p, ix->resc_state.p + kRescueHanded, nq, st)
-             : (coarse || ham_int) ? launch_scan(ix, call, ix->fail_list.p, ix->fail_count.p, nq, st)
-                                   : launch_scan(ix, call, nullptr, nullptr, nq, st);
-    if (rc) return rc;
-    if (coarse) {
-        // keep a running total on the device; sknnr_get_stats reads it (no sync here)
-        if (rescue) HIP_TRY(launch::rescue_account(ix->fail_count.p, ix->resc_state.p, ix->fail_total.p, st));
-        else HIP_TRY(launch::add_counter(ix->fail_count.p, ix->fail_total.p, st));
-        ix->stats.coarse_queries += nq;
-    } else {
-        // (weighted Hamming: the rows the integer pre-filter could not serve -- list overflow, ids beyond 16 bits -- count as
-        //  fallbacks too)
-        if (ham_int) HIP_TRY(launch::add_counter(ix->fail_count.p, ix->fail_total.p, st));
-        ix->stats.exact_only_queries += nq;
-    }
-    HIP_TRY(hipEventRecord(ct.e1, st));
-    ct.pending = true;
-    HIP_TRY(hipEventRecord(ix->ev_ws, st));
-    ix->ws_busy = true;
-    ix->stats.queries += nq;
-    return SKNNR_OK;
+    if (p.ham_int && (rc = hamming_pass(ix, p, call, nq, st))) return rc;
+    return scan_tail(ix, p, call, nq, ct, st);
 }
 
 // Rows of one forest-map chunk: the node ids of at most 2^18 rows (the integer Hamming pre-filter's chunk) and 4 GiB.  A
@@ -2253,7 +2292,7 @@ int mask_finish(sknnr_index* ix, MaskBufs& m, const void* x, long n, long nv, co
         ix->ws_busy = true;
     }
     const int64_t rec[8] = {1, n, nv, nv == n ? 1 : (nv == 0 ? 2 : 0), mask_blocks(n), (int64_t)row_bytes, valid_so_far + nv, 0};
-    std::copy(rec, rec + 8, ix->last_mask);
+    std::copy(rec, rec + 8, ix->last.mask);
     return SKNNR_OK;
 }
 
@@ -3208,19 +3247,17 @@ namespace {
 
 int merge_shards_formula(sknnr_index* ix, const SelectArgs& call, int n_shards, long nq, hipStream_t st) {
     ScanArgs a{call, ix->refT.p, nullptr, nullptr, ix->slice_v.p, ix->slice_i.p, ix->fail_list2.p, ix->fail_count.p + 2};
-    const int kkp = (call.kk + 2) & ~1, stk = (2 * call.kk + 4 + 1) & ~1;
-    const size_t msh = 4 * ((size_t)12 * kkp + (size_t)4 * stk);
-    HIP_TRY(launch::scan_merge(call.formula, a, (nq + 3) / 4, msh, 0, n_shards, st));
+    HIP_TRY(launch::scan_merge(call.formula, a, (nq + 3) / 4, scan_merge_bytes(call.kk), 0, n_shards, st));
     // rows whose merged answer is not unique (exact ties that the reference's heap settles by its history): the
     // sequential scan over ALL reference rows of this handle, as for any other tied row
     const size_t sh = scan_block_bytes(call.d, call.kk, call.formula);
-    if (sh > 150 * 1024) return fail(SKNNR_ERR_UNSUPPORTED, "n_neighbors = %d with d = %d does not fit the exact scan kernel", call.k, call.d);
+    if (sh > kLdsLimit) return fail(SKNNR_ERR_UNSUPPORTED, "n_neighbors = %d with d = %d does not fit the exact scan kernel", call.k, call.d);
     ScanArgs b{call, ix->refT.p, ix->fail_list2.p, ix->fail_count.p + 2, nullptr, nullptr, nullptr, nullptr};
     const bool chunked = call.d > kScanColChunk;
     const int nq_pass = scan_nq(call.formula);
     const long blocks = std::max<long>(1, std::min<long>((nq + nq_pass - 1) / nq_pass, kScanGridWg));
     const int64_t rec[8] = {call.formula + 1, chunked ? 1 : 0, call.kk, blocks, (int64_t)sh, nq, n_shards, 1};
-    std::copy(std::begin(rec), std::end(rec), ix->last_scan);
+    std::copy(std::begin(rec), std::end(rec), ix->last.scan);
     HIP_TRY(launch::exact_scan(call.formula, chunked, b, blocks, sh, st));
     return SKNNR_OK;
 }
@@ -3228,10 +3265,12 @@ int merge_shards_formula(sknnr_index* ix, const SelectArgs& call, int n_shards, 
 // Device-resident core of sknnr_merge_shards.
 int merge_shards_device(sknnr_index* ix, const double* xdev, long nq, const sknnr_query_opts* o, int n_shards,
                         const double* shard_val, const long* shard_idx, double* d_dist, long* d_idx, hipStream_t st) {
-    std::fill(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), 0);  // (no pre-filter runs on this path)
-    std::fill(std::begin(ix->last_scan), std::end(ix->last_scan), 0);
-    std::fill(std::begin(ix->last_rescue), std::end(ix->last_rescue), 0);
-    std::fill(std::begin(ix->last_prep), std::end(ix->last_prep), 0);
+    // No pre-filter, rescue or integer Hamming pass runs on this path (and fail_count no longer holds the last one's count);
+    // the finaliser's and the mask's records stay what the call before left.
+    SearchRecords fresh;
+    std::copy(std::begin(ix->last.finalize), std::end(ix->last.finalize), fresh.finalize);
+    std::copy(std::begin(ix->last.mask), std::end(ix->last.mask), fresh.mask);
+    ix->last = fresh;
     const int kk = o->n_neighbors + (o->exclude_self ? 1 : 0);
     const bool affine = o->apply_affine != 0 && xdev != nullptr;
     const bool self_rows = xdev == nullptr;
@@ -3243,43 +3282,25 @@ int merge_shards_device(sknnr_index* ix, const double* xdev, long nq, const sknn
     if (affine) {
         HIP_TRY(ix->xt.ensure((size_t)nq * ix->d));
         const long chunk = chunk_rows(ix->ks, 2);
-        const long cap_pad = (std::min(chunk, nq) + kRowQuantum - 1) / kRowQuantum * kRowQuantum;
+        const long cap_pad = pad_rows(std::min(chunk, nq));
         HIP_TRY(ix->qimg.ensure((size_t)(cap_pad / 32) * 2 * ix->ks * 64));
         HIP_TRY(ix->qnc.ensure(cap_pad));
+        SearchPlan prep{};  // (the map alone: nothing is searched in these rows' image)
+        prep.affine = true;
+        prep.check_finite = o->check_finite != 0;
         for (long c0 = 0; c0 < nq; c0 += chunk) {
             const long n = std::min(chunk, nq - c0);
-            const long n_pad = (n + kRowQuantum - 1) / kRowQuantum * kRowQuantum;
-            int rc = launch_prep(ix, xdev + c0 * ix->d_in, n, n_pad, true, ix->xt.p + c0 * ix->d, st, o->check_finite != 0);
+            int rc = launch_prep(ix, prep, xdev + c0 * ix->d_in, n, pad_rows(n), ix->xt.p + c0 * ix->d, st);
             if (rc) return rc;
         }
         xq_call = ix->xt.p;
     }
-    SelectArgs call{};
-    call.xq = xq_call;
-    call.ref = ix->ref64.p;
-    call.rn = ix->rn64.p;
-    call.nq = nq;
-    call.d = ix->d;
-    call.n_ref = (int)ix->n_ref;
-    call.k = o->n_neighbors;
-    call.kk = kk;
-    call.exclude_self = o->exclude_self ? 1 : 0;
-    call.deterministic = o->deterministic ? 1 : 0;
-    call.formula = o->formula;
-    call.pow10_is_divisor = o->decimals < 0;
-    call.pow10 = std::pow(10.0, std::abs(o->decimals));
-    call.row_offset = o->row_offset;
-    call.hw = ix->hw.p;
-    call.hw_sum = ix->hw_sum;
-    call.out_dist = d_dist;
-    call.out_idx = d_idx;
+    const SelectArgs call = make_select_args(ix, o, kk, xq_call, nq, d_dist, d_idx);
     const size_t heaps = (size_t)nq * n_shards * kk;
     HIP_TRY(ix->slice_v.ensure(heaps));
     HIP_TRY(ix->slice_i.ensure(heaps));
     HIP_TRY(ix->fail_list2.ensure((size_t)nq));
     HIP_TRY(hipMemsetAsync(ix->fail_count.p, 0, 16, st));
-    std::fill(std::begin(ix->last_hamming), std::end(ix->last_hamming), 0);  // (fail_count no longer holds its count)
-    ix->last_hamming_rows = 0;
     HIP_TRY(launch::pack_shards(shard_val, shard_idx, nq, n_shards, kk, ix->slice_v.p, ix->slice_i.p, st));
     int rc = merge_shards_formula(ix, call, n_shards, nq, st);
     if (rc) return rc;
@@ -3373,14 +3394,6 @@ extern "C" int sknnr_index_set_weight_law_params(sknnr_index* ix, int32_t law, d
     ix->law_code = law;
     ix->law_p0 = law != kLawNone ? p0 : 0.0;
     ix->law_p1 = law != kLawNone ? p1 : 0.0;
-    return SKNNR_OK;
-}
-
-extern "C" int sknnr_debug_last_weight_law(const sknnr_index* cix, int64_t out[8]) {
-    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "index / out is NULL");
-    sknnr_index* ix = const_cast<sknnr_index*>(cix);
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    std::copy(std::begin(ix->last_law), std::end(ix->last_law), out);
     return SKNNR_OK;
 }
 
@@ -4069,12 +4082,12 @@ extern "C" int sknnr_debug_coarse_matrix(sknnr_index* ix, const double* q, int64
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
     HIP_TRY(hipDeviceSynchronize());  // default stream below; the workspace may still be in use on another one
-    const long n_pad = (nq + kRowQuantum - 1) / kRowQuantum * kRowQuantum;
+    const long n_pad = pad_rows(nq);
     HIP_TRY(ix->xstage.ensure((size_t)nq * ix->d));
     HIP_TRY(hipMemcpy(ix->xstage.p, q, (size_t)nq * ix->d * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(ix->qimg.ensure((size_t)(n_pad / 32) * 2 * ix->ks * 64));
     HIP_TRY(ix->qnc.ensure(n_pad));
-    int rc = launch_prep(ix, ix->xstage.p, nq, n_pad, false, nullptr, nullptr);
+    int rc = launch_prep(ix, SearchPlan{}, ix->xstage.p, nq, n_pad, nullptr, nullptr);
     if (rc) return rc;
     DevBuf<float> dout;
     HIP_TRY(dout.ensure((size_t)nq * ix->n_ref));
@@ -4089,53 +4102,24 @@ extern "C" int sknnr_debug_coarse_matrix(sknnr_index* ix, const double* q, int64
     return SKNNR_OK;
 }
 
-extern "C" int sknnr_debug_last_prefilter(const sknnr_index* cix, int64_t out[8]) {
-    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
-    sknnr_index* ix = const_cast<sknnr_index*>(cix);
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    std::copy(std::begin(ix->last_prefilter), std::end(ix->last_prefilter), out);
-    return SKNNR_OK;
-}
-
-extern "C" int sknnr_debug_last_mask(const sknnr_index* cix, int64_t out[8]) {
+// the debug records that are host words only: copied under the handle's lock
+template <class Rec>
+static int copy_record(const sknnr_index* cix, int64_t out[8], Rec rec) {
     if (!cix || !out) return fail(SKNNR_ERR_INVALID, "index / out is NULL");
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
-    std::copy(std::begin(ix->last_mask), std::end(ix->last_mask), out);
+    const int64_t* r = rec(ix);
+    std::copy(r, r + 8, out);
     return SKNNR_OK;
 }
-
-extern "C" int sknnr_debug_last_narrow(const sknnr_index* cix, int64_t out[8]) {
-    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "index / out is NULL");
-    sknnr_index* ix = const_cast<sknnr_index*>(cix);
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    std::copy(std::begin(ix->last_narrow), std::end(ix->last_narrow), out);
-    return SKNNR_OK;
-}
-
-extern "C" int sknnr_debug_last_summary(const sknnr_index* cix, int64_t out[8]) {
-    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "bad argument");
-    sknnr_index* ix = const_cast<sknnr_index*>(cix);
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    std::copy(std::begin(ix->last_summary), std::end(ix->last_summary), out);
-    return SKNNR_OK;
-}
-
-extern "C" int sknnr_debug_last_plan(const sknnr_index* cix, int64_t out[8]) {
-    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "index / out is NULL");
-    sknnr_index* ix = const_cast<sknnr_index*>(cix);
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    std::copy(std::begin(ix->last_plan), std::end(ix->last_plan), out);
-    return SKNNR_OK;
-}
-
-extern "C" int sknnr_debug_last_planes(const sknnr_index* cix, int64_t out[8]) {
-    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "index / out is NULL");
-    sknnr_index* ix = const_cast<sknnr_index*>(cix);
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    std::copy(std::begin(ix->last_planes), std::end(ix->last_planes), out);
-    return SKNNR_OK;
-}
+extern "C" int sknnr_debug_last_prefilter(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last.prefilter; }); }
+extern "C" int sknnr_debug_last_mask(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last.mask; }); }
+extern "C" int sknnr_debug_last_prep(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last.prep; }); }
+extern "C" int sknnr_debug_last_narrow(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last_narrow; }); }
+extern "C" int sknnr_debug_last_summary(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last_summary; }); }
+extern "C" int sknnr_debug_last_plan(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last_plan; }); }
+extern "C" int sknnr_debug_last_planes(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last_planes; }); }
+extern "C" int sknnr_debug_last_weight_law(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last_law; }); }
 
 // The mask, the scan and the compaction alone, on the caller's device pointers (run_device_masked's sequence without the
 // search): the block offsets and the ranks, which no search result shows, come back to the host.
@@ -4224,10 +4208,10 @@ extern "C" int sknnr_debug_last_finalize(const sknnr_index* cix, int64_t out[4])
     if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
-    out[0] = ix->last_finalize[0];
-    out[1] = ix->last_finalize[1];
+    out[0] = ix->last.finalize[0];
+    out[1] = ix->last.finalize[1];
     out[2] = out[3] = 0;
-    if (ix->last_finalize[1]) {
+    if (ix->last.finalize[1]) {
         // the rows the truncation rule put on the fail list, over every device chunk of the call (the workspace is the
         // handle's: no later call has touched it, or the record would be zero)
         int n_trunc = 0;
@@ -4243,9 +4227,9 @@ extern "C" int sknnr_debug_last_hamming(const sknnr_index* cix, int64_t out[8]) 
     if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
-    std::copy(std::begin(ix->last_hamming), std::end(ix->last_hamming), out);
+    std::copy(std::begin(ix->last.hamming), std::end(ix->last.hamming), out);
     out[7] = 0;
-    if (ix->last_hamming[0]) {
+    if (ix->last.hamming[0]) {
         // the rows hamming_rescore_kernel put on the fail list, over every device chunk of the call (the workspace is the
         // handle's: no later call has touched it, or the record would be zero)
         int n_fail = 0;
@@ -4261,7 +4245,7 @@ extern "C" int sknnr_debug_last_scan(const sknnr_index* cix, int64_t out[8]) {
     if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
-    const int64_t* r = ix->last_scan;
+    const int64_t* r = ix->last.scan;
     std::copy(r, r + 8, out);
     out[7] = 0;
     if (!r[0]) return SKNNR_OK;
@@ -4273,7 +4257,7 @@ extern "C" int sknnr_debug_last_scan(const sknnr_index* cix, int64_t out[8]) {
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(cnt, ix->fail_count.p, sizeof cnt, hipMemcpyDeviceToHost));
         if (r[5] < 0) out[5] = cnt[0];
-        if (r[5] < 0 && ix->last_rescue[0]) {  // the scan consumed the rescue's second list
+        if (r[5] < 0 && ix->last.rescue[0]) {  // the scan consumed the rescue's second list
             int handed = 0;
             HIP_TRY(hipMemcpy(&handed, ix->resc_state.p + kRescueHanded, sizeof handed, hipMemcpyDeviceToHost));
             out[5] = handed;
@@ -4294,12 +4278,12 @@ extern "C" int sknnr_debug_last_rescue(const sknnr_index* cix, int64_t out[8]) {
     long long total[2] = {0, 0};
     HIP_TRY(hipMemcpy(total, ix->fail_total.p, sizeof total, hipMemcpyDeviceToHost));
     out[7] = total[1];
-    if (!ix->last_rescue[0]) return SKNNR_OK;
+    if (!ix->last.rescue[0]) return SKNNR_OK;
     // (the workspace is the handle's: no later call has touched it, or the record would be zero)
     int w[kRescueWords];
     HIP_TRY(hipMemcpy(w, ix->resc_state.p, sizeof w, hipMemcpyDeviceToHost));
     out[0] = 1;
-    out[1] = ix->last_rescue[1];
+    out[1] = ix->last.rescue[1];
     out[2] = w[kRescueOffered];
     out[3] = w[kRescueNoThr];
     out[4] = w[kRescueOverflow];
@@ -4312,9 +4296,9 @@ extern "C" int sknnr_debug_hamming_candidates(const sknnr_index* cix, int32_t* c
     if (!cix || !cnt || !ids) return fail(SKNNR_ERR_INVALID, "NULL argument");
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
-    if (!ix->last_hamming[0]) return fail(SKNNR_ERR_INVALID, "the last call did not run the integer Hamming pre-filter");
-    if (n < 0 || n > ix->last_hamming_rows)
-        return fail(SKNNR_ERR_INVALID, "n = %ld rows, the last device chunk has %ld", (long)n, ix->last_hamming_rows);
+    if (!ix->last.hamming[0]) return fail(SKNNR_ERR_INVALID, "the last call did not run the integer Hamming pre-filter");
+    if (n < 0 || n > ix->last.hamming_rows)
+        return fail(SKNNR_ERR_INVALID, "n = %ld rows, the last device chunk has %ld", (long)n, ix->last.hamming_rows);
     HIP_TRY(hipSetDevice(ix->device));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(cnt, ix->h_cand_cnt.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -4326,9 +4310,9 @@ extern "C" int sknnr_debug_coarse_candidates(const sknnr_index* cix, int64_t n, 
     if (!cix || !val || !pos || !perm) return fail(SKNNR_ERR_INVALID, "NULL argument");
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
-    const int64_t* r = ix->last_prefilter;
+    const int64_t* r = ix->last.prefilter;
     if (!r[0]) return fail(SKNNR_ERR_UNSUPPORTED, "the last call ran no Euclidean pre-filter");
-    if (ix->last_finalize[1]) return fail(SKNNR_ERR_UNSUPPORTED, "the last call filed merged candidate records, not lists");
+    if (ix->last.finalize[1]) return fail(SKNNR_ERR_UNSUPPORTED, "the last call filed merged candidate records, not lists");
     // (coarse2_kernel files its lists by position of a bucketed call and in positions of its own image: nothing reads them yet)
     if (r[0] != 1) return fail(SKNNR_ERR_UNSUPPORTED, "the last call ran the second-generation pre-filter: its lists are not served");
     // (the workspace is the handle's: no later call has touched it, or the record would be zero)
@@ -4346,34 +4330,47 @@ extern "C" int sknnr_debug_coarse_candidates(const sknnr_index* cix, int64_t n, 
     return SKNNR_OK;
 }
 
-extern "C" int sknnr_debug_last_prep(const sknnr_index* cix, int64_t out[8]) {
-    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
-    sknnr_index* ix = const_cast<sknnr_index*>(cix);
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    std::copy(std::begin(ix->last_prep), std::end(ix->last_prep), out);
-    return SKNNR_OK;
-}
-
 extern "C" int sknnr_debug_query_prep(const sknnr_index* cix, int64_t n, void* qimg, double* qnc, double* xt, uint8_t* cell,
                                       int32_t* perm, double* qnc_pos) {
     if (!cix) return fail(SKNNR_ERR_INVALID, "NULL argument");
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
-    const int64_t* r = ix->last_prep;
+    const int64_t* r = ix->last.prep;
     if (!r[0]) return fail(SKNNR_ERR_INVALID, "the last call ran no query preparation kernel");
     if (n < 0 || n > r[4]) return fail(SKNNR_ERR_INVALID, "n = %ld rows, the last device chunk has %ld with its padding", (long)n, (long)r[4]);
-    if (xt && !ix->last_prep_xt) return fail(SKNNR_ERR_INVALID, "the last call wrote no transformed rows");
-    if ((cell || perm) && !ix->last_prep_bucketed) return fail(SKNNR_ERR_INVALID, "the last call was not bucketed");
-    if (qnc_pos && !ix->last_prep_qnc_pos) return fail(SKNNR_ERR_INVALID, "the last call filed no |q'|^2 by position");
+    if (xt && !ix->last.prep_xt) return fail(SKNNR_ERR_INVALID, "the last call wrote no transformed rows");
+    if ((cell || perm) && !ix->last.prep_bucketed) return fail(SKNNR_ERR_INVALID, "the last call was not bucketed");
+    if (qnc_pos && !ix->last.prep_qnc_pos) return fail(SKNNR_ERR_INVALID, "the last call filed no |q'|^2 by position");
     HIP_TRY(hipSetDevice(ix->device));
     HIP_TRY(hipDeviceSynchronize());
     const size_t rows = (size_t)n;
     if (qimg) HIP_TRY(hipMemcpy(qimg, ix->qimg.p, rows * 64 * ix->ks, hipMemcpyDeviceToHost));
     if (qnc) HIP_TRY(hipMemcpy(qnc, ix->qnc.p, rows * sizeof(double), hipMemcpyDeviceToHost));
-    if (xt) HIP_TRY(hipMemcpy(xt, ix->last_prep_xt, (size_t)std::min<int64_t>(n, r[3]) * ix->d * sizeof(double), hipMemcpyDeviceToHost));
+    if (xt) HIP_TRY(hipMemcpy(xt, ix->last.prep_xt, (size_t)std::min<int64_t>(n, r[3]) * ix->d * sizeof(double), hipMemcpyDeviceToHost));
     if (cell) HIP_TRY(hipMemcpy(cell, ix->qcell.p, rows, hipMemcpyDeviceToHost));
     if (perm) HIP_TRY(hipMemcpy(perm, ix->qperm.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (qnc_pos) HIP_TRY(hipMemcpy(qnc_pos, ix->qnc_pos.p, rows * sizeof(double), hipMemcpyDeviceToHost));
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_search_plan(int64_t n_ref, int32_t d, int32_t cell_depth, int32_t kk, int64_t nq, int32_t formula,
+                                       int32_t flags, int64_t out[16]) {
+    const bool exclude_self = flags & 1;
+    if (!out || n_ref < 1 || d < 1 || kk < (exclude_self ? 2 : 1) || nq < 0 || cell_depth < 0 || cell_depth > kCellMaxDepth ||
+        formula < SKNNR_FORMULA_EXPANDED || formula > SKNNR_FORMULA_HAMMING)
+        return fail(SKNNR_ERR_INVALID, "bad argument");
+    // the description sknnr_index_create would leave for these shapes (no affine map)
+    const int ks = (d + 15) / 16 <= kMaxKs ? (d + 15) / 16 : 0;
+    const IndexDesc ix{n_ref, d, ks, d, image_stages2(n_ref, ks), cell_depth, (flags & 8) != 0, (flags & 4) != 0};
+    sknnr_query_opts o{};
+    o.n_neighbors = kk - (exclude_self ? 1 : 0);
+    o.exclude_self = exclude_self;
+    o.formula = formula;
+    const SearchPlan p = plan_search(ix, &o, nq, true, (flags & 2) ? 1 : 0);
+    const int64_t words[16] = {p.coarse ? (p.v2 ? 2 : 1) : 0, p.coarse ? ks : 0, p.coarse ? p.m_list : 0, p.coarse ? p.rank_extra : 0,
+                               p.bucketed ? cell_depth : 0, p.record, p.rescue, p.ham_int, p.kk, p.chunk, p.cap_pad, p.to_xt,
+                               p.d_x, p.check_finite, p.x_dtype, (p.affine ? 1 : 0) | (p.self_rows ? 2 : 0)};
+    std::copy(std::begin(words), std::end(words), out);
     return SKNNR_OK;
 }
 

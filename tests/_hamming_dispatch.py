@@ -9,7 +9,7 @@ fails there.  Sources, all in sknnr_amd/csrc:
   (``hamming_pack_kernel``), at most 4,096 trees and ``hamming_rescore_lds`` <= 150 KiB (hamming.hip.h)
 - ``quantise``: the 16-bit weights of ``sknnr_index_set_hamming_weights``.  numpy's float64 arithmetic is the host's:
   the host unit is built with -ffp-contract=off and no fast-math (sknnr_amd/_build.py)
-- ``ham_int``, the 2^18-row device chunks and ``band = T + 2``: the ``ham_int`` block of ``run_device`` (sknnr_hip.hip)
+- ``ham_int``: ``plan_search``; the 2^18-row device chunks and ``band = T + 2``: ``hamming_pass`` (sknnr_hip.hip)
 - ``compacts``, ``seed_rows``, ``kHamCand``, ``kHamMaxKK``, the 256-row steps and ``candidates``:
   ``ham_compacts``, ``ham_seed_rows`` and ``hamming_coarse_kernel`` (hamming.hip.h)
 - ``handed_to_scan``: ``hamming_rescore_kernel`` sends a row with fewer than kk candidates (or -1) to the exact scan

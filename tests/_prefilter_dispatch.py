@@ -4,11 +4,14 @@ tests/test_prefilter_instances_gpu.py asserts that ``Index.debug_last_prefilter(
 ``expected_launch`` predicts.  When dispatch changes in the library, these restatements stop matching and the
 instance tests fail loudly instead of quietly testing another kernel.  Sources, all in sknnr_amd/csrc:
 
-- ``coarse_list_len`` (both overloads), ``use_coarse2``, ``launch_coarse2``, ``chunk_rows``: sknnr_hip.hip
+- ``coarse_list_len`` (both overloads), ``use_coarse2``, ``launch_coarse2``, ``chunk_rows``, and ``plan_search``, which
+  applies them once per call: sknnr_hip.hip (tests/test_search_plan_cpu.py holds this file against ``plan_search`` itself,
+  through ``sknnr_debug_search_plan``, without a GPU)
 - ``coarse2_supported``, ``coarse2_waves``, ``coarse2_rank_extra``, ``tiles_per_stage2``, ``tile2_bytes``,
   ``kSeedTiles``, ``kCoarse2Nqb``, ``kCoarse2MaxKK*``: coarse2.hip.h
 - ``coarse_waves`` (first generation), ``kRowQuantum``: coarse.hip.h
-- the cell depth of an index: ``sknnr_index_create`` (sknnr_hip.hip), ``kCellMaxDepth``: bucket.hip.h
+- the cell depth of an index: ``sknnr_index_create`` (sknnr_hip.hip), ``kCellMaxDepth``: bucket.hip.h; ``n_tiles2``:
+  ``image_stages2`` (sknnr_hip.hip) times ``tiles_per_stage2``
 
 Only the default build and default process environment are restated: the process-static knobs
 (``SKNNR_COARSE_V2``, ``SKNNR_V2_BIG_K``, ``SKNNR_COARSE_TAIL``, ``SKNNR_CHUNK_ROWS``) are assumed unset.

@@ -4,7 +4,7 @@ tests/test_query_prep_gpu.py compares every buffer these launches fill with the 
 launch record ``Index.debug_last_prep()`` with ``expected_prep``; tests/test_query_prep_cpu.py checks this module itself
 against exact rational arithmetic.  Sources, all in sknnr_amd/csrc:
 
-- dispatch: ``launch_prep`` and the bucketing block of ``run_device`` (sknnr_hip.hip)
+- dispatch: ``launch_prep`` and ``bucket_chunk`` (sknnr_hip.hip)
 - transformed rows, image, query norm: ``prep_queries_direct_kernel``, ``prep_queries_kernel`` (exact.hip.h); the rows are
   ``oracle.affine`` of the input widened exactly to float64 (one k-ordered fma chain per output; without ``proj``: subtract,
   then divide)

@@ -51,8 +51,7 @@ def test_constants_match_the_sources():
     assert _const(host, "kScanGridWg") == S.GRID_WG
     assert _const(host, "kScanMaxKK") == S.MAX_KK
     # the bound: once in launch_scan, once in the shard merge's replay, both 150 KiB on scan_block_bytes
-    bounds = re.findall(r"if \(sh > (\d+) \* (\d+)\)", host)
-    assert len(bounds) == 2 and all(int(a) * int(b) == S.LDS_LIMIT for a, b in bounds)
+    assert len(re.findall(r"if \(sh > kLdsLimit\)", host)) == 2 and _const(host, "kLdsLimit") == S.LDS_LIMIT
     assert host.count(S.REFUSAL) == 2
     qpw = re.search(r"constexpr int scan_qpw\(int formula\) \{ return formula == 0 \? (\d+) : (\d+); \}", exact)
     assert [int(qpw.group(1)), int(qpw.group(2)), int(qpw.group(2))] == [S.scan_qpw(f) for f in G.FORMULAS]
