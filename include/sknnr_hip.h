@@ -453,6 +453,46 @@ int sknnr_debug_weight_law(int32_t law, double p0, double p1, const double* dist
 int sknnr_hamming_distances(sknnr_index* index, const double* q, int64_t nq, const int64_t* rows, int64_t n_rows,
                             double* out, int32_t mem, void* stream);
 
+/* ---- leave-group-out neighbours ---------------------------------------------------------------- */
+
+/*
+ * Independent predictions that skip groups.  The reference's independent_prediction_ (REF _base.py:37-40) leaves out
+ * each fitted row itself; that is independent only when every row is its own sampling unit.  Re-measured plots,
+ * clusters of subplots and spatial blocks need every fitted row answered from the rows of OTHER groups.  The reference
+ * has no such call; the contract, stated here once (sknnr_amd/csrc/groups.hip.h; tests/_groups.py restates it in numpy):
+ *
+ *   codes is an int32 label per reference row, k = opts->n_neighbors.  For reference row i the candidates are the rows
+ *   r with codes[r] != codes[i]; row i itself is therefore never a candidate.  Each pair has a value: the float64
+ *   number sknnr_kneighbors ranks the pair (row i, row r) by under opts->formula -- EXPANDED: |x|^2 - 2 x.r + |r|^2
+ *   clamped at 0; DIRECT: sum (x - r)^2; HAMMING: the weighted Hamming distance.  The answer of row i:
+ *     1. the k candidates smallest by (value, r), ascending in that order
+ *     2. distances: sqrt(value) for the two Euclidean formulas, the value itself for HAMMING
+ *     3. with opts->deterministic, sknnr's reorder (REF _base.py:166-175), row number i, scale over the k kept distances
+ *   under all three formulas alike.  There is NO replay of scikit-learn's heap history: exact ties at the k-th value go
+ *   to the lower index.  With every row in a group of its own the result equals sknnr_kneighbors with q = NULL bit for
+ *   bit on every row whose k-th and (k+1)-th smallest values among the other rows differ.
+ *
+ * sknnr_index_set_groups: codes HOST, n == n_ref, every code >= 0 (else SKNNR_ERR_INVALID); NULL clears.  Copied to the
+ *   device and kept on the handle, like the Hamming weights.
+ * sknnr_kneighbors_grouped: rows [opts->row_offset, opts->row_offset + nq) of the reference set, by the contract above.
+ *   Reads n_neighbors, deterministic, decimals, formula and row_offset; exclude_self must be 1 (the rows are reference
+ *   rows), apply_affine and query_dtype 0.  out_dist / out_idx / mem / stream as for sknnr_kneighbors; out_dist may be
+ *   NULL.  One float64 scan (group_scan_kernel), counted in sknnr_stats.queries and exact_only_queries.  Refused before
+ *   any launch: no groups set or a window outside [0, n_ref] (SKNNR_ERR_INVALID); n_neighbors > n_ref - largest group
+ *   (SKNNR_ERR_K_TOO_LARGE: some row would have fewer candidates than neighbours); n_neighbors > 192
+ *   (SKNNR_ERR_UNSUPPORTED).  Rows of any width are served (beyond 1024 columns in column chunks, like the exact scan).
+ */
+int sknnr_index_set_groups(sknnr_index* index, const int32_t* codes, int64_t n);
+int sknnr_kneighbors_grouped(sknnr_index* index, int64_t nq, const sknnr_query_opts* opts, double* out_dist,
+                             int64_t* out_idx, int32_t mem, void* stream);
+
+/*
+ * Debug only.  The leave-group-out scan of the last search call (zeroed by every search call).  Host memory, no device work:
+ *   out[0] 0 = no grouped scan ran, else formula + 1      out[1] k      out[2] workgroups      out[3] dynamic LDS bytes
+ *   out[4] rows      out[5] slices (1 = none)      out[6] rows of the largest group      out[7] number of groups
+ */
+int sknnr_debug_last_grouped(const sknnr_index* index, int64_t out[8]);
+
 /* ---- reference-sharded search ------------------------------------------------------------------ */
 
 /*

@@ -393,6 +393,27 @@ def replay_tree_selection(fit_X, rows_X, kk, algorithm, leaf_size, call_rows, se
     return _finish_selection(nd, neigh.astype(np.int64, copy=False), kk, call_rows, self_query, deterministic, decimals)
 
 
+def normalize_groups(groups, n_samples):
+    """The int32 group codes of ``groups``, a 1-D array-like of ``n_samples`` labels (integers, strings, a pandas Series),
+    as ``np.unique(..., return_inverse=True)`` numbers them.  ``ValueError`` for more than one dimension, a wrong length,
+    a float array holding NaN and a single group."""
+    g = groups.to_numpy() if hasattr(groups, "to_numpy") else np.asarray(groups)
+    if g.ndim != 1:
+        raise ValueError(f"groups must be 1-D with one label per fitted row, got an array of shape {g.shape}")
+    if g.shape[0] != n_samples:
+        raise ValueError(f"groups must hold one label per fitted row ({n_samples}), got {g.shape[0]}")
+    if g.dtype.kind == "f" and np.isnan(g).any():
+        raise ValueError(f"groups must not hold NaN, got {int(np.isnan(g).sum())} NaN labels")
+    try:
+        labels, codes = np.unique(g, return_inverse=True)
+    except TypeError:
+        raise ValueError(f"groups must hold labels that can be ordered, got dtype {g.dtype} with mixed types") from None
+    if labels.size < 2:
+        raise ValueError(f"groups must name at least two groups, got the single group {labels[0]!r}: "
+                         "no fitted row would have a candidate")
+    return np.ascontiguousarray(codes.reshape(-1), dtype=np.int32)
+
+
 def _reraise(err, estimator):
     """Map a native failure to the exception the reference raises for the same input."""
     if err.code == _native.ERR_K_TOO_LARGE:
@@ -854,6 +875,66 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         if X is not None:
             X = self._validate_query(X)
         return self._summarize_engine(X, stat, apply_affine=False)
+
+    # -- leave-group-out: independent predictions that skip groups ------------------------------
+    def _independent_neighbors(self, groups, k, use_deterministic_ordering=True):
+        """``(dist, idx)`` of :meth:`independent_kneighbors` as host arrays; everything is refused before device work."""
+        check_is_fitted(self, "_fit_X")
+        self._check_reference_ties_supported("independent_kneighbors with groups")
+        codes = normalize_groups(groups, self.n_samples_fit_)
+        try:
+            self.engine_.set_groups(codes)
+            return self.engine_.kneighbors_grouped(k, deterministic=bool(use_deterministic_ordering),
+                                                   decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula())
+        except _native.HipBackendError as err:
+            _reraise(err, self)
+
+    def independent_kneighbors(self, groups, n_neighbors=None, return_distance=True, return_dataframe_index=False,
+                               use_deterministic_ordering=True):
+        """Leave-group-out neighbours: for every fitted row the ``n_neighbors`` nearest fitted rows of OTHER groups.
+
+        ``groups``: a 1-D array-like of ``n_samples_fit_`` labels (integers, strings, a pandas Series) -- the plot of a
+        re-measured row, the cluster of a subplot, the block of a spatial cross-validation.  For fitted row ``i`` the
+        candidates are the fitted rows whose label differs from row ``i``'s, so never ``i`` itself.  Every pair has the
+        float64 value ``kneighbors`` ranks it by; the answer is the ``k`` candidates smallest by (value, index), their
+        distances, and -- with ``use_deterministic_ordering`` -- sknnr's reorder (REF _base.py:166-175).  Exact ties at the
+        k-th value go to the lower index: the reference has no grouped search, so no choice of its is replayed, and the
+        calls are refused under ``hamming_tie_policy("numpy")`` and ``tree_tie_policy("tree")``.  With every row in a
+        group of its own this is ``kneighbors(X=None)`` wherever the k-th and (k+1)-th values differ.
+
+        ``ValueError`` for labels that are not 1-D, of another length, NaN, or all one group, and for ``n_neighbors``
+        above ``n_samples_fit_`` minus the largest group.  Results are host arrays."""
+        k = self._resolve_k(n_neighbors)
+        dist, idx = self._independent_neighbors(groups, k, use_deterministic_ordering)
+        return self._finish_kneighbors(dist, idx, return_distance, return_dataframe_index)
+
+    def independent_predict(self, groups):
+        """``predict`` of every fitted row from its :meth:`independent_kneighbors` (``n_neighbors`` of the estimator,
+        deterministic ordering on) with the estimator's weights: what ``independent_prediction_`` is when every row is
+        its own group, and the honest figure when it is not."""
+        dist, idx = self._independent_neighbors(groups, self.n_neighbors)
+        pred = self.engine_.predict_from_neighbors(dist, idx, "uniform" if self.weights is None else self.weights)
+        return pred.reshape(-1) if self._y.ndim == 1 else pred
+
+    def independent_summarize(self, groups, statistic=None, outputs=None):
+        """:meth:`summarize` of every fitted row over its :meth:`independent_kneighbors`; ``statistic`` / ``outputs`` as there."""
+        check_is_fitted(self, "_fit_X")
+        if statistic is None and outputs is None:
+            statistic = "mean"
+        stat = resolve_statistic(statistic, outputs, self._n_targets())
+        dist, idx = self._independent_neighbors(groups, self.n_neighbors)
+        weights = "uniform" if self.weights is None else self.weights
+        if isinstance(stat, OutputPlan):
+            out = self.engine_.summarize_plan_from_neighbors(dist, idx, weights, stat.arrays)
+            if not stat.per_target:
+                return out
+        else:
+            out = self.engine_.summarize_from_neighbors(dist, idx, weights, stat)
+        return out.reshape(-1) if self._y.ndim == 1 else out
+
+    def independent_score(self, groups, sample_weight=None):
+        """R^2 of :meth:`independent_predict` against the fitted targets: ``independent_score_`` with groups left out."""
+        return float(r2_score(self._y, self.independent_predict(groups), sample_weight=sample_weight))
 
     # -- streamed tiles (raster ingestion; REF docs/pages/usage.md:101-128) --------------------
     def _check_stream_supported(self, feature):
@@ -1478,6 +1559,29 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
             X = self._validate_raw_query(X)
         return self._host_result(X, reg._summarize_engine(X, stat, apply_affine=X is not None and self._map_on_device(),
                                                           owner=self.transformer_))
+
+    def independent_kneighbors(self, groups, n_neighbors=None, return_distance=True, return_dataframe_index=False,
+                               use_deterministic_ordering=True):
+        """Leave-group-out neighbours of every fitted row, in the transformed space the estimator searches
+        (:meth:`RawKNNRegressor.independent_kneighbors`, also for the contract and the tie rule)."""
+        check_is_fitted(self, "regressor_")
+        return self.regressor_.independent_kneighbors(groups, n_neighbors, return_distance, return_dataframe_index,
+                                                      use_deterministic_ordering)
+
+    def independent_predict(self, groups):
+        """:meth:`RawKNNRegressor.independent_predict` of the fitted regressor."""
+        check_is_fitted(self, "regressor_")
+        return self.regressor_.independent_predict(groups)
+
+    def independent_summarize(self, groups, statistic=None, outputs=None):
+        """:meth:`RawKNNRegressor.independent_summarize` of the fitted regressor."""
+        check_is_fitted(self, "regressor_")
+        return self.regressor_.independent_summarize(groups, statistic, outputs)
+
+    def independent_score(self, groups):
+        """R^2 of :meth:`independent_predict` against the fitted targets (no ``sample_weight``, as :meth:`score`)."""
+        check_is_fitted(self, "regressor_")
+        return self.regressor_.independent_score(groups)
 
     def _raw_nodata(self, nodata):
         """``nodata`` of a streamed call, one value per UNTRANSFORMED input column: the mask reads the raw rows, so they

@@ -75,6 +75,7 @@ class KNNEngine:
         self.has_affine = False
         self.has_forest = False
         self._law_key = None  # (law code, p0, p1) the handle holds: weight_law()
+        self._group_codes = None  # the group codes the handle holds: set_groups()
 
     def close(self):
         self._index.close()
@@ -223,6 +224,32 @@ class KNNEngine:
         if nodata is not None:
             return self._index.kneighbors_masked_host(X, opts, nodata, fill_index, return_distance=return_distance)[:2]
         return self._index.kneighbors_host(X, opts, return_distance=return_distance)
+
+    def set_groups(self, codes):
+        """The group code of every reference row for :meth:`kneighbors_grouped` (``n_ref`` integers >= 0, ``None``
+        clears).  The engine keeps the last codes it uploaded and uploads again only when they change."""
+        if codes is None:
+            if self._group_codes is not None:
+                self._index.set_groups(None)
+                self._group_codes = None
+            return
+        codes = np.ascontiguousarray(codes, dtype=np.int32).reshape(-1)
+        if self._group_codes is not None and np.array_equal(codes, self._group_codes):
+            return
+        self._index.set_groups(codes)
+        self._group_codes = codes.copy()
+
+    def kneighbors_grouped(self, k, *, deterministic, decimals, formula, row_offset=0, n_rows=None, return_distance=True):
+        """Leave-group-out neighbours of the reference rows ``[row_offset, row_offset + n_rows)`` under the codes of
+        :meth:`set_groups`: per row the ``k`` rows of other groups smallest by (value, index) under ``formula``, the
+        square root (not for Hamming), and sknnr's reorder with ``deterministic``.  Exact ties at the k-th value go to the
+        lower index; scikit-learn's heap history is not replayed.  Numpy out: ``(dist or None, idx)``."""
+        code = {"direct": _native.FORMULA_DIRECT, "hamming": _native.FORMULA_HAMMING}.get(formula, _native.FORMULA_EXPANDED)
+        return self._index.kneighbors_grouped(k, deterministic=deterministic, decimals=decimals, formula=code,
+                                              row_offset=row_offset, n_rows=n_rows, return_distance=return_distance)
+
+    def debug_last_grouped(self) -> dict:
+        return self._index.debug_last_grouped()
 
     def weight_mode(self, weights, w32=False) -> int:
         """The native weight mode of a ``uniform`` / ``distance`` / explicit (``"explicit"``) reduction, with the

@@ -96,6 +96,9 @@ EXPORTED_SYMBOLS = (
     "sknnr_debug_last_weight_law",
     "sknnr_debug_weight_law",
     "sknnr_hamming_distances",
+    "sknnr_index_set_groups",
+    "sknnr_kneighbors_grouped",
+    "sknnr_debug_last_grouped",
     "sknnr_shard_candidates",
     "sknnr_merge_shards",
     "sknnr_stream_begin",
@@ -278,6 +281,10 @@ def load(build_if_missing: bool = False):
     lib.sknnr_debug_last_weight_law.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_debug_weight_law.argtypes = [c_int32, c_double, c_double, vp, c_int64, vp, c_int32, c_int32]
     lib.sknnr_hamming_distances.argtypes = [vp, vp, c_int64, vp, c_int64, vp, c_int32, vp]
+    if hasattr(lib, "sknnr_kneighbors_grouped"):  # (a SKNNR_HIP_LIBRARY variant built before the entry points existed)
+        lib.sknnr_index_set_groups.argtypes = [vp, vp, c_int64]
+        lib.sknnr_kneighbors_grouped.argtypes = [vp, c_int64, POINTER(QueryOpts), vp, vp, c_int32, vp]
+        lib.sknnr_debug_last_grouped.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_shard_candidates.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int64, vp, vp, c_int32, vp]
     lib.sknnr_merge_shards.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int32, vp, vp, vp, vp, c_int32, vp]
     lib.sknnr_crosswalk.argtypes = [vp, c_int64, vp, c_int64, vp, c_int32, c_int32, vp]
@@ -415,6 +422,41 @@ class Index:
     def set_hamming_weights(self, w):
         w = _c_f64(w).reshape(-1)
         check(load().sknnr_index_set_hamming_weights(self.handle, _host_ptr(w), w.size))
+
+    def set_groups(self, codes):
+        """The group code of every reference row for :meth:`kneighbors_grouped` (sknnr_index_set_groups): ``n_ref``
+        integers >= 0, copied to the device and kept on the handle; ``None`` clears them."""
+        if codes is None:
+            check(load().sknnr_index_set_groups(self.handle, None, 0))
+            return
+        codes = np.ascontiguousarray(codes, dtype=np.int32).reshape(-1)
+        check(load().sknnr_index_set_groups(self.handle, _host_ptr(codes), codes.size))
+
+    def kneighbors_grouped(self, k, *, deterministic, decimals, formula, row_offset=0, n_rows=None, return_distance=True):
+        """Leave-group-out neighbours of reference rows ``[row_offset, row_offset + n_rows)`` (sknnr_kneighbors_grouped;
+        ``n_rows=None``: to the last row): for every row the ``k`` rows of OTHER groups smallest by (value, index) under
+        ``formula``, then the square root (not for Hamming) and, with ``deterministic``, sknnr's reorder.  Exact ties at
+        the k-th value go to the lower index -- no heap history is replayed.  Returns numpy ``(dist or None, idx)``."""
+        if n_rows is None:
+            n_rows = self.n_ref - int(row_offset)
+        opts = self.make_opts(k, exclude_self=True, deterministic=deterministic, decimals=decimals, formula=formula,
+                              row_offset=row_offset)
+        n = max(int(n_rows), 0)
+        idx = np.empty((n, int(k)), dtype=np.int64)
+        dist = np.empty((n, int(k)), dtype=np.float64) if return_distance else None
+        check(load().sknnr_kneighbors_grouped(self.handle, int(n_rows), byref(opts), _host_ptr(dist), _host_ptr(idx),
+                                              MEM_HOST, None))
+        return dist, idx
+
+    GROUPED_FIELDS = ("formula_plus_1", "k", "workgroups", "lds_bytes", "rows", "slices", "largest_group", "n_groups")
+
+    def debug_last_grouped(self) -> dict:
+        """Debug only: the leave-group-out scan of the last search call (sknnr_debug_last_grouped): formula + 1 (0: no
+        grouped scan ran), k, workgroups and dynamic LDS bytes of the launch, rows, slices (1: none), the rows of the
+        largest group and the number of groups.  Every search call zeroes it first."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_grouped(self.handle, out))
+        return dict(zip(self.GROUPED_FIELDS, (int(v) for v in out)))
 
     def set_forest(self, d_in, tree_offset, threshold, feature, left, right):
         """Install the query-time forest map (sknnr_index_set_forest): the flattened trees of

@@ -1,5 +1,5 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
@@ -13,6 +13,7 @@
 #include "coarse2.hip.h"
 #include "exact.hip.h"
 #include "forest.hip.h"
+#include "groups.hip.h"
 #include "hamming.hip.h"
 #include "mask.hip.h"
 #include "narrow.hip.h"
@@ -94,6 +95,11 @@ hipError_t plan(const PlanArgs& a, hipStream_t st);
 // ---- k_weights.hip: distance-weight laws (weights.hip.h) ------------------------------------------------------------------
 // a.w[e] = law(a.dist[e]) for a.n elements; hipErrorInvalidValue for an unknown law
 hipError_t weight_law(const WeightLawArgs& a, hipStream_t st);
+
+// ---- k_groups.hip: leave-group-out neighbours (groups.hip.h) -----------------------------------------------------------------
+// reference rows [a.s.row_offset, + a.s.nq) against all rows of other groups; `blocks` workgroups take the passes grid-stride;
+// chunked: d > kScanColChunk
+hipError_t group_scan(int formula, bool chunked, const GroupScanArgs& a, long blocks, size_t lds_bytes, hipStream_t st);
 
 // ---- k_coarse1.hip / k_coarse2.hip: the MFMA pre-filters ----------------------------------------------------------------
 struct Coarse1Launch {

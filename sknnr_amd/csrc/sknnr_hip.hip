@@ -349,6 +349,9 @@ struct SearchRecords {
     int64_t rescue[2] = {};
     // the nodata front end of the last tile (sknnr_debug_last_mask)
     int64_t mask[8] = {};
+    // the leave-group-out scan of the last call (sknnr_debug_last_grouped): formula + 1, k, workgroups, LDS bytes, rows,
+    // slices (1: none), the largest group, the number of groups
+    int64_t grouped[8] = {};
 };
 
 struct sknnr_index {
@@ -380,6 +383,10 @@ struct sknnr_index {
     DevBuf<double> hw;       // weighted-Hamming weights (one per column), set by sknnr_index_set_hamming_weights
     double hw_sum = 0.0;
     bool has_hw = false;
+    // leave-group-out neighbours (groups.hip.h): the group code of every reference row, set by sknnr_index_set_groups
+    DevBuf<int> g_codes;
+    bool has_groups = false;
+    long g_largest = 0, g_count = 0;  // rows of the largest group, number of groups
     // integer pre-filter of the weighted-Hamming search (hamming.hip.h): 16-bit ids / weights, two trees per dword
     bool h16_ok = false;           // every reference id is an integer in [0, 65535]
     int h_tp = 0, h_ref_pad = 0;   // tree pairs; reference rows padded to the step of the kernel
@@ -2962,6 +2969,129 @@ extern "C" int sknnr_kneighbors(sknnr_index* ix, const void* q, int64_t nq, cons
     return run_self_rows(ix, nq, o, out_dist, (long*)out_idx, nullptr);
 }
 
+// ----------------------------------------------------------------------------------------
+// leave-group-out neighbours (groups.hip.h)
+// ----------------------------------------------------------------------------------------
+extern "C" int sknnr_index_set_groups(sknnr_index* ix, const int32_t* codes, int64_t n) {
+    if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (!codes) {  // clear
+        std::lock_guard<std::mutex> lock(ix->mtx);
+        ix->has_groups = false;
+        ix->g_largest = ix->g_count = 0;
+        return SKNNR_OK;
+    }
+    if (n != ix->n_ref) return fail(SKNNR_ERR_INVALID, "codes must hold one group code per reference row (%ld), got %ld", ix->n_ref, (long)n);
+    std::vector<int32_t> sorted(codes, codes + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (n > 0 && sorted[0] < 0) return fail(SKNNR_ERR_INVALID, "group codes must be >= 0, got %d", (int)sorted[0]);
+    long largest = 0, count = 0;
+    for (int64_t i = 0; i < n;) {
+        int64_t j = i;
+        while (j < n && sorted[j] == sorted[i]) ++j;
+        largest = std::max<long>(largest, j - i);
+        ++count;
+        i = j;
+    }
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());  // (a grouped call on another stream may still read the codes held so far)
+    HIP_TRY(ix->g_codes.ensure((size_t)n));
+    HIP_TRY(hipMemcpy(ix->g_codes.p, codes, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    ix->g_largest = largest;
+    ix->g_count = count;
+    ix->has_groups = true;
+    return SKNNR_OK;
+}
+
+namespace {
+
+// Device-resident core of sknnr_kneighbors_grouped: reference rows [o->row_offset, + nq), outputs on the device.  One
+// launch: passes of kGroupNq rows, one workgroup each, taken grid-stride by at most kScanGridWg workgroups; never sliced.
+int run_grouped_device(sknnr_index* ix, long nq, const sknnr_query_opts* o, double* d_dist, long* d_idx, hipStream_t st) {
+    zero_records(ix);
+    // (every accepted call fits: the LDS grows with min(d, kScanColChunk) and k <= kScanMaxKK only)
+    static_assert(group_scan_bytes(kScanColChunk, kScanMaxKK) <= kLdsLimit, "the widest grouped call fits a workgroup's LDS");
+    const size_t sh = group_scan_bytes(ix->d, o->n_neighbors);
+    if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));  // (the staged outputs of host calls are workspace)
+    GroupScanArgs a{};
+    a.s = make_select_args(ix, o, o->n_neighbors, nullptr, nq, d_dist, d_idx);
+    a.refT = ix->refT.p;
+    a.codes = ix->g_codes.p;
+    sknnr_index::CallTiming& ct = ix->timing[ix->timing_next];
+    ix->timing_next = (ix->timing_next + 1) % sknnr_index::kTimingRing;
+    resolve_call(ix, ct);
+    if (!ct.e0) {
+        HIP_TRY(hipEventCreate(&ct.e0));
+        HIP_TRY(hipEventCreate(&ct.e1));
+    }
+    ct.coarse_used = 0;
+    ct.coarse_rows = 0;
+    HIP_TRY(hipEventRecord(ct.e0, st));
+    const long passes = (nq + kGroupNq - 1) / kGroupNq;
+    const long blocks = std::max<long>(1, std::min<long>(passes, kScanGridWg));
+    const int64_t rec[8] = {o->formula + 1, o->n_neighbors, blocks, (int64_t)sh, nq, 1, ix->g_largest, ix->g_count};
+    std::copy(std::begin(rec), std::end(rec), ix->last.grouped);
+    HIP_TRY(launch::group_scan(o->formula, ix->d > kScanColChunk, a, blocks, sh, st));  // wide rows: in column chunks
+    HIP_TRY(hipEventRecord(ct.e1, st));
+    ct.pending = true;
+    HIP_TRY(hipEventRecord(ix->ev_ws, st));
+    ix->ws_busy = true;
+    ix->stats.queries += nq;
+    ix->stats.exact_only_queries += nq;
+    return SKNNR_OK;
+}
+
+}  // namespace
+
+extern "C" int sknnr_kneighbors_grouped(sknnr_index* ix, int64_t nq, const sknnr_query_opts* o, double* out_dist,
+                                        int64_t* out_idx, int32_t mem, void* stream) {
+    if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (!o) return fail(SKNNR_ERR_INVALID, "opts is NULL");
+    if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
+    if (!out_idx && nq > 0) return fail(SKNNR_ERR_INVALID, "out_idx is NULL");
+    if (o->n_neighbors <= 0) return fail(SKNNR_ERR_INVALID, "Expected n_neighbors > 0. Got %d", o->n_neighbors);
+    if (!o->exclude_self) return fail(SKNNR_ERR_INVALID, "the rows of a grouped search are reference rows: exclude_self must be 1");
+    if (o->apply_affine || o->query_dtype != SKNNR_DTYPE_F64)
+        return fail(SKNNR_ERR_INVALID, "a grouped search reads the handle's own rows: apply_affine and query_dtype must be 0");
+    if (o->formula != SKNNR_FORMULA_EXPANDED && o->formula != SKNNR_FORMULA_DIRECT && o->formula != SKNNR_FORMULA_HAMMING)
+        return fail(SKNNR_ERR_INVALID, "unknown formula %d", o->formula);
+    if (o->formula == SKNNR_FORMULA_HAMMING && !ix->has_hw)
+        return fail(SKNNR_ERR_INVALID, "formula = HAMMING needs sknnr_index_set_hamming_weights first");
+    if (std::abs(o->decimals) > 300) return fail(SKNNR_ERR_INVALID, "decimals out of range");
+    if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (!ix->has_groups) return fail(SKNNR_ERR_INVALID, "sknnr_kneighbors_grouped needs sknnr_index_set_groups first");
+    const long n_fit = ix->n_ref;
+    if (o->row_offset < 0 || o->row_offset + nq > n_fit)
+        return fail(SKNNR_ERR_INVALID, "grouped query rows [%ld, %ld) outside the %ld reference rows", (long)o->row_offset,
+                    (long)(o->row_offset + nq), n_fit);
+    if (o->n_neighbors > n_fit - ix->g_largest)
+        return fail(SKNNR_ERR_K_TOO_LARGE,
+                    "Expected n_neighbors <= n_samples_fit - largest group, but n_neighbors = %d, n_samples_fit = %ld, largest group = %ld",
+                    o->n_neighbors, n_fit, ix->g_largest);
+    if (o->n_neighbors > kScanMaxKK)
+        return fail(SKNNR_ERR_UNSUPPORTED, "n_neighbors = %d exceeds the HIP backend's limit of %d%s", o->n_neighbors, kScanMaxKK, "");
+    if (nq == 0) return SKNNR_OK;
+    HIP_TRY(hipSetDevice(ix->device));
+    if (mem == SKNNR_MEM_DEVICE) return run_grouped_device(ix, nq, o, out_dist, (long*)out_idx, (hipStream_t)stream);
+    hipStream_t st = nullptr;
+    const int k = o->n_neighbors;
+    for (long c0 = 0; c0 < nq; c0 += kChunkRows) {
+        const long n = std::min<long>(kChunkRows, nq - c0);
+        if (out_dist) HIP_TRY(ix->dist_stage.ensure((size_t)n * k));
+        HIP_TRY(ix->idx_stage.ensure((size_t)n * k));
+        sknnr_query_opts oc = *o;
+        oc.row_offset = o->row_offset + c0;
+        int rc = run_grouped_device(ix, n, &oc, out_dist ? ix->dist_stage.p : nullptr, ix->idx_stage.p, st);
+        if (rc) return rc;
+        if (out_dist)
+            HIP_TRY(hipMemcpyAsync(out_dist + c0 * k, ix->dist_stage.p, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out_idx + c0 * k, ix->idx_stage.p, (size_t)n * k * sizeof(long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return SKNNR_OK;
+}
+
 
 // ----------------------------------------------------------------------------------------
 // nodata rows: the mask alone, and the masked calls
@@ -4120,6 +4250,7 @@ extern "C" int sknnr_debug_last_summary(const sknnr_index* ix, int64_t out[8]) {
 extern "C" int sknnr_debug_last_plan(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last_plan; }); }
 extern "C" int sknnr_debug_last_planes(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last_planes; }); }
 extern "C" int sknnr_debug_last_weight_law(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last_law; }); }
+extern "C" int sknnr_debug_last_grouped(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last.grouped; }); }
 
 // The mask, the scan and the compaction alone, on the caller's device pointers (run_device_masked's sequence without the
 // search): the block offsets and the ranks, which no search result shows, come back to the host.
