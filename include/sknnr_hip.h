@@ -717,6 +717,49 @@ int sknnr_stream_push_typed(sknnr_stream* stream, const void* q, int64_t nq, voi
 int sknnr_stream_push_planes_typed(sknnr_stream* stream, const void* const* planes, int64_t nq, void* out_dist,
                                    void* out_idx, void* out_pred, int64_t out_stride);
 
+/* ---- neighbour usage (which reference rows made the map) ---------------------------------------- */
+
+/*
+ * Neighbour usage.  THE CONTRACT, stated here once (sknnr_amd/csrc/tally.hip.h implements it, tests/_usage.py restates it
+ * in numpy).  For one or more tallied searches over a handle with n_ref reference rows and k neighbours:
+ *   counts[r, j]  int64, (n_ref, k), C order: the number of tallied query rows whose j-th returned neighbour is reference
+ *                 row r; j is the position in the returned row, after sknnr's reorder when the call uses it.
+ *   max_dist[r]   float64, (n_ref): the largest returned distance at which r was anybody's neighbour, at any rank.  A
+ *                 distance that is not > 0 (0.0, -0.0, NaN) counts as +0.0.  A row never used holds 0.0: its counts say so.
+ * Rows masked by nodata contribute nothing.  In the from-neighbours form an entry < 0 or >= n_ref is never dereferenced:
+ * it is skipped and counted in the debug record (a whole row may go that way: a fill row is all negative).  The tally is
+ * over ROW INDICES, never dataframe ids, and is unaffected by the id table, the typed outputs, the band layout, the
+ * statistics or the plan of the same stream.  The results do not depend on launch geometry, tile cuts or arrival order:
+ * counts are integer adds, and the maximum is taken on the distances' bit patterns as unsigned 64-bit integers -- valid
+ * because they are non-negative and never NaN after the rule above -- so two runs are bit-equal.  Sums of prediction
+ * weights are deliberately absent: a float atomic sum depends on arrival order.
+ * n_ref * k must be below 2^32 (the kernel's keys are 32 bits): SKNNR_ERR_UNSUPPORTED otherwise, before any device work.
+ *
+ * sknnr_tally_from_neighbors: idx (nq, k) int64 and dist (nq, k) float64 as a search returned them; counts / max_dist as
+ *   above; all in `mem` (host arrays are staged; device arrays are used in place, enqueued on `stream`).  dist and
+ *   max_dist may both be NULL: counts only.  accumulate = 0 zeroes the outputs first; accumulate = 1 adds to what they
+ *   hold, max_dist being read back through the same rule (a value that is not > 0 is +0.0).  nq == 0 is allowed.
+ * sknnr_stream_set_tally: allowed only before the first push.  Allocates and zeroes the two accumulators for the
+ *   stream's k on the handle.  From then on the stream keeps the search's distances even when no distance or prediction
+ *   leaves, and every tile is tallied on the device behind its search: the whole tile, or with sknnr_stream_set_nodata
+ *   its valid rows (never the expanded rows: fill_index need not be negative).  What the pushes deliver is unchanged,
+ *   bit for bit.  A stream on which it is never called enqueues exactly what it did before the entry point existed.
+ * sknnr_stream_get_tally: flushes the pipeline (as sknnr_stream_flush) and copies the accumulators to HOST arrays
+ *   (either may be NULL).  May be called more than once; the accumulators keep running.
+ * sknnr_debug_last_tally: debug only; synchronises the device.  The last sknnr_tally_from_neighbors call, or -- after
+ *   sknnr_stream_set_tally -- the stream so far:
+ *   out[0] 1 = a tally kernel ran          out[1] rows given to it          out[2] k
+ *   out[3] entries tallied                 out[4] entries skipped (outside [0, n_ref))
+ *   out[5] global atomics issued on the accumulators
+ *   out[6] entries that found no slot in their workgroup's table and went to the accumulators directly
+ *   out[7] slots of a workgroup's table
+ */
+int sknnr_tally_from_neighbors(sknnr_index* index, const double* dist, const int64_t* idx, int64_t nq, int32_t k,
+                               int64_t* counts, double* max_dist, int32_t accumulate, int32_t mem, void* stream);
+int sknnr_stream_set_tally(sknnr_stream* stream);
+int sknnr_stream_get_tally(sknnr_stream* stream, int64_t* counts, double* max_dist);
+int sknnr_debug_last_tally(const sknnr_index* index, int64_t out[8]);
+
 /*
  * Debug only.  The output side of the last tile the handle's host pipeline submitted, so that a test can prove that the
  * device converted it and that only the narrow bytes were copied.  Host memory, no device work:

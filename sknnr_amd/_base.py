@@ -27,6 +27,7 @@ from sklearn.utils.validation import _is_arraylike, check_is_fitted, validate_da
 
 from . import _config, _native
 from ._engine import KNNEngine, default_device, is_torch_cuda_tensor
+from ._usage import NeighborUsage
 from .weights import DistanceWeights
 
 # Element types query rows may keep on their way to the device (include/sknnr_hip.h, sknnr_dtype): the kernel that reads
@@ -936,6 +937,33 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         """R^2 of :meth:`independent_predict` against the fitted targets: ``independent_score_`` with groups left out."""
         return float(r2_score(self._y, self.independent_predict(groups), sample_weight=sample_weight))
 
+    # -- neighbour usage: which fitted rows made the map ------------------------------------------
+    def _usage_from_neighbors(self, dist, idx):
+        counts, max_dist = self.engine_.tally_from_neighbors(dist, idx)
+        usage = NeighborUsage()
+        return usage._add(counts, max_dist, getattr(self, "dataframe_index_in_", None))
+
+    def neighbor_usage(self, X=None, n_neighbors=None):
+        """The :class:`sknnr_amd.NeighborUsage` of ``kneighbors(X, n_neighbors)`` (deterministic ordering): per fitted
+        row and rank the query rows it served, and the largest distance among them, tallied on the device from the
+        neighbours the search returns.  ``X=None``: of every fitted row's neighbours, itself excluded.  For a raster,
+        pass ``usage=`` to :meth:`kneighbors_chunks` / :meth:`predict_chunks` instead: the tally then costs no transfer."""
+        dist, idx = self.kneighbors(X, n_neighbors=n_neighbors)
+        try:
+            return self._usage_from_neighbors(dist, idx)
+        except _native.HipBackendError as err:
+            _reraise(err, self)
+
+    def independent_neighbor_usage(self, groups, n_neighbors=None):
+        """The :class:`sknnr_amd.NeighborUsage` of :meth:`independent_kneighbors` ``(groups, n_neighbors)``: which fitted
+        rows the leave-group-out predictions lean on."""
+        k = self._resolve_k(n_neighbors)
+        dist, idx = self._independent_neighbors(groups, k)
+        try:
+            return self._usage_from_neighbors(dist, idx)
+        except _native.HipBackendError as err:
+            _reraise(err, self)
+
     # -- streamed tiles (raster ingestion; REF docs/pages/usage.md:101-128) --------------------
     def _check_stream_supported(self, feature):
         """The nodata mask, the band-first transposes and the typed conversions (``feature``: "nodata is", "layout='bands'
@@ -954,7 +982,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
     def _stream_tiles(self, tiles, validate, k, *, apply_affine, weights, return_distance,
                       use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False, output=None,
-                      statistic=None, id_table=None, fill_id=-1, neighbors=False):
+                      statistic=None, id_table=None, fill_id=-1, neighbors=False, usage=None):
         """Push host tiles through one native query stream.  Returns (dist, idx, pred) arrays over all
         pushed rows (pieces of ``out`` when given, else concatenated).  ``nodata`` (float64, one value per column of the
         validated tiles): rows holding one are masked on the device and get ``fill_index`` / NaN.
@@ -974,7 +1002,13 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
         ``neighbors`` (with ``weights``): the indices (and, with ``return_distance``, the distances) the predictions are
         reduced from are delivered beside them, from the same stream; an output without an array in ``out`` is
-        collected and concatenated."""
+        collected and concatenated.
+
+        ``usage`` (a :class:`sknnr_amd.NeighborUsage`): the stream tallies every tile's neighbours on the device and the
+        call adds the result to it; nothing else about the call changes."""
+        if usage is not None:
+            self._check_stream_supported("usage is")
+            usage._check(self.n_samples_fit_, k)  # (a mismatch is refused before any device work)
         if output:
             self._check_stream_supported("typed outputs are")
         eng = self.engine_
@@ -1055,7 +1089,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              apply_affine=apply_affine, check_finite=True, query_dtype=code,
                                              nodata=nodata, fill_index=fill_index, output=output,
                                              **(dict(statistic=statistic) if plan is None else dict(plan=plan.arrays)),
-                                             **({} if id_table is None else dict(id_table=id_table, fill_id=fill_id)))
+                                             **({} if id_table is None else dict(id_table=id_table, fill_id=fill_id)),
+                                             **({} if usage is None else dict(tally=True)))
                 if first.dtype != stream_dtype:
                     if stream_dtype != np.float64:
                         raise ValueError(f"the tiles of one streamed call must share an element type: got {first.dtype} "
@@ -1085,9 +1120,20 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 if out is None or neighbors:
                     pieces.append(got)
                 row += n
+            tallied = None
             if stream is not None:
                 done, stream = stream, None
-                done.close()
+                try:
+                    if usage is not None:
+                        tallied = done.tally()
+                finally:
+                    done.close()
+            if usage is not None:  # (only a call that came through whole is added)
+                ids = getattr(self, "dataframe_index_in_", None)
+                if tallied is None:
+                    usage._bind(self.n_samples_fit_, k, ids)
+                else:
+                    usage._add(*tallied, ids)
         except _native.HipBackendError as err:
             _reraise(err, owner if owner is not None else self)
         finally:
@@ -1144,7 +1190,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
     def kneighbors_chunks(self, tiles, n_neighbors=None, return_distance=True, return_dataframe_index=False,
                           use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1, layout="rows",
-                          index_dtype=None, distance_dtype=None):
+                          index_dtype=None, distance_dtype=None, usage=None):
         """``kneighbors`` over an iterable of host tiles ``(n_i, n_features)`` -- windows of a raster,
         slices of a ``numpy.memmap`` -- as ONE logical call: the copy-in / kernels / copy-out pipeline
         stays full across tiles and row positions count over all tiles, so the result equals
@@ -1168,7 +1214,13 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         ``return_dataframe_index=True`` with integer dataframe ids (at most 64 bits, not uint64): the ids are looked up
         on the device, inside the conversion every tile's indices leave through, so ``out`` receives ids (int64, or
         int32 with ``index_dtype``) and the host never walks the output again; other labels (strings, ...) and the
-        host-side tie policies are looked up on the host afterwards, as before."""
+        host-side tie policies are looked up on the host afterwards, as before.
+
+        ``usage`` (a :class:`sknnr_amd.NeighborUsage`): every tile's neighbours are tallied on the device -- per fitted
+        row and rank the pixels it served, and the largest distance it was imputed over; masked pixels contribute
+        nothing -- and the call adds the result to the object.  Everything the call returns or writes is bit-identical to
+        the call without it; no index crosses PCIe for the tally.  The tally is over row positions whatever
+        ``return_dataframe_index`` says.  Refused under the host-side tie policies."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         k = self._resolve_k(n_neighbors)
@@ -1186,7 +1238,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                           return_distance=return_distance,
                                           use_deterministic_ordering=use_deterministic_ordering, out=o, owner=None,
                                           nodata=nodata, fill_index=-1 if return_dataframe_index else fill_index,
-                                          bands=bands, output=output, id_table=table, fill_id=fill_index)
+                                          bands=bands, output=output, id_table=table, fill_id=fill_index,
+                                          **({} if usage is None else dict(usage=usage)))
         return self._finish_chunks(dist, idx, return_distance, return_dataframe_index,
                                    fill_index=None if nodata is None else fill_index, on_device=table is not None)
 
@@ -1242,7 +1295,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
     def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
                        out_nodata=None, statistic=None, return_neighbors=False, return_distance=True,
                        return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
-                       distance_dtype=None, outputs=None):
+                       distance_dtype=None, outputs=None, usage=None):
         """``predict`` over an iterable of host tiles as one streamed call; ``out``: preallocated
         ``(n_rows, n_targets)`` float64 array (e.g. a memmap; float32 results are held exactly).  ``nodata`` as in
         :meth:`kneighbors_chunks`: masked rows are predicted NaN.  ``layout="bands"``: band-first tiles as in
@@ -1290,12 +1343,18 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         An estimator whose ``weights`` is a law of :mod:`sknnr_amd.weights` (``InverseDistance``, ...) is not a
         "callable" in the sense above: the device evaluates the law, and every keyword here applies as for
         ``weights="distance"``.  A compact law (``Triangular``, ``Epanechnikov``) predicts NaN where all k neighbours lie
-        at or beyond its bandwidth, so an integer ``out_dtype`` then needs ``out_nodata`` even without ``nodata``."""
+        at or beyond its bandwidth, so an integer ``out_dtype`` then needs ``out_nodata`` even without ``nodata``.
+
+        ``usage`` (a :class:`sknnr_amd.NeighborUsage`): as in :meth:`kneighbors_chunks` -- the neighbours the predictions
+        are reduced from are tallied on the device, with or without ``return_neighbors``, and the predictions are
+        bit-identical to the call without it.  Refused with callable weights and under the host-side tie policies."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         neighbors = self._neighbor_request(return_neighbors, return_distance, return_dataframe_index, neighbors_out,
                                            fill_index, index_dtype, distance_dtype)
         extra = {} if neighbors is None else dict(neighbors=neighbors)
+        if usage is not None:
+            extra["usage"] = usage
         statistic = resolve_statistic(statistic, outputs, self._n_targets())
         if nodata is not None:
             nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
@@ -1306,14 +1365,20 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                     typed=(out_dtype, scale, offset, out_nodata), statistic=statistic, **extra)
 
     def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None, bands=False, typed=None,
-                        statistic=None, neighbors=None):
-        """``neighbors``: :meth:`_neighbor_request`, or None -- predictions alone, exactly as before the keyword existed."""
+                        statistic=None, neighbors=None, usage=None):
+        """``neighbors``: :meth:`_neighbor_request`, or None -- predictions alone, exactly as before the keyword existed.
+        ``usage``: a :class:`sknnr_amd.NeighborUsage` the stream's tally is added to, or None."""
         weights = "uniform" if self.weights is None else self.weights
         # A distance-weight law (sknnr_amd.weights) is evaluated on the device inside the stream, so it goes wherever
         # "distance" goes; any other callable runs on the host and keeps every refusal below.
         law = isinstance(weights, DistanceWeights)
         host_callable = callable(weights) and not law
         output = None
+        if usage is not None:
+            if host_callable:
+                self._refuse_callable_weights("usage is")
+            self._check_stream_supported("usage is")
+            usage._check(self.n_samples_fit_, self.n_neighbors)
         plan = statistic if isinstance(statistic, OutputPlan) else None
         flat = self._y.ndim == 1 and (plan is None or plan.per_target)  # the result is 1-D
         if typed is not None:
@@ -1325,7 +1390,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 self._refuse_callable_weights("return_neighbors is")
             return self._predict_chunks_neighbors(tiles, validate, weights, neighbors, apply_affine=apply_affine, out=out,
                                                   owner=owner, nodata=nodata, bands=bands, output=output,
-                                                  statistic=statistic)
+                                                  statistic=statistic, usage=usage)
         if host_callable and output:
             self._refuse_callable_weights("typed outputs are")
         if host_callable and bands:
@@ -1354,13 +1419,14 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             _, _, pred = self._stream_tiles(tiles, validate, self.n_neighbors, apply_affine=apply_affine,
                                             weights=weights, return_distance=False,
                                             use_deterministic_ordering=True, out=o, owner=owner, nodata=nodata,
-                                            bands=bands, output=output, statistic=statistic)
+                                            bands=bands, output=output, statistic=statistic,
+                                            **({} if usage is None else dict(usage=usage)))
             if out is None and not output and statistic is None:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
                 pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         return pred.reshape(-1) if flat else pred
 
     def _predict_chunks_neighbors(self, tiles, validate, weights, neighbors, *, apply_affine, out, owner, nodata, bands,
-                                  output, statistic):
+                                  output, statistic, usage=None):
         """``predict_chunks(return_neighbors=True)``: one stream with all three outputs.  ``output``: the predictions'
         typed output (or None); the neighbours' types and the id table are worked out here, as ``kneighbors_chunks``
         does, every refusal before any device work."""
@@ -1379,7 +1445,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              return_distance=return_distance, use_deterministic_ordering=True, out=o,
                                              owner=owner, nodata=nodata, fill_index=-1 if ids else fill_index, bands=bands,
                                              output=merged, statistic=statistic, id_table=table, fill_id=fill_index,
-                                             neighbors=True)
+                                             neighbors=True, **({} if usage is None else dict(usage=usage)))
         if out is None and not output and statistic is None:  # (as without neighbours: float32 where scikit-learn returns it)
             pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         if self._y.ndim == 1 and not (isinstance(statistic, OutputPlan) and not statistic.per_target):
@@ -1583,6 +1649,20 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         check_is_fitted(self, "regressor_")
         return self.regressor_.independent_score(groups)
 
+    def neighbor_usage(self, X=None, n_neighbors=None):
+        """The :class:`sknnr_amd.NeighborUsage` of ``kneighbors(X, n_neighbors)`` (:meth:`RawKNNRegressor.neighbor_usage`)."""
+        dist, idx = self.kneighbors(X, n_neighbors=n_neighbors)
+        reg = self.regressor_
+        try:
+            return reg._usage_from_neighbors(dist, idx)
+        except _native.HipBackendError as err:
+            _reraise(err, self)
+
+    def independent_neighbor_usage(self, groups, n_neighbors=None):
+        """:meth:`RawKNNRegressor.independent_neighbor_usage` of the fitted regressor."""
+        check_is_fitted(self, "regressor_")
+        return self.regressor_.independent_neighbor_usage(groups, n_neighbors)
+
     def _raw_nodata(self, nodata):
         """``nodata`` of a streamed call, one value per UNTRANSFORMED input column: the mask reads the raw rows, so they
         must reach the engine raw (affine map or forests on the device)."""
@@ -1608,11 +1688,11 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
 
     def kneighbors_chunks(self, tiles, n_neighbors=None, return_distance=True, return_dataframe_index=False,
                           use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1, layout="rows",
-                          index_dtype=None, distance_dtype=None):
+                          index_dtype=None, distance_dtype=None, usage=None):
         """``kneighbors`` over an iterable of untransformed host tiles as one streamed call (see
         :meth:`RawKNNRegressor.kneighbors_chunks`, also for ``nodata`` / ``fill_index``: the nodata values are those of
-        the untransformed columns -- for ``layout="bands"`` and for ``index_dtype`` / ``distance_dtype``); each tile is
-        transformed on the device."""
+        the untransformed columns -- for ``layout="bands"``, for ``index_dtype`` / ``distance_dtype`` and for ``usage``);
+        each tile is transformed on the device."""
         bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
         reg = self.regressor_
@@ -1628,26 +1708,30 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
                                          use_deterministic_ordering=use_deterministic_ordering, out=o,
                                          owner=self.transformer_, nodata=nodata,
                                          fill_index=-1 if return_dataframe_index else fill_index, bands=bands,
-                                         output=output, id_table=table, fill_id=fill_index)
+                                         output=output, id_table=table, fill_id=fill_index,
+                                         **({} if usage is None else dict(usage=usage)))
         return reg._finish_chunks(dist, idx, return_distance, return_dataframe_index,
                                   fill_index=None if nodata is None else fill_index, on_device=table is not None)
 
     def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
                        out_nodata=None, statistic=None, return_neighbors=False, return_distance=True,
                        return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
-                       distance_dtype=None, outputs=None):
+                       distance_dtype=None, outputs=None, usage=None):
         """``predict`` over an iterable of untransformed host tiles as one streamed call (``nodata``: masked rows are
         predicted NaN; ``layout="bands"``: band-first tiles and predictions; ``out_dtype`` / ``scale`` / ``offset`` /
         ``out_nodata``: predictions converted on the device to the type the raster is stored in; ``statistic``: one name
         or one per target -- mean, mode, min, max, nearest, std or ("quantile", q) of the neighbours in place of the
         mean; ``outputs``: ``(target, statistic)`` pairs instead, ``n_out`` planes from the one search;
-        ``return_neighbors=True`` and the neighbour keywords: ``(pred, dist, idx)`` from one search; see
+        ``return_neighbors=True`` and the neighbour keywords: ``(pred, dist, idx)`` from one search; ``usage``: a
+        :class:`sknnr_amd.NeighborUsage` the device's tally of the neighbours is added to; see
         :meth:`RawKNNRegressor.kneighbors_chunks` / :meth:`RawKNNRegressor.predict_chunks`)."""
         bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
         neighbors = self.regressor_._neighbor_request(return_neighbors, return_distance, return_dataframe_index,
                                                       neighbors_out, fill_index, index_dtype, distance_dtype)
         extra = {} if neighbors is None else dict(neighbors=neighbors)
+        if usage is not None:
+            extra["usage"] = usage
         statistic = resolve_statistic(statistic, outputs, self.regressor_._n_targets())
         return self.regressor_._predict_chunks(tiles, self._band_validator(bands), apply_affine=self._map_on_device(),
                                                out=out, owner=self.transformer_, nodata=self._raw_nodata(nodata),

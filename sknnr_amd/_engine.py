@@ -315,6 +315,25 @@ class KNNEngine:
         pred = self._index.predict_from_neighbors_host(dist, idx, w, mode)
         return pred if out_dtype == np.float64 else pred.astype(np.float32)
 
+    def tally_from_neighbors(self, dist, idx):
+        """Neighbour usage of neighbours already found (sknnr_tally_from_neighbors): ``(counts, max_dist)`` as host arrays,
+        ``(n_ref, k)`` int64 and ``(n_ref,)`` float64 (0.0 where a row was never used), from numpy or torch.cuda
+        ``(dist, idx)``."""
+        if is_torch_cuda_tensor(idx):
+            import torch
+
+            idx = idx.to(torch.int64).contiguous()
+            dist = dist.to(torch.float64).contiguous()
+            nq, k = idx.shape
+            counts = torch.empty((self._index.n_ref, k), dtype=torch.int64, device=idx.device)
+            max_dist = torch.empty((self._index.n_ref,), dtype=torch.float64, device=idx.device)
+            stream = torch.cuda.current_stream(idx.device)
+            self._index.tally_from_neighbors_device(dist.data_ptr(), idx.data_ptr(), nq, k, counts.data_ptr(),
+                                                    max_dist.data_ptr(), False, stream.cuda_stream)
+            stream.synchronize()
+            return counts.cpu().numpy(), max_dist.cpu().numpy()
+        return self._index.tally_from_neighbors_host(dist, idx)
+
     def summarize_from_neighbors(self, dist, idx, weights, stat):
         """Per-target statistics (``stat``: one ``_native.STATISTICS`` code per target) of neighbours already found:
         :meth:`predict_from_neighbors` with the mean replaced column by column.  Always float64 ``(nq, t)``.  Explicit
@@ -545,7 +564,8 @@ class KNNEngine:
 
     def open_stream(self, k, *, weights=None, want_dist=True, deterministic=True, decimals=10,
                     formula="expanded", apply_affine=False, row_offset=0, check_finite=False, query_dtype=0,
-                    nodata=None, fill_index=-1, output=None, statistic=None, id_table=None, fill_id=-1, plan=None):
+                    nodata=None, fill_index=-1, output=None, statistic=None, id_table=None, fill_id=-1, plan=None,
+                    tally=False):
         """A :class:`sknnr_amd._native.QueryStream` over host tiles: ``push(tile)`` keeps the PCIe
         pipeline full across tiles and carries the global row offset.  ``weights`` (``"uniform"`` /
         ``"distance"`` / a :class:`sknnr_amd.weights.DistanceWeights` law, evaluated on the device tile by tile) also
@@ -557,7 +577,8 @@ class KNNEngine:
         neighbours (:meth:`summarize`), written where the predictions are.  ``id_table`` (int64, one dataframe id per
         reference row): the indices leave as ``id_table[idx]``, looked up on the device; keep ``fill_index`` negative,
         and masked rows get ``fill_id``.  ``plan``: an output plan ``(cols, codes, params)`` instead of ``statistic``; the
-        prediction lane then holds its ``n_out`` planes (:meth:`summarize_plan`)."""
+        prediction lane then holds its ``n_out`` planes (:meth:`summarize_plan`).  ``tally``: every tile's neighbours are
+        tallied on the device (:meth:`sknnr_amd._native.QueryStream.set_tally`); ``stream.tally()`` reads the result."""
         want_pred = weights is not None
         law = self.weight_law(weights)  # (a distance-weight law: every tile's weights are made on the device)
         if want_pred and not law and weights not in _WEIGHT_MODES:
@@ -574,7 +595,8 @@ class KNNEngine:
         if plan is not None and statistic is not None:
             raise ValueError("a stream takes statistic or an output plan, not both")
         return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred, nodata=nodata, fill_index=fill_index,
-                                       output=output, statistic=statistic, id_table=id_table, fill_id=fill_id, plan=plan)
+                                       output=output, statistic=statistic, id_table=id_table, fill_id=fill_id, plan=plan,
+                                       tally=tally)
 
     def hamming_distances(self, X, rows=None):
         """Full weighted-Hamming distance rows of ``X[rows]`` (``X`` None: of the fitted rows) from the device."""

@@ -120,6 +120,10 @@ EXPORTED_SYMBOLS = (
     "sknnr_stream_set_id_table",
     "sknnr_stream_push_typed",
     "sknnr_stream_push_planes_typed",
+    "sknnr_tally_from_neighbors",
+    "sknnr_stream_set_tally",
+    "sknnr_stream_get_tally",
+    "sknnr_debug_last_tally",
     "sknnr_debug_last_narrow",
     "sknnr_debug_last_mask",
     "sknnr_debug_mask_compact",
@@ -138,6 +142,16 @@ EXPORTED_SYMBOLS = (
     "sknnr_debug_image_constants",
     "sknnr_debug_search_plan",
 )
+
+
+# geometry of the neighbour-usage kernel (sknnr_amd/csrc/tally.hip.h: kTallyWgEntries, tally_rows_per_wg); the table's
+# slots come from the library itself (Index.debug_last_tally()["slots"])
+TALLY_WG_ENTRIES = 8192
+
+
+def tally_rows_per_workgroup(k: int) -> int:
+    """Consecutive rows one workgroup of the tally kernel takes at ``k`` neighbours."""
+    return 1 if k >= TALLY_WG_ENTRIES else TALLY_WG_ENTRIES // int(k)
 
 
 class QueryOpts(ctypes.Structure):
@@ -285,6 +299,11 @@ def load(build_if_missing: bool = False):
         lib.sknnr_index_set_groups.argtypes = [vp, vp, c_int64]
         lib.sknnr_kneighbors_grouped.argtypes = [vp, c_int64, POINTER(QueryOpts), vp, vp, c_int32, vp]
         lib.sknnr_debug_last_grouped.argtypes = [vp, POINTER(c_int64)]
+    if hasattr(lib, "sknnr_tally_from_neighbors"):  # (likewise)
+        lib.sknnr_tally_from_neighbors.argtypes = [vp, vp, vp, c_int64, c_int32, vp, vp, c_int32, c_int32, vp]
+        lib.sknnr_stream_set_tally.argtypes = [vp]
+        lib.sknnr_stream_get_tally.argtypes = [vp, vp, vp]
+        lib.sknnr_debug_last_tally.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_shard_candidates.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int64, vp, vp, c_int32, vp]
     lib.sknnr_merge_shards.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int32, vp, vp, vp, vp, c_int32, vp]
     lib.sknnr_crosswalk.argtypes = [vp, c_int64, vp, c_int64, vp, c_int32, c_int32, vp]
@@ -516,7 +535,7 @@ class Index:
         check(load().sknnr_check_finite(self.handle, c_void_p(stream or None)))
 
     def open_stream(self, opts: QueryOpts, want_dist=True, want_pred=False, nodata=None, fill_index=-1,
-                    output=None, statistic=None, id_table=None, fill_id=-1, plan=None) -> "QueryStream":
+                    output=None, statistic=None, id_table=None, fill_id=-1, plan=None, tally=False) -> "QueryStream":
         """``nodata``: float64 ``(d_in,)``, one value per column of the pushed rows -- every tile is then masked on the
         device (sknnr_stream_set_nodata) and masked rows get ``fill_index`` / NaN.  ``output``: keyword arguments of
         :meth:`QueryStream.set_output` -- the results then leave the device at those types.  ``statistic``: one
@@ -524,7 +543,7 @@ class Index:
         ``id_table`` / ``fill_id``: :meth:`QueryStream.set_id_table` -- the indices leave as those ids; ``fill_index``
         must then be negative, and masked rows get ``fill_id``.  ``plan``: an output plan ``(cols, codes, params)``
         (:meth:`QueryStream.set_plan`; not together with ``statistic``) -- the prediction lane then holds its planes, and
-        ``output``'s ``scale`` / ``offset`` one value per plane."""
+        ``output``'s ``scale`` / ``offset`` one value per plane.  ``tally``: :meth:`QueryStream.set_tally`."""
         stream = QueryStream(self, opts, want_dist, want_pred)
         try:
             if plan is not None:  # (first: it sets the width set_output's scale / offset must have)
@@ -537,6 +556,8 @@ class Index:
                 stream.set_statistics(statistic)
             if id_table is not None:
                 stream.set_id_table(id_table, fill_id)
+            if tally:
+                stream.set_tally()
         except Exception:
             stream.close()
             raise
@@ -577,6 +598,53 @@ class Index:
                                                   _host_ptr(w), nq, k, int(weight_mode),
                                                   _host_ptr(pred), MEM_HOST, None))
         return pred
+
+    # ---- neighbour usage (include/sknnr_hip.h, "Neighbour usage") ----------------------------
+    def tally_from_neighbors_host(self, dist, idx, counts=None, max_dist=None):
+        """Per-row use counts of ``idx`` ``(nq, k)`` int64 and, with ``dist``, the largest distance per reference row
+        (sknnr_tally_from_neighbors on host arrays).  ``counts`` ``(n_ref, k)`` int64 / ``max_dist`` ``(n_ref,)`` float64:
+        arrays to ADD to (``accumulate = 1``); None: fresh ones.  ``dist`` None: counts only, and ``max_dist`` comes back
+        None.  Entries outside ``[0, n_ref)`` are skipped.  Returns ``(counts, max_dist)``."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        if idx.ndim != 2:
+            raise ValueError("idx must be (nq, k)")
+        nq, k = idx.shape
+        dist = _c_f64(dist)
+        if dist is not None and dist.shape != idx.shape:
+            raise ValueError(f"dist must have the shape of idx {idx.shape}, got {dist.shape}")
+        accumulate = counts is not None
+        if accumulate:
+            if counts.dtype != np.int64 or counts.shape != (self.n_ref, k) or not counts.flags.c_contiguous:
+                raise ValueError(f"counts must be C-contiguous int64 ({self.n_ref}, {k})")
+            if dist is not None and (max_dist is None or max_dist.dtype != np.float64 or max_dist.shape != (self.n_ref,)
+                                     or not max_dist.flags.c_contiguous):
+                raise ValueError(f"max_dist must be C-contiguous float64 ({self.n_ref},)")
+        else:
+            counts = np.empty((self.n_ref, k), dtype=np.int64)
+            max_dist = np.empty(self.n_ref, dtype=np.float64) if dist is not None else None
+        if dist is None:
+            max_dist = None
+        check(load().sknnr_tally_from_neighbors(self.handle, _host_ptr(dist), _host_ptr(idx), nq, k, _host_ptr(counts),
+                                                _host_ptr(max_dist), int(accumulate), MEM_HOST, None))
+        return counts, max_dist
+
+    def tally_from_neighbors_device(self, dist_ptr, idx_ptr, nq, k, counts_ptr, max_dist_ptr=0, accumulate=False, stream=0):
+        """sknnr_tally_from_neighbors on device pointers: enqueues on ``stream`` and returns; ``dist_ptr`` and
+        ``max_dist_ptr`` both 0 for counts only."""
+        check(load().sknnr_tally_from_neighbors(self.handle, c_void_p(dist_ptr or None), c_void_p(idx_ptr or None), int(nq),
+                                                int(k), c_void_p(counts_ptr or None), c_void_p(max_dist_ptr or None),
+                                                int(bool(accumulate)), MEM_DEVICE, c_void_p(stream or None)))
+
+    TALLY_FIELDS = ("ran", "rows", "k", "tallied", "skipped", "global_atomics", "overflowed", "slots")
+
+    def debug_last_tally(self) -> dict:
+        """Debug only (sknnr_debug_last_tally; synchronises the device): the last :meth:`tally_from_neighbors_host` /
+        ``_device`` call, or the open tallying stream so far -- ran, rows, k, entries tallied, entries skipped (outside
+        ``[0, n_ref)``), global atomics issued on the accumulators, entries that found no slot in their workgroup's table,
+        and the slots of that table."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_tally(self.handle, out))
+        return dict(zip(self.TALLY_FIELDS, (int(v) for v in out)))
 
     # ---- per-target neighbour summaries (include/sknnr_hip.h) --------------------------------
     def summarize_host(self, q, opts: QueryOpts, stat, nq=None):
@@ -963,6 +1031,7 @@ class QueryStream:
         self.idx_dtype, self.dist_dtype, self.pred_dtype = np.dtype(np.int64), np.dtype(np.float64), np.dtype(np.float64)
         self._typed = False
         self.pred_cols = index.t  # columns of the prediction lane (set_plan widens it)
+        self._tally = False
         check(load().sknnr_stream_begin(index.handle, byref(opts), int(self.want_dist), int(self.want_pred),
                                         byref(self._h)))
 
@@ -1075,6 +1144,22 @@ class QueryStream:
         ``fill_index`` of a nodata mask) as ``fill_id`` -- in the stream's index type, whose range they must fit."""
         table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1)
         check(load().sknnr_stream_set_id_table(self._h, _host_ptr(table), int(table.size), int(fill_id)))
+
+    def set_tally(self):
+        """Tally every tile's neighbours on the device (sknnr_stream_set_tally; only before the first push): per
+        reference row and rank the rows it served, and its largest distance -- over valid rows only under a nodata
+        mask.  What the pushes deliver is unchanged; :meth:`tally` reads the accumulators."""
+        check(load().sknnr_stream_set_tally(self._h))
+        self._tally = True
+
+    def tally(self):
+        """Flush, then ``(counts, max_dist)`` of everything pushed so far (sknnr_stream_get_tally): ``(n_ref, k)`` int64
+        and ``(n_ref,)`` float64, 0.0 where a row was never used.  The accumulators keep running."""
+        counts = np.empty((self._index.n_ref, self.k), dtype=np.int64)
+        max_dist = np.empty(self._index.n_ref, dtype=np.float64)
+        check(load().sknnr_stream_get_tally(self._h, _host_ptr(counts), _host_ptr(max_dist)))
+        self._keep.clear()
+        return counts, max_dist
 
     def valid_rows(self) -> int:
         """Valid (unmasked) rows submitted so far; without a nodata mask, the rows pushed."""

@@ -1,9 +1,9 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_tally.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
-// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS), templates where they are instantiated.
+// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS / SKNNR_KERNELS_TALLY), templates where they are instantiated.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +21,7 @@
 #include "planes.hip.h"
 #include "rescue.hip.h"
 #include "summary.hip.h"
+#include "tally.hip.h"
 #include "weights.hip.h"
 
 namespace sknnr {
@@ -100,6 +101,15 @@ hipError_t weight_law(const WeightLawArgs& a, hipStream_t st);
 // reference rows [a.s.row_offset, + a.s.nq) against all rows of other groups; `blocks` workgroups take the passes grid-stride;
 // chunked: d > kScanColChunk
 hipError_t group_scan(int formula, bool chunked, const GroupScanArgs& a, long blocks, size_t lds_bytes, hipStream_t st);
+
+// ---- k_tally.hip: neighbour usage (tally.hip.h) -----------------------------------------------------------------------------
+// adds the a.n rows into a.cnt / a.maxbits / a.rec (none of them zeroed here); hipErrorInvalidValue for n_ref * k >= 2^32,
+// for distances without maxima (or the reverse) and for null accumulators
+hipError_t tally(const TallyArgs& a, hipStream_t st);
+bool tally_wide_ok(const TallyArgs& a);  // that launch loads 16 bytes per lane
+long tally_blocks(long n, int k);        // its workgroups
+// every value of max_dist that is not > 0 becomes +0.0 (accumulate = 1 on a caller's array)
+hipError_t tally_clean(double* max_dist, long n, hipStream_t st);
 
 // ---- k_coarse1.hip / k_coarse2.hip: the MFMA pre-filters ----------------------------------------------------------------
 struct Coarse1Launch {

@@ -493,6 +493,12 @@ struct sknnr_index {
     double law_p0 = 0.0, law_p1 = 0.0;
     DevBuf<double> law_w;
     int64_t last_law[8] = {};
+    // neighbour usage (tally.hip.h): the open stream's accumulators (sknnr_stream_set_tally), the kernels' device record --
+    // words [0, 4) of one-shot calls, [4, 8) of the open stream -- and the host's half of sknnr_debug_last_tally: ran, rows,
+    // k; last_tally_half: which device words belong to it
+    DevBuf<unsigned long long> s_tally_cnt, s_tally_max, tally_rec;
+    int64_t last_tally[3] = {};
+    int last_tally_half = 0;
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
     // a ring of call records so that several calls of one benchmark step are summed, not only the last.
@@ -2193,6 +2199,8 @@ int run_forest(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
 // ----------------------------------------------------------------------------------------
 static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, const double* w, long nq, int k,
                           int mode, int law, double* out, hipStream_t st);
+// n rows of a tile of the open stream into the handle's accumulators (sknnr_stream_set_tally), on `st` behind their search
+static int tally_tile(sknnr_index* ix, const double* dist, const long* idx, long n, int k, hipStream_t st);
 
 // The plan of the call in progress for as long as the scope lives; the caller holds ix->mtx.
 struct SummaryScope {
@@ -2263,8 +2271,10 @@ int mask_compact(MaskBufs& m, const void* x, long n, size_t row_bytes, hipStream
 // The search of a masked tile whose valid count nv the host knows, on `st`: in place when every row is valid, nothing but
 // the fill when none is, else on the packed rows (mask_compact has run, on `st` or in front of an event `st` waits for) and
 // expanded.  o->row_offset counts the valid rows in front of the tile.  d_pred: also predict; d_dist / d_idx may be null.
+// tally (a stream's tile; d_dist is given): the valid rows' neighbours are tallied where the search wrote them -- the whole
+// tile in place, or the packed rows -- never the expanded ones: a caller's fill_index need not be negative.
 int mask_finish(sknnr_index* ix, MaskBufs& m, const void* x, long n, long nv, const sknnr_query_opts* o, long fill_index,
-                double* d_dist, long* d_idx, double* d_pred, long valid_so_far, hipStream_t st) {
+                double* d_dist, long* d_idx, double* d_pred, long valid_so_far, hipStream_t st, bool tally = false) {
     const int k = o->n_neighbors, t = pred_cols(ix);  // (the prediction rows' width: the plan's entries, or the targets)
     const size_t row_bytes = (size_t)query_cols(ix, o) * dtype_bytes(o->query_dtype);
     int rc;
@@ -2272,12 +2282,14 @@ int mask_finish(sknnr_index* ix, MaskBufs& m, const void* x, long n, long nv, co
         double* dd = d_dist ? d_dist : (d_pred ? m.cd.p : nullptr);
         long* di = d_idx ? d_idx : m.ci.p;
         if ((rc = run_device(ix, x, n, o, dd, di, st))) return rc;
+        if (tally && (rc = tally_tile(ix, dd, di, n, k, st))) return rc;
         if (d_pred && (rc = launch_predict(ix, dd, di, nullptr, n, k, o->weight_mode, o->weight_law, d_pred, st))) return rc;
     } else {
         ExpandArgs e{};
         if (nv > 0) {
             double* cd = (d_dist || d_pred) ? m.cd.p : nullptr;
             if ((rc = run_device(ix, m.cx.p, nv, o, cd, m.ci.p, st))) return rc;
+            if (tally && (rc = tally_tile(ix, cd, m.ci.p, nv, k, st))) return rc;
             if (d_pred && (rc = launch_predict(ix, cd, m.ci.p, nullptr, nv, k, o->weight_mode, o->weight_law, m.cp.p, st))) return rc;
             e.valid = m.valid.p;
             e.rank = m.rank.p;
@@ -2433,7 +2445,8 @@ struct HostPipe {
         // the lane leaves through the conversion kernel, from its narrow buffer: typed, or the index lane with a table
         bool converts() const { return dtype != 0 || table != nullptr; }
     } lane[kLanes];
-    bool mask_dist = false;  // the masked path is handed the distance buffer: distances leave, or the reduction reads them
+    bool mask_dist = false;  // the masked path is handed the distance buffer: distances leave, or the reduction or the tally reads them
+    bool tally = false;      // every tile's neighbours are tallied into the handle's s_tally_cnt / s_tally_max (sknnr_stream_set_tally)
     size_t x_esz = sizeof(double);  // bytes per element of the caller's rows (opts->query_dtype)
     // nodata front end: every tile is masked behind its host-to-device copy, and o.row_offset advances by its VALID rows
     const double* nodata_dev = nullptr;  // (d_x) on the device, or null: no mask
@@ -2543,7 +2556,7 @@ int pipe_prepare_slot(HostPipe& p, int b, long n, bool planes = false) {
         if (ln.want && ln.converts()) HIP_TRY(sb.nar.ensure(units));
         if (ln.want && !ln.converts() && planes) HIP_TRY(sb.planes.ensure(wide));  // (the untyped results as planes)
     }
-    if (p.nodata_dev && (rc = mask_ensure(sl.mask, n, (size_t)p.d_x * p.x_esz, p.k, p.lane[kLanePred].cols, p.lane[kLaneDist].want, p.lane[kLanePred].want)))
+    if (p.nodata_dev && (rc = mask_ensure(sl.mask, n, (size_t)p.d_x * p.x_esz, p.k, p.lane[kLanePred].cols, p.mask_dist, p.lane[kLanePred].want)))
         return rc;
     return SKNNR_OK;
 }
@@ -2669,11 +2682,12 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     if (p.nodata_dev) {
         // (distances only where the slot has packed distances to expand from: mask_ensure sizes them by the same rule)
         rc = mask_finish(ix, sl.mask, sl.dev_x.p, n, nv, &p.o, p.fill_index, p.mask_dist ? dist.f64() : nullptr, idx.i64(),
-                         want_pred ? pred.f64() : nullptr, p.o.row_offset - p.row_offset0, ix->st_run);
+                         want_pred ? pred.f64() : nullptr, p.o.row_offset - p.row_offset0, ix->st_run, p.tally);
         if (rc) return rc;
     } else {
         rc = run_device(ix, sl.dev_x.p, n, &p.o, dist.f64(), idx.i64(), ix->st_run);
         if (rc) return rc;
+        if (p.tally && (rc = tally_tile(ix, dist.f64(), idx.i64(), n, k, ix->st_run))) return rc;
         if (want_pred) {
             rc = launch_predict(ix, dist.f64(), idx.i64(), nullptr, n, k, p.o.weight_mode, p.o.weight_law, pred.f64(), ix->st_run);
             if (rc) return rc;
@@ -4054,6 +4068,161 @@ extern "C" int sknnr_stream_set_id_table(sknnr_stream* s, const int64_t* table, 
     il.table = p.ix->s_id_table.p;
     il.has_fill = 1;  // (every negative index of a tile is the nodata expansion's fill_index)
     il.fill_id = fill_id;
+    return SKNNR_OK;
+}
+
+// ---- neighbour usage (tally.hip.h) ------------------------------------------------------------------------------------
+// One launch into cnt / maxbits on `st`; `half`: the device record's words it adds to (0 one-shot calls, 1 the open stream).
+static int launch_tally(sknnr_index* ix, const double* dist, const long* idx, long n, int k, unsigned long long* cnt,
+                        unsigned long long* maxbits, int half, hipStream_t st) {
+    TallyArgs a{};
+    a.idx = idx;
+    a.dist = maxbits ? dist : nullptr;
+    a.n = n;
+    a.k = k;
+    a.n_ref = ix->n_ref;
+    a.cnt = cnt;
+    a.maxbits = maxbits;
+    a.rec = ix->tally_rec.p + half * kTallyRecWords;
+    HIP_TRY(launch::tally(a, st));
+    return SKNNR_OK;
+}
+
+static int tally_tile(sknnr_index* ix, const double* dist, const long* idx, long n, int k, hipStream_t st) {
+    if (!dist) return fail(SKNNR_ERR_INVALID, "a tallied tile needs its distances");
+    const int rc = launch_tally(ix, dist, idx, n, k, ix->s_tally_cnt.p, ix->s_tally_max.p, 1, st);
+    if (rc) return rc;
+    ix->last_tally[0] = 1;
+    ix->last_tally[1] += n;
+    ix->last_tally[2] = k;
+    ix->last_tally_half = 1;
+    return SKNNR_OK;
+}
+
+static int tally_check_shape(const sknnr_index* ix, int32_t k) {
+    if (k < 1) return fail(SKNNR_ERR_INVALID, "k must be >= 1");
+    if ((double)ix->n_ref * (double)k >= 4294967296.0)
+        return fail(SKNNR_ERR_UNSUPPORTED, "n_ref * k = %lld * %d does not fit the tally's 32-bit keys", (long long)ix->n_ref, k);
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_tally_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, int64_t nq, int32_t k,
+                                          int64_t* counts, double* max_dist, int32_t accumulate, int32_t mem, void* stream) {
+    if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    int rc = tally_check_shape(ix, k);
+    if (rc) return rc;
+    if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
+    if (nq > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 rows in one call");
+    if (!counts) return fail(SKNNR_ERR_INVALID, "counts is NULL");
+    if (!idx && nq > 0) return fail(SKNNR_ERR_INVALID, "idx is NULL");
+    if (!dist != !max_dist) return fail(SKNNR_ERR_INVALID, "dist and max_dist come together (both NULL: counts only)");
+    if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    const size_t n_cnt = (size_t)ix->n_ref * k, n_max = (size_t)ix->n_ref, n_el = (size_t)nq * k;
+    hipStream_t st = mem == SKNNR_MEM_DEVICE ? (hipStream_t)stream : nullptr;
+    HIP_TRY(ix->tally_rec.ensure(2 * kTallyRecWords));
+    HIP_TRY(hipMemsetAsync(ix->tally_rec.p, 0, kTallyRecWords * sizeof(unsigned long long), st));
+    ix->last_tally[0] = nq > 0 ? 1 : 0;
+    ix->last_tally[1] = nq;
+    ix->last_tally[2] = k;
+    ix->last_tally_half = 0;
+    // (int64 counts and float64 maxima ARE the accumulators: the same 8-byte patterns)
+    unsigned long long* cnt = (unsigned long long*)counts;
+    unsigned long long* mx = (unsigned long long*)max_dist;
+    const long* di = (const long*)idx;
+    const double* dd = dist;
+    DevBuf<unsigned long long> dcnt, dmax;  // (host memory: freed by their destructors on every return path)
+    DevBuf<long> didx;
+    DevBuf<double> ddist;
+    if (mem == SKNNR_MEM_HOST) {
+        HIP_TRY(dcnt.ensure(n_cnt));
+        if (max_dist) HIP_TRY(dmax.ensure(n_max));
+        HIP_TRY(didx.ensure(n_el));
+        if (dist) HIP_TRY(ddist.ensure(n_el));
+        if (n_el) HIP_TRY(hipMemcpy(didx.p, idx, n_el * sizeof(long), hipMemcpyHostToDevice));
+        if (n_el && dist) HIP_TRY(hipMemcpy(ddist.p, dist, n_el * sizeof(double), hipMemcpyHostToDevice));
+        if (accumulate) {
+            HIP_TRY(hipMemcpy(dcnt.p, counts, n_cnt * 8, hipMemcpyHostToDevice));
+            if (max_dist) HIP_TRY(hipMemcpy(dmax.p, max_dist, n_max * 8, hipMemcpyHostToDevice));
+        }
+        cnt = dcnt.p;
+        mx = max_dist ? dmax.p : nullptr;
+        di = didx.p;
+        dd = dist ? ddist.p : nullptr;
+    }
+    if (!accumulate) {
+        HIP_TRY(hipMemsetAsync(cnt, 0, n_cnt * 8, st));
+        if (mx) HIP_TRY(hipMemsetAsync(mx, 0, n_max * 8, st));
+    } else if (mx) {
+        HIP_TRY(launch::tally_clean((double*)mx, (long)n_max, st));
+    }
+    if ((rc = launch_tally(ix, dd, di, nq, k, cnt, mx, 0, st))) return rc;
+    if (mem == SKNNR_MEM_HOST) {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpy(counts, dcnt.p, n_cnt * 8, hipMemcpyDeviceToHost));
+        if (max_dist) HIP_TRY(hipMemcpy(max_dist, dmax.p, n_max * 8, hipMemcpyDeviceToHost));
+    }
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_set_tally(sknnr_stream* s) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    HostPipe& p = s->pipe;
+    sknnr_index* ix = p.ix;
+    const int rc = tally_check_shape(ix, p.k);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_tally is allowed only before the first push");
+    HIP_TRY(hipSetDevice(ix->device));
+    const size_t n_cnt = (size_t)ix->n_ref * p.k, n_max = (size_t)ix->n_ref;
+    HIP_TRY(ix->s_tally_cnt.ensure(n_cnt));
+    HIP_TRY(ix->s_tally_max.ensure(n_max));
+    HIP_TRY(ix->tally_rec.ensure(2 * kTallyRecWords));
+    // (on the stream every tile's tally runs on: zeroed in front of the first of them)
+    HIP_TRY(hipMemsetAsync(ix->s_tally_cnt.p, 0, n_cnt * 8, ix->st_run));
+    HIP_TRY(hipMemsetAsync(ix->s_tally_max.p, 0, n_max * 8, ix->st_run));
+    HIP_TRY(hipMemsetAsync(ix->tally_rec.p + kTallyRecWords, 0, kTallyRecWords * sizeof(unsigned long long), ix->st_run));
+    p.tally = true;
+    p.mask_dist = true;  // the masked path keeps the search's distances whether or not they leave
+    ix->last_tally[0] = ix->last_tally[1] = 0;
+    ix->last_tally[2] = p.k;
+    ix->last_tally_half = 1;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_get_tally(sknnr_stream* s, int64_t* counts, double* max_dist) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    HostPipe& p = s->pipe;
+    sknnr_index* ix = p.ix;
+    if (!p.tally) return fail(SKNNR_ERR_INVALID, "the stream tallies nothing: sknnr_stream_set_tally was not called");
+    if (!counts && !max_dist) return fail(SKNNR_ERR_INVALID, "counts and max_dist are both NULL");
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    const int rc = pipe_flush(p);
+    if (rc) return pipe_fail(p, rc);
+    HIP_TRY(hipStreamSynchronize(ix->st_run));
+    if (counts) HIP_TRY(hipMemcpy(counts, ix->s_tally_cnt.p, (size_t)ix->n_ref * p.k * 8, hipMemcpyDeviceToHost));
+    if (max_dist) HIP_TRY(hipMemcpy(max_dist, ix->s_tally_max.p, (size_t)ix->n_ref * 8, hipMemcpyDeviceToHost));
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_tally(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::fill(out, out + 8, 0);
+    std::copy(ix->last_tally, ix->last_tally + 3, out);
+    out[7] = kTallySlots;
+    if (!ix->tally_rec.p) return SKNNR_OK;
+    unsigned long long w[kTallyRecWords];
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(w, ix->tally_rec.p + ix->last_tally_half * kTallyRecWords, sizeof w, hipMemcpyDeviceToHost));
+    out[3] = (int64_t)w[kTallyRecTallied];
+    out[4] = (int64_t)w[kTallyRecSkipped];
+    out[5] = (int64_t)w[kTallyRecAtomics];
+    out[6] = (int64_t)w[kTallyRecOverflow];
     return SKNNR_OK;
 }
 
