@@ -760,6 +760,72 @@ int sknnr_stream_set_tally(sknnr_stream* stream);
 int sknnr_stream_get_tally(sknnr_stream* stream, int64_t* counts, double* max_dist);
 int sknnr_debug_last_tally(const sknnr_index* index, int64_t out[8]);
 
+/* ---- zonal statistics (summaries of the map over stands, ownerships, counties ...) ---------------- */
+
+/*
+ * Zonal statistics.  THE CONTRACT, stated here once (sknnr_amd/csrc/zonal.hip.h implements it, tests/_zonal.py restates
+ * it in numpy).  Inputs per tallied tile: a float64 value tile (n, c) -- the prediction lane as computed: c = t targets, or
+ * the n_out planes of an output plan; zones (n) int32; and the prediction lane's conversion: an integer dst_dtype
+ * (SKNNR_DTYPE_I16 / U16 / U8 / I32) with per-column scale / offset or neither.
+ * For pixel i, column j: q = the typed output's stored value of v[i, j] (x = v * scale[j] + offset[j] as two roundings,
+ * rint, clamp, cast: "typed outputs" above, the same device function) WITHOUT the fill.  NaN is tested first, on v: a NaN
+ * entry contributes nothing -- a nodata pixel, counted in the record -- whatever fill the stream has, and even though a
+ * valid pixel's stored value may come to equal the fill.  (A v that is not NaN whose x is -- inf * 0 -- stores 0.)
+ * A zone code < 0 or >= n_zones skips the whole pixel: counted in the record, never dereferenced, and its entries are
+ * counted neither as tallied nor as NaN.
+ * Accumulators, all int64, C order:
+ *   acc[z, j, 0..5]  (n_zones, c, 6): count, sum = sum of q, sq_lo = sum of (q^2 mod 2^32), sq_hi = sum of (q^2 >> 32),
+ *                    min, max.  The sum of squares is sq_hi * 2^32 + sq_lo: exact for every accepted type up to 2^31
+ *                    pixels per zone (int32 outputs make the two limbs necessary).  min / max start at INT64_MAX /
+ *                    INT64_MIN and stay there where count == 0.
+ *   hist             for every column j with n_classes[j] > 0 (a class plane, e.g. a `mode` statistic) a block
+ *                    (n_zones, n_classes[j]); the blocks are concatenated in column order.  hist_j[z, q] counts the
+ *                    pixels with 0 <= q < n_classes[j]; a q outside that range is counted in the record as "other".
+ *                    Numeric columns have n_classes[j] == 0 and no block; class planes also get their acc entries.
+ * Every accumulator is an integer add, min or max: the results do not depend on launch geometry, tile cuts or arrival
+ * order, two runs produce the same bytes, and they equal what a zonal-statistics tool computes from the written raster.
+ * Sums of the float predictions are deliberately absent: a float atomic sum depends on arrival order.
+ * Refused with SKNNR_ERR_UNSUPPORTED before any device work: n_zones * c >= 2^32, and n_zones * max(n_classes) >= 2^32
+ * (the kernel's keys are 32 bits); and n_zones > 2^31 - 1 with c == 1 (zone codes are int32).
+ *
+ * sknnr_zonal_from_values: one-shot.  values (n, c), zones (n), acc and hist live in `mem` (host arrays are staged; device
+ *   arrays are used in place, enqueued on `stream`); scale, offset (c each, or both NULL) and n_classes (c, or NULL: no
+ *   class planes) are always HOST arrays.  accumulate = 0 initialises acc / hist first, the min / max sentinels included;
+ *   accumulate = 1 adds to what they hold.  hist may be NULL when no column has classes.  n == 0 is allowed.  The handle
+ *   gives the record and the staging buffers only: neither its rows nor its targets are read.
+ * sknnr_stream_set_zonal: allowed only before the first push, on a stream opened with predictions, and after
+ *   sknnr_stream_set_plan when there is a plan (n_classes holds one value per column of the prediction lane, or is NULL).
+ *   Allocates and initialises the accumulators on the handle.  From then on every tile's float64 prediction tile -- the
+ *   full layout, where masked rows are NaN -- is tallied on the device behind its reduction, whether or not the push asks
+ *   for the predictions, for row, plane and typed pushes alike.  What the pushes deliver is unchanged, bit for bit.  A
+ *   stream on which it is never called enqueues exactly what it did before the entry point existed.
+ * sknnr_stream_next_zones: a HOST int32 array, reusable on return, holding the zone codes of the NEXT push: one plane,
+ *   in pixel order, in either layout.  A push on a zonal stream without it, or with another nq than it gave, is
+ *   SKNNR_ERR_INVALID, and so is a prediction lane without an integer pred_dtype (sknnr_stream_set_output) at the push.
+ *   nq == 0 is accepted and ignored, as a push of no rows is.
+ * sknnr_stream_get_zonal: flushes the pipeline (as sknnr_stream_flush) and copies the accumulators to HOST arrays (either
+ *   may be NULL; hist only where a column has classes).  May be called more than once; the accumulators keep running.
+ * sknnr_debug_last_zonal: debug only; synchronises the device.  The last sknnr_zonal_from_values call, or -- after
+ *   sknnr_stream_set_zonal -- the stream so far:
+ *   out[0] 1 = a zonal kernel ran          out[1] pixels given to it        out[2] c
+ *   out[3] entries tallied                 out[4] NaN entries               out[5] pixels outside [0, n_zones)
+ *   out[6] class values outside [0, n_classes[j])
+ *   out[7] global atomics issued on the accumulators.  (The kernels' sixth counter, entries that found no slot in their
+ *          workgroup's table and went to the accumulators directly, does not fit eight words: such entries show here,
+ *          five or six atomics each, beyond what a flush of every slot can issue.)
+ * sknnr_debug_zonal_geometry: no device work.  out[0] pixels a workgroup takes at c columns, out[1] slots of its table,
+ *   out[2] slots of its class table, out[3] slots an entry probes.
+ */
+int sknnr_zonal_from_values(sknnr_index* index, const double* values, const int32_t* zones, int64_t n, int32_t c,
+                            int32_t dst_dtype, const double* scale, const double* offset, int64_t n_zones,
+                            const int32_t* n_classes, int64_t* acc, int64_t* hist, int32_t accumulate, int32_t mem,
+                            void* stream);
+int sknnr_stream_set_zonal(sknnr_stream* stream, int64_t n_zones, const int32_t* n_classes);
+int sknnr_stream_next_zones(sknnr_stream* stream, const int32_t* zones, int64_t nq);
+int sknnr_stream_get_zonal(sknnr_stream* stream, int64_t* acc, int64_t* hist);
+int sknnr_debug_last_zonal(const sknnr_index* index, int64_t out[8]);
+int sknnr_debug_zonal_geometry(int32_t c, int64_t out[4]);
+
 /*
  * Debug only.  The output side of the last tile the handle's host pipeline submitted, so that a test can prove that the
  * device converted it and that only the narrow bytes were copied.  Host memory, no device work:

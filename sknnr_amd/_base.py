@@ -28,6 +28,7 @@ from sklearn.utils.validation import _is_arraylike, check_is_fitted, validate_da
 from . import _config, _native
 from ._engine import KNNEngine, default_device, is_torch_cuda_tensor
 from ._usage import NeighborUsage
+from ._zonal import ZonalStats
 from .weights import DistanceWeights
 
 # Element types query rows may keep on their way to the device (include/sknnr_hip.h, sknnr_dtype): the kernel that reads
@@ -309,6 +310,25 @@ def normalize_band_tile(tile, n_bands, *, forest=False, estimator="the estimator
     # (ascontiguousarray copies only a band that is strided or of another dtype; reshape of a contiguous band is a view)
     bands = [np.ascontiguousarray(b, dtype=dtype).reshape(-1) for b in bands]
     return bands, int(bands[0].shape[0])
+
+
+def normalize_zone_tile(zones, n):
+    """The zone codes of one streamed tile of ``n`` pixels -- ``(n,)``, or ``(h, w)`` in the pixels' C order -- as a
+    C-contiguous int32 ``(n,)`` array.  Any integer dtype is accepted; a value outside int32 is a ``ValueError``."""
+    zones = np.asarray(zones)
+    if zones.dtype.kind not in "iu":
+        raise ValueError(f"zones must hold integer zone codes, got {zones.dtype}")
+    if zones.size != n:
+        raise ValueError(f"zones must hold one code per pixel of its tile ({n}), got {zones.size} (shape {zones.shape})")
+    if zones.dtype != np.int32 and zones.size:
+        info = np.iinfo(np.int32)
+        if zones.min() < info.min or zones.max() > info.max:
+            raise ValueError(f"zone codes must fit int32, got values in [{zones.min()}, {zones.max()}]")
+    return np.ascontiguousarray(zones, dtype=np.int32).reshape(-1)
+
+
+_ZONES_SHORT = "zones ended before tiles: the call needs one array of zone codes per tile"
+_ZONES_LONG = "tiles ended before zones: the call needs one array of zone codes per tile"
 
 
 def _empty_row_tile(tile) -> bool:
@@ -982,7 +1002,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
     def _stream_tiles(self, tiles, validate, k, *, apply_affine, weights, return_distance,
                       use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False, output=None,
-                      statistic=None, id_table=None, fill_id=-1, neighbors=False, usage=None):
+                      statistic=None, id_table=None, fill_id=-1, neighbors=False, usage=None, zones=None, zonal=None):
         """Push host tiles through one native query stream.  Returns (dist, idx, pred) arrays over all
         pushed rows (pieces of ``out`` when given, else concatenated).  ``nodata`` (float64, one value per column of the
         validated tiles): rows holding one are masked on the device and get ``fill_index`` / NaN.
@@ -1005,10 +1025,21 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         collected and concatenated.
 
         ``usage`` (a :class:`sknnr_amd.NeighborUsage`): the stream tallies every tile's neighbours on the device and the
-        call adds the result to it; nothing else about the call changes."""
+        call adds the result to it; nothing else about the call changes.
+
+        ``zones`` / ``zonal`` (an iterable in lockstep with ``tiles``, a :class:`sknnr_amd.ZonalStats`; predictions with
+        an integer ``pred_dtype`` only): the stream tallies every tile's predictions by zone on the device and the call
+        adds the result to ``zonal``; nothing else about the call changes."""
         if usage is not None:
             self._check_stream_supported("usage is")
             usage._check(self.n_samples_fit_, k)  # (a mismatch is refused before any device work)
+        zonal_binding = None
+        if zonal is not None:
+            self._check_stream_supported("zonal is")
+            plan_ = statistic if isinstance(statistic, OutputPlan) else None
+            zonal_binding = zonal._check(self._n_targets() if plan_ is None else plan_.n_out, (output or {}).get("pred_dtype"),
+                                         (output or {}).get("scale"), (output or {}).get("offset"))
+            zones = iter(zones)
         if output:
             self._check_stream_supported("typed outputs are")
         eng = self.engine_
@@ -1067,6 +1098,11 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 if is_torch_cuda_tensor(tile):
                     raise TypeError("streamed tiles are host arrays (they travel through the pinned "
                                     "PCIe pipeline); pass CUDA tensors to kneighbors() / predict()")
+                if zonal is not None:  # (in lockstep: a skipped empty tile consumes its entry too)
+                    try:
+                        tile_zones = next(zones)
+                    except StopIteration:
+                        raise ValueError(_ZONES_SHORT) from None
                 if not bands and _empty_row_tile(tile):
                     continue
                 if bands:  # (``tile``: the list of 1-D bands; ``first`` stands for its element type)
@@ -1090,7 +1126,9 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              nodata=nodata, fill_index=fill_index, output=output,
                                              **(dict(statistic=statistic) if plan is None else dict(plan=plan.arrays)),
                                              **({} if id_table is None else dict(id_table=id_table, fill_id=fill_id)),
-                                             **({} if usage is None else dict(tally=True)))
+                                             **({} if usage is None else dict(tally=True)),
+                                             **({} if zonal is None else
+                                                dict(zonal=(zonal.n_zones, zonal.n_classes(zonal_binding[0])))))
                 if first.dtype != stream_dtype:
                     if stream_dtype != np.float64:
                         raise ValueError(f"the tiles of one streamed call must share an element type: got {first.dtype} "
@@ -1113,6 +1151,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                          f"{cols} columns and at least {row + n} rows")
                     return w
 
+                if zonal is not None:
+                    stream.next_zones(normalize_zone_tile(tile_zones, n))
                 got = (stream.push_planes if bands else stream.push)(
                     tile, out_idx=window(o_idx, k, idx_dt),
                     out_dist=window(o_dist, k, dist_dt) if return_distance else None,
@@ -1120,14 +1160,22 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 if out is None or neighbors:
                     pieces.append(got)
                 row += n
-            tallied = None
+            if zonal is not None and next(zones, None) is not None:
+                raise ValueError(_ZONES_LONG)
+            tallied = zoned = None
             if stream is not None:
                 done, stream = stream, None
                 try:
                     if usage is not None:
                         tallied = done.tally()
+                    if zonal is not None:
+                        zoned = done.zonal()
                 finally:
                     done.close()
+            if zonal is not None:  # (only a call that came through whole is added)
+                zonal._bind(*zonal_binding)
+                if zoned is not None:
+                    zonal._add(*zoned)
             if usage is not None:  # (only a call that came through whole is added)
                 ids = getattr(self, "dataframe_index_in_", None)
                 if tallied is None:
@@ -1295,7 +1343,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
     def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
                        out_nodata=None, statistic=None, return_neighbors=False, return_distance=True,
                        return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
-                       distance_dtype=None, outputs=None, usage=None):
+                       distance_dtype=None, outputs=None, usage=None, zones=None, zonal=None):
         """``predict`` over an iterable of host tiles as one streamed call; ``out``: preallocated
         ``(n_rows, n_targets)`` float64 array (e.g. a memmap; float32 results are held exactly).  ``nodata`` as in
         :meth:`kneighbors_chunks`: masked rows are predicted NaN.  ``layout="bands"``: band-first tiles as in
@@ -1347,7 +1395,18 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
         ``usage`` (a :class:`sknnr_amd.NeighborUsage`): as in :meth:`kneighbors_chunks` -- the neighbours the predictions
         are reduced from are tallied on the device, with or without ``return_neighbors``, and the predictions are
-        bit-identical to the call without it.  Refused with callable weights and under the host-side tie policies."""
+        bit-identical to the call without it.  Refused with callable weights and under the host-side tie policies.
+
+        ``zones`` / ``zonal`` (together): ``zonal`` is a :class:`sknnr_amd.ZonalStats` and ``zones`` an iterable consumed
+        in lockstep with ``tiles`` -- per tile the integer zone codes of its pixels, ``(n,)``, or ``(h, w)`` for
+        ``layout="bands"``; any integer dtype whose values fit int32 (a skipped empty tile consumes its entry; one
+        iterable ending before the other is a ``ValueError``).  Every tile's final values are tallied by zone on the
+        device -- count, sum, sum of squares, min and max per zone and output plane, and the class counts of the planes
+        ``zonal`` names as classes -- over the STORED integers of the typed output, so an integer ``out_dtype`` is
+        required (a float atomic sum would depend on arrival order); nodata pixels and zone codes outside
+        ``[0, n_zones)`` contribute nothing.  The call adds the result to ``zonal`` and returns and writes exactly what
+        it does without it; it works with ``usage``, ``nodata``, ``outputs``, ``statistic`` and ``return_neighbors``.
+        Refused with callable weights and under the host-side tie policies."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         neighbors = self._neighbor_request(return_neighbors, return_distance, return_dataframe_index, neighbors_out,
@@ -1355,6 +1414,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         extra = {} if neighbors is None else dict(neighbors=neighbors)
         if usage is not None:
             extra["usage"] = usage
+        if zones is not None or zonal is not None:
+            extra.update(zones=zones, zonal=zonal)
         statistic = resolve_statistic(statistic, outputs, self._n_targets())
         if nodata is not None:
             nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
@@ -1365,9 +1426,10 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                     typed=(out_dtype, scale, offset, out_nodata), statistic=statistic, **extra)
 
     def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None, bands=False, typed=None,
-                        statistic=None, neighbors=None, usage=None):
+                        statistic=None, neighbors=None, usage=None, zones=None, zonal=None):
         """``neighbors``: :meth:`_neighbor_request`, or None -- predictions alone, exactly as before the keyword existed.
-        ``usage``: a :class:`sknnr_amd.NeighborUsage` the stream's tally is added to, or None."""
+        ``usage``: a :class:`sknnr_amd.NeighborUsage` the stream's tally is added to, or None.  ``zones`` / ``zonal``: the
+        tiles' zone codes and the :class:`sknnr_amd.ZonalStats` the stream's zonal tables are added to, or None both."""
         weights = "uniform" if self.weights is None else self.weights
         # A distance-weight law (sknnr_amd.weights) is evaluated on the device inside the stream, so it goes wherever
         # "distance" goes; any other callable runs on the host and keeps every refusal below.
@@ -1385,12 +1447,28 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             n_targets = plan.n_out if plan is not None else (1 if self._y.ndim == 1 else self._y.shape[1])
             # (a compact law can give an all-zero row: NaN predictions occur without any mask)
             output = normalize_typed_output(*typed, n_targets, nodata is not None or (law and weights.can_vanish))
+        zonal_extra = {}
+        if zones is not None or zonal is not None:  # (every refusal before any device work)
+            if zones is None or zonal is None:
+                raise ValueError("zones and zonal come together: the zone codes of every tile, and the ZonalStats they are "
+                                 "tallied into")
+            if not isinstance(zonal, ZonalStats):
+                raise TypeError(f"zonal must be a sknnr_amd.ZonalStats, got {type(zonal).__name__}")
+            if host_callable:
+                self._refuse_callable_weights("zonal is")
+            self._check_stream_supported("zonal is")
+            if not output or output.get("pred_dtype") is None or np.dtype(output["pred_dtype"]).kind not in "iu":
+                raise NotImplementedError("zonal needs an integer out_dtype (int16, uint16, uint8 or int32): a float atomic "
+                                          "sum is order-dependent, so zonal sums are taken over the stored integers of a "
+                                          "typed output")
+            zonal._check(plan.n_out if plan is not None else self._n_targets(), output["pred_dtype"], output.get("scale"), output.get("offset"))
+            zonal_extra = dict(zones=zones, zonal=zonal)
         if neighbors is not None:
             if host_callable:
                 self._refuse_callable_weights("return_neighbors is")
             return self._predict_chunks_neighbors(tiles, validate, weights, neighbors, apply_affine=apply_affine, out=out,
                                                   owner=owner, nodata=nodata, bands=bands, output=output,
-                                                  statistic=statistic, usage=usage)
+                                                  statistic=statistic, usage=usage, **zonal_extra)
         if host_callable and output:
             self._refuse_callable_weights("typed outputs are")
         if host_callable and bands:
@@ -1420,13 +1498,13 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                             weights=weights, return_distance=False,
                                             use_deterministic_ordering=True, out=o, owner=owner, nodata=nodata,
                                             bands=bands, output=output, statistic=statistic,
-                                            **({} if usage is None else dict(usage=usage)))
+                                            **({} if usage is None else dict(usage=usage)), **zonal_extra)
             if out is None and not output and statistic is None:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
                 pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         return pred.reshape(-1) if flat else pred
 
     def _predict_chunks_neighbors(self, tiles, validate, weights, neighbors, *, apply_affine, out, owner, nodata, bands,
-                                  output, statistic, usage=None):
+                                  output, statistic, usage=None, zones=None, zonal=None):
         """``predict_chunks(return_neighbors=True)``: one stream with all three outputs.  ``output``: the predictions'
         typed output (or None); the neighbours' types and the id table are worked out here, as ``kneighbors_chunks``
         does, every refusal before any device work."""
@@ -1445,7 +1523,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              return_distance=return_distance, use_deterministic_ordering=True, out=o,
                                              owner=owner, nodata=nodata, fill_index=-1 if ids else fill_index, bands=bands,
                                              output=merged, statistic=statistic, id_table=table, fill_id=fill_index,
-                                             neighbors=True, **({} if usage is None else dict(usage=usage)))
+                                             neighbors=True, **({} if usage is None else dict(usage=usage)),
+                                             **({} if zonal is None else dict(zones=zones, zonal=zonal)))
         if out is None and not output and statistic is None:  # (as without neighbours: float32 where scikit-learn returns it)
             pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         if self._y.ndim == 1 and not (isinstance(statistic, OutputPlan) and not statistic.per_target):
@@ -1716,14 +1795,15 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
     def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
                        out_nodata=None, statistic=None, return_neighbors=False, return_distance=True,
                        return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
-                       distance_dtype=None, outputs=None, usage=None):
+                       distance_dtype=None, outputs=None, usage=None, zones=None, zonal=None):
         """``predict`` over an iterable of untransformed host tiles as one streamed call (``nodata``: masked rows are
         predicted NaN; ``layout="bands"``: band-first tiles and predictions; ``out_dtype`` / ``scale`` / ``offset`` /
         ``out_nodata``: predictions converted on the device to the type the raster is stored in; ``statistic``: one name
         or one per target -- mean, mode, min, max, nearest, std or ("quantile", q) of the neighbours in place of the
         mean; ``outputs``: ``(target, statistic)`` pairs instead, ``n_out`` planes from the one search;
         ``return_neighbors=True`` and the neighbour keywords: ``(pred, dist, idx)`` from one search; ``usage``: a
-        :class:`sknnr_amd.NeighborUsage` the device's tally of the neighbours is added to; see
+        :class:`sknnr_amd.NeighborUsage` the device's tally of the neighbours is added to; ``zones`` / ``zonal``: the zone
+        codes of every tile and the :class:`sknnr_amd.ZonalStats` the device's zonal tables are added to; see
         :meth:`RawKNNRegressor.kneighbors_chunks` / :meth:`RawKNNRegressor.predict_chunks`)."""
         bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
@@ -1732,6 +1812,8 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         extra = {} if neighbors is None else dict(neighbors=neighbors)
         if usage is not None:
             extra["usage"] = usage
+        if zones is not None or zonal is not None:
+            extra.update(zones=zones, zonal=zonal)
         statistic = resolve_statistic(statistic, outputs, self.regressor_._n_targets())
         return self.regressor_._predict_chunks(tiles, self._band_validator(bands), apply_affine=self._map_on_device(),
                                                out=out, owner=self.transformer_, nodata=self._raw_nodata(nodata),

@@ -334,6 +334,33 @@ class KNNEngine:
             return counts.cpu().numpy(), max_dist.cpu().numpy()
         return self._index.tally_from_neighbors_host(dist, idx)
 
+    def zonal_from_values(self, values, zones, dtype, n_zones, scale=None, offset=None, n_classes=None):
+        """Zonal accumulators of values already computed (sknnr_zonal_from_values): ``values`` ``(n, c)`` float64 and
+        ``zones`` ``(n,)`` int32, numpy or torch.cuda; the sums are over the stored values of ``dtype`` (int16, uint16,
+        uint8 or int32) under ``scale`` / ``offset`` (host arrays, one value per column, or neither).  ``n_classes``: one
+        class count per column (0: numeric), or None.  Returns host arrays ``(acc, hist)``: ``(n_zones, c, 6)`` int64 and
+        the flat class blocks (None when no column has classes)."""
+        if is_torch_cuda_tensor(values):
+            import torch
+
+            values = values.to(torch.float64).contiguous()
+            zones = zones.to(device=values.device, dtype=torch.int32).contiguous().reshape(-1)
+            n, c = values.shape
+            if zones.numel() != n:
+                raise ValueError(f"zones must hold one code per pixel ({n}), got {zones.numel()}")
+            cls, per_zone = _native._zonal_classes(n_classes, c)
+            acc = torch.empty((int(n_zones), c, _native.ZONAL_FIELDS), dtype=torch.int64, device=values.device)
+            hist = torch.empty((int(n_zones) * per_zone,), dtype=torch.int64, device=values.device) if per_zone else None
+            stream = torch.cuda.current_stream(values.device)
+            self._index.zonal_from_values_device(values.data_ptr(), zones.data_ptr(), n, c, np.dtype(dtype), n_zones,
+                                                 acc.data_ptr(), hist.data_ptr() if per_zone else 0, scale=scale,
+                                                 offset=offset, n_classes=cls, accumulate=False,
+                                                 stream=stream.cuda_stream)
+            stream.synchronize()
+            return acc.cpu().numpy(), hist.cpu().numpy() if per_zone else None
+        return self._index.zonal_from_values_host(values, zones, dtype, n_zones, scale=scale, offset=offset,
+                                                  n_classes=n_classes)
+
     def summarize_from_neighbors(self, dist, idx, weights, stat):
         """Per-target statistics (``stat``: one ``_native.STATISTICS`` code per target) of neighbours already found:
         :meth:`predict_from_neighbors` with the mean replaced column by column.  Always float64 ``(nq, t)``.  Explicit
@@ -565,7 +592,7 @@ class KNNEngine:
     def open_stream(self, k, *, weights=None, want_dist=True, deterministic=True, decimals=10,
                     formula="expanded", apply_affine=False, row_offset=0, check_finite=False, query_dtype=0,
                     nodata=None, fill_index=-1, output=None, statistic=None, id_table=None, fill_id=-1, plan=None,
-                    tally=False):
+                    tally=False, zonal=None):
         """A :class:`sknnr_amd._native.QueryStream` over host tiles: ``push(tile)`` keeps the PCIe
         pipeline full across tiles and carries the global row offset.  ``weights`` (``"uniform"`` /
         ``"distance"`` / a :class:`sknnr_amd.weights.DistanceWeights` law, evaluated on the device tile by tile) also
@@ -578,7 +605,10 @@ class KNNEngine:
         reference row): the indices leave as ``id_table[idx]``, looked up on the device; keep ``fill_index`` negative,
         and masked rows get ``fill_id``.  ``plan``: an output plan ``(cols, codes, params)`` instead of ``statistic``; the
         prediction lane then holds its ``n_out`` planes (:meth:`summarize_plan`).  ``tally``: every tile's neighbours are
-        tallied on the device (:meth:`sknnr_amd._native.QueryStream.set_tally`); ``stream.tally()`` reads the result."""
+        tallied on the device (:meth:`sknnr_amd._native.QueryStream.set_tally`); ``stream.tally()`` reads the result.
+        ``zonal``: ``(n_zones, n_classes)`` -- every tile's predictions are tallied by zone on the device
+        (:meth:`sknnr_amd._native.QueryStream.set_zonal`; the stream needs an integer ``pred_dtype``); every push then
+        needs ``stream.next_zones(codes)`` first, and ``stream.zonal()`` reads the result."""
         want_pred = weights is not None
         law = self.weight_law(weights)  # (a distance-weight law: every tile's weights are made on the device)
         if want_pred and not law and weights not in _WEIGHT_MODES:
@@ -596,7 +626,7 @@ class KNNEngine:
             raise ValueError("a stream takes statistic or an output plan, not both")
         return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred, nodata=nodata, fill_index=fill_index,
                                        output=output, statistic=statistic, id_table=id_table, fill_id=fill_id, plan=plan,
-                                       tally=tally)
+                                       tally=tally, zonal=zonal)
 
     def hamming_distances(self, X, rows=None):
         """Full weighted-Hamming distance rows of ``X[rows]`` (``X`` None: of the fitted rows) from the device."""

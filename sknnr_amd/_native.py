@@ -124,6 +124,12 @@ EXPORTED_SYMBOLS = (
     "sknnr_stream_set_tally",
     "sknnr_stream_get_tally",
     "sknnr_debug_last_tally",
+    "sknnr_zonal_from_values",
+    "sknnr_stream_set_zonal",
+    "sknnr_stream_next_zones",
+    "sknnr_stream_get_zonal",
+    "sknnr_debug_last_zonal",
+    "sknnr_debug_zonal_geometry",
     "sknnr_debug_last_narrow",
     "sknnr_debug_last_mask",
     "sknnr_debug_mask_compact",
@@ -152,6 +158,30 @@ TALLY_WG_ENTRIES = 8192
 def tally_rows_per_workgroup(k: int) -> int:
     """Consecutive rows one workgroup of the tally kernel takes at ``k`` neighbours."""
     return 1 if k >= TALLY_WG_ENTRIES else TALLY_WG_ENTRIES // int(k)
+
+
+ZONAL_FIELDS = 6  # acc[z, j, :]: count, sum, sq_lo, sq_hi, min, max (include/sknnr_hip.h, "Zonal statistics")
+
+
+def zonal_geometry(c: int) -> dict:
+    """Geometry of the zonal kernel at ``c`` columns, from the library itself (sknnr_debug_zonal_geometry; no device work):
+    pixels a workgroup takes, slots of its table, slots of its class table, slots an entry probes."""
+    out = (c_int64 * 4)()
+    check(load().sknnr_debug_zonal_geometry(int(c), out))
+    return dict(zip(("pixels_per_workgroup", "slots", "hist_slots", "probes"), (int(v) for v in out)))
+
+
+def _zonal_classes(n_classes, c):
+    """``n_classes`` (None, or one count per column) as the C ABI takes it: int32 ``(c,)`` or None, and the histogram's length
+    per zone."""
+    if n_classes is None:
+        return None, 0
+    n_classes = np.ascontiguousarray(n_classes, dtype=np.int32).reshape(-1)
+    if n_classes.size != c:
+        raise ValueError(f"n_classes must hold one value per column ({c}), got {n_classes.size}")
+    if not n_classes.any():
+        return None, 0
+    return n_classes, int(n_classes.astype(np.int64).sum())
 
 
 class QueryOpts(ctypes.Structure):
@@ -304,6 +334,14 @@ def load(build_if_missing: bool = False):
         lib.sknnr_stream_set_tally.argtypes = [vp]
         lib.sknnr_stream_get_tally.argtypes = [vp, vp, vp]
         lib.sknnr_debug_last_tally.argtypes = [vp, POINTER(c_int64)]
+    if hasattr(lib, "sknnr_zonal_from_values"):  # (likewise)
+        lib.sknnr_zonal_from_values.argtypes = [vp, vp, vp, c_int64, c_int32, c_int32, vp, vp, c_int64, vp, vp, vp, c_int32,
+                                                c_int32, vp]
+        lib.sknnr_stream_set_zonal.argtypes = [vp, c_int64, vp]
+        lib.sknnr_stream_next_zones.argtypes = [vp, vp, c_int64]
+        lib.sknnr_stream_get_zonal.argtypes = [vp, vp, vp]
+        lib.sknnr_debug_last_zonal.argtypes = [vp, POINTER(c_int64)]
+        lib.sknnr_debug_zonal_geometry.argtypes = [c_int32, POINTER(c_int64)]
     lib.sknnr_shard_candidates.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int64, vp, vp, c_int32, vp]
     lib.sknnr_merge_shards.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int32, vp, vp, vp, vp, c_int32, vp]
     lib.sknnr_crosswalk.argtypes = [vp, c_int64, vp, c_int64, vp, c_int32, c_int32, vp]
@@ -535,7 +573,8 @@ class Index:
         check(load().sknnr_check_finite(self.handle, c_void_p(stream or None)))
 
     def open_stream(self, opts: QueryOpts, want_dist=True, want_pred=False, nodata=None, fill_index=-1,
-                    output=None, statistic=None, id_table=None, fill_id=-1, plan=None, tally=False) -> "QueryStream":
+                    output=None, statistic=None, id_table=None, fill_id=-1, plan=None, tally=False,
+                    zonal=None) -> "QueryStream":
         """``nodata``: float64 ``(d_in,)``, one value per column of the pushed rows -- every tile is then masked on the
         device (sknnr_stream_set_nodata) and masked rows get ``fill_index`` / NaN.  ``output``: keyword arguments of
         :meth:`QueryStream.set_output` -- the results then leave the device at those types.  ``statistic``: one
@@ -543,7 +582,8 @@ class Index:
         ``id_table`` / ``fill_id``: :meth:`QueryStream.set_id_table` -- the indices leave as those ids; ``fill_index``
         must then be negative, and masked rows get ``fill_id``.  ``plan``: an output plan ``(cols, codes, params)``
         (:meth:`QueryStream.set_plan`; not together with ``statistic``) -- the prediction lane then holds its planes, and
-        ``output``'s ``scale`` / ``offset`` one value per plane.  ``tally``: :meth:`QueryStream.set_tally`."""
+        ``output``'s ``scale`` / ``offset`` one value per plane.  ``tally``: :meth:`QueryStream.set_tally`.  ``zonal``:
+        ``(n_zones, n_classes)``, the arguments of :meth:`QueryStream.set_zonal`."""
         stream = QueryStream(self, opts, want_dist, want_pred)
         try:
             if plan is not None:  # (first: it sets the width set_output's scale / offset must have)
@@ -558,6 +598,8 @@ class Index:
                 stream.set_id_table(id_table, fill_id)
             if tally:
                 stream.set_tally()
+            if zonal is not None:  # (behind the plan: n_classes holds one value per plane)
+                stream.set_zonal(*zonal)
         except Exception:
             stream.close()
             raise
@@ -645,6 +687,63 @@ class Index:
         out = (c_int64 * 8)()
         check(load().sknnr_debug_last_tally(self.handle, out))
         return dict(zip(self.TALLY_FIELDS, (int(v) for v in out)))
+
+    # ---- zonal statistics (include/sknnr_hip.h, "Zonal statistics") ---------------------------
+    def zonal_from_values_host(self, values, zones, dtype, n_zones, scale=None, offset=None, n_classes=None, acc=None,
+                               hist=None):
+        """Zonal accumulators of a float64 value tile ``(n, c)`` and its ``(n,)`` int32 zone codes over the stored values of
+        ``dtype`` (int16 / uint16 / uint8 / int32) with ``scale`` / ``offset`` (``(c,)`` each, or neither):
+        sknnr_zonal_from_values on host arrays.  ``n_classes``: one class count per column (0: numeric), or None.  ``acc``
+        ``(n_zones, c, 6)`` int64 / ``hist`` (the class blocks, flat int64): arrays to ADD to (``accumulate = 1``); None:
+        fresh ones.  Returns ``(acc, hist)``, ``hist`` None when no column has classes."""
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        if values.ndim != 2:
+            raise ValueError("values must be (n, c)")
+        n, c = values.shape
+        zones = np.ascontiguousarray(zones, dtype=np.int32).reshape(-1)
+        if zones.size != n:
+            raise ValueError(f"zones must hold one code per pixel ({n}), got {zones.size}")
+        scale, offset = _c_f64(scale), _c_f64(offset)
+        n_classes, per_zone = _zonal_classes(n_classes, c)
+        accumulate = acc is not None
+        if accumulate:
+            if acc.dtype != np.int64 or acc.shape != (n_zones, c, ZONAL_FIELDS) or not acc.flags.c_contiguous:
+                raise ValueError(f"acc must be C-contiguous int64 ({n_zones}, {c}, {ZONAL_FIELDS})")
+            if per_zone and (hist is None or hist.dtype != np.int64 or hist.shape != (n_zones * per_zone,)
+                             or not hist.flags.c_contiguous):
+                raise ValueError(f"hist must be C-contiguous int64 ({n_zones * per_zone},)")
+        else:
+            acc = np.empty((n_zones, c, ZONAL_FIELDS), dtype=np.int64)
+            hist = np.empty(n_zones * per_zone, dtype=np.int64) if per_zone else None
+        if not per_zone:
+            hist = None
+        check(load().sknnr_zonal_from_values(self.handle, _host_ptr(values), _host_ptr(zones), n, c,
+                                             DTYPE_CODES.get(np.dtype(dtype), -1), _host_ptr(scale), _host_ptr(offset),
+                                             int(n_zones), _host_ptr(n_classes), _host_ptr(acc), _host_ptr(hist),
+                                             int(accumulate), MEM_HOST, None))
+        return acc, hist
+
+    def zonal_from_values_device(self, values_ptr, zones_ptr, n, c, dtype, n_zones, acc_ptr, hist_ptr=0, scale=None,
+                                 offset=None, n_classes=None, accumulate=False, stream=0):
+        """sknnr_zonal_from_values on device pointers: enqueues on ``stream`` and returns.  ``scale`` / ``offset`` /
+        ``n_classes`` are host arrays, as in the host form."""
+        scale, offset = _c_f64(scale), _c_f64(offset)
+        n_classes, _ = _zonal_classes(n_classes, c)
+        code = dtype if isinstance(dtype, int) else DTYPE_CODES.get(np.dtype(dtype), -1)
+        check(load().sknnr_zonal_from_values(self.handle, c_void_p(values_ptr or None), c_void_p(zones_ptr or None), int(n),
+                                             int(c), code, _host_ptr(scale), _host_ptr(offset), int(n_zones),
+                                             _host_ptr(n_classes), c_void_p(acc_ptr or None), c_void_p(hist_ptr or None),
+                                             int(bool(accumulate)), MEM_DEVICE, c_void_p(stream or None)))
+
+    ZONAL_RECORD = ("ran", "pixels", "c", "tallied", "nan", "outside", "other", "global_atomics")
+
+    def debug_last_zonal(self) -> dict:
+        """Debug only (sknnr_debug_last_zonal; synchronises the device): the last :meth:`zonal_from_values_host` /
+        ``_device`` call, or the open zonal stream so far -- ran, pixels, c, entries tallied, NaN entries, pixels outside
+        ``[0, n_zones)``, class values outside their range, global atomics issued on the accumulators."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_zonal(self.handle, out))
+        return dict(zip(self.ZONAL_RECORD, (int(v) for v in out)))
 
     # ---- per-target neighbour summaries (include/sknnr_hip.h) --------------------------------
     def summarize_host(self, q, opts: QueryOpts, stat, nq=None):
@@ -1032,6 +1131,7 @@ class QueryStream:
         self._typed = False
         self.pred_cols = index.t  # columns of the prediction lane (set_plan widens it)
         self._tally = False
+        self._zonal = None  # (n_zones, elements of hist per zone) once set_zonal was called
         check(load().sknnr_stream_begin(index.handle, byref(opts), int(self.want_dist), int(self.want_pred),
                                         byref(self._h)))
 
@@ -1160,6 +1260,32 @@ class QueryStream:
         check(load().sknnr_stream_get_tally(self._h, _host_ptr(counts), _host_ptr(max_dist)))
         self._keep.clear()
         return counts, max_dist
+
+    def set_zonal(self, n_zones, n_classes=None):
+        """Tally every tile's predictions by zone on the device (sknnr_stream_set_zonal; only before the first push, after
+        :meth:`set_plan`): over the stored values of the stream's integer ``pred_dtype``.  ``n_classes``: one class count
+        per column of the prediction lane (0: numeric), or None.  Every push then needs :meth:`next_zones` first; what
+        the pushes deliver is unchanged; :meth:`zonal` reads the accumulators."""
+        n_classes, per_zone = _zonal_classes(n_classes, self.pred_cols)
+        check(load().sknnr_stream_set_zonal(self._h, int(n_zones), _host_ptr(n_classes)))
+        self._zonal = (int(n_zones), per_zone)
+
+    def next_zones(self, zones):
+        """The zone codes of the next push (sknnr_stream_next_zones): int32, one per pixel; the array is free on return."""
+        zones = np.ascontiguousarray(zones, dtype=np.int32).reshape(-1)
+        check(load().sknnr_stream_next_zones(self._h, _host_ptr(zones), int(zones.size)))
+
+    def zonal(self):
+        """Flush, then ``(acc, hist)`` of everything pushed so far (sknnr_stream_get_zonal): ``(n_zones, c, 6)`` int64 and
+        the flat class blocks (None when no column has classes).  The accumulators keep running."""
+        if self._zonal is None:
+            raise ValueError("the stream has no zones: set_zonal was not called")
+        n_zones, per_zone = self._zonal
+        acc = np.empty((n_zones, self.pred_cols, ZONAL_FIELDS), dtype=np.int64)
+        hist = np.empty(n_zones * per_zone, dtype=np.int64) if per_zone else None
+        check(load().sknnr_stream_get_zonal(self._h, _host_ptr(acc), _host_ptr(hist)))
+        self._keep.clear()
+        return acc, hist
 
     def valid_rows(self) -> int:
         """Valid (unmasked) rows submitted so far; without a nodata mask, the rows pushed."""

@@ -1,9 +1,9 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_tally.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_tally.hip, k_zonal.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
-// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS / SKNNR_KERNELS_TALLY), templates where they are instantiated.
+// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS / SKNNR_KERNELS_TALLY / SKNNR_KERNELS_ZONAL), templates where they are instantiated.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +23,7 @@
 #include "summary.hip.h"
 #include "tally.hip.h"
 #include "weights.hip.h"
+#include "zonal.hip.h"
 
 namespace sknnr {
 namespace launch {
@@ -110,6 +111,14 @@ bool tally_wide_ok(const TallyArgs& a);  // that launch loads 16 bytes per lane
 long tally_blocks(long n, int k);        // its workgroups
 // every value of max_dist that is not > 0 becomes +0.0 (accumulate = 1 on a caller's array)
 hipError_t tally_clean(double* max_dist, long n, hipStream_t st);
+
+// ---- k_zonal.hip: zonal statistics of a prediction tile (zonal.hip.h) ----------------------------------------------------------
+// adds the a.n pixels into a.acc / a.hist / a.rec (none of them initialised here), converting with dst_dtype (an integer
+// sknnr_dtype); hipErrorInvalidValue for another type, for n_zones * c >= 2^32 and for null accumulators
+hipError_t zonal(const ZonalArgs& a, int dst_dtype, hipStream_t st);
+long zonal_blocks(long n, int c);  // its workgroups
+// count, sum and limbs 0, min INT64_MAX, max INT64_MIN for n_keys (zone, column) pairs
+hipError_t zonal_init(long long* acc, long n_keys, hipStream_t st);
 
 // ---- k_coarse1.hip / k_coarse2.hip: the MFMA pre-filters ----------------------------------------------------------------
 struct Coarse1Launch {

@@ -70,7 +70,7 @@ inline bool narrow_wide_ok(const void* src, const void* dst, int dst_bytes, long
     return stride % 4 == 0 && n >= 4;
 }
 
-#if defined(SKNNR_KERNELS_NARROW)
+#if defined(SKNNR_KERNELS_NARROW) || defined(SKNNR_KERNELS_ZONAL)  // (zonal.hip.h converts with narrow_one too)
 extern __shared__ __attribute__((aligned(16))) unsigned long long narrow_lds[];
 
 template <typename D>
@@ -189,6 +189,6 @@ __global__ void __launch_bounds__(kPlanesRows) narrow_planes_kernel(NarrowArgs a
         }
     }
 }
-#endif  // SKNNR_KERNELS_NARROW
+#endif  // SKNNR_KERNELS_NARROW || SKNNR_KERNELS_ZONAL
 
 }  // namespace sknnr

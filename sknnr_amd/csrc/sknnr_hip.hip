@@ -430,6 +430,8 @@ struct sknnr_index {
         double* pin_x = nullptr;  size_t pin_x_n = 0;
         DevBuf<double> dev_x;
         DevBuf<double> dev_xp;  // band-first tiles (planes.hip.h): the uploaded planes, in front of dev_x
+        int32_t* pin_z = nullptr;  size_t pin_z_n = 0;  // zonal streams: the tile's zone codes, pinned and on the device
+        DevBuf<int32_t> dev_z;
         // One output (kLaneIdx / kLaneDist / kLanePred), all in 8-byte words: int64 indices, float64 values, packed narrow elements.
         struct Lane {
             Word* pin = nullptr;  size_t pin_n = 0;  // pinned: what the device-to-host copy fills
@@ -499,6 +501,18 @@ struct sknnr_index {
     DevBuf<unsigned long long> s_tally_cnt, s_tally_max, tally_rec;
     int64_t last_tally[3] = {};
     int last_tally_half = 0;
+    // zonal statistics (zonal.hip.h): the open stream's accumulators (sknnr_stream_set_zonal) and the class table of each
+    // kind of call -- n_classes per column (zonal_cls) and where each column's block begins in hist (zonal_off); the
+    // conversion parameters of one-shot calls (zonal_par: scale then offset); the kernels' device record -- words [0, 6) of
+    // one-shot calls, [6, 12) of the open stream -- and the host's half of sknnr_debug_last_zonal: ran, pixels, c;
+    // last_zonal_half: which device words belong to it
+    DevBuf<long long> s_zonal_acc, s_zonal_hist;
+    DevBuf<int> zonal_cls, s_zonal_cls;
+    DevBuf<long> zonal_off, s_zonal_off;
+    DevBuf<double> zonal_par;
+    DevBuf<unsigned long long> zonal_rec;
+    int64_t last_zonal[3] = {};
+    int last_zonal_half = 0;
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
     // a ring of call records so that several calls of one benchmark step are summed, not only the last.
@@ -520,6 +534,7 @@ struct sknnr_index {
         (void)hipSetDevice(device);  // (the DevBuf members free themselves behind this body)
         for (auto& sl : slot) {
             if (sl.pin_x) (void)hipHostFree(sl.pin_x);
+            if (sl.pin_z) (void)hipHostFree(sl.pin_z);
             for (auto& ln : sl.lane)
                 if (ln.pin) (void)hipHostFree(ln.pin);
             for (hipEvent_t e : {sl.ev_h2d, sl.ev_done, sl.ev_d2h})
@@ -2201,6 +2216,16 @@ static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, 
                           int mode, int law, double* out, hipStream_t st);
 // n rows of a tile of the open stream into the handle's accumulators (sknnr_stream_set_tally), on `st` behind their search
 static int tally_tile(sknnr_index* ix, const double* dist, const long* idx, long n, int k, hipStream_t st);
+// what one zonal launch converts and tallies with: the zones, the tile's width, the prediction lane's conversion (scale /
+// offset on the device, or null) and whether some column has classes
+struct ZonalSpec {
+    int n_zones, c, dtype;
+    const double *scale, *offset;
+    bool classes;
+};
+// n pixels of a tile of the open stream -- its full-layout (n, c) float64 predictions and its zone codes -- into the
+// handle's accumulators (sknnr_stream_set_zonal), on `st` behind the reduction
+static int zonal_tile(sknnr_index* ix, const ZonalSpec& z, const double* pred, const int32_t* zones, long n, hipStream_t st);
 
 // The plan of the call in progress for as long as the scope lives; the caller holds ix->mtx.
 struct SummaryScope {
@@ -2447,6 +2472,12 @@ struct HostPipe {
     } lane[kLanes];
     bool mask_dist = false;  // the masked path is handed the distance buffer: distances leave, or the reduction or the tally reads them
     bool tally = false;      // every tile's neighbours are tallied into the handle's s_tally_cnt / s_tally_max (sknnr_stream_set_tally)
+    // zonal statistics (sknnr_stream_set_zonal): every tile's prediction tile is tallied by zone into the handle's
+    // s_zonal_acc / s_zonal_hist; zones_push: the zone codes of the push in progress (one per pushed row)
+    bool zonal = false;
+    int zonal_zones = 0, zonal_c = 0;
+    size_t zonal_hist = 0;  // elements of the class blocks (0: no column has classes)
+    const int32_t* zones_push = nullptr;
     size_t x_esz = sizeof(double);  // bytes per element of the caller's rows (opts->query_dtype)
     // nodata front end: every tile is masked behind its host-to-device copy, and o.row_offset advances by its VALID rows
     const double* nodata_dev = nullptr;  // (d_x) on the device, or null: no mask
@@ -2546,6 +2577,10 @@ int pipe_prepare_slot(HostPipe& p, int b, long n, bool planes = false) {
     if ((rc = ensure_pinned(sl.pin_x, sl.pin_x_n, x_f64))) return rc;
     HIP_TRY(sl.dev_x.ensure(x_f64));
     if (planes) HIP_TRY(sl.dev_xp.ensure(x_f64));  // (band-first tiles only: the uploaded planes)
+    if (p.zonal) {
+        if ((rc = ensure_pinned(sl.pin_z, sl.pin_z_n, (size_t)n))) return rc;
+        HIP_TRY(sl.dev_z.ensure((size_t)n));
+    }
     for (int l = 0; l < kLanes; ++l) {
         const HostPipe::Lane& ln = p.lane[l];
         auto& sb = sl.lane[l];
@@ -2633,8 +2668,10 @@ int pipe_enqueue_d2h(HostPipe& p) {
 // the first band's segments (they name the tile for the look-ahead), and out[] the first output plane's, with
 // out_stride elements between planes.  `planes` must stay valid until the next tile is submitted or the pipeline flushed.
 // out[l]: where lane l's results of this tile go, in the lane's own element type (null: not asked for).
+// zones (a zonal pipeline; else null): the tile's n zone codes, the next tile's behind them.
 int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], const void* q_next = nullptr,
-                long n_next = 0, const void* const* planes = nullptr, long p_off = 0, long out_stride = 0) {
+                long n_next = 0, const void* const* planes = nullptr, long p_off = 0, long out_stride = 0,
+                const int32_t* zones = nullptr) {
     sknnr_index* ix = p.ix;
     const int b = p.slot_of;
     p.slot_of = (p.slot_of + 1) % kHostSlots;
@@ -2654,6 +2691,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
         if ((rc = pipe_prepare_slot(p, b, n, planes != nullptr))) return rc;
         if (planes) stage_planes(sl.pin_x, planes, d_x, p.x_esz, p_off, n);
         else parallel_copy(sl.pin_x, q, (size_t)n * d_x * p.x_esz);
+        if (p.zonal) parallel_copy(sl.pin_z, zones, (size_t)n * sizeof(int32_t));
     }
     const double t_enq = now_ms();
     p.ms_copy_in += t_enq - t_in;
@@ -2662,6 +2700,8 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
         PlanesArgs pa{sl.dev_xp.p, sl.dev_x.p, n, d_x, n};
         HIP_TRY(launch::planes_to_rows(pa, (int)p.x_esz, ix->st_h2d));
     }
+    if (p.zonal)  // (behind the tile's rows, in front of ev_h2d)
+        HIP_TRY(hipMemcpyAsync(sl.dev_z.p, sl.pin_z, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ix->st_h2d));
     long nv = n;  // rows the tile adds to the row offset
     if (p.nodata_dev) {
         // Mask (and, when some rows but not all are masked, compaction) on the copy stream behind the tile's rows: the host
@@ -2692,6 +2732,13 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
             rc = launch_predict(ix, dist.f64(), idx.i64(), nullptr, n, k, p.o.weight_mode, p.o.weight_law, pred.f64(), ix->st_run);
             if (rc) return rc;
         }
+    }
+    // zonal statistics: the full-layout float64 prediction tile (masked rows are NaN), whether or not this push asked for
+    // the predictions, and before any conversion: the kernel converts with the conversion's own device function
+    if (p.zonal) {
+        const HostPipe::Lane& pl = p.lane[kLanePred];
+        const ZonalSpec zs{p.zonal_zones, p.zonal_c, pl.dtype, pl.scale, pl.offset, p.zonal_hist > 0};
+        if ((rc = zonal_tile(ix, zs, pred.f64(), sl.dev_z.p, n, ix->st_run))) return rc;
     }
     // The requested results in the form they leave in, behind everything that produces them: a typed output, and the
     // indices of a stream with an id table, typed or not, is converted (and, band-first, transposed in the same pass) into
@@ -2743,9 +2790,12 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
         if ((rc = pipe_prepare_slot(p, b2, n_next, planes != nullptr))) return rc;
         double* dst = ix->slot[b2].pin_x;
         const size_t bytes = (size_t)n_next * d_x * p.x_esz, esz = p.x_esz;
+        int32_t* dst_z = p.zonal ? ix->slot[b2].pin_z : nullptr;  // (the next tile's zone codes travel with its rows)
+        const int32_t* zones_next = p.zonal ? zones + n : nullptr;
         p.ahead_done = ix->w_in->post([=]() -> int {
             if (planes) stage_planes(dst, planes, d_x, esz, p_off + n, n_next);
             else parallel_copy(dst, q_next, bytes);
+            if (dst_z) parallel_copy(dst_z, zones_next, (size_t)n_next * sizeof(int32_t));
             return SKNNR_OK;
         });
         p.ahead_q = q_next;
@@ -2788,7 +2838,7 @@ int pipe_submit_rows(HostPipe& p, const void* q_, long nq, void* const out[kLane
         for (int l = 0; l < kLanes; ++l)
             tile_out[l] = out[l] ? (char*)out[l] + lane_tile_offset(c0, p.lane[l].cols, p.lane[l].esz, planes != nullptr) : nullptr;
         int rc = pipe_submit(p, q + c0 * row_bytes, n, tile_out, n_next ? q + c1 * row_bytes : nullptr, n_next, planes, c0,
-                             out_stride);
+                             out_stride, p.zonal ? p.zones_push + c0 : nullptr);
         if (rc) return rc;
         c0 = c1;
     }
@@ -3948,6 +3998,9 @@ struct sknnr_stream {
     HostPipe pipe;
     int64_t rows_pushed = 0;
     bool pushed = false;  // a push was accepted: the nodata mask can no longer change
+    // a zonal stream (sknnr_stream_set_zonal): the zone codes of the next push (sknnr_stream_next_zones), the stream's own copy
+    std::vector<int32_t> zones;
+    bool have_zones = false;
 };
 
 extern "C" int sknnr_stream_set_nodata(sknnr_stream* s, const double* nodata, int64_t fill_index) {
@@ -4002,6 +4055,7 @@ extern "C" int sknnr_stream_set_plan(sknnr_stream* s, const int32_t* cols, const
     std::lock_guard<std::mutex> lock(p.ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan is allowed only before the first push");
     if (p.stat_set) return fail(SKNNR_ERR_INVALID, "the stream has per-target statistics (sknnr_stream_set_statistics): it takes no output plan");
+    if (p.zonal) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan comes before sknnr_stream_set_zonal: n_classes holds one value per output plane");
     if (p.lane[kLanePred].scale)
         return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan comes before sknnr_stream_set_output: the scale / offset hold one value per output plane");
     HIP_TRY(hipSetDevice(p.ix->device));
@@ -4226,6 +4280,241 @@ extern "C" int sknnr_debug_last_tally(const sknnr_index* cix, int64_t out[8]) {
     return SKNNR_OK;
 }
 
+// ---- zonal statistics (zonal.hip.h) -----------------------------------------------------------------------------------
+// One launch into acc / hist on `st`; cls / off: the class table on the device (null: no class planes); `half`: the device
+// record's words it adds to (0 one-shot calls, 1 the open stream).
+static int launch_zonal(sknnr_index* ix, const ZonalSpec& z, const double* v, const int32_t* zones, long n, const int* cls,
+                        const long* off, long long* acc, long long* hist, int half, hipStream_t st) {
+    ZonalArgs a{};
+    a.v = v;
+    a.zones = zones;
+    a.n = n;
+    a.c = z.c;
+    a.n_zones = z.n_zones;
+    a.na.scale = z.scale;
+    a.na.offset = z.offset;
+    a.n_classes = z.classes ? cls : nullptr;
+    a.hist_off = z.classes ? off : nullptr;
+    a.acc = acc;
+    a.hist = z.classes ? hist : nullptr;
+    a.rec = ix->zonal_rec.p + half * kZonalRecWords;
+    HIP_TRY(launch::zonal(a, z.dtype, st));
+    return SKNNR_OK;
+}
+
+static int zonal_tile(sknnr_index* ix, const ZonalSpec& z, const double* pred, const int32_t* zones, long n, hipStream_t st) {
+    if (!pred || !zones) return fail(SKNNR_ERR_INVALID, "a zonal tile needs its predictions and its zone codes");
+    const int rc = launch_zonal(ix, z, pred, zones, n, ix->s_zonal_cls.p, ix->s_zonal_off.p, ix->s_zonal_acc.p,
+                                ix->s_zonal_hist.p, 1, st);
+    if (rc) return rc;
+    ix->last_zonal[0] = 1;
+    ix->last_zonal[1] += n;
+    ix->last_zonal[2] = z.c;
+    ix->last_zonal_half = 1;
+    return SKNNR_OK;
+}
+
+// The two refusals and the class table: off[j] where column j's block begins in hist, *n_hist its length in all.
+static int zonal_check_shape(int64_t n_zones, int32_t c, const int32_t* n_classes, std::vector<long>& off, size_t* n_hist) {
+    if (n_zones < 1) return fail(SKNNR_ERR_INVALID, "n_zones must be >= 1");
+    if (c < 1) return fail(SKNNR_ERR_INVALID, "c must be >= 1");
+    if ((double)n_zones * (double)c >= 4294967296.0)
+        return fail(SKNNR_ERR_UNSUPPORTED, "n_zones * c = %lld * %d does not fit the zonal kernel's 32-bit keys", (long long)n_zones, c);
+    if (n_zones > 0x7fffffffL)
+        return fail(SKNNR_ERR_UNSUPPORTED, "n_zones = %lld: zone codes are int32", (long long)n_zones);
+    off.assign((size_t)c, 0);
+    *n_hist = 0;
+    if (!n_classes) return SKNNR_OK;
+    for (int j = 0; j < c; ++j) {
+        if (n_classes[j] < 0) return fail(SKNNR_ERR_INVALID, "n_classes[%d] = %d is negative", j, n_classes[j]);
+        if ((double)n_zones * (double)n_classes[j] >= 4294967296.0)
+            return fail(SKNNR_ERR_UNSUPPORTED, "n_zones * n_classes[%d] = %lld * %d does not fit the zonal kernel's 32-bit keys", j,
+                        (long long)n_zones, n_classes[j]);
+        off[(size_t)j] = (long)*n_hist;
+        *n_hist += (size_t)n_zones * (size_t)n_classes[j];
+    }
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_zonal_from_values(sknnr_index* ix, const double* values, const int32_t* zones, int64_t n, int32_t c,
+                                       int32_t dst_dtype, const double* scale, const double* offset, int64_t n_zones,
+                                       const int32_t* n_classes, int64_t* acc, int64_t* hist, int32_t accumulate, int32_t mem,
+                                       void* stream) {
+    if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    std::vector<long> off;
+    size_t n_hist = 0;
+    int rc = zonal_check_shape(n_zones, c, n_classes, off, &n_hist);
+    if (rc) return rc;
+    if (n < 0) return fail(SKNNR_ERR_INVALID, "n must be >= 0");
+    if (n > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 pixels in one call");
+    if (dst_dtype < SKNNR_DTYPE_I16 || dst_dtype > SKNNR_DTYPE_I32)
+        return fail(SKNNR_ERR_INVALID, "dst_dtype = %d: zonal sums are over stored integers (SKNNR_DTYPE_I16 / U16 / U8 / I32)", dst_dtype);
+    if (!scale != !offset) return fail(SKNNR_ERR_INVALID, "scale and offset come together");
+    if (!acc) return fail(SKNNR_ERR_INVALID, "acc is NULL");
+    if (n_hist > 0 && !hist) return fail(SKNNR_ERR_INVALID, "hist is NULL and a column has classes");
+    if (n > 0 && (!values || !zones)) return fail(SKNNR_ERR_INVALID, "values / zones is NULL");
+    if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = mem == SKNNR_MEM_DEVICE ? (hipStream_t)stream : nullptr;
+    const size_t n_acc = (size_t)n_zones * c * kZonalFields, n_el = (size_t)n * c;
+    const bool classes = n_hist > 0;
+    // the handle's parameter buffers: an earlier call on `st` may still read them
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(ix->zonal_rec.ensure(2 * kZonalRecWords));
+    ZonalSpec z{(int)n_zones, c, dst_dtype, nullptr, nullptr, classes};
+    if (scale) {
+        HIP_TRY(ix->zonal_par.ensure(2 * (size_t)c));
+        HIP_TRY(hipMemcpy(ix->zonal_par.p, scale, (size_t)c * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ix->zonal_par.p + c, offset, (size_t)c * sizeof(double), hipMemcpyHostToDevice));
+        z.scale = ix->zonal_par.p;
+        z.offset = ix->zonal_par.p + c;
+    }
+    if (classes) {
+        HIP_TRY(ix->zonal_cls.ensure((size_t)c));
+        HIP_TRY(ix->zonal_off.ensure((size_t)c));
+        HIP_TRY(hipMemcpy(ix->zonal_cls.p, n_classes, (size_t)c * sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ix->zonal_off.p, off.data(), (size_t)c * sizeof(long), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemsetAsync(ix->zonal_rec.p, 0, kZonalRecWords * sizeof(unsigned long long), st));
+    ix->last_zonal[0] = n > 0 ? 1 : 0;
+    ix->last_zonal[1] = n;
+    ix->last_zonal[2] = c;
+    ix->last_zonal_half = 0;
+    long long* da = (long long*)acc;
+    long long* dh = (long long*)hist;
+    const double* dv = values;
+    const int32_t* dz = zones;
+    DevBuf<long long> bacc, bhist;  // (host memory: freed by their destructors on every return path)
+    DevBuf<double> bval;
+    DevBuf<int32_t> bzones;
+    if (mem == SKNNR_MEM_HOST) {
+        HIP_TRY(bacc.ensure(n_acc));
+        if (classes) HIP_TRY(bhist.ensure(n_hist));
+        HIP_TRY(bval.ensure(n_el));
+        HIP_TRY(bzones.ensure((size_t)n));
+        if (n) {
+            HIP_TRY(hipMemcpy(bval.p, values, n_el * sizeof(double), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(bzones.p, zones, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        if (accumulate) {
+            HIP_TRY(hipMemcpy(bacc.p, acc, n_acc * 8, hipMemcpyHostToDevice));
+            if (classes) HIP_TRY(hipMemcpy(bhist.p, hist, n_hist * 8, hipMemcpyHostToDevice));
+        }
+        da = bacc.p;
+        dh = classes ? bhist.p : nullptr;
+        dv = bval.p;
+        dz = bzones.p;
+    }
+    if (!accumulate) {
+        HIP_TRY(launch::zonal_init(da, (long)((size_t)n_zones * c), st));
+        if (classes) HIP_TRY(hipMemsetAsync(dh, 0, n_hist * 8, st));
+    }
+    if ((rc = launch_zonal(ix, z, dv, dz, n, ix->zonal_cls.p, ix->zonal_off.p, da, dh, 0, st))) return rc;
+    if (mem == SKNNR_MEM_HOST) {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpy(acc, bacc.p, n_acc * 8, hipMemcpyDeviceToHost));
+        if (classes) HIP_TRY(hipMemcpy(hist, bhist.p, n_hist * 8, hipMemcpyDeviceToHost));
+    }
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_set_zonal(sknnr_stream* s, int64_t n_zones, const int32_t* n_classes) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    HostPipe& p = s->pipe;
+    sknnr_index* ix = p.ix;
+    if (!p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
+    const int c = p.lane[kLanePred].cols;  // (the plan's entries, or the targets)
+    std::vector<long> off;
+    size_t n_hist = 0;
+    const int rc = zonal_check_shape(n_zones, c, n_classes, off, &n_hist);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_zonal is allowed only before the first push");
+    HIP_TRY(hipSetDevice(ix->device));
+    const size_t n_keys = (size_t)n_zones * c;
+    HIP_TRY(ix->s_zonal_acc.ensure(n_keys * kZonalFields));
+    HIP_TRY(ix->s_zonal_hist.ensure(n_hist));
+    HIP_TRY(ix->zonal_rec.ensure(2 * kZonalRecWords));
+    if (n_hist) {
+        HIP_TRY(ix->s_zonal_cls.ensure((size_t)c));
+        HIP_TRY(ix->s_zonal_off.ensure((size_t)c));
+        HIP_TRY(hipMemcpy(ix->s_zonal_cls.p, n_classes, (size_t)c * sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ix->s_zonal_off.p, off.data(), (size_t)c * sizeof(long), hipMemcpyHostToDevice));
+    }
+    // (on the stream every tile's launch runs on: initialised in front of the first of them)
+    HIP_TRY(launch::zonal_init(ix->s_zonal_acc.p, (long)n_keys, ix->st_run));
+    if (n_hist) HIP_TRY(hipMemsetAsync(ix->s_zonal_hist.p, 0, n_hist * 8, ix->st_run));
+    HIP_TRY(hipMemsetAsync(ix->zonal_rec.p + kZonalRecWords, 0, kZonalRecWords * sizeof(unsigned long long), ix->st_run));
+    p.zonal = true;
+    p.zonal_zones = (int)n_zones;
+    p.zonal_c = c;
+    p.zonal_hist = n_hist;
+    s->have_zones = false;
+    ix->last_zonal[0] = ix->last_zonal[1] = 0;
+    ix->last_zonal[2] = c;
+    ix->last_zonal_half = 1;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_next_zones(sknnr_stream* s, const int32_t* zones, int64_t nq) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    if (!s->pipe.zonal) return fail(SKNNR_ERR_INVALID, "the stream has no zones: sknnr_stream_set_zonal was not called");
+    if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
+    if (nq == 0) return SKNNR_OK;  // (a push of no rows takes none)
+    if (!zones) return fail(SKNNR_ERR_INVALID, "zones is NULL");
+    std::lock_guard<std::mutex> lock(s->pipe.ix->mtx);
+    s->zones.assign(zones, zones + nq);
+    s->have_zones = true;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_get_zonal(sknnr_stream* s, int64_t* acc, int64_t* hist) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    HostPipe& p = s->pipe;
+    sknnr_index* ix = p.ix;
+    if (!p.zonal) return fail(SKNNR_ERR_INVALID, "the stream has no zones: sknnr_stream_set_zonal was not called");
+    if (!acc && !hist) return fail(SKNNR_ERR_INVALID, "acc and hist are both NULL");
+    if (hist && !p.zonal_hist) return fail(SKNNR_ERR_INVALID, "hist is given and no column has classes");
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    const int rc = pipe_flush(p);
+    if (rc) return pipe_fail(p, rc);
+    HIP_TRY(hipStreamSynchronize(ix->st_run));
+    if (acc) HIP_TRY(hipMemcpy(acc, ix->s_zonal_acc.p, (size_t)p.zonal_zones * p.zonal_c * kZonalFields * 8, hipMemcpyDeviceToHost));
+    if (hist) HIP_TRY(hipMemcpy(hist, ix->s_zonal_hist.p, p.zonal_hist * 8, hipMemcpyDeviceToHost));
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_zonal(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::fill(out, out + 8, 0);
+    std::copy(ix->last_zonal, ix->last_zonal + 3, out);
+    if (!ix->zonal_rec.p) return SKNNR_OK;
+    unsigned long long w[kZonalRecWords];
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(w, ix->zonal_rec.p + ix->last_zonal_half * kZonalRecWords, sizeof w, hipMemcpyDeviceToHost));
+    // (eight words: the sixth counter, entries without a slot, does not fit; they show in the atomics)
+    out[3] = (int64_t)w[kZonalRecTallied];
+    out[4] = (int64_t)w[kZonalRecNan];
+    out[5] = (int64_t)w[kZonalRecOutside];
+    out[6] = (int64_t)w[kZonalRecOther];
+    out[7] = (int64_t)w[kZonalRecAtomics];
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_zonal_geometry(int32_t c, int64_t out[4]) {
+    if (!out || c < 1) return fail(SKNNR_ERR_INVALID, "bad argument");
+    out[0] = zonal_pixels_per_wg(c);
+    out[1] = kZonalSlots;
+    out[2] = kZonalHistSlots;
+    out[3] = kZonalProbes;
+    return SKNNR_OK;
+}
+
 extern "C" int sknnr_stream_valid_rows(const sknnr_stream* s, int64_t* out_valid_rows) {
     if (!s || !out_valid_rows) return fail(SKNNR_ERR_INVALID, "stream / out_valid_rows is NULL");
     std::lock_guard<std::mutex> lock(s->pipe.ix->mtx);
@@ -4285,6 +4574,16 @@ static int stream_push(sknnr_stream* s, const void* q, const void* const* planes
     if (outs[kLaneDist] && !p.lane[kLaneDist].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without distances");
     if (outs[kLanePred] && !p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
     std::lock_guard<std::mutex> lock(p.ix->mtx);
+    if (p.zonal) {
+        if (!s->have_zones) return fail(SKNNR_ERR_INVALID, "a push on a zonal stream needs sknnr_stream_next_zones first");
+        if ((int64_t)s->zones.size() != nq)
+            return fail(SKNNR_ERR_INVALID, "sknnr_stream_next_zones gave %lld zone codes, the push has %lld rows", (long long)s->zones.size(), (long long)nq);
+        const int dt = p.lane[kLanePred].dtype;
+        if (dt < SKNNR_DTYPE_I16 || dt > SKNNR_DTYPE_I32)
+            return fail(SKNNR_ERR_INVALID, "a zonal stream needs an integer pred_dtype (sknnr_stream_set_output): zonal sums are over stored integers");
+        s->have_zones = false;  // (consumed, whatever becomes of the push)
+        p.zones_push = s->zones.data();
+    }
     HIP_TRY(hipSetDevice(p.ix->device));
     s->pushed = true;
     const int rc = pipe_submit_rows(p, q, nq, outs, planes, out_stride);
