@@ -478,7 +478,7 @@ int sknnr_hamming_distances(sknnr_index* index, const double* q, int64_t nq, con
  *   Reads n_neighbors, deterministic, decimals, formula and row_offset; exclude_self must be 1 (the rows are reference
  *   rows), apply_affine and query_dtype 0.  out_dist / out_idx / mem / stream as for sknnr_kneighbors; out_dist may be
  *   NULL.  One float64 scan (group_scan_kernel), counted in sknnr_stats.queries and exact_only_queries.  Refused before
- *   any launch: no groups set or a window outside [0, n_ref] (SKNNR_ERR_INVALID); n_neighbors > n_ref - largest group
+ *   any launch: no groups set (nor a buffer, below) or a window outside [0, n_ref] (SKNNR_ERR_INVALID); n_neighbors > n_ref - largest group
  *   (SKNNR_ERR_K_TOO_LARGE: some row would have fewer candidates than neighbours); n_neighbors > 192
  *   (SKNNR_ERR_UNSUPPORTED).  Rows of any width are served (beyond 1024 columns in column chunks, like the exact scan).
  */
@@ -492,6 +492,50 @@ int sknnr_kneighbors_grouped(sknnr_index* index, int64_t nq, const sknnr_query_o
  *   out[4] rows      out[5] slices (1 = none)      out[6] rows of the largest group      out[7] number of groups
  */
 int sknnr_debug_last_grouped(const sknnr_index* index, int64_t out[8]);
+
+/* ---- buffered leave-out ------------------------------------------------------------------------ */
+
+/*
+ * Independent neighbours that skip nearby plots: "predict plot i from the plots farther than R from it".  "Within R" is
+ * no equivalence relation, so no group labelling encodes it; it is a second mask of sknnr_kneighbors_grouped.  The
+ * contract, stated here once (sknnr_amd/csrc/groups.hip.h and buffer.hip.h; tests/_buffer.py restates it in numpy):
+ *
+ *   coords is an (n_ref, c) float64 array of plot positions, c = 1, 2 or 3, every value finite; radius is a finite
+ *   float64 >= 0; r2 = radius * radius, one float64 multiplication.  For reference rows i and r
+ *     g(i, r) = ((x_i - x_r)*(x_i - x_r) + (y_i - y_r)*(y_i - y_r)) + (z_i - z_r)*(z_i - z_r)
+ *   every operation a separately rounded float64 operation (no fused multiply-add).  A missing column counts as 0 for
+ *   both rows: it adds +0.0, so c < 3 gives the bits of the shorter sum.  Row r is EXCLUDED for row i when
+ *   g(i, r) <= r2 and, with group codes set as well, also when codes[r] == codes[i].  g(i, i) = 0 <= r2 always: a row is
+ *   never its own candidate, and radius = 0 excludes exactly the co-located rows.  Everything else is the
+ *   leave-group-out contract above, unchanged: the candidates' values under opts->formula, the k smallest by
+ *   (value, index), sqrt (not for HAMMING), sknnr's reorder when asked for, exact ties at the k-th value to the lower
+ *   index, no replay of scikit-learn's heap history.
+ *   excluded[i] is the number of rows excluded for row i, itself included: row i has n_ref - excluded[i] candidates.
+ *
+ * sknnr_index_set_buffer: coords HOST, row-major (n, c); NULL clears the buffer.  SKNNR_ERR_INVALID for n != n_ref, c
+ *   outside 1..3, a position that is not finite, a radius that is negative or not finite.  The positions are copied to
+ *   the device as (3, n_ref) and kept on the handle with the radius, like the group codes.
+ * sknnr_kneighbors_grouped runs when groups, a buffer or both are set (with neither: its error above).  With a buffer it
+ *   is refused before the scan is launched when n_neighbors > n_ref - max(excluded) (SKNNR_ERR_K_TOO_LARGE; the message
+ *   names max(excluded) and the first row that attains it); with groups alone max(excluded) is the largest group, the
+ *   test and its message above.  excluded[] is counted on the device (buffer_count_kernel, a sweep over the positions
+ *   and the codes that never reads the feature rows) once per change of either mask and cached on the handle.
+ * sknnr_buffer_counts: excluded[] under the masks now set (groups, a buffer or both; SKNNR_ERR_INVALID with neither),
+ *   (n_ref) int64 in `mem`; mem / stream as for sknnr_kneighbors.
+ */
+int sknnr_index_set_buffer(sknnr_index* index, const double* coords, int64_t n, int32_t c, double radius);
+int sknnr_buffer_counts(sknnr_index* index, int64_t* out, int32_t mem, void* stream);
+
+/*
+ * Debug only.  The masks of the leave-out scan of the last search call (zeroed by every search call).  Host memory, no
+ * device work:
+ *   out[0] 0 = no grouped scan ran, else the mask mode: 1 groups, 2 buffer, 3 both      out[1] c (0 without a buffer)
+ *   out[2] max(excluded)      out[3] min(excluded)      out[4] workgroups of the count launch      out[5] its LDS bytes
+ *   out[6] the first row that attains max(excluded)      out[7] 0
+ * out[2] .. out[6] describe the counts cached on the handle.  A groups-only search never counts: unless
+ * sknnr_buffer_counts did since the masks last changed, out[2] is the largest group and out[3] .. out[6] are 0.
+ */
+int sknnr_debug_last_buffer(const sknnr_index* index, int64_t out[8]);
 
 /* ---- reference-sharded search ------------------------------------------------------------------ */
 

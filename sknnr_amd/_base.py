@@ -435,6 +435,42 @@ def normalize_groups(groups, n_samples):
     return np.ascontiguousarray(codes.reshape(-1), dtype=np.int32)
 
 
+def normalize_buffer(buffer, n_samples):
+    """``(coords, radius)`` of a buffered leave-out as the engine takes it: ``coords`` a C-contiguous float64
+    ``(n_samples, c)`` array, ``c`` 1 to 3 (a 1-D array-like is one column), ``radius`` a float.  ``buffer`` is a pair
+    ``(coords, radius)`` with ``coords`` an array-like or a pandas DataFrame of plot positions.  ``ValueError`` for anything
+    but a pair, a wrong length, more than 3 or fewer than 1 columns, positions that are not finite numbers, and a radius that
+    is negative, not finite or no scalar."""
+    if not isinstance(buffer, (tuple, list)) or len(buffer) != 2:
+        raise ValueError(f"buffer must be a pair (coords, radius), got {type(buffer).__name__}"
+                         + (f" of length {len(buffer)}" if isinstance(buffer, (tuple, list)) else ""))
+    coords, radius = buffer
+    c = coords.to_numpy() if hasattr(coords, "to_numpy") else np.asarray(coords)
+    if c.ndim == 1:
+        c = c.reshape(-1, 1)
+    if c.ndim != 2:
+        raise ValueError(f"buffer positions must be 2-D with one row per fitted row, got an array of shape {c.shape}")
+    if c.shape[0] != n_samples:
+        raise ValueError(f"buffer positions must hold one row per fitted row ({n_samples}), got {c.shape[0]}")
+    if not 1 <= c.shape[1] <= 3:
+        raise ValueError(f"buffer positions must have 1 to 3 columns, got {c.shape[1]}")
+    try:
+        c = np.ascontiguousarray(c, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"buffer positions must be numbers, got dtype {c.dtype}") from None
+    if not np.isfinite(c).all():
+        raise ValueError(f"buffer positions must be finite, got {int((~np.isfinite(c)).sum())} values that are not")
+    if np.ndim(radius) != 0 or isinstance(radius, (str, bytes)) or radius is None:
+        raise ValueError(f"buffer radius must be a scalar, got {radius!r}")
+    try:
+        r = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError(f"buffer radius must be a scalar, got {radius!r}") from None
+    if not np.isfinite(r) or r < 0:
+        raise ValueError(f"buffer radius must be finite and >= 0, got {r!r}")
+    return c, r
+
+
 def _reraise(err, estimator):
     """Map a native failure to the exception the reference raises for the same input."""
     if err.code == _native.ERR_K_TOO_LARGE:
@@ -898,20 +934,33 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         return self._summarize_engine(X, stat, apply_affine=False)
 
     # -- leave-group-out: independent predictions that skip groups ------------------------------
-    def _independent_neighbors(self, groups, k, use_deterministic_ordering=True):
-        """``(dist, idx)`` of :meth:`independent_kneighbors` as host arrays; everything is refused before device work."""
+    def _leave_out_masks(self, groups, buffer):
+        """``(codes or None, (coords, radius) or None)`` of a leave-out call, refused before any device work.  Without a
+        buffer ``groups`` is required, as it always was; with one it is optional."""
         check_is_fitted(self, "_fit_X")
         self._check_reference_ties_supported("independent_kneighbors with groups")
-        codes = normalize_groups(groups, self.n_samples_fit_)
+        if buffer is None:
+            return normalize_groups(groups, self.n_samples_fit_), None
+        buf = normalize_buffer(buffer, self.n_samples_fit_)
+        return (None if groups is None else normalize_groups(groups, self.n_samples_fit_)), buf
+
+    def _set_leave_out_masks(self, codes, buf):
+        """Both masks on the engine: a mask the call does not name clears the one an earlier call left."""
+        self.engine_.set_groups(codes)
+        self.engine_.set_buffer(buf)
+
+    def _independent_neighbors(self, groups, k, use_deterministic_ordering=True, buffer=None):
+        """``(dist, idx)`` of :meth:`independent_kneighbors` as host arrays; everything is refused before device work."""
+        codes, buf = self._leave_out_masks(groups, buffer)
         try:
-            self.engine_.set_groups(codes)
+            self._set_leave_out_masks(codes, buf)
             return self.engine_.kneighbors_grouped(k, deterministic=bool(use_deterministic_ordering),
                                                    decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula())
         except _native.HipBackendError as err:
             _reraise(err, self)
 
-    def independent_kneighbors(self, groups, n_neighbors=None, return_distance=True, return_dataframe_index=False,
-                               use_deterministic_ordering=True):
+    def independent_kneighbors(self, groups=None, n_neighbors=None, return_distance=True, return_dataframe_index=False,
+                               use_deterministic_ordering=True, *, buffer=None):
         """Leave-group-out neighbours: for every fitted row the ``n_neighbors`` nearest fitted rows of OTHER groups.
 
         ``groups``: a 1-D array-like of ``n_samples_fit_`` labels (integers, strings, a pandas Series) -- the plot of a
@@ -923,27 +972,36 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         calls are refused under ``hamming_tie_policy("numpy")`` and ``tree_tie_policy("tree")``.  With every row in a
         group of its own this is ``kneighbors(X=None)`` wherever the k-th and (k+1)-th values differ.
 
-        ``ValueError`` for labels that are not 1-D, of another length, NaN, or all one group, and for ``n_neighbors``
-        above ``n_samples_fit_`` minus the largest group.  Results are host arrays."""
+        ``buffer=(coords, radius)``: buffered leave-out, with or without ``groups``.  ``coords`` holds the plot position
+        of every fitted row -- an array-like or a pandas DataFrame of ``n_samples_fit_`` rows and 1 to 3 columns --
+        and a fitted row ``r`` is no candidate of row ``i`` when ``((xi - xr)**2 + (yi - yr)**2) + (zi - zr)**2 <=
+        radius * radius`` in float64 (a missing column counts as 0), so ``radius=0`` leaves out the co-located rows.
+        Given together, either mask excludes.  :meth:`buffer_counts` tells how many rows a radius removes per row.
+
+        ``ValueError`` for labels that are not 1-D, of another length, NaN, or all one group, for positions of another
+        length, with no or more than 3 columns or not finite, for a radius that is negative, not finite or no scalar,
+        and for ``n_neighbors`` above ``n_samples_fit_`` minus the largest number of rows excluded for one row (groups
+        alone: the largest group).  Results are host arrays."""
         k = self._resolve_k(n_neighbors)
-        dist, idx = self._independent_neighbors(groups, k, use_deterministic_ordering)
+        dist, idx = self._independent_neighbors(groups, k, use_deterministic_ordering, buffer)
         return self._finish_kneighbors(dist, idx, return_distance, return_dataframe_index)
 
-    def independent_predict(self, groups):
+    def independent_predict(self, groups=None, *, buffer=None):
         """``predict`` of every fitted row from its :meth:`independent_kneighbors` (``n_neighbors`` of the estimator,
         deterministic ordering on) with the estimator's weights: what ``independent_prediction_`` is when every row is
-        its own group, and the honest figure when it is not."""
-        dist, idx = self._independent_neighbors(groups, self.n_neighbors)
+        its own group, and the honest figure when it is not.  ``buffer``: as there."""
+        dist, idx = self._independent_neighbors(groups, self.n_neighbors, buffer=buffer)
         pred = self.engine_.predict_from_neighbors(dist, idx, "uniform" if self.weights is None else self.weights)
         return pred.reshape(-1) if self._y.ndim == 1 else pred
 
-    def independent_summarize(self, groups, statistic=None, outputs=None):
-        """:meth:`summarize` of every fitted row over its :meth:`independent_kneighbors`; ``statistic`` / ``outputs`` as there."""
+    def independent_summarize(self, groups=None, statistic=None, outputs=None, *, buffer=None):
+        """:meth:`summarize` of every fitted row over its :meth:`independent_kneighbors`; ``statistic`` / ``outputs`` as
+        there, ``buffer`` as for :meth:`independent_kneighbors`."""
         check_is_fitted(self, "_fit_X")
         if statistic is None and outputs is None:
             statistic = "mean"
         stat = resolve_statistic(statistic, outputs, self._n_targets())
-        dist, idx = self._independent_neighbors(groups, self.n_neighbors)
+        dist, idx = self._independent_neighbors(groups, self.n_neighbors, buffer=buffer)
         weights = "uniform" if self.weights is None else self.weights
         if isinstance(stat, OutputPlan):
             out = self.engine_.summarize_plan_from_neighbors(dist, idx, weights, stat.arrays)
@@ -953,9 +1011,23 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             out = self.engine_.summarize_from_neighbors(dist, idx, weights, stat)
         return out.reshape(-1) if self._y.ndim == 1 else out
 
-    def independent_score(self, groups, sample_weight=None):
-        """R^2 of :meth:`independent_predict` against the fitted targets: ``independent_score_`` with groups left out."""
-        return float(r2_score(self._y, self.independent_predict(groups), sample_weight=sample_weight))
+    def independent_score(self, groups=None, sample_weight=None, *, buffer=None):
+        """R^2 of :meth:`independent_predict` against the fitted targets: ``independent_score_`` with groups, the plots
+        inside a ``buffer``, or both left out."""
+        return float(r2_score(self._y, self.independent_predict(groups, buffer=buffer), sample_weight=sample_weight))
+
+    def buffer_counts(self, buffer, groups=None):
+        """How many fitted rows ``buffer=(coords, radius)`` -- together with ``groups``, when given -- excludes for every
+        fitted row, the row itself included: int64 ``(n_samples_fit_,)``, counted on the device from the positions and
+        the codes alone.  Row ``i`` has ``n_samples_fit_ - counts[i]`` candidates in :meth:`independent_kneighbors`."""
+        if buffer is None:
+            raise ValueError("buffer_counts needs buffer=(coords, radius)")
+        codes, buf = self._leave_out_masks(groups, buffer)
+        try:
+            self._set_leave_out_masks(codes, buf)
+            return self.engine_.buffer_counts()
+        except _native.HipBackendError as err:
+            _reraise(err, self)
 
     # -- neighbour usage: which fitted rows made the map ------------------------------------------
     def _usage_from_neighbors(self, dist, idx):
@@ -974,11 +1046,11 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         except _native.HipBackendError as err:
             _reraise(err, self)
 
-    def independent_neighbor_usage(self, groups, n_neighbors=None):
-        """The :class:`sknnr_amd.NeighborUsage` of :meth:`independent_kneighbors` ``(groups, n_neighbors)``: which fitted
-        rows the leave-group-out predictions lean on."""
+    def independent_neighbor_usage(self, groups=None, n_neighbors=None, *, buffer=None):
+        """The :class:`sknnr_amd.NeighborUsage` of :meth:`independent_kneighbors` ``(groups, n_neighbors, buffer=buffer)``:
+        which fitted rows the leave-out predictions lean on."""
         k = self._resolve_k(n_neighbors)
-        dist, idx = self._independent_neighbors(groups, k)
+        dist, idx = self._independent_neighbors(groups, k, buffer=buffer)
         try:
             return self._usage_from_neighbors(dist, idx)
         except _native.HipBackendError as err:
@@ -1705,28 +1777,33 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         return self._host_result(X, reg._summarize_engine(X, stat, apply_affine=X is not None and self._map_on_device(),
                                                           owner=self.transformer_))
 
-    def independent_kneighbors(self, groups, n_neighbors=None, return_distance=True, return_dataframe_index=False,
-                               use_deterministic_ordering=True):
-        """Leave-group-out neighbours of every fitted row, in the transformed space the estimator searches
-        (:meth:`RawKNNRegressor.independent_kneighbors`, also for the contract and the tie rule)."""
+    def independent_kneighbors(self, groups=None, n_neighbors=None, return_distance=True, return_dataframe_index=False,
+                               use_deterministic_ordering=True, *, buffer=None):
+        """Leave-group-out and buffered leave-out neighbours of every fitted row, in the transformed space the estimator
+        searches (:meth:`RawKNNRegressor.independent_kneighbors`, also for the contract and the tie rule)."""
         check_is_fitted(self, "regressor_")
         return self.regressor_.independent_kneighbors(groups, n_neighbors, return_distance, return_dataframe_index,
-                                                      use_deterministic_ordering)
+                                                      use_deterministic_ordering, buffer=buffer)
 
-    def independent_predict(self, groups):
+    def independent_predict(self, groups=None, *, buffer=None):
         """:meth:`RawKNNRegressor.independent_predict` of the fitted regressor."""
         check_is_fitted(self, "regressor_")
-        return self.regressor_.independent_predict(groups)
+        return self.regressor_.independent_predict(groups, buffer=buffer)
 
-    def independent_summarize(self, groups, statistic=None, outputs=None):
+    def independent_summarize(self, groups=None, statistic=None, outputs=None, *, buffer=None):
         """:meth:`RawKNNRegressor.independent_summarize` of the fitted regressor."""
         check_is_fitted(self, "regressor_")
-        return self.regressor_.independent_summarize(groups, statistic, outputs)
+        return self.regressor_.independent_summarize(groups, statistic, outputs, buffer=buffer)
 
-    def independent_score(self, groups):
+    def independent_score(self, groups=None, *, buffer=None):
         """R^2 of :meth:`independent_predict` against the fitted targets (no ``sample_weight``, as :meth:`score`)."""
         check_is_fitted(self, "regressor_")
-        return self.regressor_.independent_score(groups)
+        return self.regressor_.independent_score(groups, buffer=buffer)
+
+    def buffer_counts(self, buffer, groups=None):
+        """:meth:`RawKNNRegressor.buffer_counts` of the fitted regressor."""
+        check_is_fitted(self, "regressor_")
+        return self.regressor_.buffer_counts(buffer, groups)
 
     def neighbor_usage(self, X=None, n_neighbors=None):
         """The :class:`sknnr_amd.NeighborUsage` of ``kneighbors(X, n_neighbors)`` (:meth:`RawKNNRegressor.neighbor_usage`)."""
@@ -1737,10 +1814,10 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         except _native.HipBackendError as err:
             _reraise(err, self)
 
-    def independent_neighbor_usage(self, groups, n_neighbors=None):
+    def independent_neighbor_usage(self, groups=None, n_neighbors=None, *, buffer=None):
         """:meth:`RawKNNRegressor.independent_neighbor_usage` of the fitted regressor."""
         check_is_fitted(self, "regressor_")
-        return self.regressor_.independent_neighbor_usage(groups, n_neighbors)
+        return self.regressor_.independent_neighbor_usage(groups, n_neighbors, buffer=buffer)
 
     def _raw_nodata(self, nodata):
         """``nodata`` of a streamed call, one value per UNTRANSFORMED input column: the mask reads the raw rows, so they

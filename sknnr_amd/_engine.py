@@ -76,6 +76,7 @@ class KNNEngine:
         self.has_forest = False
         self._law_key = None  # (law code, p0, p1) the handle holds: weight_law()
         self._group_codes = None  # the group codes the handle holds: set_groups()
+        self._buffer = None  # (positions, radius) the handle holds: set_buffer()
 
     def close(self):
         self._index.close()
@@ -238,6 +239,30 @@ class KNNEngine:
             return
         self._index.set_groups(codes)
         self._group_codes = codes.copy()
+
+    def set_buffer(self, buffer):
+        """The ``(coords, radius)`` of a buffered :meth:`kneighbors_grouped` -- ``(n_ref, c)`` float64 positions, ``c`` 1
+        to 3, and a float radius -- or ``None``, which clears a buffer left by an earlier call.  The engine keeps what
+        it uploaded last and uploads again only when positions or radius change."""
+        if buffer is None:
+            if self._buffer is not None:
+                self._index.set_buffer(None)
+                self._buffer = None
+            return
+        coords, radius = buffer
+        coords = np.ascontiguousarray(coords, dtype=np.float64)
+        radius = float(radius)
+        if self._buffer is not None and radius == self._buffer[1] and np.array_equal(coords, self._buffer[0]):
+            return
+        self._index.set_buffer(coords, radius)
+        self._buffer = (coords.copy(), radius)
+
+    def buffer_counts(self):
+        """``excluded[]`` under the masks of :meth:`set_groups` / :meth:`set_buffer`: int64 ``(n_ref,)``."""
+        return self._index.buffer_counts()
+
+    def debug_last_buffer(self) -> dict:
+        return self._index.debug_last_buffer()
 
     def kneighbors_grouped(self, k, *, deterministic, decimals, formula, row_offset=0, n_rows=None, return_distance=True):
         """Leave-group-out neighbours of the reference rows ``[row_offset, row_offset + n_rows)`` under the codes of

@@ -99,6 +99,9 @@ EXPORTED_SYMBOLS = (
     "sknnr_index_set_groups",
     "sknnr_kneighbors_grouped",
     "sknnr_debug_last_grouped",
+    "sknnr_index_set_buffer",
+    "sknnr_buffer_counts",
+    "sknnr_debug_last_buffer",
     "sknnr_shard_candidates",
     "sknnr_merge_shards",
     "sknnr_stream_begin",
@@ -329,6 +332,10 @@ def load(build_if_missing: bool = False):
         lib.sknnr_index_set_groups.argtypes = [vp, vp, c_int64]
         lib.sknnr_kneighbors_grouped.argtypes = [vp, c_int64, POINTER(QueryOpts), vp, vp, c_int32, vp]
         lib.sknnr_debug_last_grouped.argtypes = [vp, POINTER(c_int64)]
+    if hasattr(lib, "sknnr_index_set_buffer"):  # (likewise)
+        lib.sknnr_index_set_buffer.argtypes = [vp, vp, c_int64, c_int32, c_double]
+        lib.sknnr_buffer_counts.argtypes = [vp, vp, c_int32, vp]
+        lib.sknnr_debug_last_buffer.argtypes = [vp, POINTER(c_int64)]
     if hasattr(lib, "sknnr_tally_from_neighbors"):  # (likewise)
         lib.sknnr_tally_from_neighbors.argtypes = [vp, vp, vp, c_int64, c_int32, vp, vp, c_int32, c_int32, vp]
         lib.sknnr_stream_set_tally.argtypes = [vp]
@@ -514,6 +521,35 @@ class Index:
         out = (c_int64 * 8)()
         check(load().sknnr_debug_last_grouped(self.handle, out))
         return dict(zip(self.GROUPED_FIELDS, (int(v) for v in out)))
+
+    def set_buffer(self, coords, radius=0.0):
+        """The plot positions and the radius of a buffered :meth:`kneighbors_grouped` (sknnr_index_set_buffer):
+        ``(n_ref, c)`` float64 positions, ``c`` 1 to 3, and a finite radius >= 0; a row within the radius of the query
+        row (``g <= radius * radius``, include/sknnr_hip.h) is no candidate.  ``None`` clears the buffer."""
+        if coords is None:
+            check(load().sknnr_index_set_buffer(self.handle, None, 0, 0, 0.0))
+            return
+        coords = _c_f64(coords)
+        if coords.ndim == 1:
+            coords = coords.reshape(-1, 1)
+        check(load().sknnr_index_set_buffer(self.handle, _host_ptr(coords), coords.shape[0], coords.shape[1], float(radius)))
+
+    def buffer_counts(self):
+        """``excluded[]`` (sknnr_buffer_counts): per reference row the rows the masks now set exclude for it, itself
+        included -- int64 ``(n_ref,)``.  Counted on the device once per change of either mask."""
+        out = np.empty(self.n_ref, dtype=np.int64)
+        check(load().sknnr_buffer_counts(self.handle, _host_ptr(out), MEM_HOST, None))
+        return out
+
+    BUFFER_FIELDS = ("mask", "c", "max_excluded", "min_excluded", "count_workgroups", "count_lds_bytes", "argmax_row", "reserved")
+
+    def debug_last_buffer(self) -> dict:
+        """Debug only: the masks of the leave-out scan of the last search call (sknnr_debug_last_buffer): mask mode (0:
+        no grouped scan ran, 1 groups, 2 buffer, 3 both), position columns, max and min of ``excluded[]``, workgroups
+        and LDS bytes of the launch that counted them, the first row that attains the maximum."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_buffer(self.handle, out))
+        return dict(zip(self.BUFFER_FIELDS, (int(v) for v in out)))
 
     def set_forest(self, d_in, tree_offset, threshold, feature, left, right):
         """Install the query-time forest map (sknnr_index_set_forest): the flattened trees of

@@ -19,6 +19,14 @@
 // Wide rows: d > kScanColChunk (the node-id rows of RFNN / GBNN) use exact_scan_kernel's column chunking -- the queries'
 // columns pass through LDS kScanColChunk at a time inside every step, the CHUNKED instantiation.
 // Slices: none.  A pass is one workgroup whatever the row count ("Leave-group-out", has the cost).
+//
+// Buffered leave-out (include/sknnr_hip.h, sknnr_index_set_buffer, states the contract once): the MASK template parameter
+// of group_scan_kernel says which predicates exclude a pair -- kMaskGroups: equal codes (the kernel as it was);
+// kMaskBuffer: g(i, r) = ((xi - xr)^2 + (yi - yr)^2) + (zi - zr)^2 <= r2 on the rows' positions, every operation a
+// separately rounded float64 operation; kMaskBoth: either.  Positions are a (3, n_ref) column-major float64 array like
+// refT (a missing column is all +0.0), loaded by a thread for its two columns at publish time only, when the row loads
+// of the feature loop are dead; the positions of the pass's queries sit in LDS beside their codes.  (Fetching a step's
+// positions one step ahead into LDS slots of the thread's own was tried and was slower: DESIGN.md, "Buffered leave-out".)
 #pragma once
 #include "exact.hip.h"
 
@@ -27,8 +35,16 @@ namespace sknnr {
 struct GroupScanArgs {
     SelectArgs s;        // s.ref: the (n_ref, d) rows the queries are read from; s.xq unused; s.kk == s.k
     const double* refT;  // (d, n_ref) transposed reference rows
-    const int* codes;    // (n_ref) group code of every reference row, >= 0
+    const int* codes;    // (n_ref) group code of every reference row, >= 0 (read when MASK has kMaskGroups)
+    const double* pos;   // (3, n_ref) plot positions, column-major (read when MASK has kMaskBuffer)
+    double r2;           // radius * radius: a pair with g(i, r) <= r2 is excluded
 };
+
+// which predicates exclude a pair (group_scan_kernel's MASK, sknnr_debug_last_buffer's out[0])
+constexpr int kMaskGroups = 1;
+constexpr int kMaskBuffer = 2;
+constexpr int kMaskBoth = kMaskGroups | kMaskBuffer;
+constexpr int kPosCols = 3;  // rows of the position array: x, y, z
 
 // Two queries per wave under every formula: the codes and the mask cost registers on top of exact_scan_kernel's, whose
 // three queries per wave (expanded formula) sit at 165 VGPRs.  Eight queries per pass also keep the LDS of the widest
@@ -36,12 +52,13 @@ struct GroupScanArgs {
 constexpr int kGroupQpw = 2;
 constexpr int kGroupNq = kScanWaves * kGroupQpw;  // queries per workgroup pass
 
-// Workgroup LDS: xs[NQ][dpad] | qn[NQ] | hv[NQ][k] | hi[NQ][kp] | code[NQ] | d2[NQ][kScanRefs]
+// Workgroup LDS: xs[NQ][dpad] | qn[NQ] | hv[NQ][k] | hi[NQ][kp] | code[NQ] | pos[NQ][3] (buffer masks only) |
+// d2[NQ][kScanRefs]
 struct GroupScanLayout {
     int dpad, kp;
-    size_t xs, qn, hv, hi, code, d2, total;
+    size_t xs, qn, hv, hi, code, pos, d2, total;
 };
-__host__ __device__ constexpr GroupScanLayout group_scan_layout(int d, int k) {
+__host__ __device__ constexpr GroupScanLayout group_scan_layout(int d, int k, int mask = kMaskGroups) {
     GroupScanLayout L{};
     L.dpad = ((d < kScanColChunk ? d : kScanColChunk) + 1) & ~1;
     L.kp = k + (k & 1);
@@ -52,11 +69,14 @@ __host__ __device__ constexpr GroupScanLayout group_scan_layout(int d, int k) {
     L.hi = b;   b += 4 * (size_t)kGroupNq * L.kp;
     L.code = b; b += 4 * (size_t)kGroupNq;
     b = (b + 15) & ~(size_t)15;
+    L.pos = b;  b += (mask & kMaskBuffer) ? 8 * (size_t)kGroupNq * kPosCols : 0;
     L.d2 = b;   b += 8 * (size_t)kGroupNq * kScanRefs;
     L.total = b;
     return L;
 }
-__host__ __device__ constexpr size_t group_scan_bytes(int d, int k) { return group_scan_layout(d, k).total; }
+__host__ __device__ constexpr size_t group_scan_bytes(int d, int k, int mask = kMaskGroups) {
+    return group_scan_layout(d, k, mask).total;
+}
 
 // The end of a query: its k list entries, ascending by (value, index) -> sqrt -> sknnr's reorder -> outputs.
 template <int FORMULA>
@@ -99,9 +119,9 @@ __device__ void group_finish_query(const SelectArgs& s, long q, double* hv, int*
 
 // One workgroup (4 waves) per pass of kGroupNq queries, passes taken grid-stride.  Per step of kScanRefs references every
 // thread loads TWO columns of the transposed copy (coalesced) and their two codes once, evaluates the float64 values to
-// all queries of the pass, and publishes them -- or +inf for a pair of one group -- to LDS; every wave then offers them,
-// in index order, to the lists of its own queries.
-template <int FORMULA, bool CHUNKED = false>
+// all queries of the pass, and publishes them -- or +inf for a pair that MASK excludes -- to LDS; every wave then offers
+// them, in index order, to the lists of its own queries.
+template <int FORMULA, bool CHUNKED = false, int MASK = kMaskGroups>
 __global__ void __launch_bounds__(kScanWaves * 64, SKNNR_SCAN_WPS) group_scan_kernel(GroupScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     constexpr int NT = kScanWaves * 64;
@@ -113,12 +133,14 @@ __global__ void __launch_bounds__(kScanWaves * 64, SKNNR_SCAN_WPS) group_scan_ke
     const int wave = tid >> 6;
     const int K = s.k;
     const int d = s.d;
-    const GroupScanLayout L = group_scan_layout(d, K);
+    constexpr bool by_group = (MASK & kMaskGroups) != 0, by_buffer = (MASK & kMaskBuffer) != 0;
+    const GroupScanLayout L = group_scan_layout(d, K, MASK);
     double* xs = (double*)(smem_raw + L.xs);
     double* qns = (double*)(smem_raw + L.qn);
     double* hv_all = (double*)(smem_raw + L.hv);
     int* hi_all = (int*)(smem_raw + L.hi);
     int* qcode = (int*)(smem_raw + L.code);
+    double* qpos = (double*)(smem_raw + L.pos);
     double* d2buf = (double*)(smem_raw + L.d2);
 
     const long n_items = s.nq;
@@ -143,7 +165,11 @@ __global__ void __launch_bounds__(kScanWaves * 64, SKNNR_SCAN_WPS) group_scan_ke
             hv_all[qi * K + e] = DBL_MAX;
             hi_all[qi * L.kp + e] = 0;
         }
-        if (tid < NQ) qcode[tid] = a.codes[s.row_offset + f0 + (tid < n_here ? tid : n_here - 1)];
+        if (by_group && tid < NQ) qcode[tid] = a.codes[s.row_offset + f0 + (tid < n_here ? tid : n_here - 1)];
+        if (by_buffer && tid < NQ * kPosCols) {
+            const int qi = tid / kPosCols, c = tid - qi * kPosCols;
+            qpos[tid] = a.pos[(size_t)c * s.n_ref + s.row_offset + f0 + (qi < n_here ? qi : n_here - 1)];
+        }
         __syncthreads();
         if (FORMULA == 0 && tid < NQ) {
             double qn = 0.0;
@@ -165,8 +191,8 @@ __global__ void __launch_bounds__(kScanWaves * 64, SKNNR_SCAN_WPS) group_scan_ke
             const double* cola = a.refT + (ja < s.n_ref ? ja : 0);
             const double* colb = a.refT + (jb < s.n_ref ? jb : 0);
             // the codes of this thread's two columns, once per step (no query has a negative code)
-            const int ca = ja < s.n_ref ? a.codes[ja] : -1;
-            const int cb = jb < s.n_ref ? a.codes[jb] : -1;
+            const int ca = (by_group && ja < s.n_ref) ? a.codes[ja] : -1;
+            const int cb = (by_group && jb < s.n_ref) ? a.codes[jb] : -1;
             double acc[NQ][2];
 #pragma unroll
             for (int qi = 0; qi < NQ; ++qi) acc[qi][0] = acc[qi][1] = 0.0;
@@ -229,6 +255,15 @@ __global__ void __launch_bounds__(kScanWaves * 64, SKNNR_SCAN_WPS) group_scan_ke
             }  // column chunks
             const double rna = (FORMULA == 0 && ja < s.n_ref) ? s.rn[ja] : 0.0;
             const double rnb = (FORMULA == 0 && jb < s.n_ref) ? s.rn[jb] : 0.0;
+            // the positions of this thread's two columns: loaded here, where the feature loop's row loads are dead
+            double pa[kPosCols] = {}, pb[kPosCols] = {};
+            if (by_buffer) {
+#pragma unroll
+                for (int c = 0; c < kPosCols; ++c) {
+                    pa[c] = a.pos[(size_t)c * ld + (ja < s.n_ref ? ja : 0)];
+                    pb[c] = a.pos[(size_t)c * ld + (jb < s.n_ref ? jb : 0)];
+                }
+            }
             __syncthreads();  // the previous step's offers have finished reading d2buf (and qns is published)
 #pragma unroll
             for (int qi = 0; qi < NQ; ++qi) {
@@ -244,10 +279,31 @@ __global__ void __launch_bounds__(kScanWaves * 64, SKNNR_SCAN_WPS) group_scan_ke
                     da = da / s.hw_sum;
                     db = db / s.hw_sum;
                 }
-                // the mask: a row of the query's own group is no candidate (ca / cb = -1 on padding columns)
-                const int qc = qcode[qi];
-                d2buf[qi * kScanRefs + tid] = (ja < s.n_ref && ca != qc) ? da : INFINITY;
-                d2buf[qi * kScanRefs + NT + tid] = (jb < s.n_ref && cb != qc) ? db : INFINITY;
+                // the mask: a row of the query's own group is no candidate (ca / cb = -1 on padding columns), nor is a
+                // row within the radius of the query's position (the query itself: g = 0 <= r2)
+                if constexpr (MASK == kMaskGroups) {
+                    const int qc = qcode[qi];
+                    d2buf[qi * kScanRefs + tid] = (ja < s.n_ref && ca != qc) ? da : INFINITY;
+                    d2buf[qi * kScanRefs + NT + tid] = (jb < s.n_ref && cb != qc) ? db : INFINITY;
+                    continue;
+                }
+                bool ka = ja < s.n_ref, kb = jb < s.n_ref;
+                if (by_group) {
+                    const int qc = qcode[qi];
+                    ka = ka && ca != qc;
+                    kb = kb && cb != qc;
+                }
+                if (by_buffer) {
+                    const double qx = qpos[qi * kPosCols], qy = qpos[qi * kPosCols + 1], qz = qpos[qi * kPosCols + 2];
+                    const double ax = qx - pa[0], ay = qy - pa[1], az = qz - pa[2];
+                    const double bx = qx - pb[0], by = qy - pb[1], bz = qz - pb[2];
+                    const double ga = (ax * ax + ay * ay) + az * az;
+                    const double gb = (bx * bx + by * by) + bz * bz;
+                    ka = ka && !(ga <= a.r2);
+                    kb = kb && !(gb <= a.r2);
+                }
+                d2buf[qi * kScanRefs + tid] = ka ? da : INFINITY;
+                d2buf[qi * kScanRefs + NT + tid] = kb ? db : INFINITY;
             }
             __syncthreads();
 #pragma unroll 1

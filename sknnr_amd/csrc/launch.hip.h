@@ -1,15 +1,16 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_tally.hip, k_zonal.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_buffer.hip, k_tally.hip, k_zonal.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
-// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS / SKNNR_KERNELS_TALLY / SKNNR_KERNELS_ZONAL), templates where they are instantiated.
+// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS / SKNNR_KERNELS_TALLY / SKNNR_KERNELS_ZONAL / SKNNR_KERNELS_BUFFER), templates where they are instantiated.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "bucket.hip.h"
+#include "buffer.hip.h"
 #include "coarse2.hip.h"
 #include "exact.hip.h"
 #include "forest.hip.h"
@@ -102,6 +103,15 @@ hipError_t weight_law(const WeightLawArgs& a, hipStream_t st);
 // reference rows [a.s.row_offset, + a.s.nq) against all rows of other groups; `blocks` workgroups take the passes grid-stride;
 // chunked: d > kScanColChunk
 hipError_t group_scan(int formula, bool chunked, const GroupScanArgs& a, long blocks, size_t lds_bytes, hipStream_t st);
+
+// ---- k_buffer.hip: buffered leave-out (buffer.hip.h; the kMaskBuffer / kMaskBoth instantiations of groups.hip.h) --------------
+// group_scan with the buffer predicate: mask is kMaskBuffer or kMaskBoth (hipErrorInvalidValue otherwise, and for a
+// missing a.pos / a.codes); lds_bytes is group_scan_bytes(d, k, mask)
+hipError_t buffer_scan(int mask, int formula, bool chunked, const GroupScanArgs& a, long blocks, size_t lds_bytes,
+                       hipStream_t st);
+// a.out[i] = rows excluded for row i under the masks given (a.pos and / or a.codes); zeroes a.out first;
+// buffer_count_grid(a.n_ref) is its grid, kCountLdsBytes its LDS
+hipError_t buffer_count(const BufferCountArgs& a, hipStream_t st);
 
 // ---- k_tally.hip: neighbour usage (tally.hip.h) -----------------------------------------------------------------------------
 // adds the a.n rows into a.cnt / a.maxbits / a.rec (none of them zeroed here); hipErrorInvalidValue for n_ref * k >= 2^32,

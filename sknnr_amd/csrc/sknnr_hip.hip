@@ -352,6 +352,9 @@ struct SearchRecords {
     // the leave-group-out scan of the last call (sknnr_debug_last_grouped): formula + 1, k, workgroups, LDS bytes, rows,
     // slices (1: none), the largest group, the number of groups
     int64_t grouped[8] = {};
+    // the masks of that scan (sknnr_debug_last_buffer): mask mode (1 groups, 2 buffer, 3 both), position columns,
+    // max(excluded), min(excluded), workgroups and LDS bytes of the count launch, a row that attains the maximum
+    int64_t buffer[8] = {};
 };
 
 struct sknnr_index {
@@ -387,6 +390,16 @@ struct sknnr_index {
     DevBuf<int> g_codes;
     bool has_groups = false;
     long g_largest = 0, g_count = 0;  // rows of the largest group, number of groups
+    // buffered leave-out (buffer.hip.h): the (3, n_ref) positions and the radius, set by sknnr_index_set_buffer; and
+    // excluded[] under the masks now set, counted once per change of either mask (ensure_excluded)
+    DevBuf<double> b_pos;
+    bool has_buffer = false;
+    int b_cols = 0;
+    double b_radius = 0.0, b_r2 = 0.0;
+    DevBuf<unsigned long long> b_excl;
+    bool b_excl_valid = false;
+    long b_max = 0, b_min = 0, b_argmax = 0;  // of excluded[]; the first row that attains the maximum
+    long b_count_wg = 0;                      // workgroups of the launch that counted them
     // integer pre-filter of the weighted-Hamming search (hamming.hip.h): 16-bit ids / weights, two trees per dword
     bool h16_ok = false;           // every reference id is an integer in [0, 65535]
     int h_tp = 0, h_ref_pad = 0;   // tree pairs; reference rows padded to the step of the kernel
@@ -3042,6 +3055,7 @@ extern "C" int sknnr_index_set_groups(sknnr_index* ix, const int32_t* codes, int
         std::lock_guard<std::mutex> lock(ix->mtx);
         ix->has_groups = false;
         ix->g_largest = ix->g_count = 0;
+        ix->b_excl_valid = false;
         return SKNNR_OK;
     }
     if (n != ix->n_ref) return fail(SKNNR_ERR_INVALID, "codes must hold one group code per reference row (%ld), got %ld", ix->n_ref, (long)n);
@@ -3064,23 +3078,94 @@ extern "C" int sknnr_index_set_groups(sknnr_index* ix, const int32_t* codes, int
     ix->g_largest = largest;
     ix->g_count = count;
     ix->has_groups = true;
+    ix->b_excl_valid = false;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_index_set_buffer(sknnr_index* ix, const double* coords, int64_t n, int32_t c, double radius) {
+    if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (!coords) {  // clear
+        std::lock_guard<std::mutex> lock(ix->mtx);
+        ix->has_buffer = false;
+        ix->b_cols = 0;
+        ix->b_radius = ix->b_r2 = 0.0;
+        ix->b_excl_valid = false;
+        return SKNNR_OK;
+    }
+    if (n != ix->n_ref) return fail(SKNNR_ERR_INVALID, "coords must hold one position per reference row (%ld), got %ld", ix->n_ref, (long)n);
+    if (c < 1 || c > kPosCols) return fail(SKNNR_ERR_INVALID, "positions have 1 to %d columns, got %d", kPosCols, (int)c);
+    if (!std::isfinite(radius) || radius < 0.0) return fail(SKNNR_ERR_INVALID, "radius must be finite and >= 0, got %g", radius);
+    // (3, n) column-major like refT; a missing column is +0.0 for every row
+    std::vector<double> pos((size_t)kPosCols * (size_t)n, 0.0);
+    for (int64_t i = 0; i < n; ++i)
+        for (int j = 0; j < c; ++j) {
+            const double v = coords[i * c + j];
+            if (!std::isfinite(v)) return fail(SKNNR_ERR_INVALID, "positions must be finite, got %g at row %ld, column %d", v, (long)i, j);
+            pos[(size_t)j * (size_t)n + (size_t)i] = v;
+        }
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());  // (a grouped call on another stream may still read the positions held so far)
+    HIP_TRY(ix->b_pos.ensure(pos.size()));
+    HIP_TRY(hipMemcpy(ix->b_pos.p, pos.data(), pos.size() * sizeof(double), hipMemcpyHostToDevice));
+    ix->b_cols = c;
+    ix->b_radius = radius;
+    ix->b_r2 = radius * radius;
+    ix->has_buffer = true;
+    ix->b_excl_valid = false;
     return SKNNR_OK;
 }
 
 namespace {
 
+// excluded[] under the masks now set, counted by buffer_count_kernel once per change of either mask: b_excl on the
+// device, its extremes on the host.  Synchronous (the counts come back for the extremes); the caller holds the lock.
+int ensure_excluded(sknnr_index* ix) {
+    if (ix->b_excl_valid) return SKNNR_OK;
+    const long n = ix->n_ref;
+    HIP_TRY(ix->b_excl.ensure((size_t)n));
+    BufferCountArgs a{};
+    a.pos = ix->has_buffer ? ix->b_pos.p : nullptr;
+    a.codes = ix->has_groups ? ix->g_codes.p : nullptr;
+    a.r2 = ix->b_r2;
+    a.n_ref = n;
+    a.out = ix->b_excl.p;
+    HIP_TRY(launch::buffer_count(a, nullptr));
+    std::vector<unsigned long long> h((size_t)n);
+    HIP_TRY(hipMemcpy(h.data(), ix->b_excl.p, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    long mx = 0, mn = n, arg = 0;
+    for (long i = 0; i < n; ++i) {
+        const long v = (long)h[(size_t)i];
+        if (v > mx) mx = v, arg = i;
+        mn = std::min(mn, v);
+    }
+    const BufferCountGrid g = buffer_count_grid(n);
+    ix->b_max = mx;
+    ix->b_min = mn;
+    ix->b_argmax = arg;
+    ix->b_count_wg = g.row_blocks * g.splits;
+    ix->b_excl_valid = true;
+    return SKNNR_OK;
+}
+
 // Device-resident core of sknnr_kneighbors_grouped: reference rows [o->row_offset, + nq), outputs on the device.  One
 // launch: passes of kGroupNq rows, one workgroup each, taken grid-stride by at most kScanGridWg workgroups; never sliced.
+// The masks set on the handle (groups, buffer, both) pick the instantiation.
 int run_grouped_device(sknnr_index* ix, long nq, const sknnr_query_opts* o, double* d_dist, long* d_idx, hipStream_t st) {
     zero_records(ix);
+    const int mask = (ix->has_groups ? kMaskGroups : 0) | (ix->has_buffer ? kMaskBuffer : 0);
     // (every accepted call fits: the LDS grows with min(d, kScanColChunk) and k <= kScanMaxKK only)
-    static_assert(group_scan_bytes(kScanColChunk, kScanMaxKK) <= kLdsLimit, "the widest grouped call fits a workgroup's LDS");
-    const size_t sh = group_scan_bytes(ix->d, o->n_neighbors);
+    static_assert(group_scan_bytes(kScanColChunk, kScanMaxKK, kMaskGroups) <= kLdsLimit &&
+                      group_scan_bytes(kScanColChunk, kScanMaxKK, kMaskBoth) <= kLdsLimit,
+                  "the widest grouped call fits a workgroup's LDS, the positions of a buffered one included");
+    const size_t sh = group_scan_bytes(ix->d, o->n_neighbors, mask);
     if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));  // (the staged outputs of host calls are workspace)
     GroupScanArgs a{};
     a.s = make_select_args(ix, o, o->n_neighbors, nullptr, nq, d_dist, d_idx);
     a.refT = ix->refT.p;
-    a.codes = ix->g_codes.p;
+    a.codes = ix->has_groups ? ix->g_codes.p : nullptr;
+    a.pos = ix->has_buffer ? ix->b_pos.p : nullptr;
+    a.r2 = ix->b_r2;
     sknnr_index::CallTiming& ct = ix->timing[ix->timing_next];
     ix->timing_next = (ix->timing_next + 1) % sknnr_index::kTimingRing;
     resolve_call(ix, ct);
@@ -3095,7 +3180,14 @@ int run_grouped_device(sknnr_index* ix, long nq, const sknnr_query_opts* o, doub
     const long blocks = std::max<long>(1, std::min<long>(passes, kScanGridWg));
     const int64_t rec[8] = {o->formula + 1, o->n_neighbors, blocks, (int64_t)sh, nq, 1, ix->g_largest, ix->g_count};
     std::copy(std::begin(rec), std::end(rec), ix->last.grouped);
-    HIP_TRY(launch::group_scan(o->formula, ix->d > kScanColChunk, a, blocks, sh, st));  // wide rows: in column chunks
+    // (groups alone are never counted by a search call: their record shows the largest group as max(excluded))
+    const bool counted = ix->b_excl_valid;
+    const int64_t brec[8] = {mask, ix->has_buffer ? ix->b_cols : 0, counted ? ix->b_max : ix->g_largest, counted ? ix->b_min : 0,
+                             counted ? ix->b_count_wg : 0, counted ? (int64_t)kCountLdsBytes : 0, counted ? ix->b_argmax : 0, 0};
+    std::copy(std::begin(brec), std::end(brec), ix->last.buffer);
+    const bool chunked = ix->d > kScanColChunk;  // wide rows: in column chunks
+    if (mask == kMaskGroups) HIP_TRY(launch::group_scan(o->formula, chunked, a, blocks, sh, st));
+    else HIP_TRY(launch::buffer_scan(mask, o->formula, chunked, a, blocks, sh, st));
     HIP_TRY(hipEventRecord(ct.e1, st));
     ct.pending = true;
     HIP_TRY(hipEventRecord(ix->ev_ws, st));
@@ -3124,15 +3216,26 @@ extern "C" int sknnr_kneighbors_grouped(sknnr_index* ix, int64_t nq, const sknnr
     if (std::abs(o->decimals) > 300) return fail(SKNNR_ERR_INVALID, "decimals out of range");
     if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
     std::lock_guard<std::mutex> lock(ix->mtx);
-    if (!ix->has_groups) return fail(SKNNR_ERR_INVALID, "sknnr_kneighbors_grouped needs sknnr_index_set_groups first");
+    if (!ix->has_groups && !ix->has_buffer) return fail(SKNNR_ERR_INVALID, "sknnr_kneighbors_grouped needs sknnr_index_set_groups first");
     const long n_fit = ix->n_ref;
     if (o->row_offset < 0 || o->row_offset + nq > n_fit)
         return fail(SKNNR_ERR_INVALID, "grouped query rows [%ld, %ld) outside the %ld reference rows", (long)o->row_offset,
                     (long)(o->row_offset + nq), n_fit);
-    if (o->n_neighbors > n_fit - ix->g_largest)
-        return fail(SKNNR_ERR_K_TOO_LARGE,
-                    "Expected n_neighbors <= n_samples_fit - largest group, but n_neighbors = %d, n_samples_fit = %ld, largest group = %ld",
-                    o->n_neighbors, n_fit, ix->g_largest);
+    if (!ix->has_buffer) {  // max(excluded) is the largest group
+        if (o->n_neighbors > n_fit - ix->g_largest)
+            return fail(SKNNR_ERR_K_TOO_LARGE,
+                        "Expected n_neighbors <= n_samples_fit - largest group, but n_neighbors = %d, n_samples_fit = %ld, largest group = %ld",
+                        o->n_neighbors, n_fit, ix->g_largest);
+    } else {
+        HIP_TRY(hipSetDevice(ix->device));
+        int rc = ensure_excluded(ix);
+        if (rc) return rc;
+        if (o->n_neighbors > n_fit - ix->b_max)
+            return fail(SKNNR_ERR_K_TOO_LARGE,
+                        "Expected n_neighbors <= n_samples_fit - max(excluded), but n_neighbors = %d, n_samples_fit = %ld, "
+                        "max(excluded) = %ld (row %ld)",
+                        o->n_neighbors, n_fit, ix->b_max, ix->b_argmax);
+    }
     if (o->n_neighbors > kScanMaxKK)
         return fail(SKNNR_ERR_UNSUPPORTED, "n_neighbors = %d exceeds the HIP backend's limit of %d%s", o->n_neighbors, kScanMaxKK, "");
     if (nq == 0) return SKNNR_OK;
@@ -3156,6 +3259,22 @@ extern "C" int sknnr_kneighbors_grouped(sknnr_index* ix, int64_t nq, const sknnr
     return SKNNR_OK;
 }
 
+extern "C" int sknnr_buffer_counts(sknnr_index* ix, int64_t* out, int32_t mem, void* stream) {
+    if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (!out) return fail(SKNNR_ERR_INVALID, "out is NULL");
+    if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (!ix->has_groups && !ix->has_buffer)
+        return fail(SKNNR_ERR_INVALID, "sknnr_buffer_counts needs sknnr_index_set_buffer or sknnr_index_set_groups first");
+    HIP_TRY(hipSetDevice(ix->device));
+    int rc = ensure_excluded(ix);
+    if (rc) return rc;
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "excluded[] is copied out as it is");
+    const size_t bytes = (size_t)ix->n_ref * sizeof(int64_t);
+    if (mem == SKNNR_MEM_DEVICE) HIP_TRY(hipMemcpyAsync(out, ix->b_excl.p, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    else HIP_TRY(hipMemcpy(out, ix->b_excl.p, bytes, hipMemcpyDeviceToHost));
+    return SKNNR_OK;
+}
 
 // ----------------------------------------------------------------------------------------
 // nodata rows: the mask alone, and the masked calls
@@ -4719,6 +4838,7 @@ extern "C" int sknnr_debug_last_plan(const sknnr_index* ix, int64_t out[8]) { re
 extern "C" int sknnr_debug_last_planes(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last_planes; }); }
 extern "C" int sknnr_debug_last_weight_law(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last_law; }); }
 extern "C" int sknnr_debug_last_grouped(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last.grouped; }); }
+extern "C" int sknnr_debug_last_buffer(const sknnr_index* ix, int64_t out[8]) { return copy_record(ix, out, [](sknnr_index* i) { return i->last.buffer; }); }
 
 // The mask, the scan and the compaction alone, on the caller's device pointers (run_device_masked's sequence without the
 // search): the block offsets and the ranks, which no search result shows, come back to the host.
