@@ -870,6 +870,64 @@ int sknnr_stream_get_zonal(sknnr_stream* stream, int64_t* acc, int64_t* hist);
 int sknnr_debug_last_zonal(const sknnr_index* index, int64_t out[8]);
 int sknnr_debug_zonal_geometry(int32_t c, int64_t out[4]);
 
+/* ---- distance domain (where the map extrapolates) -------------------------------------------------- */
+
+/*
+ * Distance domain.  THE CONTRACT, stated here once (sknnr_amd/csrc/domain.hip.h implements it, tests/_domain.py restates
+ * it in numpy).  A pixel is placed within a table of reference-to-reference distances by the distance to its r-th
+ * neighbour, in the estimator's own metric.
+ *   Table T      m float64 values, 1 <= m <= 2^31 - 1, each finite and >= 0 (-0.0 is 0), non-decreasing.  Anything else
+ *                is refused on the host with SKNNR_ERR_INVALID before any device work.
+ *   Rank r       1 <= r <= k.  The pixel's score is s = dist[i, r - 1], the float64 distance the search returned, after
+ *                sknnr's reorder when the call uses it.
+ *   Code         uint8.  c = #{ j : T[j] < s } -- a strict comparison: np.searchsorted(T, s, "left") -- and
+ *                code = (100 * c) / m in 64-bit integer arithmetic, so 0 <= code <= 100, and code == 100 exactly when
+ *                s > T[m - 1].  A score equal to a table entry is not above it.  s = +inf gives 100; s <= 0 (-0.0
+ *                included) gives 0.
+ *   Nodata       a NaN s marks a nodata pixel (a row masked by sknnr_stream_set_nodata has NaN distances in the full
+ *                layout).  Its code is 255; it enters the nodata count and nothing else.
+ *   Threshold    theta, optional, finite and >= 0: a pixel is BEYOND when s > theta (false for NaN).
+ *   Accumulators acc, int64[103]: acc[0 .. 100] the histogram of codes over the pixels that are not nodata, acc[101] the
+ *                beyond pixels (0 without a threshold), acc[102] the nodata pixels.  Integer adds only: the results do
+ *                not depend on launch geometry, tile cuts or arrival order, and two runs produce the same bytes.
+ *   mask_beyond  (streams with predictions, and only with a threshold): the float64 prediction row of a beyond pixel
+ *                becomes NaN in every column -- t targets, or the n_out planes of an output plan -- before the typed
+ *                conversion and before the zonal tally, so the pixel stores the fill and enters no zonal table, exactly
+ *                as a nodata pixel does.  Its indices, distances, ids and the usage tally are untouched.
+ * Everything the pushes deliver without the lane stays bit for bit when mask_beyond is off, and a stream on which
+ * sknnr_stream_set_domain is never called enqueues exactly what it did before the entry point existed.
+ *
+ * sknnr_domain_from_neighbors: one-shot.  dist (nq, k), codes (nq, or NULL: tallies only) and acc live in `mem` (host
+ *   arrays are staged; device arrays are used in place, enqueued on `stream`); table is always a HOST array.  The table,
+ *   the rank and the threshold are checked first, before the handle is even looked at.  accumulate = 0 zeroes acc first;
+ *   accumulate = 1 adds to what it holds.  nq == 0 is allowed.  The handle gives the record and the staging buffers only.
+ * sknnr_stream_set_domain: allowed only before the first push.  Checks the table and the rank against the stream's k,
+ *   uploads the table once and zeroes the accumulators on the handle.  mask_beyond needs a stream opened with
+ *   predictions, and a threshold.  From then on the stream keeps the search's distances even when none leave, and every
+ *   tile's full-layout distances are coded on the device behind its search (and, with the mask, behind its reduction).
+ * sknnr_stream_next_domain_out: the HOST destination of the NEXT push's code plane: nq bytes in pixel order, in either
+ *   layout, filled under the same lifetime rule as that push's own outputs (complete after a flush).  Optional: a push
+ *   without it tallies only.  A push with another nq than it named is SKNNR_ERR_INVALID.  nq == 0 is accepted and ignored.
+ * sknnr_stream_get_domain: flushes the pipeline (as sknnr_stream_flush) and copies the accumulators to a HOST array.  May
+ *   be called more than once; the accumulators keep running.
+ * sknnr_debug_last_domain: debug only; synchronises the device.  The last sknnr_domain_from_neighbors call, or -- after
+ *   sknnr_stream_set_domain -- the stream so far:
+ *   out[0] 1 = a domain kernel ran         out[1] pixels its workgroups took     out[2] k      out[3] rank     out[4] m
+ *   out[5] nodata pixels                   out[6] global atomics issued on the accumulators
+ *   out[7] prediction rows blanked by the mask
+ * sknnr_debug_domain_geometry: no device work.  out[0] pixels a workgroup takes, out[1] the most entries of its skeleton
+ *   of the table, out[2] table entries between two skeleton entries at m, out[3] skeleton entries in use at m.
+ */
+int sknnr_domain_from_neighbors(sknnr_index* index, const double* dist, int64_t nq, int32_t k, int32_t rank,
+                                const double* table, int64_t m, int32_t has_threshold, double threshold, uint8_t* codes,
+                                int64_t* acc, int32_t accumulate, int32_t mem, void* stream);
+int sknnr_stream_set_domain(sknnr_stream* stream, const double* table, int64_t m, int32_t rank, int32_t has_threshold,
+                            double threshold, int32_t mask_beyond);
+int sknnr_stream_next_domain_out(sknnr_stream* stream, uint8_t* out, int64_t nq);
+int sknnr_stream_get_domain(sknnr_stream* stream, int64_t acc[103]);
+int sknnr_debug_last_domain(const sknnr_index* index, int64_t out[8]);
+int sknnr_debug_domain_geometry(int64_t m, int64_t out[4]);
+
 /*
  * Debug only.  The output side of the last tile the handle's host pipeline submitted, so that a test can prove that the
  * device converted it and that only the narrow bytes were copied.  Host memory, no device work:

@@ -28,6 +28,7 @@ from sklearn.utils.validation import _is_arraylike, check_is_fitted, validate_da
 from . import _config, _native
 from ._engine import KNNEngine, default_device, is_torch_cuda_tensor
 from ._usage import NeighborUsage
+from ._domain import DistanceDomain
 from ._zonal import ZonalStats
 from .weights import DistanceWeights
 
@@ -1056,6 +1057,79 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         except _native.HipBackendError as err:
             _reraise(err, self)
 
+    # -- distance domain: where the map extrapolates -------------------------------------------------
+    def distance_domain(self, groups=None, *, buffer=None, rank=1, p=None, threshold=None):
+        """A :class:`sknnr_amd.DistanceDomain` of this estimator's reference plots: its table is the sorted distance of
+        every fitted row to its ``rank``-th :meth:`independent_kneighbors` neighbour -- itself (with neither ``groups``
+        nor ``buffer``: every row a group of its own), its group or the plots inside ``buffer`` left out -- in the
+        estimator's own metric.  ``p`` (``0 < p < 1``): the threshold is the
+        ``1 - p`` quantile of the table (``np.quantile``), so about a share ``p`` of the plots lie beyond it, as
+        yaImpute's "notably distant" targets are defined; ``threshold``: a distance of the caller's instead.  The two
+        are mutually exclusive; with neither the object has no threshold and counts nothing as beyond."""
+        if isinstance(rank, bool) or int(rank) != rank or int(rank) < 1:
+            raise ValueError(f"rank must be an integer >= 1, got {rank!r}")
+        if p is not None and threshold is not None:
+            raise ValueError("p and threshold are mutually exclusive: p derives the threshold from the table")
+        if p is not None and not 0.0 < float(p) < 1.0:
+            raise ValueError(f"p must lie inside (0, 1), got {p!r}")
+        rank = int(rank)
+        check_is_fitted(self, "_fit_X")
+        if groups is None and buffer is None:  # (self left out: every row a group of its own)
+            groups = np.arange(self.n_samples_fit_)
+        dist, _ = self.independent_kneighbors(groups, n_neighbors=rank, buffer=buffer)
+        table = np.sort(np.asarray(dist, dtype=np.float64)[:, rank - 1])
+        if p is not None:
+            threshold = float(np.quantile(table, 1.0 - float(p)))
+        return DistanceDomain(table, threshold=threshold, rank=rank)
+
+    def _domain_scores(self, domain, dist):
+        """The codes of neighbours already found, their tallies added to ``domain``."""
+        if not isinstance(domain, DistanceDomain):
+            raise TypeError(f"domain must be a sknnr_amd.DistanceDomain, got {type(domain).__name__}")
+        k = dist.shape[1]
+        if domain.rank > k:
+            raise ValueError(f"domain.rank={domain.rank} is above n_neighbors={k}")
+        try:
+            codes, acc = self.engine_.domain_from_neighbors(dist, domain.table, domain.rank, domain.threshold)
+        except _native.HipBackendError as err:
+            _reraise(err, self)
+        domain._add(acc)
+        return codes
+
+    def domain_scores(self, domain, X=None, n_neighbors=None):
+        """The uint8 distance-domain codes of ``kneighbors(X, n_neighbors)`` (deterministic ordering) within ``domain``
+        (a :class:`sknnr_amd.DistanceDomain`), computed on the device; the tallies are added to ``domain``.  ``X=None``:
+        of every fitted row's neighbours, itself excluded.  For a raster, pass ``domain=`` to :meth:`kneighbors_chunks`
+        / :meth:`predict_chunks` instead: the codes then cost one byte per pixel of transfer and no second pass."""
+        if not isinstance(domain, DistanceDomain):
+            raise TypeError(f"domain must be a sknnr_amd.DistanceDomain, got {type(domain).__name__}")
+        if domain.rank > self._resolve_k(n_neighbors):
+            raise ValueError(f"domain.rank={domain.rank} is above n_neighbors={self._resolve_k(n_neighbors)}")
+        dist, _ = self.kneighbors(X, n_neighbors=n_neighbors)
+        return self._domain_scores(domain, dist)
+
+    def _check_domain(self, domain, domain_out, k, beyond=False, host_callable=False):
+        """Every refusal of ``domain`` / ``domain_out`` / the mask, before any device work."""
+        if domain is None:
+            if domain_out is not None:
+                raise ValueError("domain_out needs domain: the DistanceDomain whose codes it receives")
+            if beyond:
+                raise ValueError("beyond='nodata' needs domain: a DistanceDomain with a threshold")
+            return
+        if not isinstance(domain, DistanceDomain):
+            raise TypeError(f"domain must be a sknnr_amd.DistanceDomain, got {type(domain).__name__}")
+        if host_callable:
+            self._refuse_callable_weights("domain is")
+        self._check_stream_supported("domain is")
+        if domain.rank > k:
+            raise ValueError(f"domain.rank={domain.rank} is above n_neighbors={k}")
+        if beyond and domain.threshold is None:
+            raise ValueError("beyond='nodata' needs a DistanceDomain with a threshold")
+        if domain_out is not None and (not isinstance(domain_out, np.ndarray) or domain_out.dtype != np.uint8
+                                       or domain_out.ndim != 1 or not domain_out.flags.c_contiguous
+                                       or not domain_out.flags.writeable):
+            raise ValueError("domain_out must be a writable C-contiguous uint8 (N_total,) array, one element per pixel")
+
     # -- streamed tiles (raster ingestion; REF docs/pages/usage.md:101-128) --------------------
     def _check_stream_supported(self, feature):
         """The nodata mask, the band-first transposes and the typed conversions (``feature``: "nodata is", "layout='bands'
@@ -1074,7 +1148,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
     def _stream_tiles(self, tiles, validate, k, *, apply_affine, weights, return_distance,
                       use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False, output=None,
-                      statistic=None, id_table=None, fill_id=-1, neighbors=False, usage=None, zones=None, zonal=None):
+                      statistic=None, id_table=None, fill_id=-1, neighbors=False, usage=None, zones=None, zonal=None,
+                      domain=None, domain_out=None, beyond=False):
         """Push host tiles through one native query stream.  Returns (dist, idx, pred) arrays over all
         pushed rows (pieces of ``out`` when given, else concatenated).  ``nodata`` (float64, one value per column of the
         validated tiles): rows holding one are masked on the device and get ``fill_index`` / NaN.
@@ -1101,10 +1176,17 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
         ``zones`` / ``zonal`` (an iterable in lockstep with ``tiles``, a :class:`sknnr_amd.ZonalStats`; predictions with
         an integer ``pred_dtype`` only): the stream tallies every tile's predictions by zone on the device and the call
-        adds the result to ``zonal``; nothing else about the call changes."""
+        adds the result to ``zonal``; nothing else about the call changes.
+
+        ``domain`` (a :class:`sknnr_amd.DistanceDomain`, checked by :meth:`_check_domain`): the stream codes every tile's
+        distances against its table on the device and the call adds the tallies to it; ``domain_out`` (uint8, one element
+        per pixel of the whole call) receives the codes tile by tile; ``beyond`` (predictions only): the predictions of
+        the pixels beyond the threshold become NaN on the device, in front of the conversion and the zonal tally."""
         if usage is not None:
             self._check_stream_supported("usage is")
             usage._check(self.n_samples_fit_, k)  # (a mismatch is refused before any device work)
+        if domain is not None:
+            self._check_domain(domain, domain_out, k)
         zonal_binding = None
         if zonal is not None:
             self._check_stream_supported("zonal is")
@@ -1200,7 +1282,9 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              **({} if id_table is None else dict(id_table=id_table, fill_id=fill_id)),
                                              **({} if usage is None else dict(tally=True)),
                                              **({} if zonal is None else
-                                                dict(zonal=(zonal.n_zones, zonal.n_classes(zonal_binding[0])))))
+                                                dict(zonal=(zonal.n_zones, zonal.n_classes(zonal_binding[0])))),
+                                             **({} if domain is None else
+                                                dict(domain=(domain.table, domain.rank, domain.threshold, bool(beyond)))))
                 if first.dtype != stream_dtype:
                     if stream_dtype != np.float64:
                         raise ValueError(f"the tiles of one streamed call must share an element type: got {first.dtype} "
@@ -1225,6 +1309,10 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
                 if zonal is not None:
                     stream.next_zones(normalize_zone_tile(tile_zones, n))
+                if domain_out is not None:
+                    if domain_out.size < row + n:
+                        raise ValueError(f"domain_out holds {domain_out.size} pixels: the tiles hold at least {row + n}")
+                    stream.next_domain_out(domain_out[row:row + n])
                 got = (stream.push_planes if bands else stream.push)(
                     tile, out_idx=window(o_idx, k, idx_dt),
                     out_dist=window(o_dist, k, dist_dt) if return_distance else None,
@@ -1234,7 +1322,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 row += n
             if zonal is not None and next(zones, None) is not None:
                 raise ValueError(_ZONES_LONG)
-            tallied = zoned = None
+            tallied = zoned = placed = None
             if stream is not None:
                 done, stream = stream, None
                 try:
@@ -1242,8 +1330,12 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                         tallied = done.tally()
                     if zonal is not None:
                         zoned = done.zonal()
+                    if domain is not None:
+                        placed = done.domain()
                 finally:
                     done.close()
+            if placed is not None:  # (only a call that came through whole is added)
+                domain._add(placed)
             if zonal is not None:  # (only a call that came through whole is added)
                 zonal._bind(*zonal_binding)
                 if zoned is not None:
@@ -1310,7 +1402,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
 
     def kneighbors_chunks(self, tiles, n_neighbors=None, return_distance=True, return_dataframe_index=False,
                           use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1, layout="rows",
-                          index_dtype=None, distance_dtype=None, usage=None):
+                          index_dtype=None, distance_dtype=None, usage=None, domain=None, domain_out=None):
         """``kneighbors`` over an iterable of host tiles ``(n_i, n_features)`` -- windows of a raster,
         slices of a ``numpy.memmap`` -- as ONE logical call: the copy-in / kernels / copy-out pipeline
         stays full across tiles and row positions count over all tiles, so the result equals
@@ -1340,10 +1432,20 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         row and rank the pixels it served, and the largest distance it was imputed over; masked pixels contribute
         nothing -- and the call adds the result to the object.  Everything the call returns or writes is bit-identical to
         the call without it; no index crosses PCIe for the tally.  The tally is over row positions whatever
-        ``return_dataframe_index`` says.  Refused under the host-side tie policies."""
+        ``return_dataframe_index`` says.  Refused under the host-side tie policies.
+
+        ``domain`` (a :class:`sknnr_amd.DistanceDomain`): every pixel's distance to its ``domain.rank``-th neighbour is
+        placed within the domain's table on the device -- the percentage of table entries strictly below it, 0 .. 100,
+        100 exactly when it is above them all, 255 for a masked pixel -- and the call adds the histogram of those codes
+        and the count of pixels beyond the threshold to the object.  ``domain_out``: a preallocated C-contiguous uint8
+        ``(N_total,)`` array (e.g. a memmap) that receives the codes tile by tile, in pixel order in either layout; one
+        byte per pixel crosses PCIe for it, and nothing without it.  Everything the call returns or writes is
+        bit-identical to the call without the keywords.  Refused under the host-side tie policies; ``domain.rank`` above
+        ``n_neighbors`` and a ``domain_out`` of another type, too short or without ``domain`` are ``ValueError``."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         k = self._resolve_k(n_neighbors)
+        self._check_domain(domain, domain_out, k)
         if nodata is not None:
             nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
         output = self._neighbor_output(index_dtype, distance_dtype, return_distance, return_dataframe_index, fill_index,
@@ -1359,7 +1461,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                           use_deterministic_ordering=use_deterministic_ordering, out=o, owner=None,
                                           nodata=nodata, fill_index=-1 if return_dataframe_index else fill_index,
                                           bands=bands, output=output, id_table=table, fill_id=fill_index,
-                                          **({} if usage is None else dict(usage=usage)))
+                                          **({} if usage is None else dict(usage=usage)),
+                                          **({} if domain is None else dict(domain=domain, domain_out=domain_out)))
         return self._finish_chunks(dist, idx, return_distance, return_dataframe_index,
                                    fill_index=None if nodata is None else fill_index, on_device=table is not None)
 
@@ -1415,7 +1518,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
     def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
                        out_nodata=None, statistic=None, return_neighbors=False, return_distance=True,
                        return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
-                       distance_dtype=None, outputs=None, usage=None, zones=None, zonal=None):
+                       distance_dtype=None, outputs=None, usage=None, zones=None, zonal=None, domain=None, domain_out=None,
+                       beyond="keep"):
         """``predict`` over an iterable of host tiles as one streamed call; ``out``: preallocated
         ``(n_rows, n_targets)`` float64 array (e.g. a memmap; float32 results are held exactly).  ``nodata`` as in
         :meth:`kneighbors_chunks`: masked rows are predicted NaN.  ``layout="bands"``: band-first tiles as in
@@ -1478,7 +1582,16 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         required (a float atomic sum would depend on arrival order); nodata pixels and zone codes outside
         ``[0, n_zones)`` contribute nothing.  The call adds the result to ``zonal`` and returns and writes exactly what
         it does without it; it works with ``usage``, ``nodata``, ``outputs``, ``statistic`` and ``return_neighbors``.
-        Refused with callable weights and under the host-side tie policies."""
+        Refused with callable weights and under the host-side tie policies.
+
+        ``domain`` / ``domain_out``: as in :meth:`kneighbors_chunks` -- the distances the predictions are reduced from are
+        placed within the :class:`sknnr_amd.DistanceDomain`'s table on the device, with or without ``return_neighbors``,
+        and ``domain_out`` (uint8, ``(N_total,)``) receives the codes.  ``beyond="nodata"`` (the domain needs a
+        threshold): the predictions of the pixels whose distance is above it are blanked on the device before they are
+        stored or enter ``zonal`` -- NaN, or ``out_nodata`` in a typed output, which an integer ``out_dtype`` then needs
+        -- exactly as a nodata pixel's are; their neighbours, distances, ``usage`` and codes are untouched.  With
+        ``beyond="keep"`` (the default) the call returns and writes exactly what it does without the keywords.  Refused
+        with callable weights and under the host-side tie policies."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         neighbors = self._neighbor_request(return_neighbors, return_distance, return_dataframe_index, neighbors_out,
@@ -1488,6 +1601,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             extra["usage"] = usage
         if zones is not None or zonal is not None:
             extra.update(zones=zones, zonal=zonal)
+        if domain is not None or domain_out is not None or beyond != "keep":
+            extra.update(domain=domain, domain_out=domain_out, beyond=beyond)
         statistic = resolve_statistic(statistic, outputs, self._n_targets())
         if nodata is not None:
             nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
@@ -1498,10 +1613,13 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                     typed=(out_dtype, scale, offset, out_nodata), statistic=statistic, **extra)
 
     def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None, bands=False, typed=None,
-                        statistic=None, neighbors=None, usage=None, zones=None, zonal=None):
+                        statistic=None, neighbors=None, usage=None, zones=None, zonal=None, domain=None, domain_out=None,
+                        beyond="keep"):
         """``neighbors``: :meth:`_neighbor_request`, or None -- predictions alone, exactly as before the keyword existed.
         ``usage``: a :class:`sknnr_amd.NeighborUsage` the stream's tally is added to, or None.  ``zones`` / ``zonal``: the
-        tiles' zone codes and the :class:`sknnr_amd.ZonalStats` the stream's zonal tables are added to, or None both."""
+        tiles' zone codes and the :class:`sknnr_amd.ZonalStats` the stream's zonal tables are added to, or None both.
+        ``domain`` / ``domain_out`` / ``beyond``: the :class:`sknnr_amd.DistanceDomain` the stream's codes are tallied into,
+        the plane that receives them, and "nodata" to blank the predictions beyond its threshold."""
         weights = "uniform" if self.weights is None else self.weights
         # A distance-weight law (sknnr_amd.weights) is evaluated on the device inside the stream, so it goes wherever
         # "distance" goes; any other callable runs on the host and keeps every refusal below.
@@ -1513,12 +1631,18 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 self._refuse_callable_weights("usage is")
             self._check_stream_supported("usage is")
             usage._check(self.n_samples_fit_, self.n_neighbors)
+        if beyond not in ("keep", "nodata"):
+            raise ValueError(f"beyond must be 'keep' or 'nodata', got {beyond!r}")
+        blank = beyond == "nodata"
+        self._check_domain(domain, domain_out, self.n_neighbors, blank, host_callable)  # (every refusal before any device work)
+        domain_extra = {} if domain is None else dict(domain=domain, domain_out=domain_out, beyond=blank)
         plan = statistic if isinstance(statistic, OutputPlan) else None
         flat = self._y.ndim == 1 and (plan is None or plan.per_target)  # the result is 1-D
         if typed is not None:
             n_targets = plan.n_out if plan is not None else (1 if self._y.ndim == 1 else self._y.shape[1])
             # (a compact law can give an all-zero row: NaN predictions occur without any mask)
-            output = normalize_typed_output(*typed, n_targets, nodata is not None or (law and weights.can_vanish))
+            # (so can the domain's mask: a blanked pixel is stored as a nodata pixel is)
+            output = normalize_typed_output(*typed, n_targets, nodata is not None or (law and weights.can_vanish) or blank)
         zonal_extra = {}
         if zones is not None or zonal is not None:  # (every refusal before any device work)
             if zones is None or zonal is None:
@@ -1540,7 +1664,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 self._refuse_callable_weights("return_neighbors is")
             return self._predict_chunks_neighbors(tiles, validate, weights, neighbors, apply_affine=apply_affine, out=out,
                                                   owner=owner, nodata=nodata, bands=bands, output=output,
-                                                  statistic=statistic, usage=usage, **zonal_extra)
+                                                  statistic=statistic, usage=usage, **zonal_extra, **domain_extra)
         if host_callable and output:
             self._refuse_callable_weights("typed outputs are")
         if host_callable and bands:
@@ -1570,13 +1694,14 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                             weights=weights, return_distance=False,
                                             use_deterministic_ordering=True, out=o, owner=owner, nodata=nodata,
                                             bands=bands, output=output, statistic=statistic,
-                                            **({} if usage is None else dict(usage=usage)), **zonal_extra)
+                                            **({} if usage is None else dict(usage=usage)), **zonal_extra, **domain_extra)
             if out is None and not output and statistic is None:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
                 pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         return pred.reshape(-1) if flat else pred
 
     def _predict_chunks_neighbors(self, tiles, validate, weights, neighbors, *, apply_affine, out, owner, nodata, bands,
-                                  output, statistic, usage=None, zones=None, zonal=None):
+                                  output, statistic, usage=None, zones=None, zonal=None, domain=None, domain_out=None,
+                                  beyond=False):
         """``predict_chunks(return_neighbors=True)``: one stream with all three outputs.  ``output``: the predictions'
         typed output (or None); the neighbours' types and the id table are worked out here, as ``kneighbors_chunks``
         does, every refusal before any device work."""
@@ -1596,7 +1721,9 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              owner=owner, nodata=nodata, fill_index=-1 if ids else fill_index, bands=bands,
                                              output=merged, statistic=statistic, id_table=table, fill_id=fill_index,
                                              neighbors=True, **({} if usage is None else dict(usage=usage)),
-                                             **({} if zonal is None else dict(zones=zones, zonal=zonal)))
+                                             **({} if zonal is None else dict(zones=zones, zonal=zonal)),
+                                             **({} if domain is None else
+                                                dict(domain=domain, domain_out=domain_out, beyond=beyond)))
         if out is None and not output and statistic is None:  # (as without neighbours: float32 where scikit-learn returns it)
             pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         if self._y.ndim == 1 and not (isinstance(statistic, OutputPlan) and not statistic.per_target):
@@ -1819,6 +1946,24 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         check_is_fitted(self, "regressor_")
         return self.regressor_.independent_neighbor_usage(groups, n_neighbors, buffer=buffer)
 
+    def distance_domain(self, groups=None, *, buffer=None, rank=1, p=None, threshold=None):
+        """:meth:`RawKNNRegressor.distance_domain` of the fitted regressor: the table holds distances in the transformed
+        space the estimator searches in."""
+        check_is_fitted(self, "regressor_")
+        return self.regressor_.distance_domain(groups, buffer=buffer, rank=rank, p=p, threshold=threshold)
+
+    def domain_scores(self, domain, X=None, n_neighbors=None):
+        """The uint8 distance-domain codes of ``kneighbors(X, n_neighbors)`` within ``domain``, its tallies added to it
+        (:meth:`RawKNNRegressor.domain_scores`)."""
+        check_is_fitted(self, "regressor_")
+        reg = self.regressor_
+        if not isinstance(domain, DistanceDomain):
+            raise TypeError(f"domain must be a sknnr_amd.DistanceDomain, got {type(domain).__name__}")
+        if domain.rank > reg._resolve_k(n_neighbors):
+            raise ValueError(f"domain.rank={domain.rank} is above n_neighbors={reg._resolve_k(n_neighbors)}")
+        dist, _ = self.kneighbors(X, n_neighbors=n_neighbors)
+        return reg._domain_scores(domain, dist)
+
     def _raw_nodata(self, nodata):
         """``nodata`` of a streamed call, one value per UNTRANSFORMED input column: the mask reads the raw rows, so they
         must reach the engine raw (affine map or forests on the device)."""
@@ -1844,15 +1989,16 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
 
     def kneighbors_chunks(self, tiles, n_neighbors=None, return_distance=True, return_dataframe_index=False,
                           use_deterministic_ordering=True, out=None, nodata=None, fill_index=-1, layout="rows",
-                          index_dtype=None, distance_dtype=None, usage=None):
+                          index_dtype=None, distance_dtype=None, usage=None, domain=None, domain_out=None):
         """``kneighbors`` over an iterable of untransformed host tiles as one streamed call (see
         :meth:`RawKNNRegressor.kneighbors_chunks`, also for ``nodata`` / ``fill_index``: the nodata values are those of
-        the untransformed columns -- for ``layout="bands"``, for ``index_dtype`` / ``distance_dtype`` and for ``usage``);
-        each tile is transformed on the device."""
+        the untransformed columns -- for ``layout="bands"``, for ``index_dtype`` / ``distance_dtype``, for ``usage`` and
+        for ``domain`` / ``domain_out``); each tile is transformed on the device."""
         bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
         reg = self.regressor_
         k = reg._resolve_k(n_neighbors)
+        reg._check_domain(domain, domain_out, k)
         validate = self._band_validator(bands)
         nodata = self._raw_nodata(nodata)
         output = reg._neighbor_output(index_dtype, distance_dtype, return_distance, return_dataframe_index, fill_index,
@@ -1865,14 +2011,16 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
                                          owner=self.transformer_, nodata=nodata,
                                          fill_index=-1 if return_dataframe_index else fill_index, bands=bands,
                                          output=output, id_table=table, fill_id=fill_index,
-                                         **({} if usage is None else dict(usage=usage)))
+                                         **({} if usage is None else dict(usage=usage)),
+                                         **({} if domain is None else dict(domain=domain, domain_out=domain_out)))
         return reg._finish_chunks(dist, idx, return_distance, return_dataframe_index,
                                   fill_index=None if nodata is None else fill_index, on_device=table is not None)
 
     def predict_chunks(self, tiles, out=None, nodata=None, layout="rows", out_dtype=None, scale=None, offset=None,
                        out_nodata=None, statistic=None, return_neighbors=False, return_distance=True,
                        return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
-                       distance_dtype=None, outputs=None, usage=None, zones=None, zonal=None):
+                       distance_dtype=None, outputs=None, usage=None, zones=None, zonal=None, domain=None, domain_out=None,
+                       beyond="keep"):
         """``predict`` over an iterable of untransformed host tiles as one streamed call (``nodata``: masked rows are
         predicted NaN; ``layout="bands"``: band-first tiles and predictions; ``out_dtype`` / ``scale`` / ``offset`` /
         ``out_nodata``: predictions converted on the device to the type the raster is stored in; ``statistic``: one name
@@ -1880,7 +2028,9 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         mean; ``outputs``: ``(target, statistic)`` pairs instead, ``n_out`` planes from the one search;
         ``return_neighbors=True`` and the neighbour keywords: ``(pred, dist, idx)`` from one search; ``usage``: a
         :class:`sknnr_amd.NeighborUsage` the device's tally of the neighbours is added to; ``zones`` / ``zonal``: the zone
-        codes of every tile and the :class:`sknnr_amd.ZonalStats` the device's zonal tables are added to; see
+        codes of every tile and the :class:`sknnr_amd.ZonalStats` the device's zonal tables are added to; ``domain`` /
+        ``domain_out`` / ``beyond``: the :class:`sknnr_amd.DistanceDomain` the pixels' distances are placed within on the
+        device, the uint8 plane that receives the codes, and ``"nodata"`` to blank the predictions beyond its threshold; see
         :meth:`RawKNNRegressor.kneighbors_chunks` / :meth:`RawKNNRegressor.predict_chunks`)."""
         bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
@@ -1891,6 +2041,8 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
             extra["usage"] = usage
         if zones is not None or zonal is not None:
             extra.update(zones=zones, zonal=zonal)
+        if domain is not None or domain_out is not None or beyond != "keep":
+            extra.update(domain=domain, domain_out=domain_out, beyond=beyond)
         statistic = resolve_statistic(statistic, outputs, self.regressor_._n_targets())
         return self.regressor_._predict_chunks(tiles, self._band_validator(bands), apply_affine=self._map_on_device(),
                                                out=out, owner=self.transformer_, nodata=self._raw_nodata(nodata),

@@ -386,6 +386,24 @@ class KNNEngine:
         return self._index.zonal_from_values_host(values, zones, dtype, n_zones, scale=scale, offset=offset,
                                                   n_classes=n_classes)
 
+    def domain_from_neighbors(self, dist, table, rank=1, threshold=None):
+        """Distance-domain codes of distances already found (sknnr_domain_from_neighbors): ``dist`` ``(nq, k)`` numpy or
+        torch.cuda, ``table`` the sorted host table.  Returns host arrays ``(codes, acc)``: ``(nq,)`` uint8 and the 103
+        int64 accumulators."""
+        if is_torch_cuda_tensor(dist):
+            import torch
+
+            dist = dist.to(torch.float64).contiguous()
+            nq, k = dist.shape
+            codes = torch.empty((nq,), dtype=torch.uint8, device=dist.device)
+            acc = torch.empty((_native.DOMAIN_ACC,), dtype=torch.int64, device=dist.device)
+            stream = torch.cuda.current_stream(dist.device)
+            self._index.domain_from_neighbors_device(dist.data_ptr(), nq, k, table, rank, threshold, codes.data_ptr(),
+                                                     acc.data_ptr(), False, stream.cuda_stream)
+            stream.synchronize()
+            return codes.cpu().numpy(), acc.cpu().numpy()
+        return self._index.domain_from_neighbors_host(dist, table, rank, threshold)
+
     def summarize_from_neighbors(self, dist, idx, weights, stat):
         """Per-target statistics (``stat``: one ``_native.STATISTICS`` code per target) of neighbours already found:
         :meth:`predict_from_neighbors` with the mean replaced column by column.  Always float64 ``(nq, t)``.  Explicit
@@ -617,7 +635,7 @@ class KNNEngine:
     def open_stream(self, k, *, weights=None, want_dist=True, deterministic=True, decimals=10,
                     formula="expanded", apply_affine=False, row_offset=0, check_finite=False, query_dtype=0,
                     nodata=None, fill_index=-1, output=None, statistic=None, id_table=None, fill_id=-1, plan=None,
-                    tally=False, zonal=None):
+                    tally=False, zonal=None, domain=None):
         """A :class:`sknnr_amd._native.QueryStream` over host tiles: ``push(tile)`` keeps the PCIe
         pipeline full across tiles and carries the global row offset.  ``weights`` (``"uniform"`` /
         ``"distance"`` / a :class:`sknnr_amd.weights.DistanceWeights` law, evaluated on the device tile by tile) also
@@ -633,7 +651,10 @@ class KNNEngine:
         tallied on the device (:meth:`sknnr_amd._native.QueryStream.set_tally`); ``stream.tally()`` reads the result.
         ``zonal``: ``(n_zones, n_classes)`` -- every tile's predictions are tallied by zone on the device
         (:meth:`sknnr_amd._native.QueryStream.set_zonal`; the stream needs an integer ``pred_dtype``); every push then
-        needs ``stream.next_zones(codes)`` first, and ``stream.zonal()`` reads the result."""
+        needs ``stream.next_zones(codes)`` first, and ``stream.zonal()`` reads the result.  ``domain``: ``(table, rank,
+        threshold, mask_beyond)`` -- every tile's distances are coded against the table on the device
+        (:meth:`sknnr_amd._native.QueryStream.set_domain`); ``stream.next_domain_out(plane)`` names where a push's codes go
+        and ``stream.domain()`` reads the accumulators."""
         want_pred = weights is not None
         law = self.weight_law(weights)  # (a distance-weight law: every tile's weights are made on the device)
         if want_pred and not law and weights not in _WEIGHT_MODES:
@@ -651,7 +672,7 @@ class KNNEngine:
             raise ValueError("a stream takes statistic or an output plan, not both")
         return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred, nodata=nodata, fill_index=fill_index,
                                        output=output, statistic=statistic, id_table=id_table, fill_id=fill_id, plan=plan,
-                                       tally=tally, zonal=zonal)
+                                       tally=tally, zonal=zonal, domain=domain)
 
     def hamming_distances(self, X, rows=None):
         """Full weighted-Hamming distance rows of ``X[rows]`` (``X`` None: of the fitted rows) from the device."""

@@ -133,6 +133,12 @@ EXPORTED_SYMBOLS = (
     "sknnr_stream_get_zonal",
     "sknnr_debug_last_zonal",
     "sknnr_debug_zonal_geometry",
+    "sknnr_domain_from_neighbors",
+    "sknnr_stream_set_domain",
+    "sknnr_stream_next_domain_out",
+    "sknnr_stream_get_domain",
+    "sknnr_debug_last_domain",
+    "sknnr_debug_domain_geometry",
     "sknnr_debug_last_narrow",
     "sknnr_debug_last_mask",
     "sknnr_debug_mask_compact",
@@ -185,6 +191,26 @@ def _zonal_classes(n_classes, c):
     if not n_classes.any():
         return None, 0
     return n_classes, int(n_classes.astype(np.int64).sum())
+
+
+DOMAIN_ACC = 103  # acc: codes 0 .. 100, beyond pixels, nodata pixels (include/sknnr_hip.h, "Distance domain")
+DOMAIN_NODATA_CODE = 255
+
+
+def domain_geometry(m: int) -> dict:
+    """Geometry of the domain kernel for a table of ``m`` entries, from the library itself (sknnr_debug_domain_geometry; no
+    device work): pixels a workgroup takes, the most entries of its skeleton of the table, table entries between two
+    skeleton entries, skeleton entries in use."""
+    out = (c_int64 * 4)()
+    check(load().sknnr_debug_domain_geometry(int(m), out))
+    return dict(zip(("pixels_per_workgroup", "skeleton", "stride", "skeleton_used"), (int(v) for v in out)))
+
+
+def _domain_args(table, threshold):
+    """``table`` / ``threshold`` as the C ABI takes them: a C-contiguous float64 array, its length, has_threshold and the
+    threshold (0.0 without one).  The library validates them."""
+    table = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
+    return table, int(table.size), int(threshold is not None), float(0.0 if threshold is None else threshold)
 
 
 class QueryOpts(ctypes.Structure):
@@ -349,6 +375,14 @@ def load(build_if_missing: bool = False):
         lib.sknnr_stream_get_zonal.argtypes = [vp, vp, vp]
         lib.sknnr_debug_last_zonal.argtypes = [vp, POINTER(c_int64)]
         lib.sknnr_debug_zonal_geometry.argtypes = [c_int32, POINTER(c_int64)]
+    if hasattr(lib, "sknnr_domain_from_neighbors"):  # (likewise)
+        lib.sknnr_domain_from_neighbors.argtypes = [vp, vp, c_int64, c_int32, c_int32, vp, c_int64, c_int32, c_double, vp, vp,
+                                                    c_int32, c_int32, vp]
+        lib.sknnr_stream_set_domain.argtypes = [vp, vp, c_int64, c_int32, c_int32, c_double, c_int32]
+        lib.sknnr_stream_next_domain_out.argtypes = [vp, vp, c_int64]
+        lib.sknnr_stream_get_domain.argtypes = [vp, vp]
+        lib.sknnr_debug_last_domain.argtypes = [vp, POINTER(c_int64)]
+        lib.sknnr_debug_domain_geometry.argtypes = [c_int64, POINTER(c_int64)]
     lib.sknnr_shard_candidates.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int64, vp, vp, c_int32, vp]
     lib.sknnr_merge_shards.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int32, vp, vp, vp, vp, c_int32, vp]
     lib.sknnr_crosswalk.argtypes = [vp, c_int64, vp, c_int64, vp, c_int32, c_int32, vp]
@@ -610,7 +644,7 @@ class Index:
 
     def open_stream(self, opts: QueryOpts, want_dist=True, want_pred=False, nodata=None, fill_index=-1,
                     output=None, statistic=None, id_table=None, fill_id=-1, plan=None, tally=False,
-                    zonal=None) -> "QueryStream":
+                    zonal=None, domain=None) -> "QueryStream":
         """``nodata``: float64 ``(d_in,)``, one value per column of the pushed rows -- every tile is then masked on the
         device (sknnr_stream_set_nodata) and masked rows get ``fill_index`` / NaN.  ``output``: keyword arguments of
         :meth:`QueryStream.set_output` -- the results then leave the device at those types.  ``statistic``: one
@@ -619,7 +653,8 @@ class Index:
         must then be negative, and masked rows get ``fill_id``.  ``plan``: an output plan ``(cols, codes, params)``
         (:meth:`QueryStream.set_plan`; not together with ``statistic``) -- the prediction lane then holds its planes, and
         ``output``'s ``scale`` / ``offset`` one value per plane.  ``tally``: :meth:`QueryStream.set_tally`.  ``zonal``:
-        ``(n_zones, n_classes)``, the arguments of :meth:`QueryStream.set_zonal`."""
+        ``(n_zones, n_classes)``, the arguments of :meth:`QueryStream.set_zonal`.  ``domain``: ``(table, rank, threshold,
+        mask_beyond)``, the arguments of :meth:`QueryStream.set_domain`."""
         stream = QueryStream(self, opts, want_dist, want_pred)
         try:
             if plan is not None:  # (first: it sets the width set_output's scale / offset must have)
@@ -636,6 +671,8 @@ class Index:
                 stream.set_tally()
             if zonal is not None:  # (behind the plan: n_classes holds one value per plane)
                 stream.set_zonal(*zonal)
+            if domain is not None:
+                stream.set_domain(*domain)
         except Exception:
             stream.close()
             raise
@@ -780,6 +817,47 @@ class Index:
         out = (c_int64 * 8)()
         check(load().sknnr_debug_last_zonal(self.handle, out))
         return dict(zip(self.ZONAL_RECORD, (int(v) for v in out)))
+
+    # ---- distance domain (include/sknnr_hip.h, "Distance domain") -----------------------------
+    def domain_from_neighbors_host(self, dist, table, rank=1, threshold=None, acc=None, want_codes=True):
+        """Percentile codes of ``dist`` ``(nq, k)`` float64 at ``rank`` within the sorted ``table``, and the accumulators
+        (sknnr_domain_from_neighbors on host arrays).  ``acc`` ``(103,)`` int64: an array to ADD to (``accumulate = 1``);
+        None: a fresh one.  ``want_codes=False``: tallies only, and the codes come back None.  Returns ``(codes, acc)``."""
+        dist = np.ascontiguousarray(dist, dtype=np.float64)
+        if dist.ndim != 2:
+            raise ValueError("dist must be (nq, k)")
+        nq, k = dist.shape
+        table, m, has_thr, thr = _domain_args(table, threshold)
+        accumulate = acc is not None
+        if accumulate:
+            if acc.dtype != np.int64 or acc.shape != (DOMAIN_ACC,) or not acc.flags.c_contiguous:
+                raise ValueError(f"acc must be C-contiguous int64 ({DOMAIN_ACC},)")
+        else:
+            acc = np.empty(DOMAIN_ACC, dtype=np.int64)
+        codes = np.empty(nq, dtype=np.uint8) if want_codes else None
+        check(load().sknnr_domain_from_neighbors(self.handle, _host_ptr(dist), nq, k, int(rank), _host_ptr(table), m, has_thr,
+                                                 thr, _host_ptr(codes), _host_ptr(acc), int(accumulate), MEM_HOST, None))
+        return codes, acc
+
+    def domain_from_neighbors_device(self, dist_ptr, nq, k, table, rank, threshold, codes_ptr, acc_ptr, accumulate=False,
+                                     stream=0):
+        """sknnr_domain_from_neighbors on device pointers: enqueues on ``stream`` and returns.  ``table`` is a host array,
+        as in the host form; ``codes_ptr`` 0: tallies only."""
+        table, m, has_thr, thr = _domain_args(table, threshold)
+        check(load().sknnr_domain_from_neighbors(self.handle, c_void_p(dist_ptr or None), int(nq), int(k), int(rank),
+                                                 _host_ptr(table), m, has_thr, thr, c_void_p(codes_ptr or None),
+                                                 c_void_p(acc_ptr or None), int(bool(accumulate)), MEM_DEVICE,
+                                                 c_void_p(stream or None)))
+
+    DOMAIN_RECORD = ("ran", "pixels", "k", "rank", "m", "nodata", "global_atomics", "blanked")
+
+    def debug_last_domain(self) -> dict:
+        """Debug only (sknnr_debug_last_domain; synchronises the device): the last :meth:`domain_from_neighbors_host` /
+        ``_device`` call, or the open domain stream so far -- ran, pixels, k, rank, m, nodata pixels, global atomics issued
+        on the accumulators, prediction rows blanked by the mask."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_domain(self.handle, out))
+        return dict(zip(self.DOMAIN_RECORD, (int(v) for v in out)))
 
     # ---- per-target neighbour summaries (include/sknnr_hip.h) --------------------------------
     def summarize_host(self, q, opts: QueryOpts, stat, nq=None):
@@ -1168,6 +1246,8 @@ class QueryStream:
         self.pred_cols = index.t  # columns of the prediction lane (set_plan widens it)
         self._tally = False
         self._zonal = None  # (n_zones, elements of hist per zone) once set_zonal was called
+        self._domain = False
+        self._domain_out = None  # the code plane named for the next push (next_domain_out)
         check(load().sknnr_stream_begin(index.handle, byref(opts), int(self.want_dist), int(self.want_pred),
                                         byref(self._h)))
 
@@ -1194,6 +1274,9 @@ class QueryStream:
         out_idx, out_dist, out_pred = outs
         stride = (int(strides.pop()) if strides else nq,) if planes else ()
         check(native(self._h, tile, nq, _host_ptr(out_dist), _host_ptr(out_idx), _host_ptr(out_pred), *stride))
+        if self._domain_out is not None:  # (the library consumed it with this push)
+            outs.append(self._domain_out)
+            self._domain_out = None
         self._keep.append(outs)
         if len(self._keep) > 8:
             del self._keep[:-8]  # older tiles have left the pipeline (four slots: at most the last four pushes are pending)
@@ -1322,6 +1405,34 @@ class QueryStream:
         check(load().sknnr_stream_get_zonal(self._h, _host_ptr(acc), _host_ptr(hist)))
         self._keep.clear()
         return acc, hist
+
+    def set_domain(self, table, rank=1, threshold=None, mask_beyond=False):
+        """Code every tile's distances against the sorted ``table`` on the device (sknnr_stream_set_domain; only before the
+        first push): per pixel the percentile of its ``rank``-th neighbour distance, tallied into 103 counters.
+        ``mask_beyond`` (with predictions and a ``threshold``): the predictions of pixels beyond the threshold become NaN
+        before they are converted or enter zonal tables.  :meth:`next_domain_out` names where a push's codes go;
+        :meth:`domain` reads the accumulators."""
+        table, m, has_thr, thr = _domain_args(table, threshold)
+        check(load().sknnr_stream_set_domain(self._h, _host_ptr(table), m, int(rank), has_thr, thr, int(bool(mask_beyond))))
+        self._domain = True
+
+    def next_domain_out(self, out):
+        """Where the next push's code plane goes (sknnr_stream_next_domain_out): a C-contiguous uint8 array with one
+        element per pixel of that push, filled when the push's own outputs are; kept alive until then."""
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.ndim != 1 or not out.flags.c_contiguous:
+            raise ValueError("the code plane must be a C-contiguous uint8 (n,) array")
+        check(load().sknnr_stream_next_domain_out(self._h, _host_ptr(out), int(out.size)))
+        self._domain_out = out if out.size else None
+
+    def domain(self):
+        """Flush, then the 103 int64 accumulators of everything pushed so far (sknnr_stream_get_domain): the histogram
+        of codes 0 .. 100, the beyond pixels, the nodata pixels.  The accumulators keep running."""
+        if not self._domain:
+            raise ValueError("the stream has no domain: set_domain was not called")
+        acc = np.empty(DOMAIN_ACC, dtype=np.int64)
+        check(load().sknnr_stream_get_domain(self._h, _host_ptr(acc)))
+        self._keep.clear()
+        return acc
 
     def valid_rows(self) -> int:
         """Valid (unmasked) rows submitted so far; without a nodata mask, the rows pushed."""

@@ -1,9 +1,9 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_buffer.hip, k_tally.hip, k_zonal.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_buffer.hip, k_tally.hip, k_zonal.hip, k_domain.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
-// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS / SKNNR_KERNELS_TALLY / SKNNR_KERNELS_ZONAL / SKNNR_KERNELS_BUFFER), templates where they are instantiated.
+// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS / SKNNR_KERNELS_TALLY / SKNNR_KERNELS_ZONAL / SKNNR_KERNELS_BUFFER / SKNNR_KERNELS_DOMAIN), templates where they are instantiated.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 #include "bucket.hip.h"
 #include "buffer.hip.h"
 #include "coarse2.hip.h"
+#include "domain.hip.h"
 #include "exact.hip.h"
 #include "forest.hip.h"
 #include "groups.hip.h"
@@ -129,6 +130,13 @@ hipError_t zonal(const ZonalArgs& a, int dst_dtype, hipStream_t st);
 long zonal_blocks(long n, int c);  // its workgroups
 // count, sum and limbs 0, min INT64_MAX, max INT64_MIN for n_keys (zone, column) pairs
 hipError_t zonal_init(long long* acc, long n_keys, hipStream_t st);
+
+// ---- k_domain.hip: distance domain of a tile's neighbour distances (domain.hip.h) ------------------------------------------------
+// codes the a.n pixels into a.codes (or none) and adds them into a.acc / a.rec (neither zeroed here); with a.pred the rows
+// of beyond pixels become NaN; hipErrorInvalidValue for a rank outside [1, k], m outside [1, 2^31 - 1], null accumulators
+// and a mask without a threshold
+hipError_t domain(const DomainArgs& a, hipStream_t st);
+long domain_blocks(long n);  // its workgroups
 
 // ---- k_coarse1.hip / k_coarse2.hip: the MFMA pre-filters ----------------------------------------------------------------
 struct Coarse1Launch {

@@ -445,6 +445,8 @@ struct sknnr_index {
         DevBuf<double> dev_xp;  // band-first tiles (planes.hip.h): the uploaded planes, in front of dev_x
         int32_t* pin_z = nullptr;  size_t pin_z_n = 0;  // zonal streams: the tile's zone codes, pinned and on the device
         DevBuf<int32_t> dev_z;
+        uint8_t* pin_dom = nullptr;  size_t pin_dom_n = 0;  // domain streams: the tile's code plane, on the device and pinned
+        DevBuf<uint8_t> dev_dom;
         // One output (kLaneIdx / kLaneDist / kLanePred), all in 8-byte words: int64 indices, float64 values, packed narrow elements.
         struct Lane {
             Word* pin = nullptr;  size_t pin_n = 0;  // pinned: what the device-to-host copy fills
@@ -526,6 +528,14 @@ struct sknnr_index {
     DevBuf<unsigned long long> zonal_rec;
     int64_t last_zonal[3] = {};
     int last_zonal_half = 0;
+    // distance domain (domain.hip.h): the sorted table of one-shot calls (dom_table) and of the open stream (s_dom_table,
+    // sknnr_stream_set_domain), the open stream's accumulators, the kernels' device record -- words [0, 4) of one-shot
+    // calls, [4, 8) of the open stream -- and the host's half of sknnr_debug_last_domain: ran, pixels, k, rank, m;
+    // last_domain_half: which device words belong to it
+    DevBuf<double> dom_table, s_dom_table;
+    DevBuf<unsigned long long> s_dom_acc, dom_rec;
+    int64_t last_domain[5] = {};
+    int last_domain_half = 0;
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
     // a ring of call records so that several calls of one benchmark step are summed, not only the last.
@@ -548,6 +558,7 @@ struct sknnr_index {
         for (auto& sl : slot) {
             if (sl.pin_x) (void)hipHostFree(sl.pin_x);
             if (sl.pin_z) (void)hipHostFree(sl.pin_z);
+            if (sl.pin_dom) (void)hipHostFree(sl.pin_dom);
             for (auto& ln : sl.lane)
                 if (ln.pin) (void)hipHostFree(ln.pin);
             for (hipEvent_t e : {sl.ev_h2d, sl.ev_done, sl.ev_d2h})
@@ -2239,6 +2250,18 @@ struct ZonalSpec {
 // n pixels of a tile of the open stream -- its full-layout (n, c) float64 predictions and its zone codes -- into the
 // handle's accumulators (sknnr_stream_set_zonal), on `st` behind the reduction
 static int zonal_tile(sknnr_index* ix, const ZonalSpec& z, const double* pred, const int32_t* zones, long n, hipStream_t st);
+// what one launch of a domain stream codes with: the column of the score, the table's length, the threshold
+struct DomainSpec {
+    int rank0;
+    long m;
+    int has_threshold;
+    double threshold;
+};
+// n pixels of a tile of the open stream -- its full-layout (n, k) float64 distances -- into the handle's accumulators
+// (sknnr_stream_set_domain) and into `codes` (device, or null), on `st` behind the search; pred (or null): the (n, pred_cols)
+// prediction tile whose beyond rows become NaN, behind the reduction
+static int domain_tile(sknnr_index* ix, const DomainSpec& d, const double* dist, long n, int k, uint8_t* codes, double* pred,
+                       int pred_cols, hipStream_t st);
 
 // The plan of the call in progress for as long as the scope lives; the caller holds ix->mtx.
 struct SummaryScope {
@@ -2491,6 +2514,12 @@ struct HostPipe {
     int zonal_zones = 0, zonal_c = 0;
     size_t zonal_hist = 0;  // elements of the class blocks (0: no column has classes)
     const int32_t* zones_push = nullptr;
+    // distance domain (sknnr_stream_set_domain): every tile's distances are coded against the handle's s_dom_table and
+    // tallied into s_dom_acc; domain_mask: the prediction rows of beyond pixels become NaN in front of the conversion and
+    // the zonal tally; domain_push: where the code plane of the push in progress goes (host; null: it tallies only)
+    bool domain = false, domain_mask = false;
+    DomainSpec domain_spec{};
+    uint8_t* domain_push = nullptr;
     size_t x_esz = sizeof(double);  // bytes per element of the caller's rows (opts->query_dtype)
     // nodata front end: every tile is masked behind its host-to-device copy, and o.row_offset advances by its VALID rows
     const double* nodata_dev = nullptr;  // (d_x) on the device, or null: no mask
@@ -2508,6 +2537,7 @@ struct HostPipe {
         void* out[kLanes] = {};  // the caller's arrays (the tile's first element; null: not asked for in this push)
         bool planes = false;   // the tile was pushed band-first: its results leave as planes, out_stride elements apart
         long out_stride = 0;
+        uint8_t* domain_out = nullptr;  // the caller's code plane of the tile (a domain pipeline; null: not asked for)
         std::future<int> out_done;  // copy-out job of the slot's tile (w_out)
     } pending[kHostSlots];
     int slot_of = 0;
@@ -2594,6 +2624,10 @@ int pipe_prepare_slot(HostPipe& p, int b, long n, bool planes = false) {
         if ((rc = ensure_pinned(sl.pin_z, sl.pin_z_n, (size_t)n))) return rc;
         HIP_TRY(sl.dev_z.ensure((size_t)n));
     }
+    if (p.domain) {
+        if ((rc = ensure_pinned(sl.pin_dom, sl.pin_dom_n, (size_t)n))) return rc;
+        HIP_TRY(sl.dev_dom.ensure((size_t)n));
+    }
     for (int l = 0; l < kLanes; ++l) {
         const HostPipe::Lane& ln = p.lane[l];
         auto& sb = sl.lane[l];
@@ -2648,6 +2682,9 @@ int pipe_enqueue_d2h(HostPipe& p) {
         legs[l] = Leg{pd.out[l], sb.pin, ln.cols, ln.esz};
     }
     ix->last_narrow[5] = (int64_t)moved;
+    uint8_t* const dom_dst = pd.domain_out;  // (a domain pipeline's code plane: n bytes in pixel order in either layout)
+    const uint8_t* const dom_pin = sl.pin_dom;
+    if (dom_dst) HIP_TRY(hipMemcpyAsync(sl.pin_dom, sl.dev_dom.p, (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(sl.ev_d2h, st));
     // the copy-out leg: wait for the tile's device-to-host copies, then pinned -> the caller's arrays (w_out, in order)
     {
@@ -2661,6 +2698,7 @@ int pipe_enqueue_d2h(HostPipe& p) {
                 if (planes) unstage_planes(g.dst, g.pin, g.cols, n, out_stride, g.esz);
                 else parallel_copy(g.dst, g.pin, lane_bytes(n, g.cols, g.esz));
             }
+            if (dom_dst) parallel_copy(dom_dst, dom_pin, (size_t)n);
             return SKNNR_OK;
         };
         if (pipe_workers()) {
@@ -2682,9 +2720,10 @@ int pipe_enqueue_d2h(HostPipe& p) {
 // out_stride elements between planes.  `planes` must stay valid until the next tile is submitted or the pipeline flushed.
 // out[l]: where lane l's results of this tile go, in the lane's own element type (null: not asked for).
 // zones (a zonal pipeline; else null): the tile's n zone codes, the next tile's behind them.
+// domain_out (a domain pipeline; else null): where the tile's n codes go on the host (null: the tile is tallied only).
 int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], const void* q_next = nullptr,
                 long n_next = 0, const void* const* planes = nullptr, long p_off = 0, long out_stride = 0,
-                const int32_t* zones = nullptr) {
+                const int32_t* zones = nullptr, uint8_t* domain_out = nullptr) {
     sknnr_index* ix = p.ix;
     const int b = p.slot_of;
     p.slot_of = (p.slot_of + 1) % kHostSlots;
@@ -2746,6 +2785,13 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
             if (rc) return rc;
         }
     }
+    // distance domain: the full-layout float64 distance tile (masked rows are NaN), whether or not the distances leave;
+    // with the mask, the prediction rows of beyond pixels become NaN here, in front of the zonal tally and the conversion
+    if (p.domain) {
+        rc = domain_tile(ix, p.domain_spec, dist.f64(), n, k, domain_out ? sl.dev_dom.p : nullptr,
+                         p.domain_mask ? pred.f64() : nullptr, p.lane[kLanePred].cols, ix->st_run);
+        if (rc) return rc;
+    }
     // zonal statistics: the full-layout float64 prediction tile (masked rows are NaN), whether or not this push asked for
     // the predictions, and before any conversion: the kernel converts with the conversion's own device function
     if (p.zonal) {
@@ -2794,6 +2840,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     std::copy(out, out + kLanes, pd.out);
     pd.planes = planes != nullptr;
     pd.out_stride = out_stride;
+    pd.domain_out = p.domain ? domain_out : nullptr;
     p.d2h_slot = b;  // its device-to-host copies are enqueued behind the next tile's rows, or by the flush
     p.o.row_offset += nv;
     p.ms_enqueue += now_ms() - t_enq;
@@ -2851,7 +2898,8 @@ int pipe_submit_rows(HostPipe& p, const void* q_, long nq, void* const out[kLane
         for (int l = 0; l < kLanes; ++l)
             tile_out[l] = out[l] ? (char*)out[l] + lane_tile_offset(c0, p.lane[l].cols, p.lane[l].esz, planes != nullptr) : nullptr;
         int rc = pipe_submit(p, q + c0 * row_bytes, n, tile_out, n_next ? q + c1 * row_bytes : nullptr, n_next, planes, c0,
-                             out_stride, p.zonal ? p.zones_push + c0 : nullptr);
+                             out_stride, p.zonal ? p.zones_push + c0 : nullptr,
+                             p.domain && p.domain_push ? p.domain_push + c0 : nullptr);
         if (rc) return rc;
         c0 = c1;
     }
@@ -4120,6 +4168,9 @@ struct sknnr_stream {
     // a zonal stream (sknnr_stream_set_zonal): the zone codes of the next push (sknnr_stream_next_zones), the stream's own copy
     std::vector<int32_t> zones;
     bool have_zones = false;
+    // a domain stream (sknnr_stream_set_domain): the caller's code plane of the next push (sknnr_stream_next_domain_out)
+    uint8_t* domain_out = nullptr;
+    int64_t domain_out_n = 0;
 };
 
 extern "C" int sknnr_stream_set_nodata(sknnr_stream* s, const double* nodata, int64_t fill_index) {
@@ -4634,6 +4685,193 @@ extern "C" int sknnr_debug_zonal_geometry(int32_t c, int64_t out[4]) {
     return SKNNR_OK;
 }
 
+// ---- distance domain (domain.hip.h) -----------------------------------------------------------------------------------
+// One launch into codes / acc on `st`; `half`: the device record's words it adds to (0 one-shot calls, 1 the open stream).
+static int launch_domain(sknnr_index* ix, const DomainSpec& d, const double* table, const double* dist, long n, int k,
+                         uint8_t* codes, unsigned long long* acc, double* pred, int pred_cols, int half, hipStream_t st) {
+    DomainArgs a{};
+    a.dist = dist;
+    a.n = n;
+    a.k = k;
+    a.rank0 = d.rank0;
+    a.table = table;
+    a.m = d.m;
+    a.has_threshold = d.has_threshold;
+    a.threshold = d.threshold;
+    a.codes = codes;
+    a.acc = acc;
+    a.pred = pred;
+    a.pred_cols = pred_cols;
+    a.rec = ix->dom_rec.p + half * kDomainRecWords;
+    HIP_TRY(launch::domain(a, st));
+    return SKNNR_OK;
+}
+
+static int domain_tile(sknnr_index* ix, const DomainSpec& d, const double* dist, long n, int k, uint8_t* codes, double* pred,
+                       int pred_cols, hipStream_t st) {
+    if (!dist) return fail(SKNNR_ERR_INVALID, "a domain tile needs its distances");
+    const int rc = launch_domain(ix, d, ix->s_dom_table.p, dist, n, k, codes, ix->s_dom_acc.p, pred, pred_cols, 1, st);
+    if (rc) return rc;
+    ix->last_domain[0] = 1;
+    ix->last_domain[1] += n;
+    ix->last_domain_half = 1;
+    return SKNNR_OK;
+}
+
+// The contract's refusals, all on the host: the table, the rank against k, the threshold.
+static int domain_check(const double* table, int64_t m, int32_t k, int32_t rank, int32_t has_threshold, double threshold) {
+    if (k < 1) return fail(SKNNR_ERR_INVALID, "k must be >= 1");
+    if (rank < 1 || rank > k) return fail(SKNNR_ERR_INVALID, "rank = %d outside [1, k = %d]", rank, k);
+    if (!table) return fail(SKNNR_ERR_INVALID, "table is NULL");
+    if (m < 1 || m > 0x7fffffffL) return fail(SKNNR_ERR_INVALID, "m = %lld outside [1, 2^31 - 1]", (long long)m);
+    if (has_threshold && !(std::isfinite(threshold) && threshold >= 0.0))
+        return fail(SKNNR_ERR_INVALID, "the threshold must be finite and >= 0");
+    for (int64_t j = 0; j < m; ++j) {
+        if (!(std::isfinite(table[j]) && table[j] >= 0.0))
+            return fail(SKNNR_ERR_INVALID, "table[%lld] is not a finite value >= 0", (long long)j);
+        if (j > 0 && table[j] < table[j - 1])
+            return fail(SKNNR_ERR_INVALID, "the table is not sorted: table[%lld] < table[%lld]", (long long)j, (long long)(j - 1));
+    }
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_domain_from_neighbors(sknnr_index* ix, const double* dist, int64_t nq, int32_t k, int32_t rank,
+                                           const double* table, int64_t m, int32_t has_threshold, double threshold,
+                                           uint8_t* codes, int64_t* acc, int32_t accumulate, int32_t mem, void* stream) {
+    // (the contract's own refusals first: they need no handle)
+    int rc = domain_check(table, m, k, rank, has_threshold, threshold);
+    if (rc) return rc;
+    if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
+    if (nq > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 pixels in one call");
+    if (!acc) return fail(SKNNR_ERR_INVALID, "acc is NULL");
+    if (!dist && nq > 0) return fail(SKNNR_ERR_INVALID, "dist is NULL");
+    if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = mem == SKNNR_MEM_DEVICE ? (hipStream_t)stream : nullptr;
+    // the handle's table: an earlier call on `st` may still read it
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(ix->dom_table.ensure((size_t)m));
+    HIP_TRY(hipMemcpy(ix->dom_table.p, table, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(ix->dom_rec.ensure(2 * kDomainRecWords));
+    HIP_TRY(hipMemsetAsync(ix->dom_rec.p, 0, kDomainRecWords * sizeof(unsigned long long), st));
+    const int64_t rec[5] = {nq > 0 ? 1 : 0, nq, k, rank, m};
+    std::copy(rec, rec + 5, ix->last_domain);
+    ix->last_domain_half = 0;
+    const DomainSpec d{rank - 1, (long)m, has_threshold != 0, threshold};
+    const size_t n_el = (size_t)nq * k;
+    unsigned long long* da = (unsigned long long*)acc;  // (int64 counters ARE the accumulators: the same 8-byte patterns)
+    const double* dd = dist;
+    uint8_t* dc = codes;
+    DevBuf<unsigned long long> bacc;  // (host memory: freed by their destructors on every return path)
+    DevBuf<double> bdist;
+    DevBuf<uint8_t> bcodes;
+    if (mem == SKNNR_MEM_HOST) {
+        HIP_TRY(bacc.ensure(kDomainAcc));
+        HIP_TRY(bdist.ensure(n_el));
+        if (codes) HIP_TRY(bcodes.ensure((size_t)nq));
+        if (n_el) HIP_TRY(hipMemcpy(bdist.p, dist, n_el * sizeof(double), hipMemcpyHostToDevice));
+        if (accumulate) HIP_TRY(hipMemcpy(bacc.p, acc, kDomainAcc * 8, hipMemcpyHostToDevice));
+        da = bacc.p;
+        dd = bdist.p;
+        dc = codes ? bcodes.p : nullptr;
+    }
+    if (!accumulate) HIP_TRY(hipMemsetAsync(da, 0, kDomainAcc * 8, st));
+    if ((rc = launch_domain(ix, d, ix->dom_table.p, dd, nq, k, dc, da, nullptr, 0, 0, st))) return rc;
+    if (mem == SKNNR_MEM_HOST) {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpy(acc, bacc.p, kDomainAcc * 8, hipMemcpyDeviceToHost));
+        if (codes && nq) HIP_TRY(hipMemcpy(codes, bcodes.p, (size_t)nq, hipMemcpyDeviceToHost));
+    }
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_set_domain(sknnr_stream* s, const double* table, int64_t m, int32_t rank, int32_t has_threshold,
+                                       double threshold, int32_t mask_beyond) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    HostPipe& p = s->pipe;
+    sknnr_index* ix = p.ix;
+    const int rc = domain_check(table, m, p.k, rank, has_threshold, threshold);
+    if (rc) return rc;
+    if (mask_beyond && !has_threshold) return fail(SKNNR_ERR_INVALID, "mask_beyond needs a threshold");
+    if (mask_beyond && !p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "mask_beyond: the stream was opened without predictions");
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_domain is allowed only before the first push");
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(ix->s_dom_table.ensure((size_t)m));
+    HIP_TRY(ix->s_dom_acc.ensure(kDomainAcc));
+    HIP_TRY(ix->dom_rec.ensure(2 * kDomainRecWords));
+    HIP_TRY(hipMemcpy(ix->s_dom_table.p, table, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+    // (on the stream every tile's launch runs on: zeroed in front of the first of them)
+    HIP_TRY(hipMemsetAsync(ix->s_dom_acc.p, 0, kDomainAcc * 8, ix->st_run));
+    HIP_TRY(hipMemsetAsync(ix->dom_rec.p + kDomainRecWords, 0, kDomainRecWords * sizeof(unsigned long long), ix->st_run));
+    p.domain = true;
+    p.domain_mask = mask_beyond != 0;
+    p.domain_spec = DomainSpec{rank - 1, (long)m, has_threshold != 0, threshold};
+    p.mask_dist = true;  // the masked path keeps the search's distances whether or not they leave
+    s->domain_out = nullptr;
+    const int64_t rec[5] = {0, 0, p.k, rank, m};
+    std::copy(rec, rec + 5, ix->last_domain);
+    ix->last_domain_half = 1;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_next_domain_out(sknnr_stream* s, uint8_t* out, int64_t nq) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    if (!s->pipe.domain) return fail(SKNNR_ERR_INVALID, "the stream has no domain: sknnr_stream_set_domain was not called");
+    if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
+    if (nq == 0) return SKNNR_OK;  // (a push of no rows writes none)
+    if (!out) return fail(SKNNR_ERR_INVALID, "out is NULL");
+    std::lock_guard<std::mutex> lock(s->pipe.ix->mtx);
+    s->domain_out = out;
+    s->domain_out_n = nq;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_get_domain(sknnr_stream* s, int64_t acc[103]) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    HostPipe& p = s->pipe;
+    sknnr_index* ix = p.ix;
+    if (!p.domain) return fail(SKNNR_ERR_INVALID, "the stream has no domain: sknnr_stream_set_domain was not called");
+    if (!acc) return fail(SKNNR_ERR_INVALID, "acc is NULL");
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    const int rc = pipe_flush(p);
+    if (rc) return pipe_fail(p, rc);
+    HIP_TRY(hipStreamSynchronize(ix->st_run));
+    HIP_TRY(hipMemcpy(acc, ix->s_dom_acc.p, kDomainAcc * 8, hipMemcpyDeviceToHost));
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_domain(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::fill(out, out + 8, 0);
+    std::copy(ix->last_domain, ix->last_domain + 5, out);
+    if (!ix->dom_rec.p) return SKNNR_OK;
+    unsigned long long w[kDomainRecWords];
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(w, ix->dom_rec.p + ix->last_domain_half * kDomainRecWords, sizeof w, hipMemcpyDeviceToHost));
+    // (the pixels the kernels counted, not the host's: the two agree when every launch ran)
+    out[1] = (int64_t)w[kDomainRecPixels];
+    out[5] = (int64_t)w[kDomainRecNodata];
+    out[6] = (int64_t)w[kDomainRecAtomics];
+    out[7] = (int64_t)w[kDomainRecBlanked];
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_domain_geometry(int64_t m, int64_t out[4]) {
+    if (!out || m < 1 || m > 0x7fffffffL) return fail(SKNNR_ERR_INVALID, "bad argument");
+    out[0] = kDomainWgPixels;
+    out[1] = kDomainSkel;
+    out[2] = domain_stride(m);
+    out[3] = domain_skel_entries(m);
+    return SKNNR_OK;
+}
+
 extern "C" int sknnr_stream_valid_rows(const sknnr_stream* s, int64_t* out_valid_rows) {
     if (!s || !out_valid_rows) return fail(SKNNR_ERR_INVALID, "stream / out_valid_rows is NULL");
     std::lock_guard<std::mutex> lock(s->pipe.ix->mtx);
@@ -4702,6 +4940,14 @@ static int stream_push(sknnr_stream* s, const void* q, const void* const* planes
             return fail(SKNNR_ERR_INVALID, "a zonal stream needs an integer pred_dtype (sknnr_stream_set_output): zonal sums are over stored integers");
         s->have_zones = false;  // (consumed, whatever becomes of the push)
         p.zones_push = s->zones.data();
+    }
+    if (p.domain) {
+        uint8_t* const dst = s->domain_out;
+        const int64_t dst_n = s->domain_out_n;
+        s->domain_out = nullptr;  // (consumed, whatever becomes of the push)
+        if (dst && dst_n != nq)
+            return fail(SKNNR_ERR_INVALID, "sknnr_stream_next_domain_out named %lld codes, the push has %lld rows", (long long)dst_n, (long long)nq);
+        p.domain_push = dst;
     }
     HIP_TRY(hipSetDevice(p.ix->device));
     s->pushed = true;
