@@ -928,6 +928,79 @@ int sknnr_stream_get_domain(sknnr_stream* stream, int64_t acc[103]);
 int sknnr_debug_last_domain(const sknnr_index* index, int64_t out[8]);
 int sknnr_debug_domain_geometry(int64_t m, int64_t out[4]);
 
+/* ---- neighbour replay (attribute maps from stored neighbour rasters) ---------------------------------- */
+
+/*
+ * Neighbour replay.  THE CONTRACT, stated here once (sknnr_amd/csrc/replay.hip.h implements it, tests/_replay.py restates
+ * it in numpy).  The neighbour raster -- plot ids and distances per pixel -- is made once by a search stream and stored;
+ * a replay stream takes such tiles in place of feature rows and delivers everything a search stream delivers, bit for
+ * bit what the search that wrote the neighbours delivered, without running any part of the search.
+ *   Tile        for n pixels, ks stored neighbour columns: idx (required; int32 or int64; row positions in [0, n_ref) or
+ *               ids of the handle's id table) and dist (optional; float32 or float64), as rows (n, ks) or as band-first
+ *               planes (ks, n).  A stream uses the leading k <= ks columns as stored: with ties among the neighbours
+ *               that is "the first k stored columns", not necessarily what a fresh k-search would return.
+ *   Decode      on the device, into the pipeline's own full-layout tile: int64 idx (n, k), float64 dist (n, k) -- what a
+ *               search followed by its nodata expansion leaves there.  Widening is exact (int32 -> int64,
+ *               float32 -> float64).
+ *   Masked      a pixel whose FIRST stored index equals fill_index; the test is made on the stored value, before any
+ *               lookup, and no other column takes part.  It gets index -1, NaN distances and NaN in every prediction
+ *               plane, enters neither the usage tally nor a zonal table, and gets domain code 255.
+ *   Ids         every stored value is looked up in the handle's id table (sknnr_index_set_replay_ids: the int64 ids,
+ *               sorted once on the host together with their row positions) by a lower-bound search on the device.
+ *   Unknown     an id that is not in the table, or a row position outside [0, n_ref), in any of the k USED columns of a
+ *               pixel that is not masked.  The pixel is then treated as masked, and counted.  No gather ever reads
+ *               outside y.
+ *   Afterwards  the tile goes through the unchanged later stages of the pipeline: the reduction (predictions,
+ *               per-target statistics or the output plan), the blanking pass that gives masked and unknown pixels the
+ *               state above, the usage tally, the distance domain with its mask, the zonal tally, the typed conversion
+ *               with scale / offset / fill, the band transposes and the copies.  (The tally runs behind the blanking
+ *               pass and skips the -1 indices; its sums are integer adds and do not depend on where it is enqueued.)
+ *   Weights     uniform needs no distances; distance weights and the weight laws are computed from the stored distances
+ *               as widened, never from any geometry.
+ * Nothing of the search runs -- no preparation, no pre-filter, no finaliser, no scan -- and a replay stream never reads
+ * the handle's reference rows.
+ *
+ * sknnr_index_create_targets: an attribute-only handle: it owns the (n_ref, t) float64 HOST table y and nothing else.  The
+ *   from-neighbours entries and replay streams accept it; every entry that searches or configures a search refuses it
+ *   with SKNNR_ERR_INVALID and a message that says why.  Freed by sknnr_index_destroy.
+ * sknnr_index_set_replay_ids: installs the id table (n = n_ref int64 ids, HOST).  Duplicates are refused with
+ *   SKNNR_ERR_INVALID before any device work -- the table is checked first, before the handle is even looked at;
+ *   ids = NULL removes the table.  Not while a stream is open.
+ * sknnr_replay_begin: opens a replay stream on the handle (one open stream per handle, as sknnr_stream_begin).
+ *   k / ks as above; weight_mode / weight_law as in sknnr_query_opts; idx_dtype 0 (int64) or SKNNR_DTYPE_I32; dist_dtype
+ *   0 (float64), SKNNR_DTYPE_F32 or SKNNR_REPLAY_NO_DIST; ids = 1: the stored values are ids; want_dist: pushes may ask
+ *   for the decoded distances again (needs stored ones); want_pred as in sknnr_stream_begin.  Every refusal comes before
+ *   any device work.  The stream works with sknnr_stream_set_statistics / _set_plan / _set_output / _set_id_table (the
+ *   decoded indices may leave as ids again) / _set_tally / _get_tally / _set_zonal / _next_zones / _get_zonal /
+ *   _set_domain / _next_domain_out / _get_domain / _flush / _end unchanged.  sknnr_stream_set_nodata is refused (the
+ *   mask is the fill index), and so are _set_tally and _set_domain on a stream without stored distances, and the
+ *   sknnr_stream_push* entries.
+ * sknnr_replay_push / sknnr_replay_push_planes: one tile of nq pixels.  idx / dist are HOST arrays of the stream's stored
+ *   types -- rows (nq, ks), or planes in_stride >= nq elements apart -- and may be reused as soon as the call returns;
+ *   dist is given exactly when the stream has stored distances.  The outputs are those of sknnr_stream_push_typed /
+ *   _planes_typed, in the stream's output types, each optional: a push may ask for none and still feed the tally, the
+ *   zonal tables and the domain.  nq == 0 is accepted and counts as a push.
+ * sknnr_replay_get_counts: flushes, then out[0] pixels, out[1] masked pixels, out[2] unknown pixels of the stream so
+ *   far, out[3] the first push (counted from 0, empty ones included) that held unknown values, -1 when none did.
+ * sknnr_debug_last_replay: debug only, host memory.  The last replayed tile of the handle:
+ *   out[0] its pixels    out[1] masked    out[2] unknown    (of the last tile that has left the pipeline: after a flush, the last)
+ *   out[3] the decode instantiation: 6 * (int64 indices) + 2 * (0 no distances, 1 float32, 2 float64) + (planes)
+ *   out[4] 1 = ids: the skeleton path looked the values up      out[5] searches the tile's submission ran: 0
+ *   out[6] k     out[7] ks
+ */
+#define SKNNR_REPLAY_NO_DIST (-1)
+int sknnr_index_create_targets(const double* y, int64_t n_ref, int32_t t, int32_t device, sknnr_index** out);
+int sknnr_index_set_replay_ids(sknnr_index* index, const int64_t* ids, int64_t n);
+int sknnr_replay_begin(sknnr_index* index, int32_t k, int32_t ks, int32_t weight_mode, int32_t weight_law, int32_t idx_dtype,
+                       int32_t dist_dtype, int64_t fill_index, int32_t ids, int32_t want_dist, int32_t want_pred,
+                       sknnr_stream** out);
+int sknnr_replay_push(sknnr_stream* stream, const void* idx, const void* dist, int64_t nq, void* out_dist, void* out_idx,
+                      void* out_pred);
+int sknnr_replay_push_planes(sknnr_stream* stream, const void* idx, const void* dist, int64_t nq, int64_t in_stride,
+                             void* out_dist, void* out_idx, void* out_pred, int64_t out_stride);
+int sknnr_replay_get_counts(sknnr_stream* stream, int64_t out[4]);
+int sknnr_debug_last_replay(const sknnr_index* index, int64_t out[8]);
+
 /*
  * Debug only.  The output side of the last tile the handle's host pipeline submitted, so that a test can prove that the
  * device converted it and that only the narrow bytes were copied.  Host memory, no device work:

@@ -592,6 +592,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         state = dict(super().__getstate__())
         state["_engine"] = None  # device handles do not pickle; see engine_
         state["_ref_tree"] = None  # a cache, rebuilt on first use
+        state["_replay_targets"] = None  # (table, attribute-only engine) of predict_neighbors_chunks(y=...): a device handle
         return state
 
     def _formula(self) -> str:
@@ -1732,6 +1733,276 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                     on_device=table is not None)
         return (pred, *found) if return_distance else (pred, found)
 
+    # -- neighbour replay: attribute maps from stored neighbour rasters ---------------------------
+    def _replay_target_engine(self, y):
+        """How to get the engine whose targets a replay reduces (called when the first tile is pushed: after every
+        refusal), whether the result is 1-D, the number of targets and their dtype: the estimator's own for ``y`` None,
+        else an attribute-only engine on ``y``, cached by the table's identity."""
+        if y is None:
+            return (lambda: self.engine_), self._y.ndim == 1, self._n_targets(), self._y.dtype
+        table = np.asarray(y)
+        if table.dtype.kind not in "fiub" or table.ndim not in (1, 2):
+            raise ValueError(f"y must be a numeric (n_samples, n_attributes) table, got {table.dtype} with shape {table.shape}")
+        if table.shape[0] != self.n_samples_fit_:
+            raise ValueError(f"y has {table.shape[0]} rows, but the estimator was fitted with {self.n_samples_fit_} samples")
+        if table.size == 0:
+            raise ValueError("y holds no attribute")
+        n_targets = 1 if table.ndim == 1 else table.shape[1]
+
+        def engine():
+            held = getattr(self, "_replay_targets", None)
+            if held is None or held[0] is not y:
+                if held is not None:
+                    held[1].close()
+                eng = KNNEngine.for_targets(np.ascontiguousarray(table.reshape(len(table), -1), dtype=np.float64),
+                                            device=self._device, target_dtype=table.dtype)
+                self._replay_targets = held = (y, eng)
+            return held[1]
+        return engine, table.ndim == 1, n_targets, table.dtype
+
+    def _replay_id_table(self, ids):
+        """The fitted dataframe ids as the int64 table stored ids are looked up in (``ids=True``), or None."""
+        if not ids:
+            return None
+        check_is_fitted(self, "dataframe_index_in_", msg="ids=True needs an estimator fitted with a dataframe: the stored "
+                                                         "values are looked up in its index.")
+        table = np.asarray(self.dataframe_index_in_)
+        if table.dtype.kind not in "iu":
+            raise NotImplementedError(f"ids=True needs integer dataframe ids, got {table.dtype}: labels of another kind "
+                                      "are not looked up on the device")
+        if table.dtype.itemsize > 8 or table.dtype == np.uint64:
+            raise ValueError(f"ids=True needs dataframe ids that fit int64, got {table.dtype}")
+        table = table.astype(np.int64)
+        if np.unique(table).size != table.size:
+            raise ValueError("ids=True needs unique dataframe ids: a stored id must name one reference row")
+        return table
+
+    @staticmethod
+    def _replay_tile(tile, bands, number):
+        """One tile of stored neighbours -- ``idx`` or ``(dist, idx)`` -- as ``(idx, dist or None)``: rows ``(n, ks)``, or
+        with ``bands`` planes ``(ks, n)`` from any ``(ks, ...)`` trailing shape (the rule of :func:`normalize_band_tile`)."""
+        dist = None
+        if isinstance(tile, (tuple, list)) and len(tile) == 2 and all(hasattr(a, "shape") for a in tile):
+            dist, tile = tile
+        idx = np.asarray(tile)
+        if idx.dtype.kind not in "iu" or idx.dtype in (np.uint32, np.uint64):
+            raise ValueError(f"tile {number}: stored neighbours are int32 or int64 row positions or ids, got {idx.dtype}")
+        if idx.dtype.itemsize < 4:
+            idx = idx.astype(np.int32)
+        if dist is not None:
+            dist = np.asarray(dist)
+            if dist.dtype not in (np.float32, np.float64):
+                raise ValueError(f"tile {number}: stored distances are float32 or float64, got {dist.dtype}")
+            if dist.shape != idx.shape:
+                raise ValueError(f"tile {number}: the distances have shape {dist.shape}, the indices {idx.shape}")
+        if idx.ndim < 2:
+            raise ValueError(f"tile {number}: a tile of stored neighbours is (n, ks), or (ks, ...) with layout='bands', "
+                             f"got shape {idx.shape}")
+        if bands:
+            idx = idx.reshape(idx.shape[0], int(np.prod(idx.shape[1:])))
+            dist = None if dist is None else dist.reshape(idx.shape)
+        elif idx.ndim != 2:
+            raise ValueError(f"tile {number}: a row tile of stored neighbours is (n, ks), got shape {idx.shape}")
+        return idx, dist
+
+    def predict_neighbors_chunks(self, neighbor_tiles, y=None, n_neighbors=None, ids=False, fill_index=-1, unknown="raise",
+                                 out=None, layout="rows", out_dtype=None, scale=None, offset=None, out_nodata=None,
+                                 statistic=None, outputs=None, usage=None, zones=None, zonal=None, domain=None,
+                                 domain_out=None, beyond="keep"):
+        """``predict_chunks`` from STORED neighbours instead of feature rows: the neighbour raster that
+        ``kneighbors_chunks(...)`` or ``predict_chunks(..., return_neighbors=True, neighbors_out=...)`` wrote is replayed
+        through the same device pipeline, and no search runs.  The result is bit-identical to the search call that wrote
+        those neighbours.
+
+        ``neighbor_tiles``: an iterable of ``idx`` or ``(dist, idx)`` host arrays -- int32 / int64 row positions (or
+        dataframe ids with ``ids=True``) and float32 / float64 distances; ``(n, ks)`` rows, or with ``layout="bands"``
+        any ``(ks, ...)`` shape.  All tiles of a call share one dtype pair and one ``ks``.  ``n_neighbors``: the
+        ``k <= ks`` leading columns in use, by default ``min(self.n_neighbors, ks)``; ``k < ks`` means "the first k
+        stored columns", which need not equal a fresh k-search where neighbours tie.
+
+        ``y``: an array-like or DataFrame ``(n_samples_fit_, t')`` reduced in place of the fitted targets -- a table the
+        estimator was never fitted with; ``outputs``, ``statistic``, ``scale`` and ``offset`` then count its columns.
+        A pixel whose first stored value equals ``fill_index`` is masked (NaN, or ``out_nodata``).  A stored value that
+        names no reference row makes its pixel unknown: ``unknown="raise"`` raises a ``ValueError`` at the end of the
+        call (the contents of ``out`` are then unspecified), ``unknown="nodata"`` stores it as a masked pixel -- an
+        integer ``out_dtype`` then needs ``out_nodata`` -- and the count is ``self.replay_unknown_`` either way.
+        ``uniform`` weights need no distances; ``distance`` weights, the laws of :mod:`sknnr_amd.weights`, ``usage`` and
+        ``domain`` need them.  Every other keyword has the meaning and the refusals it has in :meth:`predict_chunks`."""
+        bands = _check_layout(layout)
+        check_is_fitted(self, "_fit_X")
+        if unknown not in ("raise", "nodata"):
+            raise ValueError(f"unknown must be 'raise' or 'nodata', got {unknown!r}")
+        if beyond not in ("keep", "nodata"):
+            raise ValueError(f"beyond must be 'keep' or 'nodata', got {beyond!r}")
+        blank = beyond == "nodata"
+        weights = "uniform" if self.weights is None else self.weights
+        law = isinstance(weights, DistanceWeights)
+        if callable(weights) and not law:
+            self._refuse_callable_weights("predict_neighbors_chunks is")
+        self._check_stream_supported("predict_neighbors_chunks is")
+        if isinstance(fill_index, bool) or not isinstance(fill_index, numbers.Integral):
+            raise ValueError(f"fill_index must be an integer, got {fill_index!r}")
+        engine, flat, n_targets, target_dtype = self._replay_target_engine(y)
+        id_table = self._replay_id_table(ids)
+        statistic = resolve_statistic(statistic, outputs, n_targets)
+        plan = statistic if isinstance(statistic, OutputPlan) else None
+        flat = flat and (plan is None or plan.per_target)
+        t_cols = n_targets if plan is None else plan.n_out
+        output = normalize_typed_output(out_dtype, scale, offset, out_nodata, t_cols,
+                                        unknown == "nodata" or (law and weights.can_vanish) or blank)
+        if (zones is None) != (zonal is None):
+            raise ValueError("zones and zonal come together: the zone codes of every tile, and the ZonalStats they are tallied into")
+        zonal_binding = None
+        if zonal is not None:
+            if not isinstance(zonal, ZonalStats):
+                raise TypeError(f"zonal must be a sknnr_amd.ZonalStats, got {type(zonal).__name__}")
+            if not output or np.dtype(output["pred_dtype"]).kind not in "iu":
+                raise NotImplementedError("zonal needs an integer out_dtype (int16, uint16, uint8 or int32): zonal sums are "
+                                          "taken over the stored integers of a typed output")
+            zonal_binding = zonal._check(t_cols, output["pred_dtype"], output.get("scale"), output.get("offset"))
+            zones = iter(zones)
+        if usage is not None and not isinstance(usage, NeighborUsage):
+            raise TypeError(f"usage must be a sknnr_amd.NeighborUsage, got {type(usage).__name__}")
+        needs_dist = [name for name, on in (("weights='distance'", weights == "distance"), ("a weight law", law),
+                                            ("usage", usage is not None), ("domain", domain is not None)) if on]
+
+        def settle(k, has_dist):  # what needs k or the first tile, still before any device work
+            if usage is not None:
+                usage._check(self.n_samples_fit_, k)
+            self._check_domain(domain, domain_out, k, blank)
+            if needs_dist and not has_dist:
+                raise ValueError(f"{' and '.join(needs_dist)} need{'s' if len(needs_dist) == 1 else ''} the stored "
+                                 "distances: pass (dist, idx) tiles")
+        if n_neighbors is not None and (isinstance(n_neighbors, bool) or not isinstance(n_neighbors, numbers.Integral)
+                                        or n_neighbors < 1):
+            raise ValueError(f"n_neighbors must be a positive integer, got {n_neighbors!r}")
+        # (the rank is checked against k by settle(), once the first tile has shown ks)
+        self._check_domain(domain, domain_out, int(n_neighbors) if n_neighbors is not None else np.iinfo(np.int64).max, blank)
+        out_kw = {key: v for key, v in (output or {}).items() if v is not None}
+        pred_dt = np.dtype(out_kw.get("pred_dtype", np.float64))
+        o_pred = None
+        if out is not None:
+            o_pred = out.reshape(1, -1) if bands and out.ndim == 1 else out.reshape(out.shape[0], -1)
+        pieces, tile_of_push, row, stream, shape_key, k = [], [], 0, None, None, None
+        counts = dict(unknown=0, first_unknown=-1)
+        try:
+            for number, tile in enumerate(neighbor_tiles):
+                if zonal is not None:  # (in lockstep: a skipped empty tile consumes its entry too)
+                    try:
+                        tile_zones = next(zones)
+                    except StopIteration:
+                        raise ValueError(_ZONES_SHORT) from None
+                idx, dist = self._replay_tile(tile, bands, number)
+                ks, n = (idx.shape[0], idx.shape[1]) if bands else (idx.shape[1], idx.shape[0])
+                key = (ks, idx.dtype, None if dist is None else dist.dtype)
+                if shape_key is None:
+                    shape_key = key
+                    if ks < 1:
+                        raise ValueError(f"tile {number}: the tile holds no neighbour column")
+                    k = min(self.n_neighbors, ks) if n_neighbors is None else int(n_neighbors)
+                    if k > ks:
+                        raise ValueError(f"n_neighbors={k} is above the {ks} stored neighbour columns")
+                    settle(k, dist is not None)
+                elif key != shape_key:
+                    raise ValueError(f"tile {number}: the tiles of one call share one ks and one dtype pair: got ks={ks}, "
+                                     f"{idx.dtype} / {key[2]} after ks={shape_key[0]}, {shape_key[1]} / {shape_key[2]}")
+                if n == 0:
+                    continue
+                if stream is None:
+                    eng = engine()
+                    if id_table is not None:
+                        eng.set_replay_ids(id_table)
+                    stream = eng.open_replay(k, ks, weights=weights, idx_dtype=idx.dtype,
+                                             dist_dtype=None if dist is None else dist.dtype, fill_index=int(fill_index),
+                                             ids=id_table is not None, output=out_kw,
+                                             **(dict(statistic=statistic) if plan is None else dict(plan=plan.arrays)),
+                                             **({} if usage is None else dict(tally=True)),
+                                             **({} if zonal is None else
+                                                dict(zonal=(zonal.n_zones, zonal.n_classes(zonal_binding[0])))),
+                                             **({} if domain is None else
+                                                dict(domain=(domain.table, domain.rank, domain.threshold, blank))))
+                window = None
+                if o_pred is not None:
+                    if bands:
+                        if o_pred.shape[0] != t_cols or o_pred.dtype != pred_dt or not o_pred.flags.c_contiguous \
+                                or o_pred.shape[1] < row + n:
+                            raise ValueError(f"out must be C-contiguous, {pred_dt}, with {t_cols} rows and at least "
+                                             f"{row + n} columns")
+                        window = o_pred[:, row:row + n]
+                    else:
+                        window = o_pred[row:row + n]
+                        if window.shape != (n, t_cols) or window.dtype != pred_dt or not window.flags.c_contiguous:
+                            raise ValueError(f"out must be C-contiguous, {pred_dt}, with {t_cols} columns and at least "
+                                             f"{row + n} rows")
+                if zonal is not None:
+                    stream.next_zones(normalize_zone_tile(tile_zones, n))
+                if domain_out is not None:
+                    if domain_out.size < row + n:
+                        raise ValueError(f"domain_out holds {domain_out.size} pixels: the tiles hold at least {row + n}")
+                    stream.next_domain_out(domain_out[row:row + n])
+                got = (stream.push_planes if bands else stream.push)(idx, dist, out_pred=window)
+                tile_of_push.append(number)
+                if o_pred is None:
+                    pieces.append(got[2])
+                row += n
+            if zonal is not None and next(zones, None) is not None:
+                raise ValueError(_ZONES_LONG)
+            if shape_key is None:  # (no tile at all: what can be checked without one)
+                settle(self.n_neighbors if n_neighbors is None else int(n_neighbors), True)
+            tallied = zoned = placed = None
+            if stream is not None:
+                done, stream = stream, None
+                try:
+                    counts = done.counts()
+                    if usage is not None:
+                        tallied = done.tally()
+                    if zonal is not None:
+                        zoned = done.zonal()
+                    if domain is not None:
+                        placed = done.domain()
+                finally:
+                    done.close()
+            self.replay_unknown_ = int(counts["unknown"])
+            if counts["unknown"] and unknown == "raise":
+                raise ValueError(f"{counts['unknown']} pixels hold stored neighbours that name no reference row (an id that "
+                                 f"is not in the fitted index, or a position outside [0, {self.n_samples_fit_})); the first "
+                                 f"of them are in tile {tile_of_push[counts['first_unknown']]}.  Pass unknown='nodata' to "
+                                 "store them as nodata pixels")
+            if placed is not None:  # (only a call that came through whole is added)
+                domain._add(placed)
+            if zonal is not None:
+                zonal._bind(*zonal_binding)
+                if zoned is not None:
+                    zonal._add(*zoned)
+            if usage is not None:
+                labels = getattr(self, "dataframe_index_in_", None)
+                if tallied is None:
+                    usage._bind(self.n_samples_fit_, k if k is not None else self.n_neighbors, labels)
+                else:
+                    usage._add(*tallied, labels)
+        except _native.HipBackendError as err:
+            _reraise(err, self)
+        finally:
+            if stream is not None:  # an error on the way: free the native stream without masking it
+                try:
+                    stream.close()
+                except _native.HipBackendError:
+                    pass
+        if o_pred is not None:
+            pred = o_pred[:, :row] if bands else o_pred[:row]
+            if out.ndim == 1:
+                pred = pred.reshape(-1)
+            return pred
+        pred = (np.concatenate(pieces, axis=1 if bands else 0) if pieces
+                else np.empty((t_cols, 0) if bands else (0, t_cols), dtype=pred_dt))
+        if not output and statistic is None and target_dtype == np.float32 and weights == "uniform":
+            pred = pred.astype(np.float32, copy=False)  # (float32 where scikit-learn returns it, as predict_chunks)
+        return pred.reshape(-1) if flat else pred
+
+    def predict_neighbors(self, idx, dist=None, **kwargs):
+        """:meth:`predict_neighbors_chunks` on one tile of stored neighbours, through the same path."""
+        return self.predict_neighbors_chunks([idx if dist is None else (dist, idx)], **kwargs)
+
     def score(self, X, y, sample_weight=None):
         """R^2 of ``predict(X)`` (``X`` may be None as in REF _base.py:40)."""
         pred = self.predict(X)
@@ -2048,6 +2319,21 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
                                                out=out, owner=self.transformer_, nodata=self._raw_nodata(nodata),
                                                bands=bands, typed=(out_dtype, scale, offset, out_nodata),
                                                statistic=statistic, **extra)
+
+    def predict_neighbors_chunks(self, neighbor_tiles, **kwargs):
+        """Attribute maps from STORED neighbours (:meth:`RawKNNRegressor.predict_neighbors_chunks`, with its keywords):
+        the tiles hold neighbours, not feature rows, so nothing is transformed and nothing is searched; ``y=`` counts
+        the fitted samples."""
+        check_is_fitted(self, "regressor_")
+        reg = self.regressor_
+        try:
+            return reg.predict_neighbors_chunks(neighbor_tiles, **kwargs)
+        finally:
+            self.replay_unknown_ = getattr(reg, "replay_unknown_", 0)
+
+    def predict_neighbors(self, idx, dist=None, **kwargs):
+        """:meth:`predict_neighbors_chunks` on one tile of stored neighbours, through the same path."""
+        return self.predict_neighbors_chunks([idx if dist is None else (dist, idx)], **kwargs)
 
     def score(self, X, y):
         """REF _base.py:350-352."""

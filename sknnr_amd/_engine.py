@@ -674,6 +674,65 @@ class KNNEngine:
                                        output=output, statistic=statistic, id_table=id_table, fill_id=fill_id, plan=plan,
                                        tally=tally, zonal=zonal, domain=domain)
 
+    @classmethod
+    def for_targets(cls, y, device: int | None = None, target_dtype=None):
+        """An attribute-only engine: it owns the ``(n_ref, t)`` table ``y`` (:class:`sknnr_amd._native.TargetIndex`) and
+        serves :meth:`open_replay` and the from-neighbours reductions; it has no reference rows and searches nothing."""
+        self = cls.__new__(cls)
+        self.device = default_device() if device is None else int(device)
+        self._index = _native.TargetIndex(y, device=self.device)
+        self.n_ref, self.d, self.t = self._index.n_ref, 0, self._index.t
+        self.y32 = target_dtype is not None and np.dtype(target_dtype) == np.float32
+        self.d_in = 0
+        self.has_affine = self.has_forest = False
+        self._law_key = self._group_codes = self._buffer = None
+        return self
+
+    def set_replay_ids(self, ids):
+        """The int64 dataframe ids replay streams look stored ids up in (None: none); uploaded when they change."""
+        key = None if ids is None else np.ascontiguousarray(ids, dtype=np.int64)
+        held = getattr(self, "_replay_ids", None)
+        if (key is None) != (held is None) or (key is not None and not np.array_equal(key, held)):
+            self._index.set_replay_ids(key)
+            self._replay_ids = key
+
+    def open_replay(self, k, ks, *, weights=None, idx_dtype=np.int64, dist_dtype=None, fill_index=-1, ids=False,
+                    want_dist=False, output=None, statistic=None, id_table=None, fill_id=-1, plan=None, tally=False,
+                    zonal=None, domain=None):
+        """A :class:`sknnr_amd._native.ReplayStream`: tiles of ``ks`` stored neighbour columns (``idx_dtype`` int32 /
+        int64, ``dist_dtype`` float32 / float64 or None) in place of feature rows, the leading ``k`` in use; ``ids``:
+        the stored values are ids of :meth:`set_replay_ids`.  Every other keyword as in :meth:`open_stream`."""
+        want_pred = weights is not None
+        law = self.weight_law(weights)
+        if want_pred and not law and weights not in _WEIGHT_MODES:
+            raise ValueError("a stream predicts with 'uniform' or 'distance' weights, or a sknnr_amd.weights law, only")
+        if (statistic is not None or plan is not None) and not want_pred:
+            raise ValueError("statistics and output plans need a stream that predicts: pass weights")
+        if plan is not None and statistic is not None:
+            raise ValueError("a stream takes statistic or an output plan, not both")
+        mode = self.weight_mode("explicit" if law else weights) if want_pred else _native.WEIGHTS_UNIFORM
+        stream = self._index.open_replay(k, ks, weight_mode=mode, weight_law=law, idx_dtype=idx_dtype, dist_dtype=dist_dtype,
+                                         fill_index=fill_index, ids=ids, want_dist=want_dist, want_pred=want_pred)
+        try:  # (the order of Index.open_stream)
+            if plan is not None:
+                stream.set_plan(plan)
+            if output:
+                stream.set_output(**output)
+            if statistic is not None:
+                stream.set_statistics(statistic)
+            if id_table is not None:
+                stream.set_id_table(id_table, fill_id)
+            if tally:
+                stream.set_tally()
+            if zonal is not None:
+                stream.set_zonal(*zonal)
+            if domain is not None:
+                stream.set_domain(*domain)
+        except Exception:
+            stream.close()
+            raise
+        return stream
+
     def hamming_distances(self, X, rows=None):
         """Full weighted-Hamming distance rows of ``X[rows]`` (``X`` None: of the fitted rows) from the device."""
         return self._index.hamming_distances_host(X, rows)

@@ -139,6 +139,13 @@ EXPORTED_SYMBOLS = (
     "sknnr_stream_get_domain",
     "sknnr_debug_last_domain",
     "sknnr_debug_domain_geometry",
+    "sknnr_index_create_targets",
+    "sknnr_index_set_replay_ids",
+    "sknnr_replay_begin",
+    "sknnr_replay_push",
+    "sknnr_replay_push_planes",
+    "sknnr_replay_get_counts",
+    "sknnr_debug_last_replay",
     "sknnr_debug_last_narrow",
     "sknnr_debug_last_mask",
     "sknnr_debug_mask_compact",
@@ -383,6 +390,15 @@ def load(build_if_missing: bool = False):
         lib.sknnr_stream_get_domain.argtypes = [vp, vp]
         lib.sknnr_debug_last_domain.argtypes = [vp, POINTER(c_int64)]
         lib.sknnr_debug_domain_geometry.argtypes = [c_int64, POINTER(c_int64)]
+    if hasattr(lib, "sknnr_replay_begin"):  # (likewise)
+        lib.sknnr_index_create_targets.argtypes = [vp, c_int64, c_int32, c_int32, POINTER(vp)]
+        lib.sknnr_index_set_replay_ids.argtypes = [vp, vp, c_int64]
+        lib.sknnr_replay_begin.argtypes = [vp, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32,
+                                           c_int32, POINTER(vp)]
+        lib.sknnr_replay_push.argtypes = [vp, vp, vp, c_int64, vp, vp, vp]
+        lib.sknnr_replay_push_planes.argtypes = [vp, vp, vp, c_int64, c_int64, vp, vp, vp, c_int64]
+        lib.sknnr_replay_get_counts.argtypes = [vp, POINTER(c_int64)]
+        lib.sknnr_debug_last_replay.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_shard_candidates.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int64, vp, vp, c_int32, vp]
     lib.sknnr_merge_shards.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int32, vp, vp, vp, vp, c_int32, vp]
     lib.sknnr_crosswalk.argtypes = [vp, c_int64, vp, c_int64, vp, c_int32, c_int32, vp]
@@ -636,6 +652,28 @@ class Index:
         """The handle's distance-weight law (a ``WEIGHT_LAWS`` code, 0 clears) and its two float64 parameters
         (sknnr_index_set_weight_law_params); calls whose opts name the law use them."""
         check(load().sknnr_index_set_weight_law_params(self.handle, int(law), float(p0), float(p1)))
+
+    def set_replay_ids(self, ids) -> None:
+        """The id table of replay streams whose stored values are ids (sknnr_index_set_replay_ids): one int64 id per
+        reference row, unique; None removes it."""
+        if ids is None:
+            check(load().sknnr_index_set_replay_ids(self.handle, None, 0))
+            return
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        check(load().sknnr_index_set_replay_ids(self.handle, _host_ptr(ids), int(ids.size)))
+
+    def open_replay(self, k, ks, *, weight_mode=0, weight_law=0, idx_dtype=np.int64, dist_dtype=None, fill_index=-1,
+                    ids=False, want_dist=False, want_pred=True):
+        """A :class:`ReplayStream` on this handle (sknnr_replay_begin): tiles of ``ks`` stored neighbour columns of
+        ``idx_dtype`` (int32 / int64) and ``dist_dtype`` (float32 / float64, None: no distances), of which the leading
+        ``k`` are used."""
+        return ReplayStream(self, k, ks, weight_mode, weight_law, idx_dtype, dist_dtype, fill_index, ids, want_dist, want_pred)
+
+    def debug_last_replay(self) -> dict:
+        """Debug only: the last replayed tile of the handle (sknnr_debug_last_replay)."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_replay(self.handle, out))
+        return dict(zip(("pixels", "masked", "unknown", "instance", "skeleton", "search_launches", "k", "ks"), map(int, out)))
 
     def check_finite(self, stream=0) -> None:
         """Poll the non-finite-input flag of device-memory calls made with ``check_finite``
@@ -1248,6 +1286,10 @@ class QueryStream:
         self._zonal = None  # (n_zones, elements of hist per zone) once set_zonal was called
         self._domain = False
         self._domain_out = None  # the code plane named for the next push (next_domain_out)
+        self._idx_by_default = True  # a push that predicts nothing delivers the indices even unasked
+        self._begin(index, opts)
+
+    def _begin(self, index, opts):
         check(load().sknnr_stream_begin(index.handle, byref(opts), int(self.want_dist), int(self.want_pred),
                                         byref(self._h)))
 
@@ -1256,7 +1298,7 @@ class QueryStream:
         outputs are allocated, the given ones validated -- ``(nq, cols)`` rows, or ``(cols, nq)`` planes that share one
         stride -- and all of them kept alive while the tile may be in the pipeline."""
         outs, strides = [], set()  # (strides in ELEMENTS of each output's own type: the outputs share the pixel axis, not the byte count)
-        for a, dt, cols, wanted in ((out_idx, self.idx_dtype, self.k, need_idx or not self.want_pred),
+        for a, dt, cols, wanted in ((out_idx, self.idx_dtype, self.k, need_idx or (self._idx_by_default and not self.want_pred)),
                                     (out_dist, self.dist_dtype, self.k, self.want_dist),
                                     (out_pred, self.pred_dtype, self.pred_cols, self.want_pred)):
             if a is None and wanted:
@@ -1474,6 +1516,113 @@ class QueryStream:
                 self._h = c_void_p()
         except Exception:
             pass
+
+
+class TargetIndex(Index):
+    """Owner of an attribute-only ``sknnr_index*`` (sknnr_index_create_targets): a target table and nothing else.  The
+    from-neighbours entries and replay streams accept it; whatever searches refuses it."""
+
+    def __init__(self, y, device: int = 0):
+        y2 = _c_f64(y)
+        if y2.ndim == 1:
+            y2 = y2.reshape(-1, 1)
+        if y2.ndim != 2:
+            raise ValueError("y must be 1-D or 2-D")
+        self.n_ref, self.t = y2.shape
+        self.d = self.d_in = 0
+        self.device = device
+        self._h = c_void_p()
+        check(load().sknnr_index_create_targets(_host_ptr(y2), self.n_ref, self.t, device, byref(self._h)))
+
+
+# stored neighbour types of a replay stream: numpy dtype -> the sknnr_replay_begin code
+REPLAY_NO_DIST = -1
+REPLAY_IDX_CODES = {np.dtype(np.int64): 0, np.dtype(np.int32): DTYPE_CODES[np.dtype(np.int32)]}
+REPLAY_DIST_CODES = {np.dtype(np.float64): 0, np.dtype(np.float32): DTYPE_CODES[np.dtype(np.float32)]}
+
+
+def replay_instance(idx_dtype, dist_dtype, planes: bool) -> int:
+    """The decode instantiation ``Index.debug_last_replay()["instance"]`` names (sknnr_amd/csrc/replay.hip.h)."""
+    dk = 0 if dist_dtype is None else (1 if np.dtype(dist_dtype) == np.float32 else 2)
+    return (6 if np.dtype(idx_dtype) == np.int64 else 0) + 2 * dk + int(bool(planes))
+
+
+class ReplayStream(QueryStream):
+    """A stream whose tiles are stored neighbours (sknnr_replay_begin): every setter and getter of
+    :class:`QueryStream` but :meth:`set_nodata` works on it unchanged."""
+
+    def __init__(self, index, k, ks, weight_mode=0, weight_law=0, idx_dtype=np.int64, dist_dtype=None, fill_index=-1,
+                 ids=False, want_dist=False, want_pred=True):
+        self.ks = int(ks)
+        self.store_idx = np.dtype(idx_dtype)
+        self.store_dist = None if dist_dtype is None else np.dtype(dist_dtype)
+        if self.store_idx not in REPLAY_IDX_CODES:
+            raise ValueError(f"stored indices must be int32 or int64, got {self.store_idx}")
+        if self.store_dist is not None and self.store_dist not in REPLAY_DIST_CODES:
+            raise ValueError(f"stored distances must be float32 or float64, got {self.store_dist}")
+        self._replay = (int(fill_index), bool(ids))
+        opts = Index.make_opts(int(k))
+        opts.weight_mode, opts.weight_law = int(weight_mode), int(weight_law)
+        super().__init__(index, opts, want_dist=want_dist, want_pred=want_pred)
+        self._idx_by_default = False
+
+    def _begin(self, index, opts):
+        fill_index, ids = self._replay
+        dc = REPLAY_NO_DIST if self.store_dist is None else REPLAY_DIST_CODES[self.store_dist]
+        check(load().sknnr_replay_begin(index.handle, opts.n_neighbors, self.ks, opts.weight_mode, opts.weight_law,
+                                        REPLAY_IDX_CODES[self.store_idx], dc, fill_index, int(ids), int(self.want_dist),
+                                        int(self.want_pred), byref(self._h)))
+
+    def _stored(self, idx, dist, shape):
+        """The tile's arrays as the push reads them: of the stream's stored types, C-contiguous, ``shape``."""
+        if (dist is None) != (self.store_dist is None):
+            raise ValueError("a tile carries distances exactly when the stream was opened with stored distances")
+        out = []
+        for a, dt in ((idx, self.store_idx), (dist, self.store_dist)):
+            if a is None:
+                out.append(None)
+                continue
+            a = np.asarray(a)
+            if a.dtype != dt or a.shape != shape:
+                raise ValueError(f"a stored tile must be {shape} {dt}, got {a.shape} {a.dtype}")
+            out.append(np.ascontiguousarray(a))
+        return out
+
+    def push(self, idx, dist=None, out_idx=None, out_dist=None, out_pred=None, need_idx=False):
+        """Replay the ``(n, ks)`` row tile ``idx`` (and ``dist``); returns the (idx, dist, pred) result arrays."""
+        idx = np.asarray(idx)
+        if idx.ndim != 2 or idx.shape[1] != self.ks:
+            raise ValueError(f"a stored row tile must be (n, {self.ks}), got {idx.shape}")
+        idx, dist = self._stored(idx, dist, idx.shape)
+        lib = load()
+
+        def native(h, tile, nq, od, oi, op):
+            return lib.sknnr_replay_push(h, _host_ptr(tile[0]), _host_ptr(tile[1]), nq, od, oi, op)
+        return self._push(native, (idx, dist), idx.shape[0], False, out_idx, out_dist, out_pred, need_idx)
+
+    def push_planes(self, idx, dist=None, out_idx=None, out_dist=None, out_pred=None, need_idx=False):
+        """Replay the band-first ``(ks, n)`` tile ``idx`` (and ``dist``); returns band-first result arrays."""
+        idx = np.asarray(idx)
+        if idx.ndim != 2 or idx.shape[0] != self.ks:
+            raise ValueError(f"a stored band-first tile must be ({self.ks}, n), got {idx.shape}")
+        idx, dist = self._stored(idx, dist, idx.shape)
+        nq = idx.shape[1]
+        lib = load()
+
+        def native(h, tile, nq, od, oi, op, stride):
+            return lib.sknnr_replay_push_planes(h, _host_ptr(tile[0]), _host_ptr(tile[1]), nq, nq, od, oi, op, stride)
+        return self._push(native, (idx, dist), nq, True, out_idx, out_dist, out_pred, need_idx)
+
+    def set_nodata(self, nodata, fill_index=-1):
+        check(load().sknnr_stream_set_nodata(self._h, _host_ptr(_c_f64(nodata).reshape(-1)), int(fill_index)))
+
+    def counts(self) -> dict:
+        """Flush, then the pixels, masked and unknown pixels of the stream so far, and the first push that held unknown
+        values (-1: none) (sknnr_replay_get_counts)."""
+        out = (c_int64 * 4)()
+        check(load().sknnr_replay_get_counts(self._h, out))
+        self._keep.clear()
+        return dict(zip(("pixels", "masked", "unknown", "first_unknown"), map(int, out)))
 
 
 def affine_transform_host(x, center=None, scale=None, proj=None, device: int = 0) -> np.ndarray:

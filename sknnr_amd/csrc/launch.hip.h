@@ -1,9 +1,9 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_buffer.hip, k_tally.hip, k_zonal.hip, k_domain.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_buffer.hip, k_tally.hip, k_zonal.hip, k_domain.hip, k_replay.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
-// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS / SKNNR_KERNELS_TALLY / SKNNR_KERNELS_ZONAL / SKNNR_KERNELS_BUFFER / SKNNR_KERNELS_DOMAIN), templates where they are instantiated.
+// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS / SKNNR_KERNELS_TALLY / SKNNR_KERNELS_ZONAL / SKNNR_KERNELS_BUFFER / SKNNR_KERNELS_DOMAIN / SKNNR_KERNELS_REPLAY), templates where they are instantiated.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +21,7 @@
 #include "narrow.hip.h"
 #include "plan.hip.h"
 #include "planes.hip.h"
+#include "replay.hip.h"
 #include "rescue.hip.h"
 #include "summary.hip.h"
 #include "tally.hip.h"
@@ -137,6 +138,15 @@ hipError_t zonal_init(long long* acc, long n_keys, hipStream_t st);
 // and a mask without a threshold
 hipError_t domain(const DomainArgs& a, hipStream_t st);
 long domain_blocks(long n);  // its workgroups
+
+// ---- k_replay.hip: stored neighbour tiles into the full-layout tile (replay.hip.h) ----------------------------------------------
+// decodes the a.n pixels into a.out_idx / a.out_dist / a.bad and adds them into a.rec (not zeroed here); idx_bytes 4 or 8,
+// dist_kind kReplayDistNone / F32 / F64, planes: the stored layout; hipErrorInvalidValue for k outside [1, ks], an
+// unknown type, missing arrays, an id table of more than 2^31 - 1 entries and planes closer together than a.n
+hipError_t replay(const ReplayArgs& a, int idx_bytes, int dist_kind, bool planes, hipStream_t st);
+long replay_blocks(long n);  // its workgroups
+// the final state of the pixels a.bad marks, behind the reduction of a tile decoded with ReplayArgs::provisional
+hipError_t replay_blank(const ReplayBlankArgs& a, hipStream_t st);
 
 // ---- k_coarse1.hip / k_coarse2.hip: the MFMA pre-filters ----------------------------------------------------------------
 struct Coarse1Launch {

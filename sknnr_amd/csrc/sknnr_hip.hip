@@ -536,6 +536,19 @@ struct sknnr_index {
     DevBuf<unsigned long long> s_dom_acc, dom_rec;
     int64_t last_domain[5] = {};
     int last_domain_half = 0;
+    // neighbour replay (replay.hip.h).  targets_only: the handle was made by sknnr_index_create_targets and owns y64 and
+    // nothing of a search.  The sorted id table of sknnr_index_set_replay_ids and the row position of each of its entries;
+    // the per-tile records of the open replay stream, one per pipeline slot, on the device and pinned; the searches the
+    // handle has run (run_device), so that a replayed tile can show that it ran none; the record of the last tile
+    // (sknnr_debug_last_replay).
+    bool targets_only = false;
+    DevBuf<long> r_id_sorted;
+    DevBuf<int> r_id_perm;
+    long r_id_n = 0;
+    DevBuf<unsigned long long> replay_rec;
+    unsigned long long* pin_replay = nullptr;
+    long search_calls = 0;
+    int64_t last_replay[8] = {};
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
     // a ring of call records so that several calls of one benchmark step are summed, not only the last.
@@ -566,6 +579,7 @@ struct sknnr_index {
         }
         for (hipStream_t h : {st_h2d, st_run, st_d2h})
             if (h) (void)hipStreamDestroy(h);
+        if (pin_replay) (void)hipHostFree(pin_replay);
         if (ev_ws) (void)hipEventDestroy(ev_ws);
         if (st_side) (void)hipStreamDestroy(st_side);
         for (hipEvent_t e : {ev_fork, ev_join})
@@ -580,6 +594,13 @@ struct sknnr_index {
         }
     }
 };
+
+// An attribute-only handle (sknnr_index_create_targets) has no reference rows: whatever searches, or configures a search,
+// refuses it before any device work.
+static int refuse_targets_only(const char* entry) {
+    return fail(SKNNR_ERR_INVALID, "%s: the handle holds a target table only (sknnr_index_create_targets): it has no "
+                "reference rows to search; it serves the from-neighbours entries and replay streams", entry);
+}
 
 // ----------------------------------------------------------------------------------------
 // misc entry points
@@ -1172,6 +1193,7 @@ extern "C" void sknnr_index_destroy(sknnr_index* ix) { delete ix; }
 extern "C" int sknnr_index_set_affine(sknnr_index* ix, int32_t d_in, const double* center,
                                       const double* scale, const double* proj) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (ix->targets_only) return refuse_targets_only("sknnr_index_set_affine");
     if (d_in < 1) return fail(SKNNR_ERR_INVALID, "d_in must be >= 1");
     if (!proj && d_in != ix->d)
         return fail(SKNNR_ERR_INVALID, "without a projection d_in (%d) must equal d (%d)", d_in, ix->d);
@@ -1204,6 +1226,7 @@ extern "C" int sknnr_index_set_affine(sknnr_index* ix, int32_t d_in, const doubl
 
 extern "C" int sknnr_index_set_hamming_weights(sknnr_index* ix, const double* w, int32_t n) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (ix->targets_only) return refuse_targets_only("sknnr_index_set_hamming_weights");
     if (!w || n != ix->d) return fail(SKNNR_ERR_INVALID, "w must hold one weight per column (%d), got %d", ix->d, n);
     double total = 0.0;
     for (int i = 0; i < n; ++i) {
@@ -1266,6 +1289,7 @@ extern "C" int sknnr_index_set_forest(sknnr_index* ix, int32_t d_in, int32_t n_t
                                       const double* threshold, const int32_t* feature, const int32_t* left,
                                       const int32_t* right) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (ix->targets_only) return refuse_targets_only("sknnr_index_set_forest");
     if (d_in < 1) return fail(SKNNR_ERR_INVALID, "d_in must be >= 1");
     if (n_trees != ix->d) return fail(SKNNR_ERR_INVALID, "the forests have %d trees, the node-id rows %d columns", n_trees, ix->d);
     if (!tree_offset || !threshold || !feature || !left || !right) return fail(SKNNR_ERR_INVALID, "NULL forest array");
@@ -1778,6 +1802,7 @@ int query_cols(const sknnr_index* ix, const sknnr_query_opts* o) {
 
 int validate_call(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, int64_t* out_idx) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (ix->targets_only) return refuse_targets_only("a search call");
     if (!o) return fail(SKNNR_ERR_INVALID, "opts is NULL");
     if (o->query_dtype < 0 || o->query_dtype >= kDtypeCount) return fail(SKNNR_ERR_INVALID, "unknown query_dtype %d", o->query_dtype);
     const bool forest_map = uses_forest(ix, o);  // (the forest kernel reads every sknnr_dtype)
@@ -2148,6 +2173,7 @@ int scan_tail(sknnr_index* ix, const SearchPlan& p, const SelectArgs& call, long
 int run_device(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opts* o, double* d_dist,
                long* d_idx, hipStream_t st, int raw = 0, long id_offset = 0) {
     zero_records(ix);
+    ++ix->search_calls;
     if (xdev && uses_forest(ix, o)) return run_forest(ix, xdev, nq, o, d_dist, d_idx, st);
     const SearchPlan p = plan_search(describe(ix), o, nq, xdev != nullptr, raw);
     if (nq > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 query rows in one call");
@@ -2476,6 +2502,41 @@ int ensure_pinned(T*& p, size_t& have, size_t want) {
     return SKNNR_OK;
 }
 
+// ---- neighbour replay: what a pipeline's tiles hold instead of feature rows (replay.hip.h) -----------------------------------
+struct ReplaySpec {
+    bool on = false;
+    int ks = 0;                      // stored columns (the pipeline's k leading ones are used)
+    int idx_bytes = 8;               // 4: int32, 8: int64
+    int dist_kind = kReplayDistNone;
+    bool ids = false;                // the stored values are ids of the handle's table (sknnr_index_set_replay_ids)
+    long fill_index = -1;
+    int dist_bytes() const { return dist_kind == kReplayDistNone ? 0 : (dist_kind == kReplayDistF32 ? 4 : 8); }
+};
+// the stored arrays of one push: rows (n, ks), or planes `stride` elements apart; dist null without distances
+struct ReplaySrc {
+    const char* idx = nullptr;
+    const char* dist = nullptr;
+    bool planes = false;
+    long stride = 0;
+};
+// A tile of n pixels as it is staged and uploaded: the index block -- rows (n, ks) or planes (ks, n), packed -- and,
+// 16-byte aligned behind it, the distance block in the same layout.
+size_t replay_dist_offset(const ReplaySpec& r, long n) { return ((size_t)n * r.ks * r.idx_bytes + 15) & ~(size_t)15; }
+size_t replay_tile_bytes(const ReplaySpec& r, long n) { return replay_dist_offset(r, n) + (size_t)n * r.ks * r.dist_bytes(); }
+// Staging copy of pixels [off, off + n) of a push: plain copies, one per block of a row tile, one per plane otherwise.
+void stage_replay(void* dst, const ReplaySpec& r, const ReplaySrc& s, long off, long n) {
+    const auto block = [&](char* to, const char* from, size_t esz) {
+        if (!s.planes) {
+            parallel_copy(to, from + (size_t)off * r.ks * esz, (size_t)n * r.ks * esz);
+            return;
+        }
+        for (int j = 0; j < r.ks; ++j)
+            parallel_copy(to + (size_t)j * n * esz, from + ((size_t)j * s.stride + off) * esz, (size_t)n * esz);
+    };
+    block((char*)dst, s.idx, (size_t)r.idx_bytes);
+    if (r.dist_kind != kReplayDistNone) block((char*)dst + replay_dist_offset(r, n), s.dist, (size_t)r.dist_bytes());
+}
+
 // Pageable host arrays in, pageable host arrays out, through kHostSlots pinned/device slots:
 //   host thread : copy tile c into its slot's pinned buffer | copy results of tile c - kHostSlots out
 //   st_h2d      : pinned -> device                          (PCIe)
@@ -2520,6 +2581,14 @@ struct HostPipe {
     bool domain = false, domain_mask = false;
     DomainSpec domain_spec{};
     uint8_t* domain_push = nullptr;
+    // neighbour replay (sknnr_replay_begin): the tiles are stored neighbours, decoded on the device where a search would
+    // run (replay_tile); replay_src: the arrays of the push in progress; replay_tot / replay_first: pixels, masked and
+    // unknown pixels of the tiles that have left so far, and the first push that held unknown values (-1: none yet)
+    ReplaySpec replay{};
+    ReplaySrc replay_src{};
+    long replay_push_no = -1;
+    int64_t replay_tot[3] = {};
+    long replay_first = -1;
     size_t x_esz = sizeof(double);  // bytes per element of the caller's rows (opts->query_dtype)
     // nodata front end: every tile is masked behind its host-to-device copy, and o.row_offset advances by its VALID rows
     const double* nodata_dev = nullptr;  // (d_x) on the device, or null: no mask
@@ -2538,6 +2607,7 @@ struct HostPipe {
         bool planes = false;   // the tile was pushed band-first: its results leave as planes, out_stride elements apart
         long out_stride = 0;
         uint8_t* domain_out = nullptr;  // the caller's code plane of the tile (a domain pipeline; null: not asked for)
+        long replay_push_no = 0;        // the push the tile came with (a replay pipeline)
         std::future<int> out_done;  // copy-out job of the slot's tile (w_out)
     } pending[kHostSlots];
     int slot_of = 0;
@@ -2607,6 +2677,13 @@ int pipe_drain(HostPipe& p, int b) {
     p.ms_wait += now_ms() - t0;
     pd.live = false;
     if (rc) return fail(rc, "host pipeline: copying a tile's results out failed (HIP error while waiting for the device-to-host copy)");
+    if (p.replay.on) {
+        // (the tile's record arrived with its results: the copy-out job waited for the event behind both)
+        const unsigned long long* rec = p.ix->pin_replay + (size_t)b * kReplayRecWords;
+        for (int w = 0; w < 3; ++w) p.ix->last_replay[w] = (int64_t)rec[w];
+        for (int w = 0; w < 3; ++w) p.replay_tot[w] += (int64_t)rec[w];
+        if (rec[kReplayRecUnknown] && p.replay_first < 0) p.replay_first = pd.replay_push_no;
+    }
     return SKNNR_OK;
 }
 
@@ -2616,10 +2693,12 @@ int pipe_prepare_slot(HostPipe& p, int b, long n, bool planes = false) {
     auto& sl = ix->slot[b];
     int rc = pipe_drain(p, b);  // the slot's previous tile must have left before its buffers are reused
     if (rc) return rc;
-    const size_t x_f64 = ((size_t)n * p.d_x * p.x_esz + 7) / 8;  // the tile's rows, in 8-byte units
+    // the tile's rows -- or, replayed, its stored neighbours -- in 8-byte units
+    const size_t x_f64 = ((p.replay.on ? replay_tile_bytes(p.replay, n) : (size_t)n * p.d_x * p.x_esz) + 7) / 8;
     if ((rc = ensure_pinned(sl.pin_x, sl.pin_x_n, x_f64))) return rc;
     HIP_TRY(sl.dev_x.ensure(x_f64));
-    if (planes) HIP_TRY(sl.dev_xp.ensure(x_f64));  // (band-first tiles only: the uploaded planes)
+    if (planes && !p.replay.on) HIP_TRY(sl.dev_xp.ensure(x_f64));  // (band-first tiles only: the uploaded planes)
+    if (p.replay.on) HIP_TRY(sl.mask.valid.ensure((size_t)n));     // (the decode's bad-pixel flags)
     if (p.zonal) {
         if ((rc = ensure_pinned(sl.pin_z, sl.pin_z_n, (size_t)n))) return rc;
         HIP_TRY(sl.dev_z.ensure((size_t)n));
@@ -2685,6 +2764,9 @@ int pipe_enqueue_d2h(HostPipe& p) {
     uint8_t* const dom_dst = pd.domain_out;  // (a domain pipeline's code plane: n bytes in pixel order in either layout)
     const uint8_t* const dom_pin = sl.pin_dom;
     if (dom_dst) HIP_TRY(hipMemcpyAsync(sl.pin_dom, sl.dev_dom.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    if (p.replay.on)  // (the tile's record: pipe_drain adds it up once the copy-out job has waited for ev_d2h)
+        HIP_TRY(hipMemcpyAsync(ix->pin_replay + (size_t)b * kReplayRecWords, ix->replay_rec.p + (size_t)b * kReplayRecWords,
+                               kReplayRecWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(sl.ev_d2h, st));
     // the copy-out leg: wait for the tile's device-to-host copies, then pinned -> the caller's arrays (w_out, in order)
     {
@@ -2712,6 +2794,48 @@ int pipe_enqueue_d2h(HostPipe& p) {
     return SKNNR_OK;
 }
 
+// The replayed tile of slot b on st_run, where a search tile has its search, tally and reduction: the decode of the
+// uploaded stored neighbours into d_idx (n, k) / d_dist (n, k; null without stored distances); with d_pred the reduction
+// on the provisional tile and the blanking pass behind it (replay.hip.h); then the tally, on the tile's final state, whose
+// negative indices it skips.  The caller holds the stream's SummaryScope / PlanScope.
+int replay_tile(HostPipe& p, int b, long n, bool planes, long* d_idx, double* d_dist, double* d_pred) {
+    sknnr_index* ix = p.ix;
+    auto& sl = ix->slot[b];
+    const ReplaySpec& r = p.replay;
+    hipStream_t st = ix->st_run;
+    unsigned long long* rec = ix->replay_rec.p + (size_t)b * kReplayRecWords;
+    HIP_TRY(hipMemsetAsync(rec, 0, kReplayRecWords * sizeof(unsigned long long), st));
+    ReplayArgs a{};
+    a.idx = sl.dev_x.p;
+    a.dist = d_dist ? (const char*)sl.dev_x.p + replay_dist_offset(r, n) : nullptr;
+    a.n = n;
+    a.ks = r.ks;
+    a.k = p.k;
+    a.in_stride = n;  // (the staged planes are packed)
+    a.fill_index = r.fill_index;
+    a.n_ref = ix->n_ref;
+    a.id_sorted = r.ids ? ix->r_id_sorted.p : nullptr;
+    a.id_perm = r.ids ? ix->r_id_perm.p : nullptr;
+    a.m = r.ids ? ix->r_id_n : 0;
+    a.provisional = d_pred ? 1 : 0;
+    a.out_idx = d_idx;
+    a.out_dist = d_dist;
+    a.bad = sl.mask.valid.p;
+    a.rec = rec;
+    HIP_TRY(launch::replay(a, r.idx_bytes, r.dist_kind, planes, st));
+    int rc;
+    if (d_pred) {
+        if ((rc = launch_predict(ix, d_dist, d_idx, nullptr, n, p.k, p.o.weight_mode, p.o.weight_law, d_pred, st))) return rc;
+        const ReplayBlankArgs ba{sl.mask.valid.p, n, p.k, p.lane[kLanePred].cols, d_idx, d_dist, d_pred};
+        HIP_TRY(launch::replay_blank(ba, st));
+    }
+    if (p.tally && (rc = tally_tile(ix, d_dist, d_idx, n, p.k, st))) return rc;
+    const int64_t lr[8] = {0, 0, 0, replay_instance(r.idx_bytes, r.dist_kind, planes), r.ids ? 1 : 0,
+                           0, p.k, r.ks};  // ([0 .. 2]: pipe_drain, when the tile has left; [5]: pipe_submit)
+    std::copy(lr + 3, lr + 8, ix->last_replay + 3);
+    return SKNNR_OK;
+}
+
 // One tile of at most host_chunk_rows() rows.  `q` may be reused by the caller as soon as this returns.
 // q_next / n_next: the tile the same call will submit next (or null): its rows are staged into the next slot's pinned
 // buffer by the copy-in worker while this tile is enqueued and the caller waits for older results.
@@ -2733,6 +2857,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     const auto& pred = sl.lane[kLanePred];
     const bool want_pred = p.lane[kLanePred].want;
     const int k = p.k, d_x = p.d_x;
+    const long searches0 = ix->search_calls;
     int rc;
     const double t_in = now_ms();
     if (p.ahead_slot == b && p.ahead_q == q && p.ahead_done.valid()) {
@@ -2741,14 +2866,17 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
         if (rc) return rc;
     } else {
         if ((rc = pipe_prepare_slot(p, b, n, planes != nullptr))) return rc;
-        if (planes) stage_planes(sl.pin_x, planes, d_x, p.x_esz, p_off, n);
+        if (p.replay.on) stage_replay(sl.pin_x, p.replay, p.replay_src, p_off, n);
+        else if (planes) stage_planes(sl.pin_x, planes, d_x, p.x_esz, p_off, n);
         else parallel_copy(sl.pin_x, q, (size_t)n * d_x * p.x_esz);
         if (p.zonal) parallel_copy(sl.pin_z, zones, (size_t)n * sizeof(int32_t));
     }
+    const bool planes_in = planes && !p.replay.on;  // (a replayed band-first tile is decoded from its planes as they are)
     const double t_enq = now_ms();
     p.ms_copy_in += t_enq - t_in;
-    HIP_TRY(hipMemcpyAsync(planes ? sl.dev_xp.p : sl.dev_x.p, sl.pin_x, (size_t)n * d_x * p.x_esz, hipMemcpyHostToDevice, ix->st_h2d));
-    if (planes) {  // behind the copy, in front of the mask: dev_x as an uploaded row tile would have filled it
+    HIP_TRY(hipMemcpyAsync(planes_in ? sl.dev_xp.p : sl.dev_x.p, sl.pin_x,
+                           p.replay.on ? replay_tile_bytes(p.replay, n) : (size_t)n * d_x * p.x_esz, hipMemcpyHostToDevice, ix->st_h2d));
+    if (planes_in) {  // behind the copy, in front of the mask: dev_x as an uploaded row tile would have filled it
         PlanesArgs pa{sl.dev_xp.p, sl.dev_x.p, n, d_x, n};
         HIP_TRY(launch::planes_to_rows(pa, (int)p.x_esz, ix->st_h2d));
     }
@@ -2771,7 +2899,12 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     HIP_TRY(hipStreamWaitEvent(ix->st_run, sl.ev_h2d, 0));
     SummaryScope scope(ix, p.has_stat ? &p.stat : ix->summary);  // (a one-shot call's plan is already in place)
     PlanScope plan_scope(ix, p.has_plan ? &p.plan : ix->plan);
-    if (p.nodata_dev) {
+    if (p.replay.on) {
+        // stored neighbours: the decode leaves the tile as a search and its nodata expansion would; nothing of the search runs
+        rc = replay_tile(p, b, n, planes != nullptr, idx.i64(), p.replay.dist_kind != kReplayDistNone ? dist.f64() : nullptr,
+                         want_pred ? pred.f64() : nullptr);
+        if (rc) return rc;
+    } else if (p.nodata_dev) {
         // (distances only where the slot has packed distances to expand from: mask_ensure sizes them by the same rule)
         rc = mask_finish(ix, sl.mask, sl.dev_x.p, n, nv, &p.o, p.fill_index, p.mask_dist ? dist.f64() : nullptr, idx.i64(),
                          want_pred ? pred.f64() : nullptr, p.o.row_offset - p.row_offset0, ix->st_run, p.tally);
@@ -2829,8 +2962,8 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
         std::copy(std::begin(rec), std::end(rec), ix->last_narrow);
     }
     {
-        const int64_t rec[8] = {planes ? 1 : 0, n, d_x, (int64_t)p.x_esz, planes ? 1 : 0, planes_out,
-                                planes ? planes_chunk_cols((int)p.x_esz) : 0, 0};
+        const int64_t rec[8] = {planes_in ? 1 : 0, n, d_x, (int64_t)p.x_esz, planes ? 1 : 0, planes_out,
+                                planes_in ? planes_chunk_cols((int)p.x_esz) : 0, 0};
         std::copy(std::begin(rec), std::end(rec), ix->last_planes);
     }
     HIP_TRY(hipEventRecord(sl.ev_done, ix->st_run));
@@ -2841,6 +2974,8 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     pd.planes = planes != nullptr;
     pd.out_stride = out_stride;
     pd.domain_out = p.domain ? domain_out : nullptr;
+    pd.replay_push_no = p.replay_push_no;
+    if (p.replay.on) ix->last_replay[5] = ix->search_calls - searches0;  // (searches this tile's submission ran: none)
     p.d2h_slot = b;  // its device-to-host copies are enqueued behind the next tile's rows, or by the flush
     p.o.row_offset += nv;
     p.ms_enqueue += now_ms() - t_enq;
@@ -2852,8 +2987,11 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
         const size_t bytes = (size_t)n_next * d_x * p.x_esz, esz = p.x_esz;
         int32_t* dst_z = p.zonal ? ix->slot[b2].pin_z : nullptr;  // (the next tile's zone codes travel with its rows)
         const int32_t* zones_next = p.zonal ? zones + n : nullptr;
+        const ReplaySpec rspec = p.replay;
+        const ReplaySrc rsrc = p.replay_src;
         p.ahead_done = ix->w_in->post([=]() -> int {
-            if (planes) stage_planes(dst, planes, d_x, esz, p_off + n, n_next);
+            if (rspec.on) stage_replay(dst, rspec, rsrc, p_off + n, n_next);
+            else if (planes) stage_planes(dst, planes, d_x, esz, p_off + n, n_next);
             else parallel_copy(dst, q_next, bytes);
             if (dst_z) parallel_copy(dst_z, zones_next, (size_t)n_next * sizeof(int32_t));
             return SKNNR_OK;
@@ -2871,9 +3009,10 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
 // to out[l] + j * out_stride + c0 (in elements of lane l) for output plane j.
 int pipe_submit_rows(HostPipe& p, const void* q_, long nq, void* const out[kLanes], const void* const* planes = nullptr,
                      long out_stride = 0) {
-    const char* q = planes ? (const char*)planes[0] : (const char*)q_;
-    // (bytes between the tiles of q: a band-first tile is named by the first band's segment)
-    const size_t row_bytes = planes ? p.x_esz : (size_t)p.d_x * p.x_esz;
+    const char* q = p.replay.on ? p.replay_src.idx : planes ? (const char*)planes[0] : (const char*)q_;
+    // (bytes between the tiles of q: a band-first tile is named by the first band's segment, a replayed one by its indices)
+    const size_t row_bytes = p.replay.on ? (size_t)(planes ? 1 : p.replay.ks) * p.replay.idx_bytes
+                                         : planes ? p.x_esz : (size_t)p.d_x * p.x_esz;
     const long cap = host_chunk_rows();
     bool idle = p.d2h_slot < 0;
     for (const auto& pd : p.pending) idle = idle && !pd.live;
@@ -3043,6 +3182,7 @@ int run_self_rows(sknnr_index* ix, long nq, const sknnr_query_opts* o, double* o
 extern "C" int sknnr_forest_apply(sknnr_index* ix, const void* q, int64_t nq, int32_t query_dtype, int32_t mem,
                                   double* out_ids) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (ix->targets_only) return refuse_targets_only("sknnr_forest_apply");
     if (!ix->has_forest) return fail(SKNNR_ERR_INVALID, "sknnr_forest_apply needs sknnr_index_set_forest first");
     if (query_dtype < 0 || query_dtype >= kDtypeCount) return fail(SKNNR_ERR_INVALID, "unknown query_dtype %d", query_dtype);
     if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
@@ -3099,6 +3239,7 @@ extern "C" int sknnr_kneighbors(sknnr_index* ix, const void* q, int64_t nq, cons
 // ----------------------------------------------------------------------------------------
 extern "C" int sknnr_index_set_groups(sknnr_index* ix, const int32_t* codes, int64_t n) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (ix->targets_only) return refuse_targets_only("sknnr_index_set_groups");
     if (!codes) {  // clear
         std::lock_guard<std::mutex> lock(ix->mtx);
         ix->has_groups = false;
@@ -3132,6 +3273,7 @@ extern "C" int sknnr_index_set_groups(sknnr_index* ix, const int32_t* codes, int
 
 extern "C" int sknnr_index_set_buffer(sknnr_index* ix, const double* coords, int64_t n, int32_t c, double radius) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (ix->targets_only) return refuse_targets_only("sknnr_index_set_buffer");
     if (!coords) {  // clear
         std::lock_guard<std::mutex> lock(ix->mtx);
         ix->has_buffer = false;
@@ -3250,6 +3392,7 @@ int run_grouped_device(sknnr_index* ix, long nq, const sknnr_query_opts* o, doub
 extern "C" int sknnr_kneighbors_grouped(sknnr_index* ix, int64_t nq, const sknnr_query_opts* o, double* out_dist,
                                         int64_t* out_idx, int32_t mem, void* stream) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (ix->targets_only) return refuse_targets_only("sknnr_kneighbors_grouped");
     if (!o) return fail(SKNNR_ERR_INVALID, "opts is NULL");
     if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
     if (!out_idx && nq > 0) return fail(SKNNR_ERR_INVALID, "out_idx is NULL");
@@ -3309,6 +3452,7 @@ extern "C" int sknnr_kneighbors_grouped(sknnr_index* ix, int64_t nq, const sknnr
 
 extern "C" int sknnr_buffer_counts(sknnr_index* ix, int64_t* out, int32_t mem, void* stream) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (ix->targets_only) return refuse_targets_only("sknnr_buffer_counts");
     if (!out) return fail(SKNNR_ERR_INVALID, "out is NULL");
     if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
     std::lock_guard<std::mutex> lock(ix->mtx);
@@ -3508,6 +3652,7 @@ extern "C" int sknnr_kneighbors_masked(sknnr_index* ix, const void* q, int64_t n
 extern "C" int sknnr_hamming_distances(sknnr_index* ix, const double* q, int64_t nq, const int64_t* rows, int64_t n_rows,
                                        double* out, int32_t mem, void* stream) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    if (ix->targets_only) return refuse_targets_only("sknnr_hamming_distances");
     if (!ix->has_hw) return fail(SKNNR_ERR_INVALID, "sknnr_hamming_distances needs sknnr_index_set_hamming_weights first");
     if (n_rows < 0 || nq < 0) return fail(SKNNR_ERR_INVALID, "negative row count");
     if (n_rows == 0) return SKNNR_OK;
@@ -4177,6 +4322,8 @@ extern "C" int sknnr_stream_set_nodata(sknnr_stream* s, const double* nodata, in
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     if (!nodata) return fail(SKNNR_ERR_INVALID, "nodata is NULL");
     HostPipe& p = s->pipe;
+    if (p.replay.on)
+        return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_nodata: a replay stream has no feature rows to mask; its mask is the fill index of sknnr_replay_begin");
     std::lock_guard<std::mutex> lock(p.ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_nodata is allowed only before the first push");
     if (p.d_x > kMaskMaxCols) return fail(SKNNR_ERR_UNSUPPORTED, "more than %d input columns with a nodata mask", kMaskMaxCols);
@@ -4396,6 +4543,8 @@ extern "C" int sknnr_stream_set_tally(sknnr_stream* s) {
     sknnr_index* ix = p.ix;
     const int rc = tally_check_shape(ix, p.k);
     if (rc) return rc;
+    if (p.replay.on && p.replay.dist_kind == kReplayDistNone)
+        return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_tally: the replay stream was opened without stored distances, and the tally keeps their maxima");
     std::lock_guard<std::mutex> lock(ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_tally is allowed only before the first push");
     HIP_TRY(hipSetDevice(ix->device));
@@ -4796,6 +4945,8 @@ extern "C" int sknnr_stream_set_domain(sknnr_stream* s, const double* table, int
     if (rc) return rc;
     if (mask_beyond && !has_threshold) return fail(SKNNR_ERR_INVALID, "mask_beyond needs a threshold");
     if (mask_beyond && !p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "mask_beyond: the stream was opened without predictions");
+    if (p.replay.on && p.replay.dist_kind == kReplayDistNone)
+        return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_domain: the replay stream was opened without stored distances");
     std::lock_guard<std::mutex> lock(ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_domain is allowed only before the first push");
     HIP_TRY(hipSetDevice(ix->device));
@@ -4921,13 +5072,19 @@ static const char* const kTypedStreamMsg =
 // The body of every push: nq rows at q, or (planes non-null) nq pixels of every band; outs[l] is where lane l's results go
 // (null: not asked for), in elements of the stream's type for that lane, band-first with out_stride elements between planes.
 // The entry points check what is theirs alone and leave s and nq to this function.
+// rsrc (the replay entries; else null): the stored neighbours of the push, which a replay stream takes in place of rows.
 static int stream_push(sknnr_stream* s, const void* q, const void* const* planes, int64_t nq, void* const outs[kLanes],
-                       int64_t out_stride) {
+                       int64_t out_stride, const ReplaySrc* rsrc = nullptr) {
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
-    if (nq == 0) return SKNNR_OK;
     HostPipe& p = s->pipe;
-    if (!outs[kLaneIdx] && !outs[kLanePred]) return fail(SKNNR_ERR_INVALID, "a push needs out_idx or out_pred");
+    if (p.replay.on != (rsrc != nullptr))
+        return fail(SKNNR_ERR_INVALID, rsrc ? "sknnr_replay_push: the stream was opened by sknnr_stream_begin and takes feature rows"
+                                            : "a replay stream takes stored neighbours: use sknnr_replay_push / sknnr_replay_push_planes");
+    if (rsrc) ++p.replay_push_no;  // (every push counts, an empty one too: the caller's tile numbers)
+    if (nq == 0) return SKNNR_OK;
+    // (a replayed push may ask for nothing: its tile still feeds the tally, the zonal tables and the domain)
+    if (!rsrc && !outs[kLaneIdx] && !outs[kLanePred]) return fail(SKNNR_ERR_INVALID, "a push needs out_idx or out_pred");
     if (outs[kLaneDist] && !p.lane[kLaneDist].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without distances");
     if (outs[kLanePred] && !p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
     std::lock_guard<std::mutex> lock(p.ix->mtx);
@@ -4951,6 +5108,7 @@ static int stream_push(sknnr_stream* s, const void* q, const void* const* planes
     }
     HIP_TRY(hipSetDevice(p.ix->device));
     s->pushed = true;
+    if (rsrc) p.replay_src = *rsrc;
     const int rc = pipe_submit_rows(p, q, nq, outs, planes, out_stride);
     if (rc) return pipe_fail(p, rc);
     s->rows_pushed += nq;
@@ -5008,6 +5166,176 @@ extern "C" int sknnr_stream_end(sknnr_stream* s, int64_t* rows_pushed) {
     if (rows_pushed) *rows_pushed = s->rows_pushed;
     delete s;
     return rc;
+}
+
+// ----------------------------------------------------------------------------------------
+// neighbour replay (replay.hip.h): streams whose tiles are stored neighbours
+// ----------------------------------------------------------------------------------------
+extern "C" int sknnr_index_create_targets(const double* y, int64_t n_ref, int32_t t, int32_t device, sknnr_index** out) {
+    if (!out) return fail(SKNNR_ERR_INVALID, "sknnr_index_create_targets: out is NULL");
+    *out = nullptr;
+    if (!y || n_ref < 1 || t < 1) return fail(SKNNR_ERR_INVALID, "sknnr_index_create_targets: y must be a non-empty (n_ref, t) matrix");
+    if (n_ref > 0x7fffff00L) return fail(SKNNR_ERR_UNSUPPORTED, "sknnr_index_create_targets: n_ref = %ld exceeds 2^31 - 256", (long)n_ref);
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) return fail(SKNNR_ERR_NO_DEVICE, "no HIP device is visible");
+    if (device < 0 || device >= n_dev) return fail(SKNNR_ERR_INVALID, "device %d out of range [0, %d)", device, n_dev);
+    HIP_TRY(hipSetDevice(device));
+    sknnr_index* ix = new (std::nothrow) sknnr_index();
+    if (!ix) return fail(SKNNR_ERR_INVALID, "out of host memory");
+    struct Guard {
+        sknnr_index* p;
+        ~Guard() { delete p; }
+    } guard{ix};
+    ix->device = device;
+    ix->n_ref = n_ref;
+    ix->t = t;
+    ix->targets_only = true;
+    HIP_TRY(ix->y64.ensure((size_t)n_ref * t));
+    HIP_TRY(hipMemcpy(ix->y64.p, y, (size_t)n_ref * t * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipEventCreateWithFlags(&ix->ev_ws, hipEventDisableTiming));
+    guard.p = nullptr;
+    *out = ix;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_index_set_replay_ids(sknnr_index* ix, const int64_t* ids, int64_t n) {
+    // (the table itself is checked first, before the handle is even looked at)
+    if (ids && (n < 1 || n > 0x7fffff00L)) return fail(SKNNR_ERR_INVALID, "sknnr_index_set_replay_ids: n = %lld outside [1, 2^31 - 256]", (long long)n);
+    std::vector<std::pair<long, int>> tab;
+    if (ids) {
+        tab.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) tab[(size_t)i] = {(long)ids[i], (int)i};
+        std::sort(tab.begin(), tab.end());
+        for (size_t i = 1; i < tab.size(); ++i)
+            if (tab[i].first == tab[i - 1].first)
+                return fail(SKNNR_ERR_INVALID, "sknnr_index_set_replay_ids: id %lld names rows %d and %d: the ids must be unique",
+                            (long long)tab[i].first, tab[i - 1].second, tab[i].second);
+    }
+    if (!ix) return fail(SKNNR_ERR_INVALID, "sknnr_index_set_replay_ids: index is NULL");
+    if (ids && n != ix->n_ref)
+        return fail(SKNNR_ERR_INVALID, "sknnr_index_set_replay_ids: n = %lld, the handle has %lld reference rows", (long long)n, (long long)ix->n_ref);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (ix->stream_open) return fail(SKNNR_ERR_INVALID, "sknnr_index_set_replay_ids: a stream is open on this handle: end it first");
+    ix->r_id_n = 0;
+    if (!ids) return SKNNR_OK;
+    std::vector<long> sorted(tab.size());
+    std::vector<int> perm(tab.size());
+    for (size_t i = 0; i < tab.size(); ++i) {
+        sorted[i] = tab[i].first;
+        perm[i] = tab[i].second;
+    }
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(ix->r_id_sorted.ensure(sorted.size()));
+    HIP_TRY(ix->r_id_perm.ensure(perm.size()));
+    HIP_TRY(hipMemcpy(ix->r_id_sorted.p, sorted.data(), sorted.size() * sizeof(long), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ix->r_id_perm.p, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice));
+    ix->r_id_n = (long)n;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_replay_begin(sknnr_index* ix, int32_t k, int32_t ks, int32_t weight_mode, int32_t weight_law,
+                                  int32_t idx_dtype, int32_t dist_dtype, int64_t fill_index, int32_t ids, int32_t want_dist,
+                                  int32_t want_pred, sknnr_stream** out) {
+    if (!out) return fail(SKNNR_ERR_INVALID, "sknnr_replay_begin: out is NULL");
+    *out = nullptr;
+    if (!ix) return fail(SKNNR_ERR_INVALID, "sknnr_replay_begin: index is NULL");
+    if (ks < 1 || k < 1 || k > ks) return fail(SKNNR_ERR_INVALID, "sknnr_replay_begin: k = %d outside [1, ks = %d]", k, ks);
+    if (idx_dtype != SKNNR_DTYPE_F64 && idx_dtype != SKNNR_DTYPE_I32)
+        return fail(SKNNR_ERR_INVALID, "sknnr_replay_begin: idx_dtype = %d: stored indices are int64 (0) or int32 (SKNNR_DTYPE_I32)", idx_dtype);
+    if (dist_dtype != SKNNR_REPLAY_NO_DIST && dist_dtype != SKNNR_DTYPE_F64 && dist_dtype != SKNNR_DTYPE_F32)
+        return fail(SKNNR_ERR_INVALID, "sknnr_replay_begin: dist_dtype = %d: stored distances are float64 (0), float32 (SKNNR_DTYPE_F32) or absent (SKNNR_REPLAY_NO_DIST)", dist_dtype);
+    const bool has_dist = dist_dtype != SKNNR_REPLAY_NO_DIST;
+    if (want_dist && !has_dist) return fail(SKNNR_ERR_INVALID, "sknnr_replay_begin: want_dist without stored distances");
+    if (ids && ix->r_id_n == 0)
+        return fail(SKNNR_ERR_INVALID, "sknnr_replay_begin: ids = 1 needs the id table (sknnr_index_set_replay_ids) first");
+    sknnr_query_opts o{};
+    o.n_neighbors = k;
+    o.weight_mode = weight_mode;
+    o.weight_law = weight_law;
+    if (want_pred) {
+        if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "sknnr_replay_begin: the index was created without targets");
+        if (k > kScanMaxKK) return fail(SKNNR_ERR_UNSUPPORTED, "sknnr_replay_begin: k = %d exceeds the HIP backend's limit of %d", k, kScanMaxKK);
+        const int law = weight_law_check(ix, &o);
+        if (law < 0) return law;
+        if (!law && !weight_mode_ok(weight_mode, false))
+            return fail(SKNNR_ERR_INVALID, "sknnr_replay_begin: a stream predicts with uniform or distance weights, or a weight law, only");
+        if (!has_dist && (law || (weight_mode & SKNNR_WEIGHTS_BASE_MASK) == SKNNR_WEIGHTS_DISTANCE))
+            return fail(SKNNR_ERR_INVALID, "sknnr_replay_begin: distance weights and weight laws need the stored distances");
+    }
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (ix->stream_open) return fail(SKNNR_ERR_INVALID, "sknnr_replay_begin: a query stream is already open on this handle");
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(ix->replay_rec.ensure((size_t)kHostSlots * kReplayRecWords));
+    if (!ix->pin_replay)
+        HIP_TRY(hipHostMalloc((void**)&ix->pin_replay, (size_t)kHostSlots * kReplayRecWords * sizeof(unsigned long long), hipHostMallocDefault));
+    sknnr_stream* s = new (std::nothrow) sknnr_stream();
+    if (!s) return fail(SKNNR_ERR_INVALID, "out of host memory");
+    const int rc = pipe_open(s->pipe, ix, &o, want_dist != 0, want_pred != 0);
+    if (rc) {
+        delete s;
+        return rc;
+    }
+    HostPipe& p = s->pipe;
+    p.replay.on = true;
+    p.replay.ks = ks;
+    p.replay.idx_bytes = idx_dtype == SKNNR_DTYPE_I32 ? 4 : 8;
+    p.replay.dist_kind = !has_dist ? kReplayDistNone : (dist_dtype == SKNNR_DTYPE_F32 ? kReplayDistF32 : kReplayDistF64);
+    p.replay.ids = ids != 0;
+    p.replay.fill_index = (long)fill_index;
+    p.lane[kLaneDist].search_out = has_dist;  // (the decode writes the distance tile only when distances are stored)
+    std::fill(std::begin(ix->last_replay), std::end(ix->last_replay), 0);
+    ix->stream_open = true;
+    *out = s;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_replay_push(sknnr_stream* s, const void* idx, const void* dist, int64_t nq, void* out_dist, void* out_idx,
+                                 void* out_pred) {
+    if (s && s->pipe.replay.on && nq > 0) {
+        if (!idx) return fail(SKNNR_ERR_INVALID, "sknnr_replay_push: idx is NULL");
+        if (!dist != (s->pipe.replay.dist_kind == kReplayDistNone))
+            return fail(SKNNR_ERR_INVALID, "sknnr_replay_push: dist is given exactly when the stream was opened with stored distances");
+    }
+    const ReplaySrc src{(const char*)idx, (const char*)dist, false, 0};
+    void* const outs[kLanes] = {out_idx, out_dist, out_pred};  // (lane order)
+    return stream_push(s, idx, nullptr, nq, outs, 0, &src);
+}
+
+extern "C" int sknnr_replay_push_planes(sknnr_stream* s, const void* idx, const void* dist, int64_t nq, int64_t in_stride,
+                                        void* out_dist, void* out_idx, void* out_pred, int64_t out_stride) {
+    if (s && s->pipe.replay.on && nq > 0) {
+        if (!idx) return fail(SKNNR_ERR_INVALID, "sknnr_replay_push_planes: idx is NULL");
+        if (!dist != (s->pipe.replay.dist_kind == kReplayDistNone))
+            return fail(SKNNR_ERR_INVALID, "sknnr_replay_push_planes: dist is given exactly when the stream was opened with stored distances");
+        if (in_stride < nq) return fail(SKNNR_ERR_INVALID, "sknnr_replay_push_planes: in_stride (%lld) is below nq (%lld)", (long long)in_stride, (long long)nq);
+        if (out_stride < nq) return fail(SKNNR_ERR_INVALID, "sknnr_replay_push_planes: out_stride (%lld) is below nq (%lld)", (long long)out_stride, (long long)nq);
+    }
+    const ReplaySrc src{(const char*)idx, (const char*)dist, true, (long)in_stride};
+    static const void* const kBandTag[1] = {nullptr};  // (non-null: the results leave as planes; a replayed tile has no row planes)
+    void* const outs[kLanes] = {out_idx, out_dist, out_pred};  // (lane order)
+    return stream_push(s, idx, kBandTag, nq, outs, out_stride, &src);
+}
+
+extern "C" int sknnr_replay_get_counts(sknnr_stream* s, int64_t out[4]) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "sknnr_replay_get_counts: stream is NULL");
+    if (!out) return fail(SKNNR_ERR_INVALID, "sknnr_replay_get_counts: out is NULL");
+    HostPipe& p = s->pipe;
+    if (!p.replay.on) return fail(SKNNR_ERR_INVALID, "sknnr_replay_get_counts: the stream was opened by sknnr_stream_begin");
+    std::lock_guard<std::mutex> lock(p.ix->mtx);
+    HIP_TRY(hipSetDevice(p.ix->device));
+    const int rc = pipe_flush(p);
+    if (rc) return pipe_fail(p, rc);
+    std::copy(p.replay_tot, p.replay_tot + 3, out);
+    out[3] = p.replay_first;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_replay(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "sknnr_debug_last_replay: NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::copy(ix->last_replay, ix->last_replay + 8, out);
+    return SKNNR_OK;
 }
 
 // ----------------------------------------------------------------------------------------
