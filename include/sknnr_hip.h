@@ -1075,6 +1075,92 @@ int sknnr_debug_expand_rows(int64_t nq, int32_t k, int32_t t, const uint8_t* val
 int sknnr_crosswalk(const int64_t* table, int64_t n_table, const int64_t* idx, int64_t n,
                     int64_t* out, int32_t device, int32_t mem, void* stream);
 
+/* ---- Bootstrap (standard errors per pixel from one search) -------------------------------------------- */
+
+/*
+ * How uncertain is a pixel's value because the plots are a sample?  The bootstrap over plots answers it: replicate b
+ * contains reference row r M[b, r] = 0, 1, 2 ... times.  The k nearest rows of a pixel inside replicate b are found by
+ * walking the pixel's ordinary neighbour list, nearest first, and taking M[b, r_j] copies of each neighbour until k copies
+ * are taken -- so ONE search at a wider kw > k serves all B replicates, and the reduction per pixel runs on the device
+ * (sknnr_amd/csrc/bootstrap.hip.h; tests/_bootstrap.py restates every line below in numpy).  The transform of a
+ * transformed estimator is NOT refitted per replicate.  No product is fused into an addition anywhere: every product is
+ * rounded, then added.
+ *
+ * Inputs per pixel: its kw neighbours (d_j, r_j), j = 0 .. kw - 1, in the order sknnr_kneighbors returns them; the handle's
+ * table M, uint8 (B, n_ref) (sknnr_index_set_bootstrap); the replicate size k <= kw <= 192; a plan of n_out entries
+ * (cols[e], stat[e]), stat a sknnr_bootstrap_statistic.
+ *
+ * Copies.  For replicate b: left = k; for j ascending c_j = min(M[b, r_j], left), left -= c_j; stop at left == 0.  The
+ *   replicate is SHORT for this pixel when left > 0 behind column kw - 1.
+ * Weights.  Those sknnr_predict uses, evaluated on d_j; only the taken columns (c_j > 0) count.
+ *   UNIFORM  : 1
+ *   DISTANCE : 1 / d_j.  If a TAKEN column has d_j == 0 the weights become the 0 / 1 mask of d == 0 over the taken columns;
+ *              a zero-distance neighbour that is absent from the replicate does not trigger the mask.
+ *   a law    : w(d_j) of sknnr_weight_law, bit for bit (weight_mode SKNNR_WEIGHTS_EXPLICIT names it, as in sknnr_predict)
+ * Replicate value of target column col: den = sum_j cw_j, num = sum_j cw_j * y[r_j, col], cw_j = (double)c_j * w_j; both
+ *   sums sequential, j ascending over the taken columns, from +0.0; p_b = num / den.  A replicate is INVALID when it is
+ *   short or when den is not > 0 (a compact law).
+ * Point value.  p0 is the same formula with c_j = 1 for j < k and 0 behind.  If its den is not > 0 every plane of the pixel
+ *   is NaN and its count is 0.
+ * Across replicates, per pixel and entry: a_b = p_b - p0 for a valid replicate, +0.0 for an invalid one; m = the valid
+ *   replicates.  64 partial sums: partial l adds a_b (for S2: a_b * a_b) over b = l, l + 64, l + 128 ... ascending, from
+ *   +0.0; they are folded by P[l] = P[l] + P[l + s] for l < s, s = 32, 16, 8, 4, 2, 1; the result is P[0].
+ * Outputs:
+ *   SKNNR_BOOT_BIAS  : S1 / m                          NaN when m == 0
+ *   SKNNR_BOOT_MEAN  : p0 + S1 / m                     NaN when m == 0
+ *   SKNNR_BOOT_SE    : sqrt(max((S2 - S1 * (S1 / m)) / (m - 1), 0.0))      NaN when m < 2
+ *   SKNNR_BOOT_COUNT : (double)m; cols[e] is not read
+ * Tallies, integer adds: tally[0] the pixels reduced, tally[1] the sum of m over them.
+ * A pixel whose list names a row outside [0, n_ref) (the -1 of a blanked pixel) is all NaN with count 0 and enters
+ * neither tally.
+ * Multiplicities above 255 may be clamped to 255 by the caller without changing any result, since k <= 192.
+ */
+enum sknnr_bootstrap_statistic { SKNNR_BOOT_SE = 0, SKNNR_BOOT_MEAN = 1, SKNNR_BOOT_BIAS = 2, SKNNR_BOOT_COUNT = 3 };
+
+/*
+ * Installs (or with table == NULL removes) the multiplicity table: HOST memory, uint8 (B, n) row-major, n == n_ref,
+ * 1 <= B <= 4096.  The handle keeps a transposed copy on the device.  Refused while a stream is open.  Handles of
+ * sknnr_index_create_targets accept it.
+ */
+int sknnr_index_set_bootstrap(sknnr_index* index, const uint8_t* table, int32_t B, int64_t n);
+
+/*
+ * The reduction alone, from (dist, idx) of kw columns.
+ *   dist, idx  : (nq, kw) float64 / int64 in `mem`; dist may be NULL for UNIFORM weights
+ *   weight_mode, weight_law : as opts->weight_mode / opts->weight_law of sknnr_predict; explicit weights without a law
+ *                and the F32 flags are refused
+ *   cols, stat : HOST arrays of n_out, whatever `mem` is
+ *   out        : (nq, n_out) float64 in `mem`
+ *   tally      : (2) int64 in `mem`, set by the call; may be NULL
+ * SKNNR_ERR_INVALID before any device work: no table installed, k outside [1, kw], kw above 192 or above n_ref, n_out
+ * outside [1, 1024], a column outside [0, t), an unknown code, NULL arrays.
+ * SKNNR_MEM_HOST returns when out is written; SKNNR_MEM_DEVICE enqueues on `stream`.
+ */
+int sknnr_bootstrap_from_neighbors(sknnr_index* index, const double* dist, const int64_t* idx, int64_t nq, int32_t kw,
+                                   int32_t k, int32_t weight_mode, int32_t weight_law, const int32_t* cols,
+                                   const int32_t* stat, int32_t n_out, double* out, int64_t* tally, int32_t mem,
+                                   void* stream);
+
+/*
+ * A stream whose reduction stage is the bootstrap: valid on search streams opened at opts->n_neighbors = kw and on replay
+ * streams (k of sknnr_replay_begin = kw), both opened with predictions; `k` here is the replicate size.  The prediction
+ * lane becomes n_out wide; everything behind the reduction runs unchanged (blanking, typed conversion, band transposes,
+ * copies).  Only before the first push and before sknnr_stream_set_output.  Refused together with
+ * sknnr_stream_set_statistics, _set_plan, _set_tally, _set_domain and _set_zonal, whichever comes second; the caps of
+ * sknnr_bootstrap_from_neighbors apply.  The F32_TARGETS flag of the stream's weight mode is ignored: the bootstrap
+ * reduces in float64.  Masked pixels (nodata, replay fill, replay unknown) enter neither tally.
+ * sknnr_stream_get_bootstrap flushes the stream and returns the two tallies over all tiles pushed so far (host memory).
+ */
+int sknnr_stream_set_bootstrap(sknnr_stream* stream, int32_t k, const int32_t* cols, const int32_t* stat, int32_t n_out);
+int sknnr_stream_get_bootstrap(sknnr_stream* stream, int64_t tally[2]);
+
+/*
+ * Debug only.  The last bootstrap reduction the handle launched.  Host memory, no device work:
+ *   out[0] rows      out[1] B      out[2] k      out[3] kw      out[4] n_out
+ *   out[5] pixels per wave (1, 2 or 4)      out[6] kernel launches      out[7] 0
+ */
+int sknnr_debug_last_bootstrap(const sknnr_index* index, int64_t out[8]);
+
 /* ---- diagnostics (used by the parity tests to validate the MFMA operand maps) ----------- */
 
 /*

@@ -20,6 +20,7 @@ from ._forest_nn import GBNNRegressor, RFNNRegressor
 from ._usage import NeighborUsage  # noqa: F401  (the backend's own, like the settings above: an attribute, not an export)
 from ._zonal import ZonalStats  # noqa: F401  (likewise)
 from ._domain import DistanceDomain  # noqa: F401  (likewise)
+from ._bootstrap import Bootstrap  # noqa: F401  (likewise)
 from . import weights  # noqa: F401  (the distance-weight laws: a submodule, not an export -- __all__ stays the reference's)
 
 __version__ = "0.2.0"

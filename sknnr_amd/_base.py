@@ -30,6 +30,7 @@ from ._engine import KNNEngine, default_device, is_torch_cuda_tensor
 from ._usage import NeighborUsage
 from ._domain import DistanceDomain
 from ._zonal import ZonalStats
+from ._bootstrap import MAX_CANDIDATES, Bootstrap, has_boot_names, normalize_boot_outputs
 from .weights import DistanceWeights
 
 # Element types query rows may keep on their way to the device (include/sknnr_hip.h, sknnr_dtype): the kernel that reads
@@ -248,6 +249,8 @@ def resolve_statistic(statistic, outputs, n_targets):
     in ``statistic`` the median is spelled ``("quantile", 0.5)``), an :class:`OutputPlan` for ``outputs`` or for a
     ``statistic`` that holds ``("quantile", q)`` entries (the plan ``[(0, s0), ..., (t-1, s_(t-1))]``), or None when
     neither is given."""
+    if has_boot_names(statistic, outputs):
+        raise ValueError("the 'boot_*' outputs need bootstrap=: pass a sknnr_amd.Bootstrap")
     if outputs is not None:
         if statistic is not None:
             raise ValueError("outputs and statistic cannot be given together: outputs names the statistic of every plane")
@@ -904,7 +907,44 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             return out
         return out.reshape(-1) if self._y.ndim == 1 else out
 
-    def summarize(self, X=None, statistic=None, outputs=None):
+    def _bootstrap_request(self, bootstrap, statistic, outputs, *, self_query=False, n_targets=None, stored=False, **others):
+        """``(kw, plan, table)`` of a ``bootstrap=`` call, every refusal before any device work: ``others`` are the call's
+        keywords that do not go with a bootstrap (name -> value, refused when set); ``n_targets``: the columns of a replay's
+        own ``y``; ``stored``: the candidates are stored columns, so ``kw`` is settled by the first tile (None here)."""
+        if not isinstance(bootstrap, Bootstrap):
+            raise TypeError(f"bootstrap must be a sknnr_amd.Bootstrap, got {type(bootstrap).__name__}")
+        if callable(self.weights) and not isinstance(self.weights, DistanceWeights):
+            self._refuse_callable_weights("bootstrap is", "and a bootstrap weighs the copies each replicate takes on the device")
+        self._check_stream_supported("bootstrap is")
+        if statistic is not None:
+            raise ValueError("statistic is not available with bootstrap=: name the planes in outputs, as (target, 'boot_se' | "
+                             "'boot_mean' | 'boot_bias') pairs or 'boot_count'")
+        for name, value in others.items():
+            if name == "zonal" and value is not None:
+                raise ValueError("zonal is not available with bootstrap=: a zonal sum of pixel standard errors is not the "
+                                 "standard error of the zonal mean")
+            if value is not None and value is not False:
+                raise ValueError(f"{name} is not available with bootstrap=: the stream's reduction stage holds the bootstrap")
+        plan = normalize_boot_outputs(outputs, self._n_targets() if n_targets is None else n_targets)
+        n = self.n_samples_fit_
+        table = bootstrap._bind(n)
+        kw = None if stored else bootstrap.candidates(self.n_neighbors, n - (1 if self_query else 0))
+        return kw, plan, table
+
+    def _bootstrap_engine(self, X, bootstrap, request, *, apply_affine, owner=None):
+        """One search at ``kw`` columns, then the bootstrap reduction on the device: float64 ``(n, n_out)``."""
+        kw, plan, table = request
+        dist, idx = self._kneighbors_engine(X, kw, apply_affine=apply_affine, use_deterministic_ordering=True, owner=owner)
+        weights = "uniform" if self.weights is None else self.weights
+        try:
+            self.engine_.set_bootstrap(table)
+            out, tally = self.engine_.bootstrap_from_neighbors(dist, idx, self.n_neighbors, weights, plan)
+        except _native.HipBackendError as err:
+            _reraise(err, owner if owner is not None else self)
+        bootstrap._add(tally)
+        return out
+
+    def summarize(self, X=None, statistic=None, outputs=None, bootstrap=None):
         """A summary of each query's neighbours per target, reduced on the device from the neighbours ``kneighbors``
         finds (deterministic ordering on, as ``predict``); ``X=None`` summarises every fitted row's neighbours, itself
         excluded.  ``statistic``: one name, or one name per target -- ``"mean"`` (what ``predict`` gives, bit for bit), ``"mode"``
@@ -926,8 +966,18 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         ``outputs`` (instead of ``statistic``): a sequence of ``(target, statistic)`` pairs -- ``target`` an integer
         column position that may repeat, ``statistic`` any of the above or ``"median"`` -- all reduced from ONE search, e.g.
         ``[(0, "mean"), (0, "std"), (0, ("quantile", .1)), (0, ("quantile", .9))]``.  Returns float64 ``(n, n_out)``,
-        always 2-D; a plane with one of the six names equals that column of ``summarize(X, statistic=name)`` bit for bit."""
+        always 2-D; a plane with one of the six names equals that column of ``summarize(X, statistic=name)`` bit for bit.
+
+        ``bootstrap`` (a :class:`sknnr_amd.Bootstrap`): the planes are bootstrap statistics over the fitted rows instead --
+        ``outputs`` takes ``(target, "boot_se" | "boot_mean" | "boot_bias")`` pairs and ``"boot_count"``, by default
+        ``boot_se`` of every target.  ONE search runs at ``bootstrap.n_candidates`` columns; every replicate's k nearest
+        copies are taken from that list on the device (include/sknnr_hip.h, "Bootstrap").  Returns float64 ``(n, n_out)``."""
         check_is_fitted(self, "_fit_X")
+        if bootstrap is not None:
+            request = self._bootstrap_request(bootstrap, statistic, outputs, self_query=X is None)
+            if X is not None:
+                X = self._validate_query(X)
+            return self._bootstrap_engine(X, bootstrap, request, apply_affine=False)
         if statistic is None and outputs is None:
             statistic = "mean"
         stat = resolve_statistic(statistic, outputs, self._n_targets())
@@ -1150,7 +1200,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
     def _stream_tiles(self, tiles, validate, k, *, apply_affine, weights, return_distance,
                       use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False, output=None,
                       statistic=None, id_table=None, fill_id=-1, neighbors=False, usage=None, zones=None, zonal=None,
-                      domain=None, domain_out=None, beyond=False):
+                      domain=None, domain_out=None, beyond=False, bootstrap=None):
         """Push host tiles through one native query stream.  Returns (dist, idx, pred) arrays over all
         pushed rows (pieces of ``out`` when given, else concatenated).  ``nodata`` (float64, one value per column of the
         validated tiles): rows holding one are masked on the device and get ``fill_index`` / NaN.
@@ -1182,7 +1232,11 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         ``domain`` (a :class:`sknnr_amd.DistanceDomain`, checked by :meth:`_check_domain`): the stream codes every tile's
         distances against its table on the device and the call adds the tallies to it; ``domain_out`` (uint8, one element
         per pixel of the whole call) receives the codes tile by tile; ``beyond`` (predictions only): the predictions of
-        the pixels beyond the threshold become NaN on the device, in front of the conversion and the zonal tally."""
+        the pixels beyond the threshold become NaN on the device, in front of the conversion and the zonal tally.
+
+        ``bootstrap``: ``(Bootstrap, request)`` with ``request`` from :meth:`_bootstrap_request` -- ``k`` is then the number
+        of candidates searched, the stream's reduction stage is the bootstrap with replicates of ``n_neighbors`` copies, the
+        prediction lane holds the request's planes, and the call adds the stream's tallies to the ``Bootstrap``."""
         if usage is not None:
             self._check_stream_supported("usage is")
             usage._check(self.n_samples_fit_, k)  # (a mismatch is refused before any device work)
@@ -1201,6 +1255,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         want_pred = weights is not None
         plan = statistic if isinstance(statistic, OutputPlan) else None  # (the prediction lane then has n_out columns)
         t_cols = eng.t if plan is None else plan.n_out
+        if bootstrap is not None:
+            t_cols = len(bootstrap[1][1][0])
         output = {key: v for key, v in (output or {}).items() if v is not None}
         idx_dt = np.dtype(output.get("index_dtype", np.int64))
         dist_dt = np.dtype(output.get("distance_dtype", np.float64))
@@ -1274,6 +1330,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                     stream_dtype = first.dtype if code else np.dtype(np.float64)
                     if nodata is not None:  # (a NaN entry needs rows that can hold NaN)
                         nodata = normalize_nodata(nodata, n_cols, stream_dtype)
+                    if bootstrap is not None:
+                        eng.set_bootstrap(bootstrap[1][2])
                     stream = eng.open_stream(k, weights=weights, want_dist=return_distance,
                                              deterministic=use_deterministic_ordering,
                                              decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula(),
@@ -1285,7 +1343,9 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              **({} if zonal is None else
                                                 dict(zonal=(zonal.n_zones, zonal.n_classes(zonal_binding[0])))),
                                              **({} if domain is None else
-                                                dict(domain=(domain.table, domain.rank, domain.threshold, bool(beyond)))))
+                                                dict(domain=(domain.table, domain.rank, domain.threshold, bool(beyond)))),
+                                             **({} if bootstrap is None else
+                                                dict(bootstrap=(self.n_neighbors, bootstrap[1][1]))))
                 if first.dtype != stream_dtype:
                     if stream_dtype != np.float64:
                         raise ValueError(f"the tiles of one streamed call must share an element type: got {first.dtype} "
@@ -1323,7 +1383,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 row += n
             if zonal is not None and next(zones, None) is not None:
                 raise ValueError(_ZONES_LONG)
-            tallied = zoned = placed = None
+            tallied = zoned = placed = booted = None
             if stream is not None:
                 done, stream = stream, None
                 try:
@@ -1333,8 +1393,12 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                         zoned = done.zonal()
                     if domain is not None:
                         placed = done.domain()
+                    if bootstrap is not None:
+                        booted = done.bootstrap()
                 finally:
                     done.close()
+            if booted is not None:  # (only a call that came through whole is added)
+                bootstrap[0]._add(booted)
             if placed is not None:  # (only a call that came through whole is added)
                 domain._add(placed)
             if zonal is not None:  # (only a call that came through whole is added)
@@ -1520,7 +1584,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                        out_nodata=None, statistic=None, return_neighbors=False, return_distance=True,
                        return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
                        distance_dtype=None, outputs=None, usage=None, zones=None, zonal=None, domain=None, domain_out=None,
-                       beyond="keep"):
+                       beyond="keep", bootstrap=None):
         """``predict`` over an iterable of host tiles as one streamed call; ``out``: preallocated
         ``(n_rows, n_targets)`` float64 array (e.g. a memmap; float32 results are held exactly).  ``nodata`` as in
         :meth:`kneighbors_chunks`: masked rows are predicted NaN.  ``layout="bands"``: band-first tiles as in
@@ -1592,9 +1656,29 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         stored or enter ``zonal`` -- NaN, or ``out_nodata`` in a typed output, which an integer ``out_dtype`` then needs
         -- exactly as a nodata pixel's are; their neighbours, distances, ``usage`` and codes are untouched.  With
         ``beyond="keep"`` (the default) the call returns and writes exactly what it does without the keywords.  Refused
-        with callable weights and under the host-side tie policies."""
+        with callable weights and under the host-side tie policies.
+
+        ``bootstrap`` (a :class:`sknnr_amd.Bootstrap`): the planes are bootstrap statistics as :meth:`summarize` defines
+        them -- ``outputs`` takes ``(target, "boot_se" | "boot_mean" | "boot_bias")`` and ``"boot_count"``, by default
+        ``boot_se`` of every target; the stream searches ``bootstrap.n_candidates`` neighbours once and reduces every
+        replicate from them on the device.  The result is ``(N, n_out)`` (``(n_out, N)`` with ``layout="bands"``), always
+        2-D, and equals ``summarize(np.concatenate(tiles), outputs=outputs, bootstrap=...)`` bit for bit.  ``out``,
+        ``nodata``, ``layout`` and ``out_dtype`` / ``scale`` / ``offset`` / ``out_nodata`` apply unchanged, except that an
+        integer ``out_dtype`` always needs ``out_nodata``: the planes can be NaN.  ``statistic``, ``usage``, ``domain``,
+        ``return_neighbors`` and ``zonal`` are refused."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
+        if bootstrap is not None:
+            request = self._boot_chunks_request(bootstrap, statistic, outputs, return_neighbors, return_distance,
+                                                return_dataframe_index, neighbors_out, fill_index, index_dtype, distance_dtype,
+                                                usage, zones, zonal, domain, domain_out, beyond)
+            if nodata is not None:
+                nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
+            validate = self._validate_query
+            if bands:
+                validate = lambda t: normalize_band_tile(t, self.n_features_in_, estimator=type(self).__name__)  # noqa: E731
+            return self._bootstrap_chunks(tiles, validate, bootstrap, request, apply_affine=False, out=out, owner=None,
+                                          nodata=nodata, bands=bands, typed=(out_dtype, scale, offset, out_nodata))
         neighbors = self._neighbor_request(return_neighbors, return_distance, return_dataframe_index, neighbors_out,
                                            fill_index, index_dtype, distance_dtype)
         extra = {} if neighbors is None else dict(neighbors=neighbors)
@@ -1612,6 +1696,31 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             validate = lambda t: normalize_band_tile(t, self.n_features_in_, estimator=type(self).__name__)  # noqa: E731
         return self._predict_chunks(tiles, validate, apply_affine=False, out=out, owner=None, nodata=nodata, bands=bands,
                                     typed=(out_dtype, scale, offset, out_nodata), statistic=statistic, **extra)
+
+    def _boot_chunks_request(self, bootstrap, statistic, outputs, return_neighbors=False, return_distance=True,
+                             return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
+                             distance_dtype=None, usage=None, zones=None, zonal=None, domain=None, domain_out=None,
+                             beyond="keep", **kw):
+        """:meth:`_bootstrap_request` of a streamed call: its keywords that do not go with a bootstrap are refused."""
+        return self._bootstrap_request(
+            bootstrap, statistic, outputs, zonal=zonal, zones=zones, usage=usage, domain=domain, domain_out=domain_out,
+            beyond=None if beyond == "keep" else beyond, return_neighbors=bool(return_neighbors) or None,
+            return_dataframe_index=bool(return_dataframe_index) or None, neighbors_out=neighbors_out,
+            index_dtype=index_dtype, distance_dtype=distance_dtype, **kw)
+
+    def _bootstrap_chunks(self, tiles, validate, bootstrap, request, *, apply_affine, out, owner, nodata, bands, typed):
+        """``predict_chunks(bootstrap=...)``: one stream at ``kw`` candidates whose reduction stage is the bootstrap."""
+        kw, plan, _ = request
+        n_out = len(plan[0])
+        output = normalize_typed_output(*typed, n_out, True)  # (a plane can be NaN without any mask)
+        weights = "uniform" if self.weights is None else self.weights
+        if out is not None and out.ndim != 2:
+            raise ValueError(f"out must be 2-D, ({'n_out, N' if bands else 'N, n_out'}), with bootstrap=; got {out.ndim}-D")
+        o = None if out is None else (None, None, out)
+        _, _, pred = self._stream_tiles(tiles, validate, kw, apply_affine=apply_affine, weights=weights,
+                                        return_distance=False, use_deterministic_ordering=True, out=o, owner=owner,
+                                        nodata=nodata, bands=bands, output=output, bootstrap=(bootstrap, request))
+        return pred
 
     def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None, bands=False, typed=None,
                         statistic=None, neighbors=None, usage=None, zones=None, zonal=None, domain=None, domain_out=None,
@@ -1827,7 +1936,38 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         call (the contents of ``out`` are then unspecified), ``unknown="nodata"`` stores it as a masked pixel -- an
         integer ``out_dtype`` then needs ``out_nodata`` -- and the count is ``self.replay_unknown_`` either way.
         ``uniform`` weights need no distances; ``distance`` weights, the laws of :mod:`sknnr_amd.weights`, ``usage`` and
-        ``domain`` need them.  Every other keyword has the meaning and the refusals it has in :meth:`predict_chunks`."""
+        ``domain`` need them.  Every other keyword has the meaning and the refusals it has in :meth:`predict_chunks`.
+        (Bootstrap planes from a stored raster: :meth:`bootstrap_neighbors_chunks`.)"""
+        return self._replay_chunks(neighbor_tiles, y=y, n_neighbors=n_neighbors, ids=ids, fill_index=fill_index,
+                                   unknown=unknown, out=out, layout=layout, out_dtype=out_dtype, scale=scale, offset=offset,
+                                   out_nodata=out_nodata, statistic=statistic, outputs=outputs, usage=usage, zones=zones,
+                                   zonal=zonal, domain=domain, domain_out=domain_out, beyond=beyond)
+
+    def bootstrap_neighbors_chunks(self, neighbor_tiles, bootstrap, y=None, n_neighbors=None, ids=False, fill_index=-1,
+                                   unknown="raise", out=None, layout="rows", out_dtype=None, scale=None, offset=None,
+                                   out_nodata=None, outputs=None):
+        """``predict_chunks(..., bootstrap=bootstrap)`` from STORED neighbours: the bootstrap planes of a
+        :class:`sknnr_amd.Bootstrap` reduced from the neighbour raster a search stream stored, through the replay pipeline of
+        :meth:`predict_neighbors_chunks`; no search runs.  ``n_neighbors`` is the number of CANDIDATES ``kw`` taken from the
+        stored columns (by default ``bootstrap.n_candidates``, else every stored column) and the replicate size is the
+        estimator's ``n_neighbors``; the result equals the search-side bootstrap that searched those ``kw`` neighbours bit
+        for bit.  ``outputs`` as in :meth:`summarize` with ``bootstrap=``; ``y``, ``ids``, ``fill_index``, ``unknown``,
+        ``out``, ``layout`` and the typed-output keywords as in :meth:`predict_neighbors_chunks` (an integer ``out_dtype``
+        always needs ``out_nodata``).  The result is ``(N, n_out)``, ``(n_out, N)`` with ``layout="bands"``."""
+        if bootstrap is None:
+            raise TypeError("bootstrap must be a sknnr_amd.Bootstrap, got NoneType")
+        return self._replay_chunks(neighbor_tiles, y=y, n_neighbors=n_neighbors, ids=ids, fill_index=fill_index,
+                                   unknown=unknown, out=out, layout=layout, out_dtype=out_dtype, scale=scale, offset=offset,
+                                   out_nodata=out_nodata, outputs=outputs, bootstrap=bootstrap)
+
+    def bootstrap_neighbors(self, idx, dist=None, *, bootstrap, **kwargs):
+        """:meth:`bootstrap_neighbors_chunks` on one tile of stored neighbours, through the same path."""
+        return self.bootstrap_neighbors_chunks([idx if dist is None else (dist, idx)], bootstrap, **kwargs)
+
+    def _replay_chunks(self, neighbor_tiles, y=None, n_neighbors=None, ids=False, fill_index=-1, unknown="raise", out=None,
+                       layout="rows", out_dtype=None, scale=None, offset=None, out_nodata=None, statistic=None, outputs=None,
+                       usage=None, zones=None, zonal=None, domain=None, domain_out=None, beyond="keep", bootstrap=None):
+        """The replay behind :meth:`predict_neighbors_chunks` and, with ``bootstrap``, :meth:`bootstrap_neighbors_chunks`."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         if unknown not in ("raise", "nodata"):
@@ -1844,12 +1984,20 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             raise ValueError(f"fill_index must be an integer, got {fill_index!r}")
         engine, flat, n_targets, target_dtype = self._replay_target_engine(y)
         id_table = self._replay_id_table(ids)
+        boot = None
+        if bootstrap is not None:  # (every refusal before any device work)
+            boot = self._boot_chunks_request(bootstrap, statistic, outputs, usage=usage, zones=zones, zonal=zonal,
+                                             domain=domain, domain_out=domain_out, beyond=beyond, n_targets=n_targets,
+                                             stored=True)
+            statistic = outputs = None
         statistic = resolve_statistic(statistic, outputs, n_targets)
         plan = statistic if isinstance(statistic, OutputPlan) else None
-        flat = flat and (plan is None or plan.per_target)
+        flat = flat and (plan is None or plan.per_target) and boot is None
         t_cols = n_targets if plan is None else plan.n_out
+        if boot is not None:
+            t_cols = len(boot[1][0])
         output = normalize_typed_output(out_dtype, scale, offset, out_nodata, t_cols,
-                                        unknown == "nodata" or (law and weights.can_vanish) or blank)
+                                        unknown == "nodata" or (law and weights.can_vanish) or blank or boot is not None)
         if (zones is None) != (zonal is None):
             raise ValueError("zones and zonal come together: the zone codes of every tile, and the ZonalStats they are tallied into")
         zonal_binding = None
@@ -1900,8 +2048,20 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                     if ks < 1:
                         raise ValueError(f"tile {number}: the tile holds no neighbour column")
                     k = min(self.n_neighbors, ks) if n_neighbors is None else int(n_neighbors)
+                    if boot is not None and n_neighbors is None:  # (k is the number of candidates)
+                        k = ks if bootstrap.n_candidates is None else bootstrap.n_candidates
                     if k > ks:
                         raise ValueError(f"n_neighbors={k} is above the {ks} stored neighbour columns")
+                    if boot is not None:  # (k is kw: the caps of Bootstrap.candidates, before any device work)
+                        if self.n_neighbors > k:
+                            raise ValueError(f"bootstrap: n_neighbors = {self.n_neighbors} exceeds the {k} candidates in use: a "
+                                             "replicate takes k of the kw neighbours stored")
+                        if k > MAX_CANDIDATES:
+                            raise ValueError(f"bootstrap: {k} candidates in use exceed the limit of {MAX_CANDIDATES}: pass "
+                                             "n_neighbors (or n_candidates) to take the leading columns")
+                        if k > self.n_samples_fit_:
+                            raise ValueError(f"bootstrap: {k} candidates in use exceed the {self.n_samples_fit_} rows that "
+                                             "can be neighbours")
                     settle(k, dist is not None)
                 elif key != shape_key:
                     raise ValueError(f"tile {number}: the tiles of one call share one ks and one dtype pair: got ks={ks}, "
@@ -1912,6 +2072,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                     eng = engine()
                     if id_table is not None:
                         eng.set_replay_ids(id_table)
+                    if boot is not None:
+                        eng.set_bootstrap(boot[2])
                     stream = eng.open_replay(k, ks, weights=weights, idx_dtype=idx.dtype,
                                              dist_dtype=None if dist is None else dist.dtype, fill_index=int(fill_index),
                                              ids=id_table is not None, output=out_kw,
@@ -1920,7 +2082,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              **({} if zonal is None else
                                                 dict(zonal=(zonal.n_zones, zonal.n_classes(zonal_binding[0])))),
                                              **({} if domain is None else
-                                                dict(domain=(domain.table, domain.rank, domain.threshold, blank))))
+                                                dict(domain=(domain.table, domain.rank, domain.threshold, blank))),
+                                             **({} if boot is None else dict(bootstrap=(self.n_neighbors, boot[1]))))
                 window = None
                 if o_pred is not None:
                     if bands:
@@ -1949,11 +2112,13 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 raise ValueError(_ZONES_LONG)
             if shape_key is None:  # (no tile at all: what can be checked without one)
                 settle(self.n_neighbors if n_neighbors is None else int(n_neighbors), True)
-            tallied = zoned = placed = None
+            tallied = zoned = placed = booted = None
             if stream is not None:
                 done, stream = stream, None
                 try:
                     counts = done.counts()
+                    if boot is not None:
+                        booted = done.bootstrap()
                     if usage is not None:
                         tallied = done.tally()
                     if zonal is not None:
@@ -1968,6 +2133,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                  f"is not in the fitted index, or a position outside [0, {self.n_samples_fit_})); the first "
                                  f"of them are in tile {tile_of_push[counts['first_unknown']]}.  Pass unknown='nodata' to "
                                  "store them as nodata pixels")
+            if booted is not None:  # (only a call that came through whole is added)
+                bootstrap._add(booted)
             if placed is not None:  # (only a call that came through whole is added)
                 domain._add(placed)
             if zonal is not None:
@@ -2161,12 +2328,19 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         return self._host_result(X, self.regressor_._predict_engine(X, apply_affine=X is not None and self._map_on_device(),
                                                                     owner=self.transformer_))
 
-    def summarize(self, X=None, statistic=None, outputs=None):
+    def summarize(self, X=None, statistic=None, outputs=None, bootstrap=None):
         """Per-target summaries of each query's neighbours (:meth:`RawKNNRegressor.summarize`, also for the definitions
-        of ``statistic`` and of ``outputs``, the ``(target, statistic)`` pairs reduced from one search); ``X=None``: of
-        every fitted row's neighbours, itself excluded."""
+        of ``statistic`` and of ``outputs``, the ``(target, statistic)`` pairs reduced from one search, and for
+        ``bootstrap``; the transform stays the one fitted on all plots); ``X=None``: of every fitted row's neighbours,
+        itself excluded."""
         check_is_fitted(self, "regressor_")
         reg = self.regressor_
+        if bootstrap is not None:
+            request = reg._bootstrap_request(bootstrap, statistic, outputs, self_query=X is None)
+            if X is not None:
+                X = self._validate_raw_query(X)
+            return self._host_result(X, reg._bootstrap_engine(X, bootstrap, request, owner=self.transformer_,
+                                                              apply_affine=X is not None and self._map_on_device()))
         if statistic is None and outputs is None:
             statistic = "mean"
         stat = resolve_statistic(statistic, outputs, reg._n_targets())
@@ -2291,7 +2465,7 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
                        out_nodata=None, statistic=None, return_neighbors=False, return_distance=True,
                        return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
                        distance_dtype=None, outputs=None, usage=None, zones=None, zonal=None, domain=None, domain_out=None,
-                       beyond="keep"):
+                       beyond="keep", bootstrap=None):
         """``predict`` over an iterable of untransformed host tiles as one streamed call (``nodata``: masked rows are
         predicted NaN; ``layout="bands"``: band-first tiles and predictions; ``out_dtype`` / ``scale`` / ``offset`` /
         ``out_nodata``: predictions converted on the device to the type the raster is stored in; ``statistic``: one name
@@ -2301,10 +2475,21 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         :class:`sknnr_amd.NeighborUsage` the device's tally of the neighbours is added to; ``zones`` / ``zonal``: the zone
         codes of every tile and the :class:`sknnr_amd.ZonalStats` the device's zonal tables are added to; ``domain`` /
         ``domain_out`` / ``beyond``: the :class:`sknnr_amd.DistanceDomain` the pixels' distances are placed within on the
-        device, the uint8 plane that receives the codes, and ``"nodata"`` to blank the predictions beyond its threshold; see
+        device, the uint8 plane that receives the codes, and ``"nodata"`` to blank the predictions beyond its threshold;
+        ``bootstrap``: a :class:`sknnr_amd.Bootstrap` -- the planes are bootstrap statistics reduced from one search at its
+        ``n_candidates``, the transform staying the one fitted on all plots; see
         :meth:`RawKNNRegressor.kneighbors_chunks` / :meth:`RawKNNRegressor.predict_chunks`)."""
         bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
+        if bootstrap is not None:
+            reg = self.regressor_
+            request = reg._boot_chunks_request(bootstrap, statistic, outputs, return_neighbors, return_distance,
+                                               return_dataframe_index, neighbors_out, fill_index, index_dtype, distance_dtype,
+                                               usage, zones, zonal, domain, domain_out, beyond)
+            return reg._bootstrap_chunks(tiles, self._band_validator(bands), bootstrap, request,
+                                         apply_affine=self._map_on_device(), out=out, owner=self.transformer_,
+                                         nodata=self._raw_nodata(nodata), bands=bands,
+                                         typed=(out_dtype, scale, offset, out_nodata))
         neighbors = self.regressor_._neighbor_request(return_neighbors, return_distance, return_dataframe_index,
                                                       neighbors_out, fill_index, index_dtype, distance_dtype)
         extra = {} if neighbors is None else dict(neighbors=neighbors)
@@ -2334,6 +2519,20 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
     def predict_neighbors(self, idx, dist=None, **kwargs):
         """:meth:`predict_neighbors_chunks` on one tile of stored neighbours, through the same path."""
         return self.predict_neighbors_chunks([idx if dist is None else (dist, idx)], **kwargs)
+
+    def bootstrap_neighbors_chunks(self, neighbor_tiles, bootstrap, **kwargs):
+        """Bootstrap planes from STORED neighbours (:meth:`RawKNNRegressor.bootstrap_neighbors_chunks`, with its keywords);
+        nothing is transformed and nothing is searched, and the transform stays the one fitted on all plots."""
+        check_is_fitted(self, "regressor_")
+        reg = self.regressor_
+        try:
+            return reg.bootstrap_neighbors_chunks(neighbor_tiles, bootstrap, **kwargs)
+        finally:
+            self.replay_unknown_ = getattr(reg, "replay_unknown_", 0)
+
+    def bootstrap_neighbors(self, idx, dist=None, *, bootstrap, **kwargs):
+        """:meth:`bootstrap_neighbors_chunks` on one tile of stored neighbours, through the same path."""
+        return self.bootstrap_neighbors_chunks([idx if dist is None else (dist, idx)], bootstrap, **kwargs)
 
     def score(self, X, y):
         """REF _base.py:350-352."""

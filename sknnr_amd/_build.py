@@ -41,12 +41,13 @@ UNITS = [
     ("k_zonal", "k_zonal.hip", []),
     ("k_domain", "k_domain.hip", []),
     ("k_replay", "k_replay.hip", []),
+    ("k_bootstrap", "k_bootstrap.hip", []),
     ("k_coarse1", "k_coarse1.hip", []),
     ("k_coarse2_a", "k_coarse2.hip", ["-DSKNNR_C2_PART=0"]),
     ("k_coarse2_b", "k_coarse2.hip", ["-DSKNNR_C2_PART=1"]),
 ]
 SOURCES = sorted({u[1] for u in UNITS})
-HEADERS = ["launch.hip.h", "coarse.hip.h", "coarse2.hip.h", "bucket.hip.h", "hamming.hip.h", "exact.hip.h", "rescue.hip.h", "forest.hip.h", "mask.hip.h", "planes.hip.h", "narrow.hip.h", "summary.hip.h", "plan.hip.h", "weights.hip.h", "groups.hip.h", "buffer.hip.h", "tally.hip.h", "zonal.hip.h", "domain.hip.h", "replay.hip.h",
+HEADERS = ["launch.hip.h", "coarse.hip.h", "coarse2.hip.h", "bucket.hip.h", "hamming.hip.h", "exact.hip.h", "rescue.hip.h", "forest.hip.h", "mask.hip.h", "planes.hip.h", "narrow.hip.h", "summary.hip.h", "plan.hip.h", "weights.hip.h", "groups.hip.h", "buffer.hip.h", "tally.hip.h", "zonal.hip.h", "domain.hip.h", "replay.hip.h", "bootstrap.hip.h",
            "../../include/sknnr_hip.h"]
 
 HIPCC_FLAGS = [

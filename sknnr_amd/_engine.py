@@ -635,7 +635,7 @@ class KNNEngine:
     def open_stream(self, k, *, weights=None, want_dist=True, deterministic=True, decimals=10,
                     formula="expanded", apply_affine=False, row_offset=0, check_finite=False, query_dtype=0,
                     nodata=None, fill_index=-1, output=None, statistic=None, id_table=None, fill_id=-1, plan=None,
-                    tally=False, zonal=None, domain=None):
+                    tally=False, zonal=None, domain=None, bootstrap=None):
         """A :class:`sknnr_amd._native.QueryStream` over host tiles: ``push(tile)`` keeps the PCIe
         pipeline full across tiles and carries the global row offset.  ``weights`` (``"uniform"`` /
         ``"distance"`` / a :class:`sknnr_amd.weights.DistanceWeights` law, evaluated on the device tile by tile) also
@@ -654,7 +654,9 @@ class KNNEngine:
         needs ``stream.next_zones(codes)`` first, and ``stream.zonal()`` reads the result.  ``domain``: ``(table, rank,
         threshold, mask_beyond)`` -- every tile's distances are coded against the table on the device
         (:meth:`sknnr_amd._native.QueryStream.set_domain`); ``stream.next_domain_out(plane)`` names where a push's codes go
-        and ``stream.domain()`` reads the accumulators."""
+        and ``stream.domain()`` reads the accumulators.  ``bootstrap``: ``(k, (cols, codes))`` -- the stream's reduction
+        stage is the bootstrap of the table of :meth:`set_bootstrap` (``k`` of this call is then the number of candidates
+        searched); ``stream.bootstrap()`` reads its tallies."""
         want_pred = weights is not None
         law = self.weight_law(weights)  # (a distance-weight law: every tile's weights are made on the device)
         if want_pred and not law and weights not in _WEIGHT_MODES:
@@ -672,7 +674,7 @@ class KNNEngine:
             raise ValueError("a stream takes statistic or an output plan, not both")
         return self._index.open_stream(opts, want_dist=want_dist, want_pred=want_pred, nodata=nodata, fill_index=fill_index,
                                        output=output, statistic=statistic, id_table=id_table, fill_id=fill_id, plan=plan,
-                                       tally=tally, zonal=zonal, domain=domain)
+                                       tally=tally, zonal=zonal, domain=domain, bootstrap=bootstrap)
 
     @classmethod
     def for_targets(cls, y, device: int | None = None, target_dtype=None):
@@ -698,7 +700,7 @@ class KNNEngine:
 
     def open_replay(self, k, ks, *, weights=None, idx_dtype=np.int64, dist_dtype=None, fill_index=-1, ids=False,
                     want_dist=False, output=None, statistic=None, id_table=None, fill_id=-1, plan=None, tally=False,
-                    zonal=None, domain=None):
+                    zonal=None, domain=None, bootstrap=None):
         """A :class:`sknnr_amd._native.ReplayStream`: tiles of ``ks`` stored neighbour columns (``idx_dtype`` int32 /
         int64, ``dist_dtype`` float32 / float64 or None) in place of feature rows, the leading ``k`` in use; ``ids``:
         the stored values are ids of :meth:`set_replay_ids`.  Every other keyword as in :meth:`open_stream`."""
@@ -716,6 +718,8 @@ class KNNEngine:
         try:  # (the order of Index.open_stream)
             if plan is not None:
                 stream.set_plan(plan)
+            if bootstrap is not None:
+                stream.set_bootstrap(*bootstrap)
             if output:
                 stream.set_output(**output)
             if statistic is not None:
@@ -732,6 +736,45 @@ class KNNEngine:
             stream.close()
             raise
         return stream
+
+    def set_bootstrap(self, table):
+        """The uint8 ``(B, n_ref)`` multiplicity table of bootstrap reductions (None: none); uploaded when it changes."""
+        held = getattr(self, "_boot_table", None)
+        if table is held:
+            return
+        if table is None or held is None or not np.array_equal(table, held):
+            self._index.set_bootstrap(table)
+        self._boot_table = table
+
+    def bootstrap_weights(self, weights):
+        """``(weight_mode, weight_law)`` of a bootstrap reduction: always float64, uniform / distance / a device law."""
+        law = self.weight_law(weights)
+        if law:
+            return _native.WEIGHTS_EXPLICIT, law
+        if callable(weights) or weights not in _WEIGHT_MODES:
+            raise ValueError("a bootstrap reduces with 'uniform' or 'distance' weights, or a sknnr_amd.weights law, only")
+        return _WEIGHT_MODES[weights], 0
+
+    def bootstrap_from_neighbors(self, dist, idx, k, weights, plan):
+        """The bootstrap reduction (include/sknnr_hip.h, "Bootstrap") of ``(dist, idx)`` of ``kw`` columns with replicates of
+        ``k`` copies, from the table of :meth:`set_bootstrap`: ``(out, tally)`` -- ``out`` float64 ``(nq, n_out)`` for the plan
+        ``(cols, codes)``, numpy -> numpy or torch.cuda -> torch.cuda, and ``tally`` the int64 pair (pixels, valid replicates)."""
+        if self.t < 1:
+            raise ValueError("the engine was built without targets")
+        mode, law = self.bootstrap_weights(weights)
+        kw = idx.shape[1]
+        if is_torch_cuda_tensor(idx):
+            import torch
+
+            idx = idx.to(torch.int64).contiguous()
+            dist = None if dist is None else dist.to(torch.float64).contiguous()
+            out = torch.empty((idx.shape[0], len(plan[0])), dtype=torch.float64, device=idx.device)
+            tally = torch.zeros(2, dtype=torch.int64, device=idx.device)
+            stream = torch.cuda.current_stream(idx.device).cuda_stream
+            self._index.bootstrap_from_neighbors_device(0 if dist is None else dist.data_ptr(), idx.data_ptr(), idx.shape[0], kw,
+                                                        k, plan, out.data_ptr(), tally.data_ptr(), mode, law, stream)
+            return out, tally.cpu().numpy()
+        return self._index.bootstrap_from_neighbors_host(dist, idx, k, plan, mode, law)
 
     def hamming_distances(self, X, rows=None):
         """Full weighted-Hamming distance rows of ``X[rows]`` (``X`` None: of the fitted rows) from the device."""

@@ -146,6 +146,11 @@ EXPORTED_SYMBOLS = (
     "sknnr_replay_push_planes",
     "sknnr_replay_get_counts",
     "sknnr_debug_last_replay",
+    "sknnr_index_set_bootstrap",
+    "sknnr_bootstrap_from_neighbors",
+    "sknnr_stream_set_bootstrap",
+    "sknnr_stream_get_bootstrap",
+    "sknnr_debug_last_bootstrap",
     "sknnr_debug_last_narrow",
     "sknnr_debug_last_mask",
     "sknnr_debug_mask_compact",
@@ -399,6 +404,13 @@ def load(build_if_missing: bool = False):
         lib.sknnr_replay_push_planes.argtypes = [vp, vp, vp, c_int64, c_int64, vp, vp, vp, c_int64]
         lib.sknnr_replay_get_counts.argtypes = [vp, POINTER(c_int64)]
         lib.sknnr_debug_last_replay.argtypes = [vp, POINTER(c_int64)]
+    if hasattr(lib, "sknnr_bootstrap_from_neighbors"):  # (likewise)
+        lib.sknnr_index_set_bootstrap.argtypes = [vp, vp, c_int32, c_int64]
+        lib.sknnr_bootstrap_from_neighbors.argtypes = [vp, vp, vp, c_int64, c_int32, c_int32, c_int32, c_int32, vp, vp, c_int32,
+                                                       vp, vp, c_int32, vp]
+        lib.sknnr_stream_set_bootstrap.argtypes = [vp, c_int32, vp, vp, c_int32]
+        lib.sknnr_stream_get_bootstrap.argtypes = [vp, POINTER(c_int64)]
+        lib.sknnr_debug_last_bootstrap.argtypes = [vp, POINTER(c_int64)]
     lib.sknnr_shard_candidates.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int64, vp, vp, c_int32, vp]
     lib.sknnr_merge_shards.argtypes = [vp, vp, c_int64, POINTER(QueryOpts), c_int32, vp, vp, vp, vp, c_int32, vp]
     lib.sknnr_crosswalk.argtypes = [vp, c_int64, vp, c_int64, vp, c_int32, c_int32, vp]
@@ -471,6 +483,29 @@ def _c_plan(plan):
     if not (cols.size == codes.size == params.size):
         raise ValueError("an output plan's columns, codes and parameters must have one length")
     return cols, codes, params
+
+
+# sknnr_bootstrap_statistic (include/sknnr_hip.h)
+BOOT_STATISTICS = {"boot_se": 0, "boot_mean": 1, "boot_bias": 2, "boot_count": 3}
+
+
+def bootstrap_pixels_per_wave(B: int, kw: int) -> int:
+    """Pixels one wave of the bootstrap kernel reduces (sknnr_amd/csrc/bootstrap.hip.h: bootstrap_ppw)."""
+    if B <= 16 and 4 * kw <= 192:
+        return 4
+    if B <= 32 and 2 * kw <= 192:
+        return 2
+    return 1
+
+
+def _c_boot_plan(plan):
+    """A bootstrap plan ``(cols, codes)`` as the C entry points read it: two int32 host arrays of one length."""
+    cols, codes = plan
+    cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+    codes = np.ascontiguousarray(codes, dtype=np.int32).reshape(-1)
+    if cols.size != codes.size:
+        raise ValueError("a bootstrap plan's columns and codes must have one length")
+    return cols, codes
 
 
 def _c_rows(a, opts):
@@ -675,6 +710,51 @@ class Index:
         check(load().sknnr_debug_last_replay(self.handle, out))
         return dict(zip(("pixels", "masked", "unknown", "instance", "skeleton", "search_launches", "k", "ks"), map(int, out)))
 
+    # ---- bootstrap (include/sknnr_hip.h, "Bootstrap") --------------------------------------------
+    def set_bootstrap(self, table) -> None:
+        """The multiplicity table of bootstrap reductions (sknnr_index_set_bootstrap): ``(B, n_ref)`` non-negative
+        integers, clamped to 255 (no result can tell, k <= 192); ``None`` removes it."""
+        if table is None:
+            check(load().sknnr_index_set_bootstrap(self.handle, None, 0, 0))
+            return
+        table = np.asarray(table)
+        if table.ndim != 2:
+            raise ValueError(f"a bootstrap table is (B, n_ref), got shape {table.shape}")
+        table = np.ascontiguousarray(np.minimum(table, 255), dtype=np.uint8)
+        check(load().sknnr_index_set_bootstrap(self.handle, _host_ptr(table), int(table.shape[0]), int(table.shape[1])))
+
+    def bootstrap_from_neighbors_host(self, dist, idx, k, plan, weight_mode=0, weight_law=0):
+        """The bootstrap reduction alone (sknnr_bootstrap_from_neighbors) on host ``(nq, kw)`` neighbours:
+        ``(out, tally)`` with ``out`` ``(nq, n_out)`` float64 and ``tally`` the int64 pair (pixels, valid replicates).
+        ``plan``: ``(cols, codes)`` (``BOOT_STATISTICS`` codes)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        dist = _c_f64(dist)
+        cols, codes = _c_boot_plan(plan)
+        nq, kw = idx.shape
+        out = np.empty((nq, cols.size), dtype=np.float64)
+        tally = np.zeros(2, dtype=np.int64)
+        check(load().sknnr_bootstrap_from_neighbors(
+            self.handle, _host_ptr(dist), _host_ptr(idx), nq, kw, int(k), int(weight_mode), int(weight_law), _host_ptr(cols),
+            _host_ptr(codes), int(cols.size), _host_ptr(out), _host_ptr(tally), MEM_HOST, None))
+        return out, tally
+
+    def bootstrap_from_neighbors_device(self, dist_ptr, idx_ptr, nq, kw, k, plan, out_ptr, tally_ptr=0, weight_mode=0,
+                                        weight_law=0, stream=0):
+        """Device pointers in and out (``tally_ptr``: two int64 words, or 0); the plan stays host arrays."""
+        cols, codes = _c_boot_plan(plan)
+        check(load().sknnr_bootstrap_from_neighbors(
+            self.handle, c_void_p(dist_ptr or None), c_void_p(idx_ptr), nq, kw, int(k), int(weight_mode), int(weight_law),
+            _host_ptr(cols), _host_ptr(codes), int(cols.size), c_void_p(out_ptr), c_void_p(tally_ptr or None), MEM_DEVICE,
+            c_void_p(stream or None)))
+
+    BOOTSTRAP_FIELDS = ("rows", "B", "k", "kw", "n_out", "pixels_per_wave", "launches", "reserved")
+
+    def debug_last_bootstrap(self) -> dict:
+        """Debug only: the last bootstrap reduction of the handle (sknnr_debug_last_bootstrap)."""
+        out = (c_int64 * 8)()
+        check(load().sknnr_debug_last_bootstrap(self.handle, out))
+        return dict(zip(self.BOOTSTRAP_FIELDS, (int(v) for v in out)))
+
     def check_finite(self, stream=0) -> None:
         """Poll the non-finite-input flag of device-memory calls made with ``check_finite``
         (synchronises ``stream``); raises :class:`HipBackendError` (``ERR_NONFINITE``)."""
@@ -682,7 +762,7 @@ class Index:
 
     def open_stream(self, opts: QueryOpts, want_dist=True, want_pred=False, nodata=None, fill_index=-1,
                     output=None, statistic=None, id_table=None, fill_id=-1, plan=None, tally=False,
-                    zonal=None, domain=None) -> "QueryStream":
+                    zonal=None, domain=None, bootstrap=None) -> "QueryStream":
         """``nodata``: float64 ``(d_in,)``, one value per column of the pushed rows -- every tile is then masked on the
         device (sknnr_stream_set_nodata) and masked rows get ``fill_index`` / NaN.  ``output``: keyword arguments of
         :meth:`QueryStream.set_output` -- the results then leave the device at those types.  ``statistic``: one
@@ -692,11 +772,14 @@ class Index:
         (:meth:`QueryStream.set_plan`; not together with ``statistic``) -- the prediction lane then holds its planes, and
         ``output``'s ``scale`` / ``offset`` one value per plane.  ``tally``: :meth:`QueryStream.set_tally`.  ``zonal``:
         ``(n_zones, n_classes)``, the arguments of :meth:`QueryStream.set_zonal`.  ``domain``: ``(table, rank, threshold,
-        mask_beyond)``, the arguments of :meth:`QueryStream.set_domain`."""
+        mask_beyond)``, the arguments of :meth:`QueryStream.set_domain`.  ``bootstrap``: ``(k, (cols, codes))``, the
+        arguments of :meth:`QueryStream.set_bootstrap` -- the stream searches ``opts.n_neighbors`` candidates."""
         stream = QueryStream(self, opts, want_dist, want_pred)
         try:
             if plan is not None:  # (first: it sets the width set_output's scale / offset must have)
                 stream.set_plan(plan)
+            if bootstrap is not None:  # (likewise)
+                stream.set_bootstrap(*bootstrap)
             if nodata is not None:
                 stream.set_nodata(nodata, fill_index)
             if output:
@@ -1370,6 +1453,23 @@ class QueryStream:
         cols, codes, params = _c_plan(plan)
         check(load().sknnr_stream_set_plan(self._h, _host_ptr(cols), _host_ptr(codes), _host_ptr(params), int(cols.size)))
         self.pred_cols = int(cols.size)
+
+    def set_bootstrap(self, k, plan):
+        """The bootstrap of the handle's table (:meth:`Index.set_bootstrap`) as the stream's reduction stage
+        (sknnr_stream_set_bootstrap; only before the first push, before :meth:`set_output`, and not together with
+        statistics, plans, the usage tally, zonal statistics or a domain): ``k`` copies per replicate out of the
+        stream's ``self.k`` candidates, ``plan`` = ``(cols, codes)``; the predictions become its ``n_out`` planes."""
+        cols, codes = _c_boot_plan(plan)
+        check(load().sknnr_stream_set_bootstrap(self._h, int(k), _host_ptr(cols), _host_ptr(codes), int(cols.size)))
+        self.pred_cols = int(cols.size)
+
+    def bootstrap(self):
+        """Flush, then the int64 pair (pixels reduced, valid replicates over them) of everything pushed so far
+        (sknnr_stream_get_bootstrap)."""
+        out = (c_int64 * 2)()
+        check(load().sknnr_stream_get_bootstrap(self._h, out))
+        self._keep.clear()
+        return np.array([out[0], out[1]], dtype=np.int64)
 
     def set_output(self, index_dtype=None, distance_dtype=None, pred_dtype=None, scale=None, offset=None, fill=None):
         """The element types in which the results leave the device (sknnr_stream_set_output; only before the first

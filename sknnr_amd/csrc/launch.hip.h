@@ -1,14 +1,15 @@
 // launch.hip.h -- the seam between the host translation unit (sknnr_hip.hip: index build, workspace, host pipeline, C ABI)
-// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_buffer.hip, k_tally.hip, k_zonal.hip, k_domain.hip, k_replay.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
+// and the kernel translation units (k_exact.hip, k_hamming.hip, k_forest.hip, k_mask.hip, k_planes.hip, k_narrow.hip, k_summary.hip, k_plan.hip, k_weights.hip, k_groups.hip, k_buffer.hip, k_tally.hip, k_zonal.hip, k_domain.hip, k_replay.hip, k_bootstrap.hip, k_coarse1.hip, k_coarse2.hip), which are compiled in
 // parallel by _build.py.  Every kernel is launched through one of the functions below; each returns the launch's
 // hipGetLastError() (the coarse launchers: an int that also says "no such instance").  Argument structs, geometry
 // constants and shared-memory sizes live in the kernel headers; a header's non-template kernels are defined only in the unit
-// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS / SKNNR_KERNELS_TALLY / SKNNR_KERNELS_ZONAL / SKNNR_KERNELS_BUFFER / SKNNR_KERNELS_DOMAIN / SKNNR_KERNELS_REPLAY), templates where they are instantiated.
+// that owns them (SKNNR_KERNELS_EXACT / SKNNR_KERNELS_HAMMING / SKNNR_KERNELS_FOREST / SKNNR_KERNELS_MASK / SKNNR_KERNELS_PLANES / SKNNR_KERNELS_NARROW / SKNNR_KERNELS_SUMMARY / SKNNR_KERNELS_PLAN / SKNNR_KERNELS_WEIGHTS / SKNNR_KERNELS_TALLY / SKNNR_KERNELS_ZONAL / SKNNR_KERNELS_BUFFER / SKNNR_KERNELS_DOMAIN / SKNNR_KERNELS_REPLAY / SKNNR_KERNELS_BOOTSTRAP), templates where they are instantiated.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "bootstrap.hip.h"
 #include "bucket.hip.h"
 #include "buffer.hip.h"
 #include "coarse2.hip.h"
@@ -147,6 +148,13 @@ hipError_t replay(const ReplayArgs& a, int idx_bytes, int dist_kind, bool planes
 long replay_blocks(long n);  // its workgroups
 // the final state of the pixels a.bad marks, behind the reduction of a tile decoded with ReplayArgs::provisional
 hipError_t replay_blank(const ReplayBlankArgs& a, hipStream_t st);
+
+// ---- k_bootstrap.hip: bootstrap standard errors of a tile's neighbour lists (bootstrap.hip.h) -----------------------------------
+// the a.n_out entries of every pixel into (nq, n_out) and the two tallies added into a.tally (not zeroed here);
+// hipErrorInvalidValue for B outside [1, kBootMaxB], k outside [1, kw], kw above kBootMaxKw, n_out outside [1, kBootMaxOut],
+// an unknown mode or law, missing arrays, a table pitch that is no multiple of 64 and a.ppw other than bootstrap_ppw(B, kw)
+hipError_t bootstrap(const BootstrapArgs& a, hipStream_t st);
+long bootstrap_blocks(long n, int ppw);  // its workgroups: the pixel groups, at most kBootMaxGrid (they stride)
 
 // ---- k_coarse1.hip / k_coarse2.hip: the MFMA pre-filters ----------------------------------------------------------------
 struct Coarse1Launch {

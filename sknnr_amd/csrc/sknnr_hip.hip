@@ -232,6 +232,16 @@ bool summary_table(const int32_t* stat, int t, std::vector<int>& tab, int* bad) 
 }
 // An output plan of one call or stream (plan.hip.h): the device arrays plan_kernel reads, and how many entries are means
 // (the predict kernels run into the handle's mean_stage for them).  The prediction lane is n_out wide while one is set.
+// The bootstrap stage of an open stream (sknnr_stream_set_bootstrap; bootstrap.hip.h): the plan's device arrays as the
+// kernel reads them and the replicate size.  The handle's `boot` points at it while one of the stream's tiles is enqueued.
+struct BootStage {
+    int n_out = 0, n_u = 0;
+    int k = 0;
+    const int* ucols = nullptr;
+    const int* uidx = nullptr;
+    const int* codes = nullptr;
+};
+
 struct OutputPlan {
     int n_out = 0;
     int n_mean = 0;
@@ -549,6 +559,21 @@ struct sknnr_index {
     unsigned long long* pin_replay = nullptr;
     long search_calls = 0;
     int64_t last_replay[8] = {};
+    // bootstrap (bootstrap.hip.h): the transposed multiplicity table of sknnr_index_set_bootstrap, (n_ref, boot_bpad) bytes,
+    // and its replicates (0: none installed); the plan arrays and the two tally words of a one-shot call; the record of the
+    // last reduction (sknnr_debug_last_bootstrap)
+    DevBuf<unsigned char> boot_mt;
+    int boot_B = 0, boot_bpad = 0;
+    DevBuf<int> c_boot;
+    DevBuf<unsigned long long> boot_tally;
+    int64_t last_boot[8] = {};
+    // the open stream's stage: `boot` is set and cleared under mtx (BootScope) and read by launch_predict and pred_cols;
+    // its plan arrays (s_boot) and the stream's two tally words (s_boot_tally); boot_skip: (rows) of the reduction in
+    // progress, pixels the blanking pass owns (a replayed tile's bad pixels), or null
+    const BootStage* boot = nullptr;
+    DevBuf<int> s_boot;
+    DevBuf<unsigned long long> s_boot_tally;
+    const unsigned char* boot_skip = nullptr;
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
     // a ring of call records so that several calls of one benchmark step are summed, not only the last.
@@ -2307,8 +2332,17 @@ struct PlanScope {
     PlanScope(const PlanScope&) = delete;
     PlanScope& operator=(const PlanScope&) = delete;
 };
-// Columns of a prediction row of the call in progress: the plan's entries, or the t targets.
-static inline int pred_cols(const sknnr_index* ix) { return ix->plan ? ix->plan->n_out : ix->t; }
+// The bootstrap stage of the stream tile in progress, in the same way.
+struct BootScope {
+    sknnr_index* ix;
+    const BootStage* before;
+    BootScope(sknnr_index* ix_, const BootStage* stage) : ix(ix_), before(ix_->boot) { ix->boot = stage; }
+    ~BootScope() { ix->boot = before; }
+    BootScope(const BootScope&) = delete;
+    BootScope& operator=(const BootScope&) = delete;
+};
+// Columns of a prediction row of the call in progress: the bootstrap's or the plan's entries, or the t targets.
+static inline int pred_cols(const sknnr_index* ix) { return ix->boot ? ix->boot->n_out : ix->plan ? ix->plan->n_out : ix->t; }
 
 namespace {
 
@@ -2600,6 +2634,10 @@ struct HostPipe {
     // output plan (sknnr_stream_set_plan): the prediction lane is plan.n_out wide and the reductions follow `plan`
     bool has_plan = false;
     OutputPlan plan;
+    // bootstrap (sknnr_stream_set_bootstrap): the reduction stage is the bootstrap of `boot`; the search (or the stored
+    // lists) has k = kw columns, the prediction lane boot.n_out
+    bool has_boot = false;
+    BootStage boot;
     struct Pending {
         bool live = false;
         long n = 0;
@@ -2825,7 +2863,10 @@ int replay_tile(HostPipe& p, int b, long n, bool planes, long* d_idx, double* d_
     HIP_TRY(launch::replay(a, r.idx_bytes, r.dist_kind, planes, st));
     int rc;
     if (d_pred) {
-        if ((rc = launch_predict(ix, d_dist, d_idx, nullptr, n, p.k, p.o.weight_mode, p.o.weight_law, d_pred, st))) return rc;
+        ix->boot_skip = sl.mask.valid.p;  // (a bootstrap stage: the provisional rows of bad pixels enter no tally)
+        rc = launch_predict(ix, d_dist, d_idx, nullptr, n, p.k, p.o.weight_mode, p.o.weight_law, d_pred, st);
+        ix->boot_skip = nullptr;
+        if (rc) return rc;
         const ReplayBlankArgs ba{sl.mask.valid.p, n, p.k, p.lane[kLanePred].cols, d_idx, d_dist, d_pred};
         HIP_TRY(launch::replay_blank(ba, st));
     }
@@ -2899,6 +2940,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     HIP_TRY(hipStreamWaitEvent(ix->st_run, sl.ev_h2d, 0));
     SummaryScope scope(ix, p.has_stat ? &p.stat : ix->summary);  // (a one-shot call's plan is already in place)
     PlanScope plan_scope(ix, p.has_plan ? &p.plan : ix->plan);
+    BootScope boot_scope(ix, p.has_boot ? &p.boot : nullptr);
     if (p.replay.on) {
         // stored neighbours: the decode leaves the tile as a search and its nodata expansion would; nothing of the search runs
         rc = replay_tile(p, b, n, planes != nullptr, idx.i64(), p.replay.dist_kind != kReplayDistNone ? dist.f64() : nullptr,
@@ -3953,8 +3995,12 @@ static int summary_upload(sknnr_index* ix, const std::vector<int>& tab, SummaryP
 // law (sknnr_weight_law of the call's opts; kLawNone: nothing here changes): the weights are law(dist), written by
 // weight_law_kernel into the handle's law_w in front of the reduction, which then is the explicit one on that buffer
 // (the F32_TARGETS flag stays).  law_w belongs to the workspace: `st` first waits for the workspace's last user.
+static int launch_bootstrap_stage(sknnr_index* ix, const double* dist, const long* idx, long nq, int kw, int mode, int law,
+                                  double* out, hipStream_t st);
 static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, const double* w, long nq, int k,
                           int mode, int law, double* out, hipStream_t st) {
+    if (ix->boot)  // (a stream with a bootstrap stage: the k columns are the kw candidates, and nothing below runs)
+        return launch_bootstrap_stage(ix, dist, idx, nq, k, mode, law, out, st);
     if (law != kLawNone) {
         if (!dist) return fail(SKNNR_ERR_INVALID, "a distance-weight law needs the distances");
         if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));
@@ -4346,6 +4392,7 @@ extern "C" int sknnr_stream_set_statistics(sknnr_stream* s, const int32_t* stat,
     std::lock_guard<std::mutex> lock(p.ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_statistics is allowed only before the first push");
     if (p.has_plan) return fail(SKNNR_ERR_INVALID, "the stream has an output plan (sknnr_stream_set_plan): it takes no per-target statistics");
+    if (p.has_boot) return fail(SKNNR_ERR_INVALID, "the stream has a bootstrap stage (sknnr_stream_set_bootstrap): it takes no per-target statistics");
     p.stat_set = true;
     p.stat = SummaryPlan{};
     p.stat.nc = (int)tab.size() / 2;
@@ -4372,6 +4419,7 @@ extern "C" int sknnr_stream_set_plan(sknnr_stream* s, const int32_t* cols, const
     std::lock_guard<std::mutex> lock(p.ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan is allowed only before the first push");
     if (p.stat_set) return fail(SKNNR_ERR_INVALID, "the stream has per-target statistics (sknnr_stream_set_statistics): it takes no output plan");
+    if (p.has_boot) return fail(SKNNR_ERR_INVALID, "the stream has a bootstrap stage (sknnr_stream_set_bootstrap): it takes no output plan");
     if (p.zonal) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan comes before sknnr_stream_set_zonal: n_classes holds one value per output plane");
     if (p.lane[kLanePred].scale)
         return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan comes before sknnr_stream_set_output: the scale / offset hold one value per output plane");
@@ -4547,6 +4595,7 @@ extern "C" int sknnr_stream_set_tally(sknnr_stream* s) {
         return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_tally: the replay stream was opened without stored distances, and the tally keeps their maxima");
     std::lock_guard<std::mutex> lock(ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_tally is allowed only before the first push");
+    if (p.has_boot) return fail(SKNNR_ERR_INVALID, "the stream has a bootstrap stage (sknnr_stream_set_bootstrap): it takes no usage tally");
     HIP_TRY(hipSetDevice(ix->device));
     const size_t n_cnt = (size_t)ix->n_ref * p.k, n_max = (size_t)ix->n_ref;
     HIP_TRY(ix->s_tally_cnt.ensure(n_cnt));
@@ -4750,6 +4799,7 @@ extern "C" int sknnr_stream_set_zonal(sknnr_stream* s, int64_t n_zones, const in
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_zonal is allowed only before the first push");
+    if (p.has_boot) return fail(SKNNR_ERR_INVALID, "the stream has a bootstrap stage (sknnr_stream_set_bootstrap): it takes no zonal statistics");
     HIP_TRY(hipSetDevice(ix->device));
     const size_t n_keys = (size_t)n_zones * c;
     HIP_TRY(ix->s_zonal_acc.ensure(n_keys * kZonalFields));
@@ -4949,6 +4999,7 @@ extern "C" int sknnr_stream_set_domain(sknnr_stream* s, const double* table, int
         return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_domain: the replay stream was opened without stored distances");
     std::lock_guard<std::mutex> lock(ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_domain is allowed only before the first push");
+    if (p.has_boot) return fail(SKNNR_ERR_INVALID, "the stream has a bootstrap stage (sknnr_stream_set_bootstrap): it takes no distance domain");
     HIP_TRY(hipSetDevice(ix->device));
     HIP_TRY(ix->s_dom_table.ensure((size_t)m));
     HIP_TRY(ix->s_dom_acc.ensure(kDomainAcc));
@@ -5335,6 +5386,263 @@ extern "C" int sknnr_debug_last_replay(const sknnr_index* cix, int64_t out[8]) {
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
     std::lock_guard<std::mutex> lock(ix->mtx);
     std::copy(ix->last_replay, ix->last_replay + 8, out);
+    return SKNNR_OK;
+}
+
+// ----------------------------------------------------------------------------------------
+// bootstrap
+// ----------------------------------------------------------------------------------------
+extern "C" int sknnr_index_set_bootstrap(sknnr_index* ix, const uint8_t* table, int32_t B, int64_t n) {
+    if (!ix) return fail(SKNNR_ERR_INVALID, "sknnr_index_set_bootstrap: index is NULL");
+    if (table) {
+        if (B < 1 || B > kBootMaxB)
+            return fail(SKNNR_ERR_INVALID, "sknnr_index_set_bootstrap: B = %d outside [1, %d]", B, kBootMaxB);
+        if (n != ix->n_ref)
+            return fail(SKNNR_ERR_INVALID, "sknnr_index_set_bootstrap: the table has %lld rows per replicate, the handle has %lld reference rows",
+                        (long long)n, (long long)ix->n_ref);
+    }
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (ix->stream_open) return fail(SKNNR_ERR_INVALID, "sknnr_index_set_bootstrap: a stream is open on this handle: end it first");
+    ix->boot_B = 0;
+    if (!table) return SKNNR_OK;
+    const int bpad = (B + 63) / 64 * 64;
+    std::vector<unsigned char> mt((size_t)n * bpad, 0);
+    for (int64_t r0 = 0; r0 < n; r0 += 64)  // (64 x 64 blocks: both sides stay in cache)
+        for (int b0 = 0; b0 < B; b0 += 64)
+            for (int b = b0; b < std::min(B, b0 + 64); ++b)
+                for (int64_t r = r0; r < std::min<int64_t>(n, r0 + 64); ++r) mt[(size_t)r * bpad + b] = table[(size_t)b * n + r];
+    HIP_TRY(hipSetDevice(ix->device));
+    if (ix->ws_busy) HIP_TRY(hipEventSynchronize(ix->ev_ws));  // (a reduction of an earlier call may still read the old table)
+    HIP_TRY(ix->boot_mt.ensure(mt.size()));
+    HIP_TRY(hipMemcpy(ix->boot_mt.p, mt.data(), mt.size(), hipMemcpyHostToDevice));
+    ix->boot_B = B;
+    ix->boot_bpad = bpad;
+    return SKNNR_OK;
+}
+
+// A bootstrap plan as the kernel reads it: the distinct columns, every entry's place among them, the codes.
+struct BootPlan {
+    std::vector<int> ucols, uidx, codes;
+};
+static int boot_plan_check(const sknnr_index* ix, const int32_t* cols, const int32_t* stat, int32_t n_out, BootPlan& bp) {
+    if (n_out < 1 || n_out > kBootMaxOut)
+        return fail(SKNNR_ERR_INVALID, "a bootstrap plan has 1 to %d entries, got %d", kBootMaxOut, n_out);
+    if (!cols || !stat) return fail(SKNNR_ERR_INVALID, "a bootstrap plan needs cols and stat");
+    bp.uidx.assign((size_t)n_out, 0);
+    bp.codes.assign(stat, stat + n_out);
+    std::vector<int> place((size_t)ix->t, -1);
+    for (int e = 0; e < n_out; ++e) {
+        if (stat[e] < 0 || stat[e] >= kBootStatCount)
+            return fail(SKNNR_ERR_INVALID, "bootstrap plan entry %d: unknown statistic %d", e, stat[e]);
+        if (stat[e] == kBootCount) continue;  // (takes no column)
+        if (cols[e] < 0 || cols[e] >= ix->t)
+            return fail(SKNNR_ERR_INVALID, "bootstrap plan entry %d: column %d outside [0, %d)", e, cols[e], ix->t);
+        if (place[(size_t)cols[e]] < 0) {
+            place[(size_t)cols[e]] = (int)bp.ucols.size();
+            bp.ucols.push_back(cols[e]);
+        }
+        bp.uidx[(size_t)e] = place[(size_t)cols[e]];
+    }
+    if (bp.ucols.empty()) bp.ucols.push_back(0);  // (counts only: the walk still needs a column to carry)
+    return SKNNR_OK;
+}
+
+// The caps of a bootstrap reduction over lists of kw columns with replicates of k copies
+static int boot_shape_check(const sknnr_index* ix, int32_t kw, int32_t k, int32_t mode, int32_t law) {
+    if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
+    if (ix->boot_B < 1) return fail(SKNNR_ERR_INVALID, "the handle has no bootstrap table (sknnr_index_set_bootstrap)");
+    if (k < 1 || k > kw || kw > kBootMaxKw)
+        return fail(SKNNR_ERR_INVALID, "a bootstrap needs 1 <= k <= kw <= %d, got k = %d, kw = %d", kBootMaxKw, k, kw);
+    if (kw > ix->n_ref)
+        return fail(SKNNR_ERR_INVALID, "kw = %d exceeds the handle's %lld reference rows", kw, (long long)ix->n_ref);
+    if (mode & ~SKNNR_WEIGHTS_BASE_MASK)
+        return fail(SKNNR_ERR_INVALID, "a bootstrap reduces in float64: weight mode flags are refused (mode %d)", mode);
+    if (law == kLawNone) {
+        if (mode == SKNNR_WEIGHTS_EXPLICIT) return fail(SKNNR_ERR_INVALID, "a bootstrap takes no explicit weights");
+        if (mode != SKNNR_WEIGHTS_UNIFORM && mode != SKNNR_WEIGHTS_DISTANCE)
+            return fail(SKNNR_ERR_INVALID, "unknown weight mode %d", mode);
+        return SKNNR_OK;
+    }
+    sknnr_query_opts o{};
+    o.weight_mode = mode;
+    o.weight_law = law;
+    const int rc = weight_law_check(ix, &o);
+    return rc < 0 ? rc : SKNNR_OK;
+}
+
+// The kernel's arguments for lists of kw columns with the plan arrays at `plan` (ucols, uidx, codes back to back) and the
+// launch; tally is added to.  Under the handle's lock.
+static int enqueue_bootstrap(sknnr_index* ix, const double* dist, const long* idx, long nq, int kw, int k, int mode, int law,
+                             const int* plan, int n_u, int n_out, double* out, unsigned long long* tally,
+                             const unsigned char* skip, hipStream_t st) {
+    BootstrapArgs a{};
+    a.y = ix->y64.p;
+    a.dist = mode == SKNNR_WEIGHTS_UNIFORM && law == kLawNone ? nullptr : dist;
+    a.idx = idx;
+    a.mt = ix->boot_mt.p;
+    a.skip = skip;
+    a.nq = nq;
+    a.n_ref = ix->n_ref;
+    a.kw = kw;
+    a.k = k;
+    a.t = ix->t;
+    a.mode = law != kLawNone ? 2 : mode;
+    a.law = law;
+    a.p0 = ix->law_p0;
+    a.p1 = ix->law_p1;
+    a.B = ix->boot_B;
+    a.bpad = ix->boot_bpad;
+    a.ucols = plan;
+    a.uidx = a.ucols + n_u;
+    a.codes = a.uidx + n_out;
+    a.n_u = n_u;
+    a.n_out = n_out;
+    a.out = out;
+    a.tally = tally;
+    a.ppw = bootstrap_ppw(a.B, kw);
+    HIP_TRY(launch::bootstrap(a, st));
+    const int64_t rec[8] = {nq, a.B, k, kw, n_out, a.ppw, nq > 0 ? 1 : 0, 0};
+    std::copy(rec, rec + 8, ix->last_boot);
+    return SKNNR_OK;
+}
+
+static std::vector<int> boot_plan_image(const BootPlan& bp) {
+    std::vector<int> img;
+    img.insert(img.end(), bp.ucols.begin(), bp.ucols.end());
+    img.insert(img.end(), bp.uidx.begin(), bp.uidx.end());
+    img.insert(img.end(), bp.codes.begin(), bp.codes.end());
+    return img;
+}
+
+// A one-shot reduction: uploads the plan, zeroes the two tally words and launches; dist / idx / out are device memory.
+static int launch_bootstrap(sknnr_index* ix, const double* dist, const long* idx, long nq, int kw, int k, int mode, int law,
+                            const BootPlan& bp, double* out, unsigned long long* tally, hipStream_t st) {
+    const std::vector<int> img = boot_plan_image(bp);
+    if (ix->ws_busy) HIP_TRY(hipEventSynchronize(ix->ev_ws));
+    HIP_TRY(ix->c_boot.ensure(img.size()));
+    HIP_TRY(hipMemcpy(ix->c_boot.p, img.data(), img.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(tally, 0, 2 * sizeof(unsigned long long), st));
+    const int rc = enqueue_bootstrap(ix, dist, idx, nq, kw, k, mode, law, ix->c_boot.p, (int)bp.ucols.size(),
+                                     (int)bp.codes.size(), out, tally, nullptr, st);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(ix->ev_ws, st));
+    ix->ws_busy = true;
+    return SKNNR_OK;
+}
+
+// The reduction stage of a tile of the open stream whose stage is ix->boot (launch_predict): the stream's tallies are
+// added to; always float64, whatever flags the stream's weight mode carries.
+static int launch_bootstrap_stage(sknnr_index* ix, const double* dist, const long* idx, long nq, int kw, int mode, int law,
+                                  double* out, hipStream_t st) {
+    const BootStage& b = *ix->boot;
+    const int base = law != kLawNone ? SKNNR_WEIGHTS_EXPLICIT : (mode & SKNNR_WEIGHTS_BASE_MASK);
+    if (base != SKNNR_WEIGHTS_UNIFORM && !dist) return fail(SKNNR_ERR_INVALID, "these weights need the distances");
+    const int rc = enqueue_bootstrap(ix, dist, idx, nq, kw, b.k, base, law, b.ucols, b.n_u, b.n_out, out, ix->s_boot_tally.p,
+                                     ix->boot_skip, st);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(ix->ev_ws, st));
+    ix->ws_busy = true;
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_bootstrap_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, int64_t nq, int32_t kw,
+                                              int32_t k, int32_t weight_mode, int32_t weight_law, const int32_t* cols,
+                                              const int32_t* stat, int32_t n_out, double* out, int64_t* tally, int32_t mem,
+                                              void* stream) {
+    if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
+    int rc = boot_shape_check(ix, kw, k, weight_mode, weight_law);
+    if (rc) return rc;
+    BootPlan bp;
+    if ((rc = boot_plan_check(ix, cols, stat, n_out, bp))) return rc;
+    if (nq < 0 || !idx || !out) return fail(SKNNR_ERR_INVALID, "bad argument");
+    if (weight_mode != SKNNR_WEIGHTS_UNIFORM && !dist) return fail(SKNNR_ERR_INVALID, "these weights need dist");
+    if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (ix->boot_B < 1) return fail(SKNNR_ERR_INVALID, "the handle has no bootstrap table (sknnr_index_set_bootstrap)");
+    HIP_TRY(hipSetDevice(ix->device));
+    if (mem == SKNNR_MEM_DEVICE) {
+        hipStream_t st = (hipStream_t)stream;
+        unsigned long long* dt = (unsigned long long*)tally;
+        if (!dt) {
+            if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));
+            HIP_TRY(ix->boot_tally.ensure(2));
+            dt = ix->boot_tally.p;
+        }
+        return launch_bootstrap(ix, dist, (const long*)idx, nq, kw, k, weight_mode, weight_law, bp, out, dt, st);
+    }
+    DevBuf<double> dd, dout;  // freed by their destructors on every return path
+    DevBuf<long> di;
+    DevBuf<unsigned long long> dt;
+    HIP_TRY(di.ensure((size_t)nq * kw));
+    HIP_TRY(dout.ensure((size_t)nq * n_out));
+    HIP_TRY(dt.ensure(2));
+    HIP_TRY(hipMemcpy(di.p, idx, (size_t)nq * kw * sizeof(long), hipMemcpyHostToDevice));
+    if (dist && weight_mode != SKNNR_WEIGHTS_UNIFORM) {
+        HIP_TRY(dd.ensure((size_t)nq * kw));
+        HIP_TRY(hipMemcpy(dd.p, dist, (size_t)nq * kw * sizeof(double), hipMemcpyHostToDevice));
+    }
+    rc = launch_bootstrap(ix, dd.p, di.p, nq, kw, k, weight_mode, weight_law, bp, dout.p, dt.p, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out, dout.p, (size_t)nq * n_out * sizeof(double), hipMemcpyDeviceToHost));
+    if (tally) HIP_TRY(hipMemcpy(tally, dt.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_set_bootstrap(sknnr_stream* s, int32_t k, const int32_t* cols, const int32_t* stat, int32_t n_out) {
+    if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
+    HostPipe& p = s->pipe;
+    sknnr_index* ix = p.ix;
+    if (!p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
+    int rc = boot_shape_check(ix, p.k, k, p.o.weight_mode & SKNNR_WEIGHTS_BASE_MASK, p.o.weight_law);
+    if (rc) return rc;
+    BootPlan bp;
+    if ((rc = boot_plan_check(ix, cols, stat, n_out, bp))) return rc;
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_bootstrap is allowed only before the first push");
+    if (p.stat_set) return fail(SKNNR_ERR_INVALID, "the stream has per-target statistics (sknnr_stream_set_statistics): it takes no bootstrap");
+    if (p.has_plan) return fail(SKNNR_ERR_INVALID, "the stream has an output plan (sknnr_stream_set_plan): it takes no bootstrap");
+    if (p.tally) return fail(SKNNR_ERR_INVALID, "the stream tallies neighbour usage (sknnr_stream_set_tally): it takes no bootstrap");
+    if (p.domain) return fail(SKNNR_ERR_INVALID, "the stream has a distance domain (sknnr_stream_set_domain): it takes no bootstrap");
+    if (p.zonal) return fail(SKNNR_ERR_INVALID, "the stream has zonal statistics (sknnr_stream_set_zonal): it takes no bootstrap");
+    if (p.lane[kLanePred].scale)
+        return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_bootstrap comes before sknnr_stream_set_output: the scale / offset hold one value per output plane");
+    HIP_TRY(hipSetDevice(ix->device));
+    const std::vector<int> img = boot_plan_image(bp);
+    HIP_TRY(ix->s_boot.ensure(img.size()));
+    HIP_TRY(hipMemcpy(ix->s_boot.p, img.data(), img.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(ix->s_boot_tally.ensure(2));
+    HIP_TRY(hipMemsetAsync(ix->s_boot_tally.p, 0, 2 * sizeof(unsigned long long), ix->st_run));  // (in front of the first tile)
+    p.boot = BootStage{};
+    p.boot.n_out = n_out;
+    p.boot.n_u = (int)bp.ucols.size();
+    p.boot.k = k;
+    p.boot.ucols = ix->s_boot.p;
+    p.boot.uidx = p.boot.ucols + p.boot.n_u;
+    p.boot.codes = p.boot.uidx + n_out;
+    p.has_boot = true;
+    p.lane[kLanePred].cols = n_out;  // from now on the prediction lane is n_out wide
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_stream_get_bootstrap(sknnr_stream* s, int64_t tally[2]) {
+    if (!s || !tally) return fail(SKNNR_ERR_INVALID, "sknnr_stream_get_bootstrap: NULL argument");
+    HostPipe& p = s->pipe;
+    sknnr_index* ix = p.ix;
+    if (!p.has_boot) return fail(SKNNR_ERR_INVALID, "the stream has no bootstrap stage: sknnr_stream_set_bootstrap was not called");
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    HIP_TRY(hipSetDevice(ix->device));
+    const int rc = pipe_flush(p);
+    if (rc) return pipe_fail(p, rc);
+    HIP_TRY(hipStreamSynchronize(ix->st_run));
+    HIP_TRY(hipMemcpy(tally, ix->s_boot_tally.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return SKNNR_OK;
+}
+
+extern "C" int sknnr_debug_last_bootstrap(const sknnr_index* cix, int64_t out[8]) {
+    if (!cix || !out) return fail(SKNNR_ERR_INVALID, "sknnr_debug_last_bootstrap: NULL argument");
+    sknnr_index* ix = const_cast<sknnr_index*>(cix);
+    std::lock_guard<std::mutex> lock(ix->mtx);
+    std::copy(ix->last_boot, ix->last_boot + 8, out);
     return SKNNR_OK;
 }
 
