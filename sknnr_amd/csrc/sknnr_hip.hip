@@ -233,7 +233,7 @@ bool summary_table(const int32_t* stat, int t, std::vector<int>& tab, int* bad) 
 // An output plan of one call or stream (plan.hip.h): the device arrays plan_kernel reads, and how many entries are means
 // (the predict kernels run into the handle's mean_stage for them).  The prediction lane is n_out wide while one is set.
 // The bootstrap stage of an open stream (sknnr_stream_set_bootstrap; bootstrap.hip.h): the plan's device arrays as the
-// kernel reads them and the replicate size.  The handle's `boot` points at it while one of the stream's tiles is enqueued.
+// kernel reads them and the replicate size.
 struct BootStage {
     int n_out = 0, n_u = 0;
     int k = 0;
@@ -248,6 +248,19 @@ struct OutputPlan {
     const int* cols = nullptr;
     const int* codes = nullptr;
     const double* param = nullptr;
+};
+// What the reduction behind a search (or behind stored neighbours) computes: the kind and the part that belongs to it.
+// Every function between an entry point and launch_predict takes it as an argument; the handle holds none.  A default
+// one is the mean of every target; a statistics table that is all mean (stat.nc == 0) enqueues the same launches.
+enum { kReduceMean = 0, kReduceStats, kReducePlan, kReduceBoot };
+struct Reduction {
+    int kind = kReduceMean;
+    SummaryPlan stat;
+    OutputPlan plan;
+    BootStage boot;
+    unsigned long long* boot_tally = nullptr;  // the two tally words a bootstrap launch adds to (device)
+    // columns of a prediction row over t targets
+    int cols(int t) const { return kind == kReduceBoot ? boot.n_out : kind == kReducePlan ? plan.n_out : t; }
 };
 // The host image of a plan's device arrays: n_out parameters, then (as ints) n_out columns and n_out codes.
 std::vector<double> plan_image(const int32_t* cols, const int32_t* stat, const double* param, int n_out) {
@@ -497,20 +510,14 @@ struct sknnr_index {
     DevBuf<double> s_scale, s_offset;
     DevBuf<long> s_id_table;
     int64_t last_narrow[8] = {};
-    // per-target statistics (summary.hip.h).  `summary`: the plan of the call in progress, set and cleared under mtx
-    // (SummaryScope), read by launch_predict; null: every column is the mean.  The device tables of a one-shot call
-    // (c_stat, a workspace buffer behind ev_ws) and of the open stream (s_stat); the record of the last reduction
-    // (sknnr_debug_last_summary).
-    const SummaryPlan* summary = nullptr;
+    // per-target statistics (summary.hip.h): the device tables of a one-shot call (c_stat, a workspace buffer behind
+    // ev_ws) and of the open stream (s_stat); the record of the last reduction (sknnr_debug_last_summary).
     DevBuf<int> c_stat, s_stat;
     int64_t last_summary[8] = {};
-    // output plans (plan.hip.h).  `plan`: the plan of the call in progress, set and cleared under mtx (PlanScope), read by
-    // launch_predict and by whatever sizes the prediction lane (pred_cols); null: the lane holds the t targets.  The device
-    // arrays of a one-shot call (c_plan, a workspace buffer behind ev_ws) and of the open stream (s_plan); the (rows, t)
-    // means the predict kernels write for a plan's `mean` entries (mean_stage, behind ev_ws too); the record of the last
-    // reduction (sknnr_debug_last_plan): plan kernel ran, path (1 register, 2 wide), rows, n_out, k, mean entries, predict
-    // kernels ran.
-    const OutputPlan* plan = nullptr;
+    // output plans (plan.hip.h): the device arrays of a one-shot call (c_plan, a workspace buffer behind ev_ws) and of the
+    // open stream (s_plan); the (rows, t) means the predict kernels write for a plan's `mean` entries (mean_stage, behind
+    // ev_ws too); the record of the last reduction (sknnr_debug_last_plan): plan kernel ran, path (1 register, 2 wide),
+    // rows, n_out, k, mean entries, predict kernels ran.
     DevBuf<double> c_plan, s_plan, mean_stage;
     int64_t last_plan[8] = {};
     // distance-weight laws (weights.hip.h): the handle's law and its parameters (sknnr_index_set_weight_law_params), the
@@ -567,13 +574,9 @@ struct sknnr_index {
     DevBuf<int> c_boot;
     DevBuf<unsigned long long> boot_tally;
     int64_t last_boot[8] = {};
-    // the open stream's stage: `boot` is set and cleared under mtx (BootScope) and read by launch_predict and pred_cols;
-    // its plan arrays (s_boot) and the stream's two tally words (s_boot_tally); boot_skip: (rows) of the reduction in
-    // progress, pixels the blanking pass owns (a replayed tile's bad pixels), or null
-    const BootStage* boot = nullptr;
+    // the open stream's stage: its plan arrays (s_boot) and the stream's two tally words (s_boot_tally)
     DevBuf<int> s_boot;
     DevBuf<unsigned long long> s_boot_tally;
-    const unsigned char* boot_skip = nullptr;
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
     // a ring of call records so that several calls of one benchmark step are summed, not only the last.
@@ -2287,8 +2290,9 @@ int run_forest(sknnr_index* ix, const void* xdev, long nq, const sknnr_query_opt
 // ----------------------------------------------------------------------------------------
 // host-buffer pipeline
 // ----------------------------------------------------------------------------------------
-static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, const double* w, long nq, int k,
-                          int mode, int law, double* out, hipStream_t st);
+// skip (a bootstrap only; else null): (nq) rows that enter no tally
+static int launch_predict(sknnr_index* ix, const Reduction& red, const double* dist, const long* idx, const double* w, long nq,
+                          int k, int mode, int law, double* out, hipStream_t st, const unsigned char* skip = nullptr);
 // n rows of a tile of the open stream into the handle's accumulators (sknnr_stream_set_tally), on `st` behind their search
 static int tally_tile(sknnr_index* ix, const double* dist, const long* idx, long n, int k, hipStream_t st);
 // what one zonal launch converts and tallies with: the zones, the tile's width, the prediction lane's conversion (scale /
@@ -2313,36 +2317,6 @@ struct DomainSpec {
 // prediction tile whose beyond rows become NaN, behind the reduction
 static int domain_tile(sknnr_index* ix, const DomainSpec& d, const double* dist, long n, int k, uint8_t* codes, double* pred,
                        int pred_cols, hipStream_t st);
-
-// The plan of the call in progress for as long as the scope lives; the caller holds ix->mtx.
-struct SummaryScope {
-    sknnr_index* ix;
-    const SummaryPlan* before;
-    SummaryScope(sknnr_index* ix_, const SummaryPlan* plan) : ix(ix_), before(ix_->summary) { ix->summary = plan; }
-    ~SummaryScope() { ix->summary = before; }
-    SummaryScope(const SummaryScope&) = delete;
-    SummaryScope& operator=(const SummaryScope&) = delete;
-};
-// The output plan of the call in progress, in the same way.
-struct PlanScope {
-    sknnr_index* ix;
-    const OutputPlan* before;
-    PlanScope(sknnr_index* ix_, const OutputPlan* plan) : ix(ix_), before(ix_->plan) { ix->plan = plan; }
-    ~PlanScope() { ix->plan = before; }
-    PlanScope(const PlanScope&) = delete;
-    PlanScope& operator=(const PlanScope&) = delete;
-};
-// The bootstrap stage of the stream tile in progress, in the same way.
-struct BootScope {
-    sknnr_index* ix;
-    const BootStage* before;
-    BootScope(sknnr_index* ix_, const BootStage* stage) : ix(ix_), before(ix_->boot) { ix->boot = stage; }
-    ~BootScope() { ix->boot = before; }
-    BootScope(const BootScope&) = delete;
-    BootScope& operator=(const BootScope&) = delete;
-};
-// Columns of a prediction row of the call in progress: the bootstrap's or the plan's entries, or the t targets.
-static inline int pred_cols(const sknnr_index* ix) { return ix->boot ? ix->boot->n_out : ix->plan ? ix->plan->n_out : ix->t; }
 
 namespace {
 
@@ -2394,9 +2368,10 @@ int mask_compact(MaskBufs& m, const void* x, long n, size_t row_bytes, hipStream
 // expanded.  o->row_offset counts the valid rows in front of the tile.  d_pred: also predict; d_dist / d_idx may be null.
 // tally (a stream's tile; d_dist is given): the valid rows' neighbours are tallied where the search wrote them -- the whole
 // tile in place, or the packed rows -- never the expanded ones: a caller's fill_index need not be negative.
-int mask_finish(sknnr_index* ix, MaskBufs& m, const void* x, long n, long nv, const sknnr_query_opts* o, long fill_index,
-                double* d_dist, long* d_idx, double* d_pred, long valid_so_far, hipStream_t st, bool tally = false) {
-    const int k = o->n_neighbors, t = pred_cols(ix);  // (the prediction rows' width: the plan's entries, or the targets)
+int mask_finish(sknnr_index* ix, const Reduction& red, MaskBufs& m, const void* x, long n, long nv, const sknnr_query_opts* o,
+                long fill_index, double* d_dist, long* d_idx, double* d_pred, long valid_so_far, hipStream_t st,
+                bool tally = false) {
+    const int k = o->n_neighbors, t = red.cols(ix->t);  // (the prediction rows' width: the plan's entries, or the targets)
     const size_t row_bytes = (size_t)query_cols(ix, o) * dtype_bytes(o->query_dtype);
     int rc;
     if (nv == n) {
@@ -2404,14 +2379,14 @@ int mask_finish(sknnr_index* ix, MaskBufs& m, const void* x, long n, long nv, co
         long* di = d_idx ? d_idx : m.ci.p;
         if ((rc = run_device(ix, x, n, o, dd, di, st))) return rc;
         if (tally && (rc = tally_tile(ix, dd, di, n, k, st))) return rc;
-        if (d_pred && (rc = launch_predict(ix, dd, di, nullptr, n, k, o->weight_mode, o->weight_law, d_pred, st))) return rc;
+        if (d_pred && (rc = launch_predict(ix, red, dd, di, nullptr, n, k, o->weight_mode, o->weight_law, d_pred, st))) return rc;
     } else {
         ExpandArgs e{};
         if (nv > 0) {
             double* cd = (d_dist || d_pred) ? m.cd.p : nullptr;
             if ((rc = run_device(ix, m.cx.p, nv, o, cd, m.ci.p, st))) return rc;
             if (tally && (rc = tally_tile(ix, cd, m.ci.p, nv, k, st))) return rc;
-            if (d_pred && (rc = launch_predict(ix, cd, m.ci.p, nullptr, nv, k, o->weight_mode, o->weight_law, m.cp.p, st))) return rc;
+            if (d_pred && (rc = launch_predict(ix, red, cd, m.ci.p, nullptr, nv, k, o->weight_mode, o->weight_law, m.cp.p, st))) return rc;
             e.valid = m.valid.p;
             e.rank = m.rank.p;
             e.c_idx = m.ci.p;
@@ -2437,14 +2412,15 @@ int mask_finish(sknnr_index* ix, MaskBufs& m, const void* x, long n, long nv, co
 }
 
 // A masked device-memory call: mask, one 8-byte read of the valid count (synchronises `st`), then the search.
-int run_device_masked(sknnr_index* ix, const void* q, long nq, const sknnr_query_opts* o, const double* nodata,
-                      long fill_index, double* d_dist, long* d_idx, double* d_pred, hipStream_t st, int64_t* out_n_valid) {
+int run_device_masked(sknnr_index* ix, const Reduction& red, const void* q, long nq, const sknnr_query_opts* o,
+                      const double* nodata, long fill_index, double* d_dist, long* d_idx, double* d_pred, hipStream_t st,
+                      int64_t* out_n_valid) {
     const int d_x = query_cols(ix, o);
     const size_t row_bytes = (size_t)d_x * dtype_bytes(o->query_dtype);
     if (nq > 0x7fffffffL) return fail(SKNNR_ERR_UNSUPPORTED, "more than 2^31 - 1 query rows in one call");
     if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));  // the mask buffers belong to the workspace
     MaskBufs& m = ix->mask;
-    int rc = mask_ensure(m, nq, row_bytes, o->n_neighbors, pred_cols(ix), d_dist != nullptr, d_pred != nullptr);
+    int rc = mask_ensure(m, nq, row_bytes, o->n_neighbors, red.cols(ix->t), d_dist != nullptr, d_pred != nullptr);
     if (rc) return rc;
     HIP_TRY(ix->m_nodata.ensure((size_t)d_x));
     HIP_TRY(hipMemcpyAsync(ix->m_nodata.p, nodata, (size_t)d_x * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2453,7 +2429,7 @@ int run_device_masked(sknnr_index* ix, const void* q, long nq, const sknnr_query
     const long nv = *m.pin_nv;
     if (nv > 0 && nv < nq && (rc = mask_compact(m, q, nq, row_bytes, st))) return rc;
     if (out_n_valid) *out_n_valid = nv;
-    return mask_finish(ix, m, q, nq, nv, o, fill_index, d_dist, d_idx, d_pred, 0, st);
+    return mask_finish(ix, red, m, q, nq, nv, o, fill_index, d_dist, d_idx, d_pred, 0, st);
 }
 
 }  // namespace
@@ -2628,16 +2604,10 @@ struct HostPipe {
     const double* nodata_dev = nullptr;  // (d_x) on the device, or null: no mask
     long fill_index = -1;
     long row_offset0 = 0;                // o.row_offset when the pipeline was opened
-    // per-target statistics (sknnr_stream_set_statistics): the reductions of this pipeline's tiles follow `stat`
-    bool has_stat = false, stat_set = false;  // (stat_set: the call was made, even with an all-mean table)
-    SummaryPlan stat;
-    // output plan (sknnr_stream_set_plan): the prediction lane is plan.n_out wide and the reductions follow `plan`
-    bool has_plan = false;
-    OutputPlan plan;
-    // bootstrap (sknnr_stream_set_bootstrap): the reduction stage is the bootstrap of `boot`; the search (or the stored
-    // lists) has k = kw columns, the prediction lane boot.n_out
-    bool has_boot = false;
-    BootStage boot;
+    // The reduction of this pipeline's tiles: a one-shot call's, or what sknnr_stream_set_statistics, _set_plan or
+    // _set_bootstrap installed (a stream takes one of the three).  The prediction lane is red.cols(t) wide.  With a
+    // bootstrap the search (or the stored lists) has k = kw columns.
+    Reduction red;
     struct Pending {
         bool live = false;
         long n = 0;
@@ -2671,17 +2641,18 @@ bool pipe_workers() {
     return v;
 }
 
-int pipe_open(HostPipe& p, sknnr_index* ix, const sknnr_query_opts* o, bool want_dist, bool want_pred) {
+int pipe_open(HostPipe& p, sknnr_index* ix, const sknnr_query_opts* o, const Reduction& red, bool want_dist, bool want_pred) {
     p = HostPipe{};
     p.ix = ix;
     p.o = *o;
     p.k = o->n_neighbors;
     p.t = ix->t;
+    p.red = red;
     // The indices are always wanted (so their pinned buffer is sized even for pushes that leave them out), and the search
     // writes indices and distances whether or not the distances leave.
     p.lane[kLaneIdx] = {true, true, p.k, kNarrowIndex};  // (want, search_out, cols, kind)
     p.lane[kLaneDist] = {want_dist, true, p.k, kNarrowValue};
-    p.lane[kLanePred] = {want_pred, false, pred_cols(ix), kNarrowValue};  // (a one-shot call's plan is already in place)
+    p.lane[kLanePred] = {want_pred, false, red.cols(ix->t), kNarrowValue};
     p.mask_dist = want_dist || want_pred;
     p.d_x = query_cols(ix, o);
     p.x_esz = (size_t)dtype_bytes(o->query_dtype);
@@ -2835,7 +2806,7 @@ int pipe_enqueue_d2h(HostPipe& p) {
 // The replayed tile of slot b on st_run, where a search tile has its search, tally and reduction: the decode of the
 // uploaded stored neighbours into d_idx (n, k) / d_dist (n, k; null without stored distances); with d_pred the reduction
 // on the provisional tile and the blanking pass behind it (replay.hip.h); then the tally, on the tile's final state, whose
-// negative indices it skips.  The caller holds the stream's SummaryScope / PlanScope.
+// negative indices it skips.
 int replay_tile(HostPipe& p, int b, long n, bool planes, long* d_idx, double* d_dist, double* d_pred) {
     sknnr_index* ix = p.ix;
     auto& sl = ix->slot[b];
@@ -2863,9 +2834,8 @@ int replay_tile(HostPipe& p, int b, long n, bool planes, long* d_idx, double* d_
     HIP_TRY(launch::replay(a, r.idx_bytes, r.dist_kind, planes, st));
     int rc;
     if (d_pred) {
-        ix->boot_skip = sl.mask.valid.p;  // (a bootstrap stage: the provisional rows of bad pixels enter no tally)
-        rc = launch_predict(ix, d_dist, d_idx, nullptr, n, p.k, p.o.weight_mode, p.o.weight_law, d_pred, st);
-        ix->boot_skip = nullptr;
+        // (the skip flags -- a bootstrap stage: the provisional rows of bad pixels enter no tally)
+        rc = launch_predict(ix, p.red, d_dist, d_idx, nullptr, n, p.k, p.o.weight_mode, p.o.weight_law, d_pred, st, sl.mask.valid.p);
         if (rc) return rc;
         const ReplayBlankArgs ba{sl.mask.valid.p, n, p.k, p.lane[kLanePred].cols, d_idx, d_dist, d_pred};
         HIP_TRY(launch::replay_blank(ba, st));
@@ -2938,9 +2908,6 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     // the PREVIOUS tile's results travel behind this tile's rows, on the same stream (see pipe_enqueue_d2h)
     if ((rc = pipe_enqueue_d2h(p))) return rc;
     HIP_TRY(hipStreamWaitEvent(ix->st_run, sl.ev_h2d, 0));
-    SummaryScope scope(ix, p.has_stat ? &p.stat : ix->summary);  // (a one-shot call's plan is already in place)
-    PlanScope plan_scope(ix, p.has_plan ? &p.plan : ix->plan);
-    BootScope boot_scope(ix, p.has_boot ? &p.boot : nullptr);
     if (p.replay.on) {
         // stored neighbours: the decode leaves the tile as a search and its nodata expansion would; nothing of the search runs
         rc = replay_tile(p, b, n, planes != nullptr, idx.i64(), p.replay.dist_kind != kReplayDistNone ? dist.f64() : nullptr,
@@ -2948,7 +2915,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
         if (rc) return rc;
     } else if (p.nodata_dev) {
         // (distances only where the slot has packed distances to expand from: mask_ensure sizes them by the same rule)
-        rc = mask_finish(ix, sl.mask, sl.dev_x.p, n, nv, &p.o, p.fill_index, p.mask_dist ? dist.f64() : nullptr, idx.i64(),
+        rc = mask_finish(ix, p.red, sl.mask, sl.dev_x.p, n, nv, &p.o, p.fill_index, p.mask_dist ? dist.f64() : nullptr, idx.i64(),
                          want_pred ? pred.f64() : nullptr, p.o.row_offset - p.row_offset0, ix->st_run, p.tally);
         if (rc) return rc;
     } else {
@@ -2956,7 +2923,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
         if (rc) return rc;
         if (p.tally && (rc = tally_tile(ix, dist.f64(), idx.i64(), n, k, ix->st_run))) return rc;
         if (want_pred) {
-            rc = launch_predict(ix, dist.f64(), idx.i64(), nullptr, n, k, p.o.weight_mode, p.o.weight_law, pred.f64(), ix->st_run);
+            rc = launch_predict(ix, p.red, dist.f64(), idx.i64(), nullptr, n, k, p.o.weight_mode, p.o.weight_law, pred.f64(), ix->st_run);
             if (rc) return rc;
         }
     }
@@ -3164,12 +3131,13 @@ struct Prefault {
 };
 
 // nodata (host, one value per column of q) / fill_index / out_n_valid: the masked call; nodata == null: no mask
-int run_host_pipeline(sknnr_index* ix, const void* q, long nq, const sknnr_query_opts* o, void* out_dist, void* out_idx,
-                      void* out_pred, const double* nodata = nullptr, long fill_index = -1, int64_t* out_n_valid = nullptr) {
+int run_host_pipeline(sknnr_index* ix, const Reduction& red, const void* q, long nq, const sknnr_query_opts* o, void* out_dist,
+                      void* out_idx, void* out_pred, const double* nodata = nullptr, long fill_index = -1,
+                      int64_t* out_n_valid = nullptr) {
     if (ix->stream_open) return fail(SKNNR_ERR_INVALID, "a query stream is open on this handle: end it first");
     void* const out[kLanes] = {out_idx, out_dist, out_pred};  // (lane order)
     HostPipe p;
-    int rc = pipe_open(p, ix, o, out_dist != nullptr, out_pred != nullptr);
+    int rc = pipe_open(p, ix, o, red, out_dist != nullptr, out_pred != nullptr);
     if (!rc && nodata) {
         HIP_TRY(hipDeviceSynchronize());  // (m_nodata belongs to the workspace)
         HIP_TRY(ix->m_nodata.ensure((size_t)p.d_x));
@@ -3190,9 +3158,10 @@ int run_host_pipeline(sknnr_index* ix, const void* q, long nq, const sknnr_query
 
 // X=None (the query rows are the handle's own reference rows, already on the device): only the results
 // travel.  Runs on the default stream, chunk by chunk.
-int run_self_rows(sknnr_index* ix, long nq, const sknnr_query_opts* o, double* out_dist, long* out_idx, double* out_pred) {
+int run_self_rows(sknnr_index* ix, const Reduction& red, long nq, const sknnr_query_opts* o, double* out_dist, long* out_idx,
+                  double* out_pred) {
     hipStream_t st = nullptr;
-    const int k = o->n_neighbors, pc = pred_cols(ix);
+    const int k = o->n_neighbors, pc = red.cols(ix->t);
     for (long c0 = 0; c0 < nq; c0 += kChunkRows) {
         const long n = std::min<long>(kChunkRows, nq - c0);
         HIP_TRY(ix->dist_stage.ensure((size_t)n * k));
@@ -3203,7 +3172,7 @@ int run_self_rows(sknnr_index* ix, long nq, const sknnr_query_opts* o, double* o
         int rc = run_device(ix, nullptr, n, &oc, ix->dist_stage.p, ix->idx_stage.p, st);
         if (rc) return rc;
         if (out_pred) {
-            rc = launch_predict(ix, ix->dist_stage.p, ix->idx_stage.p, nullptr, n, k, o->weight_mode, o->weight_law, ix->pred_stage.p, st);
+            rc = launch_predict(ix, red, ix->dist_stage.p, ix->idx_stage.p, nullptr, n, k, o->weight_mode, o->weight_law, ix->pred_stage.p, st);
             if (rc) return rc;
             HIP_TRY(hipMemcpyAsync(out_pred + c0 * pc, ix->pred_stage.p, (size_t)n * pc * sizeof(double), hipMemcpyDeviceToHost, st));
         }
@@ -3272,8 +3241,8 @@ extern "C" int sknnr_kneighbors(sknnr_index* ix, const void* q, int64_t nq, cons
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
     if (mem == SKNNR_MEM_DEVICE) return run_device(ix, q, nq, o, out_dist, (long*)out_idx, (hipStream_t)stream);
-    if (q) return run_host_pipeline(ix, q, nq, o, out_dist, out_idx, nullptr);
-    return run_self_rows(ix, nq, o, out_dist, (long*)out_idx, nullptr);
+    if (q) return run_host_pipeline(ix, Reduction{}, q, nq, o, out_dist, out_idx, nullptr);  // (out_pred is null: never read)
+    return run_self_rows(ix, Reduction{}, nq, o, out_dist, (long*)out_idx, nullptr);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -3684,8 +3653,9 @@ extern "C" int sknnr_kneighbors_masked(sknnr_index* ix, const void* q, int64_t n
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
     if (mem == SKNNR_MEM_DEVICE)
-        return run_device_masked(ix, q, nq, o, nodata, fill_index, out_dist, (long*)out_idx, nullptr, (hipStream_t)stream, out_n_valid);
-    return run_host_pipeline(ix, q, nq, o, out_dist, out_idx, nullptr, nodata, fill_index, out_n_valid);
+        return run_device_masked(ix, Reduction{}, q, nq, o, nodata, fill_index, out_dist, (long*)out_idx, nullptr,
+                                 (hipStream_t)stream, out_n_valid);
+    return run_host_pipeline(ix, Reduction{}, q, nq, o, out_dist, out_idx, nullptr, nodata, fill_index, out_n_valid);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -3975,32 +3945,37 @@ extern "C" int sknnr_debug_weight_law(int32_t law, double p0, double p1, const d
     return SKNNR_OK;
 }
 
-// The table of a one-shot call into the handle's c_stat.  The buffer belongs to the workspace: the previous reduction may
-// still read it, so wait for the workspace's last user first.
-static int summary_upload(sknnr_index* ix, const std::vector<int>& tab, SummaryPlan& plan) {
-    plan.nc = (int)tab.size() / 2;
-    plan.n_mean = ix->t - plan.nc;
-    plan.tab = nullptr;
-    if (!plan.nc) return SKNNR_OK;
-    if (ix->ws_busy) HIP_TRY(hipEventSynchronize(ix->ev_ws));
-    HIP_TRY(ix->c_stat.ensure(tab.size()));
-    HIP_TRY(hipMemcpy(ix->c_stat.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
-    plan.tab = ix->c_stat.p;
-    return SKNNR_OK;
+// The fields the predict, plan and summary kernels' arguments share, and the predict kernels' two float32 flags
+template <class Args>
+static Args reduce_args(const sknnr_index* ix, const double* dist, const long* idx, const double* w, long nq, int k, int mode) {
+    Args a{};
+    a.y = ix->y64.p;
+    a.dist = dist;
+    a.idx = idx;
+    a.w = w;
+    a.nq = nq;
+    a.k = k;
+    a.t = ix->t;
+    a.mode = mode & SKNNR_WEIGHTS_BASE_MASK;
+    if constexpr (std::is_same<Args, PredictArgs>::value) {
+        a.y32 = (mode & SKNNR_WEIGHTS_F32_TARGETS) ? 1 : 0;
+        a.w32 = (mode & SKNNR_WEIGHTS_F32_WEIGHTS) ? 1 : 0;
+    }
+    return a;
 }
 
-// The reduction of one launch's rows: the predict kernels give every column its mean unless no column wants it, then the
-// summary kernel overwrites the columns of ix->summary (the call's or the stream's statistics; null: all mean).
+// The reduction `red` of one launch's rows.  Mean and per-target statistics: the predict kernels give every column its
+// mean unless no column wants it, then the summary kernel overwrites the columns of red.stat.
 //
 // law (sknnr_weight_law of the call's opts; kLawNone: nothing here changes): the weights are law(dist), written by
 // weight_law_kernel into the handle's law_w in front of the reduction, which then is the explicit one on that buffer
 // (the F32_TARGETS flag stays).  law_w belongs to the workspace: `st` first waits for the workspace's last user.
-static int launch_bootstrap_stage(sknnr_index* ix, const double* dist, const long* idx, long nq, int kw, int mode, int law,
-                                  double* out, hipStream_t st);
-static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, const double* w, long nq, int k,
-                          int mode, int law, double* out, hipStream_t st) {
-    if (ix->boot)  // (a stream with a bootstrap stage: the k columns are the kw candidates, and nothing below runs)
-        return launch_bootstrap_stage(ix, dist, idx, nq, k, mode, law, out, st);
+static int launch_bootstrap(sknnr_index* ix, const Reduction& red, const double* dist, const long* idx, long nq, int kw,
+                            int mode, int law, double* out, const unsigned char* skip, hipStream_t st);
+static int launch_predict(sknnr_index* ix, const Reduction& red, const double* dist, const long* idx, const double* w, long nq,
+                          int k, int mode, int law, double* out, hipStream_t st, const unsigned char* skip) {
+    if (red.kind == kReduceBoot)  // (the k columns are the kw candidates, and nothing below runs)
+        return launch_bootstrap(ix, red, dist, idx, nq, k, mode, law, out, skip, st);
     if (law != kLawNone) {
         if (!dist) return fail(SKNNR_ERR_INVALID, "a distance-weight law needs the distances");
         if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));
@@ -4018,37 +3993,20 @@ static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, 
     }
     const int64_t law_rec[8] = {law, nq, k, law != kLawNone ? 1 : 0, 0, 0, 0, 0};
     std::copy(std::begin(law_rec), std::end(law_rec), ix->last_law);
-    if (const OutputPlan* op = ix->plan) {
+    if (red.kind == kReducePlan) {
         // An output plan: `out` is (nq, n_out).  The unchanged predict kernels give the plan's `mean` entries their values
         // through the handle's (nq, t) mean_stage -- a workspace buffer, so `st` first waits for the workspace's last user
         // -- and plan_kernel writes every entry.
+        const OutputPlan* op = &red.plan;
         const bool means = op->n_mean > 0;
         if (means) {
             if (ix->ws_busy && law == kLawNone) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));
             HIP_TRY(ix->mean_stage.ensure((size_t)nq * ix->t));
-            PredictArgs a{};
-            a.y = ix->y64.p;
-            a.dist = dist;
-            a.idx = idx;
-            a.w = w;
-            a.nq = nq;
-            a.k = k;
-            a.t = ix->t;
-            a.mode = mode & SKNNR_WEIGHTS_BASE_MASK;
-            a.y32 = (mode & SKNNR_WEIGHTS_F32_TARGETS) ? 1 : 0;
-            a.w32 = (mode & SKNNR_WEIGHTS_F32_WEIGHTS) ? 1 : 0;
+            PredictArgs a = reduce_args<PredictArgs>(ix, dist, idx, w, nq, k, mode);
             a.out = ix->mean_stage.p;
             HIP_TRY(launch::predict(a, st));
         }
-        PlanArgs a{};
-        a.y = ix->y64.p;
-        a.dist = dist;
-        a.idx = idx;
-        a.w = w;
-        a.nq = nq;
-        a.k = k;
-        a.t = ix->t;
-        a.mode = mode & SKNNR_WEIGHTS_BASE_MASK;
+        PlanArgs a = reduce_args<PlanArgs>(ix, dist, idx, w, nq, k, mode);
         a.cols = op->cols;
         a.codes = op->codes;
         a.param = op->param;
@@ -4065,34 +4023,16 @@ static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, 
         return SKNNR_OK;
     }
     std::fill(std::begin(ix->last_plan), std::end(ix->last_plan), 0);  // (host record only: no plan kernel in this reduction)
-    const SummaryPlan* sp = ix->summary;
+    const SummaryPlan* sp = red.kind == kReduceStats ? &red.stat : nullptr;  // (null: all mean)
     const bool means = !sp || sp->n_mean > 0;
     if (means) {
-        PredictArgs a{};
-        a.y = ix->y64.p;
-        a.dist = dist;
-        a.idx = idx;
-        a.w = w;
-        a.nq = nq;
-        a.k = k;
-        a.t = ix->t;
-        a.mode = mode & SKNNR_WEIGHTS_BASE_MASK;
-        a.y32 = (mode & SKNNR_WEIGHTS_F32_TARGETS) ? 1 : 0;
-        a.w32 = (mode & SKNNR_WEIGHTS_F32_WEIGHTS) ? 1 : 0;
+        PredictArgs a = reduce_args<PredictArgs>(ix, dist, idx, w, nq, k, mode);
         a.out = out;
         HIP_TRY(launch::predict(a, st));
     }
     const int nc = sp ? sp->nc : 0;
     if (nc) {
-        SummaryArgs a{};
-        a.y = ix->y64.p;
-        a.dist = dist;
-        a.idx = idx;
-        a.w = w;
-        a.nq = nq;
-        a.k = k;
-        a.t = ix->t;
-        a.mode = mode & SKNNR_WEIGHTS_BASE_MASK;
+        SummaryArgs a = reduce_args<SummaryArgs>(ix, dist, idx, w, nq, k, mode);
         a.tab = sp->tab;
         a.nc = nc;
         a.out = out;
@@ -4107,73 +4047,77 @@ static int launch_predict(sknnr_index* ix, const double* dist, const long* idx, 
     return SKNNR_OK;
 }
 
-// A summary entry's statistics, checked before any device work: stat must be given and hold sknnr_statistic codes.
-static int summary_check(const sknnr_index* ix, const int32_t* stat, std::vector<int>& tab) {
-    if (!stat) return fail(SKNNR_ERR_INVALID, "stat is NULL");
-    int bad = 0;
-    if (!summary_table(stat, ix->t, tab, &bad))
-        return fail(SKNNR_ERR_INVALID, "stat[%d] = %d is no sknnr_statistic", bad, stat[bad]);
-    return SKNNR_OK;
-}
-
-// An output plan as a caller hands it over (host arrays of n_out entries), checked before any device work.
-struct PlanSpec {
-    const int32_t* cols;
-    const int32_t* stat;
-    const double* param;
-    int32_t n_out;
+// The reduction as a caller hands it over: the kind and the host arrays that belong to it -- (t) codes in `stat` for
+// per-target statistics; `cols` / `stat` / `param` of n_out entries for an output plan.
+struct ReduceSpec {
+    int kind = kReduceMean;
+    const int32_t* stat = nullptr;
+    const int32_t* cols = nullptr;
+    const double* param = nullptr;
+    int32_t n_out = 0;
+    std::vector<int> tab;  // reduce_check leaves the host image of a statistics table here
 };
-static int plan_check(const sknnr_index* ix, const PlanSpec& ps, int* n_mean) {
-    if (!ps.cols || !ps.stat || !ps.param) return fail(SKNNR_ERR_INVALID, "cols / stat / param is NULL");
-    if (ps.n_out < 1 || ps.n_out > kPlanMaxOut)
-        return fail(SKNNR_ERR_INVALID, "n_out = %d outside [1, %d]", ps.n_out, kPlanMaxOut);
-    *n_mean = 0;
-    for (int e = 0; e < ps.n_out; ++e) {
-        if (ps.cols[e] < 0 || ps.cols[e] >= ix->t)
-            return fail(SKNNR_ERR_INVALID, "cols[%d] = %d: the handle has %d targets", e, ps.cols[e], ix->t);
-        if (ps.stat[e] < 0 || ps.stat[e] >= kPlanStatCount)
-            return fail(SKNNR_ERR_INVALID, "stat[%d] = %d is no sknnr_statistic", e, ps.stat[e]);
-        if (ps.stat[e] == kStatQuantile && !(ps.param[e] >= 0.0 && ps.param[e] <= 1.0))
-            return fail(SKNNR_ERR_INVALID, "param[%d] = %g: a quantile's q lies in [0, 1]", e, ps.param[e]);
-        if (ps.stat[e] == kStatMean) ++*n_mean;
+// The spec checked before any device work; red: its kind and counts, the device pointers still null (reduce_upload).
+static int reduce_check(const sknnr_index* ix, ReduceSpec& rs, Reduction& red) {
+    red = Reduction{};
+    red.kind = rs.kind;
+    if (rs.kind == kReduceStats) {  // stat must be given and hold sknnr_statistic codes
+        if (!rs.stat) return fail(SKNNR_ERR_INVALID, "stat is NULL");
+        int bad = 0;
+        if (!summary_table(rs.stat, ix->t, rs.tab, &bad))
+            return fail(SKNNR_ERR_INVALID, "stat[%d] = %d is no sknnr_statistic", bad, rs.stat[bad]);
+        red.stat.nc = (int)rs.tab.size() / 2;
+        red.stat.n_mean = ix->t - red.stat.nc;
+    } else if (rs.kind == kReducePlan) {
+        if (!rs.cols || !rs.stat || !rs.param) return fail(SKNNR_ERR_INVALID, "cols / stat / param is NULL");
+        if (rs.n_out < 1 || rs.n_out > kPlanMaxOut)
+            return fail(SKNNR_ERR_INVALID, "n_out = %d outside [1, %d]", rs.n_out, kPlanMaxOut);
+        for (int e = 0; e < rs.n_out; ++e) {
+            if (rs.cols[e] < 0 || rs.cols[e] >= ix->t)
+                return fail(SKNNR_ERR_INVALID, "cols[%d] = %d: the handle has %d targets", e, rs.cols[e], ix->t);
+            if (rs.stat[e] < 0 || rs.stat[e] >= kPlanStatCount)
+                return fail(SKNNR_ERR_INVALID, "stat[%d] = %d is no sknnr_statistic", e, rs.stat[e]);
+            if (rs.stat[e] == kStatQuantile && !(rs.param[e] >= 0.0 && rs.param[e] <= 1.0))
+                return fail(SKNNR_ERR_INVALID, "param[%d] = %g: a quantile's q lies in [0, 1]", e, rs.param[e]);
+            if (rs.stat[e] == kStatMean) ++red.plan.n_mean;
+        }
+        red.plan.n_out = rs.n_out;
     }
     return SKNNR_OK;
 }
-// The plan's arrays into `buf` (the handle's c_plan: a workspace buffer, so the caller has waited for the workspace's last
-// user; or the open stream's s_plan).
-static int plan_upload(DevBuf<double>& buf, const PlanSpec& ps, int n_mean, OutputPlan& plan) {
-    const std::vector<double> img = plan_image(ps.cols, ps.stat, ps.param, ps.n_out);
-    HIP_TRY(buf.ensure(img.size()));
-    HIP_TRY(hipMemcpy(buf.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
-    plan.n_out = ps.n_out;
-    plan.n_mean = n_mean;
-    plan.param = buf.p;
-    plan.cols = (const int*)(buf.p + ps.n_out);
-    plan.codes = plan.cols + ps.n_out;
+// The checked spec's table or arrays into the buffer of its kind, and red's device pointers: the open stream's s_stat /
+// s_plan, or a one-shot call's c_stat / c_plan (reduce_upload_call).  A mean, or a table that is all mean, uploads nothing.
+static int reduce_upload(const ReduceSpec& rs, DevBuf<int>& stat_buf, DevBuf<double>& plan_buf, Reduction& red) {
+    if (rs.kind == kReduceStats && red.stat.nc) {
+        HIP_TRY(stat_buf.ensure(rs.tab.size()));
+        HIP_TRY(hipMemcpy(stat_buf.p, rs.tab.data(), rs.tab.size() * sizeof(int), hipMemcpyHostToDevice));
+        red.stat.tab = stat_buf.p;
+    } else if (rs.kind == kReducePlan) {
+        const std::vector<double> img = plan_image(rs.cols, rs.stat, rs.param, rs.n_out);
+        HIP_TRY(plan_buf.ensure(img.size()));
+        HIP_TRY(hipMemcpy(plan_buf.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+        red.plan.param = plan_buf.p;
+        red.plan.cols = (const int*)(plan_buf.p + rs.n_out);
+        red.plan.codes = red.plan.cols + rs.n_out;
+    }
     return SKNNR_OK;
 }
-static int plan_upload_call(sknnr_index* ix, const PlanSpec& ps, int n_mean, OutputPlan& plan) {
-    if (ix->ws_busy) HIP_TRY(hipEventSynchronize(ix->ev_ws));
-    return plan_upload(ix->c_plan, ps, n_mean, plan);
+// A one-shot call's upload.  c_stat and c_plan belong to the workspace: the previous reduction may still read them, so
+// wait for the workspace's last user first.
+static int reduce_upload_call(sknnr_index* ix, const ReduceSpec& rs, Reduction& red) {
+    const bool uploads = rs.kind == kReducePlan || (rs.kind == kReduceStats && red.stat.nc);
+    if (uploads && ix->ws_busy) HIP_TRY(hipEventSynchronize(ix->ev_ws));
+    return reduce_upload(rs, ix->c_stat, ix->c_plan, red);
 }
 
-// sknnr_predict_from_neighbors (summarize false, ps null), sknnr_summarize_from_neighbors (summarize) and
-// sknnr_summarize_plan_from_neighbors (ps: out_pred is (nq, n_out))
+// sknnr_predict_from_neighbors (a mean), sknnr_summarize_from_neighbors (per-target statistics) and
+// sknnr_summarize_plan_from_neighbors (an output plan: out_pred is (nq, n_out))
 static int reduce_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w, int64_t nq,
-                                 int32_t k, int32_t mode, bool summarize, const int32_t* stat, const PlanSpec* ps,
-                                 double* out_pred, int32_t mem, void* stream) {
+                                 int32_t k, int32_t mode, ReduceSpec rs, double* out_pred, int32_t mem, void* stream) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
     if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
-    std::vector<int> tab;
-    if (summarize) {
-        const int rc = summary_check(ix, stat, tab);
-        if (rc) return rc;
-    }
-    int n_mean = 0;
-    if (ps) {
-        const int rc = plan_check(ix, *ps, &n_mean);
-        if (rc) return rc;
-    }
+    Reduction red;
+    if (const int rc = reduce_check(ix, rs, red)) return rc;
     if (nq < 0 || k < 1 || !idx || !out_pred) return fail(SKNNR_ERR_INVALID, "bad argument");
     if (!weight_mode_ok(mode, true)) return fail(SKNNR_ERR_INVALID, "unknown weight mode %d", mode);
     if ((mode & SKNNR_WEIGHTS_BASE_MASK) == SKNNR_WEIGHTS_DISTANCE && !dist)
@@ -4186,21 +4130,10 @@ static int reduce_from_neighbors(sknnr_index* ix, const double* dist, const int6
     if (nq == 0) return SKNNR_OK;
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
-    SummaryPlan plan;
-    if (summarize) {
-        const int rc = summary_upload(ix, tab, plan);
-        if (rc) return rc;
-    }
-    SummaryScope scope(ix, summarize ? &plan : nullptr);
-    OutputPlan oplan;
-    if (ps) {
-        const int rc = plan_upload_call(ix, *ps, n_mean, oplan);
-        if (rc) return rc;
-    }
-    PlanScope plan_scope(ix, ps ? &oplan : nullptr);
-    const int pc = pred_cols(ix);
+    if (const int rc = reduce_upload_call(ix, rs, red)) return rc;
+    const int pc = red.cols(ix->t);
     if (mem == SKNNR_MEM_DEVICE)
-        return launch_predict(ix, dist, (const long*)idx, w, nq, k, mode, kLawNone, out_pred, (hipStream_t)stream);
+        return launch_predict(ix, red, dist, (const long*)idx, w, nq, k, mode, kLawNone, out_pred, (hipStream_t)stream);
     hipStream_t st = nullptr;
     DevBuf<double> dd, dw, dout;  // freed by their destructors on every return path
     DevBuf<long> di;
@@ -4215,7 +4148,7 @@ static int reduce_from_neighbors(sknnr_index* ix, const double* dist, const int6
         HIP_TRY(dw.ensure((size_t)nq * k));
         HIP_TRY(hipMemcpy(dw.p, w, (size_t)nq * k * sizeof(double), hipMemcpyHostToDevice));
     }
-    int rc = launch_predict(ix, dist ? dd.p : nullptr, di.p, w ? dw.p : nullptr, nq, k, mode, kLawNone, dout.p, st);
+    int rc = launch_predict(ix, red, dist ? dd.p : nullptr, di.p, w ? dw.p : nullptr, nq, k, mode, kLawNone, dout.p, st);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(out_pred, dout.p, (size_t)nq * pc * sizeof(double), hipMemcpyDeviceToHost));
     return SKNNR_OK;
@@ -4224,39 +4157,30 @@ static int reduce_from_neighbors(sknnr_index* ix, const double* dist, const int6
 extern "C" int sknnr_predict_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w,
                                             int64_t nq, int32_t k, int32_t mode, double* out_pred, int32_t mem,
                                             void* stream) {
-    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, false, nullptr, nullptr, out_pred, mem, stream);
+    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, ReduceSpec{}, out_pred, mem, stream);
 }
 
 extern "C" int sknnr_summarize_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w,
                                               int64_t nq, int32_t k, int32_t mode, const int32_t* stat, double* out,
                                               int32_t mem, void* stream) {
-    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, true, stat, nullptr, out, mem, stream);
+    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, ReduceSpec{kReduceStats, stat}, out, mem, stream);
 }
 
 extern "C" int sknnr_summarize_plan_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w,
                                                    int64_t nq, int32_t k, int32_t mode, const int32_t* cols,
                                                    const int32_t* stat, const double* param, int32_t n_out, double* out,
                                                    int32_t mem, void* stream) {
-    const PlanSpec ps{cols, stat, param, n_out};
-    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, false, nullptr, &ps, out, mem, stream);
+    return reduce_from_neighbors(ix, dist, idx, w, nq, k, mode, ReduceSpec{kReducePlan, stat, cols, param, n_out}, out, mem, stream);
 }
 
-// sknnr_predict (summarize false, ps null), sknnr_summarize (summarize) and sknnr_summarize_plan (ps: out_pred is (nq, n_out))
-static int search_and_reduce(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, bool summarize,
-                             const int32_t* stat, const PlanSpec* ps, double* out_pred, double* out_dist, int64_t* out_idx,
-                             int32_t mem, void* stream) {
+// sknnr_predict (a mean), sknnr_summarize (per-target statistics) and sknnr_summarize_plan (an output plan: out_pred is
+// (nq, n_out))
+static int search_and_reduce(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, ReduceSpec rs,
+                             double* out_pred, double* out_dist, int64_t* out_idx, int32_t mem, void* stream) {
     if (!ix) return fail(SKNNR_ERR_INVALID, "index is NULL");
     if (ix->t < 1) return fail(SKNNR_ERR_NO_TARGETS, "the index was created without targets");
-    std::vector<int> tab;
-    if (summarize) {
-        const int rc0 = summary_check(ix, stat, tab);
-        if (rc0) return rc0;
-    }
-    int n_mean = 0;
-    if (ps) {
-        const int rc0 = plan_check(ix, *ps, &n_mean);
-        if (rc0) return rc0;
-    }
+    Reduction red;
+    if (const int rc0 = reduce_check(ix, rs, red)) return rc0;
     if (!o) return fail(SKNNR_ERR_INVALID, "opts is NULL");
     if (!out_pred && nq > 0) return fail(SKNNR_ERR_INVALID, "out_pred is NULL");
     const int law = weight_law_check(ix, o);
@@ -4275,12 +4199,7 @@ static int search_and_reduce(sknnr_index* ix, const void* q, int64_t nq, const s
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
     const int k = o->n_neighbors;
-    SummaryPlan plan;
-    if (summarize && (rc = summary_upload(ix, tab, plan))) return rc;
-    SummaryScope scope(ix, summarize ? &plan : nullptr);
-    OutputPlan oplan;
-    if (ps && (rc = plan_upload_call(ix, *ps, n_mean, oplan))) return rc;
-    PlanScope plan_scope(ix, ps ? &oplan : nullptr);
+    if ((rc = reduce_upload_call(ix, rs, red))) return rc;
 
     if (mem == SKNNR_MEM_DEVICE) {
         hipStream_t st = (hipStream_t)stream;
@@ -4300,27 +4219,26 @@ static int search_and_reduce(sknnr_index* ix, const void* q, int64_t nq, const s
         }
         rc = run_device(ix, q, nq, o, dd, di, st);
         if (rc) return rc;
-        return launch_predict(ix, dd, di, nullptr, nq, k, o->weight_mode, o->weight_law, out_pred, st);
+        return launch_predict(ix, red, dd, di, nullptr, nq, k, o->weight_mode, o->weight_law, out_pred, st);
     }
-    if (q) return run_host_pipeline(ix, q, nq, o, out_dist, out_idx, out_pred);
-    return run_self_rows(ix, nq, o, out_dist, (long*)out_idx, out_pred);
+    if (q) return run_host_pipeline(ix, red, q, nq, o, out_dist, out_idx, out_pred);
+    return run_self_rows(ix, red, nq, o, out_dist, (long*)out_idx, out_pred);
 }
 
 extern "C" int sknnr_predict(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, double* out_pred,
                              double* out_dist, int64_t* out_idx, int32_t mem, void* stream) {
-    return search_and_reduce(ix, q, nq, o, false, nullptr, nullptr, out_pred, out_dist, out_idx, mem, stream);
+    return search_and_reduce(ix, q, nq, o, ReduceSpec{}, out_pred, out_dist, out_idx, mem, stream);
 }
 
 extern "C" int sknnr_summarize(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o, const int32_t* stat,
                                double* out, double* out_dist, int64_t* out_idx, int32_t mem, void* stream) {
-    return search_and_reduce(ix, q, nq, o, true, stat, nullptr, out, out_dist, out_idx, mem, stream);
+    return search_and_reduce(ix, q, nq, o, ReduceSpec{kReduceStats, stat}, out, out_dist, out_idx, mem, stream);
 }
 
 extern "C" int sknnr_summarize_plan(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o,
                                     const int32_t* cols, const int32_t* stat, const double* param, int32_t n_out, double* out,
                                     double* out_dist, int64_t* out_idx, int32_t mem, void* stream) {
-    const PlanSpec ps{cols, stat, param, n_out};
-    return search_and_reduce(ix, q, nq, o, false, nullptr, &ps, out, out_dist, out_idx, mem, stream);
+    return search_and_reduce(ix, q, nq, o, ReduceSpec{kReducePlan, stat, cols, param, n_out}, out, out_dist, out_idx, mem, stream);
 }
 
 extern "C" int sknnr_predict_masked(sknnr_index* ix, const void* q, int64_t nq, const sknnr_query_opts* o,
@@ -4345,8 +4263,9 @@ extern "C" int sknnr_predict_masked(sknnr_index* ix, const void* q, int64_t nq, 
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
     if (mem == SKNNR_MEM_DEVICE)
-        return run_device_masked(ix, q, nq, o, nodata, fill_index, out_dist, (long*)out_idx, out_pred, (hipStream_t)stream, out_n_valid);
-    return run_host_pipeline(ix, q, nq, o, out_dist, out_idx, out_pred, nodata, fill_index, out_n_valid);
+        return run_device_masked(ix, Reduction{}, q, nq, o, nodata, fill_index, out_dist, (long*)out_idx, out_pred,
+                                 (hipStream_t)stream, out_n_valid);
+    return run_host_pipeline(ix, Reduction{}, q, nq, o, out_dist, out_idx, out_pred, nodata, fill_index, out_n_valid);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -4381,29 +4300,31 @@ extern "C" int sknnr_stream_set_nodata(sknnr_stream* s, const double* nodata, in
     return SKNNR_OK;
 }
 
+// The stream's reduction stage refuses what a setter would add, or nothing (SKNNR_OK).  own: the kind the setter installs
+// (the same kind again replaces the stage), or kReduceMean for a setter of another stage, which only a bootstrap excludes.
+static int stage_refusal(const HostPipe& p, int own, const char* what) {
+    static const char* const has[] = {nullptr, "per-target statistics (sknnr_stream_set_statistics)",
+                                      "an output plan (sknnr_stream_set_plan)", "a bootstrap stage (sknnr_stream_set_bootstrap)"};
+    const int kind = p.red.kind;
+    if (kind == kReduceMean || kind == own || (own == kReduceMean && kind != kReduceBoot)) return SKNNR_OK;
+    return fail(SKNNR_ERR_INVALID, "the stream has %s: it takes no %s", has[kind], what);
+}
+
 extern "C" int sknnr_stream_set_statistics(sknnr_stream* s, const int32_t* stat, int32_t t) {
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     HostPipe& p = s->pipe;
     if (!p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
     if (t != p.t) return fail(SKNNR_ERR_INVALID, "t = %d: the handle has %d targets", t, p.t);
-    std::vector<int> tab;
-    int rc = summary_check(p.ix, stat, tab);
+    ReduceSpec rs{kReduceStats, stat};
+    Reduction red;
+    int rc = reduce_check(p.ix, rs, red);
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(p.ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_statistics is allowed only before the first push");
-    if (p.has_plan) return fail(SKNNR_ERR_INVALID, "the stream has an output plan (sknnr_stream_set_plan): it takes no per-target statistics");
-    if (p.has_boot) return fail(SKNNR_ERR_INVALID, "the stream has a bootstrap stage (sknnr_stream_set_bootstrap): it takes no per-target statistics");
-    p.stat_set = true;
-    p.stat = SummaryPlan{};
-    p.stat.nc = (int)tab.size() / 2;
-    p.stat.n_mean = p.t - p.stat.nc;
-    if (p.stat.nc) {
-        HIP_TRY(hipSetDevice(p.ix->device));
-        HIP_TRY(p.ix->s_stat.ensure(tab.size()));
-        HIP_TRY(hipMemcpy(p.ix->s_stat.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
-        p.stat.tab = p.ix->s_stat.p;
-    }
-    p.has_stat = p.stat.nc > 0;  // (an all-mean table: the stream enqueues what it did without one)
+    if ((rc = stage_refusal(p, kReduceStats, "per-target statistics"))) return rc;
+    HIP_TRY(hipSetDevice(p.ix->device));
+    if ((rc = reduce_upload(rs, p.ix->s_stat, p.ix->s_plan, red))) return rc;
+    p.red = red;  // (an all-mean table: the stream enqueues what it did without one, and still takes no other stage)
     return SKNNR_OK;
 }
 
@@ -4412,20 +4333,19 @@ extern "C" int sknnr_stream_set_plan(sknnr_stream* s, const int32_t* cols, const
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     HostPipe& p = s->pipe;
     if (!p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
-    const PlanSpec ps{cols, stat, param, n_out};
-    int n_mean = 0;
-    int rc = plan_check(p.ix, ps, &n_mean);
+    ReduceSpec rs{kReducePlan, stat, cols, param, n_out};
+    Reduction red;
+    int rc = reduce_check(p.ix, rs, red);
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(p.ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan is allowed only before the first push");
-    if (p.stat_set) return fail(SKNNR_ERR_INVALID, "the stream has per-target statistics (sknnr_stream_set_statistics): it takes no output plan");
-    if (p.has_boot) return fail(SKNNR_ERR_INVALID, "the stream has a bootstrap stage (sknnr_stream_set_bootstrap): it takes no output plan");
+    if ((rc = stage_refusal(p, kReducePlan, "output plan"))) return rc;
     if (p.zonal) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan comes before sknnr_stream_set_zonal: n_classes holds one value per output plane");
     if (p.lane[kLanePred].scale)
         return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan comes before sknnr_stream_set_output: the scale / offset hold one value per output plane");
     HIP_TRY(hipSetDevice(p.ix->device));
-    if ((rc = plan_upload(p.ix->s_plan, ps, n_mean, p.plan))) return rc;
-    p.has_plan = true;
+    if ((rc = reduce_upload(rs, p.ix->s_stat, p.ix->s_plan, red))) return rc;
+    p.red = red;
     p.lane[kLanePred].cols = n_out;  // from now on the prediction lane is n_out wide
     return SKNNR_OK;
 }
@@ -4595,7 +4515,7 @@ extern "C" int sknnr_stream_set_tally(sknnr_stream* s) {
         return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_tally: the replay stream was opened without stored distances, and the tally keeps their maxima");
     std::lock_guard<std::mutex> lock(ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_tally is allowed only before the first push");
-    if (p.has_boot) return fail(SKNNR_ERR_INVALID, "the stream has a bootstrap stage (sknnr_stream_set_bootstrap): it takes no usage tally");
+    if (int no = stage_refusal(p, kReduceMean, "usage tally")) return no;
     HIP_TRY(hipSetDevice(ix->device));
     const size_t n_cnt = (size_t)ix->n_ref * p.k, n_max = (size_t)ix->n_ref;
     HIP_TRY(ix->s_tally_cnt.ensure(n_cnt));
@@ -4799,7 +4719,7 @@ extern "C" int sknnr_stream_set_zonal(sknnr_stream* s, int64_t n_zones, const in
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_zonal is allowed only before the first push");
-    if (p.has_boot) return fail(SKNNR_ERR_INVALID, "the stream has a bootstrap stage (sknnr_stream_set_bootstrap): it takes no zonal statistics");
+    if (int no = stage_refusal(p, kReduceMean, "zonal statistics")) return no;
     HIP_TRY(hipSetDevice(ix->device));
     const size_t n_keys = (size_t)n_zones * c;
     HIP_TRY(ix->s_zonal_acc.ensure(n_keys * kZonalFields));
@@ -4999,7 +4919,7 @@ extern "C" int sknnr_stream_set_domain(sknnr_stream* s, const double* table, int
         return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_domain: the replay stream was opened without stored distances");
     std::lock_guard<std::mutex> lock(ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_domain is allowed only before the first push");
-    if (p.has_boot) return fail(SKNNR_ERR_INVALID, "the stream has a bootstrap stage (sknnr_stream_set_bootstrap): it takes no distance domain");
+    if (int no = stage_refusal(p, kReduceMean, "distance domain")) return no;
     HIP_TRY(hipSetDevice(ix->device));
     HIP_TRY(ix->s_dom_table.ensure((size_t)m));
     HIP_TRY(ix->s_dom_acc.ensure(kDomainAcc));
@@ -5102,7 +5022,7 @@ extern "C" int sknnr_stream_begin(sknnr_index* ix, const sknnr_query_opts* o, in
     HIP_TRY(hipSetDevice(ix->device));
     sknnr_stream* s = new (std::nothrow) sknnr_stream();
     if (!s) return fail(SKNNR_ERR_INVALID, "out of host memory");
-    rc = pipe_open(s->pipe, ix, o, want_dist != 0, want_pred != 0);
+    rc = pipe_open(s->pipe, ix, o, Reduction{}, want_dist != 0, want_pred != 0);
     if (rc) {
         delete s;
         return rc;
@@ -5321,7 +5241,7 @@ extern "C" int sknnr_replay_begin(sknnr_index* ix, int32_t k, int32_t ks, int32_
         HIP_TRY(hipHostMalloc((void**)&ix->pin_replay, (size_t)kHostSlots * kReplayRecWords * sizeof(unsigned long long), hipHostMallocDefault));
     sknnr_stream* s = new (std::nothrow) sknnr_stream();
     if (!s) return fail(SKNNR_ERR_INVALID, "out of host memory");
-    const int rc = pipe_open(s->pipe, ix, &o, want_dist != 0, want_pred != 0);
+    const int rc = pipe_open(s->pipe, ix, &o, Reduction{}, want_dist != 0, want_pred != 0);
     if (rc) {
         delete s;
         return rc;
@@ -5514,31 +5434,43 @@ static std::vector<int> boot_plan_image(const BootPlan& bp) {
     return img;
 }
 
-// A one-shot reduction: uploads the plan, zeroes the two tally words and launches; dist / idx / out are device memory.
-static int launch_bootstrap(sknnr_index* ix, const double* dist, const long* idx, long nq, int kw, int k, int mode, int law,
-                            const BootPlan& bp, double* out, unsigned long long* tally, hipStream_t st) {
+// The plan's arrays into `buf` (a one-shot call's c_boot, or the open stream's s_boot) and the bootstrap of replicates of
+// k copies over them; the caller names the tally words.
+static int boot_upload(DevBuf<int>& buf, const BootPlan& bp, int k, Reduction& red) {
     const std::vector<int> img = boot_plan_image(bp);
-    if (ix->ws_busy) HIP_TRY(hipEventSynchronize(ix->ev_ws));
-    HIP_TRY(ix->c_boot.ensure(img.size()));
-    HIP_TRY(hipMemcpy(ix->c_boot.p, img.data(), img.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(tally, 0, 2 * sizeof(unsigned long long), st));
-    const int rc = enqueue_bootstrap(ix, dist, idx, nq, kw, k, mode, law, ix->c_boot.p, (int)bp.ucols.size(),
-                                     (int)bp.codes.size(), out, tally, nullptr, st);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(ix->ev_ws, st));
-    ix->ws_busy = true;
+    HIP_TRY(buf.ensure(img.size()));
+    HIP_TRY(hipMemcpy(buf.p, img.data(), img.size() * sizeof(int), hipMemcpyHostToDevice));
+    red = Reduction{};
+    red.kind = kReduceBoot;
+    red.boot.n_out = (int)bp.codes.size();
+    red.boot.n_u = (int)bp.ucols.size();
+    red.boot.k = k;
+    red.boot.ucols = buf.p;
+    red.boot.uidx = red.boot.ucols + red.boot.n_u;
+    red.boot.codes = red.boot.uidx + red.boot.n_out;
     return SKNNR_OK;
 }
 
-// The reduction stage of a tile of the open stream whose stage is ix->boot (launch_predict): the stream's tallies are
-// added to; always float64, whatever flags the stream's weight mode carries.
-static int launch_bootstrap_stage(sknnr_index* ix, const double* dist, const long* idx, long nq, int kw, int mode, int law,
-                                  double* out, hipStream_t st) {
-    const BootStage& b = *ix->boot;
+// A one-shot reduction: uploads the plan, zeroes the two tally words and launches; dist / idx / out are device memory.
+static int bootstrap_call(sknnr_index* ix, const double* dist, const long* idx, long nq, int kw, int k, int mode, int law,
+                          const BootPlan& bp, double* out, unsigned long long* tally, hipStream_t st) {
+    if (ix->ws_busy) HIP_TRY(hipEventSynchronize(ix->ev_ws));
+    Reduction red;
+    const int rc = boot_upload(ix->c_boot, bp, k, red);
+    if (rc) return rc;
+    red.boot_tally = tally;
+    HIP_TRY(hipMemsetAsync(tally, 0, 2 * sizeof(unsigned long long), st));
+    return launch_bootstrap(ix, red, dist, idx, nq, kw, mode, law, out, nullptr, st);
+}
+
+// The bootstrap `red` of one launch's rows (launch_predict; a one-shot call comes here directly): red.boot_tally is added
+// to; always float64, whatever flags the weight mode carries.  skip (or null): rows that enter no tally.
+static int launch_bootstrap(sknnr_index* ix, const Reduction& red, const double* dist, const long* idx, long nq, int kw,
+                            int mode, int law, double* out, const unsigned char* skip, hipStream_t st) {
+    const BootStage& b = red.boot;
     const int base = law != kLawNone ? SKNNR_WEIGHTS_EXPLICIT : (mode & SKNNR_WEIGHTS_BASE_MASK);
     if (base != SKNNR_WEIGHTS_UNIFORM && !dist) return fail(SKNNR_ERR_INVALID, "these weights need the distances");
-    const int rc = enqueue_bootstrap(ix, dist, idx, nq, kw, b.k, base, law, b.ucols, b.n_u, b.n_out, out, ix->s_boot_tally.p,
-                                     ix->boot_skip, st);
+    const int rc = enqueue_bootstrap(ix, dist, idx, nq, kw, b.k, base, law, b.ucols, b.n_u, b.n_out, out, red.boot_tally, skip, st);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(ix->ev_ws, st));
     ix->ws_busy = true;
@@ -5568,7 +5500,7 @@ extern "C" int sknnr_bootstrap_from_neighbors(sknnr_index* ix, const double* dis
             HIP_TRY(ix->boot_tally.ensure(2));
             dt = ix->boot_tally.p;
         }
-        return launch_bootstrap(ix, dist, (const long*)idx, nq, kw, k, weight_mode, weight_law, bp, out, dt, st);
+        return bootstrap_call(ix, dist, (const long*)idx, nq, kw, k, weight_mode, weight_law, bp, out, dt, st);
     }
     DevBuf<double> dd, dout;  // freed by their destructors on every return path
     DevBuf<long> di;
@@ -5581,7 +5513,7 @@ extern "C" int sknnr_bootstrap_from_neighbors(sknnr_index* ix, const double* dis
         HIP_TRY(dd.ensure((size_t)nq * kw));
         HIP_TRY(hipMemcpy(dd.p, dist, (size_t)nq * kw * sizeof(double), hipMemcpyHostToDevice));
     }
-    rc = launch_bootstrap(ix, dd.p, di.p, nq, kw, k, weight_mode, weight_law, bp, dout.p, dt.p, nullptr);
+    rc = bootstrap_call(ix, dd.p, di.p, nq, kw, k, weight_mode, weight_law, bp, dout.p, dt.p, nullptr);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(out, dout.p, (size_t)nq * n_out * sizeof(double), hipMemcpyDeviceToHost));
     if (tally) HIP_TRY(hipMemcpy(tally, dt.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -5599,27 +5531,19 @@ extern "C" int sknnr_stream_set_bootstrap(sknnr_stream* s, int32_t k, const int3
     if ((rc = boot_plan_check(ix, cols, stat, n_out, bp))) return rc;
     std::lock_guard<std::mutex> lock(ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_bootstrap is allowed only before the first push");
-    if (p.stat_set) return fail(SKNNR_ERR_INVALID, "the stream has per-target statistics (sknnr_stream_set_statistics): it takes no bootstrap");
-    if (p.has_plan) return fail(SKNNR_ERR_INVALID, "the stream has an output plan (sknnr_stream_set_plan): it takes no bootstrap");
+    if ((rc = stage_refusal(p, kReduceBoot, "bootstrap"))) return rc;
     if (p.tally) return fail(SKNNR_ERR_INVALID, "the stream tallies neighbour usage (sknnr_stream_set_tally): it takes no bootstrap");
     if (p.domain) return fail(SKNNR_ERR_INVALID, "the stream has a distance domain (sknnr_stream_set_domain): it takes no bootstrap");
     if (p.zonal) return fail(SKNNR_ERR_INVALID, "the stream has zonal statistics (sknnr_stream_set_zonal): it takes no bootstrap");
     if (p.lane[kLanePred].scale)
         return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_bootstrap comes before sknnr_stream_set_output: the scale / offset hold one value per output plane");
     HIP_TRY(hipSetDevice(ix->device));
-    const std::vector<int> img = boot_plan_image(bp);
-    HIP_TRY(ix->s_boot.ensure(img.size()));
-    HIP_TRY(hipMemcpy(ix->s_boot.p, img.data(), img.size() * sizeof(int), hipMemcpyHostToDevice));
+    Reduction red;
+    if ((rc = boot_upload(ix->s_boot, bp, k, red))) return rc;
     HIP_TRY(ix->s_boot_tally.ensure(2));
     HIP_TRY(hipMemsetAsync(ix->s_boot_tally.p, 0, 2 * sizeof(unsigned long long), ix->st_run));  // (in front of the first tile)
-    p.boot = BootStage{};
-    p.boot.n_out = n_out;
-    p.boot.n_u = (int)bp.ucols.size();
-    p.boot.k = k;
-    p.boot.ucols = ix->s_boot.p;
-    p.boot.uidx = p.boot.ucols + p.boot.n_u;
-    p.boot.codes = p.boot.uidx + n_out;
-    p.has_boot = true;
+    red.boot_tally = ix->s_boot_tally.p;
+    p.red = red;
     p.lane[kLanePred].cols = n_out;  // from now on the prediction lane is n_out wide
     return SKNNR_OK;
 }
@@ -5628,7 +5552,7 @@ extern "C" int sknnr_stream_get_bootstrap(sknnr_stream* s, int64_t tally[2]) {
     if (!s || !tally) return fail(SKNNR_ERR_INVALID, "sknnr_stream_get_bootstrap: NULL argument");
     HostPipe& p = s->pipe;
     sknnr_index* ix = p.ix;
-    if (!p.has_boot) return fail(SKNNR_ERR_INVALID, "the stream has no bootstrap stage: sknnr_stream_set_bootstrap was not called");
+    if (p.red.kind != kReduceBoot) return fail(SKNNR_ERR_INVALID, "the stream has no bootstrap stage: sknnr_stream_set_bootstrap was not called");
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
     const int rc = pipe_flush(p);

@@ -19,6 +19,9 @@ against column j of the existing ``summarize_from_neighbors`` with that statisti
 that the predict kernels ran exactly when the plan holds a mean); and that the host-memory call gives the same bits as the
 device-memory one.
 
+One more test runs reductions of every kind one after another on one handle (searches on a small handle of its own): each
+gives the bits it gives alone on a fresh handle, so a handle carries nothing from one call's reduction into the next.
+
 Without the feature every test here fails with ``AttributeError`` (``Index`` has no ``summarize_plan_from_neighbors_device``)."""
 
 from __future__ import annotations
@@ -172,6 +175,72 @@ def test_plan_kernels(index, nq, k, weights, n):
     ix.summarize_from_neighbors_device(*ptrs, mode, np.full(T, NS.CODES["max"], dtype=np.int32), out.data_ptr(), stream)
     torch.cuda.synchronize()
     assert ix.debug_last_plan()["ran"] == 0 and ix.debug_last_summary()["path"] == (1 if k <= 8 else 2)
+
+
+def test_a_handle_carries_no_reduction_into_the_next_call():
+    """Seven calls of different reductions on ONE handle -- a plan, a mean, a statistics table, three masked means (no row,
+    a third of the rows, every row holding nodata), a stream with an all-mean table, a bootstrap stream, a mean again --
+    give, call by call, the bits of the same call on a fresh handle; the two plain means are equal and leave no plan record."""
+    from sknnr_amd import _native
+
+    n_ref, d, t, k, nq, B, kw = 300, 8, 3, 5, 257, 8, 8
+    rng = np.random.default_rng(2024)
+    ref, y, q = rng.standard_normal((n_ref, d)), rng.standard_normal((n_ref, t)), rng.standard_normal((nq, d))
+    table = np.stack([np.bincount(rng.integers(0, n_ref, n_ref), minlength=n_ref) for _ in range(B)]).astype(np.uint8)
+    nodata = np.full(d, -9999.0)
+    third, every = q.copy(), q.copy()
+    third[rng.permutation(nq)[: nq // 3], rng.integers(0, d, nq // 3)] = -9999.0
+    every[np.arange(nq), rng.integers(0, d, nq)] = -9999.0
+    plan = OP.arrays([(1, ("quantile", 0.25)), (0, "max"), (1, "mean"), (1, "median")])
+    mixed = np.array([NS.CODES["max"], NS.CODES["mean"], NS.CODES["std"]], dtype=np.int32)
+    boot = (np.array([0, 2, 0], dtype=np.int32),
+            np.array([_native.BOOT_STATISTICS[s] for s in ("boot_se", "boot_mean", "boot_count")], dtype=np.int32))
+    opts, opts_kw = _native.Index.make_opts(k), _native.Index.make_opts(kw)
+
+    def plain(ix):
+        out = ix.predict_host(q, opts)
+        assert ix.debug_last_plan()["ran"] == 0
+        return [out]
+
+    def masked(ix):
+        outs = [ix.predict_masked_host(x, opts, nodata) for x in (q, third, every)]
+        assert [nv for _, nv in outs] == [nq, nq - nq // 3, 0]  # (mask_finish: in place, packed and expanded, the fill alone)
+        return [pred for pred, _ in outs]
+
+    def stream(ix):
+        with ix.open_stream(opts, want_dist=False, want_pred=True) as s:
+            s.set_statistics(np.zeros(t, dtype=np.int32))
+            outs = [s.push(x, need_idx=False)[2] for x in (q[:130], q[130:])]
+        return outs
+
+    def boot_stream(ix):
+        with ix.open_stream(opts_kw, want_dist=False, want_pred=True) as s:
+            s.set_bootstrap(k, boot)
+            outs = [s.push(q, need_idx=False)[2]]
+        return outs
+
+    steps = [lambda ix: [ix.summarize_plan_host(q, opts, plan)], plain, lambda ix: [ix.summarize_host(q, opts, mixed)],
+             masked, stream, boot_stream, plain]
+
+    def fresh():
+        ix = _native.Index(ref, y)
+        ix.set_bootstrap(table)
+        return ix
+
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint64)  # noqa: E731
+    one = fresh()
+    got = [step(one) for step in steps]
+    one.close()
+    assert got[0][0].shape == (nq, 4) and got[5][0].shape == (nq, 3) and np.isnan(got[3][2]).all()
+    assert np.isnan(got[3][1]).any(axis=1).sum() == nq // 3 and not np.isnan(got[3][0]).any()
+    for n, step in enumerate(steps):
+        ix = fresh()
+        want = step(ix)
+        ix.close()
+        assert len(want) == len(got[n])
+        for a, b in zip(got[n], want):
+            assert a.shape == b.shape and np.array_equal(bits(a), bits(b)), f"step {n + 1}"
+    assert np.array_equal(bits(got[1][0]), bits(got[6][0]))
 
 
 def test_uniform_quantile_ends_are_min_and_max(index):
