@@ -29,8 +29,8 @@ from . import _config, _native
 from ._engine import KNNEngine, default_device, is_torch_cuda_tensor
 from ._usage import NeighborUsage
 from ._domain import DistanceDomain
-from ._zonal import ZonalStats
 from ._bootstrap import MAX_CANDIDATES, Bootstrap, has_boot_names, normalize_boot_outputs
+from ._products import StreamProducts, normalize_zone_tile  # noqa: F401  (normalize_zone_tile: the zone rule, beside the tile rules)
 from .weights import DistanceWeights
 
 # Element types query rows may keep on their way to the device (include/sknnr_hip.h, sknnr_dtype): the kernel that reads
@@ -316,30 +316,30 @@ def normalize_band_tile(tile, n_bands, *, forest=False, estimator="the estimator
     return bands, int(bands[0].shape[0])
 
 
-def normalize_zone_tile(zones, n):
-    """The zone codes of one streamed tile of ``n`` pixels -- ``(n,)``, or ``(h, w)`` in the pixels' C order -- as a
-    C-contiguous int32 ``(n,)`` array.  Any integer dtype is accepted; a value outside int32 is a ``ValueError``."""
-    zones = np.asarray(zones)
-    if zones.dtype.kind not in "iu":
-        raise ValueError(f"zones must hold integer zone codes, got {zones.dtype}")
-    if zones.size != n:
-        raise ValueError(f"zones must hold one code per pixel of its tile ({n}), got {zones.size} (shape {zones.shape})")
-    if zones.dtype != np.int32 and zones.size:
-        info = np.iinfo(np.int32)
-        if zones.min() < info.min or zones.max() > info.max:
-            raise ValueError(f"zone codes must fit int32, got values in [{zones.min()}, {zones.max()}]")
-    return np.ascontiguousarray(zones, dtype=np.int32).reshape(-1)
-
-
-_ZONES_SHORT = "zones ended before tiles: the call needs one array of zone codes per tile"
-_ZONES_LONG = "tiles ended before zones: the call needs one array of zone codes per tile"
-
-
 def _empty_row_tile(tile) -> bool:
     """A row tile ``(0, n_features)``: a window that holds no pixel.  A streamed call skips it, as it skips an empty
     band-first tile, before scikit-learn's validation, which refuses arrays without rows."""
     shape = getattr(tile, "shape", None)
     return shape is not None and len(shape) == 2 and shape[0] == 0
+
+
+def _out_window(arr, row, n, cols, dtype, bands, noun):
+    """Rows ``[row, row + n)`` of a preallocated output ``arr`` (None: None) of ``cols`` columns -- with ``bands`` its
+    columns of ``cols`` planes, which stay one full row of ``arr`` apart -- refused unless C-contiguous, of ``dtype`` and
+    long enough.  ``noun``: what the refusal calls the array."""
+    if arr is None:
+        return None
+    if bands:
+        if arr.ndim != 2 or arr.shape[0] != cols or arr.dtype != dtype or not arr.flags.c_contiguous \
+                or arr.shape[1] < row + n:
+            raise ValueError(f"{noun} must be C-contiguous, {np.dtype(dtype)}, with {cols} rows and at least "
+                             f"{row + n} columns")
+        return arr[:, row:row + n]
+    w = arr[row:row + n]
+    if w.shape != (n, cols) or w.dtype != dtype or not w.flags.c_contiguous:
+        raise ValueError(f"{noun} must be C-contiguous, {np.dtype(dtype)}, with {cols} columns and at least "
+                         f"{row + n} rows")
+    return w
 
 
 def _resolve_fit_method(algorithm, n_ref, d, k):
@@ -1159,28 +1159,6 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         dist, _ = self.kneighbors(X, n_neighbors=n_neighbors)
         return self._domain_scores(domain, dist)
 
-    def _check_domain(self, domain, domain_out, k, beyond=False, host_callable=False):
-        """Every refusal of ``domain`` / ``domain_out`` / the mask, before any device work."""
-        if domain is None:
-            if domain_out is not None:
-                raise ValueError("domain_out needs domain: the DistanceDomain whose codes it receives")
-            if beyond:
-                raise ValueError("beyond='nodata' needs domain: a DistanceDomain with a threshold")
-            return
-        if not isinstance(domain, DistanceDomain):
-            raise TypeError(f"domain must be a sknnr_amd.DistanceDomain, got {type(domain).__name__}")
-        if host_callable:
-            self._refuse_callable_weights("domain is")
-        self._check_stream_supported("domain is")
-        if domain.rank > k:
-            raise ValueError(f"domain.rank={domain.rank} is above n_neighbors={k}")
-        if beyond and domain.threshold is None:
-            raise ValueError("beyond='nodata' needs a DistanceDomain with a threshold")
-        if domain_out is not None and (not isinstance(domain_out, np.ndarray) or domain_out.dtype != np.uint8
-                                       or domain_out.ndim != 1 or not domain_out.flags.c_contiguous
-                                       or not domain_out.flags.writeable):
-            raise ValueError("domain_out must be a writable C-contiguous uint8 (N_total,) array, one element per pixel")
-
     # -- streamed tiles (raster ingestion; REF docs/pages/usage.md:101-128) --------------------
     def _check_stream_supported(self, feature):
         """The nodata mask, the band-first transposes and the typed conversions (``feature``: "nodata is", "layout='bands'
@@ -1197,10 +1175,9 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                   f"the search and the reduction, {how}; use 'uniform', 'distance' or a law of "
                                   "sknnr_amd.weights (evaluated on the device)")
 
-    def _stream_tiles(self, tiles, validate, k, *, apply_affine, weights, return_distance,
+    def _stream_tiles(self, tiles, validate, k, *, products, apply_affine, weights, return_distance,
                       use_deterministic_ordering, out, owner, nodata=None, fill_index=-1, bands=False, output=None,
-                      statistic=None, id_table=None, fill_id=-1, neighbors=False, usage=None, zones=None, zonal=None,
-                      domain=None, domain_out=None, beyond=False, bootstrap=None):
+                      statistic=None, id_table=None, fill_id=-1, neighbors=False):
         """Push host tiles through one native query stream.  Returns (dist, idx, pred) arrays over all
         pushed rows (pieces of ``out`` when given, else concatenated).  ``nodata`` (float64, one value per column of the
         validated tiles): rows holding one are masked on the device and get ``fill_index`` / NaN.
@@ -1222,41 +1199,20 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         reduced from are delivered beside them, from the same stream; an output without an array in ``out`` is
         collected and concatenated.
 
-        ``usage`` (a :class:`sknnr_amd.NeighborUsage`): the stream tallies every tile's neighbours on the device and the
-        call adds the result to it; nothing else about the call changes.
-
-        ``zones`` / ``zonal`` (an iterable in lockstep with ``tiles``, a :class:`sknnr_amd.ZonalStats`; predictions with
-        an integer ``pred_dtype`` only): the stream tallies every tile's predictions by zone on the device and the call
-        adds the result to ``zonal``; nothing else about the call changes.
-
-        ``domain`` (a :class:`sknnr_amd.DistanceDomain`, checked by :meth:`_check_domain`): the stream codes every tile's
-        distances against its table on the device and the call adds the tallies to it; ``domain_out`` (uint8, one element
-        per pixel of the whole call) receives the codes tile by tile; ``beyond`` (predictions only): the predictions of
-        the pixels beyond the threshold become NaN on the device, in front of the conversion and the zonal tally.
-
-        ``bootstrap``: ``(Bootstrap, request)`` with ``request`` from :meth:`_bootstrap_request` -- ``k`` is then the number
-        of candidates searched, the stream's reduction stage is the bootstrap with replicates of ``n_neighbors`` copies, the
-        prediction lane holds the request's planes, and the call adds the stream's tallies to the ``Bootstrap``."""
-        if usage is not None:
-            self._check_stream_supported("usage is")
-            usage._check(self.n_samples_fit_, k)  # (a mismatch is refused before any device work)
-        if domain is not None:
-            self._check_domain(domain, domain_out, k)
-        zonal_binding = None
-        if zonal is not None:
-            self._check_stream_supported("zonal is")
-            plan_ = statistic if isinstance(statistic, OutputPlan) else None
-            zonal_binding = zonal._check(self._n_targets() if plan_ is None else plan_.n_out, (output or {}).get("pred_dtype"),
-                                         (output or {}).get("scale"), (output or {}).get("offset"))
-            zones = iter(zones)
+        ``products`` (a :class:`sknnr_amd._products.StreamProducts` the caller has checked): the stream computes
+        the call's side products -- usage, zonal statistics, the distance domain -- on the device beside its results and
+        the call adds them to the user's objects once it has come through whole; nothing else about the call changes.
+        With a bootstrap among them ``k`` is the number of candidates searched, the stream's reduction stage is the
+        bootstrap with replicates of ``n_neighbors`` copies, and the prediction lane holds the request's planes.  Every
+        product refuses the host-side tie policies, so the tile-by-tile branch below never sees one."""
         if output:
             self._check_stream_supported("typed outputs are")
         eng = self.engine_
         want_pred = weights is not None
         plan = statistic if isinstance(statistic, OutputPlan) else None  # (the prediction lane then has n_out columns)
         t_cols = eng.t if plan is None else plan.n_out
-        if bootstrap is not None:
-            t_cols = len(bootstrap[1][1][0])
+        if products.bootstrap is not None:
+            t_cols = len(products.request[1][0])
         output = {key: v for key, v in (output or {}).items() if v is not None}
         idx_dt = np.dtype(output.get("index_dtype", np.int64))
         dist_dt = np.dtype(output.get("distance_dtype", np.float64))
@@ -1270,6 +1226,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 raise ValueError(f"out arrays must share one number of columns (the stride between planes), got {sorted(widths)}")
         if self._reference_ties():
             # the reference's choice among tied rows is made on the host, per call: tile by tile, positions carried
+            # (no side product gets here: each of them has refused these policies)
             parts, row = [], 0
             for tile in tiles:
                 if _empty_row_tile(tile):
@@ -1309,11 +1266,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 if is_torch_cuda_tensor(tile):
                     raise TypeError("streamed tiles are host arrays (they travel through the pinned "
                                     "PCIe pipeline); pass CUDA tensors to kneighbors() / predict()")
-                if zonal is not None:  # (in lockstep: a skipped empty tile consumes its entry too)
-                    try:
-                        tile_zones = next(zones)
-                    except StopIteration:
-                        raise ValueError(_ZONES_SHORT) from None
+                products.next_tile()
                 if not bands and _empty_row_tile(tile):
                     continue
                 if bands:  # (``tile``: the list of 1-D bands; ``first`` stands for its element type)
@@ -1330,8 +1283,6 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                     stream_dtype = first.dtype if code else np.dtype(np.float64)
                     if nodata is not None:  # (a NaN entry needs rows that can hold NaN)
                         nodata = normalize_nodata(nodata, n_cols, stream_dtype)
-                    if bootstrap is not None:
-                        eng.set_bootstrap(bootstrap[1][2])
                     stream = eng.open_stream(k, weights=weights, want_dist=return_distance,
                                              deterministic=use_deterministic_ordering,
                                              decimals=self.DISTANCE_PRECISION_DECIMALS, formula=self._formula(),
@@ -1339,41 +1290,15 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                              nodata=nodata, fill_index=fill_index, output=output,
                                              **(dict(statistic=statistic) if plan is None else dict(plan=plan.arrays)),
                                              **({} if id_table is None else dict(id_table=id_table, fill_id=fill_id)),
-                                             **({} if usage is None else dict(tally=True)),
-                                             **({} if zonal is None else
-                                                dict(zonal=(zonal.n_zones, zonal.n_classes(zonal_binding[0])))),
-                                             **({} if domain is None else
-                                                dict(domain=(domain.table, domain.rank, domain.threshold, bool(beyond)))),
-                                             **({} if bootstrap is None else
-                                                dict(bootstrap=(self.n_neighbors, bootstrap[1][1]))))
+                                             **products.open_keywords(eng, self.n_neighbors))
                 if first.dtype != stream_dtype:
                     if stream_dtype != np.float64:
                         raise ValueError(f"the tiles of one streamed call must share an element type: got {first.dtype} "
                                          f"after {stream_dtype}")
                     tile = ([np.ascontiguousarray(b, dtype=np.float64) for b in tile] if bands
                             else np.ascontiguousarray(tile, dtype=np.float64))
-
-                def window(arr, cols, dtype):
-                    if arr is None:
-                        return None
-                    if bands:  # (cols planes; the window's planes stay one full row of arr apart)
-                        if arr.ndim != 2 or arr.shape[0] != cols or arr.dtype != dtype or not arr.flags.c_contiguous \
-                                or arr.shape[1] < row + n:
-                            raise ValueError(f"out arrays must be C-contiguous, {np.dtype(dtype)}, with "
-                                             f"{cols} rows and at least {row + n} columns")
-                        return arr[:, row:row + n]
-                    w = arr[row:row + n]
-                    if w.shape != (n, cols) or w.dtype != dtype or not w.flags.c_contiguous:
-                        raise ValueError(f"out arrays must be C-contiguous, {np.dtype(dtype)}, with "
-                                         f"{cols} columns and at least {row + n} rows")
-                    return w
-
-                if zonal is not None:
-                    stream.next_zones(normalize_zone_tile(tile_zones, n))
-                if domain_out is not None:
-                    if domain_out.size < row + n:
-                        raise ValueError(f"domain_out holds {domain_out.size} pixels: the tiles hold at least {row + n}")
-                    stream.next_domain_out(domain_out[row:row + n])
+                products.feed(stream, row, n)
+                window = lambda arr, cols, dtype: _out_window(arr, row, n, cols, dtype, bands, "out arrays")  # noqa: E731
                 got = (stream.push_planes if bands else stream.push)(
                     tile, out_idx=window(o_idx, k, idx_dt),
                     out_dist=window(o_dist, k, dist_dt) if return_distance else None,
@@ -1381,36 +1306,14 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                 if out is None or neighbors:
                     pieces.append(got)
                 row += n
-            if zonal is not None and next(zones, None) is not None:
-                raise ValueError(_ZONES_LONG)
-            tallied = zoned = placed = booted = None
+            products.end_of_tiles()
             if stream is not None:
                 done, stream = stream, None
                 try:
-                    if usage is not None:
-                        tallied = done.tally()
-                    if zonal is not None:
-                        zoned = done.zonal()
-                    if domain is not None:
-                        placed = done.domain()
-                    if bootstrap is not None:
-                        booted = done.bootstrap()
+                    products.collect(done)
                 finally:
                     done.close()
-            if booted is not None:  # (only a call that came through whole is added)
-                bootstrap[0]._add(booted)
-            if placed is not None:  # (only a call that came through whole is added)
-                domain._add(placed)
-            if zonal is not None:  # (only a call that came through whole is added)
-                zonal._bind(*zonal_binding)
-                if zoned is not None:
-                    zonal._add(*zoned)
-            if usage is not None:  # (only a call that came through whole is added)
-                ids = getattr(self, "dataframe_index_in_", None)
-                if tallied is None:
-                    usage._bind(self.n_samples_fit_, k, ids)
-                else:
-                    usage._add(*tallied, ids)
+            products.commit(self, k)
         except _native.HipBackendError as err:
             _reraise(err, owner if owner is not None else self)
         finally:
@@ -1510,7 +1413,8 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         k = self._resolve_k(n_neighbors)
-        self._check_domain(domain, domain_out, k)
+        products = StreamProducts(usage=usage, domain=domain, domain_out=domain_out)
+        products.check_domain(self, k)
         if nodata is not None:
             nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
         output = self._neighbor_output(index_dtype, distance_dtype, return_distance, return_dataframe_index, fill_index,
@@ -1521,13 +1425,12 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             validate = lambda t: normalize_band_tile(t, self.n_features_in_, estimator=type(self).__name__)  # noqa: E731
         # (dataframe ids: masked rows travel as -1, which no row index equals, and take fill_index in the crosswalk)
         table = self._device_id_table(return_dataframe_index)
-        dist, idx, _ = self._stream_tiles(tiles, validate, k, apply_affine=False, weights=None,
+        products.check_usage(self, k)
+        dist, idx, _ = self._stream_tiles(tiles, validate, k, products=products, apply_affine=False, weights=None,
                                           return_distance=return_distance,
                                           use_deterministic_ordering=use_deterministic_ordering, out=o, owner=None,
                                           nodata=nodata, fill_index=-1 if return_dataframe_index else fill_index,
-                                          bands=bands, output=output, id_table=table, fill_id=fill_index,
-                                          **({} if usage is None else dict(usage=usage)),
-                                          **({} if domain is None else dict(domain=domain, domain_out=domain_out)))
+                                          bands=bands, output=output, id_table=table, fill_id=fill_index)
         return self._finish_chunks(dist, idx, return_distance, return_dataframe_index,
                                    fill_index=None if nodata is None else fill_index, on_device=table is not None)
 
@@ -1668,84 +1571,55 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         ``return_neighbors`` and ``zonal`` are refused."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
+        products = StreamProducts(usage, zones, zonal, domain, domain_out, beyond, bootstrap)
         if bootstrap is not None:
-            request = self._boot_chunks_request(bootstrap, statistic, outputs, return_neighbors, return_distance,
-                                                return_dataframe_index, neighbors_out, fill_index, index_dtype, distance_dtype,
-                                                usage, zones, zonal, domain, domain_out, beyond)
-            if nodata is not None:
-                nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
-            validate = self._validate_query
-            if bands:
-                validate = lambda t: normalize_band_tile(t, self.n_features_in_, estimator=type(self).__name__)  # noqa: E731
-            return self._bootstrap_chunks(tiles, validate, bootstrap, request, apply_affine=False, out=out, owner=None,
-                                          nodata=nodata, bands=bands, typed=(out_dtype, scale, offset, out_nodata))
-        neighbors = self._neighbor_request(return_neighbors, return_distance, return_dataframe_index, neighbors_out,
-                                           fill_index, index_dtype, distance_dtype)
-        extra = {} if neighbors is None else dict(neighbors=neighbors)
-        if usage is not None:
-            extra["usage"] = usage
-        if zones is not None or zonal is not None:
-            extra.update(zones=zones, zonal=zonal)
-        if domain is not None or domain_out is not None or beyond != "keep":
-            extra.update(domain=domain, domain_out=domain_out, beyond=beyond)
-        statistic = resolve_statistic(statistic, outputs, self._n_targets())
+            products.bootstrap_request(self, statistic, outputs, return_neighbors=return_neighbors,
+                                       return_dataframe_index=return_dataframe_index, neighbors_out=neighbors_out,
+                                       index_dtype=index_dtype, distance_dtype=distance_dtype)
+        else:
+            neighbors = self._neighbor_request(return_neighbors, return_distance, return_dataframe_index, neighbors_out,
+                                               fill_index, index_dtype, distance_dtype)
+            statistic = resolve_statistic(statistic, outputs, self._n_targets())
         if nodata is not None:
             nodata = normalize_nodata(nodata, self.n_features_in_, np.float64)
         validate = self._validate_query
         if bands:
             validate = lambda t: normalize_band_tile(t, self.n_features_in_, estimator=type(self).__name__)  # noqa: E731
-        return self._predict_chunks(tiles, validate, apply_affine=False, out=out, owner=None, nodata=nodata, bands=bands,
-                                    typed=(out_dtype, scale, offset, out_nodata), statistic=statistic, **extra)
+        typed = (out_dtype, scale, offset, out_nodata)
+        if bootstrap is not None:
+            return self._bootstrap_chunks(tiles, validate, products, apply_affine=False, out=out, owner=None, nodata=nodata,
+                                          bands=bands, typed=typed)
+        return self._predict_chunks(tiles, validate, products, apply_affine=False, out=out, owner=None, nodata=nodata,
+                                    bands=bands, typed=typed, statistic=statistic, neighbors=neighbors)
 
-    def _boot_chunks_request(self, bootstrap, statistic, outputs, return_neighbors=False, return_distance=True,
-                             return_dataframe_index=False, neighbors_out=None, fill_index=-1, index_dtype=None,
-                             distance_dtype=None, usage=None, zones=None, zonal=None, domain=None, domain_out=None,
-                             beyond="keep", **kw):
-        """:meth:`_bootstrap_request` of a streamed call: its keywords that do not go with a bootstrap are refused."""
-        return self._bootstrap_request(
-            bootstrap, statistic, outputs, zonal=zonal, zones=zones, usage=usage, domain=domain, domain_out=domain_out,
-            beyond=None if beyond == "keep" else beyond, return_neighbors=bool(return_neighbors) or None,
-            return_dataframe_index=bool(return_dataframe_index) or None, neighbors_out=neighbors_out,
-            index_dtype=index_dtype, distance_dtype=distance_dtype, **kw)
-
-    def _bootstrap_chunks(self, tiles, validate, bootstrap, request, *, apply_affine, out, owner, nodata, bands, typed):
+    def _bootstrap_chunks(self, tiles, validate, products, *, apply_affine, out, owner, nodata, bands, typed):
         """``predict_chunks(bootstrap=...)``: one stream at ``kw`` candidates whose reduction stage is the bootstrap."""
-        kw, plan, _ = request
+        kw, plan, _ = products.request
         n_out = len(plan[0])
         output = normalize_typed_output(*typed, n_out, True)  # (a plane can be NaN without any mask)
         weights = "uniform" if self.weights is None else self.weights
         if out is not None and out.ndim != 2:
             raise ValueError(f"out must be 2-D, ({'n_out, N' if bands else 'N, n_out'}), with bootstrap=; got {out.ndim}-D")
         o = None if out is None else (None, None, out)
-        _, _, pred = self._stream_tiles(tiles, validate, kw, apply_affine=apply_affine, weights=weights,
+        _, _, pred = self._stream_tiles(tiles, validate, kw, products=products, apply_affine=apply_affine, weights=weights,
                                         return_distance=False, use_deterministic_ordering=True, out=o, owner=owner,
-                                        nodata=nodata, bands=bands, output=output, bootstrap=(bootstrap, request))
+                                        nodata=nodata, bands=bands, output=output)
         return pred
 
-    def _predict_chunks(self, tiles, validate, *, apply_affine, out, owner, nodata=None, bands=False, typed=None,
-                        statistic=None, neighbors=None, usage=None, zones=None, zonal=None, domain=None, domain_out=None,
-                        beyond="keep"):
+    def _predict_chunks(self, tiles, validate, products, *, apply_affine, out, owner, nodata=None, bands=False, typed=None,
+                        statistic=None, neighbors=None):
         """``neighbors``: :meth:`_neighbor_request`, or None -- predictions alone, exactly as before the keyword existed.
-        ``usage``: a :class:`sknnr_amd.NeighborUsage` the stream's tally is added to, or None.  ``zones`` / ``zonal``: the
-        tiles' zone codes and the :class:`sknnr_amd.ZonalStats` the stream's zonal tables are added to, or None both.
-        ``domain`` / ``domain_out`` / ``beyond``: the :class:`sknnr_amd.DistanceDomain` the stream's codes are tallied into,
-        the plane that receives them, and "nodata" to blank the predictions beyond its threshold."""
+        ``products``: the call's :class:`sknnr_amd._products.StreamProducts`, checked here, every refusal before any
+        device work."""
         weights = "uniform" if self.weights is None else self.weights
         # A distance-weight law (sknnr_amd.weights) is evaluated on the device inside the stream, so it goes wherever
         # "distance" goes; any other callable runs on the host and keeps every refusal below.
         law = isinstance(weights, DistanceWeights)
         host_callable = callable(weights) and not law
         output = None
-        if usage is not None:
-            if host_callable:
-                self._refuse_callable_weights("usage is")
-            self._check_stream_supported("usage is")
-            usage._check(self.n_samples_fit_, self.n_neighbors)
-        if beyond not in ("keep", "nodata"):
-            raise ValueError(f"beyond must be 'keep' or 'nodata', got {beyond!r}")
-        blank = beyond == "nodata"
-        self._check_domain(domain, domain_out, self.n_neighbors, blank, host_callable)  # (every refusal before any device work)
-        domain_extra = {} if domain is None else dict(domain=domain, domain_out=domain_out, beyond=blank)
+        products.check_usage(self, self.n_neighbors, host_callable)
+        blank = products.check_beyond()
+        products.check_domain(self, self.n_neighbors, host_callable)
         plan = statistic if isinstance(statistic, OutputPlan) else None
         flat = self._y.ndim == 1 and (plan is None or plan.per_target)  # the result is 1-D
         if typed is not None:
@@ -1753,28 +1627,13 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             # (a compact law can give an all-zero row: NaN predictions occur without any mask)
             # (so can the domain's mask: a blanked pixel is stored as a nodata pixel is)
             output = normalize_typed_output(*typed, n_targets, nodata is not None or (law and weights.can_vanish) or blank)
-        zonal_extra = {}
-        if zones is not None or zonal is not None:  # (every refusal before any device work)
-            if zones is None or zonal is None:
-                raise ValueError("zones and zonal come together: the zone codes of every tile, and the ZonalStats they are "
-                                 "tallied into")
-            if not isinstance(zonal, ZonalStats):
-                raise TypeError(f"zonal must be a sknnr_amd.ZonalStats, got {type(zonal).__name__}")
-            if host_callable:
-                self._refuse_callable_weights("zonal is")
-            self._check_stream_supported("zonal is")
-            if not output or output.get("pred_dtype") is None or np.dtype(output["pred_dtype"]).kind not in "iu":
-                raise NotImplementedError("zonal needs an integer out_dtype (int16, uint16, uint8 or int32): a float atomic "
-                                          "sum is order-dependent, so zonal sums are taken over the stored integers of a "
-                                          "typed output")
-            zonal._check(plan.n_out if plan is not None else self._n_targets(), output["pred_dtype"], output.get("scale"), output.get("offset"))
-            zonal_extra = dict(zones=zones, zonal=zonal)
+        products.check_zonal(self, plan.n_out if plan is not None else self._n_targets(), output, host_callable)
         if neighbors is not None:
             if host_callable:
                 self._refuse_callable_weights("return_neighbors is")
-            return self._predict_chunks_neighbors(tiles, validate, weights, neighbors, apply_affine=apply_affine, out=out,
-                                                  owner=owner, nodata=nodata, bands=bands, output=output,
-                                                  statistic=statistic, usage=usage, **zonal_extra, **domain_extra)
+            return self._predict_chunks_neighbors(tiles, validate, weights, neighbors, products, apply_affine=apply_affine,
+                                                  out=out, owner=owner, nodata=nodata, bands=bands, output=output,
+                                                  statistic=statistic)
         if host_callable and output:
             self._refuse_callable_weights("typed outputs are")
         if host_callable and bands:
@@ -1782,6 +1641,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         if host_callable and nodata is not None:
             self._refuse_callable_weights("nodata is")
         if host_callable:  # a Python callable runs between the search and the reduction: tile by tile
+            # (every side product has refused it: ``products`` is empty here)
             # (the reorder's second key is the row's position in the WHOLE call: carry it from tile to tile)
             preds, row = [], 0
             for t in tiles:
@@ -1800,18 +1660,16 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             o = None if out is None else (None, None, out.reshape(out.shape[0], -1))
             if bands and out is not None and out.ndim == 1:  # (a 1-D y: the one target plane)
                 o = (None, None, out.reshape(1, -1))
-            _, _, pred = self._stream_tiles(tiles, validate, self.n_neighbors, apply_affine=apply_affine,
+            _, _, pred = self._stream_tiles(tiles, validate, self.n_neighbors, products=products, apply_affine=apply_affine,
                                             weights=weights, return_distance=False,
                                             use_deterministic_ordering=True, out=o, owner=owner, nodata=nodata,
-                                            bands=bands, output=output, statistic=statistic,
-                                            **({} if usage is None else dict(usage=usage)), **zonal_extra, **domain_extra)
+                                            bands=bands, output=output, statistic=statistic)
             if out is None and not output and statistic is None:  # the stream's float64 rows hold float32 values where scikit-learn returns float32
                 pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         return pred.reshape(-1) if flat else pred
 
-    def _predict_chunks_neighbors(self, tiles, validate, weights, neighbors, *, apply_affine, out, owner, nodata, bands,
-                                  output, statistic, usage=None, zones=None, zonal=None, domain=None, domain_out=None,
-                                  beyond=False):
+    def _predict_chunks_neighbors(self, tiles, validate, weights, neighbors, products, *, apply_affine, out, owner, nodata,
+                                  bands, output, statistic):
         """``predict_chunks(return_neighbors=True)``: one stream with all three outputs.  ``output``: the predictions'
         typed output (or None); the neighbours' types and the id table are worked out here, as ``kneighbors_chunks``
         does, every refusal before any device work."""
@@ -1826,14 +1684,11 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             o_pred = out.reshape(1, -1)
         o = None if (o_dist is None and o_idx is None and o_pred is None) else (o_dist, o_idx, o_pred)
         merged = {**(output or {}), **(n_output or {})} or None
-        dist, idx, pred = self._stream_tiles(tiles, validate, self.n_neighbors, apply_affine=apply_affine, weights=weights,
-                                             return_distance=return_distance, use_deterministic_ordering=True, out=o,
-                                             owner=owner, nodata=nodata, fill_index=-1 if ids else fill_index, bands=bands,
-                                             output=merged, statistic=statistic, id_table=table, fill_id=fill_index,
-                                             neighbors=True, **({} if usage is None else dict(usage=usage)),
-                                             **({} if zonal is None else dict(zones=zones, zonal=zonal)),
-                                             **({} if domain is None else
-                                                dict(domain=domain, domain_out=domain_out, beyond=beyond)))
+        dist, idx, pred = self._stream_tiles(tiles, validate, self.n_neighbors, products=products, apply_affine=apply_affine,
+                                             weights=weights, return_distance=return_distance,
+                                             use_deterministic_ordering=True, out=o, owner=owner, nodata=nodata,
+                                             fill_index=-1 if ids else fill_index, bands=bands, output=merged,
+                                             statistic=statistic, id_table=table, fill_id=fill_index, neighbors=True)
         if out is None and not output and statistic is None:  # (as without neighbours: float32 where scikit-learn returns it)
             pred = pred.astype(self.engine_.pred_dtype(weights), copy=False)
         if self._y.ndim == 1 and not (isinstance(statistic, OutputPlan) and not statistic.per_target):
@@ -1938,10 +1793,10 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         ``uniform`` weights need no distances; ``distance`` weights, the laws of :mod:`sknnr_amd.weights`, ``usage`` and
         ``domain`` need them.  Every other keyword has the meaning and the refusals it has in :meth:`predict_chunks`.
         (Bootstrap planes from a stored raster: :meth:`bootstrap_neighbors_chunks`.)"""
-        return self._replay_chunks(neighbor_tiles, y=y, n_neighbors=n_neighbors, ids=ids, fill_index=fill_index,
+        products = StreamProducts(usage, zones, zonal, domain, domain_out, beyond)
+        return self._replay_chunks(neighbor_tiles, products, y=y, n_neighbors=n_neighbors, ids=ids, fill_index=fill_index,
                                    unknown=unknown, out=out, layout=layout, out_dtype=out_dtype, scale=scale, offset=offset,
-                                   out_nodata=out_nodata, statistic=statistic, outputs=outputs, usage=usage, zones=zones,
-                                   zonal=zonal, domain=domain, domain_out=domain_out, beyond=beyond)
+                                   out_nodata=out_nodata, statistic=statistic, outputs=outputs)
 
     def bootstrap_neighbors_chunks(self, neighbor_tiles, bootstrap, y=None, n_neighbors=None, ids=False, fill_index=-1,
                                    unknown="raise", out=None, layout="rows", out_dtype=None, scale=None, offset=None,
@@ -1956,25 +1811,24 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         always needs ``out_nodata``).  The result is ``(N, n_out)``, ``(n_out, N)`` with ``layout="bands"``."""
         if bootstrap is None:
             raise TypeError("bootstrap must be a sknnr_amd.Bootstrap, got NoneType")
-        return self._replay_chunks(neighbor_tiles, y=y, n_neighbors=n_neighbors, ids=ids, fill_index=fill_index,
-                                   unknown=unknown, out=out, layout=layout, out_dtype=out_dtype, scale=scale, offset=offset,
-                                   out_nodata=out_nodata, outputs=outputs, bootstrap=bootstrap)
+        return self._replay_chunks(neighbor_tiles, StreamProducts(bootstrap=bootstrap), y=y, n_neighbors=n_neighbors, ids=ids,
+                                   fill_index=fill_index, unknown=unknown, out=out, layout=layout, out_dtype=out_dtype,
+                                   scale=scale, offset=offset, out_nodata=out_nodata, outputs=outputs)
 
     def bootstrap_neighbors(self, idx, dist=None, *, bootstrap, **kwargs):
         """:meth:`bootstrap_neighbors_chunks` on one tile of stored neighbours, through the same path."""
         return self.bootstrap_neighbors_chunks([idx if dist is None else (dist, idx)], bootstrap, **kwargs)
 
-    def _replay_chunks(self, neighbor_tiles, y=None, n_neighbors=None, ids=False, fill_index=-1, unknown="raise", out=None,
-                       layout="rows", out_dtype=None, scale=None, offset=None, out_nodata=None, statistic=None, outputs=None,
-                       usage=None, zones=None, zonal=None, domain=None, domain_out=None, beyond="keep", bootstrap=None):
-        """The replay behind :meth:`predict_neighbors_chunks` and, with ``bootstrap``, :meth:`bootstrap_neighbors_chunks`."""
+    def _replay_chunks(self, neighbor_tiles, products, y=None, n_neighbors=None, ids=False, fill_index=-1, unknown="raise",
+                       out=None, layout="rows", out_dtype=None, scale=None, offset=None, out_nodata=None, statistic=None,
+                       outputs=None):
+        """The replay behind :meth:`predict_neighbors_chunks` and, with a bootstrap among ``products`` (the call's
+        :class:`sknnr_amd._products.StreamProducts`), :meth:`bootstrap_neighbors_chunks`."""
         bands = _check_layout(layout)
         check_is_fitted(self, "_fit_X")
         if unknown not in ("raise", "nodata"):
             raise ValueError(f"unknown must be 'raise' or 'nodata', got {unknown!r}")
-        if beyond not in ("keep", "nodata"):
-            raise ValueError(f"beyond must be 'keep' or 'nodata', got {beyond!r}")
-        blank = beyond == "nodata"
+        blank = products.check_beyond()
         weights = "uniform" if self.weights is None else self.weights
         law = isinstance(weights, DistanceWeights)
         if callable(weights) and not law:
@@ -1984,11 +1838,9 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             raise ValueError(f"fill_index must be an integer, got {fill_index!r}")
         engine, flat, n_targets, target_dtype = self._replay_target_engine(y)
         id_table = self._replay_id_table(ids)
-        boot = None
+        bootstrap, boot = products.bootstrap, None
         if bootstrap is not None:  # (every refusal before any device work)
-            boot = self._boot_chunks_request(bootstrap, statistic, outputs, usage=usage, zones=zones, zonal=zonal,
-                                             domain=domain, domain_out=domain_out, beyond=beyond, n_targets=n_targets,
-                                             stored=True)
+            boot = products.bootstrap_request(self, statistic, outputs, n_targets=n_targets, stored=True)
             statistic = outputs = None
         statistic = resolve_statistic(statistic, outputs, n_targets)
         plan = statistic if isinstance(statistic, OutputPlan) else None
@@ -1998,26 +1850,14 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
             t_cols = len(boot[1][0])
         output = normalize_typed_output(out_dtype, scale, offset, out_nodata, t_cols,
                                         unknown == "nodata" or (law and weights.can_vanish) or blank or boot is not None)
-        if (zones is None) != (zonal is None):
-            raise ValueError("zones and zonal come together: the zone codes of every tile, and the ZonalStats they are tallied into")
-        zonal_binding = None
-        if zonal is not None:
-            if not isinstance(zonal, ZonalStats):
-                raise TypeError(f"zonal must be a sknnr_amd.ZonalStats, got {type(zonal).__name__}")
-            if not output or np.dtype(output["pred_dtype"]).kind not in "iu":
-                raise NotImplementedError("zonal needs an integer out_dtype (int16, uint16, uint8 or int32): zonal sums are "
-                                          "taken over the stored integers of a typed output")
-            zonal_binding = zonal._check(t_cols, output["pred_dtype"], output.get("scale"), output.get("offset"))
-            zones = iter(zones)
-        if usage is not None and not isinstance(usage, NeighborUsage):
-            raise TypeError(f"usage must be a sknnr_amd.NeighborUsage, got {type(usage).__name__}")
+        products.check_zonal(self, t_cols, output)
+        products.check_usage(self)
         needs_dist = [name for name, on in (("weights='distance'", weights == "distance"), ("a weight law", law),
-                                            ("usage", usage is not None), ("domain", domain is not None)) if on]
+                                            ("usage", products.usage is not None),
+                                            ("domain", products.domain is not None)) if on]
 
         def settle(k, has_dist):  # what needs k or the first tile, still before any device work
-            if usage is not None:
-                usage._check(self.n_samples_fit_, k)
-            self._check_domain(domain, domain_out, k, blank)
+            products.settle(self, k)
             if needs_dist and not has_dist:
                 raise ValueError(f"{' and '.join(needs_dist)} need{'s' if len(needs_dist) == 1 else ''} the stored "
                                  "distances: pass (dist, idx) tiles")
@@ -2025,7 +1865,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                         or n_neighbors < 1):
             raise ValueError(f"n_neighbors must be a positive integer, got {n_neighbors!r}")
         # (the rank is checked against k by settle(), once the first tile has shown ks)
-        self._check_domain(domain, domain_out, int(n_neighbors) if n_neighbors is not None else np.iinfo(np.int64).max, blank)
+        products.check_domain(self, None if n_neighbors is None else int(n_neighbors))
         out_kw = {key: v for key, v in (output or {}).items() if v is not None}
         pred_dt = np.dtype(out_kw.get("pred_dtype", np.float64))
         o_pred = None
@@ -2035,11 +1875,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
         counts = dict(unknown=0, first_unknown=-1)
         try:
             for number, tile in enumerate(neighbor_tiles):
-                if zonal is not None:  # (in lockstep: a skipped empty tile consumes its entry too)
-                    try:
-                        tile_zones = next(zones)
-                    except StopIteration:
-                        raise ValueError(_ZONES_SHORT) from None
+                products.next_tile()
                 idx, dist = self._replay_tile(tile, bands, number)
                 ks, n = (idx.shape[0], idx.shape[1]) if bands else (idx.shape[1], idx.shape[0])
                 key = (ks, idx.dtype, None if dist is None else dist.dtype)
@@ -2072,59 +1908,26 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                     eng = engine()
                     if id_table is not None:
                         eng.set_replay_ids(id_table)
-                    if boot is not None:
-                        eng.set_bootstrap(boot[2])
                     stream = eng.open_replay(k, ks, weights=weights, idx_dtype=idx.dtype,
                                              dist_dtype=None if dist is None else dist.dtype, fill_index=int(fill_index),
                                              ids=id_table is not None, output=out_kw,
                                              **(dict(statistic=statistic) if plan is None else dict(plan=plan.arrays)),
-                                             **({} if usage is None else dict(tally=True)),
-                                             **({} if zonal is None else
-                                                dict(zonal=(zonal.n_zones, zonal.n_classes(zonal_binding[0])))),
-                                             **({} if domain is None else
-                                                dict(domain=(domain.table, domain.rank, domain.threshold, blank))),
-                                             **({} if boot is None else dict(bootstrap=(self.n_neighbors, boot[1]))))
-                window = None
-                if o_pred is not None:
-                    if bands:
-                        if o_pred.shape[0] != t_cols or o_pred.dtype != pred_dt or not o_pred.flags.c_contiguous \
-                                or o_pred.shape[1] < row + n:
-                            raise ValueError(f"out must be C-contiguous, {pred_dt}, with {t_cols} rows and at least "
-                                             f"{row + n} columns")
-                        window = o_pred[:, row:row + n]
-                    else:
-                        window = o_pred[row:row + n]
-                        if window.shape != (n, t_cols) or window.dtype != pred_dt or not window.flags.c_contiguous:
-                            raise ValueError(f"out must be C-contiguous, {pred_dt}, with {t_cols} columns and at least "
-                                             f"{row + n} rows")
-                if zonal is not None:
-                    stream.next_zones(normalize_zone_tile(tile_zones, n))
-                if domain_out is not None:
-                    if domain_out.size < row + n:
-                        raise ValueError(f"domain_out holds {domain_out.size} pixels: the tiles hold at least {row + n}")
-                    stream.next_domain_out(domain_out[row:row + n])
+                                             **products.open_keywords(eng, self.n_neighbors))
+                window = _out_window(o_pred, row, n, t_cols, pred_dt, bands, "out")
+                products.feed(stream, row, n)
                 got = (stream.push_planes if bands else stream.push)(idx, dist, out_pred=window)
                 tile_of_push.append(number)
                 if o_pred is None:
                     pieces.append(got[2])
                 row += n
-            if zonal is not None and next(zones, None) is not None:
-                raise ValueError(_ZONES_LONG)
+            products.end_of_tiles()
             if shape_key is None:  # (no tile at all: what can be checked without one)
                 settle(self.n_neighbors if n_neighbors is None else int(n_neighbors), True)
-            tallied = zoned = placed = booted = None
             if stream is not None:
                 done, stream = stream, None
                 try:
                     counts = done.counts()
-                    if boot is not None:
-                        booted = done.bootstrap()
-                    if usage is not None:
-                        tallied = done.tally()
-                    if zonal is not None:
-                        zoned = done.zonal()
-                    if domain is not None:
-                        placed = done.domain()
+                    products.collect(done)
                 finally:
                     done.close()
             self.replay_unknown_ = int(counts["unknown"])
@@ -2133,20 +1936,7 @@ class RawKNNRegressor(DFIndexCrosswalkMixin, MultiOutputMixin, RegressorMixin, B
                                  f"is not in the fitted index, or a position outside [0, {self.n_samples_fit_})); the first "
                                  f"of them are in tile {tile_of_push[counts['first_unknown']]}.  Pass unknown='nodata' to "
                                  "store them as nodata pixels")
-            if booted is not None:  # (only a call that came through whole is added)
-                bootstrap._add(booted)
-            if placed is not None:  # (only a call that came through whole is added)
-                domain._add(placed)
-            if zonal is not None:
-                zonal._bind(*zonal_binding)
-                if zoned is not None:
-                    zonal._add(*zoned)
-            if usage is not None:
-                labels = getattr(self, "dataframe_index_in_", None)
-                if tallied is None:
-                    usage._bind(self.n_samples_fit_, k if k is not None else self.n_neighbors, labels)
-                else:
-                    usage._add(*tallied, labels)
+            products.commit(self, k if k is not None else self.n_neighbors)
         except _native.HipBackendError as err:
             _reraise(err, self)
         finally:
@@ -2443,21 +2233,21 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         check_is_fitted(self, "regressor_")
         reg = self.regressor_
         k = reg._resolve_k(n_neighbors)
-        reg._check_domain(domain, domain_out, k)
+        products = StreamProducts(usage=usage, domain=domain, domain_out=domain_out)
+        products.check_domain(reg, k)
         validate = self._band_validator(bands)
         nodata = self._raw_nodata(nodata)
         output = reg._neighbor_output(index_dtype, distance_dtype, return_distance, return_dataframe_index, fill_index,
                                       nodata is not None)
         o = None if out is None else (out[0], out[1], None)
         table = reg._device_id_table(return_dataframe_index)
-        dist, idx, _ = reg._stream_tiles(tiles, validate, k, apply_affine=self._map_on_device(), weights=None,
-                                         return_distance=return_distance,
+        products.check_usage(reg, k)
+        dist, idx, _ = reg._stream_tiles(tiles, validate, k, products=products, apply_affine=self._map_on_device(),
+                                         weights=None, return_distance=return_distance,
                                          use_deterministic_ordering=use_deterministic_ordering, out=o,
                                          owner=self.transformer_, nodata=nodata,
                                          fill_index=-1 if return_dataframe_index else fill_index, bands=bands,
-                                         output=output, id_table=table, fill_id=fill_index,
-                                         **({} if usage is None else dict(usage=usage)),
-                                         **({} if domain is None else dict(domain=domain, domain_out=domain_out)))
+                                         output=output, id_table=table, fill_id=fill_index)
         return reg._finish_chunks(dist, idx, return_distance, return_dataframe_index,
                                   fill_index=None if nodata is None else fill_index, on_device=table is not None)
 
@@ -2481,29 +2271,21 @@ class TransformedKNeighborsRegressor(BaseEstimator, ABC):
         :meth:`RawKNNRegressor.kneighbors_chunks` / :meth:`RawKNNRegressor.predict_chunks`)."""
         bands = _check_layout(layout)
         check_is_fitted(self, "regressor_")
+        reg = self.regressor_
+        products = StreamProducts(usage, zones, zonal, domain, domain_out, beyond, bootstrap)
+        common = dict(apply_affine=self._map_on_device(), out=out, owner=self.transformer_, bands=bands,
+                      typed=(out_dtype, scale, offset, out_nodata))
         if bootstrap is not None:
-            reg = self.regressor_
-            request = reg._boot_chunks_request(bootstrap, statistic, outputs, return_neighbors, return_distance,
-                                               return_dataframe_index, neighbors_out, fill_index, index_dtype, distance_dtype,
-                                               usage, zones, zonal, domain, domain_out, beyond)
-            return reg._bootstrap_chunks(tiles, self._band_validator(bands), bootstrap, request,
-                                         apply_affine=self._map_on_device(), out=out, owner=self.transformer_,
-                                         nodata=self._raw_nodata(nodata), bands=bands,
-                                         typed=(out_dtype, scale, offset, out_nodata))
-        neighbors = self.regressor_._neighbor_request(return_neighbors, return_distance, return_dataframe_index,
-                                                      neighbors_out, fill_index, index_dtype, distance_dtype)
-        extra = {} if neighbors is None else dict(neighbors=neighbors)
-        if usage is not None:
-            extra["usage"] = usage
-        if zones is not None or zonal is not None:
-            extra.update(zones=zones, zonal=zonal)
-        if domain is not None or domain_out is not None or beyond != "keep":
-            extra.update(domain=domain, domain_out=domain_out, beyond=beyond)
-        statistic = resolve_statistic(statistic, outputs, self.regressor_._n_targets())
-        return self.regressor_._predict_chunks(tiles, self._band_validator(bands), apply_affine=self._map_on_device(),
-                                               out=out, owner=self.transformer_, nodata=self._raw_nodata(nodata),
-                                               bands=bands, typed=(out_dtype, scale, offset, out_nodata),
-                                               statistic=statistic, **extra)
+            products.bootstrap_request(reg, statistic, outputs, return_neighbors=return_neighbors,
+                                       return_dataframe_index=return_dataframe_index, neighbors_out=neighbors_out,
+                                       index_dtype=index_dtype, distance_dtype=distance_dtype)
+            return reg._bootstrap_chunks(tiles, self._band_validator(bands), products, nodata=self._raw_nodata(nodata),
+                                         **common)
+        neighbors = reg._neighbor_request(return_neighbors, return_distance, return_dataframe_index, neighbors_out,
+                                          fill_index, index_dtype, distance_dtype)
+        statistic = resolve_statistic(statistic, outputs, reg._n_targets())
+        return reg._predict_chunks(tiles, self._band_validator(bands), products, nodata=self._raw_nodata(nodata),
+                                   statistic=statistic, neighbors=neighbors, **common)
 
     def predict_neighbors_chunks(self, neighbor_tiles, **kwargs):
         """Attribute maps from STORED neighbours (:meth:`RawKNNRegressor.predict_neighbors_chunks`, with its keywords):

@@ -715,27 +715,8 @@ class KNNEngine:
         mode = self.weight_mode("explicit" if law else weights) if want_pred else _native.WEIGHTS_UNIFORM
         stream = self._index.open_replay(k, ks, weight_mode=mode, weight_law=law, idx_dtype=idx_dtype, dist_dtype=dist_dtype,
                                          fill_index=fill_index, ids=ids, want_dist=want_dist, want_pred=want_pred)
-        try:  # (the order of Index.open_stream)
-            if plan is not None:
-                stream.set_plan(plan)
-            if bootstrap is not None:
-                stream.set_bootstrap(*bootstrap)
-            if output:
-                stream.set_output(**output)
-            if statistic is not None:
-                stream.set_statistics(statistic)
-            if id_table is not None:
-                stream.set_id_table(id_table, fill_id)
-            if tally:
-                stream.set_tally()
-            if zonal is not None:
-                stream.set_zonal(*zonal)
-            if domain is not None:
-                stream.set_domain(*domain)
-        except Exception:
-            stream.close()
-            raise
-        return stream
+        return stream.configure(output=output, statistic=statistic, id_table=id_table, fill_id=fill_id, plan=plan,
+                                tally=tally, zonal=zonal, domain=domain, bootstrap=bootstrap)
 
     def set_bootstrap(self, table):
         """The uint8 ``(B, n_ref)`` multiplicity table of bootstrap reductions (None: none); uploaded when it changes."""

@@ -774,30 +774,9 @@ class Index:
         ``(n_zones, n_classes)``, the arguments of :meth:`QueryStream.set_zonal`.  ``domain``: ``(table, rank, threshold,
         mask_beyond)``, the arguments of :meth:`QueryStream.set_domain`.  ``bootstrap``: ``(k, (cols, codes))``, the
         arguments of :meth:`QueryStream.set_bootstrap` -- the stream searches ``opts.n_neighbors`` candidates."""
-        stream = QueryStream(self, opts, want_dist, want_pred)
-        try:
-            if plan is not None:  # (first: it sets the width set_output's scale / offset must have)
-                stream.set_plan(plan)
-            if bootstrap is not None:  # (likewise)
-                stream.set_bootstrap(*bootstrap)
-            if nodata is not None:
-                stream.set_nodata(nodata, fill_index)
-            if output:
-                stream.set_output(**output)
-            if statistic is not None:
-                stream.set_statistics(statistic)
-            if id_table is not None:
-                stream.set_id_table(id_table, fill_id)
-            if tally:
-                stream.set_tally()
-            if zonal is not None:  # (behind the plan: n_classes holds one value per plane)
-                stream.set_zonal(*zonal)
-            if domain is not None:
-                stream.set_domain(*domain)
-        except Exception:
-            stream.close()
-            raise
-        return stream
+        return QueryStream(self, opts, want_dist, want_pred).configure(
+            nodata=nodata, fill_index=fill_index, output=output, statistic=statistic, id_table=id_table, fill_id=fill_id,
+            plan=plan, tally=tally, zonal=zonal, domain=domain, bootstrap=bootstrap)
 
     # ---- host (numpy) entry points --------------------------------------------------------
     def kneighbors_host(self, q, opts: QueryOpts, nq=None, return_distance=True):
@@ -1375,6 +1354,35 @@ class QueryStream:
     def _begin(self, index, opts):
         check(load().sknnr_stream_begin(index.handle, byref(opts), int(self.want_dist), int(self.want_pred),
                                         byref(self._h)))
+
+    def configure(self, *, nodata=None, fill_index=-1, output=None, statistic=None, id_table=None, fill_id=-1, plan=None,
+                  tally=False, zonal=None, domain=None, bootstrap=None):
+        """Every ``set_*`` a fresh stream was asked for (the keywords of :meth:`Index.open_stream`), in the one order they
+        work in, for a search stream and a replay alike (a replay has no ``nodata``).  Returns the stream; a refusal
+        closes it."""
+        try:
+            if plan is not None:  # (first: it sets the width set_output's scale / offset must have)
+                self.set_plan(plan)
+            if bootstrap is not None:  # (likewise)
+                self.set_bootstrap(*bootstrap)
+            if nodata is not None:
+                self.set_nodata(nodata, fill_index)
+            if output:
+                self.set_output(**output)
+            if statistic is not None:
+                self.set_statistics(statistic)
+            if id_table is not None:
+                self.set_id_table(id_table, fill_id)
+            if tally:
+                self.set_tally()
+            if zonal is not None:  # (behind the plan: n_classes holds one value per plane)
+                self.set_zonal(*zonal)
+            if domain is not None:
+                self.set_domain(*domain)
+        except Exception:
+            self.close()
+            raise
+        return self
 
     def _push(self, native, tile, nq, planes, out_idx, out_dist, out_pred, need_idx):
         """Push one tile of ``nq`` pixels through ``native`` (a row push, or with ``planes`` a band-first one): the missing

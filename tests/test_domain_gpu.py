@@ -10,7 +10,9 @@ must be bit-equal to the call without it unless ``beyond="nodata"`` blanks it.
 
 Without the feature every test here fails: the keywords, the class and the methods do not exist.
 
-Measured on an MI355X: the 13 cases take 4.0 s, of which 3.3 s are the first fixture's device set-up; no case takes more than
+The last case has an estimator of its own: 64 reference rows, two tiles of 8 pixels, every side product in one call.
+
+Measured on an MI355X: the 14 cases take 3.8 s, of which 3.1 s are the first fixture's device set-up; no case takes more than
 0.05 s.
 """
 
@@ -343,3 +345,56 @@ def test_python_refusals(raw):
             with pytest.raises(NotImplementedError, match=r"domain is not supported under hamming_tie_policy\('numpy'\)"):
                 call(iter(tiles), domain=d)
     assert d.n_pixels == 0
+
+
+def test_all_products_in_one_call_add_up_to_the_separate_calls_or_to_nothing():
+    """usage, zonal and domain with ``domain_out`` in ONE ``predict_chunks`` call over two tiles of 8 pixels -- the smallest
+    shape with two tiles and a partial last window: a ``domain_out`` one element short is refused at the second tile and
+    leaves all three objects as they were; a whole call gives, byte for byte, what three calls with one keyword each
+    give; and the replay of the stored neighbours does both just the same."""
+    import copy
+
+    import sknnr_amd
+
+    rng = np.random.default_rng(5)
+    X = rng.integers(0, 200, size=(64, 4)).astype(np.float64)
+    y = np.column_stack([X[:, 0] + 0.25 * X[:, 1], X[:, 2] - X[:, 3]])
+    est = sknnr_amd.RawKNNRegressor(n_neighbors=3).fit(X, y)
+    px = rng.integers(0, 200, size=(16, 4)).astype(np.float64)
+    zones = (np.arange(16) % 3).astype(np.int32)
+    typed = dict(out_dtype=np.int16, scale=10.0)
+    table = est.distance_domain().table
+
+    def fresh():
+        return sknnr_amd.NeighborUsage(), sknnr_amd.ZonalStats(3), sknnr_amd.DistanceDomain(table, threshold=table[40])
+
+    # three separate calls, one keyword each: the expectation of every whole call below
+    usage1, zonal1, domain1 = fresh()
+    codes1 = np.full(16, 77, dtype=np.uint8)
+    want = est.predict_chunks(iter(cut(px, (8, 8))), **typed)
+    for one in (dict(usage=usage1), dict(zones=iter(cut(zones, (8, 8))), zonal=zonal1), dict(domain=domain1, domain_out=codes1)):
+        assert est.predict_chunks(iter(cut(px, (8, 8))), **one, **typed).tobytes() == want.tobytes()
+    assert want.dtype == np.int16 and usage1.n_rows == 16 and domain1.n_pixels == 16 and zonal1.n_planes == 2
+    _, dist, idx = est.predict_chunks(iter(cut(px, (8, 8))), return_neighbors=True)
+
+    def search(**kw):
+        return est.predict_chunks(iter(cut(px, (8, 8))), **typed, **kw)
+
+    def replay(**kw):
+        return est.predict_neighbors_chunks(zip(cut(dist, (8, 8)), cut(idx, (8, 8))), **typed, **kw)
+
+    for call in (search, replay):
+        usage, zonal, domain = fresh()
+        before = copy.deepcopy((usage, zonal, domain))
+        with pytest.raises(ValueError, match="domain_out holds 15 pixels: the tiles hold at least 16"):
+            call(usage=usage, zones=iter(cut(zones, (8, 8))), zonal=zonal, domain=domain,
+                 domain_out=np.zeros(15, dtype=np.uint8))
+        assert (usage, zonal, domain) == before
+        assert usage.shape is None and zonal.n_planes is None and domain.n_pixels == 0
+        codes = np.full(16, 77, dtype=np.uint8)
+        got = call(usage=usage, zones=iter(cut(zones, (8, 8))), zonal=zonal, domain=domain, domain_out=codes)
+        assert got.dtype == want.dtype and got.tobytes() == want.tobytes()
+        assert codes.tobytes() == codes1.tobytes()
+        assert usage == usage1 and zonal == zonal1 and domain == domain1
+        assert usage.counts.tobytes() == usage1.counts.tobytes() and zonal._acc.tobytes() == zonal1._acc.tobytes()
+        assert domain.hist.tobytes() == domain1.hist.tobytes()

@@ -146,6 +146,7 @@ def test_transformed_estimators_pass_the_arguments_through():
 # ---- what reaches the stream ---------------------------------------------------------------------------------------------
 BEFORE = {"apply_affine", "weights", "return_distance", "use_deterministic_ordering", "out", "owner", "nodata", "bands",
           "output", "statistic"}  # the keywords predict_chunks handed to _stream_tiles before return_neighbors existed
+BEFORE |= {"products"}  # (the call's side products as one object: empty in these calls)
 
 
 def recording(est, k=3, t=3):
@@ -177,9 +178,10 @@ def test_without_return_neighbors_nothing_new_reaches_the_stream(wrap):
     assert pred.shape == (4, 3)
     (k, kw), = calls
     assert k == 3 and set(kw) == BEFORE and kw["return_distance"] is False and kw["output"] is None
+    assert not kw["products"] and kw["products"].open_keywords(None, k) == {}
     pred = est.predict_chunks(TILES, return_neighbors=False, return_distance=True, return_dataframe_index=False,
                               neighbors_out=None, fill_index=-1, index_dtype=None, distance_dtype=None)
-    assert set(calls[1][1]) == BEFORE and not isinstance(pred, tuple)
+    assert set(calls[1][1]) == BEFORE and not calls[1][1]["products"] and not isinstance(pred, tuple)
 
 
 @pytest.mark.parametrize("wrap", [False, True])
