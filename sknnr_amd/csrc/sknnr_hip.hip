@@ -139,11 +139,113 @@ struct DevBuf {
         if (e == hipSuccess) n = count;
         return e;
     }
+    // room for `count` elements, filled from host memory
+    int upload(const void* src, size_t count) {
+        HIP_TRY(ensure(count));
+        HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+        return SKNNR_OK;
+    }
     void release() {
         if (p) (void)hipFree(p);
         p = nullptr;
         n = 0;
     }
+};
+
+// One array argument of a one-shot call that takes either memspace.  Device memory: p is the caller's pointer.  Host
+// memory: p is a device buffer of this object's own, filled from the caller's array when the launch reads it (kStageIn,
+// kStageInOut) and copied back by download() when the launch writes it (kStageOut, kStageInOut).  A null argument stays
+// null.  The buffer is freed by the destructor on every return path.
+enum { kStageIn = 1, kStageOut = 2, kStageInOut = kStageIn | kStageOut };
+template <typename T>
+struct Staged {
+    T* p = nullptr;
+    DevBuf<T> buf;
+    void* host = nullptr;  // where download() copies `count` elements to (null: nowhere)
+    size_t count = 0;
+    int stage(const void* caller, size_t n, int mem, int dir) {
+        p = (T*)caller;
+        if (mem != SKNNR_MEM_HOST || !caller) return SKNNR_OK;
+        HIP_TRY(buf.ensure(n));
+        if ((dir & kStageIn) && n) HIP_TRY(hipMemcpy(buf.p, caller, n * sizeof(T), hipMemcpyHostToDevice));
+        if (dir & kStageOut) host = (void*)caller;
+        count = n;
+        p = buf.p;
+        return SKNNR_OK;
+    }
+    int download() {
+        if (host && count) HIP_TRY(hipMemcpy(host, buf.p, count * sizeof(T), hipMemcpyDeviceToHost));
+        return SKNNR_OK;
+    }
+};
+
+// The debug record of a side product (neighbour usage, zonal statistics, distance domain): the device words its kernels
+// add to -- two halves of `words` each, half 0 of one-shot calls, half 1 of the open stream, so that neither disturbs the
+// other's counters -- and the host's words of the sknnr_debug_last_* entry (ran, rows, then the product's own), with the
+// half they belong to: whoever started or ran last.
+struct ProductRec {
+    const int words;
+    DevBuf<unsigned long long> dev;
+    int64_t host[5] = {};
+    int half = 0;
+    explicit ProductRec(int words_) : words(words_) {}
+    hipError_t ensure() { return dev.ensure(2 * (size_t)words); }
+    unsigned long long* at(int h) const { return dev.p + h * words; }
+    // a call or a stream begins: its device words are zeroed on `st`, the host's words are `h5` (the rest zero)
+    hipError_t reset(int h, hipStream_t st, std::initializer_list<int64_t> h5) {
+        std::fill(host, host + 5, 0);
+        std::copy(h5.begin(), h5.end(), host);
+        half = h;
+        return hipMemsetAsync(at(h), 0, words * sizeof(unsigned long long), st);
+    }
+    // a tile of the open stream was launched
+    void ran(int h, long n) {
+        host[0] = 1;
+        host[1] += n;
+        half = h;
+    }
+    // out: the host's words, zeros behind them; w: the device words of their half, once the device is idle (zeros while
+    // nothing was launched).  Takes the handle's lock.
+    int read(std::mutex& mtx, int device, int64_t out[8], unsigned long long w[]) {
+        std::lock_guard<std::mutex> lock(mtx);
+        std::fill(out, out + 8, 0);
+        std::copy(host, host + 5, out);
+        std::fill(w, w + words, 0);
+        if (!dev.p) return SKNNR_OK;
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(w, at(half), words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        return SKNNR_OK;
+    }
+};
+
+// The side products on the handle, one struct each: `call` holds what a one-shot call parks on the handle, `stream` what
+// the open stream's setter (sknnr_stream_set_*) installed and the stream's accumulators, `rec` the debug record.
+// Neighbour usage (tally.hip.h): the stream's counts (n_ref, k) and maxima (n_ref); the record's host words are ran,
+// rows, k.
+struct TallyProduct {
+    struct { DevBuf<unsigned long long> cnt, max; } stream;
+    ProductRec rec{kTallyRecWords};
+};
+// Zonal statistics (zonal.hip.h): the class table of each kind of call -- n_classes per column (cls) and where each
+// column's block begins in hist (off); the conversion parameters of one-shot calls (par: scale then offset); the
+// stream's accumulators and class blocks; the record's host words are ran, pixels, c.
+struct ZonalProduct {
+    struct { DevBuf<int> cls; DevBuf<long> off; DevBuf<double> par; } call;
+    struct { DevBuf<int> cls; DevBuf<long> off; DevBuf<long long> acc, hist; } stream;
+    ProductRec rec{kZonalRecWords};
+};
+// Distance domain (domain.hip.h): the sorted table of each kind of call and the stream's accumulators; the record's host
+// words are ran, pixels, k, rank, m.
+struct DomainProduct {
+    struct { DevBuf<double> table; } call;
+    struct { DevBuf<double> table; DevBuf<unsigned long long> acc; } stream;
+    ProductRec rec{kDomainRecWords};
+};
+// Bootstrap (bootstrap.hip.h): the plan arrays and the two tally words of a one-shot call (the plan is a workspace buffer
+// behind ev_ws) and of the open stream's stage; its record is the handle's last_boot.
+struct BootProduct {
+    struct Bufs { DevBuf<int> plan; DevBuf<unsigned long long> tally; } call, stream;
 };
 
 // Device buffers of the nodata front end (mask.hip.h) for one tile: the handle has a set for device-memory calls, every
@@ -527,32 +629,11 @@ struct sknnr_index {
     double law_p0 = 0.0, law_p1 = 0.0;
     DevBuf<double> law_w;
     int64_t last_law[8] = {};
-    // neighbour usage (tally.hip.h): the open stream's accumulators (sknnr_stream_set_tally), the kernels' device record --
-    // words [0, 4) of one-shot calls, [4, 8) of the open stream -- and the host's half of sknnr_debug_last_tally: ran, rows,
-    // k; last_tally_half: which device words belong to it
-    DevBuf<unsigned long long> s_tally_cnt, s_tally_max, tally_rec;
-    int64_t last_tally[3] = {};
-    int last_tally_half = 0;
-    // zonal statistics (zonal.hip.h): the open stream's accumulators (sknnr_stream_set_zonal) and the class table of each
-    // kind of call -- n_classes per column (zonal_cls) and where each column's block begins in hist (zonal_off); the
-    // conversion parameters of one-shot calls (zonal_par: scale then offset); the kernels' device record -- words [0, 6) of
-    // one-shot calls, [6, 12) of the open stream -- and the host's half of sknnr_debug_last_zonal: ran, pixels, c;
-    // last_zonal_half: which device words belong to it
-    DevBuf<long long> s_zonal_acc, s_zonal_hist;
-    DevBuf<int> zonal_cls, s_zonal_cls;
-    DevBuf<long> zonal_off, s_zonal_off;
-    DevBuf<double> zonal_par;
-    DevBuf<unsigned long long> zonal_rec;
-    int64_t last_zonal[3] = {};
-    int last_zonal_half = 0;
-    // distance domain (domain.hip.h): the sorted table of one-shot calls (dom_table) and of the open stream (s_dom_table,
-    // sknnr_stream_set_domain), the open stream's accumulators, the kernels' device record -- words [0, 4) of one-shot
-    // calls, [4, 8) of the open stream -- and the host's half of sknnr_debug_last_domain: ran, pixels, k, rank, m;
-    // last_domain_half: which device words belong to it
-    DevBuf<double> dom_table, s_dom_table;
-    DevBuf<unsigned long long> s_dom_acc, dom_rec;
-    int64_t last_domain[5] = {};
-    int last_domain_half = 0;
+    // the side products (TallyProduct ... BootProduct above: call-side buffers, stream-side buffers, the debug record)
+    TallyProduct tally;
+    ZonalProduct zonal;
+    DomainProduct domain;
+    BootProduct boot;
     // neighbour replay (replay.hip.h).  targets_only: the handle was made by sknnr_index_create_targets and owns y64 and
     // nothing of a search.  The sorted id table of sknnr_index_set_replay_ids and the row position of each of its entries;
     // the per-tile records of the open replay stream, one per pipeline slot, on the device and pinned; the searches the
@@ -567,16 +648,11 @@ struct sknnr_index {
     long search_calls = 0;
     int64_t last_replay[8] = {};
     // bootstrap (bootstrap.hip.h): the transposed multiplicity table of sknnr_index_set_bootstrap, (n_ref, boot_bpad) bytes,
-    // and its replicates (0: none installed); the plan arrays and the two tally words of a one-shot call; the record of the
-    // last reduction (sknnr_debug_last_bootstrap)
+    // and its replicates (0: none installed); the record of the last reduction (sknnr_debug_last_bootstrap); the plans
+    // and tally words are in `boot` above
     DevBuf<unsigned char> boot_mt;
     int boot_B = 0, boot_bpad = 0;
-    DevBuf<int> c_boot;
-    DevBuf<unsigned long long> boot_tally;
     int64_t last_boot[8] = {};
-    // the open stream's stage: its plan arrays (s_boot) and the stream's two tally words (s_boot_tally)
-    DevBuf<int> s_boot;
-    DevBuf<unsigned long long> s_boot_tally;
 
     // Device timing of calls (HIP events on the launch stream), resolved lazily by sknnr_get_stats:
     // a ring of call records so that several calls of one benchmark step are summed, not only the last.
@@ -2578,19 +2654,21 @@ struct HostPipe {
         bool converts() const { return dtype != 0 || table != nullptr; }
     } lane[kLanes];
     bool mask_dist = false;  // the masked path is handed the distance buffer: distances leave, or the reduction or the tally reads them
-    bool tally = false;      // every tile's neighbours are tallied into the handle's s_tally_cnt / s_tally_max (sknnr_stream_set_tally)
-    // zonal statistics (sknnr_stream_set_zonal): every tile's prediction tile is tallied by zone into the handle's
-    // s_zonal_acc / s_zonal_hist; zones_push: the zone codes of the push in progress (one per pushed row)
-    bool zonal = false;
-    int zonal_zones = 0, zonal_c = 0;
-    size_t zonal_hist = 0;  // elements of the class blocks (0: no column has classes)
-    const int32_t* zones_push = nullptr;
-    // distance domain (sknnr_stream_set_domain): every tile's distances are coded against the handle's s_dom_table and
-    // tallied into s_dom_acc; domain_mask: the prediction rows of beyond pixels become NaN in front of the conversion and
-    // the zonal tally; domain_push: where the code plane of the push in progress goes (host; null: it tallies only)
-    bool domain = false, domain_mask = false;
-    DomainSpec domain_spec{};
-    uint8_t* domain_push = nullptr;
+    // The side products every tile feeds, into the `stream` buffers of the handle's member of the same name:
+    // tally (sknnr_stream_set_tally): the tile's neighbours are tallied;
+    // zonal (sknnr_stream_set_zonal): the prediction tile is tallied by zone -- zones by c columns, zonal_hist elements of
+    // class blocks (0: no column has classes);
+    // domain (sknnr_stream_set_domain): the tile's distances are coded against the table and tallied; domain_mask: the
+    // prediction rows of beyond pixels become NaN in front of the conversion and the zonal tally.
+    struct Products {
+        bool tally = false, zonal = false, domain = false;
+        int zonal_zones = 0, zonal_c = 0;
+        size_t zonal_hist = 0;
+        bool domain_mask = false;
+        DomainSpec domain_spec{};
+    } prod;
+    const int32_t* zones_push = nullptr;  // a zonal pipeline: the zone codes of the push in progress (one per pushed row)
+    uint8_t* domain_push = nullptr;  // a domain pipeline: where the push's code plane goes (host; null: it tallies only)
     // neighbour replay (sknnr_replay_begin): the tiles are stored neighbours, decoded on the device where a search would
     // run (replay_tile); replay_src: the arrays of the push in progress; replay_tot / replay_first: pixels, masked and
     // unknown pixels of the tiles that have left so far, and the first push that held unknown values (-1: none yet)
@@ -2708,11 +2786,11 @@ int pipe_prepare_slot(HostPipe& p, int b, long n, bool planes = false) {
     HIP_TRY(sl.dev_x.ensure(x_f64));
     if (planes && !p.replay.on) HIP_TRY(sl.dev_xp.ensure(x_f64));  // (band-first tiles only: the uploaded planes)
     if (p.replay.on) HIP_TRY(sl.mask.valid.ensure((size_t)n));     // (the decode's bad-pixel flags)
-    if (p.zonal) {
+    if (p.prod.zonal) {
         if ((rc = ensure_pinned(sl.pin_z, sl.pin_z_n, (size_t)n))) return rc;
         HIP_TRY(sl.dev_z.ensure((size_t)n));
     }
-    if (p.domain) {
+    if (p.prod.domain) {
         if ((rc = ensure_pinned(sl.pin_dom, sl.pin_dom_n, (size_t)n))) return rc;
         HIP_TRY(sl.dev_dom.ensure((size_t)n));
     }
@@ -2840,7 +2918,7 @@ int replay_tile(HostPipe& p, int b, long n, bool planes, long* d_idx, double* d_
         const ReplayBlankArgs ba{sl.mask.valid.p, n, p.k, p.lane[kLanePred].cols, d_idx, d_dist, d_pred};
         HIP_TRY(launch::replay_blank(ba, st));
     }
-    if (p.tally && (rc = tally_tile(ix, d_dist, d_idx, n, p.k, st))) return rc;
+    if (p.prod.tally && (rc = tally_tile(ix, d_dist, d_idx, n, p.k, st))) return rc;
     const int64_t lr[8] = {0, 0, 0, replay_instance(r.idx_bytes, r.dist_kind, planes), r.ids ? 1 : 0,
                            0, p.k, r.ks};  // ([0 .. 2]: pipe_drain, when the tile has left; [5]: pipe_submit)
     std::copy(lr + 3, lr + 8, ix->last_replay + 3);
@@ -2880,7 +2958,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
         if (p.replay.on) stage_replay(sl.pin_x, p.replay, p.replay_src, p_off, n);
         else if (planes) stage_planes(sl.pin_x, planes, d_x, p.x_esz, p_off, n);
         else parallel_copy(sl.pin_x, q, (size_t)n * d_x * p.x_esz);
-        if (p.zonal) parallel_copy(sl.pin_z, zones, (size_t)n * sizeof(int32_t));
+        if (p.prod.zonal) parallel_copy(sl.pin_z, zones, (size_t)n * sizeof(int32_t));
     }
     const bool planes_in = planes && !p.replay.on;  // (a replayed band-first tile is decoded from its planes as they are)
     const double t_enq = now_ms();
@@ -2891,7 +2969,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
         PlanesArgs pa{sl.dev_xp.p, sl.dev_x.p, n, d_x, n};
         HIP_TRY(launch::planes_to_rows(pa, (int)p.x_esz, ix->st_h2d));
     }
-    if (p.zonal)  // (behind the tile's rows, in front of ev_h2d)
+    if (p.prod.zonal)  // (behind the tile's rows, in front of ev_h2d)
         HIP_TRY(hipMemcpyAsync(sl.dev_z.p, sl.pin_z, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ix->st_h2d));
     long nv = n;  // rows the tile adds to the row offset
     if (p.nodata_dev) {
@@ -2916,12 +2994,12 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     } else if (p.nodata_dev) {
         // (distances only where the slot has packed distances to expand from: mask_ensure sizes them by the same rule)
         rc = mask_finish(ix, p.red, sl.mask, sl.dev_x.p, n, nv, &p.o, p.fill_index, p.mask_dist ? dist.f64() : nullptr, idx.i64(),
-                         want_pred ? pred.f64() : nullptr, p.o.row_offset - p.row_offset0, ix->st_run, p.tally);
+                         want_pred ? pred.f64() : nullptr, p.o.row_offset - p.row_offset0, ix->st_run, p.prod.tally);
         if (rc) return rc;
     } else {
         rc = run_device(ix, sl.dev_x.p, n, &p.o, dist.f64(), idx.i64(), ix->st_run);
         if (rc) return rc;
-        if (p.tally && (rc = tally_tile(ix, dist.f64(), idx.i64(), n, k, ix->st_run))) return rc;
+        if (p.prod.tally && (rc = tally_tile(ix, dist.f64(), idx.i64(), n, k, ix->st_run))) return rc;
         if (want_pred) {
             rc = launch_predict(ix, p.red, dist.f64(), idx.i64(), nullptr, n, k, p.o.weight_mode, p.o.weight_law, pred.f64(), ix->st_run);
             if (rc) return rc;
@@ -2929,16 +3007,16 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     }
     // distance domain: the full-layout float64 distance tile (masked rows are NaN), whether or not the distances leave;
     // with the mask, the prediction rows of beyond pixels become NaN here, in front of the zonal tally and the conversion
-    if (p.domain) {
-        rc = domain_tile(ix, p.domain_spec, dist.f64(), n, k, domain_out ? sl.dev_dom.p : nullptr,
-                         p.domain_mask ? pred.f64() : nullptr, p.lane[kLanePred].cols, ix->st_run);
+    if (p.prod.domain) {
+        rc = domain_tile(ix, p.prod.domain_spec, dist.f64(), n, k, domain_out ? sl.dev_dom.p : nullptr,
+                         p.prod.domain_mask ? pred.f64() : nullptr, p.lane[kLanePred].cols, ix->st_run);
         if (rc) return rc;
     }
     // zonal statistics: the full-layout float64 prediction tile (masked rows are NaN), whether or not this push asked for
     // the predictions, and before any conversion: the kernel converts with the conversion's own device function
-    if (p.zonal) {
+    if (p.prod.zonal) {
         const HostPipe::Lane& pl = p.lane[kLanePred];
-        const ZonalSpec zs{p.zonal_zones, p.zonal_c, pl.dtype, pl.scale, pl.offset, p.zonal_hist > 0};
+        const ZonalSpec zs{p.prod.zonal_zones, p.prod.zonal_c, pl.dtype, pl.scale, pl.offset, p.prod.zonal_hist > 0};
         if ((rc = zonal_tile(ix, zs, pred.f64(), sl.dev_z.p, n, ix->st_run))) return rc;
     }
     // The requested results in the form they leave in, behind everything that produces them: a typed output, and the
@@ -2982,7 +3060,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     std::copy(out, out + kLanes, pd.out);
     pd.planes = planes != nullptr;
     pd.out_stride = out_stride;
-    pd.domain_out = p.domain ? domain_out : nullptr;
+    pd.domain_out = p.prod.domain ? domain_out : nullptr;
     pd.replay_push_no = p.replay_push_no;
     if (p.replay.on) ix->last_replay[5] = ix->search_calls - searches0;  // (searches this tile's submission ran: none)
     p.d2h_slot = b;  // its device-to-host copies are enqueued behind the next tile's rows, or by the flush
@@ -2994,8 +3072,8 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
         if ((rc = pipe_prepare_slot(p, b2, n_next, planes != nullptr))) return rc;
         double* dst = ix->slot[b2].pin_x;
         const size_t bytes = (size_t)n_next * d_x * p.x_esz, esz = p.x_esz;
-        int32_t* dst_z = p.zonal ? ix->slot[b2].pin_z : nullptr;  // (the next tile's zone codes travel with its rows)
-        const int32_t* zones_next = p.zonal ? zones + n : nullptr;
+        int32_t* dst_z = p.prod.zonal ? ix->slot[b2].pin_z : nullptr;  // (the next tile's zone codes travel with its rows)
+        const int32_t* zones_next = p.prod.zonal ? zones + n : nullptr;
         const ReplaySpec rspec = p.replay;
         const ReplaySrc rsrc = p.replay_src;
         p.ahead_done = ix->w_in->post([=]() -> int {
@@ -3046,8 +3124,8 @@ int pipe_submit_rows(HostPipe& p, const void* q_, long nq, void* const out[kLane
         for (int l = 0; l < kLanes; ++l)
             tile_out[l] = out[l] ? (char*)out[l] + lane_tile_offset(c0, p.lane[l].cols, p.lane[l].esz, planes != nullptr) : nullptr;
         int rc = pipe_submit(p, q + c0 * row_bytes, n, tile_out, n_next ? q + c1 * row_bytes : nullptr, n_next, planes, c0,
-                             out_stride, p.zonal ? p.zones_push + c0 : nullptr,
-                             p.domain && p.domain_push ? p.domain_push + c0 : nullptr);
+                             out_stride, p.prod.zonal ? p.zones_push + c0 : nullptr,
+                             p.prod.domain && p.domain_push ? p.domain_push + c0 : nullptr);
         if (rc) return rc;
         c0 = c1;
     }
@@ -3501,22 +3579,18 @@ extern "C" int sknnr_mask_rows(const void* q, int64_t nq, int32_t d_in, int32_t 
     DevBuf<double> nd;
     DevBuf<int> blk;
     DevBuf<long> nv;
-    DevBuf<char> dq;
-    DevBuf<unsigned char> dvalid;
+    Staged<char> dq;
+    Staged<unsigned char> dvalid;
     HIP_TRY(nd.ensure((size_t)d_in));
     HIP_TRY(blk.ensure((size_t)mask_blocks(nq)));
     HIP_TRY(nv.ensure(1));
     HIP_TRY(hipMemcpy(nd.p, nodata, (size_t)d_in * sizeof(double), hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = dq.stage(q, (size_t)nq * row_bytes, mem, kStageIn)) || (rc = dvalid.stage(out_valid, (size_t)nq, mem, kStageOut)))
+        return rc;
     MaskArgs a{};
-    a.x = q;
-    a.valid = out_valid;
-    if (mem == SKNNR_MEM_HOST) {
-        HIP_TRY(dq.ensure((size_t)nq * row_bytes));
-        HIP_TRY(dvalid.ensure((size_t)nq));
-        HIP_TRY(hipMemcpy(dq.p, q, (size_t)nq * row_bytes, hipMemcpyHostToDevice));
-        a.x = dq.p;
-        a.valid = dvalid.p;
-    }
+    a.x = dq.p;
+    a.valid = dvalid.p;
     a.x_dtype = query_dtype;
     a.nq = nq;
     a.d_in = d_in;
@@ -3526,9 +3600,8 @@ extern "C" int sknnr_mask_rows(const void* q, int64_t nq, int32_t d_in, int32_t 
     HIP_TRY(hipStreamSynchronize(st));
     long n_valid = 0;
     HIP_TRY(hipMemcpy(&n_valid, nv.p, sizeof n_valid, hipMemcpyDeviceToHost));
-    if (mem == SKNNR_MEM_HOST) HIP_TRY(hipMemcpy(out_valid, dvalid.p, (size_t)nq, hipMemcpyDeviceToHost));
     if (out_n_valid) *out_n_valid = n_valid;
-    return SKNNR_OK;
+    return dvalid.download();
 }
 
 // ----------------------------------------------------------------------------------------
@@ -3742,23 +3815,20 @@ extern "C" int sknnr_shard_candidates(sknnr_index* ix, const double* q, int64_t 
     if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
-    if (mem == SKNNR_MEM_DEVICE) return run_device(ix, q, nq, o, out_val, (long*)out_idx, (hipStream_t)stream, 1, index_offset);
     // host buffers: one staged round trip (a shard's candidates are an intermediate of a multi-GPU call, not a hot host path)
-    const int k = o->n_neighbors;
+    const size_t n_el = (size_t)nq * o->n_neighbors;
     const int d_x = o->apply_affine ? ix->d_in : ix->d;
-    DevBuf<double> dq, dv;
-    DevBuf<long> di;
-    HIP_TRY(dq.ensure((size_t)nq * d_x));
-    HIP_TRY(dv.ensure((size_t)nq * k));
-    HIP_TRY(di.ensure((size_t)nq * k));
-    HIP_TRY(hipMemcpy(dq.p, q, (size_t)nq * d_x * sizeof(double), hipMemcpyHostToDevice));
-    rc = run_device(ix, dq.p, nq, o, dv.p, di.p, nullptr, 1, index_offset);
-    if (rc) return rc;
+    Staged<double> dq, dv;
+    Staged<long> di;
+    if ((rc = dq.stage(q, (size_t)nq * d_x, mem, kStageIn)) || (rc = dv.stage(out_val, n_el, mem, kStageOut)) ||
+        (rc = di.stage(out_idx, n_el, mem, kStageOut)))
+        return rc;
+    rc = run_device(ix, dq.p, nq, o, dv.p, di.p, mem == SKNNR_MEM_DEVICE ? (hipStream_t)stream : nullptr, 1, index_offset);
+    if (rc || mem == SKNNR_MEM_DEVICE) return rc;
     HIP_TRY(hipDeviceSynchronize());
     if (o->check_finite && (rc = poll_status(ix))) return rc;
-    HIP_TRY(hipMemcpy(out_val, dv.p, (size_t)nq * k * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_idx, di.p, (size_t)nq * k * sizeof(long), hipMemcpyDeviceToHost));
-    return SKNNR_OK;
+    if ((rc = dv.download())) return rc;
+    return di.download();
 }
 
 namespace {
@@ -3846,30 +3916,21 @@ extern "C" int sknnr_merge_shards(sknnr_index* ix, const double* q, int64_t nq, 
     if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
-    if (mem == SKNNR_MEM_DEVICE)
-        return merge_shards_device(ix, q, nq, o, n_shards, shard_val, (const long*)shard_idx, out_dist, (long*)out_idx, (hipStream_t)stream);
-    const int k = o->n_neighbors;
+    const size_t n_el = (size_t)nq * o->n_neighbors;
     const int d_x = o->apply_affine ? ix->d_in : ix->d;
     const size_t n_cand = (size_t)nq * n_shards * kk;
-    DevBuf<double> dq, dv, dd;
-    DevBuf<long> dsi, di;
-    if (q) {
-        HIP_TRY(dq.ensure((size_t)nq * d_x));
-        HIP_TRY(hipMemcpy(dq.p, q, (size_t)nq * d_x * sizeof(double), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(dv.ensure(n_cand));
-    HIP_TRY(dsi.ensure(n_cand));
-    HIP_TRY(dd.ensure((size_t)nq * k));
-    HIP_TRY(di.ensure((size_t)nq * k));
-    HIP_TRY(hipMemcpy(dv.p, shard_val, n_cand * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dsi.p, shard_idx, n_cand * sizeof(long), hipMemcpyHostToDevice));
-    rc = merge_shards_device(ix, q ? dq.p : nullptr, nq, o, n_shards, dv.p, dsi.p, dd.p, di.p, nullptr);
-    if (rc) return rc;
+    Staged<double> dq, dv, dd;
+    Staged<long> dsi, di;
+    if ((rc = dq.stage(q, (size_t)nq * d_x, mem, kStageIn)) || (rc = dv.stage(shard_val, n_cand, mem, kStageIn)) ||
+        (rc = dsi.stage(shard_idx, n_cand, mem, kStageIn)) || (rc = dd.stage(out_dist, n_el, mem, kStageOut)) ||
+        (rc = di.stage(out_idx, n_el, mem, kStageOut)))
+        return rc;
+    rc = merge_shards_device(ix, dq.p, nq, o, n_shards, dv.p, dsi.p, dd.p, di.p, mem == SKNNR_MEM_DEVICE ? (hipStream_t)stream : nullptr);
+    if (rc || mem == SKNNR_MEM_DEVICE) return rc;
     HIP_TRY(hipDeviceSynchronize());
     if (o->check_finite && q && (rc = poll_status(ix))) return rc;
-    if (out_dist) HIP_TRY(hipMemcpy(out_dist, dd.p, (size_t)nq * k * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_idx, di.p, (size_t)nq * k * sizeof(long), hipMemcpyDeviceToHost));
-    return SKNNR_OK;
+    if ((rc = dd.download())) return rc;
+    return di.download();
 }
 
 // ----------------------------------------------------------------------------------------
@@ -3928,21 +3989,14 @@ extern "C" int sknnr_debug_weight_law(int32_t law, double p0, double p1, const d
     a.law = law;
     a.p0 = p0;
     a.p1 = p1;
-    DevBuf<double> dd, dw;  // (host memory: freed by their destructors on every return path)
-    if (mem == SKNNR_MEM_HOST) {
-        HIP_TRY(dd.ensure((size_t)n));
-        HIP_TRY(dw.ensure((size_t)n));
-        HIP_TRY(hipMemcpy(dd.p, dist, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-        a.dist = dd.p;
-        a.w = dw.p;
-    } else {
-        a.dist = dist;
-        a.w = out;
-    }
+    Staged<double> dd, dw;
+    int rc;
+    if ((rc = dd.stage(dist, (size_t)n, mem, kStageIn)) || (rc = dw.stage(out, (size_t)n, mem, kStageOut))) return rc;
+    a.dist = dd.p;
+    a.w = dw.p;
     HIP_TRY(launch::weight_law(a, nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
-    if (mem == SKNNR_MEM_HOST) HIP_TRY(hipMemcpy(out, dw.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    return SKNNR_OK;
+    return dw.download();
 }
 
 // The fields the predict, plan and summary kernels' arguments share, and the predict kernels' two float32 flags
@@ -4089,13 +4143,11 @@ static int reduce_check(const sknnr_index* ix, ReduceSpec& rs, Reduction& red) {
 // s_plan, or a one-shot call's c_stat / c_plan (reduce_upload_call).  A mean, or a table that is all mean, uploads nothing.
 static int reduce_upload(const ReduceSpec& rs, DevBuf<int>& stat_buf, DevBuf<double>& plan_buf, Reduction& red) {
     if (rs.kind == kReduceStats && red.stat.nc) {
-        HIP_TRY(stat_buf.ensure(rs.tab.size()));
-        HIP_TRY(hipMemcpy(stat_buf.p, rs.tab.data(), rs.tab.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (int rc = stat_buf.upload(rs.tab.data(), rs.tab.size())) return rc;
         red.stat.tab = stat_buf.p;
     } else if (rs.kind == kReducePlan) {
         const std::vector<double> img = plan_image(rs.cols, rs.stat, rs.param, rs.n_out);
-        HIP_TRY(plan_buf.ensure(img.size()));
-        HIP_TRY(hipMemcpy(plan_buf.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (int rc = plan_buf.upload(img.data(), img.size())) return rc;
         red.plan.param = plan_buf.p;
         red.plan.cols = (const int*)(plan_buf.p + rs.n_out);
         red.plan.codes = red.plan.cols + rs.n_out;
@@ -4131,27 +4183,16 @@ static int reduce_from_neighbors(sknnr_index* ix, const double* dist, const int6
     std::lock_guard<std::mutex> lock(ix->mtx);
     HIP_TRY(hipSetDevice(ix->device));
     if (const int rc = reduce_upload_call(ix, rs, red)) return rc;
-    const int pc = red.cols(ix->t);
-    if (mem == SKNNR_MEM_DEVICE)
-        return launch_predict(ix, red, dist, (const long*)idx, w, nq, k, mode, kLawNone, out_pred, (hipStream_t)stream);
-    hipStream_t st = nullptr;
-    DevBuf<double> dd, dw, dout;  // freed by their destructors on every return path
-    DevBuf<long> di;
-    HIP_TRY(di.ensure((size_t)nq * k));
-    HIP_TRY(dout.ensure((size_t)nq * pc));
-    HIP_TRY(hipMemcpy(di.p, idx, (size_t)nq * k * sizeof(long), hipMemcpyHostToDevice));
-    if (dist) {
-        HIP_TRY(dd.ensure((size_t)nq * k));
-        HIP_TRY(hipMemcpy(dd.p, dist, (size_t)nq * k * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (w) {
-        HIP_TRY(dw.ensure((size_t)nq * k));
-        HIP_TRY(hipMemcpy(dw.p, w, (size_t)nq * k * sizeof(double), hipMemcpyHostToDevice));
-    }
-    int rc = launch_predict(ix, red, dist ? dd.p : nullptr, di.p, w ? dw.p : nullptr, nq, k, mode, kLawNone, dout.p, st);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_pred, dout.p, (size_t)nq * pc * sizeof(double), hipMemcpyDeviceToHost));
-    return SKNNR_OK;
+    hipStream_t st = mem == SKNNR_MEM_DEVICE ? (hipStream_t)stream : nullptr;
+    const size_t n_el = (size_t)nq * k;
+    Staged<long> di;
+    Staged<double> dd, dw, dout;
+    int rc;
+    if ((rc = di.stage(idx, n_el, mem, kStageIn)) || (rc = dout.stage(out_pred, (size_t)nq * red.cols(ix->t), mem, kStageOut)) ||
+        (rc = dd.stage(dist, n_el, mem, kStageIn)) || (rc = dw.stage(w, n_el, mem, kStageIn)))
+        return rc;
+    if ((rc = launch_predict(ix, red, dd.p, di.p, dw.p, nq, k, mode, kLawNone, dout.p, st))) return rc;
+    return dout.download();
 }
 
 extern "C" int sknnr_predict_from_neighbors(sknnr_index* ix, const double* dist, const int64_t* idx, const double* w,
@@ -4275,13 +4316,27 @@ struct sknnr_stream {
     HostPipe pipe;
     int64_t rows_pushed = 0;
     bool pushed = false;  // a push was accepted: the nodata mask can no longer change
-    // a zonal stream (sknnr_stream_set_zonal): the zone codes of the next push (sknnr_stream_next_zones), the stream's own copy
-    std::vector<int32_t> zones;
-    bool have_zones = false;
-    // a domain stream (sknnr_stream_set_domain): the caller's code plane of the next push (sknnr_stream_next_domain_out)
-    uint8_t* domain_out = nullptr;
-    int64_t domain_out_n = 0;
+    // What the caller named for the next push (which products the stream carries: pipe.prod).  A zonal stream: the zone
+    // codes (sknnr_stream_next_zones), the stream's own copy.  A domain stream: the caller's code plane
+    // (sknnr_stream_next_domain_out).
+    struct {
+        std::vector<int32_t> zones;
+        bool have_zones = false;
+        uint8_t* domain_out = nullptr;
+        int64_t domain_out_n = 0;
+    } next;
 };
+
+// What every collecting entry of a stream does behind its own refusals: takes the handle's lock (held through `lock` when
+// this returns), flushes the pipeline and waits for the stream the tiles' launches ran on; the copies are the caller's.
+static int collect_begin(HostPipe& p, std::unique_lock<std::mutex>& lock) {
+    lock = std::unique_lock<std::mutex>(p.ix->mtx);
+    HIP_TRY(hipSetDevice(p.ix->device));
+    const int rc = pipe_flush(p);
+    if (rc) return pipe_fail(p, rc);
+    HIP_TRY(hipStreamSynchronize(p.ix->st_run));
+    return SKNNR_OK;
+}
 
 extern "C" int sknnr_stream_set_nodata(sknnr_stream* s, const double* nodata, int64_t fill_index) {
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
@@ -4293,8 +4348,7 @@ extern "C" int sknnr_stream_set_nodata(sknnr_stream* s, const double* nodata, in
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_nodata is allowed only before the first push");
     if (p.d_x > kMaskMaxCols) return fail(SKNNR_ERR_UNSUPPORTED, "more than %d input columns with a nodata mask", kMaskMaxCols);
     HIP_TRY(hipSetDevice(p.ix->device));
-    HIP_TRY(p.ix->s_nodata.ensure((size_t)p.d_x));
-    HIP_TRY(hipMemcpy(p.ix->s_nodata.p, nodata, (size_t)p.d_x * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = p.ix->s_nodata.upload(nodata, (size_t)p.d_x)) return rc;
     p.nodata_dev = p.ix->s_nodata.p;
     p.fill_index = fill_index;
     return SKNNR_OK;
@@ -4310,6 +4364,17 @@ static int stage_refusal(const HostPipe& p, int own, const char* what) {
     return fail(SKNNR_ERR_INVALID, "the stream has %s: it takes no %s", has[kind], what);
 }
 
+// What every setter of a stage or a side product does behind its own argument checks: takes the handle's lock (held
+// through `lock` when this returns), refuses after the first push under the entry's name, asks the reduction stage
+// (stage_refusal with the setter's kind and label) and selects the device.
+static int setter_begin(sknnr_stream* s, std::unique_lock<std::mutex>& lock, const char* entry, int own, const char* what) {
+    lock = std::unique_lock<std::mutex>(s->pipe.ix->mtx);
+    if (s->pushed) return fail(SKNNR_ERR_INVALID, "%s is allowed only before the first push", entry);
+    if (int no = stage_refusal(s->pipe, own, what)) return no;
+    HIP_TRY(hipSetDevice(s->pipe.ix->device));
+    return SKNNR_OK;
+}
+
 extern "C" int sknnr_stream_set_statistics(sknnr_stream* s, const int32_t* stat, int32_t t) {
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     HostPipe& p = s->pipe;
@@ -4319,10 +4384,8 @@ extern "C" int sknnr_stream_set_statistics(sknnr_stream* s, const int32_t* stat,
     Reduction red;
     int rc = reduce_check(p.ix, rs, red);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lock(p.ix->mtx);
-    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_statistics is allowed only before the first push");
-    if ((rc = stage_refusal(p, kReduceStats, "per-target statistics"))) return rc;
-    HIP_TRY(hipSetDevice(p.ix->device));
+    std::unique_lock<std::mutex> lock;
+    if ((rc = setter_begin(s, lock, "sknnr_stream_set_statistics", kReduceStats, "per-target statistics"))) return rc;
     if ((rc = reduce_upload(rs, p.ix->s_stat, p.ix->s_plan, red))) return rc;
     p.red = red;  // (an all-mean table: the stream enqueues what it did without one, and still takes no other stage)
     return SKNNR_OK;
@@ -4337,13 +4400,11 @@ extern "C" int sknnr_stream_set_plan(sknnr_stream* s, const int32_t* cols, const
     Reduction red;
     int rc = reduce_check(p.ix, rs, red);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lock(p.ix->mtx);
-    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan is allowed only before the first push");
-    if ((rc = stage_refusal(p, kReducePlan, "output plan"))) return rc;
-    if (p.zonal) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan comes before sknnr_stream_set_zonal: n_classes holds one value per output plane");
+    std::unique_lock<std::mutex> lock;
+    if ((rc = setter_begin(s, lock, "sknnr_stream_set_plan", kReducePlan, "output plan"))) return rc;
+    if (p.prod.zonal) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan comes before sknnr_stream_set_zonal: n_classes holds one value per output plane");
     if (p.lane[kLanePred].scale)
         return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_plan comes before sknnr_stream_set_output: the scale / offset hold one value per output plane");
-    HIP_TRY(hipSetDevice(p.ix->device));
     if ((rc = reduce_upload(rs, p.ix->s_stat, p.ix->s_plan, red))) return rc;
     p.red = red;
     p.lane[kLanePred].cols = n_out;  // from now on the prediction lane is n_out wide
@@ -4375,10 +4436,8 @@ extern "C" int sknnr_stream_set_output(sknnr_stream* s, int32_t idx_dtype, int32
     if (pred_scale) {
         HIP_TRY(hipSetDevice(p.ix->device));
         const size_t pc = (size_t)p.lane[kLanePred].cols;  // (one value per output plane: the plan's entries, or the targets)
-        HIP_TRY(p.ix->s_scale.ensure(pc));
-        HIP_TRY(p.ix->s_offset.ensure(pc));
-        HIP_TRY(hipMemcpy(p.ix->s_scale.p, pred_scale, pc * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(p.ix->s_offset.p, pred_offset, pc * sizeof(double), hipMemcpyHostToDevice));
+        if (int rc = p.ix->s_scale.upload(pred_scale, pc)) return rc;
+        if (int rc = p.ix->s_offset.upload(pred_offset, pc)) return rc;
         pl.scale = p.ix->s_scale.p;
         pl.offset = p.ix->s_offset.p;
     }
@@ -4401,8 +4460,7 @@ extern "C" int sknnr_stream_set_id_table(sknnr_stream* s, const int64_t* table, 
     std::lock_guard<std::mutex> lock(p.ix->mtx);
     if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_id_table is allowed only before the first push");
     HIP_TRY(hipSetDevice(p.ix->device));
-    HIP_TRY(p.ix->s_id_table.ensure((size_t)n_table));
-    HIP_TRY(hipMemcpy(p.ix->s_id_table.p, table, (size_t)n_table * sizeof(long), hipMemcpyHostToDevice));
+    if (int rc = p.ix->s_id_table.upload(table, (size_t)n_table)) return rc;
     HostPipe::Lane& il = p.lane[kLaneIdx];
     il.table = p.ix->s_id_table.p;
     il.has_fill = 1;  // (every negative index of a tile is the nodata expansion's fill_index)
@@ -4422,19 +4480,17 @@ static int launch_tally(sknnr_index* ix, const double* dist, const long* idx, lo
     a.n_ref = ix->n_ref;
     a.cnt = cnt;
     a.maxbits = maxbits;
-    a.rec = ix->tally_rec.p + half * kTallyRecWords;
+    a.rec = ix->tally.rec.at(half);
     HIP_TRY(launch::tally(a, st));
     return SKNNR_OK;
 }
 
 static int tally_tile(sknnr_index* ix, const double* dist, const long* idx, long n, int k, hipStream_t st) {
     if (!dist) return fail(SKNNR_ERR_INVALID, "a tallied tile needs its distances");
-    const int rc = launch_tally(ix, dist, idx, n, k, ix->s_tally_cnt.p, ix->s_tally_max.p, 1, st);
+    const int rc = launch_tally(ix, dist, idx, n, k, ix->tally.stream.cnt.p, ix->tally.stream.max.p, 1, st);
     if (rc) return rc;
-    ix->last_tally[0] = 1;
-    ix->last_tally[1] += n;
-    ix->last_tally[2] = k;
-    ix->last_tally_half = 1;
+    ix->tally.rec.ran(1, n);
+    ix->tally.rec.host[2] = k;
     return SKNNR_OK;
 }
 
@@ -4460,49 +4516,26 @@ extern "C" int sknnr_tally_from_neighbors(sknnr_index* ix, const double* dist, c
     HIP_TRY(hipSetDevice(ix->device));
     const size_t n_cnt = (size_t)ix->n_ref * k, n_max = (size_t)ix->n_ref, n_el = (size_t)nq * k;
     hipStream_t st = mem == SKNNR_MEM_DEVICE ? (hipStream_t)stream : nullptr;
-    HIP_TRY(ix->tally_rec.ensure(2 * kTallyRecWords));
-    HIP_TRY(hipMemsetAsync(ix->tally_rec.p, 0, kTallyRecWords * sizeof(unsigned long long), st));
-    ix->last_tally[0] = nq > 0 ? 1 : 0;
-    ix->last_tally[1] = nq;
-    ix->last_tally[2] = k;
-    ix->last_tally_half = 0;
+    HIP_TRY(ix->tally.rec.ensure());
+    HIP_TRY(ix->tally.rec.reset(0, st, {nq > 0 ? 1 : 0, nq, k}));
     // (int64 counts and float64 maxima ARE the accumulators: the same 8-byte patterns)
-    unsigned long long* cnt = (unsigned long long*)counts;
-    unsigned long long* mx = (unsigned long long*)max_dist;
-    const long* di = (const long*)idx;
-    const double* dd = dist;
-    DevBuf<unsigned long long> dcnt, dmax;  // (host memory: freed by their destructors on every return path)
-    DevBuf<long> didx;
-    DevBuf<double> ddist;
-    if (mem == SKNNR_MEM_HOST) {
-        HIP_TRY(dcnt.ensure(n_cnt));
-        if (max_dist) HIP_TRY(dmax.ensure(n_max));
-        HIP_TRY(didx.ensure(n_el));
-        if (dist) HIP_TRY(ddist.ensure(n_el));
-        if (n_el) HIP_TRY(hipMemcpy(didx.p, idx, n_el * sizeof(long), hipMemcpyHostToDevice));
-        if (n_el && dist) HIP_TRY(hipMemcpy(ddist.p, dist, n_el * sizeof(double), hipMemcpyHostToDevice));
-        if (accumulate) {
-            HIP_TRY(hipMemcpy(dcnt.p, counts, n_cnt * 8, hipMemcpyHostToDevice));
-            if (max_dist) HIP_TRY(hipMemcpy(dmax.p, max_dist, n_max * 8, hipMemcpyHostToDevice));
-        }
-        cnt = dcnt.p;
-        mx = max_dist ? dmax.p : nullptr;
-        di = didx.p;
-        dd = dist ? ddist.p : nullptr;
-    }
+    const int acc_dir = accumulate ? kStageInOut : kStageOut;
+    Staged<long> di;
+    Staged<double> dd;
+    Staged<unsigned long long> cnt, mx;
+    if ((rc = di.stage(idx, n_el, mem, kStageIn)) || (rc = dd.stage(dist, n_el, mem, kStageIn)) ||
+        (rc = cnt.stage(counts, n_cnt, mem, acc_dir)) || (rc = mx.stage(max_dist, n_max, mem, acc_dir)))
+        return rc;
     if (!accumulate) {
-        HIP_TRY(hipMemsetAsync(cnt, 0, n_cnt * 8, st));
-        if (mx) HIP_TRY(hipMemsetAsync(mx, 0, n_max * 8, st));
-    } else if (mx) {
-        HIP_TRY(launch::tally_clean((double*)mx, (long)n_max, st));
+        HIP_TRY(hipMemsetAsync(cnt.p, 0, n_cnt * 8, st));
+        if (mx.p) HIP_TRY(hipMemsetAsync(mx.p, 0, n_max * 8, st));
+    } else if (mx.p) {
+        HIP_TRY(launch::tally_clean((double*)mx.p, (long)n_max, st));
     }
-    if ((rc = launch_tally(ix, dd, di, nq, k, cnt, mx, 0, st))) return rc;
-    if (mem == SKNNR_MEM_HOST) {
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(counts, dcnt.p, n_cnt * 8, hipMemcpyDeviceToHost));
-        if (max_dist) HIP_TRY(hipMemcpy(max_dist, dmax.p, n_max * 8, hipMemcpyDeviceToHost));
-    }
-    return SKNNR_OK;
+    if ((rc = launch_tally(ix, dd.p, di.p, nq, k, cnt.p, mx.p, 0, st))) return rc;
+    if (mem == SKNNR_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = cnt.download())) return rc;
+    return mx.download();
 }
 
 extern "C" int sknnr_stream_set_tally(sknnr_stream* s) {
@@ -4513,23 +4546,19 @@ extern "C" int sknnr_stream_set_tally(sknnr_stream* s) {
     if (rc) return rc;
     if (p.replay.on && p.replay.dist_kind == kReplayDistNone)
         return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_tally: the replay stream was opened without stored distances, and the tally keeps their maxima");
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_tally is allowed only before the first push");
-    if (int no = stage_refusal(p, kReduceMean, "usage tally")) return no;
-    HIP_TRY(hipSetDevice(ix->device));
+    std::unique_lock<std::mutex> lock;
+    if (int no = setter_begin(s, lock, "sknnr_stream_set_tally", kReduceMean, "usage tally")) return no;
     const size_t n_cnt = (size_t)ix->n_ref * p.k, n_max = (size_t)ix->n_ref;
-    HIP_TRY(ix->s_tally_cnt.ensure(n_cnt));
-    HIP_TRY(ix->s_tally_max.ensure(n_max));
-    HIP_TRY(ix->tally_rec.ensure(2 * kTallyRecWords));
+    auto& ts = ix->tally.stream;
+    HIP_TRY(ts.cnt.ensure(n_cnt));
+    HIP_TRY(ts.max.ensure(n_max));
+    HIP_TRY(ix->tally.rec.ensure());
     // (on the stream every tile's tally runs on: zeroed in front of the first of them)
-    HIP_TRY(hipMemsetAsync(ix->s_tally_cnt.p, 0, n_cnt * 8, ix->st_run));
-    HIP_TRY(hipMemsetAsync(ix->s_tally_max.p, 0, n_max * 8, ix->st_run));
-    HIP_TRY(hipMemsetAsync(ix->tally_rec.p + kTallyRecWords, 0, kTallyRecWords * sizeof(unsigned long long), ix->st_run));
-    p.tally = true;
+    HIP_TRY(hipMemsetAsync(ts.cnt.p, 0, n_cnt * 8, ix->st_run));
+    HIP_TRY(hipMemsetAsync(ts.max.p, 0, n_max * 8, ix->st_run));
+    HIP_TRY(ix->tally.rec.reset(1, ix->st_run, {0, 0, p.k}));
+    p.prod.tally = true;
     p.mask_dist = true;  // the masked path keeps the search's distances whether or not they leave
-    ix->last_tally[0] = ix->last_tally[1] = 0;
-    ix->last_tally[2] = p.k;
-    ix->last_tally_half = 1;
     return SKNNR_OK;
 }
 
@@ -4537,30 +4566,21 @@ extern "C" int sknnr_stream_get_tally(sknnr_stream* s, int64_t* counts, double* 
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     HostPipe& p = s->pipe;
     sknnr_index* ix = p.ix;
-    if (!p.tally) return fail(SKNNR_ERR_INVALID, "the stream tallies nothing: sknnr_stream_set_tally was not called");
+    if (!p.prod.tally) return fail(SKNNR_ERR_INVALID, "the stream tallies nothing: sknnr_stream_set_tally was not called");
     if (!counts && !max_dist) return fail(SKNNR_ERR_INVALID, "counts and max_dist are both NULL");
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    HIP_TRY(hipSetDevice(ix->device));
-    const int rc = pipe_flush(p);
-    if (rc) return pipe_fail(p, rc);
-    HIP_TRY(hipStreamSynchronize(ix->st_run));
-    if (counts) HIP_TRY(hipMemcpy(counts, ix->s_tally_cnt.p, (size_t)ix->n_ref * p.k * 8, hipMemcpyDeviceToHost));
-    if (max_dist) HIP_TRY(hipMemcpy(max_dist, ix->s_tally_max.p, (size_t)ix->n_ref * 8, hipMemcpyDeviceToHost));
+    std::unique_lock<std::mutex> lock;
+    if (const int rc = collect_begin(p, lock)) return rc;
+    if (counts) HIP_TRY(hipMemcpy(counts, ix->tally.stream.cnt.p, (size_t)ix->n_ref * p.k * 8, hipMemcpyDeviceToHost));
+    if (max_dist) HIP_TRY(hipMemcpy(max_dist, ix->tally.stream.max.p, (size_t)ix->n_ref * 8, hipMemcpyDeviceToHost));
     return SKNNR_OK;
 }
 
 extern "C" int sknnr_debug_last_tally(const sknnr_index* cix, int64_t out[8]) {
     if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    std::fill(out, out + 8, 0);
-    std::copy(ix->last_tally, ix->last_tally + 3, out);
-    out[7] = kTallySlots;
-    if (!ix->tally_rec.p) return SKNNR_OK;
     unsigned long long w[kTallyRecWords];
-    HIP_TRY(hipSetDevice(ix->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(w, ix->tally_rec.p + ix->last_tally_half * kTallyRecWords, sizeof w, hipMemcpyDeviceToHost));
+    if (const int rc = ix->tally.rec.read(ix->mtx, ix->device, out, w)) return rc;
+    out[7] = kTallySlots;
     out[3] = (int64_t)w[kTallyRecTallied];
     out[4] = (int64_t)w[kTallyRecSkipped];
     out[5] = (int64_t)w[kTallyRecAtomics];
@@ -4585,20 +4605,18 @@ static int launch_zonal(sknnr_index* ix, const ZonalSpec& z, const double* v, co
     a.hist_off = z.classes ? off : nullptr;
     a.acc = acc;
     a.hist = z.classes ? hist : nullptr;
-    a.rec = ix->zonal_rec.p + half * kZonalRecWords;
+    a.rec = ix->zonal.rec.at(half);
     HIP_TRY(launch::zonal(a, z.dtype, st));
     return SKNNR_OK;
 }
 
 static int zonal_tile(sknnr_index* ix, const ZonalSpec& z, const double* pred, const int32_t* zones, long n, hipStream_t st) {
     if (!pred || !zones) return fail(SKNNR_ERR_INVALID, "a zonal tile needs its predictions and its zone codes");
-    const int rc = launch_zonal(ix, z, pred, zones, n, ix->s_zonal_cls.p, ix->s_zonal_off.p, ix->s_zonal_acc.p,
-                                ix->s_zonal_hist.p, 1, st);
+    const auto& zs = ix->zonal.stream;
+    const int rc = launch_zonal(ix, z, pred, zones, n, zs.cls.p, zs.off.p, zs.acc.p, zs.hist.p, 1, st);
     if (rc) return rc;
-    ix->last_zonal[0] = 1;
-    ix->last_zonal[1] += n;
-    ix->last_zonal[2] = z.c;
-    ix->last_zonal_half = 1;
+    ix->zonal.rec.ran(1, n);
+    ix->zonal.rec.host[2] = z.c;
     return SKNNR_OK;
 }
 
@@ -4649,62 +4667,33 @@ extern "C" int sknnr_zonal_from_values(sknnr_index* ix, const double* values, co
     const bool classes = n_hist > 0;
     // the handle's parameter buffers: an earlier call on `st` may still read them
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(ix->zonal_rec.ensure(2 * kZonalRecWords));
+    HIP_TRY(ix->zonal.rec.ensure());
+    auto& zc = ix->zonal.call;
     ZonalSpec z{(int)n_zones, c, dst_dtype, nullptr, nullptr, classes};
     if (scale) {
-        HIP_TRY(ix->zonal_par.ensure(2 * (size_t)c));
-        HIP_TRY(hipMemcpy(ix->zonal_par.p, scale, (size_t)c * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ix->zonal_par.p + c, offset, (size_t)c * sizeof(double), hipMemcpyHostToDevice));
-        z.scale = ix->zonal_par.p;
-        z.offset = ix->zonal_par.p + c;
+        HIP_TRY(zc.par.ensure(2 * (size_t)c));
+        HIP_TRY(hipMemcpy(zc.par.p, scale, (size_t)c * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(zc.par.p + c, offset, (size_t)c * sizeof(double), hipMemcpyHostToDevice));
+        z.scale = zc.par.p;
+        z.offset = zc.par.p + c;
     }
-    if (classes) {
-        HIP_TRY(ix->zonal_cls.ensure((size_t)c));
-        HIP_TRY(ix->zonal_off.ensure((size_t)c));
-        HIP_TRY(hipMemcpy(ix->zonal_cls.p, n_classes, (size_t)c * sizeof(int), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ix->zonal_off.p, off.data(), (size_t)c * sizeof(long), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemsetAsync(ix->zonal_rec.p, 0, kZonalRecWords * sizeof(unsigned long long), st));
-    ix->last_zonal[0] = n > 0 ? 1 : 0;
-    ix->last_zonal[1] = n;
-    ix->last_zonal[2] = c;
-    ix->last_zonal_half = 0;
-    long long* da = (long long*)acc;
-    long long* dh = (long long*)hist;
-    const double* dv = values;
-    const int32_t* dz = zones;
-    DevBuf<long long> bacc, bhist;  // (host memory: freed by their destructors on every return path)
-    DevBuf<double> bval;
-    DevBuf<int32_t> bzones;
-    if (mem == SKNNR_MEM_HOST) {
-        HIP_TRY(bacc.ensure(n_acc));
-        if (classes) HIP_TRY(bhist.ensure(n_hist));
-        HIP_TRY(bval.ensure(n_el));
-        HIP_TRY(bzones.ensure((size_t)n));
-        if (n) {
-            HIP_TRY(hipMemcpy(bval.p, values, n_el * sizeof(double), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(bzones.p, zones, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        if (accumulate) {
-            HIP_TRY(hipMemcpy(bacc.p, acc, n_acc * 8, hipMemcpyHostToDevice));
-            if (classes) HIP_TRY(hipMemcpy(bhist.p, hist, n_hist * 8, hipMemcpyHostToDevice));
-        }
-        da = bacc.p;
-        dh = classes ? bhist.p : nullptr;
-        dv = bval.p;
-        dz = bzones.p;
-    }
+    if (classes && ((rc = zc.cls.upload(n_classes, (size_t)c)) || (rc = zc.off.upload(off.data(), (size_t)c)))) return rc;
+    HIP_TRY(ix->zonal.rec.reset(0, st, {n > 0 ? 1 : 0, n, c}));
+    const int acc_dir = accumulate ? kStageInOut : kStageOut;
+    Staged<double> dv;
+    Staged<int32_t> dz;
+    Staged<long long> da, dh;
+    if ((rc = dv.stage(values, n_el, mem, kStageIn)) || (rc = dz.stage(zones, (size_t)n, mem, kStageIn)) ||
+        (rc = da.stage(acc, n_acc, mem, acc_dir)) || (rc = dh.stage(classes ? hist : nullptr, n_hist, mem, acc_dir)))
+        return rc;
     if (!accumulate) {
-        HIP_TRY(launch::zonal_init(da, (long)((size_t)n_zones * c), st));
-        if (classes) HIP_TRY(hipMemsetAsync(dh, 0, n_hist * 8, st));
+        HIP_TRY(launch::zonal_init(da.p, (long)((size_t)n_zones * c), st));
+        if (classes) HIP_TRY(hipMemsetAsync(dh.p, 0, n_hist * 8, st));
     }
-    if ((rc = launch_zonal(ix, z, dv, dz, n, ix->zonal_cls.p, ix->zonal_off.p, da, dh, 0, st))) return rc;
-    if (mem == SKNNR_MEM_HOST) {
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(acc, bacc.p, n_acc * 8, hipMemcpyDeviceToHost));
-        if (classes) HIP_TRY(hipMemcpy(hist, bhist.p, n_hist * 8, hipMemcpyDeviceToHost));
-    }
-    return SKNNR_OK;
+    if ((rc = launch_zonal(ix, z, dv.p, dz.p, n, zc.cls.p, zc.off.p, da.p, dh.p, 0, st))) return rc;
+    if (mem == SKNNR_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = da.download())) return rc;
+    return dh.download();
 }
 
 extern "C" int sknnr_stream_set_zonal(sknnr_stream* s, int64_t n_zones, const int32_t* n_classes) {
@@ -4717,44 +4706,38 @@ extern "C" int sknnr_stream_set_zonal(sknnr_stream* s, int64_t n_zones, const in
     size_t n_hist = 0;
     const int rc = zonal_check_shape(n_zones, c, n_classes, off, &n_hist);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_zonal is allowed only before the first push");
-    if (int no = stage_refusal(p, kReduceMean, "zonal statistics")) return no;
-    HIP_TRY(hipSetDevice(ix->device));
+    std::unique_lock<std::mutex> lock;
+    if (int no = setter_begin(s, lock, "sknnr_stream_set_zonal", kReduceMean, "zonal statistics")) return no;
     const size_t n_keys = (size_t)n_zones * c;
-    HIP_TRY(ix->s_zonal_acc.ensure(n_keys * kZonalFields));
-    HIP_TRY(ix->s_zonal_hist.ensure(n_hist));
-    HIP_TRY(ix->zonal_rec.ensure(2 * kZonalRecWords));
+    auto& zs = ix->zonal.stream;
+    HIP_TRY(zs.acc.ensure(n_keys * kZonalFields));
+    HIP_TRY(zs.hist.ensure(n_hist));
+    HIP_TRY(ix->zonal.rec.ensure());
     if (n_hist) {
-        HIP_TRY(ix->s_zonal_cls.ensure((size_t)c));
-        HIP_TRY(ix->s_zonal_off.ensure((size_t)c));
-        HIP_TRY(hipMemcpy(ix->s_zonal_cls.p, n_classes, (size_t)c * sizeof(int), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ix->s_zonal_off.p, off.data(), (size_t)c * sizeof(long), hipMemcpyHostToDevice));
+        if (int no = zs.cls.upload(n_classes, (size_t)c)) return no;
+        if (int no = zs.off.upload(off.data(), (size_t)c)) return no;
     }
     // (on the stream every tile's launch runs on: initialised in front of the first of them)
-    HIP_TRY(launch::zonal_init(ix->s_zonal_acc.p, (long)n_keys, ix->st_run));
-    if (n_hist) HIP_TRY(hipMemsetAsync(ix->s_zonal_hist.p, 0, n_hist * 8, ix->st_run));
-    HIP_TRY(hipMemsetAsync(ix->zonal_rec.p + kZonalRecWords, 0, kZonalRecWords * sizeof(unsigned long long), ix->st_run));
-    p.zonal = true;
-    p.zonal_zones = (int)n_zones;
-    p.zonal_c = c;
-    p.zonal_hist = n_hist;
-    s->have_zones = false;
-    ix->last_zonal[0] = ix->last_zonal[1] = 0;
-    ix->last_zonal[2] = c;
-    ix->last_zonal_half = 1;
+    HIP_TRY(launch::zonal_init(zs.acc.p, (long)n_keys, ix->st_run));
+    if (n_hist) HIP_TRY(hipMemsetAsync(zs.hist.p, 0, n_hist * 8, ix->st_run));
+    HIP_TRY(ix->zonal.rec.reset(1, ix->st_run, {0, 0, c}));
+    p.prod.zonal = true;
+    p.prod.zonal_zones = (int)n_zones;
+    p.prod.zonal_c = c;
+    p.prod.zonal_hist = n_hist;
+    s->next.have_zones = false;
     return SKNNR_OK;
 }
 
 extern "C" int sknnr_stream_next_zones(sknnr_stream* s, const int32_t* zones, int64_t nq) {
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
-    if (!s->pipe.zonal) return fail(SKNNR_ERR_INVALID, "the stream has no zones: sknnr_stream_set_zonal was not called");
+    if (!s->pipe.prod.zonal) return fail(SKNNR_ERR_INVALID, "the stream has no zones: sknnr_stream_set_zonal was not called");
     if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
     if (nq == 0) return SKNNR_OK;  // (a push of no rows takes none)
     if (!zones) return fail(SKNNR_ERR_INVALID, "zones is NULL");
     std::lock_guard<std::mutex> lock(s->pipe.ix->mtx);
-    s->zones.assign(zones, zones + nq);
-    s->have_zones = true;
+    s->next.zones.assign(zones, zones + nq);
+    s->next.have_zones = true;
     return SKNNR_OK;
 }
 
@@ -4762,30 +4745,22 @@ extern "C" int sknnr_stream_get_zonal(sknnr_stream* s, int64_t* acc, int64_t* hi
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     HostPipe& p = s->pipe;
     sknnr_index* ix = p.ix;
-    if (!p.zonal) return fail(SKNNR_ERR_INVALID, "the stream has no zones: sknnr_stream_set_zonal was not called");
+    if (!p.prod.zonal) return fail(SKNNR_ERR_INVALID, "the stream has no zones: sknnr_stream_set_zonal was not called");
     if (!acc && !hist) return fail(SKNNR_ERR_INVALID, "acc and hist are both NULL");
-    if (hist && !p.zonal_hist) return fail(SKNNR_ERR_INVALID, "hist is given and no column has classes");
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    HIP_TRY(hipSetDevice(ix->device));
-    const int rc = pipe_flush(p);
-    if (rc) return pipe_fail(p, rc);
-    HIP_TRY(hipStreamSynchronize(ix->st_run));
-    if (acc) HIP_TRY(hipMemcpy(acc, ix->s_zonal_acc.p, (size_t)p.zonal_zones * p.zonal_c * kZonalFields * 8, hipMemcpyDeviceToHost));
-    if (hist) HIP_TRY(hipMemcpy(hist, ix->s_zonal_hist.p, p.zonal_hist * 8, hipMemcpyDeviceToHost));
+    if (hist && !p.prod.zonal_hist) return fail(SKNNR_ERR_INVALID, "hist is given and no column has classes");
+    std::unique_lock<std::mutex> lock;
+    if (const int rc = collect_begin(p, lock)) return rc;
+    const auto& zs = ix->zonal.stream;
+    if (acc) HIP_TRY(hipMemcpy(acc, zs.acc.p, (size_t)p.prod.zonal_zones * p.prod.zonal_c * kZonalFields * 8, hipMemcpyDeviceToHost));
+    if (hist) HIP_TRY(hipMemcpy(hist, zs.hist.p, p.prod.zonal_hist * 8, hipMemcpyDeviceToHost));
     return SKNNR_OK;
 }
 
 extern "C" int sknnr_debug_last_zonal(const sknnr_index* cix, int64_t out[8]) {
     if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    std::fill(out, out + 8, 0);
-    std::copy(ix->last_zonal, ix->last_zonal + 3, out);
-    if (!ix->zonal_rec.p) return SKNNR_OK;
     unsigned long long w[kZonalRecWords];
-    HIP_TRY(hipSetDevice(ix->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(w, ix->zonal_rec.p + ix->last_zonal_half * kZonalRecWords, sizeof w, hipMemcpyDeviceToHost));
+    if (const int rc = ix->zonal.rec.read(ix->mtx, ix->device, out, w)) return rc;
     // (eight words: the sixth counter, entries without a slot, does not fit; they show in the atomics)
     out[3] = (int64_t)w[kZonalRecTallied];
     out[4] = (int64_t)w[kZonalRecNan];
@@ -4821,7 +4796,7 @@ static int launch_domain(sknnr_index* ix, const DomainSpec& d, const double* tab
     a.acc = acc;
     a.pred = pred;
     a.pred_cols = pred_cols;
-    a.rec = ix->dom_rec.p + half * kDomainRecWords;
+    a.rec = ix->domain.rec.at(half);
     HIP_TRY(launch::domain(a, st));
     return SKNNR_OK;
 }
@@ -4829,11 +4804,10 @@ static int launch_domain(sknnr_index* ix, const DomainSpec& d, const double* tab
 static int domain_tile(sknnr_index* ix, const DomainSpec& d, const double* dist, long n, int k, uint8_t* codes, double* pred,
                        int pred_cols, hipStream_t st) {
     if (!dist) return fail(SKNNR_ERR_INVALID, "a domain tile needs its distances");
-    const int rc = launch_domain(ix, d, ix->s_dom_table.p, dist, n, k, codes, ix->s_dom_acc.p, pred, pred_cols, 1, st);
+    const auto& ds = ix->domain.stream;
+    const int rc = launch_domain(ix, d, ds.table.p, dist, n, k, codes, ds.acc.p, pred, pred_cols, 1, st);
     if (rc) return rc;
-    ix->last_domain[0] = 1;
-    ix->last_domain[1] += n;
-    ix->last_domain_half = 1;
+    ix->domain.rec.ran(1, n);
     return SKNNR_OK;
 }
 
@@ -4871,39 +4845,22 @@ extern "C" int sknnr_domain_from_neighbors(sknnr_index* ix, const double* dist, 
     hipStream_t st = mem == SKNNR_MEM_DEVICE ? (hipStream_t)stream : nullptr;
     // the handle's table: an earlier call on `st` may still read it
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(ix->dom_table.ensure((size_t)m));
-    HIP_TRY(hipMemcpy(ix->dom_table.p, table, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(ix->dom_rec.ensure(2 * kDomainRecWords));
-    HIP_TRY(hipMemsetAsync(ix->dom_rec.p, 0, kDomainRecWords * sizeof(unsigned long long), st));
-    const int64_t rec[5] = {nq > 0 ? 1 : 0, nq, k, rank, m};
-    std::copy(rec, rec + 5, ix->last_domain);
-    ix->last_domain_half = 0;
+    DevBuf<double>& dtable = ix->domain.call.table;
+    if ((rc = dtable.upload(table, (size_t)m))) return rc;
+    HIP_TRY(ix->domain.rec.ensure());
+    HIP_TRY(ix->domain.rec.reset(0, st, {nq > 0 ? 1 : 0, nq, k, rank, m}));
     const DomainSpec d{rank - 1, (long)m, has_threshold != 0, threshold};
-    const size_t n_el = (size_t)nq * k;
-    unsigned long long* da = (unsigned long long*)acc;  // (int64 counters ARE the accumulators: the same 8-byte patterns)
-    const double* dd = dist;
-    uint8_t* dc = codes;
-    DevBuf<unsigned long long> bacc;  // (host memory: freed by their destructors on every return path)
-    DevBuf<double> bdist;
-    DevBuf<uint8_t> bcodes;
-    if (mem == SKNNR_MEM_HOST) {
-        HIP_TRY(bacc.ensure(kDomainAcc));
-        HIP_TRY(bdist.ensure(n_el));
-        if (codes) HIP_TRY(bcodes.ensure((size_t)nq));
-        if (n_el) HIP_TRY(hipMemcpy(bdist.p, dist, n_el * sizeof(double), hipMemcpyHostToDevice));
-        if (accumulate) HIP_TRY(hipMemcpy(bacc.p, acc, kDomainAcc * 8, hipMemcpyHostToDevice));
-        da = bacc.p;
-        dd = bdist.p;
-        dc = codes ? bcodes.p : nullptr;
-    }
-    if (!accumulate) HIP_TRY(hipMemsetAsync(da, 0, kDomainAcc * 8, st));
-    if ((rc = launch_domain(ix, d, ix->dom_table.p, dd, nq, k, dc, da, nullptr, 0, 0, st))) return rc;
-    if (mem == SKNNR_MEM_HOST) {
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(acc, bacc.p, kDomainAcc * 8, hipMemcpyDeviceToHost));
-        if (codes && nq) HIP_TRY(hipMemcpy(codes, bcodes.p, (size_t)nq, hipMemcpyDeviceToHost));
-    }
-    return SKNNR_OK;
+    Staged<double> dd;
+    Staged<uint8_t> dc;
+    Staged<unsigned long long> da;  // (int64 counters ARE the accumulators: the same 8-byte patterns)
+    if ((rc = dd.stage(dist, (size_t)nq * k, mem, kStageIn)) || (rc = dc.stage(codes, (size_t)nq, mem, kStageOut)) ||
+        (rc = da.stage(acc, kDomainAcc, mem, accumulate ? kStageInOut : kStageOut)))
+        return rc;
+    if (!accumulate) HIP_TRY(hipMemsetAsync(da.p, 0, kDomainAcc * 8, st));
+    if ((rc = launch_domain(ix, d, dtable.p, dd.p, nq, k, dc.p, da.p, nullptr, 0, 0, st))) return rc;
+    if (mem == SKNNR_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = da.download())) return rc;
+    return dc.download();
 }
 
 extern "C" int sknnr_stream_set_domain(sknnr_stream* s, const double* table, int64_t m, int32_t rank, int32_t has_threshold,
@@ -4917,37 +4874,32 @@ extern "C" int sknnr_stream_set_domain(sknnr_stream* s, const double* table, int
     if (mask_beyond && !p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "mask_beyond: the stream was opened without predictions");
     if (p.replay.on && p.replay.dist_kind == kReplayDistNone)
         return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_domain: the replay stream was opened without stored distances");
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_domain is allowed only before the first push");
-    if (int no = stage_refusal(p, kReduceMean, "distance domain")) return no;
-    HIP_TRY(hipSetDevice(ix->device));
-    HIP_TRY(ix->s_dom_table.ensure((size_t)m));
-    HIP_TRY(ix->s_dom_acc.ensure(kDomainAcc));
-    HIP_TRY(ix->dom_rec.ensure(2 * kDomainRecWords));
-    HIP_TRY(hipMemcpy(ix->s_dom_table.p, table, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+    std::unique_lock<std::mutex> lock;
+    if (int no = setter_begin(s, lock, "sknnr_stream_set_domain", kReduceMean, "distance domain")) return no;
+    auto& ds = ix->domain.stream;
+    if (int no = ds.table.upload(table, (size_t)m)) return no;
+    HIP_TRY(ds.acc.ensure(kDomainAcc));
+    HIP_TRY(ix->domain.rec.ensure());
     // (on the stream every tile's launch runs on: zeroed in front of the first of them)
-    HIP_TRY(hipMemsetAsync(ix->s_dom_acc.p, 0, kDomainAcc * 8, ix->st_run));
-    HIP_TRY(hipMemsetAsync(ix->dom_rec.p + kDomainRecWords, 0, kDomainRecWords * sizeof(unsigned long long), ix->st_run));
-    p.domain = true;
-    p.domain_mask = mask_beyond != 0;
-    p.domain_spec = DomainSpec{rank - 1, (long)m, has_threshold != 0, threshold};
+    HIP_TRY(hipMemsetAsync(ds.acc.p, 0, kDomainAcc * 8, ix->st_run));
+    HIP_TRY(ix->domain.rec.reset(1, ix->st_run, {0, 0, p.k, rank, m}));
+    p.prod.domain = true;
+    p.prod.domain_mask = mask_beyond != 0;
+    p.prod.domain_spec = DomainSpec{rank - 1, (long)m, has_threshold != 0, threshold};
     p.mask_dist = true;  // the masked path keeps the search's distances whether or not they leave
-    s->domain_out = nullptr;
-    const int64_t rec[5] = {0, 0, p.k, rank, m};
-    std::copy(rec, rec + 5, ix->last_domain);
-    ix->last_domain_half = 1;
+    s->next.domain_out = nullptr;
     return SKNNR_OK;
 }
 
 extern "C" int sknnr_stream_next_domain_out(sknnr_stream* s, uint8_t* out, int64_t nq) {
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
-    if (!s->pipe.domain) return fail(SKNNR_ERR_INVALID, "the stream has no domain: sknnr_stream_set_domain was not called");
+    if (!s->pipe.prod.domain) return fail(SKNNR_ERR_INVALID, "the stream has no domain: sknnr_stream_set_domain was not called");
     if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
     if (nq == 0) return SKNNR_OK;  // (a push of no rows writes none)
     if (!out) return fail(SKNNR_ERR_INVALID, "out is NULL");
     std::lock_guard<std::mutex> lock(s->pipe.ix->mtx);
-    s->domain_out = out;
-    s->domain_out_n = nq;
+    s->next.domain_out = out;
+    s->next.domain_out_n = nq;
     return SKNNR_OK;
 }
 
@@ -4955,28 +4907,19 @@ extern "C" int sknnr_stream_get_domain(sknnr_stream* s, int64_t acc[103]) {
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     HostPipe& p = s->pipe;
     sknnr_index* ix = p.ix;
-    if (!p.domain) return fail(SKNNR_ERR_INVALID, "the stream has no domain: sknnr_stream_set_domain was not called");
+    if (!p.prod.domain) return fail(SKNNR_ERR_INVALID, "the stream has no domain: sknnr_stream_set_domain was not called");
     if (!acc) return fail(SKNNR_ERR_INVALID, "acc is NULL");
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    HIP_TRY(hipSetDevice(ix->device));
-    const int rc = pipe_flush(p);
-    if (rc) return pipe_fail(p, rc);
-    HIP_TRY(hipStreamSynchronize(ix->st_run));
-    HIP_TRY(hipMemcpy(acc, ix->s_dom_acc.p, kDomainAcc * 8, hipMemcpyDeviceToHost));
+    std::unique_lock<std::mutex> lock;
+    if (const int rc = collect_begin(p, lock)) return rc;
+    HIP_TRY(hipMemcpy(acc, ix->domain.stream.acc.p, kDomainAcc * 8, hipMemcpyDeviceToHost));
     return SKNNR_OK;
 }
 
 extern "C" int sknnr_debug_last_domain(const sknnr_index* cix, int64_t out[8]) {
     if (!cix || !out) return fail(SKNNR_ERR_INVALID, "NULL argument");
     sknnr_index* ix = const_cast<sknnr_index*>(cix);
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    std::fill(out, out + 8, 0);
-    std::copy(ix->last_domain, ix->last_domain + 5, out);
-    if (!ix->dom_rec.p) return SKNNR_OK;
     unsigned long long w[kDomainRecWords];
-    HIP_TRY(hipSetDevice(ix->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(w, ix->dom_rec.p + ix->last_domain_half * kDomainRecWords, sizeof w, hipMemcpyDeviceToHost));
+    if (const int rc = ix->domain.rec.read(ix->mtx, ix->device, out, w)) return rc;
     // (the pixels the kernels counted, not the host's: the two agree when every launch ran)
     out[1] = (int64_t)w[kDomainRecPixels];
     out[5] = (int64_t)w[kDomainRecNodata];
@@ -5059,20 +5002,20 @@ static int stream_push(sknnr_stream* s, const void* q, const void* const* planes
     if (outs[kLaneDist] && !p.lane[kLaneDist].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without distances");
     if (outs[kLanePred] && !p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
     std::lock_guard<std::mutex> lock(p.ix->mtx);
-    if (p.zonal) {
-        if (!s->have_zones) return fail(SKNNR_ERR_INVALID, "a push on a zonal stream needs sknnr_stream_next_zones first");
-        if ((int64_t)s->zones.size() != nq)
-            return fail(SKNNR_ERR_INVALID, "sknnr_stream_next_zones gave %lld zone codes, the push has %lld rows", (long long)s->zones.size(), (long long)nq);
+    if (p.prod.zonal) {
+        if (!s->next.have_zones) return fail(SKNNR_ERR_INVALID, "a push on a zonal stream needs sknnr_stream_next_zones first");
+        if ((int64_t)s->next.zones.size() != nq)
+            return fail(SKNNR_ERR_INVALID, "sknnr_stream_next_zones gave %lld zone codes, the push has %lld rows", (long long)s->next.zones.size(), (long long)nq);
         const int dt = p.lane[kLanePred].dtype;
         if (dt < SKNNR_DTYPE_I16 || dt > SKNNR_DTYPE_I32)
             return fail(SKNNR_ERR_INVALID, "a zonal stream needs an integer pred_dtype (sknnr_stream_set_output): zonal sums are over stored integers");
-        s->have_zones = false;  // (consumed, whatever becomes of the push)
-        p.zones_push = s->zones.data();
+        s->next.have_zones = false;  // (consumed, whatever becomes of the push)
+        p.zones_push = s->next.zones.data();
     }
-    if (p.domain) {
-        uint8_t* const dst = s->domain_out;
-        const int64_t dst_n = s->domain_out_n;
-        s->domain_out = nullptr;  // (consumed, whatever becomes of the push)
+    if (p.prod.domain) {
+        uint8_t* const dst = s->next.domain_out;
+        const int64_t dst_n = s->next.domain_out_n;
+        s->next.domain_out = nullptr;  // (consumed, whatever becomes of the push)
         if (dst && dst_n != nq)
             return fail(SKNNR_ERR_INVALID, "sknnr_stream_next_domain_out named %lld codes, the push has %lld rows", (long long)dst_n, (long long)nq);
         p.domain_push = dst;
@@ -5292,10 +5235,8 @@ extern "C" int sknnr_replay_get_counts(sknnr_stream* s, int64_t out[4]) {
     if (!out) return fail(SKNNR_ERR_INVALID, "sknnr_replay_get_counts: out is NULL");
     HostPipe& p = s->pipe;
     if (!p.replay.on) return fail(SKNNR_ERR_INVALID, "sknnr_replay_get_counts: the stream was opened by sknnr_stream_begin");
-    std::lock_guard<std::mutex> lock(p.ix->mtx);
-    HIP_TRY(hipSetDevice(p.ix->device));
-    const int rc = pipe_flush(p);
-    if (rc) return pipe_fail(p, rc);
+    std::unique_lock<std::mutex> lock;
+    if (const int rc = collect_begin(p, lock)) return rc;
     std::copy(p.replay_tot, p.replay_tot + 3, out);
     out[3] = p.replay_first;
     return SKNNR_OK;
@@ -5333,8 +5274,7 @@ extern "C" int sknnr_index_set_bootstrap(sknnr_index* ix, const uint8_t* table, 
                 for (int64_t r = r0; r < std::min<int64_t>(n, r0 + 64); ++r) mt[(size_t)r * bpad + b] = table[(size_t)b * n + r];
     HIP_TRY(hipSetDevice(ix->device));
     if (ix->ws_busy) HIP_TRY(hipEventSynchronize(ix->ev_ws));  // (a reduction of an earlier call may still read the old table)
-    HIP_TRY(ix->boot_mt.ensure(mt.size()));
-    HIP_TRY(hipMemcpy(ix->boot_mt.p, mt.data(), mt.size(), hipMemcpyHostToDevice));
+    if (int rc = ix->boot_mt.upload(mt.data(), mt.size())) return rc;
     ix->boot_B = B;
     ix->boot_bpad = bpad;
     return SKNNR_OK;
@@ -5434,12 +5374,11 @@ static std::vector<int> boot_plan_image(const BootPlan& bp) {
     return img;
 }
 
-// The plan's arrays into `buf` (a one-shot call's c_boot, or the open stream's s_boot) and the bootstrap of replicates of
-// k copies over them; the caller names the tally words.
+// The plan's arrays into `buf` (a one-shot call's boot.call.plan, or the open stream's boot.stream.plan) and the bootstrap
+// of replicates of k copies over them; the caller names the tally words.
 static int boot_upload(DevBuf<int>& buf, const BootPlan& bp, int k, Reduction& red) {
     const std::vector<int> img = boot_plan_image(bp);
-    HIP_TRY(buf.ensure(img.size()));
-    HIP_TRY(hipMemcpy(buf.p, img.data(), img.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (int rc = buf.upload(img.data(), img.size())) return rc;
     red = Reduction{};
     red.kind = kReduceBoot;
     red.boot.n_out = (int)bp.codes.size();
@@ -5449,18 +5388,6 @@ static int boot_upload(DevBuf<int>& buf, const BootPlan& bp, int k, Reduction& r
     red.boot.uidx = red.boot.ucols + red.boot.n_u;
     red.boot.codes = red.boot.uidx + red.boot.n_out;
     return SKNNR_OK;
-}
-
-// A one-shot reduction: uploads the plan, zeroes the two tally words and launches; dist / idx / out are device memory.
-static int bootstrap_call(sknnr_index* ix, const double* dist, const long* idx, long nq, int kw, int k, int mode, int law,
-                          const BootPlan& bp, double* out, unsigned long long* tally, hipStream_t st) {
-    if (ix->ws_busy) HIP_TRY(hipEventSynchronize(ix->ev_ws));
-    Reduction red;
-    const int rc = boot_upload(ix->c_boot, bp, k, red);
-    if (rc) return rc;
-    red.boot_tally = tally;
-    HIP_TRY(hipMemsetAsync(tally, 0, 2 * sizeof(unsigned long long), st));
-    return launch_bootstrap(ix, red, dist, idx, nq, kw, mode, law, out, nullptr, st);
 }
 
 // The bootstrap `red` of one launch's rows (launch_predict; a one-shot call comes here directly): red.boot_tally is added
@@ -5492,32 +5419,31 @@ extern "C" int sknnr_bootstrap_from_neighbors(sknnr_index* ix, const double* dis
     std::lock_guard<std::mutex> lock(ix->mtx);
     if (ix->boot_B < 1) return fail(SKNNR_ERR_INVALID, "the handle has no bootstrap table (sknnr_index_set_bootstrap)");
     HIP_TRY(hipSetDevice(ix->device));
-    if (mem == SKNNR_MEM_DEVICE) {
-        hipStream_t st = (hipStream_t)stream;
-        unsigned long long* dt = (unsigned long long*)tally;
-        if (!dt) {
-            if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));
-            HIP_TRY(ix->boot_tally.ensure(2));
-            dt = ix->boot_tally.p;
-        }
-        return bootstrap_call(ix, dist, (const long*)idx, nq, kw, k, weight_mode, weight_law, bp, out, dt, st);
+    hipStream_t st = mem == SKNNR_MEM_DEVICE ? (hipStream_t)stream : nullptr;
+    const size_t n_el = (size_t)nq * kw;
+    Staged<long> di;
+    Staged<double> dd, dout;
+    Staged<unsigned long long> dt;
+    // (uniform weights read no distances)
+    if ((rc = di.stage(idx, n_el, mem, kStageIn)) || (rc = dout.stage(out, (size_t)nq * n_out, mem, kStageOut)) ||
+        (rc = dt.stage(tally, 2, mem, kStageOut)) ||
+        (rc = dd.stage(weight_mode != SKNNR_WEIGHTS_UNIFORM ? dist : nullptr, n_el, mem, kStageIn)))
+        return rc;
+    unsigned long long* tw = dt.p;
+    if (!tw) {  // (not asked for: the handle's two words, behind the workspace's last user on `st`)
+        if (ix->ws_busy) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ws, 0));
+        HIP_TRY(ix->boot.call.tally.ensure(2));
+        tw = ix->boot.call.tally.p;
     }
-    DevBuf<double> dd, dout;  // freed by their destructors on every return path
-    DevBuf<long> di;
-    DevBuf<unsigned long long> dt;
-    HIP_TRY(di.ensure((size_t)nq * kw));
-    HIP_TRY(dout.ensure((size_t)nq * n_out));
-    HIP_TRY(dt.ensure(2));
-    HIP_TRY(hipMemcpy(di.p, idx, (size_t)nq * kw * sizeof(long), hipMemcpyHostToDevice));
-    if (dist && weight_mode != SKNNR_WEIGHTS_UNIFORM) {
-        HIP_TRY(dd.ensure((size_t)nq * kw));
-        HIP_TRY(hipMemcpy(dd.p, dist, (size_t)nq * kw * sizeof(double), hipMemcpyHostToDevice));
-    }
-    rc = bootstrap_call(ix, dd.p, di.p, nq, kw, k, weight_mode, weight_law, bp, dout.p, dt.p, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, dout.p, (size_t)nq * n_out * sizeof(double), hipMemcpyDeviceToHost));
-    if (tally) HIP_TRY(hipMemcpy(tally, dt.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
-    return SKNNR_OK;
+    // the plan is a workspace buffer: the previous reduction may still read it
+    if (ix->ws_busy) HIP_TRY(hipEventSynchronize(ix->ev_ws));
+    Reduction red;
+    if ((rc = boot_upload(ix->boot.call.plan, bp, k, red))) return rc;
+    red.boot_tally = tw;
+    HIP_TRY(hipMemsetAsync(tw, 0, 2 * sizeof(unsigned long long), st));
+    if ((rc = launch_bootstrap(ix, red, dd.p, di.p, nq, kw, weight_mode, weight_law, dout.p, nullptr, st))) return rc;
+    if ((rc = dout.download())) return rc;
+    return dt.download();
 }
 
 extern "C" int sknnr_stream_set_bootstrap(sknnr_stream* s, int32_t k, const int32_t* cols, const int32_t* stat, int32_t n_out) {
@@ -5529,20 +5455,19 @@ extern "C" int sknnr_stream_set_bootstrap(sknnr_stream* s, int32_t k, const int3
     if (rc) return rc;
     BootPlan bp;
     if ((rc = boot_plan_check(ix, cols, stat, n_out, bp))) return rc;
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    if (s->pushed) return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_bootstrap is allowed only before the first push");
-    if ((rc = stage_refusal(p, kReduceBoot, "bootstrap"))) return rc;
-    if (p.tally) return fail(SKNNR_ERR_INVALID, "the stream tallies neighbour usage (sknnr_stream_set_tally): it takes no bootstrap");
-    if (p.domain) return fail(SKNNR_ERR_INVALID, "the stream has a distance domain (sknnr_stream_set_domain): it takes no bootstrap");
-    if (p.zonal) return fail(SKNNR_ERR_INVALID, "the stream has zonal statistics (sknnr_stream_set_zonal): it takes no bootstrap");
+    std::unique_lock<std::mutex> lock;
+    if ((rc = setter_begin(s, lock, "sknnr_stream_set_bootstrap", kReduceBoot, "bootstrap"))) return rc;
+    if (p.prod.tally) return fail(SKNNR_ERR_INVALID, "the stream tallies neighbour usage (sknnr_stream_set_tally): it takes no bootstrap");
+    if (p.prod.domain) return fail(SKNNR_ERR_INVALID, "the stream has a distance domain (sknnr_stream_set_domain): it takes no bootstrap");
+    if (p.prod.zonal) return fail(SKNNR_ERR_INVALID, "the stream has zonal statistics (sknnr_stream_set_zonal): it takes no bootstrap");
     if (p.lane[kLanePred].scale)
         return fail(SKNNR_ERR_INVALID, "sknnr_stream_set_bootstrap comes before sknnr_stream_set_output: the scale / offset hold one value per output plane");
-    HIP_TRY(hipSetDevice(ix->device));
     Reduction red;
-    if ((rc = boot_upload(ix->s_boot, bp, k, red))) return rc;
-    HIP_TRY(ix->s_boot_tally.ensure(2));
-    HIP_TRY(hipMemsetAsync(ix->s_boot_tally.p, 0, 2 * sizeof(unsigned long long), ix->st_run));  // (in front of the first tile)
-    red.boot_tally = ix->s_boot_tally.p;
+    auto& bs = ix->boot.stream;
+    if ((rc = boot_upload(bs.plan, bp, k, red))) return rc;
+    HIP_TRY(bs.tally.ensure(2));
+    HIP_TRY(hipMemsetAsync(bs.tally.p, 0, 2 * sizeof(unsigned long long), ix->st_run));  // (in front of the first tile)
+    red.boot_tally = bs.tally.p;
     p.red = red;
     p.lane[kLanePred].cols = n_out;  // from now on the prediction lane is n_out wide
     return SKNNR_OK;
@@ -5553,12 +5478,9 @@ extern "C" int sknnr_stream_get_bootstrap(sknnr_stream* s, int64_t tally[2]) {
     HostPipe& p = s->pipe;
     sknnr_index* ix = p.ix;
     if (p.red.kind != kReduceBoot) return fail(SKNNR_ERR_INVALID, "the stream has no bootstrap stage: sknnr_stream_set_bootstrap was not called");
-    std::lock_guard<std::mutex> lock(ix->mtx);
-    HIP_TRY(hipSetDevice(ix->device));
-    const int rc = pipe_flush(p);
-    if (rc) return pipe_fail(p, rc);
-    HIP_TRY(hipStreamSynchronize(ix->st_run));
-    HIP_TRY(hipMemcpy(tally, ix->s_boot_tally.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::unique_lock<std::mutex> lock;
+    if (const int rc = collect_begin(p, lock)) return rc;
+    HIP_TRY(hipMemcpy(tally, ix->boot.stream.tally.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
     return SKNNR_OK;
 }
 
@@ -5579,19 +5501,13 @@ extern "C" int sknnr_crosswalk(const int64_t* table, int64_t n_table, const int6
     if (mem != SKNNR_MEM_DEVICE && mem != SKNNR_MEM_HOST) return fail(SKNNR_ERR_INVALID, "unknown memspace %d", mem);
     if (n == 0) return SKNNR_OK;
     HIP_TRY(hipSetDevice(device));
-    if (mem == SKNNR_MEM_DEVICE) {
-        HIP_TRY(launch::crosswalk((const long*)table, (const long*)idx, n, (long*)out, (hipStream_t)stream));
-        return SKNNR_OK;
-    }
-    DevBuf<long> dt, di, dout;  // freed by their destructors on every return path
-    HIP_TRY(dt.ensure(n_table));
-    HIP_TRY(di.ensure(n));
-    HIP_TRY(dout.ensure(n));
-    HIP_TRY(hipMemcpy(dt.p, table, n_table * sizeof(long), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(di.p, idx, n * sizeof(long), hipMemcpyHostToDevice));
-    HIP_TRY(launch::crosswalk(dt.p, di.p, n, dout.p, nullptr));
-    HIP_TRY(hipMemcpy(out, dout.p, n * sizeof(long), hipMemcpyDeviceToHost));
-    return SKNNR_OK;
+    Staged<long> dt, di, dout;
+    int rc;
+    if ((rc = dt.stage(table, (size_t)n_table, mem, kStageIn)) || (rc = di.stage(idx, (size_t)n, mem, kStageIn)) ||
+        (rc = dout.stage(out, (size_t)n, mem, kStageOut)))
+        return rc;
+    HIP_TRY(launch::crosswalk(dt.p, di.p, n, dout.p, mem == SKNNR_MEM_DEVICE ? (hipStream_t)stream : nullptr));
+    return dout.download();
 }
 
 // ----------------------------------------------------------------------------------------
