@@ -1,5 +1,5 @@
-// The byte arithmetic of the host pipeline's output lanes (the first section of sknnr_amd/csrc/sknnr_hip.hip), alone on the
-// CPU and under the sanitizers:
+// The byte arithmetic of the host pipeline's output lanes (sknnr_amd/csrc/host_stage.h, as sknnr_hip.hip includes it), alone
+// on the CPU and under the sanitizers:
 //
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all scripts/lane_arithmetic_check.cpp -o /tmp/lane_check
 //   /tmp/lane_check

@@ -5,7 +5,9 @@
 repository snapshot to the GPU box.
 
 The sources are one host translation unit (``sknnr_hip.hip``: index build, workspace, host
-pipeline, C ABI) and the kernel translation units ``k_*.hip`` behind ``launch.hip.h``; the units
+pipeline, C ABI; the pipeline's plain host arithmetic -- staging copies, tile cuts, the ``Push``
+that describes a push -- is ``host_stage.h``, which includes nothing of HIP and is also compiled
+alone by tests/test_host_stage_cpu.py) and the kernel translation units ``k_*.hip`` behind ``launch.hip.h``; the units
 are compiled in parallel into ``csrc/_obj/`` (each one only when it or a header is newer than its
 object) and linked by hipcc.
 """
@@ -48,7 +50,7 @@ UNITS = [
 ]
 SOURCES = sorted({u[1] for u in UNITS})
 HEADERS = ["launch.hip.h", "coarse.hip.h", "coarse2.hip.h", "bucket.hip.h", "hamming.hip.h", "exact.hip.h", "rescue.hip.h", "forest.hip.h", "mask.hip.h", "planes.hip.h", "narrow.hip.h", "summary.hip.h", "plan.hip.h", "weights.hip.h", "groups.hip.h", "buffer.hip.h", "tally.hip.h", "zonal.hip.h", "domain.hip.h", "replay.hip.h", "bootstrap.hip.h",
-           "../../include/sknnr_hip.h"]
+           "host_stage.h", "../../include/sknnr_hip.h"]
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",

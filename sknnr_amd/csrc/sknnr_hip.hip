@@ -4,21 +4,9 @@
 // the per-chunk launch sequence  prep -> coarse (MFMA) -> finalize -> exact_scan,
 // staging for host buffers, error reporting.  No CPU path computes results: if a
 // device call fails the function fails.
-#include <cstddef>
-
-// ----------------------------------------------------------------------------------------
-// the outputs of the host pipeline: one lane each
-// ----------------------------------------------------------------------------------------
-// What the host pipeline hands to the caller, in the order the debug records use (bit `1 << lane` of last_narrow's wide mask).
-enum { kLaneIdx = 0, kLaneDist = 1, kLanePred = 2, kLanes = 3 };
-
-// The byte arithmetic of a lane: `cols` columns (k, k, t) of `esz` bytes per element (8 unless the output is typed).  No HIP
-// here: scripts/lane_arithmetic_check.cpp compiles this section alone (SKNNR_LANE_ARITHMETIC_ONLY), under the sanitizers.
-inline size_t lane_bytes(long n, int cols, size_t esz) { return (size_t)n * cols * esz; }               // a tile of n rows
-inline size_t lane_units(long n, int cols, size_t esz) { return (lane_bytes(n, cols, esz) + 7) / 8; }  // ... in 8-byte words
-// Where tile [c0, ...) starts in the caller's array: packed (N, cols) rows, or planes -- there the tile is a segment of
-// every plane, and the address is that of the first plane's.
-inline size_t lane_tile_offset(long c0, int cols, size_t esz, bool planes) { return (size_t)c0 * (planes ? 1 : cols) * esz; }
+// The host pipeline's lanes, staging copies, tile cuts and push description: no HIP in there.  (scripts/lane_arithmetic_check.cpp
+// compiles this file up to here alone, SKNNR_LANE_ARITHMETIC_ONLY, under the sanitizers.)
+#include "host_stage.h"
 
 #ifndef SKNNR_LANE_ARITHMETIC_ONLY
 #include "../../include/sknnr_hip.h"
@@ -2439,6 +2427,19 @@ int mask_compact(MaskBufs& m, const void* x, long n, size_t row_bytes, hipStream
     return SKNNR_OK;
 }
 
+// The search body of every call and tile, on `st`: the n rows at x searched into dd / di, their neighbours tallied if asked,
+// and reduced into d_pred if non-null.  What sits between a search and its reduction goes here, once.
+// (replay_tile keeps its own order -- decode, reduce, blank, tally: there the tally must see the tile's final state.)
+int search_tile(sknnr_index* ix, const Reduction& red, const void* x, long n, const sknnr_query_opts* o, double* dd, long* di,
+                double* d_pred, bool tally, hipStream_t st) {
+    const int k = o->n_neighbors;
+    int rc = run_device(ix, x, n, o, dd, di, st);
+    if (rc) return rc;
+    if (tally && (rc = tally_tile(ix, dd, di, n, k, st))) return rc;
+    if (d_pred) return launch_predict(ix, red, dd, di, nullptr, n, k, o->weight_mode, o->weight_law, d_pred, st);
+    return SKNNR_OK;
+}
+
 // The search of a masked tile whose valid count nv the host knows, on `st`: in place when every row is valid, nothing but
 // the fill when none is, else on the packed rows (mask_compact has run, on `st` or in front of an event `st` waits for) and
 // expanded.  o->row_offset counts the valid rows in front of the tile.  d_pred: also predict; d_dist / d_idx may be null.
@@ -2453,16 +2454,12 @@ int mask_finish(sknnr_index* ix, const Reduction& red, MaskBufs& m, const void* 
     if (nv == n) {
         double* dd = d_dist ? d_dist : (d_pred ? m.cd.p : nullptr);
         long* di = d_idx ? d_idx : m.ci.p;
-        if ((rc = run_device(ix, x, n, o, dd, di, st))) return rc;
-        if (tally && (rc = tally_tile(ix, dd, di, n, k, st))) return rc;
-        if (d_pred && (rc = launch_predict(ix, red, dd, di, nullptr, n, k, o->weight_mode, o->weight_law, d_pred, st))) return rc;
+        if ((rc = search_tile(ix, red, x, n, o, dd, di, d_pred, tally, st))) return rc;
     } else {
         ExpandArgs e{};
         if (nv > 0) {
             double* cd = (d_dist || d_pred) ? m.cd.p : nullptr;
-            if ((rc = run_device(ix, m.cx.p, nv, o, cd, m.ci.p, st))) return rc;
-            if (tally && (rc = tally_tile(ix, cd, m.ci.p, nv, k, st))) return rc;
-            if (d_pred && (rc = launch_predict(ix, red, cd, m.ci.p, nullptr, nv, k, o->weight_mode, o->weight_law, m.cp.p, st))) return rc;
+            if ((rc = search_tile(ix, red, m.cx.p, nv, o, cd, m.ci.p, d_pred ? m.cp.p : nullptr, tally, st))) return rc;
             e.valid = m.valid.p;
             e.rank = m.rank.p;
             e.c_idx = m.ci.p;
@@ -2523,60 +2520,6 @@ long host_chunk_rows() {
     return v;
 }
 
-// memcpy split over a few threads: a single core copies ~10 GB/s, PCIe Gen5 x16 moves ~50
-void parallel_copy(void* dst, const void* src, size_t bytes) {
-    const size_t kMin = 8u << 20;
-    unsigned n = std::min<unsigned>(8, std::max(1u, std::thread::hardware_concurrency()));
-    if (bytes < 2 * kMin) n = 1;
-    if (n == 1) {
-        std::memcpy(dst, src, bytes);
-        return;
-    }
-    std::vector<std::thread> th;
-    const size_t per = ((bytes / n) + 4095) & ~(size_t)4095;
-    for (unsigned i = 0; i < n; ++i) {
-        const size_t a = (size_t)i * per;
-        if (a >= bytes) break;
-        const size_t len = std::min(per, bytes - a);
-        th.emplace_back([=] { std::memcpy((char*)dst + a, (const char*)src + a, len); });
-    }
-    for (auto& t : th) t.join();
-}
-
-// Staging copy of a band-first tile: elements [off, off + n) of each of `c` separately held planes, packed (c, n) into
-// dst.  Plain copies, one per band (nothing is transposed on the host); a large tile's bands are shared out over a few
-// threads by the bytes of the packed destination, as parallel_copy does for rows.
-void stage_planes(void* dst, const void* const* planes, int c, size_t esz, long off, long n) {
-    const size_t seg = (size_t)n * esz, bytes = seg * c;
-    auto piece = [=](size_t a, size_t b) {  // bytes [a, b) of the packed destination
-        while (a < b) {
-            const size_t j = a / seg, within = a - j * seg, len = std::min(seg - within, b - a);
-            std::memcpy((char*)dst + a, (const char*)planes[j] + (size_t)off * esz + within, len);
-            a += len;
-        }
-    };
-    const size_t kMin = 8u << 20;
-    unsigned nt = std::min<unsigned>(8, std::max(1u, std::thread::hardware_concurrency()));
-    if (bytes < 2 * kMin) nt = 1;
-    if (nt == 1) {
-        piece(0, bytes);
-        return;
-    }
-    std::vector<std::thread> th;
-    const size_t per = ((bytes / nt) + 4095) & ~(size_t)4095;
-    for (unsigned i = 0; i < nt; ++i) {
-        const size_t a = (size_t)i * per;
-        if (a >= bytes) break;
-        th.emplace_back(piece, a, std::min(a + per, bytes));
-    }
-    for (auto& t : th) t.join();
-}
-// The copy-out counterpart: `c` segments of n elements of esz bytes, packed in src, to dst + j * stride.
-void unstage_planes(void* dst, const void* src, int c, long n, long stride, size_t esz) {
-    for (int j = 0; j < c; ++j)
-        parallel_copy((char*)dst + (size_t)j * stride * esz, (const char*)src + (size_t)j * n * esz, (size_t)n * esz);
-}
-
 template <typename T>
 int ensure_pinned(T*& p, size_t& have, size_t want) {
     if (p && have >= want) return SKNNR_OK;
@@ -2596,32 +2539,9 @@ struct ReplaySpec {
     int dist_kind = kReplayDistNone;
     bool ids = false;                // the stored values are ids of the handle's table (sknnr_index_set_replay_ids)
     long fill_index = -1;
-    int dist_bytes() const { return dist_kind == kReplayDistNone ? 0 : (dist_kind == kReplayDistF32 ? 4 : 8); }
+    // what host_stage.h lays a staged tile out by
+    ReplayLayout layout() const { return {ks, idx_bytes, dist_kind == kReplayDistNone ? 0 : (dist_kind == kReplayDistF32 ? 4 : 8)}; }
 };
-// the stored arrays of one push: rows (n, ks), or planes `stride` elements apart; dist null without distances
-struct ReplaySrc {
-    const char* idx = nullptr;
-    const char* dist = nullptr;
-    bool planes = false;
-    long stride = 0;
-};
-// A tile of n pixels as it is staged and uploaded: the index block -- rows (n, ks) or planes (ks, n), packed -- and,
-// 16-byte aligned behind it, the distance block in the same layout.
-size_t replay_dist_offset(const ReplaySpec& r, long n) { return ((size_t)n * r.ks * r.idx_bytes + 15) & ~(size_t)15; }
-size_t replay_tile_bytes(const ReplaySpec& r, long n) { return replay_dist_offset(r, n) + (size_t)n * r.ks * r.dist_bytes(); }
-// Staging copy of pixels [off, off + n) of a push: plain copies, one per block of a row tile, one per plane otherwise.
-void stage_replay(void* dst, const ReplaySpec& r, const ReplaySrc& s, long off, long n) {
-    const auto block = [&](char* to, const char* from, size_t esz) {
-        if (!s.planes) {
-            parallel_copy(to, from + (size_t)off * r.ks * esz, (size_t)n * r.ks * esz);
-            return;
-        }
-        for (int j = 0; j < r.ks; ++j)
-            parallel_copy(to + (size_t)j * n * esz, from + ((size_t)j * s.stride + off) * esz, (size_t)n * esz);
-    };
-    block((char*)dst, s.idx, (size_t)r.idx_bytes);
-    if (r.dist_kind != kReplayDistNone) block((char*)dst + replay_dist_offset(r, n), s.dist, (size_t)r.dist_bytes());
-}
 
 // Pageable host arrays in, pageable host arrays out, through kHostSlots pinned/device slots:
 //   host thread : copy tile c into its slot's pinned buffer | copy results of tile c - kHostSlots out
@@ -2667,14 +2587,11 @@ struct HostPipe {
         bool domain_mask = false;
         DomainSpec domain_spec{};
     } prod;
-    const int32_t* zones_push = nullptr;  // a zonal pipeline: the zone codes of the push in progress (one per pushed row)
-    uint8_t* domain_push = nullptr;  // a domain pipeline: where the push's code plane goes (host; null: it tallies only)
+    long push_no = -1;  // the push in progress (Push::push_no): every push counts, an empty one too -- the caller's tile numbers
     // neighbour replay (sknnr_replay_begin): the tiles are stored neighbours, decoded on the device where a search would
-    // run (replay_tile); replay_src: the arrays of the push in progress; replay_tot / replay_first: pixels, masked and
-    // unknown pixels of the tiles that have left so far, and the first push that held unknown values (-1: none yet)
+    // run (replay_tile); replay_tot / replay_first: pixels, masked and unknown pixels of the tiles that have left so far,
+    // and the first push that held unknown values (-1: none yet)
     ReplaySpec replay{};
-    ReplaySrc replay_src{};
-    long replay_push_no = -1;
     int64_t replay_tot[3] = {};
     long replay_first = -1;
     size_t x_esz = sizeof(double);  // bytes per element of the caller's rows (opts->query_dtype)
@@ -2688,19 +2605,15 @@ struct HostPipe {
     Reduction red;
     struct Pending {
         bool live = false;
-        long n = 0;
-        void* out[kLanes] = {};  // the caller's arrays (the tile's first element; null: not asked for in this push)
-        bool planes = false;   // the tile was pushed band-first: its results leave as planes, out_stride elements apart
-        long out_stride = 0;
-        uint8_t* domain_out = nullptr;  // the caller's code plane of the tile (a domain pipeline; null: not asked for)
-        long replay_push_no = 0;        // the push the tile came with (a replay pipeline)
+        Push push;         // the tile: pixels [off, off + n) of this push
+        long off = 0, n = 0;
         std::future<int> out_done;  // copy-out job of the slot's tile (w_out)
     } pending[kHostSlots];
     int slot_of = 0;
-    // look-ahead copy-in (one-shot calls know their next tile): the job that stages tile `ahead_tile` into slot `ahead_slot`
     std::packaged_task<int()> deferred[kHostSlots];  // SKNNR_PIPE_WORKERS=0: the copy-out jobs, run when the slot is drained
+    // look-ahead copy-in (a push knows its next tile): the job that stages tile (ahead_push_no, ahead_off) into slot ahead_slot
     std::future<int> ahead_done;
-    const void* ahead_q = nullptr;
+    long ahead_push_no = -1, ahead_off = 0;
     int ahead_slot = -1;
     int d2h_slot = -1;  // slot whose kernels are enqueued and whose device-to-host copies are not yet (pipe_enqueue_d2h)
     double ms_copy_in = 0, ms_copy_out = 0, ms_wait = 0, ms_enqueue = 0;  // host-thread time per phase (SKNNR_PIPE_TRACE=1)
@@ -2769,22 +2682,23 @@ int pipe_drain(HostPipe& p, int b) {
         const unsigned long long* rec = p.ix->pin_replay + (size_t)b * kReplayRecWords;
         for (int w = 0; w < 3; ++w) p.ix->last_replay[w] = (int64_t)rec[w];
         for (int w = 0; w < 3; ++w) p.replay_tot[w] += (int64_t)rec[w];
-        if (rec[kReplayRecUnknown] && p.replay_first < 0) p.replay_first = pd.replay_push_no;
+        if (rec[kReplayRecUnknown] && p.replay_first < 0) p.replay_first = pd.push.push_no;
     }
     return SKNNR_OK;
 }
 
-// Drain slot b and size its pinned / device buffers for a tile of n rows.
-int pipe_prepare_slot(HostPipe& p, int b, long n, bool planes = false) {
+// Drain slot b and size its pinned / device buffers for a tile of n pixels of push u.
+int pipe_prepare_slot(HostPipe& p, int b, const Push& u, long n) {
     sknnr_index* ix = p.ix;
     auto& sl = ix->slot[b];
+    const bool planes = u.band_first;
     int rc = pipe_drain(p, b);  // the slot's previous tile must have left before its buffers are reused
     if (rc) return rc;
     // the tile's rows -- or, replayed, its stored neighbours -- in 8-byte units
-    const size_t x_f64 = ((p.replay.on ? replay_tile_bytes(p.replay, n) : (size_t)n * p.d_x * p.x_esz) + 7) / 8;
+    const size_t x_f64 = (u.staged_bytes(n) + 7) / 8;
     if ((rc = ensure_pinned(sl.pin_x, sl.pin_x_n, x_f64))) return rc;
     HIP_TRY(sl.dev_x.ensure(x_f64));
-    if (planes && !p.replay.on) HIP_TRY(sl.dev_xp.ensure(x_f64));  // (band-first tiles only: the uploaded planes)
+    if (u.source == Push::kBands) HIP_TRY(sl.dev_xp.ensure(x_f64));  // (band-first rows only: the uploaded planes)
     if (p.replay.on) HIP_TRY(sl.mask.valid.ensure((size_t)n));     // (the decode's bad-pixel flags)
     if (p.prod.zonal) {
         if ((rc = ensure_pinned(sl.pin_z, sl.pin_z_n, (size_t)n))) return rc;
@@ -2826,8 +2740,8 @@ int pipe_enqueue_d2h(HostPipe& p) {
     static const bool one_stream = [] { const char* e = std::getenv("SKNNR_PIPE_ONE_STREAM"); return !(e && std::atoi(e) == 0); }();
     hipStream_t st = one_stream ? ix->st_h2d : ix->st_d2h;
     HIP_TRY(hipStreamWaitEvent(st, sl.ev_done, 0));
-    const bool planes = pd.planes;  // (then the plane buffers hold the untyped results, packed (k or t, n))
-    const long out_stride = pd.out_stride;
+    const bool planes = pd.push.band_first;  // (then the plane buffers hold the untyped results, packed (k or t, n))
+    const long out_stride = pd.push.out_stride;
     struct Leg {  // one requested output on its way out: the caller's array (null: none), the pinned bytes, the lane's shape
         void* dst;
         const void* pin;
@@ -2837,7 +2751,7 @@ int pipe_enqueue_d2h(HostPipe& p) {
     std::array<Leg, kLanes> legs{};
     size_t moved = 0;
     for (int l = 0; l < kLanes; ++l) {
-        if (!pd.out[l]) continue;
+        if (!pd.push.out[l]) continue;
         const HostPipe::Lane& ln = p.lane[l];
         const auto& sb = sl.lane[l];
         // (a converted output leaves from its narrow buffer, rows or planes alike, at its own element size)
@@ -2845,10 +2759,10 @@ int pipe_enqueue_d2h(HostPipe& p) {
         const size_t bytes = lane_bytes(n, ln.cols, ln.esz);
         HIP_TRY(hipMemcpyAsync(sb.pin, src, bytes, hipMemcpyDeviceToHost, st));
         moved += bytes;
-        legs[l] = Leg{pd.out[l], sb.pin, ln.cols, ln.esz};
+        legs[l] = Leg{pd.push.out_at(l, pd.off, ln.cols, ln.esz), sb.pin, ln.cols, ln.esz};
     }
     ix->last_narrow[5] = (int64_t)moved;
-    uint8_t* const dom_dst = pd.domain_out;  // (a domain pipeline's code plane: n bytes in pixel order in either layout)
+    uint8_t* const dom_dst = pd.push.domain_at(pd.off);  // (a domain pipeline's code plane: n bytes in pixel order in either layout)
     const uint8_t* const dom_pin = sl.pin_dom;
     if (dom_dst) HIP_TRY(hipMemcpyAsync(sl.pin_dom, sl.dev_dom.p, (size_t)n, hipMemcpyDeviceToHost, st));
     if (p.replay.on)  // (the tile's record: pipe_drain adds it up once the copy-out job has waited for ev_d2h)
@@ -2894,7 +2808,7 @@ int replay_tile(HostPipe& p, int b, long n, bool planes, long* d_idx, double* d_
     HIP_TRY(hipMemsetAsync(rec, 0, kReplayRecWords * sizeof(unsigned long long), st));
     ReplayArgs a{};
     a.idx = sl.dev_x.p;
-    a.dist = d_dist ? (const char*)sl.dev_x.p + replay_dist_offset(r, n) : nullptr;
+    a.dist = d_dist ? (const char*)sl.dev_x.p + replay_dist_offset(r.layout(), n) : nullptr;
     a.n = n;
     a.ks = r.ks;
     a.k = p.k;
@@ -2925,19 +2839,13 @@ int replay_tile(HostPipe& p, int b, long n, bool planes, long* d_idx, double* d_
     return SKNNR_OK;
 }
 
-// One tile of at most host_chunk_rows() rows.  `q` may be reused by the caller as soon as this returns.
-// q_next / n_next: the tile the same call will submit next (or null): its rows are staged into the next slot's pinned
+// One tile of at most host_chunk_rows() pixels: [off, off + n) of push u.  Its input pixels may be reused by the caller as
+// soon as this returns.
+// n_next: the pixels of the tile the same push will submit next (0: none): they are staged into the next slot's pinned
 // buffer by the copy-in worker while this tile is enqueued and the caller waits for older results.
-// planes (or null): the tile is band-first -- elements [p_off, p_off + n) of each of the d_x planes; q / q_next are then
-// the first band's segments (they name the tile for the look-ahead), and out[] the first output plane's, with
-// out_stride elements between planes.  `planes` must stay valid until the next tile is submitted or the pipeline flushed.
-// out[l]: where lane l's results of this tile go, in the lane's own element type (null: not asked for).
-// zones (a zonal pipeline; else null): the tile's n zone codes, the next tile's behind them.
-// domain_out (a domain pipeline; else null): where the tile's n codes go on the host (null: the tile is tallied only).
-int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], const void* q_next = nullptr,
-                long n_next = 0, const void* const* planes = nullptr, long p_off = 0, long out_stride = 0,
-                const int32_t* zones = nullptr, uint8_t* domain_out = nullptr) {
+int pipe_submit(HostPipe& p, const Push& u, long off, long n, long n_next) {
     sknnr_index* ix = p.ix;
+    const bool planes = u.band_first, planes_in = u.source == Push::kBands;  // (stored planes are decoded as they are)
     const int b = p.slot_of;
     p.slot_of = (p.slot_of + 1) % kHostSlots;
     auto& sl = ix->slot[b];
@@ -2949,22 +2857,18 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     const long searches0 = ix->search_calls;
     int rc;
     const double t_in = now_ms();
-    if (p.ahead_slot == b && p.ahead_q == q && p.ahead_done.valid()) {
+    if (p.ahead_slot == b && p.ahead_push_no == u.push_no && p.ahead_off == off && p.ahead_done.valid()) {
         rc = p.ahead_done.get();  // staged ahead by the worker (the slot was prepared when the job was posted)
         p.ahead_slot = -1;
         if (rc) return rc;
     } else {
-        if ((rc = pipe_prepare_slot(p, b, n, planes != nullptr))) return rc;
-        if (p.replay.on) stage_replay(sl.pin_x, p.replay, p.replay_src, p_off, n);
-        else if (planes) stage_planes(sl.pin_x, planes, d_x, p.x_esz, p_off, n);
-        else parallel_copy(sl.pin_x, q, (size_t)n * d_x * p.x_esz);
-        if (p.prod.zonal) parallel_copy(sl.pin_z, zones, (size_t)n * sizeof(int32_t));
+        if ((rc = pipe_prepare_slot(p, b, u, n))) return rc;
+        u.stage(sl.pin_x, off, n);
+        if (u.zones) parallel_copy(sl.pin_z, u.zones + off, (size_t)n * sizeof(int32_t));
     }
-    const bool planes_in = planes && !p.replay.on;  // (a replayed band-first tile is decoded from its planes as they are)
     const double t_enq = now_ms();
     p.ms_copy_in += t_enq - t_in;
-    HIP_TRY(hipMemcpyAsync(planes_in ? sl.dev_xp.p : sl.dev_x.p, sl.pin_x,
-                           p.replay.on ? replay_tile_bytes(p.replay, n) : (size_t)n * d_x * p.x_esz, hipMemcpyHostToDevice, ix->st_h2d));
+    HIP_TRY(hipMemcpyAsync(planes_in ? sl.dev_xp.p : sl.dev_x.p, sl.pin_x, u.staged_bytes(n), hipMemcpyHostToDevice, ix->st_h2d));
     if (planes_in) {  // behind the copy, in front of the mask: dev_x as an uploaded row tile would have filled it
         PlanesArgs pa{sl.dev_xp.p, sl.dev_x.p, n, d_x, n};
         HIP_TRY(launch::planes_to_rows(pa, (int)p.x_esz, ix->st_h2d));
@@ -2988,7 +2892,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     HIP_TRY(hipStreamWaitEvent(ix->st_run, sl.ev_h2d, 0));
     if (p.replay.on) {
         // stored neighbours: the decode leaves the tile as a search and its nodata expansion would; nothing of the search runs
-        rc = replay_tile(p, b, n, planes != nullptr, idx.i64(), p.replay.dist_kind != kReplayDistNone ? dist.f64() : nullptr,
+        rc = replay_tile(p, b, n, planes, idx.i64(), p.replay.dist_kind != kReplayDistNone ? dist.f64() : nullptr,
                          want_pred ? pred.f64() : nullptr);
         if (rc) return rc;
     } else if (p.nodata_dev) {
@@ -2997,18 +2901,13 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
                          want_pred ? pred.f64() : nullptr, p.o.row_offset - p.row_offset0, ix->st_run, p.prod.tally);
         if (rc) return rc;
     } else {
-        rc = run_device(ix, sl.dev_x.p, n, &p.o, dist.f64(), idx.i64(), ix->st_run);
+        rc = search_tile(ix, p.red, sl.dev_x.p, n, &p.o, dist.f64(), idx.i64(), want_pred ? pred.f64() : nullptr, p.prod.tally, ix->st_run);
         if (rc) return rc;
-        if (p.prod.tally && (rc = tally_tile(ix, dist.f64(), idx.i64(), n, k, ix->st_run))) return rc;
-        if (want_pred) {
-            rc = launch_predict(ix, p.red, dist.f64(), idx.i64(), nullptr, n, k, p.o.weight_mode, p.o.weight_law, pred.f64(), ix->st_run);
-            if (rc) return rc;
-        }
     }
     // distance domain: the full-layout float64 distance tile (masked rows are NaN), whether or not the distances leave;
     // with the mask, the prediction rows of beyond pixels become NaN here, in front of the zonal tally and the conversion
     if (p.prod.domain) {
-        rc = domain_tile(ix, p.prod.domain_spec, dist.f64(), n, k, domain_out ? sl.dev_dom.p : nullptr,
+        rc = domain_tile(ix, p.prod.domain_spec, dist.f64(), n, k, u.domain_out ? sl.dev_dom.p : nullptr,
                          p.prod.domain_mask ? pred.f64() : nullptr, p.lane[kLanePred].cols, ix->st_run);
         if (rc) return rc;
     }
@@ -3025,7 +2924,7 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     // untyped row output leaves from where it was computed, with no kernel here.
     int planes_out = 0, wide_mask = 0, narrowed = 0, crosswalked = 0;
     for (int l = 0; l < kLanes; ++l) {
-        if (!out[l]) continue;
+        if (!u.out[l]) continue;
         const HostPipe::Lane& ln = p.lane[l];
         const auto& sb = sl.lane[l];
         if (ln.converts()) {
@@ -3056,76 +2955,51 @@ int pipe_submit(HostPipe& p, const void* q, long n, void* const out[kLanes], con
     HIP_TRY(hipEventRecord(sl.ev_done, ix->st_run));
     auto& pd = p.pending[b];
     pd.live = true;
+    pd.push = u;
+    pd.off = off;
     pd.n = n;
-    std::copy(out, out + kLanes, pd.out);
-    pd.planes = planes != nullptr;
-    pd.out_stride = out_stride;
-    pd.domain_out = p.prod.domain ? domain_out : nullptr;
-    pd.replay_push_no = p.replay_push_no;
     if (p.replay.on) ix->last_replay[5] = ix->search_calls - searches0;  // (searches this tile's submission ran: none)
     p.d2h_slot = b;  // its device-to-host copies are enqueued behind the next tile's rows, or by the flush
     p.o.row_offset += nv;
     p.ms_enqueue += now_ms() - t_enq;
-    if (pipe_workers() && q_next && n_next > 0) {
+    if (pipe_workers() && n_next > 0) {
         // the copy-in leg of the next tile (w_in): its slot is drained and sized here, on this thread
         const int b2 = p.slot_of;
-        if ((rc = pipe_prepare_slot(p, b2, n_next, planes != nullptr))) return rc;
+        const long off2 = off + n;
+        if ((rc = pipe_prepare_slot(p, b2, u, n_next))) return rc;
         double* dst = ix->slot[b2].pin_x;
-        const size_t bytes = (size_t)n_next * d_x * p.x_esz, esz = p.x_esz;
-        int32_t* dst_z = p.prod.zonal ? ix->slot[b2].pin_z : nullptr;  // (the next tile's zone codes travel with its rows)
-        const int32_t* zones_next = p.prod.zonal ? zones + n : nullptr;
-        const ReplaySpec rspec = p.replay;
-        const ReplaySrc rsrc = p.replay_src;
-        p.ahead_done = ix->w_in->post([=]() -> int {
-            if (rspec.on) stage_replay(dst, rspec, rsrc, p_off + n, n_next);
-            else if (planes) stage_planes(dst, planes, d_x, esz, p_off + n, n_next);
-            else parallel_copy(dst, q_next, bytes);
-            if (dst_z) parallel_copy(dst_z, zones_next, (size_t)n_next * sizeof(int32_t));
+        int32_t* dst_z = ix->slot[b2].pin_z;  // (the next tile's zone codes travel with its rows)
+        p.ahead_done = ix->w_in->post([u, dst, dst_z, off2, n_next]() -> int {
+            u.stage(dst, off2, n_next);
+            if (u.zones) parallel_copy(dst_z, u.zones + off2, (size_t)n_next * sizeof(int32_t));
             return SKNNR_OK;
         });
-        p.ahead_q = q_next;
+        p.ahead_push_no = u.push_no;
+        p.ahead_off = off2;
         p.ahead_slot = b2;
     }
     return SKNNR_OK;
 }
 
-// Submit `nq` rows in tiles of at most host_chunk_rows().  A pipeline that starts empty ramps up: the device waits for
-// the first tile's staging copy and host-to-device transfer (7 ms for a 1M-row tile) with nothing to do, so the first
-// tiles are an eighth, a quarter and a half of the regular size.
-// planes (or null): a band-first push -- q_ is ignored, a tile [c0, c1) is that segment of every band, and its results go
-// to out[l] + j * out_stride + c0 (in elements of lane l) for output plane j.
-int pipe_submit_rows(HostPipe& p, const void* q_, long nq, void* const out[kLanes], const void* const* planes = nullptr,
-                     long out_stride = 0) {
-    const char* q = p.replay.on ? p.replay_src.idx : planes ? (const char*)planes[0] : (const char*)q_;
-    // (bytes between the tiles of q: a band-first tile is named by the first band's segment, a replayed one by its indices)
-    const size_t row_bytes = p.replay.on ? (size_t)(planes ? 1 : p.replay.ks) * p.replay.idx_bytes
-                                         : planes ? p.x_esz : (size_t)p.d_x * p.x_esz;
-    const long cap = host_chunk_rows();
+// What a push takes from its pipeline: the shape of its source, and its number among the pipeline's pushes.
+Push& pipe_adopt(HostPipe& p, Push& u) {
+    u.cols = p.d_x;
+    u.esz = p.x_esz;
+    u.layout = p.replay.layout();
+    u.push_no = ++p.push_no;
+    return u;
+}
+
+// Submit the nq pixels of push u in tiles of at most host_chunk_rows(), cut by tile_cuts (host_stage.h): a pipeline that
+// starts empty ramps up.
+int pipe_submit_rows(HostPipe& p, const Push& u, long nq) {
     bool idle = p.d2h_slot < 0;
     for (const auto& pd : p.pending) idle = idle && !pd.live;
-    std::vector<long> cuts;  // tile boundaries
-    long c = 0;
-    if (idle && nq > cap / 2 && !std::getenv("SKNNR_PIPE_NO_RAMP"))
-        for (long part : {cap / 8, cap / 4, cap / 2}) {
-            part = std::max<long>(part / kRowQuantum * kRowQuantum, kRowQuantum);
-            if (c + part >= nq) break;
-            c += part;
-            cuts.push_back(c);
-        }
-    while (c < nq) {
-        c = std::min(nq, c + cap);
-        cuts.push_back(c);
-    }
+    const std::vector<long> cuts = tile_cuts(nq, host_chunk_rows(), idle, !std::getenv("SKNNR_PIPE_NO_RAMP"), kRowQuantum);
     long c0 = 0;
     for (size_t i = 0; i < cuts.size(); ++i) {
-        const long c1 = cuts[i], n = c1 - c0;
-        const long n_next = i + 1 < cuts.size() ? cuts[i + 1] - c1 : 0;
-        void* tile_out[kLanes];
-        for (int l = 0; l < kLanes; ++l)
-            tile_out[l] = out[l] ? (char*)out[l] + lane_tile_offset(c0, p.lane[l].cols, p.lane[l].esz, planes != nullptr) : nullptr;
-        int rc = pipe_submit(p, q + c0 * row_bytes, n, tile_out, n_next ? q + c1 * row_bytes : nullptr, n_next, planes, c0,
-                             out_stride, p.prod.zonal ? p.zones_push + c0 : nullptr,
-                             p.prod.domain && p.domain_push ? p.domain_push + c0 : nullptr);
+        const long c1 = cuts[i];
+        int rc = pipe_submit(p, u, c0, c1 - c0, i + 1 < cuts.size() ? cuts[i + 1] - c1 : 0);
         if (rc) return rc;
         c0 = c1;
     }
@@ -3213,8 +3087,9 @@ int run_host_pipeline(sknnr_index* ix, const Reduction& red, const void* q, long
                       void* out_idx, void* out_pred, const double* nodata = nullptr, long fill_index = -1,
                       int64_t* out_n_valid = nullptr) {
     if (ix->stream_open) return fail(SKNNR_ERR_INVALID, "a query stream is open on this handle: end it first");
-    void* const out[kLanes] = {out_idx, out_dist, out_pred};  // (lane order)
     HostPipe p;
+    Push u(Push::kRows, false, out_idx, out_dist, out_pred, 0);  // (the call is one push of rows)
+    u.rows = q;
     int rc = pipe_open(p, ix, o, red, out_dist != nullptr, out_pred != nullptr);
     if (!rc && nodata) {
         HIP_TRY(hipDeviceSynchronize());  // (m_nodata belongs to the workspace)
@@ -3225,9 +3100,9 @@ int run_host_pipeline(sknnr_index* ix, const Reduction& red, const void* q, long
     }
     Prefault pf;  // (joined when the call returns)
     if (!rc && std::getenv("SKNNR_PREFAULT")) {  // (measured: 96 ms without, 115 ms with -- the populate threads take bandwidth the copies need)
-        for (int l = 0; l < kLanes; ++l) pf.add(out[l], lane_bytes(nq, p.lane[l].cols, p.lane[l].esz));
+        for (int l = 0; l < kLanes; ++l) pf.add(u.out[l], lane_bytes(nq, p.lane[l].cols, p.lane[l].esz));
     }
-    if (!rc) rc = pipe_submit_rows(p, q, nq, out);
+    if (!rc) rc = pipe_submit_rows(p, pipe_adopt(p, u), nq);
     if (!rc) rc = pipe_flush(p);
     if (rc) pipe_fail(p, rc);
     if (out_n_valid) *out_n_valid = p.o.row_offset - p.row_offset0;
@@ -3247,13 +3122,10 @@ int run_self_rows(sknnr_index* ix, const Reduction& red, long nq, const sknnr_qu
         if (out_pred) HIP_TRY(ix->pred_stage.ensure((size_t)n * pc));
         sknnr_query_opts oc = *o;
         oc.row_offset = o->row_offset + c0;
-        int rc = run_device(ix, nullptr, n, &oc, ix->dist_stage.p, ix->idx_stage.p, st);
+        int rc = search_tile(ix, red, nullptr, n, &oc, ix->dist_stage.p, ix->idx_stage.p, out_pred ? ix->pred_stage.p : nullptr, false, st);
         if (rc) return rc;
-        if (out_pred) {
-            rc = launch_predict(ix, red, ix->dist_stage.p, ix->idx_stage.p, nullptr, n, k, o->weight_mode, o->weight_law, ix->pred_stage.p, st);
-            if (rc) return rc;
+        if (out_pred)
             HIP_TRY(hipMemcpyAsync(out_pred + c0 * pc, ix->pred_stage.p, (size_t)n * pc * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
         if (out_dist)
             HIP_TRY(hipMemcpyAsync(out_dist + c0 * k, ix->dist_stage.p, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, st));
         if (out_idx)
@@ -4258,9 +4130,7 @@ static int search_and_reduce(sknnr_index* ix, const void* q, int64_t nq, const s
             HIP_TRY(ix->idx_stage.ensure((size_t)nq * k));
             di = ix->idx_stage.p;
         }
-        rc = run_device(ix, q, nq, o, dd, di, st);
-        if (rc) return rc;
-        return launch_predict(ix, red, dd, di, nullptr, nq, k, o->weight_mode, o->weight_law, out_pred, st);
+        return search_tile(ix, red, q, nq, o, dd, di, out_pred, false, st);
     }
     if (q) return run_host_pipeline(ix, red, q, nq, o, out_dist, out_idx, out_pred);
     return run_self_rows(ix, red, nq, o, out_dist, (long*)out_idx, out_pred);
@@ -4983,24 +4853,23 @@ static bool stream_typed(const sknnr_stream* s) {
 static const char* const kTypedStreamMsg =
     "the stream has typed outputs (sknnr_stream_set_output): use sknnr_stream_push_typed / sknnr_stream_push_planes_typed";
 
-// The body of every push: nq rows at q, or (planes non-null) nq pixels of every band; outs[l] is where lane l's results go
-// (null: not asked for), in elements of the stream's type for that lane, band-first with out_stride elements between planes.
-// The entry points check what is theirs alone and leave s and nq to this function.
-// rsrc (the replay entries; else null): the stored neighbours of the push, which a replay stream takes in place of rows.
-static int stream_push(sknnr_stream* s, const void* q, const void* const* planes, int64_t nq, void* const outs[kLanes],
-                       int64_t out_stride, const ReplaySrc* rsrc = nullptr) {
+// The body of every push of nq pixels.  The entry points name the source, the layout and the caller's output arrays (in
+// elements of the stream's type for each lane) and check what is theirs alone; s, nq, the zone codes and the code plane
+// named for this push, and the push's number are this function's.
+static int stream_push(sknnr_stream* s, Push u, int64_t nq) {
     if (!s) return fail(SKNNR_ERR_INVALID, "stream is NULL");
     if (nq < 0) return fail(SKNNR_ERR_INVALID, "nq must be >= 0");
     HostPipe& p = s->pipe;
-    if (p.replay.on != (rsrc != nullptr))
-        return fail(SKNNR_ERR_INVALID, rsrc ? "sknnr_replay_push: the stream was opened by sknnr_stream_begin and takes feature rows"
-                                            : "a replay stream takes stored neighbours: use sknnr_replay_push / sknnr_replay_push_planes");
-    if (rsrc) ++p.replay_push_no;  // (every push counts, an empty one too: the caller's tile numbers)
+    const bool stored = u.source == Push::kStored;
+    if (p.replay.on != stored)
+        return fail(SKNNR_ERR_INVALID, stored ? "sknnr_replay_push: the stream was opened by sknnr_stream_begin and takes feature rows"
+                                              : "a replay stream takes stored neighbours: use sknnr_replay_push / sknnr_replay_push_planes");
+    pipe_adopt(p, u);
     if (nq == 0) return SKNNR_OK;
     // (a replayed push may ask for nothing: its tile still feeds the tally, the zonal tables and the domain)
-    if (!rsrc && !outs[kLaneIdx] && !outs[kLanePred]) return fail(SKNNR_ERR_INVALID, "a push needs out_idx or out_pred");
-    if (outs[kLaneDist] && !p.lane[kLaneDist].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without distances");
-    if (outs[kLanePred] && !p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
+    if (!stored && !u.out[kLaneIdx] && !u.out[kLanePred]) return fail(SKNNR_ERR_INVALID, "a push needs out_idx or out_pred");
+    if (u.out[kLaneDist] && !p.lane[kLaneDist].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without distances");
+    if (u.out[kLanePred] && !p.lane[kLanePred].want) return fail(SKNNR_ERR_INVALID, "the stream was opened without predictions");
     std::lock_guard<std::mutex> lock(p.ix->mtx);
     if (p.prod.zonal) {
         if (!s->next.have_zones) return fail(SKNNR_ERR_INVALID, "a push on a zonal stream needs sknnr_stream_next_zones first");
@@ -5010,7 +4879,7 @@ static int stream_push(sknnr_stream* s, const void* q, const void* const* planes
         if (dt < SKNNR_DTYPE_I16 || dt > SKNNR_DTYPE_I32)
             return fail(SKNNR_ERR_INVALID, "a zonal stream needs an integer pred_dtype (sknnr_stream_set_output): zonal sums are over stored integers");
         s->next.have_zones = false;  // (consumed, whatever becomes of the push)
-        p.zones_push = s->next.zones.data();
+        u.zones = s->next.zones.data();
     }
     if (p.prod.domain) {
         uint8_t* const dst = s->next.domain_out;
@@ -5018,12 +4887,11 @@ static int stream_push(sknnr_stream* s, const void* q, const void* const* planes
         s->next.domain_out = nullptr;  // (consumed, whatever becomes of the push)
         if (dst && dst_n != nq)
             return fail(SKNNR_ERR_INVALID, "sknnr_stream_next_domain_out named %lld codes, the push has %lld rows", (long long)dst_n, (long long)nq);
-        p.domain_push = dst;
+        u.domain_out = dst;
     }
     HIP_TRY(hipSetDevice(p.ix->device));
     s->pushed = true;
-    if (rsrc) p.replay_src = *rsrc;
-    const int rc = pipe_submit_rows(p, q, nq, outs, planes, out_stride);
+    const int rc = pipe_submit_rows(p, u, nq);
     if (rc) return pipe_fail(p, rc);
     s->rows_pushed += nq;
     return SKNNR_OK;
@@ -5032,8 +4900,9 @@ static int stream_push(sknnr_stream* s, const void* q, const void* const* planes
 extern "C" int sknnr_stream_push_typed(sknnr_stream* s, const void* q, int64_t nq, void* out_dist, void* out_idx,
                                        void* out_pred) {
     if (s && nq > 0 && !q) return fail(SKNNR_ERR_INVALID, "q is NULL");
-    void* const outs[kLanes] = {out_idx, out_dist, out_pred};  // (lane order)
-    return stream_push(s, q, nullptr, nq, outs, 0);
+    Push u(Push::kRows, false, out_idx, out_dist, out_pred, 0);
+    u.rows = q;
+    return stream_push(s, u, nq);
 }
 
 extern "C" int sknnr_stream_push(sknnr_stream* s, const void* q, int64_t nq, double* out_dist, int64_t* out_idx,
@@ -5052,8 +4921,9 @@ extern "C" int sknnr_stream_push_planes_typed(sknnr_stream* s, const void* const
         if (out_stride < nq) return fail(SKNNR_ERR_INVALID, "out_stride (%lld) is below nq (%lld)", (long long)out_stride, (long long)nq);
         if (d_x > kMaskMaxCols) return fail(SKNNR_ERR_UNSUPPORTED, "more than %d input columns in a band-first push", kMaskMaxCols);
     }
-    void* const outs[kLanes] = {out_idx, out_dist, out_pred};  // (lane order)
-    return stream_push(s, nullptr, planes, nq, outs, out_stride);
+    Push u(Push::kBands, true, out_idx, out_dist, out_pred, (long)out_stride);
+    u.bands = planes;
+    return stream_push(s, u, nq);
 }
 
 extern "C" int sknnr_stream_push_planes(sknnr_stream* s, const void* const* planes, int64_t nq, double* out_dist,
@@ -5210,9 +5080,9 @@ extern "C" int sknnr_replay_push(sknnr_stream* s, const void* idx, const void* d
         if (!dist != (s->pipe.replay.dist_kind == kReplayDistNone))
             return fail(SKNNR_ERR_INVALID, "sknnr_replay_push: dist is given exactly when the stream was opened with stored distances");
     }
-    const ReplaySrc src{(const char*)idx, (const char*)dist, false, 0};
-    void* const outs[kLanes] = {out_idx, out_dist, out_pred};  // (lane order)
-    return stream_push(s, idx, nullptr, nq, outs, 0, &src);
+    Push u(Push::kStored, false, out_idx, out_dist, out_pred, 0);
+    u.stored = {(const char*)idx, (const char*)dist, 0};
+    return stream_push(s, u, nq);
 }
 
 extern "C" int sknnr_replay_push_planes(sknnr_stream* s, const void* idx, const void* dist, int64_t nq, int64_t in_stride,
@@ -5224,10 +5094,9 @@ extern "C" int sknnr_replay_push_planes(sknnr_stream* s, const void* idx, const 
         if (in_stride < nq) return fail(SKNNR_ERR_INVALID, "sknnr_replay_push_planes: in_stride (%lld) is below nq (%lld)", (long long)in_stride, (long long)nq);
         if (out_stride < nq) return fail(SKNNR_ERR_INVALID, "sknnr_replay_push_planes: out_stride (%lld) is below nq (%lld)", (long long)out_stride, (long long)nq);
     }
-    const ReplaySrc src{(const char*)idx, (const char*)dist, true, (long)in_stride};
-    static const void* const kBandTag[1] = {nullptr};  // (non-null: the results leave as planes; a replayed tile has no row planes)
-    void* const outs[kLanes] = {out_idx, out_dist, out_pred};  // (lane order)
-    return stream_push(s, idx, kBandTag, nq, outs, out_stride, &src);
+    Push u(Push::kStored, true, out_idx, out_dist, out_pred, (long)out_stride);
+    u.stored = {(const char*)idx, (const char*)dist, (long)in_stride};
+    return stream_push(s, u, nq);
 }
 
 extern "C" int sknnr_replay_get_counts(sknnr_stream* s, int64_t out[4]) {
